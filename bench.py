@@ -3,7 +3,11 @@
 all-reduce], clamp +-5, Adam) of mn-att-ques-im-hist + disc on synthetic VisDial-v1.0-shaped batches
 (BASELINE.json configs[3]: batch 20 dialogs x 10 rounds x 100 options, 14x14x512 pool5 map) per GPU.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (the `roofline` block comes from HIP events of the last
+timed step).  --full adds everything that takes runs of its own: `roofline.alone`, the `alt` leg, `other_configs` and `cpu_baseline`
+(each still skippable with its --no-* flag).  --dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy.
 
 N > 1: when RANK is not in the environment the script re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (one rank per GPU over
@@ -19,6 +23,7 @@ on the host cores), never for the measured path.
 import argparse
 import json
 import os
+import re
 import sys
 import time
 
@@ -408,6 +413,31 @@ def cpu_baseline(seconds_budget=30.0, batch=20):
                          dt, threads, os.cpu_count() or 0, ("%.0f CPUs" % quota) if quota else "none")}
 
 
+DUMP_SAMPLE = 1 << 17       # elements kept of an array larger than this: ~13 MB for the 25 parameter + 25 gradient tensors of configs[3]
+# Not dumped: the bias of an attention score layer (att.b, att2.b, ...) adds one constant to every region's score in front of the softmax,
+# so its exact gradient is 0 and what a step computes for it is rounding noise, summed with float atomics in an order that changes from run
+# to run; Adam turns that noise into steps of up to the learning rate.  Neither tensor is reproducible, and neither changes any other output.
+DUMP_SKIP = re.compile(r'att\d*\.b')
+
+
+def dump_outputs(model, loss, dirname):
+    """what the timed path handed its caller after the LAST timed step, as DIR/<name>.npy: the step's loss (loss.npy, float64), the
+    parameters after its update (param.<tensor>.npy) and the gradients it computed (grad.<tensor>.npy), float32, except the DUMP_SKIP
+    tensors.  A tensor above DUMP_SAMPLE elements is cut to a fixed sample of flat positions (seeded, the same for every build and every
+    run), in position order."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, 'loss.npy'), np.array([float(loss)], np.float64))
+    for kind, tensors in (('param', model.get_parameters_dict()), ('grad', model.get_gradients_dict())):
+        for name in sorted(tensors):
+            if DUMP_SKIP.fullmatch(name):
+                continue
+            a = np.asarray(tensors[name], np.float32)
+            if a.size > DUMP_SAMPLE:
+                a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+            np.save(os.path.join(dirname, '%s.%s.npy' % (kind, name)), a)
+
+
 def comm_self_check(model, collective, lib_comm, local):
     """what this rank's gradient exchange looked like in the warm-up steps"""
     import torch
@@ -441,8 +471,12 @@ def main():
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--batch', type=int, default=20, help='dialogs per GPU (headline: 20)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-other-configs', action='store_true', help='skip the configs[0], [1], [2], [4] legs after the headline')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also run what takes runs of its own: roofline.alone, `alt`, other_configs, cpu_baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's loss, updated parameters and gradients (rank 0) as DIR/<name>.npy")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline')
+    ap.add_argument('--no-other-configs', action='store_true', help='(--full) skip the configs[0], [1], [2], [4] legs after the headline')
     ap.add_argument('--same-batch', action='store_true', help='reuse one resident batch (round-1 behaviour; A/B only)')
     ap.add_argument('--no-streams', action='store_true', help='whole step on one HIP stream (A/B only)')
     ap.add_argument('--config', type=int, choices=[3, 4], default=3,
@@ -452,7 +486,7 @@ def main():
                          'of three bf16 values, all 9 bf16 MFMA products, fp32 accumulate -- fp32-grade results (errors at the fp32 MFMA\'s own level, 0.5-1.4x per tensor: '
                          'tests/test_ops_gpu.py::test_split_error_table, tests/test_full_size_golden.py); fp32 = v_mfma_f32_32x32x2_f32 (reported '
                          'beside the headline as `alt`); split6 = 6 products (data only, never a headline)')
-    ap.add_argument('--no-alt', action='store_true', help='skip the `alt` leg (the same steps with the fp32-MFMA recurrence) after the headline')
+    ap.add_argument('--no-alt', action='store_true', help='(--full) skip the `alt` leg (the same steps with the fp32-MFMA recurrence) after the headline')
     ap.add_argument('--collective', choices=['library', 'torch'], default='library',
                     help='native host, N > 1: library = RCCL behind the C ABI (default); torch = host-side torch.distributed')
     ap.add_argument('--host', choices=['python', 'native'], default=os.environ.get('VD_BENCH_HOST', 'native'),
@@ -575,6 +609,8 @@ def main():
         elapsed = float(t.item())
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(model, loss, args.dump_outputs)
         ms_per_step = elapsed / args.steps * 1e3
         value = world * N * args.steps / elapsed
         # dominant kernel family = the option-LSTM recurrence (fused recurrent GEMM + cell update): To-1 kernel launches
@@ -599,7 +635,7 @@ def main():
             roof = split_roofline(fams, dom, args.recurrence, traffic_of(args.recurrence + ':' + dom))
         elif dom:
             roof = fp32_roofline(fams, dom, value, traffic, traffic_build)
-        if roof and roof.get("bound") == "mfma" and world == 1 and args.config == 3:
+        if args.full and roof and roof.get("bound") == "mfma" and world == 1 and args.config == 3:
             try:
                 roof["alone"] = dominant_kernel_alone(p, N, recurrence=args.recurrence)   # same kernel, same shapes, nothing else on the chip
             except Exception as exc:                            # never let the extra figure break the bench line
@@ -634,12 +670,12 @@ def main():
         }
         if world == 1 and args.config == 3 and args.host == 'native':
             model.close()
-        if world == 1 and args.config == 3 and args.recurrence != 'fp32' and args.host == 'native' and not args.no_alt:
+        if args.full and world == 1 and args.config == 3 and args.recurrence != 'fp32' and args.host == 'native' and not args.no_alt:
             try:
                 out["alt"] = alt_leg(args, N)
             except Exception as exc:
                 out["alt"] = {"recurrence": "fp32", "error": str(exc)[:200]}
-        if world == 1 and args.config == 3 and args.host == 'native' and not args.no_other_configs:
+        if args.full and world == 1 and args.config == 3 and args.host == 'native' and not args.no_other_configs:
             # the other single-GPU configurations of BASELINE.json, driver-visible (the headline `value` above is unaffected:
             # they run after its timed region, on their own models)
             out["other_configs"] = []
@@ -648,7 +684,7 @@ def main():
                     out["other_configs"].append(other_config(cfg))
                 except Exception as exc:
                     out["other_configs"].append({"workload": "BASELINE.json configs[%d]" % cfg, "error": str(exc)[:200]})
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         else:
             out["cpu_baseline"] = None

@@ -27,13 +27,13 @@ d, d50 = last_json(G + TAG + '_bench_default.json'), last_json(G + TAG + '_bench
 r, alt = d['roofline'], d.get('alt') or {}
 fam = r['families'][r['kernel']]
 hdr = [
-    "# rocprofv3 --kernel-trace --marker-trace -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --no-alt   (MI355X, round %s state,"
+    "# rocprofv3 --kernel-trace --marker-trace -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --no-alt   (MI355X, round %s state,"
     % TAG[1:].lstrip('0'),
     "# scripts/measure_round.sh: native host = model-level C ABI, GPU_MAX_HW_QUEUES=1, 7 training steps traced; summarised from the rocpd database by",
     "# `scripts/rocpd_stats.py <db> --steps-only`, i.e. up to the last optimiser launch -- bench.py's `roofline.alone` leg is excluded).  The option recurrence runs",
     "# the exact-split kernels (csrc/split_core.h: gemm_split_kernel<9, Epi> = the step kernels, gemm_split_tn_kernel<9> = dWh), everything else v_mfma_f32_32x32x2_f32",
     "# (gemm_f32<WMxWKxNTxKWxDBxMINWxLDSMINxBF16|A, B, Epi>, gemm_f32_glds = LDS-DMA pipeline kernels, gemm_f32_grouped = encoder ticks).",
-    "# Same box, un-profiled: `python bench.py` = %.3f ms/step (%.0f QA-rounds/s), 50 steps: %.3f ms/step; alt (fp32-MFMA recurrence, same run): %s ms/step."
+    "# Same box, un-profiled: `python bench.py --full` = %.3f ms/step (%.0f QA-rounds/s), 50 steps: %.3f ms/step; alt (fp32-MFMA recurrence, same run): %s ms/step."
     % (d['ms_per_step'], d['value'], d50['ms_per_step'], alt.get('ms_per_step')),
     "# Dominant kernel = %s timestep (split9): HIP events %.1f us per launch in the step -> %.0f TFLOP/s of executed bf16 MFMA work = %.3f of the 2.5 PFLOP/s"
     % (r['kernel'], fam['avg_launch_ms'] * 1e3, r['achieved'], r['frac']),

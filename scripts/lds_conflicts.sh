@@ -1,6 +1,6 @@
 ROOT=$PWD; OUT=$PWD/gpurun_out; cd /tmp; export TMPDIR=/tmp
 for WHAT in "bench" "cfg1"; do
-  if [ $WHAT = bench ]; then CMD="python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --no-alt"; else CMD="python $ROOT/scripts/run_config.py 1 3 1"; fi
+  if [ $WHAT = bench ]; then CMD="python $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --no-alt"; else CMD="python $ROOT/scripts/run_config.py 1 3 1"; fi
   rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES -d $OUT/ldsc -o p -- $CMD > /dev/null 2>&1
   DBP=$(ls $OUT/ldsc/*.db | head -1)
   python - "$DBP" > $OUT/r05_lds_conflicts_$WHAT.txt <<'PY'

@@ -71,6 +71,21 @@ def grad_mismatches(g, ref, tol=1e-4, zero=()):
     return bad
 
 
+def tie_repeated_options(scores, batch):
+    """oracle scores [N, O] of `batch` with every repeat of a candidate (the same tokens among one question's options: `options` for disc,
+    `option_in` + `option_out` for gen) given the score of its first occurrence.  Identical candidates have identical exact scores and the
+    reference breaks such ties by lower index (utils.lua:106-128); a threaded BLAS may round two identical rows of one product an ulp
+    apart, depending on where its blocking puts them."""
+    import numpy as np
+    s = np.array(scores, dtype=np.float64)
+    cand = [batch['options']] if 'options' in batch else [batch['option_in'], batch['option_out']]
+    opts = np.concatenate([np.asarray(c).reshape(s.shape[0], s.shape[1], -1) for c in cand], -1)
+    for r in range(s.shape[0]):
+        _, first, inv = np.unique(opts[r], axis=0, return_index=True, return_inverse=True)
+        s[r] = s[r, first[inv.reshape(-1)]]
+    return s
+
+
 def unexplained_rank_flips(dev_scores, ref_scores, tol=1e-4):
     """(flipped pairs, unexplained ones): option pairs whose ORDER differs between the device scores and the fp64 oracle's
     scores; a flip is explained only if the fp64 scores are a near tie, |s_a - s_b| < tol * max(1, |s_a|, |s_b|).  Ties

@@ -109,3 +109,34 @@ def test_bench_configs_name_the_baseline_workloads(bench):
     assert bench.config_params(3)['encoder'] == 'mn-att-ques-im-hist' and bench.config_params(3)['decoder'] == 'disc'
     assert bench.config_params(1)['decoder'] == 'gen' and bench.config_params(4)['lstmPrecision'] == 'bf16'
     assert bench.config_params(2)['lstmPrecision'] == 'split9' and bench.config_params(3)['lstmPrecision'] == 'split9'   # the library default; bench.py sets it again from --recurrence
+
+
+def test_dump_outputs_is_a_fixed_bounded_sample(bench, tmp_path):
+    """--dump-outputs: loss (float64), every parameter and gradient tensor (float32); a tensor above DUMP_SAMPLE elements is cut to the SAME
+    seeded positions in every run, so two builds can be compared file for file; the attention score bias (exact gradient 0: rounding noise)
+    is left out; the headline model's dump stays far under 64 MB"""
+    import numpy as np
+    from oracle import visdial_oracle as vo
+
+    class Fake(object):
+        def get_parameters_dict(self):
+            return {'embed': np.arange(3 * bench.DUMP_SAMPLE, dtype=np.float32).reshape(-1, 3), 'opt.b': np.ones(8, np.float32),
+                    'att.b': np.ones(1, np.float32), 'att2.b': np.ones(1, np.float32), 'att.W': np.ones((1, 4), np.float32)}
+
+        def get_gradients_dict(self):
+            return {k: -v for k, v in self.get_parameters_dict().items()}
+    for d in ('a', 'b'):
+        bench.dump_outputs(Fake(), 1.25, str(tmp_path / d))
+    names = sorted(os.listdir(str(tmp_path / 'a')))
+    assert names == ['grad.att.W.npy', 'grad.embed.npy', 'grad.opt.b.npy', 'loss.npy', 'param.att.W.npy', 'param.embed.npy', 'param.opt.b.npy']
+    for n in names:
+        a, b = np.load(str(tmp_path / 'a' / n)), np.load(str(tmp_path / 'b' / n))
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and (a == b).all(), n
+    assert np.load(str(tmp_path / 'a' / 'loss.npy')).tolist() == [1.25]
+    assert np.load(str(tmp_path / 'a' / 'param.opt.b.npy')).shape == (8,)
+    e = np.load(str(tmp_path / 'a' / 'param.embed.npy'))
+    assert e.shape == (bench.DUMP_SAMPLE,) and (np.diff(e) > 0).all() and e[-1] < 3 * bench.DUMP_SAMPLE     # distinct positions, in order
+    assert (np.load(str(tmp_path / 'a' / 'grad.embed.npy')) == -e).all()
+    p = bench.config_params(3)
+    sizes = [int(np.prod(s[1])) for s in vo.param_spec(p['encoder'], p['decoder'], p)]
+    assert 2 * 4 * sum(min(n, bench.DUMP_SAMPLE) for n in sizes) < 64e6

@@ -94,6 +94,10 @@ def test_bench_line_under_torchrun(world):
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
+    if world > 1:
+        # the hardware-queue line below is bench.py's own policy: an inherited explicit setting would win over it
+        for k in ('GPU_MAX_HW_QUEUES', 'VD_BENCH_HW_QUEUES'):
+            env.pop(k, None)
     if world > 1 and torch.cuda.device_count() < world:
         env['VD_BENCH_SHARE_GPU'] = '1'
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(world), '--master-addr', '127.0.0.1',

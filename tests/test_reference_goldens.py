@@ -25,7 +25,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, grad_mismatches, unexplained_rank_flips
+from conftest import ROOT, grad_mismatches, tie_repeated_options, unexplained_rank_flips
 from oracle import visdial_oracle as vo
 from visdial_amd.opts import derive
 
@@ -306,7 +306,7 @@ def test_split_loops_on_an_oracle_host_reproduce_the_executed_reference(path):
             return vo.forward_backward(enc, dec, P64, p, batch, None, only_forward=True)['loss']
 
         def retrieveBatch(self, batch):
-            sc = vo.retrieve(enc, dec, P64, p, batch)
+            sc = tie_repeated_options(vo.retrieve(enc, dec, P64, p, batch), batch)
             return vo.compute_ranks(sc, batch['answer_ind'].reshape(-1) - 1) if self.params['useGt'] else vo.compute_ranks(sc)
     _check_split(OracleHost(), z, exact=True)
 

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from conftest import ROOT, tie_repeated_options
 from oracle import visdial_oracle as vo
 from visdial_amd import t7
 from visdial_amd.dataloader import Dataloader
@@ -91,7 +91,7 @@ def test_oracle_replays_the_executed_train_lua(path):
     val, start, gt_r, all_r = batch.loader, 1, [], []
     while start <= 5:
         b, start = val.getTestBatch(start, dict(opt, batchSize=2), 'val')
-        sc = vo.retrieve(enc, dec, P, opt, b)
+        sc = tie_repeated_options(vo.retrieve(enc, dec, P, opt, b), b)
         gt_r.append(vo.compute_ranks(sc, np.asarray(b['answer_ind']).reshape(-1) - 1).reshape(-1, 10))
         all_r.append(vo.compute_ranks(sc).reshape(-1, 10, sc.shape[1]))
     np.testing.assert_array_equal(np.concatenate(gt_r), z['eval.gt_ranks'])
