@@ -34,7 +34,8 @@ extern "C" {
 const char* vd_last_error(void);
 /* Bumped whenever an exported symbol is removed or the meaning of an argument changes; hosts compare it with the VD_ABI_VERSION they
  * were written against right after loading (visdial_amd/_lib.py, lua/visdial_ffi.lua).  2 = round 4's surface: vd_tune_set /
- * vd_tune_clear / vd_lstm_seq_status removed, vd_model_params.lstmBf16 also takes 3 / 6 / 9 (exact-operand split). */
+ * vd_tune_clear / vd_lstm_seq_status removed, vd_model_params.lstmBf16 also takes 3 / 6 / 9 (exact-operand split).  Adding entry points
+ * does not bump it: 94 entry points (56 operator-level, 31 model-level, 7 vd_comm_*), vd_beam_* and vd_model_beam_search added under 2. */
 #define VD_ABI_VERSION 2
 int vd_abi_version(void);
 int vd_device_count(int* count);
@@ -234,6 +235,30 @@ int vd_log_softmax_rows(float* x, int64_t ld, int64_t rows, int V, void* stream)
 /* utils.computeRanks (utils.lua:106-128): 1-based descending-sort position of every option */
 int vd_ranks(const float* scores, int32_t* ranks, int N, int O, void* stream);
 
+/* ---- batched beam search (Model:generateAnswers, model.lua:466-573; csrc/beam.hip states the rules).  One group = one QA
+ *      round with k = beamSize slots (k <= 32), hypothesis row r = group * k + slot; scores are fp64 [groups x k]; the token
+ *      history is int32 [groups x k x beam_len], double-buffered (hist_in != hist_out).
+ *   topk         nn.LogSoftMax of logits [rows x ld] (V valid columns; bit-identical to vd_log_softmax_rows) fused with the
+ *                top-k of every row, value descending then index ascending (model.lua:524-531); a row whose token tok[r] is 0
+ *                is the all-zero row of MaskZero(LogSoftMax) (decoders/gen.lua:24): indices 0..k-1 at 0.  logits are not written.
+ *   init         beams[1] = <START>, scores = 0, no finished candidate (model.lua:466-477); tok = <START> for every row
+ *   advance      one step s in [1, beam_len): candidates of slot 0 (s = 1) or all slots, <END> ones tracked as the group's best
+ *                finished (best_len = 0: none yet), the rest sorted stably and the first min(#, k) kept (model.lua:532-573);
+ *                src[r] = source slot of slot r or -1 (keeps its column, score and pre-step state), next_tok = the history
+ *                token at s
+ *   select_rows  cur[r] = stepped[group(r) * k + src[r]] where src[r] >= 0 (the hidden-state copies of model.lua:556-566)
+ *   finish       per group the best finished column and score, else column 0 (the reference errors there) */
+int vd_beam_topk(const float* logits, int64_t ld, int64_t rows, int V, const int32_t* tok, int k, int32_t* top_idx, float* top_val,
+                 void* stream);
+int vd_beam_init(int groups, int k, int beam_len, int start_token, int32_t* hist, int32_t* tok, double* scores, double* best_score,
+                 int32_t* best_len, void* stream);
+int vd_beam_advance(const int32_t* top_idx, const float* top_val, int groups, int k, int step, int beam_len, int end_token,
+                    double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok, double* best_score,
+                    int32_t* best_len, int32_t* best_hist, void* stream);
+int vd_beam_select_rows(float* cur, const float* stepped, const int32_t* src, int64_t rows, int k, int H, void* stream);
+int vd_beam_finish(int groups, int k, int beam_len, const int32_t* hist, const double* scores, const double* best_score,
+                   const int32_t* best_len, const int32_t* best_hist, int32_t* out_tokens, double* out_scores, void* stream);
+
 /* ---- wrapperdW:clamp(-5,5) + adam (model.lua:96-99; model_utils/optim_updates.lua:62-91) ---- */
 int vd_clamp_adam(float* w, float* g, float* m, float* v, int64_t n, float gscale, float clip, float beta1,
                   float beta2, float eps, float step, void* stream);
@@ -338,6 +363,12 @@ int vd_model_encode(vd_model* m);
 int vd_model_decode_begin(vd_model* m, const int32_t* rounds, int n);
 int vd_model_decode_step(vd_model* m, const int32_t* tokens, float* host_logprobs);
 int vd_model_decode_select(vd_model* m, const int32_t* src, int n_keep);
+/* the whole beam search of Model:generateAnswers (model.lua:466-573) for EVERY round of the last vd_model_encode batch at once,
+ * on the device (the vd_beam_* kernels above): N = B*R groups of beam_size hypotheses, beam_len-1 steps enqueued without a host
+ * synchronisation, then one copy back.  host_tokens [N x beam_len] = each round's answer (best finished column, else column 0;
+ * zero-padded), host_scores [N] its fp64 score.  Same answers as the host loop over decode_begin / step / select. */
+int vd_model_beam_search(vd_model* m, int beam_size, int beam_len, int start_token, int end_token, int32_t* host_tokens,
+                         double* host_scores);
 int vd_model_scores(vd_model* m, float* host_scores, int64_t n);        /* [N x O] of the last forward / retrieve */
 int vd_model_ranks(vd_model* m, int use_gt, int32_t* host_ranks);       /* utils.computeRanks (utils.lua:106-128) */
 /* decoder disc: rows the option LSTM executed for the batch of the LAST STEP (before any step: of the uploaded batch) vs the N * O

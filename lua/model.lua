@@ -271,10 +271,16 @@ end
 -- one dialog at a time.  Candidate bookkeeping is host control flow as in the reference; the device side is four calls:
 -- vd_model_encode (encoder forward), vd_model_decode_begin (hiddenBeams), vd_model_decode_step (one decoder step for all
 -- live hypotheses -> log-probabilities on the host), vd_model_decode_select (beam back-pointers).
+-- params.beamBatch = B > 0: the beam search of dialogs [s, s+B) runs on the device for every round of the chunk at once
+-- (vd_model_beam_search after one vd_model_encode per chunk); the records are the same.
 function Model:generateAnswers(dataloader, dtype, params)
     if self.params.decoder == 'disc' then error('Sampling/beam search only for generative model') end
     params = params or {}
     local sampleWords = params.sampleWords == 1
+    local beamBatch = params.beamBatch or 0
+    if beamBatch > 0 and sampleWords then
+        error('beamBatch > 0 is batched beam search; sampling (sampleWords = 1) runs on the host: use beamBatch = 0')
+    end
     local temperature = params.temperature or 1.0
     local beamSize, beamLen = params.beamSize or 5, params.beamLen or 20
     local startToken, endToken = dataloader.word2ind['<START>'], dataloader.word2ind['<END>']
@@ -283,6 +289,34 @@ function Model:generateAnswers(dataloader, dtype, params)
     local answerTable = {}
     self:commitW()
     self:setMode(false)
+    if beamBatch > 0 then
+        local ids = dataloader['unique_img_' .. dtype]
+        local function words(ids_) return utils.idToWords(ids_, dataloader.ind2word) end
+        for first = 1, numThreads, beamBatch do
+            local last = math.min(first + beamBatch - 1, numThreads)
+            local inds = {}
+            for convId = first, last do inds[#inds + 1] = convId end
+            local batch = dataloader:getIndexData(torch.LongTensor(inds), self.params, dtype)
+            local B, R = batch['ques_fwd']:size(1), batch['ques_fwd']:size(2)
+            self:upload({ques_fwd = batch['ques_fwd'], hist = batch['hist'], img_feat = batch['img_feat']})
+            self.havePrefetched = false
+            vd.call('vd_model_encode', self.h)
+            local toks, scores = ffi.new('int32_t[?]', B * R * beamLen), ffi.new('double[?]', B * R)
+            vd.call('vd_model_beam_search', self.h, beamSize, beamLen, startToken, endToken, toks, scores)
+            for b = 1, B do
+                local threadAnswers = {}
+                for iter = 1, R do
+                    local ans, row = {}, ((b - 1) * R + iter - 1) * beamLen   -- row = dialog * R + round
+                    for t = 1, beamLen do ans[t] = toks[row + t - 1] end
+                    threadAnswers[#threadAnswers + 1] = {question = words(batch['ques_fwd'][{b, iter}]), answer = words(torch.LongTensor(ans))}
+                end
+                local convId = first + b - 1
+                answerTable[#answerTable + 1] = {image_id = ids and ids[convId] or convId, dialog = threadAnswers}
+            end
+        end
+        self:setMode(true)
+        return answerTable
+    end
     for convId = 1, numThreads do
         local batch = dataloader:getIndexData(torch.LongTensor{convId}, self.params, dtype)
         local R = batch['ques_fwd']:size(2)

@@ -97,6 +97,11 @@ PROTOTYPES = {
     "vd_img_common_wgrad": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p],
     "vd_score_ce": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _p],
     "vd_ranks": [_p, _p, _i, _i, _p],
+    "vd_beam_topk": [_p, _l, _l, _i, _p, _i, _p, _p, _p],
+    "vd_beam_init": [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p],
+    "vd_beam_advance": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "vd_beam_select_rows": [_p, _p, _p, _l, _i, _i, _p],
+    "vd_beam_finish": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],
     "vd_clamp_adam": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _p],
     # model-level entry points (csrc/runtime.hip)
     "vd_model_create": [C.POINTER(ModelParams), C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)],
@@ -129,6 +134,7 @@ PROTOTYPES = {
     "vd_model_decode_begin": [_p, _p, _i],
     "vd_model_decode_step": [_p, _p, _p],
     "vd_model_decode_select": [_p, _p, _i],
+    "vd_model_beam_search": [_p, _i, _i, _i, _i, _p, _p],
     "vd_model_update": [_p, _f],
     "vd_model_learning_rate": [_p, C.POINTER(C.c_double), _i],
     "vd_model_scores": [_p, _p, _l],

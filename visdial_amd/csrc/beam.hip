@@ -1,0 +1,279 @@
+// Batched beam search of Model:generateAnswers (reference model.lua:466-573) on the device: the candidate bookkeeping the
+// hosts keep in split_eval.py:113-145 / lua/model.lua:294-332 (and oracle/visdial_oracle.py:generate_beam restates in fp64),
+// for every QA round of a batch at once.  One *group* = one round, with k = beamSize slots; hypothesis row r = group * k + slot.
+//
+// The rules all three agree on, reproduced here exactly:
+//  1. slot state starts from the round's encoder state (Gen_begin, rt_decoders.h; model.lua:478-503); beams[0] = <START>,
+//     scores = 0 in fp64.
+//  2. step s = 1 .. beamLen-1:
+//     - explore slot 0 only at s == 1, all k slots after that;
+//     - the top-k of an explored row is taken value descending, index ascending (a stable argsort);
+//     - a row whose input token is 0 (a slot never filled) has an ALL-ZERO log-probability row (MaskZero(LogSoftMax),
+//       decoders/gen.lua:24): its top-k is indices 0..k-1 at value 0, and its LSTM state is zero (maskZero);
+//     - token = index + 1; candidate score = scores[w] + (double)logp, added in fp64;
+//     - insertion order is (w, rank).  <END> candidates go to the finished set; the rest are sorted stably by descending
+//       score and the first n_keep = min(#cands, k) are kept;
+//     - slot i < n_keep takes the candidate's column, score and the STEPPED state of its source slot; slots >= n_keep keep
+//       their old column, score and PRE-step state (so their next token is 0 and the zero-row rule applies).
+//  3. the answer is the finished candidate with the highest score, ties to the earliest inserted (step, then w, then rank);
+//     if nothing finished, column 0 (the reference errors there).
+//  4. all beamLen-1 steps run: zero rows can still add finished candidates.
+#include "common.h"
+
+#define VD_BEAM_KMAX 32
+
+namespace {
+
+// value descending, index ascending
+__device__ __forceinline__ bool beam_better(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
+
+// Fused nn.LogSoftMax + top-k of one hypothesis row per workgroup.  The log-sum-exp is computed exactly as
+// log_softmax_rows_kernel (loss.hip) computes it -- 256 strided threads, wave_max / wave_sum, the four wave partials summed in
+// the same order -- so every value is bit-identical to that kernel's output row[c] - lse.  Each thread keeps a sorted list of
+// its KM best (value, index) pairs in registers (compile-time indices only: no scratch), then k rounds of a workgroup
+// arg-max over the list heads pop the row's top-k in order.
+template <int KM>
+__global__ void __launch_bounds__(256)
+beam_topk_kernel(const float* __restrict__ x, long ld, int V, const int32_t* __restrict__ tok, int k,
+                 int32_t* __restrict__ top_idx, float* __restrict__ top_val) {
+  __shared__ float red[8];
+  __shared__ float wv[4];
+  __shared__ int wi[4];
+  const long r = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int32_t* oi = top_idx + r * k;
+  float* ov = top_val + r * k;
+  if (tok[r] == 0) {                     // MaskZero(LogSoftMax): an all-zero row, ties to the lower index
+    if (tid < k) { oi[tid] = tid; ov[tid] = 0.f; }
+    return;
+  }
+  const float* row = x + r * ld;
+  float mx = -INFINITY;
+  for (int c = tid; c < V; c += 256) mx = fmaxf(mx, row[c]);
+  mx = wave_max(mx);
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float sum = 0.f;
+  for (int c = tid; c < V; c += 256) sum += expf(row[c] - mx);
+  sum = wave_sum(sum);
+  if (lane == 0) red[4 + wave] = sum;
+  __syncthreads();
+  const float lse = mx + logf(red[4] + red[5] + red[6] + red[7]);
+
+  float lv[KM];
+  int li[KM];
+#pragma unroll
+  for (int j = 0; j < KM; ++j) { lv[j] = -INFINITY; li[j] = INT_MAX; }
+  for (int c = tid; c < V; c += 256) {   // ascending c: an equal value never overtakes an earlier index
+    const float v = row[c] - lse;
+    if (beam_better(v, c, lv[KM - 1], li[KM - 1])) {
+      lv[KM - 1] = v;
+      li[KM - 1] = c;
+#pragma unroll
+      for (int j = KM - 1; j > 0; --j) {
+        if (beam_better(lv[j], li[j], lv[j - 1], li[j - 1])) {
+          const float tv = lv[j]; lv[j] = lv[j - 1]; lv[j - 1] = tv;
+          const int ti = li[j]; li[j] = li[j - 1]; li[j - 1] = ti;
+        }
+      }
+    }
+  }
+  for (int q = 0; q < k; ++q) {
+    float bv = lv[0];
+    int bi = li[0];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float v2 = __shfl_xor(bv, o, 64);
+      const int i2 = __shfl_xor(bi, o, 64);
+      if (beam_better(v2, i2, bv, bi)) { bv = v2; bi = i2; }
+    }
+    if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
+    __syncthreads();
+    bv = wv[0]; bi = wi[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+      if (beam_better(wv[w], wi[w], bv, bi)) { bv = wv[w]; bi = wi[w]; }
+    if (tid == 0) { oi[q] = bi; ov[q] = bv; }
+    if (li[0] == bi) {                   // indices are unique across threads: exactly one owner pops its head
+#pragma unroll
+      for (int j = 0; j < KM - 1; ++j) { lv[j] = lv[j + 1]; li[j] = li[j + 1]; }
+      lv[KM - 1] = -INFINITY;
+      li[KM - 1] = INT_MAX;
+    }
+    __syncthreads();                     // wv / wi are rewritten by the next round
+  }
+}
+
+// rule 1 for every group: history column <START>, 0, ..., next token <START>, scores 0, no finished candidate
+__global__ void beam_init_kernel(int groups, int k, int L, int start, int32_t* __restrict__ hist, int32_t* __restrict__ tok,
+                                 double* __restrict__ scores, double* __restrict__ best_score, int32_t* __restrict__ best_len) {
+  const long n = (long)groups * k;
+  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n * L; e += (long)gridDim.x * blockDim.x) {
+    hist[e] = e % L == 0 ? start : 0;
+    if (e < n) { tok[e] = start; scores[e] = 0.0; }
+    if (e < groups) { best_score[e] = 0.0; best_len[e] = 0; }
+  }
+}
+
+// rule 2 for one group per workgroup.  Candidate c = w * k + rank (insertion order).  A candidate's place among its kind
+// (unfinished / finished) is the number of that kind with a higher score or an equal score inserted earlier: for the
+// unfinished ones that is the stable sort's position, for the finished ones place 0 is this step's best.  The best finished
+// candidate so far is kept per group (score, length, column); a later one replaces it only with a strictly higher score, so
+// ties stay with the earliest inserted (rule 3).
+__global__ void __launch_bounds__(256)
+beam_advance_kernel(const int32_t* __restrict__ top_idx, const float* __restrict__ top_val, int k, int step, int L, int end_tok,
+                    double* __restrict__ scores, const int32_t* __restrict__ hist_in, int32_t* __restrict__ hist_out,
+                    int32_t* __restrict__ src, int32_t* __restrict__ next_tok, double* __restrict__ best_score,
+                    int32_t* __restrict__ best_len, int32_t* __restrict__ best_hist) {
+  __shared__ double csc[VD_BEAM_KMAX * VD_BEAM_KMAX];
+  __shared__ int ctok[VD_BEAM_KMAX * VD_BEAM_KMAX];
+  __shared__ double slot_sc[VD_BEAM_KMAX];
+  __shared__ int slot_src[VD_BEAM_KMAX], slot_tok[VD_BEAM_KMAX];
+  __shared__ int n_cands, best_c;
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const long g0 = (long)g * k;
+  const int explore = step == 1 ? 1 : k, C = explore * k;
+  if (tid == 0) { n_cands = 0; best_c = -1; }
+  if (tid < VD_BEAM_KMAX) slot_src[tid] = 0;                      // a valid source row even if a NaN score left a place unfilled
+  for (int c = tid; c < C; c += blockDim.x) {
+    const int w = c / k, q = c - w * k;
+    const long e = (g0 + w) * k + q;
+    ctok[c] = top_idx[e] + 1;                                      // vocabulary ids are 1-based
+    csc[c] = scores[g0 + w] + (double)top_val[e];                  // fp64, as the hosts add
+  }
+  __syncthreads();
+  for (int c = tid; c < C; c += blockDim.x) {
+    const bool fin = ctok[c] == end_tok;
+    const double sc = csc[c];
+    int pos = 0;
+    for (int c2 = 0; c2 < C; ++c2) {
+      if ((ctok[c2] == end_tok) != fin) continue;
+      const double s2 = csc[c2];
+      pos += (s2 > sc || (s2 == sc && c2 < c)) ? 1 : 0;
+    }
+    if (fin) {
+      if (pos == 0) best_c = c;
+    } else {
+      atomicAdd(&n_cands, 1);
+      if (pos < k) { slot_sc[pos] = sc; slot_src[pos] = c / k; slot_tok[pos] = ctok[c]; }
+    }
+  }
+  __syncthreads();
+  const int n_keep = min(n_cands, k);
+  if (tid == 0 && best_c >= 0) {
+    const double sc = csc[best_c];
+    if (best_len[g] == 0 || sc > best_score[g]) {
+      const int32_t* col = hist_in + (g0 + best_c / k) * L;
+      best_score[g] = sc;
+      best_len[g] = step + 1;
+      for (int p = 0; p < L; ++p) best_hist[(long)g * L + p] = p < step ? col[p] : p == step ? end_tok : 0;
+    }
+  }
+  for (int e = tid; e < k * L; e += blockDim.x) {
+    const int i = e / L, p = e - i * L;
+    int v;
+    if (i < n_keep) v = p == step ? slot_tok[i] : hist_in[(g0 + slot_src[i]) * L + p];
+    else v = hist_in[(g0 + i) * L + p];
+    hist_out[(g0 + i) * L + p] = v;
+    if (p == step) next_tok[g0 + i] = v;
+  }
+  for (int i = tid; i < k; i += blockDim.x) {
+    src[g0 + i] = i < n_keep ? slot_src[i] : -1;
+    if (i < n_keep) scores[g0 + i] = slot_sc[i];                  // every read of `scores` happened before the first barrier
+  }
+}
+
+// cur[r] = stepped[group(r) * k + src[r]] where src[r] >= 0; the row is left alone otherwise
+__global__ void beam_select_rows_kernel(float* __restrict__ cur, const float* __restrict__ stepped, const int32_t* __restrict__ src,
+                                        long rows, int k, int H) {
+  const long n = rows * H;
+  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+    const long r = e / H;
+    const int s = src[r];
+    if (s >= 0) cur[e] = stepped[((r / k) * k + s) * H + (e - r * H)];
+  }
+}
+
+// rule 3: the best finished candidate, else column 0 and its score
+__global__ void beam_finish_kernel(int groups, int k, int L, const int32_t* __restrict__ hist, const double* __restrict__ scores,
+                                   const double* __restrict__ best_score, const int32_t* __restrict__ best_len,
+                                   const int32_t* __restrict__ best_hist, int32_t* __restrict__ out_tok, double* __restrict__ out_score) {
+  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < (long)groups * L; e += (long)gridDim.x * blockDim.x) {
+    const long g = e / L, p = e - g * L;
+    const bool fin = best_len[g] > 0;
+    out_tok[e] = fin ? best_hist[e] : hist[g * k * L + p];
+    if (p == 0) out_score[g] = fin ? best_score[g] : scores[g * k];
+  }
+}
+
+inline unsigned grid_for(long n) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, 4096)); }
+
+}  // namespace
+
+extern "C" {
+
+int vd_beam_topk(const float* logits, int64_t ld, int64_t rows, int V, const int32_t* tok, int k, int32_t* top_idx, float* top_val,
+                 void* stream) {
+  VD_CHECK_ARG(logits && tok && top_idx && top_val && rows >= 0 && V >= 1 && ld >= V, "vd_beam_topk: bad args");
+  VD_CHECK_ARG(k >= 1 && k <= VD_BEAM_KMAX && k <= V, "vd_beam_topk: k = %d must be in [1, %d] and <= V = %d", k, VD_BEAM_KMAX, V);
+  if (rows == 0) return VD_OK;
+  if (k <= 8)
+    hipLaunchKernelGGL(beam_topk_kernel<8>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, V, tok, k,
+                       top_idx, top_val);
+  else
+    hipLaunchKernelGGL(beam_topk_kernel<VD_BEAM_KMAX>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, V,
+                       tok, k, top_idx, top_val);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+int vd_beam_init(int groups, int k, int beam_len, int start_token, int32_t* hist, int32_t* tok, double* scores, double* best_score,
+                 int32_t* best_len, void* stream) {
+  VD_CHECK_ARG(hist && tok && scores && best_score && best_len && groups >= 0 && beam_len >= 1, "vd_beam_init: bad args");
+  VD_CHECK_ARG(k >= 1 && k <= VD_BEAM_KMAX, "vd_beam_init: k = %d must be in [1, %d]", k, VD_BEAM_KMAX);
+  if (groups == 0) return VD_OK;
+  const long n = (long)groups * k * beam_len;
+  hipLaunchKernelGGL(beam_init_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, groups, k, beam_len, start_token, hist,
+                     tok, scores, best_score, best_len);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+int vd_beam_advance(const int32_t* top_idx, const float* top_val, int groups, int k, int step, int beam_len, int end_token,
+                    double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok, double* best_score,
+                    int32_t* best_len, int32_t* best_hist, void* stream) {
+  VD_CHECK_ARG(top_idx && top_val && scores && hist_in && hist_out && src && next_tok && best_score && best_len && best_hist &&
+               groups >= 0 && hist_in != hist_out, "vd_beam_advance: bad args");
+  VD_CHECK_ARG(k >= 1 && k <= VD_BEAM_KMAX, "vd_beam_advance: k = %d must be in [1, %d]", k, VD_BEAM_KMAX);
+  VD_CHECK_ARG(step >= 1 && step < beam_len, "vd_beam_advance: step %d outside [1, %d)", step, beam_len);
+  if (groups == 0) return VD_OK;
+  hipLaunchKernelGGL(beam_advance_kernel, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, top_idx, top_val, k, step,
+                     beam_len, end_token, scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+int vd_beam_select_rows(float* cur, const float* stepped, const int32_t* src, int64_t rows, int k, int H, void* stream) {
+  VD_CHECK_ARG(cur && stepped && src && rows >= 0 && H >= 1 && cur != stepped, "vd_beam_select_rows: bad args");
+  VD_CHECK_ARG(k >= 1 && rows % k == 0, "vd_beam_select_rows: %lld rows are not whole groups of k = %d", (long long)rows, k);
+  if (rows == 0) return VD_OK;
+  hipLaunchKernelGGL(beam_select_rows_kernel, dim3(grid_for(rows * H)), dim3(256), 0, (hipStream_t)stream, cur, stepped, src,
+                     (long)rows, k, H);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+int vd_beam_finish(int groups, int k, int beam_len, const int32_t* hist, const double* scores, const double* best_score,
+                   const int32_t* best_len, const int32_t* best_hist, int32_t* out_tokens, double* out_scores, void* stream) {
+  VD_CHECK_ARG(hist && scores && best_score && best_len && best_hist && out_tokens && out_scores && groups >= 0 && k >= 1 &&
+               beam_len >= 1, "vd_beam_finish: bad args");
+  if (groups == 0) return VD_OK;
+  const long n = (long)groups * beam_len;
+  hipLaunchKernelGGL(beam_finish_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, groups, k, beam_len, hist, scores,
+                     best_score, best_len, best_hist, out_tokens, out_scores);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+}  // extern "C"

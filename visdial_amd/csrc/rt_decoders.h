@@ -17,6 +17,7 @@ struct Decoder {
   virtual int gen_begin(vd_model*, const int32_t*, int) { return no_gen(); }
   virtual int gen_step(vd_model*, const int32_t*, float*) { return no_gen(); }
   virtual int gen_select(vd_model*, const int32_t*, int) { return no_gen(); }
+  virtual int gen_beam_search(vd_model*, int, int, int, int, int32_t*, double*) { return no_gen(); }
   static int no_gen() {
     vd_set_error("sampling / beam search only for the generative decoder (model.lua:436-438)");
     return VD_ERR_STATE;
@@ -206,11 +207,15 @@ struct Gen;
 int Gen_begin(Gen* g, vd_model* m, const int32_t* rounds, int n);
 int Gen_step(Gen* g, vd_model* m, const int32_t* tokens, float* host_logp);
 int Gen_select(Gen* g, vd_model* m, const int32_t* src, int n_keep);
+int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end, int32_t* host_tokens, double* host_scores);
 
 struct Gen : Decoder {
   int gen_begin(vd_model* m, const int32_t* r, int n) override { return Gen_begin(this, m, r, n); }
   int gen_step(vd_model* m, const int32_t* t, float* lp) override { return Gen_step(this, m, t, lp); }
   int gen_select(vd_model* m, const int32_t* src, int k) override { return Gen_select(this, m, src, k); }
+  int gen_beam_search(vd_model* m, int k, int L, int st, int en, int32_t* t, double* sc) override {
+    return Gen_beam_search(this, m, k, L, st, en, t, sc);
+  }
   std::vector<SeqLSTM> rnn;
   long E = 0, H = 0, V = 0, Vp = 0;
   int gen_n = 0;                                     // live hypotheses of the running generation
@@ -389,6 +394,27 @@ inline int Gen_begin(Gen* g, vd_model* m, const int32_t* rounds, int n) {
   g->gen_n = n;
   return VD_OK;
 }
+// The device part of one decoder step (model.lua:518-522): the n hypotheses' tokens (device) through embedding, LSTM stack
+// and vocabulary projection from the current state gen.h<l> / gen.c<l> -> logits [n x Vp]; the stepped state is left in
+// rnn[l].out_at(0) / cell_at(0).  Shared by vd_model_decode_step and vd_model_beam_search.
+inline int gen_forward(Gen* g, vd_model* m, const int32_t* tok, int n, float** logits) {
+  hipStream_t s = m->s_main;
+  const long H = g->H, E = g->E, V = g->V, Vp = g->Vp;
+  for (size_t l = 0; l < g->rnn.size(); ++l) {
+    float *h, *c;
+    VD_TRY(ws_get(m, "gen.h" + std::to_string(l), (size_t)n * H, &h));
+    VD_TRY(ws_get(m, "gen.c" + std::to_string(l), (size_t)n * H, &c));
+    g->rnn[l].userPrevOutput = h;
+    g->rnn[l].userPrevCell = c;
+  }
+  float *x, *top;
+  VD_TRY(ws_get(m, "gen1.x", (size_t)n * E, &x));
+  VD_TRY(ws_get(m, "gen1.logits", (size_t)n * Vp, logits));
+  VD_TRY(vd_embed_gather(Wp(m, "embed"), tok, nullptr, x, n, (int)E, 1.f, s));
+  VD_TRY(lstm_stack_forward(m, s, g->rnn, {x}, 1, n, tok, &top));
+  VD_TRY(vd_gemm_nt(top, H, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), *logits, Vp, n, (int)V, (int)H, VD_ACT_NONE, 0, s));
+  return VD_OK;
+}
 // model.lua:518-522 / :590-596: one decoder step for the n live hypotheses -> log-probabilities [n x V] on the host
 inline int Gen_step(Gen* g, vd_model* m, const int32_t* tokens, float* host_logp) {
   const int n = g->gen_n;
@@ -398,26 +424,15 @@ inline int Gen_step(Gen* g, vd_model* m, const int32_t* tokens, float* host_logp
   int32_t* tok;
   VD_TRY(gen_rows(m, "gen.tok", tokens, n, &tok));
   VD_TRY(vd_memset(Wp(m, "embed"), 0, E * 4, s));                                   // LookupTableMaskZero pad row
-  const int L = (int)g->rnn.size();
-  std::vector<float*> h(L), c(L), hn(L), cn(L);
-  for (int l = 0; l < L; ++l) {
-    VD_TRY(ws_get(m, "gen.h" + std::to_string(l), (size_t)n * H, &h[l]));
-    VD_TRY(ws_get(m, "gen.c" + std::to_string(l), (size_t)n * H, &c[l]));
-    VD_TRY(ws_get(m, "gen.hn" + std::to_string(l), (size_t)n * H, &hn[l]));
-    VD_TRY(ws_get(m, "gen.cn" + std::to_string(l), (size_t)n * H, &cn[l]));
-    g->rnn[l].userPrevOutput = h[l];
-    g->rnn[l].userPrevCell = c[l];
-  }
-  float *x, *top, *logits;
-  VD_TRY(ws_get(m, "gen1.x", (size_t)n * E, &x));
-  VD_TRY(ws_get(m, "gen1.logits", (size_t)n * Vp, &logits));
-  VD_TRY(vd_embed_gather(Wp(m, "embed"), tok, nullptr, x, n, (int)E, 1.f, s));
-  VD_TRY(lstm_stack_forward(m, s, g->rnn, {x}, 1, n, tok, &top));
-  VD_TRY(vd_gemm_nt(top, H, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), logits, Vp, n, (int)V, (int)H, VD_ACT_NONE, 0, s));
+  float* logits;
+  VD_TRY(gen_forward(g, m, tok, n, &logits));
   VD_TRY(vd_log_softmax_rows(logits, Vp, n, (int)V, s));
-  for (int l = 0; l < L; ++l) {                                                      // the stepped state (decoderConnect, gen.lua:63-68)
-    VD_TRY(vd_memcpy_d2d(hn[l], g->rnn[l].out_at(0), (long)n * H * 4, s));
-    VD_TRY(vd_memcpy_d2d(cn[l], g->rnn[l].cell_at(0), (long)n * H * 4, s));
+  for (size_t l = 0; l < g->rnn.size(); ++l) {                                       // the stepped state (decoderConnect, gen.lua:63-68)
+    float *hn, *cn;
+    VD_TRY(ws_get(m, "gen.hn" + std::to_string(l), (size_t)n * H, &hn));
+    VD_TRY(ws_get(m, "gen.cn" + std::to_string(l), (size_t)n * H, &cn));
+    VD_TRY(vd_memcpy_d2d(hn, g->rnn[l].out_at(0), (long)n * H * 4, s));
+    VD_TRY(vd_memcpy_d2d(cn, g->rnn[l].cell_at(0), (long)n * H * 4, s));
   }
   VD_HIP(hipMemcpy2DAsync(host_logp, (size_t)V * 4, logits, (size_t)Vp * 4, (size_t)V * 4, (size_t)n, hipMemcpyDeviceToHost, s));
   VD_HIP(hipStreamSynchronize(s));
@@ -446,6 +461,64 @@ inline int Gen_select(Gen* g, vd_model* m, const int32_t* src, int n_keep) {
     VD_TRY(vd_embed_gather(hn, idx, nullptr, h, n_keep, (int)H, 1.f, s));
     VD_TRY(vd_embed_gather(cn, idx, nullptr, c, n_keep, (int)H, 1.f, s));
   }
+  return VD_OK;
+}
+
+// Model:generateAnswers' beam search (model.lua:466-573) for all N rounds of the last vd_model_encode batch at once: N groups
+// of k slots = N * k hypothesis rows.  Per step, on s_main only: embedding gather -> LSTM stack -> vocabulary GEMM -> fused
+// log-softmax + top-k -> advance (candidate bookkeeping, csrc/beam.hip) -> state select.  The next tokens never leave the
+// device; the answers come back in ONE copy after the last step.
+inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end, int32_t* host_tokens, double* host_scores) {
+  VD_CHECK_ARG(m->gen_enc_out && m->N > 0, "vd_model_beam_search: call vd_model_encode first");
+  VD_CHECK_ARG(host_tokens && host_scores && L >= 1, "vd_model_beam_search: bad arguments");
+  VD_CHECK_ARG(k >= 1 && k <= 32 && k <= g->V, "vd_model_beam_search: beam size %d must be in [1, min(32, vocabSize)]", k);
+  const int G = m->N, n = G * k;
+  const long H = g->H, E = g->E, V = g->V, Vp = g->Vp;
+  std::vector<int32_t> rounds(n);
+  for (int i = 0; i < n; ++i) rounds[i] = i / k;                                     // hiddenBeams (model.lua:478-503)
+  VD_TRY(Gen_begin(g, m, rounds.data(), n));
+  hipStream_t s = m->s_main;
+  int32_t *tok, *top_idx, *src, *hist[2], *best_len, *best_hist;
+  float* top_val;
+  double *scores, *best_score;
+  uint8_t* out;
+  const size_t tok_bytes = ((size_t)G * L * 4 + 7) / 8 * 8;
+  VD_TRY(ws_get(m, "beam.tok", (size_t)n, &tok));
+  VD_TRY(ws_get(m, "beam.top_idx", (size_t)n * k, &top_idx));
+  VD_TRY(ws_get(m, "beam.top_val", (size_t)n * k, &top_val));
+  VD_TRY(ws_get(m, "beam.src", (size_t)n, &src));
+  VD_TRY(ws_get(m, "beam.hist0", (size_t)n * L, &hist[0]));
+  VD_TRY(ws_get(m, "beam.hist1", (size_t)n * L, &hist[1]));
+  VD_TRY(ws_get(m, "beam.scores", (size_t)n, &scores));
+  VD_TRY(ws_get(m, "beam.best_score", (size_t)G, &best_score));
+  VD_TRY(ws_get(m, "beam.best_len", (size_t)G, &best_len));
+  VD_TRY(ws_get(m, "beam.best_hist", (size_t)G * L, &best_hist));
+  VD_TRY(ws_get(m, "beam.out", tok_bytes + (size_t)G * 8, &out));
+  VD_TRY(vd_beam_init(G, k, L, start, hist[0], tok, scores, best_score, best_len, s));
+  VD_TRY(vd_memset(Wp(m, "embed"), 0, E * 4, s));                                   // LookupTableMaskZero pad row
+  int cur = 0;
+  for (int step = 1; step < L; ++step) {
+    float* logits;
+    VD_TRY(gen_forward(g, m, tok, n, &logits));
+    VD_TRY(vd_beam_topk(logits, Vp, n, (int)V, tok, k, top_idx, top_val, s));
+    VD_TRY(vd_beam_advance(top_idx, top_val, G, k, step, L, end, scores, hist[cur], hist[cur ^ 1], src, tok, best_score, best_len,
+                           best_hist, s));
+    for (size_t l = 0; l < g->rnn.size(); ++l) {
+      float *h, *c;
+      VD_TRY(ws_get(m, "gen.h" + std::to_string(l), (size_t)n * H, &h));
+      VD_TRY(ws_get(m, "gen.c" + std::to_string(l), (size_t)n * H, &c));
+      VD_TRY(vd_beam_select_rows(h, g->rnn[l].out_at(0), src, n, k, (int)H, s));
+      VD_TRY(vd_beam_select_rows(c, g->rnn[l].cell_at(0), src, n, k, (int)H, s));
+    }
+    cur ^= 1;
+  }
+  VD_TRY(vd_beam_finish(G, k, L, hist[cur], scores, best_score, best_len, best_hist, reinterpret_cast<int32_t*>(out),
+                        reinterpret_cast<double*>(out + tok_bytes), s));
+  std::vector<uint8_t> staged(tok_bytes + (size_t)G * 8);
+  VD_HIP(hipMemcpyAsync(staged.data(), out, staged.size(), hipMemcpyDeviceToHost, s));
+  VD_HIP(hipStreamSynchronize(s));
+  memcpy(host_tokens, staged.data(), (size_t)G * L * 4);
+  memcpy(host_scores, staged.data() + tok_bytes, (size_t)G * 8);
   return VD_OK;
 }
 

@@ -540,6 +540,12 @@ int vd_model_decode_select(vd_model* m, const int32_t* src, int n_keep) {
   VD_CHECK_ARG(m, "vd_model_decode_select: null model");
   return m->dec->gen_select(m, src, n_keep);
 }
+int vd_model_beam_search(vd_model* m, int beam_size, int beam_len, int start_token, int end_token, int32_t* host_tokens,
+                         double* host_scores) {
+  VD_CHECK_ARG(m, "vd_model_beam_search: null model");
+  VdRange r("vd_model_beam_search");
+  return m->dec->gen_beam_search(m, beam_size, beam_len, start_token, end_token, host_tokens, host_scores);
+}
 
 // waits for the loss of the last vd_model_forward_backward: disc = mean cross-entropy over the rounds, gen = summed
 // NLL over the non-pad answer tokens (SequencerCriterion of ClassNLLCriterion, model.lua:32-36)

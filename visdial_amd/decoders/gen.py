@@ -57,10 +57,10 @@ class Decoder(object):
         return float(loss_rows.cpu().numpy().astype(np.float64).sum())
 
 
-    def step_logprobs(self, tok, hidden):
-        """One decoder step for K hypotheses (the `self.decoder:forward(beams[{{step-1}}])` of model.lua:518):
-        tok device int32 [1 x K]; hidden = per-layer (h [K x H], c [K x H]).  Returns (log-probs [K x V] on the
-        host, new per-layer (h, c) device tensors)."""
+    def step_logits(self, tok, hidden):
+        """The device part of one decoder step for K hypotheses: tok device int32 [1 x K]; hidden = per-layer (h [K x H],
+        c [K x H]).  Returns (logits [K x Vp] on the device, stepped per-layer (h, c) = views of the layers' state, valid until
+        the next step)."""
         ws, H, V, Vp = self.ws, self.H, self.V, self.Vp
         K = tok.shape[1]
         for l, (h0, c0) in zip(self.rnnLayers, hidden):
@@ -70,8 +70,16 @@ class Decoder(object):
         h = lstm_stack_forward(self.rnnLayers, x, 1, K, tok).view(K, H)
         logits = ws.get('gen1.logits', (K, Vp))
         ops.gemm_nt(h, self.Wv, logits, bias=self.bv, M=K, N=V, K=H, ldc=Vp)
+        return logits, [(l.output[0], l.cell[0]) for l in self.rnnLayers]
+
+    def step_logprobs(self, tok, hidden):
+        """One decoder step for K hypotheses (the `self.decoder:forward(beams[{{step-1}}])` of model.lua:518):
+        tok device int32 [1 x K]; hidden = per-layer (h [K x H], c [K x H]).  Returns (log-probs [K x V] on the
+        host, new per-layer (h, c) device tensors)."""
+        V = self.V
+        logits, stepped = self.step_logits(tok, hidden)
         ops.log_softmax_rows(logits, V)
-        new_hidden = [(l.output[0].clone(), l.cell[0].clone()) for l in self.rnnLayers]
+        new_hidden = [(h.clone(), c.clone()) for h, c in stepped]
         logp = logits[:, :V].cpu().numpy()
         logp[tok[0].cpu().numpy() == 0] = 0.0        # MaskZero(Linear) + MaskZero(LogSoftMax) (gen.lua:23-24): a pad token's row is all zeros
         return logp, new_hidden

@@ -357,6 +357,35 @@ class Model(SplitEval):
             hidden.append((h, c))
         g['hidden'] = hidden
 
+    def _gen_beam(self, beamSize, beamLen, startToken, endToken):
+        """the batched beam search (beamBatch > 0, model.lua:466-573) of every round of the last `_gen_encode` batch on the device:
+        per step the decoder step (decoders/gen.py step_logits) -> fused log-softmax + top-k -> advance -> state select, the next
+        tokens staying on the device.  Returns (tokens [N x beamLen], fp64 scores [N]) on the host."""
+        g, k, L, V = self._gen, int(beamSize), int(beamLen), self.params['vocabSize']
+        G = g['encOut'].shape[0]
+        n = G * k
+        self._gen_begin(np.repeat(np.arange(G, dtype=np.int32), k))           # hiddenBeams (model.lua:478-503)
+        i32, f64 = dict(dtype=torch.int32, device=self.device), dict(dtype=torch.float64, device=self.device)
+        tok, src = torch.empty(1, n, **i32), torch.empty(n, **i32)
+        hist = [torch.empty(n, L, **i32), torch.empty(n, L, **i32)]
+        scores, best_score = torch.empty(n, **f64), torch.empty(G, **f64)
+        best_len, best_hist = torch.empty(G, **i32), torch.empty(G, L, **i32)
+        top_idx, top_val = torch.empty(n, k, **i32), torch.empty(n, k, dtype=torch.float32, device=self.device)
+        ops.beam_init(G, k, L, startToken, hist[0], tok, scores, best_score, best_len)
+        cur = 0
+        for step in range(1, L):
+            logits, stepped = self.decoder.step_logits(tok, g['hidden'])
+            ops.beam_topk(logits, V, tok, k, top_idx, top_val)
+            ops.beam_advance(top_idx, top_val, G, k, step, L, endToken, scores, hist[cur], hist[cur ^ 1], src, tok, best_score,
+                             best_len, best_hist)
+            for (h, c), (h_new, c_new) in zip(g['hidden'], stepped):
+                ops.beam_select_rows(h, h_new, src, k)
+                ops.beam_select_rows(c, c_new, src, k)
+            cur ^= 1
+        out_tok, out_score = torch.empty(G, L, **i32), torch.empty(G, **f64)
+        ops.beam_finish(G, k, L, hist[cur], scores, best_score, best_len, best_hist, out_tok, out_score)
+        return out_tok.cpu().numpy(), out_score.cpu().numpy()
+
     # ------------------------------------------------------------------ test / checkpoint helpers
     def get_parameters_dict(self):
         return self.fp.to_host('w')

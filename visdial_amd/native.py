@@ -313,6 +313,15 @@ class NativeModel(SplitEval):
         s_ = np.ascontiguousarray(src, dtype=np.int32)
         call("vd_model_decode_select", self.h, s_.ctypes.data, int(n_keep))
 
+    def _gen_beam(self, beamSize, beamLen, startToken, endToken):
+        """the batched beam search (beamBatch > 0) of every round of the last `_gen_encode` batch: vd_model_beam_search"""
+        N = int(self._N)
+        tokens = np.zeros((N, int(beamLen)), np.int32)
+        scores = np.zeros(N, np.float64)
+        call("vd_model_beam_search", self.h, int(beamSize), int(beamLen), int(startToken), int(endToken), tokens.ctypes.data,
+             scores.ctypes.data)
+        return tokens, scores
+
     def option_rows(self):
         """(rows the option LSTM executes, N * O candidates) of the current batch: the upload de-duplicates candidates"""
         a, b = C.c_int64(), C.c_int64()

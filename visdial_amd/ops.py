@@ -322,6 +322,38 @@ def log_softmax_rows(x, V):
     return x
 
 
+# ---------------------------------------------------------------- batched beam search (model.lua:466-573; csrc/beam.hip)
+F64 = torch.float64
+
+
+def beam_topk(logits, V, tok, k, top_idx, top_val):
+    """fused nn.LogSoftMax + top-k (value descending, index ascending) of every row; token-0 rows are all-zero rows"""
+    call("vd_beam_topk", _p(logits, F32), logits.stride(0), logits.shape[0], V, _p(tok, I32), int(k), _p(top_idx, I32),
+         _p(top_val, F32), _stream())
+
+
+def beam_init(groups, k, L, start, hist, tok, scores, best_score, best_len):
+    call("vd_beam_init", int(groups), int(k), int(L), int(start), _p(hist, I32), _p(tok, I32), _p(scores, F64), _p(best_score, F64),
+         _p(best_len, I32), _stream())
+
+
+def beam_advance(top_idx, top_val, groups, k, step, L, end, scores, hist_in, hist_out, src, next_tok, best_score, best_len,
+                 best_hist):
+    call("vd_beam_advance", _p(top_idx, I32), _p(top_val, F32), int(groups), int(k), int(step), int(L), int(end), _p(scores, F64),
+         _p(hist_in, I32), _p(hist_out, I32), _p(src, I32), _p(next_tok, I32), _p(best_score, F64), _p(best_len, I32),
+         _p(best_hist, I32), _stream())
+
+
+def beam_select_rows(cur, stepped, src, k):
+    """cur[r] = stepped[group(r) * k + src[r]] where src[r] >= 0"""
+    call("vd_beam_select_rows", _p(cur, F32), _p(stepped, F32), _p(src, I32), cur.shape[0], int(k), cur.shape[1], _stream())
+
+
+def beam_finish(groups, k, L, hist, scores, best_score, best_len, best_hist, out_tokens, out_scores):
+    call("vd_beam_finish", int(groups), int(k), int(L), _p(hist, I32), _p(scores, F64), _p(best_score, F64), _p(best_len, I32),
+         _p(best_hist, I32), _p(out_tokens, I32), _p(out_scores, F64), _stream())
+
+
 def zero(t):
     """t[...] = 0 through vd_memset (hipMemsetAsync on the current stream); contiguous tensors only"""
     call("vd_memset", _p(t), 0, t.numel() * t.element_size(), _stream())

@@ -3,7 +3,10 @@ perplexity), Model:retrieve (ground-truth ranks + R@k / MRR) and Model:predict (
 sequential batches of `dataloader:getTestBatch`.  A host provides `params`, `_set_training(bool)`,
 `forwardBackward(batch, onlyForward=True)` and `retrieveBatch(batch)` (ranks per `params['useGt']`); for
 Model:generateAnswers the four device steps `_gen_encode(batch)`, `_gen_begin(rounds)`, `_gen_step(tokens) -> logp`,
-`_gen_select(src, n_keep)` (= vd_model_encode / decode_begin / decode_step / decode_select of the model-level ABI)."""
+`_gen_select(src, n_keep)` (= vd_model_encode / decode_begin / decode_step / decode_select of the model-level ABI), and for the
+batched beam search (params beamBatch > 0) `_gen_beam(beamSize, beamLen, startToken, endToken) -> (tokens [N x beamLen], scores
+[N])` over every round of the last `_gen_encode` batch (= vd_model_beam_search; the operator-level host composes the vd_beam_*
+kernels)."""
 import math
 
 import numpy as np
@@ -92,11 +95,15 @@ class SplitEval(object):
         """Beam search (default) or temperature sampling with the generative decoder, one dialog at a time,
         exactly as the reference drives it from the host: the decoder step (embedding, LSTM stack, vocabulary
         projection, log-softmax) runs on the device for all hypotheses at once, candidate bookkeeping is host
-        control flow.  Returns [{image_id, dialog: [{question, answer}...]}]."""
+        control flow.  params beamBatch = B > 0: the beam search of dialogs [s, s+B) runs together on the device, every round of
+        the chunk at once (one encode + one `_gen_beam` per chunk); same records.  Returns [{image_id, dialog: [{question, answer}...]}]."""
         if self.params['decoder'] == 'disc':
             raise SystemExit('Sampling/beam search only for generative model')
         params = params or {}
         sampleWords = bool(params.get('sampleWords', 0) == 1)
+        beamBatch = int(params.get('beamBatch', 0) or 0)
+        if beamBatch > 0 and sampleWords:
+            raise ValueError('beamBatch > 0 is batched beam search; sampling (sampleWords = 1) runs on the host: use beamBatch = 0')
         temperature = float(params.get('temperature', 1.0))
         beamSize, beamLen = int(params.get('beamSize', 5)), int(params.get('beamLen', 20))
         startToken, endToken = dataloader.word2ind['<START>'], dataloader.word2ind['<END>']
@@ -105,6 +112,20 @@ class SplitEval(object):
         ind2word = dataloader.ind2word
         answerTable = []
         self._set_training(False)
+        img_ids = getattr(dataloader, 'unique_img_' + dtype, None)
+        if beamBatch > 0:
+            for first in range(1, numThreads + 1, beamBatch):
+                convIds = np.arange(first, min(first + beamBatch, numThreads + 1))
+                batch = dataloader.getIndexData(convIds, self.params, dtype)
+                R = batch['ques_fwd'].shape[1]
+                self._gen_encode(batch)
+                tokens, _ = self._gen_beam(beamSize, beamLen, startToken, endToken)   # row = dialog * R + round
+                for i, convId in enumerate(convIds):
+                    threadAnswers = [{'question': utils.idToWords(batch['ques_fwd'][i, it], ind2word),
+                                      'answer': utils.idToWords(tokens[i * R + it], ind2word)} for it in range(R)]
+                    answerTable.append({'image_id': img_ids[convId - 1] if img_ids else int(convId), 'dialog': threadAnswers})
+            self._set_training(True)
+            return answerTable
         for convId in range(1, numThreads + 1):
             batch = dataloader.getIndexData(np.array([convId]), self.params, dtype)
             R = batch['ques_fwd'].shape[1]
@@ -159,7 +180,6 @@ class SplitEval(object):
                 for it in range(R):
                     threadAnswers.append({'question': utils.idToWords(batch['ques_fwd'][0, it], ind2word),
                                           'answer': utils.idToWords(answer[it], ind2word)})
-            img_ids = getattr(dataloader, 'unique_img_' + dtype, None)
             answerTable.append({'image_id': img_ids[convId - 1] if img_ids else convId, 'dialog': threadAnswers})
         self._set_training(True)
         return answerTable
