@@ -104,6 +104,17 @@ def test_native_refuses_unknown_plugins(gpu):
         NativeModel(derive(small_params(encoder='lf-ques', decoder='gen')) | {'decoder': 'ctc'})
 
 
+def test_native_refuses_unknown_precision(gpu):
+    """vd_model_params.lstmBf16 takes 0, 1, 3, 6 or 9; any other value is an argument error, not a quiet fp32 pass"""
+    import ctypes as C
+    from visdial_amd import _lib
+    mp = _lib.ModelParams(vocabSize=60, embedSize=20, rnnHiddenSize=64, maxQuesCount=5, numOptions=9, lstmBf16=5)
+    h = C.c_void_p()
+    with pytest.raises(_lib.VisdialHipError, match='lstmBf16'):
+        _lib.call("vd_model_create", C.byref(mp), b'lf-ques', b'disc', C.byref(h))
+    assert not h.value
+
+
 @pytest.mark.parametrize("enc,dec", [(e, d) for e in ALL_ENC for d in ('disc', 'gen')
                                      if (e, d) != ('mn-att-ques-im-hist', 'disc')])     # that pair: tests above
 @pytest.mark.parametrize("case", ['tiny', 'mid'])

@@ -724,10 +724,6 @@ __global__ void __launch_bounds__(256) transpose32_kernel(const float* __restric
   }
 }
 
-static bool img_split_ok(int flags, long rows, int H, int Kc) {
-  return (flags & VD_FLAG_SPLIT9) && rows >= 128 && H % 16 == 0 && Kc % 16 == 0 && H % 4 == 0 && rows * (long)(H > Kc ? H : Kc) * 4 < (1L << 32);
-}
-
 // xdrop[(n, s), :] = dropout1(pre[(n / R, s), :]) -- once per step, shared by every attention hop's forward product and weight gradient
 int vd_img_drop_gather(const float* pre, const uint8_t* mask1, float* xdrop, int N, int R, int S2, int H, float scale, hipStream_t stream) {
   VD_CHECK_ARG(pre && xdrop && N >= 0 && R >= 1 && S2 >= 1 && H % 4 == 0, "vd_img_drop_gather: bad args");
@@ -740,7 +736,7 @@ int vd_img_drop_gather(const float* pre, const uint8_t* mask1, float* xdrop, int
 
 int vd_img_common_forward_p(const float* pre, const uint8_t* mask1, const float* xdrop, const float* Wc, const float* bc, const float* qc,
                             const uint8_t* mask2, float* iqc, int N, int R, int S2, int H, int Kc, float scale, int flags, hipStream_t stream) {
-  if (!xdrop || !img_split_ok(flags, (long)N * S2, H, Kc))
+  if (!xdrop || !(flags & VD_FLAG_SPLIT9) || !vd_img_split_ok((long)N * S2, H, Kc))
     return vd_img_common_forward(pre, mask1, Wc, bc, qc, mask2, iqc, N, R, S2, H, Kc, scale, stream);
   VdStreamScratch scr;
   if (int rc = vd_stream_scratch(stream, (size_t)Kc * H * 6, 0, &scr)) return rc;
@@ -752,7 +748,7 @@ int vd_img_common_forward_p(const float* pre, const uint8_t* mask1, const float*
 
 int vd_img_tr_backward_p(const float* dz, const float* Wc, const float* p, const float* datt, const uint8_t* mask1, float* dpre, int N, int R,
                          int S2, int H, int Kc, float scale, int flags, hipStream_t stream) {
-  if (!img_split_ok(flags, (long)N * S2, H, Kc)) return vd_img_tr_backward(dz, Wc, p, datt, mask1, dpre, N, R, S2, H, Kc, scale, stream);
+  if (!(flags & VD_FLAG_SPLIT9) || !vd_img_split_ok((long)N * S2, H, Kc)) return vd_img_tr_backward(dz, Wc, p, datt, mask1, dpre, N, R, S2, H, Kc, scale, stream);
   VdStreamScratch scr;
   if (int rc = vd_stream_scratch(stream, (size_t)Kc * H * 10, 0, &scr)) return rc;
   float* WcT = scr.wht;                                                                    // [H x Kc]: B^T of dz * Wc, rows k-contiguous
@@ -767,7 +763,7 @@ int vd_img_tr_backward_p(const float* dz, const float* Wc, const float* p, const
 int vd_img_common_wgrad_p(const float* dz, const float* pre, const uint8_t* mask1, const float* xdrop, float* dWc, int N, int R, int S2, int H,
                           int Kc, float scale, int flags, hipStream_t stream) {
   const long K = (long)N * S2;
-  if (!xdrop || !(flags & VD_FLAG_SPLIT9) || Kc % SplitTnCfg::BM != 0 || H % SplitTnCfg::BN != 0 || K < 1024)
+  if (!xdrop || !(flags & VD_FLAG_SPLIT9) || !vd_img_split_ok(K, H, Kc) || !vd_tn_split_tiles(Kc, H) || K < 1024)
     return vd_img_common_wgrad(dz, pre, mask1, dWc, N, R, S2, H, Kc, scale, stream);
   const int K1 = (int)(K & ~15L);
   if (int rc = launch_gemm_split_tn<9>(Kc, H, K1, dz, (long)Kc, xdrop, (long)H, dWc, (long)H, stream)) return rc;

@@ -102,7 +102,6 @@ const vd_bf16_bits* vd_bf16_shadow_find(const float* p, size_t floats);
 void vd_bf16_shadow_invalidate(const float* p, size_t floats);
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Gate nonlinearities on the hardware exp and reciprocal (v_exp_f32, v_rcp_f32: ~1 ulp each): absolute error ~1e-7,
 // two orders below the 1e-5 per-op / 1e-4 end-to-end parity budget.  The reciprocal is the bare instruction on
@@ -111,39 +110,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // issue in the epilogue comes straight out of the co-resident waves' matrix-pipe time.
 __device__ __forceinline__ float vd_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float vd_sigmoid(float x) { return vd_rcp(1.0f + __expf(-x)); }
-#ifndef VD_TANH_FMA
 __device__ __forceinline__ float vd_tanh(float x) {
   const float e = __expf(-2.0f * fabsf(x));          // in (0, 1]: no overflow
   const float t = (1.0f - e) * vd_rcp(1.0f + e);
   return copysignf(t, x);
-}
-#else
-// A/B build (-DVD_TANH_FMA): tanh(x) = 2 / (1 + e^(-2x)) - 1 -- three VALU + two transcendental instructions instead of five + two,
-// the same ~6e-8 absolute error near 0, no NaN (e^(-2x) = inf -> rcp = 0 -> -1).  43 / 53 instructions fewer in the forward / backward
-// step epilogues, all 226 GPU tests green, no measurable change of the step (profiles/r03_experiments.txt 13d): not the default.
-__device__ __forceinline__ float vd_tanh(float x) { return fmaf(2.0f, vd_rcp(1.0f + __expf(-2.0f * x)), -1.0f); }
-#endif
-
-// Streaming (non-temporal) 16-byte accesses for data that is written once and read much later (saved gates, da):
-// A/B build knob -DVD_EPI_NT=1 (`make variant NAME=nt DEFS=-DVD_EPI_NT=1`), else plain accesses.
-#ifndef VD_EPI_NT
-#define VD_EPI_NT 0
-#endif
-__device__ __forceinline__ void vd_st4_stream(float* p, const float4& v) {
-#if VD_EPI_NT
-  f32x4 t = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(p));
-#else
-  *reinterpret_cast<float4*>(p) = v;
-#endif
-}
-__device__ __forceinline__ float4 vd_ld4_stream(const float* p) {
-#if VD_EPI_NT
-  const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-  return make_float4(t[0], t[1], t[2], t[3]);
-#else
-  return *reinterpret_cast<const float4*>(p);
-#endif
 }
 
 // Buffer addressing for the step kernels' epilogues: an SGPR descriptor per tensor + a 32-bit VGPR byte offset + an

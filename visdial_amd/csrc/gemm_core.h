@@ -156,13 +156,11 @@ struct EpiPreOf {
   static constexpr bool value = false;
   using type = EpiNoPre;
 };
-#ifndef VD_NO_EPI_PRE   // (A/B build knob: `make variant NAME=nopre DEFS=-DVD_NO_EPI_PRE`)
 template <class Epi>
 struct EpiPreOf<Epi, std::void_t<typename Epi::Pre>> {
   static constexpr bool value = true;
   using type = typename Epi::Pre;
 };
-#endif
 
 // Epilogue functors of the split-K latency shapes may offer a DISTRIBUTED form (HAS_DIST, DOps, dist_ok / dist_load / dist_store): the four
 // K-slice waves of a 32-row tile each finish one 8-row group instead of wave 0 finishing all four.
@@ -187,17 +185,15 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 // lanes take sixteen consecutive k of one column group: the transposing LDS stores (ds_write_b32: two groups of 32 lanes, 32 banks) then
 // write 16 consecutive floats per row group, and the two row groups of a lane group sit 4 * STRIDE = 16 (mod 32) banks apart --
 // conflict-free.  (With runs of eight k the four row groups of a lane group fell on two bank sets: 2-way conflicts, 8 instead of 4 cycles
-// on each of the 64 store instructions of a forward-tick iteration.)   `make variant DEFS=-DVD_KMAJ_OLD` restores runs of eight.
+// on each of the 64 store instructions of a forward-tick iteration.)  Tiles whose BK is no multiple of 16 keep runs of eight.
 template <int D, int BK>
 __device__ __forceinline__ void kmaj_piece(int f, int& r4, int& kk) {
-#ifndef VD_KMAJ_OLD
   if constexpr (BK % 16 == 0) {
     const int klo = f & 15, g = f >> 4;
     r4 = g % (D / 4);
     kk = (g / (D / 4)) * 16 + klo;
     return;
   }
-#endif
   const int klo = f & 7, g = f >> 3;
   r4 = g % (D / 4);
   kk = (g / (D / 4)) * 8 + klo;

@@ -436,7 +436,7 @@ int vd_gemm_tn_acc(const float* A, int64_t lda, const float* B, int64_t ldb, flo
   // the 1.33-round tail, not the pipeline, decided).
   // exact-operand split (split_core.h): the big contraction of a split9 pass (dWh of the option recurrence); a ragged row tail (< 16
   // rows) goes through the fp32-MFMA kernel below
-  if ((flags & VD_FLAG_SPLIT9) && !(flags & VD_FLAG_BF16) && M % SplitTnCfg::BM == 0 && N % SplitTnCfg::BN == 0 && K >= 8192 &&
+  if ((flags & VD_FLAG_SPLIT9) && !(flags & VD_FLAG_BF16) && vd_tn_split_tiles(M, N) && K >= 8192 &&
       16L * lda * 4 < (1L << 31) && 16L * ldb * 4 < (1L << 31)) {
     const int K1 = K & ~15;
     if (int rc = launch_gemm_split_tn<9>(M, N, K1, A, lda, B, ldb, C, ldc, (hipStream_t)stream)) return rc;
@@ -444,7 +444,7 @@ int vd_gemm_tn_acc(const float* A, int64_t lda, const float* B, int64_t ldb, flo
     SrcK a2{A + (long)K1 * lda, lda}, b2{B + (long)K1 * ldb, ldb};
     return launch_gemm<GemmCfg<4, 1, 4, 16, 0, 4, 41984>>(M, N, K - K1, 1, a2, b2, e, (hipStream_t)stream);
   }
-  const bool kmaj = !(flags & VD_FLAG_BF16) && M % 128 == 0 && N % 128 == 0 && K >= 1024;
+  const bool kmaj = !(flags & VD_FLAG_BF16) && vd_tn_kmajor_fits(M, N, K);
   if (kmaj && K % 16 != 0) {
     // the k-major pipeline moves whole 16-row K tiles: contract the first floor(K / 16) * 16 rows with it and the last
     // < 16 rows with the register-staged kernel (one short launch; e.g. the encoder's (T-1)*N = 7 800 rows)
@@ -475,7 +475,7 @@ int vd_gemm_tn_acc(const float* A, int64_t lda, const float* B, int64_t ldb, flo
     // fp32 operands in memory (the encoder's saved state in a bf16 pass of the model-level runtime): LDS-DMA tiles of the fp32 rows, both
     // operands rounded to bf16 in registers, one v_mfma_f32_32x32x16_bf16 per 16 k = the exact-split kernel with its first product
     // only (split_core.h).  The last < 16 rows through the staging kernel.
-    if (M % SplitTnCfg::BM == 0 && N % SplitTnCfg::BN == 0 && K >= 1024 && lda % 4 == 0 && ldb % 4 == 0 && 16L * lda * 4 < (1L << 31) &&
+    if (vd_tn_split_tiles(M, N) && K >= 1024 && lda % 4 == 0 && ldb % 4 == 0 && 16L * lda * 4 < (1L << 31) &&
         16L * ldb * 4 < (1L << 31)) {
       const int K1 = K & ~15;
       if (int rc = launch_gemm_split_tn<1>(M, N, K1, A, lda, B, ldb, C, ldc, (hipStream_t)stream)) return rc;
@@ -554,11 +554,7 @@ int vd_gemm_tn_acc_bf16(const vd_bf16_bits* A16, const vd_bf16_bits* B16, float*
   VD_CHECK_ARG(A16 && B16 && C && M % 128 == 0 && N % 128 == 0 && K >= 0, "vd_gemm_tn_acc_bf16: M, N must be multiples of 128");
   const int K1 = K & ~31;
   if (K1 > 0) {
-#ifdef VD_NO_TR256   // (A/B build knob: `make variant NAME=notr256 DEFS=-DVD_NO_TR256`)
-    const bool big = false;
-#else
     const bool big = M % 256 == 0 && N % 256 == 0 && K1 >= 8192;
-#endif
     if (int rc = big ? launch_gemm_bf16_tn_tr256(A16, B16, C, ldc, M, N, K1, stream) : launch_gemm_bf16_tn_tr(A16, B16, C, ldc, M, N, K1, stream)) return rc;
   }
   if (K1 < K) {   // the last < 32 rows

@@ -36,7 +36,8 @@ struct EpiLstmFwdT {
   float* h_out;           // [N x H]
   int H;
   vd_bf16_bits* h16 = nullptr;   // nullable: bf16 copy of h_out (bf16 pass: operand of the weight-gradient contraction)
-  // SEQ = 1: compiler-scheduled epilogue (kept for the tick kernels' build switch VD_TICK_EPI_SEQ); 2: diagnostic, K loop only
+  // SEQ = 1: compiler-scheduled epilogue (the encoder tick kernels: 3 spilled VGPRs in the persistent kernel at the 128-register cap,
+  // 12 with the hand-scheduled one below); 0: hand-scheduled (the throughput kernels)
   // The four accumulator tiles are i,f,o,g of hidden units [j0, j0+32).  Each is staged through the wave's LDS
   // scratch so that a lane ends up with 4 consecutive hidden units of one row: every global access of the cell
   // update is a 16-byte one (8 lanes = one 128-byte segment of a row).
@@ -173,20 +174,6 @@ struct EpiLstmFwdT {
   }
   __device__ __forceinline__ void operator()(const f32x16 (&acc)[4], int row0, int vcol0, int lane, int M,
                                              int /*Nv*/, float* scr, const Pre* pre = nullptr) const {
-    if constexpr (SEQ == 2) {
-      // DIAGNOSTIC build (SEQ = 2): no epilogue loads, no gate math, one
-      // 16-byte store per row -- isolates the K loop of the step kernel.  Results are garbage by construction.
-      float4 a0[4];
-      const f32x16 sum = acc[0] + acc[1] + acc[2] + acc[3];   // keeps every MFMA of the K loop live
-      tile_to_rows(sum, scr, lane, a0);
-      const int j0 = (vcol0 >> 7) * 32 + (lane & 7) * 4;
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const int row = row0 + p * 8 + (lane >> 3);
-        if (row < M) *reinterpret_cast<float4*>(h_out + (long)row * H + j0) = a0[p];
-      }
-      return;
-    }
     if constexpr (SEQ == 1) {
       sequential(acc, row0, vcol0, lane, M, scr);
       return;
@@ -333,11 +320,6 @@ struct EpiLstmFwdT {
 };
 
 using EpiLstmFwd = EpiLstmFwdT<0>;
-
-#ifndef VD_TICK_EPI_SEQ
-#define VD_TICK_EPI_SEQ 1   // epilogue flavour of the encoder tick kernels: 1 = compiler-scheduled (3 spilled VGPRs in the persistent
-                           // kernel at the 128-register cap), 0 = the hand-scheduled one of the throughput kernels (12 spills)
-#endif
 
 // ---------------------------------------------------------------------------
 // backward epilogue: acc = (da_{t+1} * Wh^T)[row, j]  (zero at the last step)
@@ -608,38 +590,29 @@ static int weights_to_bf16(const float* src, vd_bf16_bits* dst, long n, hipStrea
   return VD_OK;
 }
 
-// LDS-DMA pipeline eligibility: throughput shape, K % 16 == 0, 32-bit row byte offsets
-static bool use_glds_fwd(int N, int H) {
-  static const int cfg = (20);
-  return cfg == 20 && N >= 2048 && H % 32 == 0 && (long)N * H * 4 < (1L << 32);
-}
-static bool use_glds_bwd(int N, int H) {
-  static const int cfg = (20);
-  return cfg == 20 && N >= 2048 && H % 32 == 0 && (long)N * 4 * H * 4 < (1L << 32);
-}
-
 static int lstm_step_fwd(const float* h_prev, const float* Wh, int N, int H, int K, const EpiLstmFwd& epi,
                          hipStream_t s) {
   SrcRow a{h_prev, H};
   SrcKGate4 b{Wh, 4L * H, H};
-  if (N >= 2048) return launch_gemm<CfgF9>(N, 4 * H, K, 1, a, b, epi, s);   // (throughput shapes normally take the LDS-DMA drivers)
+  if (N >= VD_THROUGHPUT_ROWS) return launch_gemm<CfgF9>(N, 4 * H, K, 1, a, b, epi, s);   // (throughput shapes normally take the LDS-DMA drivers)
   return launch_gemm<CfgFwdSmallA>(N, 4 * H, K, 1, a, b, epi, s);
 }
 
+// one backward step with the kernels vd_lstm_backward chose for the pass: the exact split (split = products per step, W3 the weight
+// planes), bf16 operands (da16 = this step's shadow), or fp32
 static int lstm_step_bwd(const float* da_next, const float* Wh, int N, int H, int K, const float* dh_a,
                          const float* dh_b, float* gates, const float* c_t, const float* c_prev, float* dc,
-                         int dc_first, hipStream_t s, int flags = 0, vd_bf16_bits* da16 = nullptr,
-                         const vd_bf16_bits* da16_next = nullptr, const vd_bf16_bits* Wh16 = nullptr,
-                         const vd_bf16_bits* W3 = nullptr) {
+                         int dc_first, hipStream_t s, int split = 0, const vd_bf16_bits* W3 = nullptr, vd_bf16_bits* da16 = nullptr,
+                         const vd_bf16_bits* da16_next = nullptr, const vd_bf16_bits* Wh16 = nullptr) {
   SrcRow a{da_next, 4L * H};
   SrcRow b{Wh, 4L * H};  // B[k][n] = Wh[n][k]
-  if (W3 && K > 0 && !(dh_a && dh_b)) {   // exact-operand split: da_{t+1} stays fp32 in memory, Wh as three bf16 planes
+  if (split && K > 0 && !(dh_a && dh_b)) {   // exact-operand split: da_{t+1} stays fp32 in memory, Wh as three bf16 planes
     EpiLstmBwd<4, 2, false> e{dh_a, dh_b, gates, c_t, c_prev, dc, dc_first, H};   // 128 x 128 tiles: half the A re-reads of the fp32 kernel's 128 x 64
-    if (flags & VD_FLAG_SPLIT9) return launch_gemm_split<9>(N, H, K, da_next, 4L * H, W3, 4L * H, 4L * H * H, e, s);
-    if (flags & VD_FLAG_SPLIT6) return launch_gemm_split<6>(N, H, K, da_next, 4L * H, W3, 4L * H, 4L * H * H, e, s);
+    if (split == 9) return launch_gemm_split<9>(N, H, K, da_next, 4L * H, W3, 4L * H, 4L * H * H, e, s);
+    if (split == 6) return launch_gemm_split<6>(N, H, K, da_next, 4L * H, W3, 4L * H, 4L * H * H, e, s);
     return launch_gemm_split<3>(N, H, K, da_next, 4L * H, W3, 4L * H, 4L * H * H, e, s);
   }
-  if ((flags & VD_FLAG_BF16) && N >= 2048 && K > 0) {
+  if (da16 && K > 0) {
     EpiLstmBwd<2> e{dh_a, dh_b, gates, c_t, c_prev, dc, dc_first, H, da16};
     // shadows on: da_{t+1} and Wh are read as the bf16 rows their producers wrote (half the operand bytes, no conversion
     // while staging, LDS-DMA pipeline); K counts bf16 pairs
@@ -648,12 +621,12 @@ static int lstm_step_bwd(const float* da_next, const float* Wh, int N, int H, in
                                                  reinterpret_cast<const float*>(Wh16), 2L * H, e, s);
     return launch_gemm<CfgBbf16>(N, H, K, 1, a, b, e, s);
   }
-  if (da16 && N >= 2048) {   // bf16 pass, step without a recurrent product (the last one): same shadow, generic kernel
+  if (da16) {   // bf16 pass, step without a recurrent product (the last one): same shadow, generic kernel
     EpiLstmBwd<2> e{dh_a, dh_b, gates, c_t, c_prev, dc, dc_first, H, da16};
     return launch_gemm<CfgB11>(N, H, K, 1, a, b, e, s);
   }
-  if (N >= 2048) {
-    if (use_glds_bwd(N, H) && K > 0) {
+  if (N >= VD_THROUGHPUT_ROWS) {
+    if (vd_lstm_glds_bwd_fits(N, H) && K > 0) {
       // LDS-DMA pipeline: A = da_{t+1} rows, Bt = Wh rows (both contiguous in k = the 4H gate columns).  The two-slot epilogue
       // (loads of two slots in flight before either is consumed: half the serialised round trips) fits the 128-VGPR build with
       // buffer addressing; a step with a recurrent product has at most one incoming-gradient operand
@@ -706,13 +679,12 @@ struct SrcKSel {
     return *reinterpret_cast<const float4*>(p + (long)k * ld + col);
   }
 };
-using EpiLstmFwdTick = EpiLstmFwdT<VD_TICK_EPI_SEQ>;
 struct EpiTickFwd {
   int kind;  // 0 = LSTM cell update, 1 = plain store (+bias)
-  EpiLstmFwdTick f;
+  EpiLstmFwdT<1> f;
   EpiStore<4> s;
   static constexpr bool HAS_DIST = true;      // both kinds finish distributed over the four K-slice waves (gemm_block): no one-wave path is compiled
-  using DOps = EpiLstmFwdTick::DOps;
+  using DOps = EpiLstmFwdT<1>::DOps;
   __device__ __forceinline__ bool dist_ok() const { return true; }
   __device__ __forceinline__ void dist_load(DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
     if (kind == 0) f.dist_load(q, row0, vcol0, lane, grp, M);
@@ -871,15 +843,16 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
                "vd_lstm_forward: N=%d rows x 4H=%d exceed 4 GB per step: split the batch", N, 4 * H);
   hipStream_t s = (hipStream_t)stream;
   const long NH = (long)N * H;
+  // the step kernel of the pass, chosen once: bf16 operands, the exact-operand split (split_core.h) on the fp32 LDS-DMA pipeline's
+  // shapes, that pipeline, or the generic kernel.  All but the last multiply by a transposed copy of Wh made here.
+  const bool bf16 = (flags & VD_FLAG_BF16) && vd_lstm_bf16_fits(N, H);
+  const bool glds = !bf16 && T > 1 && vd_lstm_glds_fwd_fits(N, H);
+  const int split = glds ? vd_split_nprod(flags) : 0;
+  const bool transposed = glds || (bf16 && (T > 1 || h0));
   float* WhT = nullptr;
-  const bool bf16 = (flags & VD_FLAG_BF16) && N >= 2048 && H % 32 == 0;
-  // exact-operand split (split_core.h): the throughput shapes of the fp32 LDS-DMA pipeline only
-  const int split = (!bf16 && (flags & VD_FLAG_SPLIT) && use_glds_fwd(N, H) && T > 1)
-                        ? ((flags & VD_FLAG_SPLIT9) ? 9 : (flags & VD_FLAG_SPLIT6) ? 6 : 3) : 0;
-  const bool glds = (use_glds_fwd(N, H) || bf16) && T > 1;   // both paths multiply by the transposed copy
   VdStreamScratch scr;
   vd_bf16_bits* W3 = nullptr;
-  if (glds) {
+  if (transposed) {
     if (int rc0 = vd_stream_scratch(s, (size_t)4 * H * H * (split ? 10 : bf16 ? 6 : 4), 0, &scr)) return rc0;
     WhT = scr.wht;
     hipLaunchKernelGGL(wh_gate_transpose_kernel, dim3(4 * H / 32, H / 32), dim3(256), 0, s, Wh, WhT, H);
@@ -899,7 +872,7 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
   vd_bf16_shadow_invalidate(gates, (size_t)T * 4 * NH);     // this pass overwrites `gates`: a da shadow registered over it (last backward) is stale
   // ... and READ the shadow of h_{t-1} and a bf16 copy of the transposed weights through the LDS-DMA pipeline
   vd_bf16_bits* WhT16 = nullptr;
-  if (h16 && glds) {
+  if (bf16 && T > 1) {
     WhT16 = reinterpret_cast<vd_bf16_bits*>(scr.wht + (size_t)4 * H * H);
     if (int rc0 = weights_to_bf16(WhT, WhT16, 4L * H * H, s)) return rc0;
   }
@@ -918,21 +891,23 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
     e.H = H;
     e.h16 = h16 ? h16 + t * NH : nullptr;
     int rc;
-    if (bf16 && hp && WhT16 && t > 0)
+    if (!hp)   // first step without h0: no recurrent product
+      rc = lstm_step_fwd(nullptr, Wh, N, H, 0, e, s);
+    else if (bf16 && t > 0)   // the shadow of h_{t-1}
       rc = launch_gemm_glds<CfgF9bf16, false>(N, 4 * H, H / 2, 1, reinterpret_cast<const float*>(h16 + (t - 1) * NH), (long)H / 2,
                                               reinterpret_cast<const float*>(WhT16), (long)H / 2, e, s);
-    else if (bf16 && hp)
+    else if (bf16)            // h0 (fp32)
       rc = launch_gemm<CfgFbf16>(N, 4 * H, H, 1, SrcRow{hp, H}, SrcRow{WhT, H}, e, s);
-    else if (split == 9 && hp)
+    else if (split == 9)
       rc = launch_gemm_split<9>(N, 4 * H, H, hp, (long)H, W3, (long)H, 4L * H * H, e, s);
-    else if (split == 6 && hp)
+    else if (split == 6)
       rc = launch_gemm_split<6>(N, 4 * H, H, hp, (long)H, W3, (long)H, 4L * H * H, e, s);
-    else if (split == 3 && hp)
+    else if (split == 3)
       rc = launch_gemm_split<3>(N, 4 * H, H, hp, (long)H, W3, (long)H, 4L * H * H, e, s);
-    else if (glds && hp)
+    else if (glds)
       rc = launch_gemm_glds<CfgF9, false>(N, 4 * H, H, 1, hp, (long)H, WhT, (long)H, e, s);
     else
-      rc = lstm_step_fwd(hp, Wh, N, H, hp ? H : 0, e, s);
+      rc = lstm_step_fwd(hp, Wh, N, H, H, e, s);
     if (rc) return rc;
   }
   return VD_OK;
@@ -948,10 +923,13 @@ int vd_lstm_backward(const float* Wh, float* gates, const float* c, const float*
   hipStream_t s = (hipStream_t)stream;
   const long NH = (long)N * H;
   if (dc_last && dc_last != dc_work) VD_HIP(hipMemcpyAsync(dc_work, dc_last, NH * sizeof(float), hipMemcpyDeviceToDevice, s));
+  // the step kernels of the pass, chosen once: bf16 operands, the exact-operand split on the fp32 LDS-DMA pipeline's shapes, or fp32
+  const bool bf16 = (flags & VD_FLAG_BF16) && vd_lstm_bf16_fits(N, H);
+  const int split = !bf16 && T > 1 && vd_lstm_glds_bwd_fits(N, H) ? vd_split_nprod(flags) : 0;
   // bf16 pass: the step kernels also write a bf16 copy of da (the other operand of the dWh contraction)
   vd_bf16_bits* da16 = nullptr;
   vd_bf16_bits* Wh16 = nullptr;
-  if ((flags & VD_FLAG_BF16) && N >= 2048 && H % 32 == 0) {
+  if (bf16) {
     if (int rc0 = vd_bf16_shadow_get(1, gates, (size_t)T * 4 * NH, &da16)) return rc0;
     if (T > 1) {
       VdStreamScratch wscr;
@@ -963,7 +941,7 @@ int vd_lstm_backward(const float* Wh, float* gates, const float* c, const float*
     vd_bf16_shadow_invalidate(gates, (size_t)T * 4 * NH);
   }
   const vd_bf16_bits* W3 = nullptr;
-  if (!(flags & VD_FLAG_BF16) && (flags & VD_FLAG_SPLIT) && use_glds_bwd(N, H) && T > 1 && (4 * H) % 32 == 0) {
+  if (split) {
     VdStreamScratch wscr;
     if (int rc0 = vd_stream_scratch(s, (size_t)4 * H * H * 10, 0, &wscr)) return rc0;
     vd_bf16_bits* w3 = reinterpret_cast<vd_bf16_bits*>(wscr.wht + (size_t)4 * H * H);    // (behind the forward pass's transposed copy)
@@ -974,8 +952,8 @@ int vd_lstm_backward(const float* Wh, float* gates, const float* c, const float*
     const bool last = (t == T - 1);
     const float* da_next = last ? nullptr : gates + (long)(t + 1) * 4 * NH;
     const int rc = lstm_step_bwd(da_next, Wh, N, H, last ? 0 : 4 * H, dh_seq ? dh_seq + t * NH : nullptr, (last && dh_last) ? dh_last : nullptr,
-                                 gates + (long)t * 4 * NH, c + t * NH, t ? c + (t - 1) * NH : c0, dc_work, (last && !dc_last) ? 1 : 0, s, flags,
-                                 da16 ? da16 + (long)t * 4 * NH : nullptr, (da16 && !last) ? da16 + (long)(t + 1) * 4 * NH : nullptr, Wh16, W3);
+                                 gates + (long)t * 4 * NH, c + t * NH, t ? c + (t - 1) * NH : c0, dc_work, (last && !dc_last) ? 1 : 0, s, split,
+                                 W3, da16 ? da16 + (long)t * 4 * NH : nullptr, (da16 && !last) ? da16 + (long)(t + 1) * 4 * NH : nullptr, Wh16);
     if (rc) return rc;
   }
   int rc = VD_OK;
@@ -1033,7 +1011,7 @@ static int lstm2_forward_ticks(const vd_lstm2_fwd_t* st, int nstacks, int H, int
         P.b = SrcKSel{S.Wx2, 4L * H, H, 0};
         P.e.kind = 1;
         P.e.s = EpiStore<4>{S.gates2 + (long)t * 4 * NH, 4L * H, S.b2, VD_ACT_NONE, 0};
-        P.e.f = EpiLstmFwdTick{nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, H};
+        P.e.f = EpiLstmFwdT<1>{nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, H};
       }
     }
     if (g.nprob == 0) continue;
@@ -1084,8 +1062,8 @@ int vd_f32_to_bf16(const float* src, vd_bf16_bits* dst, int64_t n, hipStream_t s
 
 int vd_lstm_forward_c16(const vd_bf16_bits* table16, int64_t tab_ld, const int32_t* tok_gather, const float* Wh, vd_bf16_bits* gates16,
                         vd_bf16_bits* h16, float* h_last, float* c, int T, int N, int H, hipStream_t s) {
-  VD_CHECK_ARG(table16 && tok_gather && Wh && gates16 && h16 && h_last && c && T >= 1 && N >= 2048 && H % 128 == 0 && tab_ld % 4 == 0,
-               "vd_lstm_forward_c16: throughput shapes only (N >= 2048, H %% 128 == 0)");
+  VD_CHECK_ARG(table16 && tok_gather && Wh && gates16 && h16 && h_last && c && T >= 1 && vd_lstm_c16_fits(N, H) && tab_ld % 4 == 0,
+               "vd_lstm_forward_c16: throughput shapes only (N >= %ld, H %% 128 == 0)", VD_THROUGHPUT_ROWS);
   VD_CHECK_ARG((long)N * 4 * H * 4 < (1L << 32), "vd_lstm_forward_c16: N x 4H exceeds 4 GB per step");
   const long NH = (long)N * H;
   VdStreamScratch scr;
@@ -1118,7 +1096,7 @@ int vd_lstm_forward_c16(const vd_bf16_bits* table16, int64_t tab_ld, const int32
 
 int vd_lstm_backward_c16(const float* Wh, vd_bf16_bits* gates16, const float* c, const float* dh_last, float* dc_work, int T, int N, int H,
                          hipStream_t s) {
-  VD_CHECK_ARG(Wh && gates16 && c && dh_last && dc_work && T >= 1 && N >= 2048 && H % 128 == 0, "vd_lstm_backward_c16: throughput shapes only");
+  VD_CHECK_ARG(Wh && gates16 && c && dh_last && dc_work && T >= 1 && vd_lstm_c16_fits(N, H), "vd_lstm_backward_c16: throughput shapes only");
   const long NH = (long)N * H;
   VdStreamScratch wscr;
   if (int rc = vd_stream_scratch(s, (size_t)4 * H * H * 6, 0, &wscr)) return rc;

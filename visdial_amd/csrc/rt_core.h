@@ -20,6 +20,7 @@
 
 #include "../../include/visdial_hip.h"
 #include "common.h"
+#include "paths.h"
 
 // lstm.hip: the two-layer wavefront with the pass's arithmetic (flags & VD_FLAG_BF16: bf16 operands on the ticks' MFMAs in a bf16 pass;
 // the C-ABI entry points vd_lstm2_forward / vd_lstm2_backward are these with flags = 0)
@@ -97,6 +98,7 @@ struct Decoder;
 
 struct vd_model {
   vd_model_params p;
+  int flags = 0;   // p.lstmBf16 as VD_FLAG_* (paths.h vd_precision_flags): the arithmetic of every pass
   std::string enc_name, dec_name;
   std::vector<vdrt::Tensor> spec;
   std::map<std::string, int> index;
@@ -428,10 +430,10 @@ struct SeqLSTM {
     // the option dWh kernel's rate, and its workgroups live ~0.1 ms instead of ~0.8 ms -- the index-list kernel is a chain
     // of dependent (row index -> row) loads per K tile whose long-lived workgroups take the third slot of a third of the
     // CUs away from the option-LSTM backward kernels for most of their run.
-    auto dense_fits = [&](long Mrows, long K) { return Mrows % 128 == 0 && (4 * H) % 128 == 0 && K >= 1024; };
+    auto dense_fits = [&](long Mrows, long K) { return vd_tn_kmajor_fits(Mrows, 4 * H, K); };
     // bf16 pass (lstmPrecision = 'bf16', configs[4]): the dense contractions whose shape the bf16 kernel takes (256-row tiles) round both
     // fp32 operands to bf16 in registers and multiply on the bf16 MFMA (gemm_ops.hip: 77 vs 167 us at K = 8 000)
-    auto wg_flags = [&](long Mrows) { return m->p.lstmBf16 == 1 && Mrows % 256 == 0 ? VD_FLAG_BF16 : 0; };
+    auto wg_flags = [&](long Mrows) { return (m->flags & VD_FLAG_BF16) && vd_tn_split_tiles(Mrows, 4 * H) ? VD_FLAG_BF16 : 0; };
     if (by_rows && !(T > 1 && dense_fits(H, (long)(T - 1) * N))) {
       if (rows->n_act1 > 0)
         VD_TRY(vd_gemm_tn_rows_acc(h, H, rows->prev1, gates, 4 * H, rows->act1, dWh, 4 * H, (int)H, (int)(4 * H), rows->n_act1, s));

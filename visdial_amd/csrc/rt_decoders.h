@@ -78,14 +78,13 @@ struct Disc : Decoder {
     VD_TRY(ws_get(m, "opt.scores", (size_t)N * O, &scores));
     VD_TRY(ws_get(m, "crit.loss_rows", (size_t)N, &loss_rows));
     float* Wopt = Wp(m, "opt.W");
-    const int flags = m->p.lstmBf16 == 1 ? VD_FLAG_BF16 : m->p.lstmBf16 == 9 ? VD_FLAG_SPLIT9 : m->p.lstmBf16 == 6 ? VD_FLAG_SPLIT6
-                      : m->p.lstmBf16 == 3 ? VD_FLAG_SPLIT3 : 0;
+    const int flags = m->flags;
     VD_TRY(fork_stream(m, s, se));
     float* enc_out = nullptr;
     VD_TRY(vd_gemm_nn(Wp(m, "embed"), E, Wopt, 4 * H, Wp(m, "opt.b"), table, 4 * H, (int)V + 1, (int)(4 * H), (int)E, 0, s));
     // bf16 pass at a throughput shape: COMPACT state (common.h) -- gates / da only as bf16 (in the first half of `gates`), the
     // projection table as bf16 rows, h as bf16 plus the last step's fp32 state; c stays fp32
-    const bool c16 = (flags & VD_FLAG_BF16) && NO >= 2048 && H % 128 == 0;
+    const bool c16 = (flags & VD_FLAG_BF16) && vd_lstm_c16_fits(NO, (int)H);
     vd_bf16_bits *gates16 = reinterpret_cast<vd_bf16_bits*>(gates), *h16 = reinterpret_cast<vd_bf16_bits*>(h), *table16 = nullptr;
     float* h_last = nullptr;
     if (c16) {

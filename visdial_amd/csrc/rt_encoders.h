@@ -20,7 +20,7 @@ struct Encoder {
 
 // arithmetic of the encoder's recurrent products: bf16 operands in a bf16 pass (lstmPrecision = 'bf16', BASELINE configs[4] "bf16 LSTM
 // step"), fp32 MFMA otherwise (the exact-split modes of the option recurrence leave the encoder on fp32: it is not on their critical path)
-inline int tick_flags(const vd_model* m) { return m->p.lstmBf16 == 1 ? VD_FLAG_BF16 : 0; }
+inline int tick_flags(const vd_model* m) { return m->flags & VD_FLAG_BF16; }
 
 inline int causal_mask(vd_model* m, int B, int R, uint8_t** out) {
   // model.lua:280-294: mask[i][j] = 0 iff j <= i, tiled over the batch ([N x R] bytes, 1 = hidden)
@@ -306,8 +306,7 @@ struct SANBlock {
     for (int i = 0; i < L; ++i) VD_TRY(drop_mask(m, "iqc" + hop_sfx(i), (size_t)N * S2 * K, 0.5f, si, &m2[i]));
     sc = m1 ? 2.f : 1.f;
     // split9 pass: the attention's dense products run on the exact split, from the materialised per-round image tensor (attention.hip)
-    static const int img_split_on = [] { const char* e = getenv("VD_SPLIT_IMG"); return e ? atoi(e) : 1; }();     // (A/B switch)
-    iflags = (m->p.lstmBf16 == 9 && img_split_on && (long)N * S2 >= 128 && H % 16 == 0 && K % 16 == 0) ? VD_FLAG_SPLIT9 : 0;
+    iflags = (m->flags & VD_FLAG_SPLIT9) && vd_img_split_ok((long)N * S2, (int)H, (int)K) ? VD_FLAG_SPLIT9 : 0;
     xdrop = nullptr;
     if (iflags) {
       VD_TRY(ws_get(m, "att.xdrop", (size_t)N * S2 * H, &xdrop));

@@ -134,8 +134,11 @@ int vd_model_create(const vd_model_params* p, const char* encoder, const char* d
   VD_CHECK_ARG(!(has(en, "hre") && use_im) || (p->imgEmbedSize > 0 && p->imgEmbedSize % 4 == 0),
                "vd_model_create: imgEmbedSize must be a positive multiple of 4 for hre*-ques-im-hist");
   VD_CHECK_ARG(p->dropout >= 0.f && p->dropout < 1.f, "vd_model_create: dropout must lie in [0, 1)");
+  const int flags = vd_precision_flags(p->lstmBf16);
+  VD_CHECK_ARG(flags >= 0, "vd_model_create: lstmBf16 must be 0, 1, 3, 6 or 9 (got %d)", p->lstmBf16);
   vd_model* m = new vd_model();
   m->p = *p;
+  m->flags = flags;
   if (m->p.numAttentionLayers < 1 || has(en, "lf-att")) m->p.numAttentionLayers = 1;   // (lf-att-ques-im-hist.lua:49 hard-codes one hop)
   if (m->p.numLayers < 1) m->p.numLayers = 2;        // opts.lua:27
   m->enc_name = encoder;

@@ -22,24 +22,13 @@
 // bigger wave tiles (64 x 128 per wave: half the LDS-DMA bytes and fragment reads per MFMA) do not change it.
 #pragma once
 #include "gemm_core.h"
+#include "paths.h"
 
 typedef __bf16 vd_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float vd_f32x4 __attribute__((ext_vector_type(4)));
 
 // v (8 consecutive k of one row) -> hi / mid / lo planes
 __device__ __forceinline__ void vd_split3(const float4& u, const float4& w, vd_bf16x8& hi, vd_bf16x8& mid, vd_bf16x8& lo) {
-#ifdef VD_PROBE_NOSPLIT
-  // PROBE build only (`make variant NAME=nosplit DEFS=-DVD_PROBE_NOSPLIT`; results are garbage): the operand bits reinterpreted as bf16 planes,
-  // no conversion -- the instruction stream a kernel over PRE-SPLIT planes would run (optimistic: it moves 4 instead of 6 bytes per value)
-  // (exponent fields forced to 0x7E: random signs and mantissas with magnitudes in [0.5, 1) -- bit patterns of ordinary operands, so the
-  //  matrix pipe draws what it draws on real data instead of saturating to NaN; one v_and_or_b32 per register)
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 a = (__builtin_bit_cast(u32x4, u) & 0x807F807Fu) | 0x3F003F00u, b = (__builtin_bit_cast(u32x4, w) & 0x807F807Fu) | 0x3F003F00u;
-  hi = __builtin_bit_cast(vd_bf16x8, a);
-  mid = __builtin_bit_cast(vd_bf16x8, b);
-  lo = __builtin_bit_cast(vd_bf16x8, a ^ 0x00150015u);
-  return;
-#endif
   const float v[8] = {u.x, u.y, u.z, u.w, w.x, w.y, w.z, w.w};
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -96,6 +85,7 @@ struct SplitCfg {
 #ifndef VD_SPLIT_CG
 #define VD_SPLIT_CG 2
 #endif
+static_assert(VD_SPLIT_CG >= 1 && VD_SPLIT_CG <= 8 && 8 % VD_SPLIT_CG == 0, "the XCD grid is VD_SPLIT_CG x (8 / VD_SPLIT_CG)");
 __device__ __forceinline__ bool split_tile_of(int bid, int nwg, int tiles_m, int tiles_n, int& tile_m, int& tile_n) {
   constexpr int CG = VD_SPLIT_CG, RG = 8 / CG;
   if ((tiles_n % CG) == 0 && tiles_n >= 8) {
@@ -250,6 +240,7 @@ struct SplitTnCfg {
   static constexpr int STAGE = ATILE + BTILE;                     // 24 KB
   static constexpr int LDS_BYTES = 2 * STAGE;                     // 48 KB: two workgroups per CU (the registers allow no more)
 };
+static_assert(SplitTnCfg::BM == VD_SPLIT_TN_BM && SplitTnCfg::BN == VD_SPLIT_TN_BN, "paths.h vd_tn_split_tiles");
 
 template <int NPROD>
 __global__ void __launch_bounds__(256, 2)
