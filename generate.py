@@ -29,6 +29,9 @@ def main():
     ap.add_argument('-maxThreads', '--maxThreads', type=int, default=50)
     ap.add_argument('-beamBatch', '--beamBatch', type=int, default=0,
                     help='> 0: beam search of that many dialogs at once, all on the device (0 = one dialog at a time, host bookkeeping)')
+    ap.add_argument('-sampleBatch', '--sampleBatch', type=int, default=0,
+                    help='> 0 (with -sampleWords 1): sample that many dialogs at once, all on the device (0 = one dialog at a time)')
+    ap.add_argument('-seed', '--seed', type=int, default=1234, help='seed of the sampling generator (numpy RandomState)')
     ap.add_argument('-gpuid', '--gpuid', type=int, default=0)
     ap.add_argument('-host', '--host', default='python', choices=['python', 'native'],
                     help="'native' drives the model-level C ABI (what lua/model.lua calls)")
@@ -51,7 +54,8 @@ def main():
     restore_weights(model, saved, a['paramOrder'] or None)
     answers = model.generateAnswers(dl, 'val', dict(beamSize=a['beamSize'], beamLen=a['beamLen'],
                                                     maxThreads=a['maxThreads'], sampleWords=a['sampleWords'],
-                                                    temperature=a['temperature'], beamBatch=a['beamBatch']))
+                                                    temperature=a['temperature'], beamBatch=a['beamBatch'],
+                                                    sampleBatch=a['sampleBatch'], seed=a['seed']))
     os.makedirs(a['resultPath'], exist_ok=True)
     path = os.path.join(a['resultPath'], 'results.json')
     utils.writeJSON(path, {'opts': a, 'data': answers})

@@ -35,7 +35,8 @@ const char* vd_last_error(void);
 /* Bumped whenever an exported symbol is removed or the meaning of an argument changes; hosts compare it with the VD_ABI_VERSION they
  * were written against right after loading (visdial_amd/_lib.py, lua/visdial_ffi.lua).  2 = round 4's surface: vd_tune_set /
  * vd_tune_clear / vd_lstm_seq_status removed, vd_model_params.lstmBf16 also takes 3 / 6 / 9 (exact-operand split).  Adding entry points
- * does not bump it: 94 entry points (56 operator-level, 31 model-level, 7 vd_comm_*), vd_beam_* and vd_model_beam_search added under 2. */
+ * does not bump it: 97 entry points (58 operator-level, 32 model-level, 7 vd_comm_*), vd_beam_* / vd_model_beam_search and
+ * vd_sample_* / vd_model_sample added under 2. */
 #define VD_ABI_VERSION 2
 int vd_abi_version(void);
 int vd_device_count(int* count);
@@ -259,6 +260,21 @@ int vd_beam_select_rows(float* cur, const float* stepped, const int32_t* src, in
 int vd_beam_finish(int groups, int k, int beam_len, const int32_t* hist, const double* scores, const double* best_score,
                    const int32_t* best_len, const int32_t* best_hist, int32_t* out_tokens, double* out_scores, void* stream);
 
+/* ---- batched temperature sampling (Model:generateAnswers with sampleWords = 1, model.lua:576-613; csrc/sample.hip states the
+ *      rule).  One hypothesis row per QA round; the token history is int32 [rows x (beam_len + 1)] with column 0 = <START>, the
+ *      log-likelihood fp64 [rows], status one int32 (0 = every draw made).  The uniforms are the host's: no device RNG.
+ *   init   history <START>, 0, ...; tok = <START>; log-likelihood 0; status 0
+ *   draw   step s in [1, beam_len]: nn.LogSoftMax of logits [rows x ld] (V valid columns; bit-identical to vd_log_softmax_rows; a
+ *          row whose token tok[r] is 0 is the all-zero row of MaskZero(LogSoftMax)) and the inverse-CDF draw of
+ *          RandomState.choice(V, p) from the fp64 weights exp(logp / temperature) with the uniform uniforms[r] in [0, 1) (not
+ *          checked here): history column s and tok[r] = the drawn id, the log-likelihood adds its logp until the row has
+ *          emitted <END> (the <END> counts).  A row whose weights all underflow sets status = 1 and draws nothing (token 0).
+ *          temperature must be finite and > 0; logits are not written. */
+int vd_sample_init(int64_t rows, int beam_len, int start_token, int32_t* hist, int32_t* tok, double* loglik, int32_t* status,
+                   void* stream);
+int vd_sample_draw(const float* logits, int64_t ld, int64_t rows, int V, int32_t* tok, const double* uniforms, double temperature,
+                   int step, int beam_len, int end_token, int32_t* hist, double* loglik, int32_t* status, void* stream);
+
 /* ---- wrapperdW:clamp(-5,5) + adam (model.lua:96-99; model_utils/optim_updates.lua:62-91) ---- */
 int vd_clamp_adam(float* w, float* g, float* m, float* v, int64_t n, float gscale, float clip, float beta1,
                   float beta2, float eps, float step, void* stream);
@@ -369,6 +385,16 @@ int vd_model_decode_select(vd_model* m, const int32_t* src, int n_keep);
  * zero-padded), host_scores [N] its fp64 score.  Same answers as the host loop over decode_begin / step / select. */
 int vd_model_beam_search(vd_model* m, int beam_size, int beam_len, int start_token, int end_token, int32_t* host_tokens,
                          double* host_scores);
+/* temperature sampling of Model:generateAnswers (sampleWords = 1, model.lua:576-613) for EVERY round of the last vd_model_encode
+ * batch at once, on the device (the vd_sample_* kernels above): N = B*R rows, all beam_len steps (the reference samples through
+ * <END>) enqueued without a host synchronisation after one upload of the host's uniforms [beam_len x N] (step-major, row =
+ * dialog * R + round, each in [0, 1)), then one copy back.  host_tokens [N x (beam_len + 1)] = <START> and the sampled ids,
+ * host_loglik [N] the fp64 log-likelihood through the first <END>.  The tokens of the host loop over decode_step drawing with
+ * RandomState.choice from the same uniforms, up to draws within rounding of a CDF boundary.  Argument errors: no
+ * vd_model_encode first, beam_len < 1, a temperature that is not finite and > 0, a uniform outside [0, 1), and a row whose
+ * weights exp(logp / temperature) all underflow (nothing to draw from; the host path fails there too). */
+int vd_model_sample(vd_model* m, int beam_len, int start_token, int end_token, double temperature, const double* host_uniforms,
+                    int32_t* host_tokens, double* host_loglik);
 int vd_model_scores(vd_model* m, float* host_scores, int64_t n);        /* [N x O] of the last forward / retrieve */
 int vd_model_ranks(vd_model* m, int use_gt, int32_t* host_ranks);       /* utils.computeRanks (utils.lua:106-128) */
 /* decoder disc: rows the option LSTM executed for the batch of the LAST STEP (before any step: of the uploaded batch) vs the N * O

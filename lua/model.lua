@@ -273,6 +273,11 @@ end
 -- live hypotheses -> log-probabilities on the host), vd_model_decode_select (beam back-pointers).
 -- params.beamBatch = B > 0: the beam search of dialogs [s, s+B) runs on the device for every round of the chunk at once
 -- (vd_model_beam_search after one vd_model_encode per chunk); the records are the same.
+-- params.sampleBatch = B > 0 (with sampleWords = 1): the same for temperature sampling (vd_model_sample).  The uniforms still come
+-- from the torch generator that the per-dialog torch.multinomial loop draws from, one double per draw in that loop's order
+-- (dialog, step, round); on the same generator state the records are the same up to draws within about 1e-6 of a CDF boundary
+-- (the per-dialog loop normalises fp32 weights, the device fp64 ones).  That a real Torch7 multinomial consumes exactly one
+-- uniform per draw this way is the behaviour of tests/luavm's torch stub, not checked against Torch7.
 function Model:generateAnswers(dataloader, dtype, params)
     if self.params.decoder == 'disc' then error('Sampling/beam search only for generative model') end
     params = params or {}
@@ -280,6 +285,10 @@ function Model:generateAnswers(dataloader, dtype, params)
     local beamBatch = params.beamBatch or 0
     if beamBatch > 0 and sampleWords then
         error('beamBatch > 0 is batched beam search; sampling (sampleWords = 1) runs on the host: use beamBatch = 0')
+    end
+    local sampleBatch = params.sampleBatch or 0
+    if sampleBatch > 0 and not sampleWords then
+        error('sampleBatch > 0 is batched sampling: it needs sampleWords = 1')
     end
     local temperature = params.temperature or 1.0
     local beamSize, beamLen = params.beamSize or 5, params.beamLen or 20
@@ -308,6 +317,42 @@ function Model:generateAnswers(dataloader, dtype, params)
                 for iter = 1, R do
                     local ans, row = {}, ((b - 1) * R + iter - 1) * beamLen   -- row = dialog * R + round
                     for t = 1, beamLen do ans[t] = toks[row + t - 1] end
+                    threadAnswers[#threadAnswers + 1] = {question = words(batch['ques_fwd'][{b, iter}]), answer = words(torch.LongTensor(ans))}
+                end
+                local convId = first + b - 1
+                answerTable[#answerTable + 1] = {image_id = ids and ids[convId] or convId, dialog = threadAnswers}
+            end
+        end
+        self:setMode(true)
+        return answerTable
+    end
+    if sampleBatch > 0 then
+        local ids = dataloader['unique_img_' .. dtype]
+        local function words(ids_) return utils.idToWords(ids_, dataloader.ind2word) end
+        for first = 1, numThreads, sampleBatch do
+            local last = math.min(first + sampleBatch - 1, numThreads)
+            local inds = {}
+            for convId = first, last do inds[#inds + 1] = convId end
+            local batch = dataloader:getIndexData(torch.LongTensor(inds), self.params, dtype)
+            local B, R = batch['ques_fwd']:size(1), batch['ques_fwd']:size(2)
+            self:upload({ques_fwd = batch['ques_fwd'], hist = batch['hist'], img_feat = batch['img_feat']})
+            self.havePrefetched = false
+            vd.call('vd_model_encode', self.h)
+            local n = B * R
+            local u = torch.DoubleTensor(B, beamLen, R):uniform()       -- the per-dialog loop's draws: dialog, step, round
+            local us = ffi.new('double[?]', beamLen * n)
+            for b = 1, B do
+                for t = 1, beamLen do
+                    for iter = 1, R do us[(t - 1) * n + (b - 1) * R + iter - 1] = u[{b, t, iter}] end   -- [step x row]
+                end
+            end
+            local toks, lhood = ffi.new('int32_t[?]', n * (beamLen + 1)), ffi.new('double[?]', n)
+            vd.call('vd_model_sample', self.h, beamLen, startToken, endToken, temperature, us, toks, lhood)
+            for b = 1, B do
+                local threadAnswers = {}
+                for iter = 1, R do
+                    local ans, row = {}, ((b - 1) * R + iter - 1) * (beamLen + 1)   -- row = dialog * R + round
+                    for t = 1, beamLen + 1 do ans[t] = toks[row + t - 1] end
                     threadAnswers[#threadAnswers + 1] = {question = words(batch['ques_fwd'][{b, iter}]), answer = words(torch.LongTensor(ans))}
                 end
                 local convId = first + b - 1

@@ -15,6 +15,7 @@ _p = C.c_void_p
 _i = C.c_int
 _l = C.c_int64
 _f = C.c_float
+_d = C.c_double
 _u64 = C.c_uint64
 
 class Lstm2Fwd(C.Structure):
@@ -102,6 +103,8 @@ PROTOTYPES = {
     "vd_beam_advance": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "vd_beam_select_rows": [_p, _p, _p, _l, _i, _i, _p],
     "vd_beam_finish": [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "vd_sample_init": [_l, _i, _i, _p, _p, _p, _p, _p],
+    "vd_sample_draw": [_p, _l, _l, _i, _p, _p, _d, _i, _i, _i, _p, _p, _p, _p],
     "vd_clamp_adam": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _p],
     # model-level entry points (csrc/runtime.hip)
     "vd_model_create": [C.POINTER(ModelParams), C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)],
@@ -135,6 +138,7 @@ PROTOTYPES = {
     "vd_model_decode_step": [_p, _p, _p],
     "vd_model_decode_select": [_p, _p, _i],
     "vd_model_beam_search": [_p, _i, _i, _i, _i, _p, _p],
+    "vd_model_sample": [_p, _i, _i, _i, _d, _p, _p, _p],
     "vd_model_update": [_p, _f],
     "vd_model_learning_rate": [_p, C.POINTER(C.c_double), _i],
     "vd_model_scores": [_p, _p, _l],

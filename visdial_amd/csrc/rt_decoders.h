@@ -18,6 +18,7 @@ struct Decoder {
   virtual int gen_step(vd_model*, const int32_t*, float*) { return no_gen(); }
   virtual int gen_select(vd_model*, const int32_t*, int) { return no_gen(); }
   virtual int gen_beam_search(vd_model*, int, int, int, int, int32_t*, double*) { return no_gen(); }
+  virtual int gen_sample(vd_model*, int, int, int, double, const double*, int32_t*, double*) { return no_gen(); }
   static int no_gen() {
     vd_set_error("sampling / beam search only for the generative decoder (model.lua:436-438)");
     return VD_ERR_STATE;
@@ -207,6 +208,8 @@ int Gen_begin(Gen* g, vd_model* m, const int32_t* rounds, int n);
 int Gen_step(Gen* g, vd_model* m, const int32_t* tokens, float* host_logp);
 int Gen_select(Gen* g, vd_model* m, const int32_t* src, int n_keep);
 int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end, int32_t* host_tokens, double* host_scores);
+int Gen_sample(Gen* g, vd_model* m, int L, int start, int end, double T, const double* host_u, int32_t* host_tokens,
+               double* host_loglik);
 
 struct Gen : Decoder {
   int gen_begin(vd_model* m, const int32_t* r, int n) override { return Gen_begin(this, m, r, n); }
@@ -214,6 +217,9 @@ struct Gen : Decoder {
   int gen_select(vd_model* m, const int32_t* src, int k) override { return Gen_select(this, m, src, k); }
   int gen_beam_search(vd_model* m, int k, int L, int st, int en, int32_t* t, double* sc) override {
     return Gen_beam_search(this, m, k, L, st, en, t, sc);
+  }
+  int gen_sample(vd_model* m, int L, int st, int en, double T, const double* u, int32_t* t, double* ll) override {
+    return Gen_sample(this, m, L, st, en, T, u, t, ll);
   }
   std::vector<SeqLSTM> rnn;
   long E = 0, H = 0, V = 0, Vp = 0;
@@ -518,6 +524,62 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
   VD_HIP(hipStreamSynchronize(s));
   memcpy(host_tokens, staged.data(), (size_t)G * L * 4);
   memcpy(host_scores, staged.data() + tok_bytes, (size_t)G * 8);
+  return VD_OK;
+}
+
+// Model:generateAnswers' temperature sampling (model.lua:576-613) for all N rounds of the last vd_model_encode batch at once:
+// hypothesis row i = round i.  The host's uniforms [L x N] go up in one copy; per step, on s_main only: embedding gather ->
+// LSTM stack -> vocabulary GEMM -> fused log-softmax + inverse-CDF draw (csrc/sample.hip) -> the stepped state becomes the
+// current one (decoderConnect, gen.lua:63-68).  The sampled tokens never leave the device; history, log-likelihoods and the
+// status word share one buffer and come back in ONE copy after the last step.
+inline int Gen_sample(Gen* g, vd_model* m, int L, int start, int end, double T, const double* host_u, int32_t* host_tokens,
+                      double* host_loglik) {
+  VD_CHECK_ARG(m->gen_enc_out && m->N > 0, "vd_model_sample: call vd_model_encode first");
+  VD_CHECK_ARG(host_u && host_tokens && host_loglik, "vd_model_sample: bad arguments");
+  VD_CHECK_ARG(L >= 1, "vd_model_sample: beam_len = %d must be >= 1", L);
+  VD_CHECK_ARG(std::isfinite(T) && T > 0, "vd_model_sample: temperature %g must be finite and > 0", T);
+  const int n = m->N;
+  for (long i = 0; i < (long)L * n; ++i)
+    VD_CHECK_ARG(host_u[i] >= 0.0 && host_u[i] < 1.0, "vd_model_sample: uniform %ld = %g is outside [0, 1)", i, host_u[i]);
+  std::vector<int32_t> rounds(n);
+  for (int i = 0; i < n; ++i) rounds[i] = i;
+  VD_TRY(Gen_begin(g, m, rounds.data(), n));
+  hipStream_t s = m->s_main;
+  const long H = g->H, E = g->E, V = g->V, Vp = g->Vp;
+  const size_t cols = (size_t)L + 1, hist_bytes = ((size_t)n * cols * 4 + 7) / 8 * 8, out_bytes = hist_bytes + (size_t)n * 8 + 8;
+  uint8_t* out;
+  double* u;
+  int32_t* tok;
+  VD_TRY(ws_get(m, "sample.out", out_bytes, &out));
+  VD_TRY(ws_get(m, "sample.u", (size_t)L * n, &u));
+  VD_TRY(ws_get(m, "sample.tok", (size_t)n, &tok));
+  int32_t* hist = reinterpret_cast<int32_t*>(out);
+  double* loglik = reinterpret_cast<double*>(out + hist_bytes);
+  int32_t* status = reinterpret_cast<int32_t*>(out + hist_bytes + (size_t)n * 8);
+  VD_HIP(hipMemcpyAsync(u, host_u, (size_t)L * n * 8, hipMemcpyHostToDevice, s));
+  VD_TRY(vd_sample_init(n, L, start, hist, tok, loglik, status, s));
+  VD_TRY(vd_memset(Wp(m, "embed"), 0, E * 4, s));                                   // LookupTableMaskZero pad row
+  for (int step = 1; step <= L; ++step) {
+    float* logits;
+    VD_TRY(gen_forward(g, m, tok, n, &logits));
+    VD_TRY(vd_sample_draw(logits, Vp, n, (int)V, tok, u + (size_t)(step - 1) * n, T, step, L, end, hist, loglik, status, s));
+    for (size_t l = 0; l < g->rnn.size(); ++l) {
+      float *h, *c;
+      VD_TRY(ws_get(m, "gen.h" + std::to_string(l), (size_t)n * H, &h));
+      VD_TRY(ws_get(m, "gen.c" + std::to_string(l), (size_t)n * H, &c));
+      VD_TRY(vd_memcpy_d2d(h, g->rnn[l].out_at(0), (long)n * H * 4, s));
+      VD_TRY(vd_memcpy_d2d(c, g->rnn[l].cell_at(0), (long)n * H * 4, s));
+    }
+  }
+  std::vector<uint8_t> staged(out_bytes);
+  VD_HIP(hipMemcpyAsync(staged.data(), out, out_bytes, hipMemcpyDeviceToHost, s));
+  VD_HIP(hipStreamSynchronize(s));
+  int32_t st;
+  memcpy(&st, staged.data() + hist_bytes + (size_t)n * 8, 4);
+  VD_CHECK_ARG(st == 0, "vd_model_sample: every weight exp(logp / temperature) of a row underflowed at temperature %g: nothing to sample "
+               "from (the per-dialog path fails there too)", T);
+  memcpy(host_tokens, staged.data(), (size_t)n * cols * 4);
+  memcpy(host_loglik, staged.data() + hist_bytes, (size_t)n * 8);
   return VD_OK;
 }
 

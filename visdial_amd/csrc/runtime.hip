@@ -549,6 +549,12 @@ int vd_model_beam_search(vd_model* m, int beam_size, int beam_len, int start_tok
   VdRange r("vd_model_beam_search");
   return m->dec->gen_beam_search(m, beam_size, beam_len, start_token, end_token, host_tokens, host_scores);
 }
+int vd_model_sample(vd_model* m, int beam_len, int start_token, int end_token, double temperature, const double* host_uniforms,
+                    int32_t* host_tokens, double* host_loglik) {
+  VD_CHECK_ARG(m, "vd_model_sample: null model");
+  VdRange r("vd_model_sample");
+  return m->dec->gen_sample(m, beam_len, start_token, end_token, temperature, host_uniforms, host_tokens, host_loglik);
+}
 
 // waits for the loss of the last vd_model_forward_backward: disc = mean cross-entropy over the rounds, gen = summed
 // NLL over the non-pad answer tokens (SequencerCriterion of ClassNLLCriterion, model.lua:32-36)

@@ -386,6 +386,35 @@ class Model(SplitEval):
         ops.beam_finish(G, k, L, hist[cur], scores, best_score, best_len, best_hist, out_tok, out_score)
         return out_tok.cpu().numpy(), out_score.cpu().numpy()
 
+    def _gen_sample(self, beamLen, startToken, endToken, temperature, uniforms):
+        """the batched temperature sampling (sampleBatch > 0, model.lua:576-613) of every round of the last `_gen_encode` batch on
+        the device with the host's uniforms [beamLen x N]: per step the decoder step (decoders/gen.py step_logits) -> fused
+        log-softmax + inverse-CDF draw -> the stepped state becomes the current one, the tokens staying on the device.  Returns
+        (tokens [N x (beamLen + 1)], fp64 log-likelihoods [N]) on the host."""
+        g, L, V, H = self._gen, int(beamLen), self.params['vocabSize'], self.params['rnnHiddenSize']
+        n = g['encOut'].shape[0]
+        u = np.ascontiguousarray(uniforms, dtype=np.float64)
+        if u.shape != (L, n) or not ((u >= 0) & (u < 1)).all():
+            raise ValueError('uniforms must be [beamLen x N] = [%d x %d] in [0, 1)' % (L, n))
+        if not (math.isfinite(temperature) and temperature > 0):
+            raise ValueError('temperature %g must be finite and > 0' % temperature)
+        self._gen_begin(np.arange(n, dtype=np.int32))                          # row i = round i
+        i32 = dict(dtype=torch.int32, device=self.device)
+        tok, hist, status = torch.empty(1, n, **i32), torch.empty(n, L + 1, **i32), torch.empty(1, **i32)
+        loglik = torch.empty(n, dtype=torch.float64, device=self.device)
+        u_dev = torch.from_numpy(u).to(self.device)
+        ops.sample_init(L, startToken, hist, tok, loglik, status)
+        for step in range(1, L + 1):
+            logits, stepped = self.decoder.step_logits(tok, g['hidden'])
+            ops.sample_draw(logits, V, tok, u_dev[step - 1], temperature, step, L, endToken, hist, loglik, status)
+            for (h, c), (h_new, c_new) in zip(g['hidden'], stepped):            # decoderConnect (gen.lua:63-68)
+                ops.copy_2d(h, H, h_new, H, n, H)
+                ops.copy_2d(c, H, c_new, H, n, H)
+        if int(status.item()) != 0:
+            raise ValueError('every weight exp(logp / temperature) of a row underflowed at temperature %g: nothing to sample from'
+                             % temperature)
+        return hist.cpu().numpy(), loglik.cpu().numpy()
+
     # ------------------------------------------------------------------ test / checkpoint helpers
     def get_parameters_dict(self):
         return self.fp.to_host('w')

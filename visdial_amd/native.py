@@ -322,6 +322,19 @@ class NativeModel(SplitEval):
              scores.ctypes.data)
         return tokens, scores
 
+    def _gen_sample(self, beamLen, startToken, endToken, temperature, uniforms):
+        """the batched temperature sampling (sampleBatch > 0) of every round of the last `_gen_encode` batch with the host's
+        uniforms [beamLen x N]: vd_model_sample.  Returns (tokens [N x (beamLen + 1)], fp64 log-likelihoods [N])."""
+        N, L = int(self._N), int(beamLen)
+        u = np.ascontiguousarray(uniforms, dtype=np.float64)
+        if u.shape != (L, N):
+            raise ValueError('uniforms must be [beamLen x N] = [%d x %d], got %s' % (L, N, u.shape))
+        tokens = np.zeros((N, L + 1), np.int32)
+        loglik = np.zeros(N, np.float64)
+        call("vd_model_sample", self.h, L, int(startToken), int(endToken), float(temperature), u.ctypes.data, tokens.ctypes.data,
+             loglik.ctypes.data)
+        return tokens, loglik
+
     def option_rows(self):
         """(rows the option LSTM executes, N * O candidates) of the current batch: the upload de-duplicates candidates"""
         a, b = C.c_int64(), C.c_int64()

@@ -354,6 +354,19 @@ def beam_finish(groups, k, L, hist, scores, best_score, best_len, best_hist, out
          _p(best_hist, I32), _p(out_tokens, I32), _p(out_scores, F64), _stream())
 
 
+# ---------------------------------------------------------------- batched temperature sampling (model.lua:576-613; csrc/sample.hip)
+def sample_init(L, start, hist, tok, loglik, status):
+    """history [rows x (L + 1)] = <START>, 0, ...; tok = <START>; log-likelihood 0; status 0"""
+    call("vd_sample_init", hist.shape[0], int(L), int(start), _p(hist, I32), _p(tok, I32), _p(loglik, F64), _p(status, I32), _stream())
+
+
+def sample_draw(logits, V, tok, u, temperature, step, L, end, hist, loglik, status):
+    """fused nn.LogSoftMax + the inverse-CDF draw of RandomState.choice from exp(logp / temperature) of every row with the host's
+    uniforms u [rows] (fp64, device): history column `step` and tok = the drawn ids, the log-likelihood adds their logp until <END>"""
+    call("vd_sample_draw", _p(logits, F32), logits.stride(0), logits.shape[0], V, _p(tok, I32), _p(u, F64), float(temperature),
+         int(step), int(L), int(end), _p(hist, I32), _p(loglik, F64), _p(status, I32), _stream())
+
+
 def zero(t):
     """t[...] = 0 through vd_memset (hipMemsetAsync on the current stream); contiguous tensors only"""
     call("vd_memset", _p(t), 0, t.numel() * t.element_size(), _stream())

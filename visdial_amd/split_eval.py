@@ -6,7 +6,8 @@ Model:generateAnswers the four device steps `_gen_encode(batch)`, `_gen_begin(ro
 `_gen_select(src, n_keep)` (= vd_model_encode / decode_begin / decode_step / decode_select of the model-level ABI), and for the
 batched beam search (params beamBatch > 0) `_gen_beam(beamSize, beamLen, startToken, endToken) -> (tokens [N x beamLen], scores
 [N])` over every round of the last `_gen_encode` batch (= vd_model_beam_search; the operator-level host composes the vd_beam_*
-kernels)."""
+kernels), and for batched sampling (params sampleBatch > 0) `_gen_sample(beamLen, startToken, endToken, temperature, uniforms
+[beamLen x N]) -> (tokens [N x (beamLen + 1)], log-likelihoods [N])` (= vd_model_sample; vd_sample_* for the operator-level host)."""
 import math
 
 import numpy as np
@@ -96,7 +97,10 @@ class SplitEval(object):
         exactly as the reference drives it from the host: the decoder step (embedding, LSTM stack, vocabulary
         projection, log-softmax) runs on the device for all hypotheses at once, candidate bookkeeping is host
         control flow.  params beamBatch = B > 0: the beam search of dialogs [s, s+B) runs together on the device, every round of
-        the chunk at once (one encode + one `_gen_beam` per chunk); same records.  Returns [{image_id, dialog: [{question, answer}...]}]."""
+        the chunk at once (one encode + one `_gen_beam` per chunk); same records.  params sampleBatch = B > 0 (with sampleWords = 1):
+        the same for temperature sampling (one encode + one `_gen_sample` per chunk); the host still draws every uniform, in the
+        per-dialog loop's order, so the records are the same up to draws within rounding of a CDF boundary.
+        Returns [{image_id, dialog: [{question, answer}...]}]."""
         if self.params['decoder'] == 'disc':
             raise SystemExit('Sampling/beam search only for generative model')
         params = params or {}
@@ -104,6 +108,9 @@ class SplitEval(object):
         beamBatch = int(params.get('beamBatch', 0) or 0)
         if beamBatch > 0 and sampleWords:
             raise ValueError('beamBatch > 0 is batched beam search; sampling (sampleWords = 1) runs on the host: use beamBatch = 0')
+        sampleBatch = int(params.get('sampleBatch', 0) or 0)
+        if sampleBatch > 0 and not sampleWords:
+            raise ValueError('sampleBatch > 0 is batched sampling: it needs sampleWords = 1')
         temperature = float(params.get('temperature', 1.0))
         beamSize, beamLen = int(params.get('beamSize', 5)), int(params.get('beamLen', 20))
         startToken, endToken = dataloader.word2ind['<START>'], dataloader.word2ind['<END>']
@@ -120,6 +127,21 @@ class SplitEval(object):
                 R = batch['ques_fwd'].shape[1]
                 self._gen_encode(batch)
                 tokens, _ = self._gen_beam(beamSize, beamLen, startToken, endToken)   # row = dialog * R + round
+                for i, convId in enumerate(convIds):
+                    threadAnswers = [{'question': utils.idToWords(batch['ques_fwd'][i, it], ind2word),
+                                      'answer': utils.idToWords(tokens[i * R + it], ind2word)} for it in range(R)]
+                    answerTable.append({'image_id': img_ids[convId - 1] if img_ids else int(convId), 'dialog': threadAnswers})
+            self._set_training(True)
+            return answerTable
+        if sampleBatch > 0:
+            for first in range(1, numThreads + 1, sampleBatch):
+                convIds = np.arange(first, min(first + sampleBatch, numThreads + 1))
+                batch = dataloader.getIndexData(convIds, self.params, dtype)
+                B, R = len(convIds), batch['ques_fwd'].shape[1]
+                self._gen_encode(batch)
+                u = rng.random_sample((B, beamLen, R))      # the per-dialog loop's draws: dialog, then step, then round
+                tokens, _ = self._gen_sample(beamLen, startToken, endToken, temperature,
+                                             u.transpose(1, 0, 2).reshape(beamLen, B * R))   # [step x row], row = dialog * R + round
                 for i, convId in enumerate(convIds):
                     threadAnswers = [{'question': utils.idToWords(batch['ques_fwd'][i, it], ind2word),
                                       'answer': utils.idToWords(tokens[i * R + it], ind2word)} for it in range(R)]
