@@ -298,39 +298,20 @@ function Model:generateAnswers(dataloader, dtype, params)
     local answerTable = {}
     self:commitW()
     self:setMode(false)
-    if beamBatch > 0 then
-        local ids = dataloader['unique_img_' .. dtype]
-        local function words(ids_) return utils.idToWords(ids_, dataloader.ind2word) end
-        for first = 1, numThreads, beamBatch do
-            local last = math.min(first + beamBatch - 1, numThreads)
-            local inds = {}
-            for convId = first, last do inds[#inds + 1] = convId end
-            local batch = dataloader:getIndexData(torch.LongTensor(inds), self.params, dtype)
-            local B, R = batch['ques_fwd']:size(1), batch['ques_fwd']:size(2)
-            self:upload({ques_fwd = batch['ques_fwd'], hist = batch['hist'], img_feat = batch['img_feat']})
-            self.havePrefetched = false
-            vd.call('vd_model_encode', self.h)
-            local toks, scores = ffi.new('int32_t[?]', B * R * beamLen), ffi.new('double[?]', B * R)
-            vd.call('vd_model_beam_search', self.h, beamSize, beamLen, startToken, endToken, toks, scores)
-            for b = 1, B do
-                local threadAnswers = {}
-                for iter = 1, R do
-                    local ans, row = {}, ((b - 1) * R + iter - 1) * beamLen   -- row = dialog * R + round
-                    for t = 1, beamLen do ans[t] = toks[row + t - 1] end
-                    threadAnswers[#threadAnswers + 1] = {question = words(batch['ques_fwd'][{b, iter}]), answer = words(torch.LongTensor(ans))}
-                end
-                local convId = first + b - 1
-                answerTable[#answerTable + 1] = {image_id = ids and ids[convId] or convId, dialog = threadAnswers}
-            end
+    local ids = dataloader['unique_img_' .. dtype]
+    local function words(ids_) return utils.idToWords(ids_, dataloader.ind2word) end
+    -- {image_id, dialog = {{question, answer}...}}: questions from row b of the batch, answers[iter] = round iter's token ids
+    local function record(convId, batch, b, answers)
+        local dialog = {}
+        for iter = 1, #answers do
+            dialog[iter] = {question = words(batch['ques_fwd'][{b, iter}]), answer = words(torch.LongTensor(answers[iter]))}
         end
-        self:setMode(true)
-        return answerTable
+        return {image_id = ids and ids[convId] or convId, dialog = dialog}
     end
-    if sampleBatch > 0 then
-        local ids = dataloader['unique_img_' .. dtype]
-        local function words(ids_) return utils.idToWords(ids_, dataloader.ind2word) end
-        for first = 1, numThreads, sampleBatch do
-            local last = math.min(first + sampleBatch - 1, numThreads)
+    local chunk = sampleWords and sampleBatch or beamBatch
+    if chunk > 0 then
+        for first = 1, numThreads, chunk do
+            local last = math.min(first + chunk - 1, numThreads)
             local inds = {}
             for convId = first, last do inds[#inds + 1] = convId end
             local batch = dataloader:getIndexData(torch.LongTensor(inds), self.params, dtype)
@@ -338,25 +319,28 @@ function Model:generateAnswers(dataloader, dtype, params)
             self:upload({ques_fwd = batch['ques_fwd'], hist = batch['hist'], img_feat = batch['img_feat']})
             self.havePrefetched = false
             vd.call('vd_model_encode', self.h)
-            local n = B * R
-            local u = torch.DoubleTensor(B, beamLen, R):uniform()       -- the per-dialog loop's draws: dialog, step, round
-            local us = ffi.new('double[?]', beamLen * n)
-            for b = 1, B do
-                for t = 1, beamLen do
-                    for iter = 1, R do us[(t - 1) * n + (b - 1) * R + iter - 1] = u[{b, t, iter}] end   -- [step x row]
+            local n, width = B * R, sampleWords and beamLen + 1 or beamLen
+            local toks, scores = ffi.new('int32_t[?]', n * width), ffi.new('double[?]', n)
+            if sampleWords then
+                local u = torch.DoubleTensor(B, beamLen, R):uniform()       -- the per-dialog loop's draws: dialog, step, round
+                local us = ffi.new('double[?]', beamLen * n)
+                for b = 1, B do
+                    for t = 1, beamLen do
+                        for iter = 1, R do us[(t - 1) * n + (b - 1) * R + iter - 1] = u[{b, t, iter}] end   -- [step x row]
+                    end
                 end
+                vd.call('vd_model_sample', self.h, beamLen, startToken, endToken, temperature, us, toks, scores)
+            else
+                vd.call('vd_model_beam_search', self.h, beamSize, beamLen, startToken, endToken, toks, scores)
             end
-            local toks, lhood = ffi.new('int32_t[?]', n * (beamLen + 1)), ffi.new('double[?]', n)
-            vd.call('vd_model_sample', self.h, beamLen, startToken, endToken, temperature, us, toks, lhood)
             for b = 1, B do
-                local threadAnswers = {}
+                local answers = {}
                 for iter = 1, R do
-                    local ans, row = {}, ((b - 1) * R + iter - 1) * (beamLen + 1)   -- row = dialog * R + round
-                    for t = 1, beamLen + 1 do ans[t] = toks[row + t - 1] end
-                    threadAnswers[#threadAnswers + 1] = {question = words(batch['ques_fwd'][{b, iter}]), answer = words(torch.LongTensor(ans))}
+                    local row = ((b - 1) * R + iter - 1) * width             -- row = dialog * R + round
+                    answers[iter] = {}
+                    for t = 1, width do answers[iter][t] = toks[row + t - 1] end
                 end
-                local convId = first + b - 1
-                answerTable[#answerTable + 1] = {image_id = ids and ids[convId] or convId, dialog = threadAnswers}
+                answerTable[#answerTable + 1] = record(first + b - 1, batch, b, answers)
             end
         end
         self:setMode(true)
@@ -368,8 +352,7 @@ function Model:generateAnswers(dataloader, dtype, params)
         self:upload({ques_fwd = batch['ques_fwd'], hist = batch['hist'], img_feat = batch['img_feat']})
         self.havePrefetched = false
         vd.call('vd_model_encode', self.h)                             -- forwardBackward(batch, true, true)
-        local threadAnswers = {}
-        local function words(ids) return utils.idToWords(ids, dataloader.ind2word) end
+        local answers = {}
         if not sampleWords then
             local n = beamSize
             local rounds, toks, src = ffi.new('int32_t[?]', n), ffi.new('int32_t[?]', n), ffi.new('int32_t[?]', n)
@@ -406,8 +389,7 @@ function Model:generateAnswers(dataloader, dtype, params)
                     for i = 1, keep do beams[i] = cands[i].beam; scores[i] = cands[i].score end
                 end
                 table.sort(finish, function(a, b) if a.score ~= b.score then return a.score > b.score end return a.order < b.order end)
-                local best = (#finish > 0) and finish[1].beam or beams[1]
-                threadAnswers[#threadAnswers + 1] = {question = words(batch['ques_fwd'][{1, iter}]), answer = words(torch.LongTensor(best))}
+                answers[iter] = (#finish > 0) and finish[1].beam or beams[1]
             end
         else
             local n = R
@@ -415,8 +397,7 @@ function Model:generateAnswers(dataloader, dtype, params)
             local logp = ffi.new('float[?]', n * V)
             for i = 0, n - 1 do rounds[i] = i; src[i] = i; toks[i] = startToken end
             vd.call('vd_model_decode_begin', self.h, rounds, n)
-            local answer = {}
-            for i = 1, n do answer[i] = {startToken} end
+            for i = 1, n do answers[i] = {startToken} end
             for _ = 1, beamLen do
                 vd.call('vd_model_decode_step', self.h, toks, logp)
                 vd.call('vd_model_decode_select', self.h, src, n)
@@ -424,15 +405,11 @@ function Model:generateAnswers(dataloader, dtype, params)
                     local pr = torch.FloatTensor(V)
                     for c = 1, V do pr[c] = math.exp(logp[(i - 1) * V + c - 1] / temperature) end
                     local nxt = torch.multinomial(pr:div(pr:sum()), 1)[1]
-                    answer[i][#answer[i] + 1] = nxt; toks[i - 1] = nxt
+                    answers[i][#answers[i] + 1] = nxt; toks[i - 1] = nxt
                 end
             end
-            for iter = 1, R do
-                threadAnswers[#threadAnswers + 1] = {question = words(batch['ques_fwd'][{1, iter}]), answer = words(torch.LongTensor(answer[iter]))}
-            end
         end
-        local ids = dataloader['unique_img_' .. dtype]
-        answerTable[#answerTable + 1] = {image_id = ids and ids[convId] or convId, dialog = threadAnswers}
+        answerTable[#answerTable + 1] = record(convId, batch, 1, answers)
     end
     self:setMode(true)
     return answerTable

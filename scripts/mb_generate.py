@@ -1,0 +1,71 @@
+"""Answer generation at full size through the native host (model-level ABI): the per-dialog host loop (beamBatch / sampleBatch 0:
+vd_model_decode_step + a V-wide host sort or draw per explored row) against the batched device path (beamBatch / sampleBatch 20:
+vd_model_beam_search / vd_model_sample over every round of 20 dialogs, the host's uniforms uploaded once).  lf-ques-im-hist + gen,
+H = 512, V = 11 322, 2 layers, length 20, random weights; beam 5, or sampling at temperature 1.  Prints dialogs/s per path and how
+many dialogs have identical records.
+    python scripts/mb_generate.py --mode beam|sample [dialogs] [--only batched]   (--only batched: the device path alone, for a trace)"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+
+from visdial_amd.dataloader import SyntheticDataloader  # noqa: E402
+from visdial_amd.native import NativeModel  # noqa: E402
+from visdial_amd.opts import default_params, derive  # noqa: E402
+
+ap = argparse.ArgumentParser(description='batched vs per-dialog answer generation at full size')
+ap.add_argument('dialogs', nargs='?', type=int, default=20)
+ap.add_argument('--mode', choices=('beam', 'sample'), required=True)
+ap.add_argument('--only', choices=('batched',), help='the device path alone, for a kernel trace')
+opt = ap.parse_args()
+MODE, D, ONLY_BATCHED = opt.mode, opt.dialogs, opt.only == 'batched'
+V, R = 11322, 10
+
+
+class Dialogs(object):
+    """D synthetic dialogs behind the getIndexData / word2ind / ind2word surface generateAnswers reads"""
+
+    def __init__(self, p, n):
+        q = dict(p, batchSize=n)
+        self.b = SyntheticDataloader(q, seed=5).getTrainBatch(q)
+        self.numThreads = {'val': n}
+        self.word2ind = {'<START>': V - 1, '<END>': V}
+        self.ind2word = {i: '<START>' if i == V - 1 else '<END>' if i == V else 'w%d' % i for i in range(1, V + 1)}
+
+    def getIndexData(self, inds, params, dtype):
+        ix = np.asarray(inds, np.int64) - 1
+        return {k: np.ascontiguousarray(self.b[k][ix]) for k in ('ques_fwd', 'hist', 'img_feat')}
+
+
+p = derive(default_params(encoder='lf-ques-im-hist', decoder='gen', vocabSize=V, embedSize=300, rnnHiddenSize=512, imgFeatureSize=4096,
+                          numLayers=2, maxQuesCount=R, maxQuesLen=20, maxAnsLen=20, maxHistoryLenPerRound=40, batchSize=20, gpuid=0))
+dl = Dialogs(p, D)
+nat = NativeModel(p, init_seed=1)
+nat.training(False)
+if MODE == 'beam':
+    key, cfg = 'beamBatch', dict(beamSize=5, beamLen=20, maxThreads=D)
+    what = 'beam %d' % cfg['beamSize']
+else:
+    key, cfg = 'sampleBatch', dict(sampleWords=1, beamLen=20, temperature=1.0, maxThreads=D, seed=1234)
+    what = 'sampling'
+print("lf-ques-im-hist + gen, H %d, V %d, %d layers, %s, length %d%s, %d dialogs x %d rounds" % (
+    p['rnnHiddenSize'], V, p['numLayers'], what, cfg['beamLen'],
+    ', temperature %g' % cfg['temperature'] if MODE == 'sample' else '', D, R), flush=True)
+nat.generateAnswers(dl, 'val', dict(cfg, maxThreads=min(D, 20), **{key: 20}))          # warm-up: workspaces, code objects
+res = {}
+for b in ((20,) if ONLY_BATCHED else (0, 20)):
+    reps = 1 if b == 0 else 5
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        out = nat.generateAnswers(dl, 'val', dict(cfg, **{key: b}))
+    dt = (time.perf_counter() - t0) / reps
+    res[b] = out
+    print("%s %2d: %8.3f s for %d dialogs = %9.2f dialogs/s  (%.2f ms per dialog)" % (key, b, dt, D, D / dt, dt / D * 1e3), flush=True)
+    res[b, 't'] = dt
+if not ONLY_BATCHED:
+    same = sum(a == b for a, b in zip(res[0], res[20]))
+    print("speed-up %.1fx; dialogs with identical records: %d of %d" % (res[0, 't'] / res[20, 't'], same, D))
+nat.close()

@@ -1,6 +1,6 @@
 """The batched beam-search kernels (csrc/beam.hip: vd_beam_topk / init / advance / select_rows / finish) against a numpy
-restatement of the bookkeeping of split_eval.py:113-145 (model.lua:466-573), bit for bit: top-k indices and values, the
-per-slot source, the history buffer, the fp64 scores and the best finished candidate after every step."""
+restatement of the per-dialog bookkeeping of SplitEval.generateAnswers (split_eval.py; model.lua:466-573), bit for bit: top-k
+indices and values, the per-slot source, the history buffer, the fp64 scores and the best finished candidate after every step."""
 import numpy as np
 import pytest
 import torch
@@ -73,8 +73,8 @@ def test_topk_refuses_k_above_its_bound(gpu):
 
 # ---------------------------------------------------------------------------------------------------------------- advance
 def ref_advance(top_idx, top_val, k, step, L, END, scores, hist, best):
-    """split_eval.py:120-140 for every group: returns (scores, hist, src, next_tok) and updates best in place.  best[g] =
-    None or (score, length, column)."""
+    """one step of the per-dialog beam search of SplitEval.generateAnswers for every group: returns (scores, hist, src, next_tok)
+    and updates best in place.  best[g] = None or (score, length, column)."""
     G = scores.shape[0]
     explore = 1 if step == 1 else k
     scores, hist = scores.copy(), hist.copy()

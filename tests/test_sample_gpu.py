@@ -293,7 +293,7 @@ def test_generate_py_sample_batch_writes_the_same_results(gpu, tmp_path):
 
 # ---------------------------------------------------------------------------------------------------------------- full size
 class Dialogs(object):
-    """synthetic dialogs behind the getIndexData / word2ind / ind2word surface generateAnswers reads (scripts/mb_sample.py)"""
+    """synthetic dialogs behind the getIndexData / word2ind / ind2word surface generateAnswers reads (scripts/mb_generate.py)"""
 
     def __init__(self, p, n, V):
         q = dict(p, batchSize=n)

@@ -1,6 +1,7 @@
 // Batched beam search of Model:generateAnswers (reference model.lua:466-573) on the device: the candidate bookkeeping the
-// hosts keep in split_eval.py:113-145 / lua/model.lua:294-332 (and oracle/visdial_oracle.py:generate_beam restates in fp64),
-// for every QA round of a batch at once.  One *group* = one round, with k = beamSize slots; hypothesis row r = group * k + slot.
+// per-dialog host loops keep in SplitEval.generateAnswers (split_eval.py) and Model:generateAnswers (lua/model.lua), and
+// oracle/visdial_oracle.py:generate_beam restates in fp64, for every QA round of a batch at once.  One *group* = one round,
+// with k = beamSize slots; hypothesis row r = group * k + slot.
 //
 // The rules all three agree on, reproduced here exactly:
 //  1. slot state starts from the round's encoder state (Gen_begin, rt_decoders.h; model.lua:478-503); beams[0] = <START>,
@@ -27,11 +28,10 @@ namespace {
 // value descending, index ascending
 __device__ __forceinline__ bool beam_better(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
 
-// Fused nn.LogSoftMax + top-k of one hypothesis row per workgroup.  The log-sum-exp is computed exactly as
-// log_softmax_rows_kernel (loss.hip) computes it -- 256 strided threads, wave_max / wave_sum, the four wave partials summed in
-// the same order -- so every value is bit-identical to that kernel's output row[c] - lse.  Each thread keeps a sorted list of
-// its KM best (value, index) pairs in registers (compile-time indices only: no scratch), then k rounds of a workgroup
-// arg-max over the list heads pop the row's top-k in order.
+// Fused nn.LogSoftMax + top-k of one hypothesis row per workgroup.  The log-sum-exp is block_row_lse (common.h), which
+// log_softmax_rows_kernel (loss.hip) calls too, so every value is bit-identical to that kernel's output row[c] - lse.  Each
+// thread keeps a sorted list of its KM best (value, index) pairs in registers (compile-time indices only: no scratch), then
+// k rounds of a workgroup arg-max over the list heads pop the row's top-k in order.
 template <int KM>
 __global__ void __launch_bounds__(256)
 beam_topk_kernel(const float* __restrict__ x, long ld, int V, const int32_t* __restrict__ tok, int k,
@@ -48,18 +48,7 @@ beam_topk_kernel(const float* __restrict__ x, long ld, int V, const int32_t* __r
     return;
   }
   const float* row = x + r * ld;
-  float mx = -INFINITY;
-  for (int c = tid; c < V; c += 256) mx = fmaxf(mx, row[c]);
-  mx = wave_max(mx);
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  float sum = 0.f;
-  for (int c = tid; c < V; c += 256) sum += expf(row[c] - mx);
-  sum = wave_sum(sum);
-  if (lane == 0) red[4 + wave] = sum;
-  __syncthreads();
-  const float lse = mx + logf(red[4] + red[5] + red[6] + red[7]);
+  const float lse = block_row_lse(row, V, red);
 
   float lv[KM];
   int li[KM];
@@ -206,8 +195,6 @@ __global__ void beam_finish_kernel(int groups, int k, int L, const int32_t* __re
     if (p == 0) out_score[g] = fin ? best_score[g] : scores[g * k];
   }
 }
-
-inline unsigned grid_for(long n) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, 4096)); }
 
 }  // namespace
 

@@ -39,6 +39,8 @@ void vd_set_error(const char* fmt, ...);
 #define VD_LAUNCH_CHECK() VD_HIP(hipGetLastError())
 
 static inline int vd_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// blocks of 256 threads for a grid-stride loop over n elements: one per 256, at least 1, at most 4096
+static inline unsigned grid_for(long n) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, 4096)); }
 
 // ROCTx ranges around the phases of a step (SURVEY.md section 5 "tracing"): host-side ranges on the enqueuing thread, visible in
 // `rocprofv3 --marker-trace --kernel-trace` next to the kernels dispatched inside them.  librocprofiler-sdk-roctx.so / libroctx64.so is
@@ -168,4 +170,24 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// Log-sum-exp of one row of V logits for a 256-thread block: 256 strided threads take the max, then the sum of exp(x - max),
+// each reduced by wave_max / wave_sum with the four wave partials combined in a fixed order; `red` is the block's 8-float
+// shared buffer.  The one row arithmetic of vd_logsoftmax_nll, vd_log_softmax_rows, vd_beam_topk and vd_sample_draw: the
+// generation kernels' log-probabilities are bit-identical to vd_log_softmax_rows because all of them call this.
+__device__ __forceinline__ float block_row_lse(const float* row, int V, float* red) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float mx = -INFINITY;
+  for (int c = tid; c < V; c += 256) mx = fmaxf(mx, row[c]);
+  mx = wave_max(mx);
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float sum = 0.f;
+  for (int c = tid; c < V; c += 256) sum += expf(row[c] - mx);
+  sum = wave_sum(sum);
+  if (lane == 0) red[4 + wave] = sum;
+  __syncthreads();
+  return mx + logf(red[4] + red[5] + red[6] + red[7]);
 }

@@ -88,7 +88,7 @@ logsoftmax_nll_kernel(float* __restrict__ logits, long ld, int V, const int* __r
                       const int* __restrict__ target, float* __restrict__ loss_rows, int write_grad) {
   __shared__ float red[8];
   const long r = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   float* row = logits + r * ld;
   if (write_grad && tid < ld - V) row[V + tid] = 0.f;  // keep the alignment pad columns finite (K-padding rule)
   // masked rows: a pad decoder input (MaskZero, gen.lua:23-24) or a pad TARGET -- utils.computeLhood masks on
@@ -101,18 +101,7 @@ logsoftmax_nll_kernel(float* __restrict__ logits, long ld, int V, const int* __r
       for (int c = tid; c < V; c += 256) row[c] = 0.f;
     return;
   }
-  float mx = -INFINITY;
-  for (int c = tid; c < V; c += 256) mx = fmaxf(mx, row[c]);
-  mx = wave_max(mx);
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  float sum = 0.f;
-  for (int c = tid; c < V; c += 256) sum += expf(row[c] - mx);
-  sum = wave_sum(sum);
-  if (lane == 0) red[4 + wave] = sum;
-  __syncthreads();
-  const float lse = mx + logf(red[4] + red[5] + red[6] + red[7]);
+  const float lse = block_row_lse(row, V, red);
   const int tgt = target[r] - 1;
   if (tid == 0) loss_rows[r] = lse - row[tgt];
   if (write_grad) {
@@ -126,19 +115,8 @@ __global__ void __launch_bounds__(256)
 log_softmax_rows_kernel(float* __restrict__ x, long ld, int V) {
   __shared__ float red[8];
   float* row = x + (long)blockIdx.x * ld;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  float mx = -INFINITY;
-  for (int c = tid; c < V; c += 256) mx = fmaxf(mx, row[c]);
-  mx = wave_max(mx);
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  float sum = 0.f;
-  for (int c = tid; c < V; c += 256) sum += expf(row[c] - mx);
-  sum = wave_sum(sum);
-  if (lane == 0) red[4 + wave] = sum;
-  __syncthreads();
-  const float lse = mx + logf(red[4] + red[5] + red[6] + red[7]);
+  const int tid = threadIdx.x;
+  const float lse = block_row_lse(row, V, red);
   for (int c = tid; c < V; c += 256) row[c] -= lse;
 }
 

@@ -369,6 +369,38 @@ inline int gen_rows(vd_model* m, const char* key, const int32_t* host, int n, in
   VD_HIP(hipStreamSynchronize(m->s_main));           // `host` may be a temporary of the caller
   return VD_OK;
 }
+// Layer l's state of the n hypotheses, [n x H] each: the current state a step starts from (gen.h<l> / gen.c<l>) and the stepped
+// state vd_model_decode_step keeps for vd_model_decode_select (gen.hn<l> / gen.cn<l>).
+struct GenState {
+  float *h, *c, *hn, *cn;
+};
+inline int gen_state(Gen* g, vd_model* m, size_t l, int n, GenState* st) {
+  const std::string sfx = std::to_string(l);
+  const size_t count = (size_t)n * g->H;
+  VD_TRY(ws_get(m, "gen.h" + sfx, count, &st->h));
+  VD_TRY(ws_get(m, "gen.c" + sfx, count, &st->c));
+  VD_TRY(ws_get(m, "gen.hn" + sfx, count, &st->hn));
+  VD_TRY(ws_get(m, "gen.cn" + sfx, count, &st->cn));
+  return VD_OK;
+}
+// decoderConnect (gen.lua:63-68): the stepped state rnn[l].out_at(0) / cell_at(0) of the n hypotheses goes to the current state
+// (`next`: to the stepped buffers hn / cn).  With `src` (beam search), row r takes stepped row group(r) * k + src[r] and a row
+// with src[r] < 0 is left alone (vd_beam_select_rows); without, every row is copied.
+inline int gen_carry(Gen* g, vd_model* m, int n, bool next, const int32_t* src = nullptr, int k = 1) {
+  hipStream_t s = m->s_main;
+  const long H = g->H;
+  for (size_t l = 0; l < g->rnn.size(); ++l) {
+    GenState st;
+    VD_TRY(gen_state(g, m, l, n, &st));
+    float* dst[2] = {next ? st.hn : st.h, next ? st.cn : st.c};
+    const float* stepped[2] = {g->rnn[l].out_at(0), g->rnn[l].cell_at(0)};
+    for (int i = 0; i < 2; ++i) {
+      if (src) VD_TRY(vd_beam_select_rows(dst[i], stepped[i], src, n, k, (int)H, s));
+      else VD_TRY(vd_memcpy_d2d(dst[i], stepped[i], (long)n * H * 4, s));
+    }
+  }
+  return VD_OK;
+}
 // hiddenBeams (model.lua:478-503): hypothesis i starts from the encoder state of QA round rounds[i]
 inline int Gen_begin(Gen* g, vd_model* m, const int32_t* rounds, int n) {
   VD_CHECK_ARG(m->gen_enc_out && rounds && n > 0, "vd_model_decode_begin: call vd_model_encode first");
@@ -380,20 +412,17 @@ inline int Gen_begin(Gen* g, vd_model* m, const int32_t* rounds, int n) {
   const int L = (int)g->rnn.size(), seqLen = m->gen_seq_len;
   const long H = g->H;
   for (int l = 0; l < L; ++l) {
-    float *h, *c, *hn, *cn;
-    VD_TRY(ws_get(m, "gen.h" + std::to_string(l), (size_t)n * H, &h));
-    VD_TRY(ws_get(m, "gen.c" + std::to_string(l), (size_t)n * H, &c));
-    VD_TRY(ws_get(m, "gen.hn" + std::to_string(l), (size_t)n * H, &hn));
-    VD_TRY(ws_get(m, "gen.cn" + std::to_string(l), (size_t)n * H, &cn));
+    GenState st;
+    VD_TRY(gen_state(g, m, l, n, &st));
     if (layers) {
       VD_CHECK_ARG(l < (int)layers->size(), "decoder has more layers than the encoder's recurrence");
       const float* hs = l == (int)layers->size() - 1 ? m->gen_enc_out : (*layers)[l].out_at(seqLen - 1);
-      VD_TRY(vd_embed_gather(hs, idx, nullptr, h, n, (int)H, 1.f, s));
-      VD_TRY(vd_embed_gather((*layers)[l].cell_at(seqLen - 1), idx, nullptr, c, n, (int)H, 1.f, s));
+      VD_TRY(vd_embed_gather(hs, idx, nullptr, st.h, n, (int)H, 1.f, s));
+      VD_TRY(vd_embed_gather((*layers)[l].cell_at(seqLen - 1), idx, nullptr, st.c, n, (int)H, 1.f, s));
     } else {
-      VD_TRY(vd_memset(c, 0, (long)n * H * 4, s));
-      if (l == L - 1) VD_TRY(vd_embed_gather(m->gen_enc_out, idx, nullptr, h, n, (int)H, 1.f, s));
-      else VD_TRY(vd_memset(h, 0, (long)n * H * 4, s));
+      VD_TRY(vd_memset(st.c, 0, (long)n * H * 4, s));
+      if (l == L - 1) VD_TRY(vd_embed_gather(m->gen_enc_out, idx, nullptr, st.h, n, (int)H, 1.f, s));
+      else VD_TRY(vd_memset(st.h, 0, (long)n * H * 4, s));
     }
   }
   g->gen_n = n;
@@ -401,16 +430,15 @@ inline int Gen_begin(Gen* g, vd_model* m, const int32_t* rounds, int n) {
 }
 // The device part of one decoder step (model.lua:518-522): the n hypotheses' tokens (device) through embedding, LSTM stack
 // and vocabulary projection from the current state gen.h<l> / gen.c<l> -> logits [n x Vp]; the stepped state is left in
-// rnn[l].out_at(0) / cell_at(0).  Shared by vd_model_decode_step and vd_model_beam_search.
+// rnn[l].out_at(0) / cell_at(0).  Shared by vd_model_decode_step and the batched generations.
 inline int gen_forward(Gen* g, vd_model* m, const int32_t* tok, int n, float** logits) {
   hipStream_t s = m->s_main;
   const long H = g->H, E = g->E, V = g->V, Vp = g->Vp;
   for (size_t l = 0; l < g->rnn.size(); ++l) {
-    float *h, *c;
-    VD_TRY(ws_get(m, "gen.h" + std::to_string(l), (size_t)n * H, &h));
-    VD_TRY(ws_get(m, "gen.c" + std::to_string(l), (size_t)n * H, &c));
-    g->rnn[l].userPrevOutput = h;
-    g->rnn[l].userPrevCell = c;
+    GenState st;
+    VD_TRY(gen_state(g, m, l, n, &st));
+    g->rnn[l].userPrevOutput = st.h;
+    g->rnn[l].userPrevCell = st.c;
   }
   float *x, *top;
   VD_TRY(ws_get(m, "gen1.x", (size_t)n * E, &x));
@@ -425,20 +453,14 @@ inline int Gen_step(Gen* g, vd_model* m, const int32_t* tokens, float* host_logp
   const int n = g->gen_n;
   VD_CHECK_ARG(n > 0 && tokens && host_logp, "vd_model_decode_step: call vd_model_decode_begin first");
   hipStream_t s = m->s_main;
-  const long H = g->H, E = g->E, V = g->V, Vp = g->Vp;
+  const long E = g->E, V = g->V, Vp = g->Vp;
   int32_t* tok;
   VD_TRY(gen_rows(m, "gen.tok", tokens, n, &tok));
   VD_TRY(vd_memset(Wp(m, "embed"), 0, E * 4, s));                                   // LookupTableMaskZero pad row
   float* logits;
   VD_TRY(gen_forward(g, m, tok, n, &logits));
   VD_TRY(vd_log_softmax_rows(logits, Vp, n, (int)V, s));
-  for (size_t l = 0; l < g->rnn.size(); ++l) {                                       // the stepped state (decoderConnect, gen.lua:63-68)
-    float *hn, *cn;
-    VD_TRY(ws_get(m, "gen.hn" + std::to_string(l), (size_t)n * H, &hn));
-    VD_TRY(ws_get(m, "gen.cn" + std::to_string(l), (size_t)n * H, &cn));
-    VD_TRY(vd_memcpy_d2d(hn, g->rnn[l].out_at(0), (long)n * H * 4, s));
-    VD_TRY(vd_memcpy_d2d(cn, g->rnn[l].cell_at(0), (long)n * H * 4, s));
-  }
+  VD_TRY(gen_carry(g, m, n, true));                                                  // kept for vd_model_decode_select
   VD_HIP(hipMemcpy2DAsync(host_logp, (size_t)V * 4, logits, (size_t)Vp * 4, (size_t)V * 4, (size_t)n, hipMemcpyDeviceToHost, s));
   VD_HIP(hipStreamSynchronize(s));
   // Sequencer(MaskZero(Linear)) + Sequencer(MaskZero(LogSoftMax)) (decoders/gen.lua:23-24): the row of a hypothesis whose token is 0 -- a
@@ -456,32 +478,53 @@ inline int Gen_select(Gen* g, vd_model* m, const int32_t* src, int n_keep) {
   hipStream_t s = m->s_main;
   int32_t* idx;
   VD_TRY(gen_rows(m, "gen.idx", src, n_keep, &idx));
-  const long H = g->H;
   for (size_t l = 0; l < g->rnn.size(); ++l) {
-    float *h, *c, *hn, *cn;
-    VD_TRY(ws_get(m, "gen.h" + std::to_string(l), (size_t)n * H, &h));
-    VD_TRY(ws_get(m, "gen.c" + std::to_string(l), (size_t)n * H, &c));
-    VD_TRY(ws_get(m, "gen.hn" + std::to_string(l), (size_t)n * H, &hn));
-    VD_TRY(ws_get(m, "gen.cn" + std::to_string(l), (size_t)n * H, &cn));
-    VD_TRY(vd_embed_gather(hn, idx, nullptr, h, n_keep, (int)H, 1.f, s));
-    VD_TRY(vd_embed_gather(cn, idx, nullptr, c, n_keep, (int)H, 1.f, s));
+    GenState st;
+    VD_TRY(gen_state(g, m, l, n, &st));
+    VD_TRY(vd_embed_gather(st.hn, idx, nullptr, st.h, n_keep, (int)g->H, 1.f, s));
+    VD_TRY(vd_embed_gather(st.cn, idx, nullptr, st.c, n_keep, (int)g->H, 1.f, s));
   }
   return VD_OK;
 }
 
-// Model:generateAnswers' beam search (model.lua:466-573) for all N rounds of the last vd_model_encode batch at once: N groups
-// of k slots = N * k hypothesis rows.  Per step, on s_main only: embedding gather -> LSTM stack -> vocabulary GEMM -> fused
-// log-softmax + top-k -> advance (candidate bookkeeping, csrc/beam.hip) -> state select.  The next tokens never leave the
-// device; the answers come back in ONE copy after the last step.
+// The batched generations (vd_model_beam_search, vd_model_sample) run every round of the last vd_model_encode batch at once, on
+// s_main only.  gen_batch_begin: hypothesis row i = slot i % k of round i / k starts from that round's encoder state (hiddenBeams,
+// model.lua:478-503).  gen_batch_steps: steps 1 .. `steps` of gen_forward on the device tokens `tok` -> `head(step, logits)`, the
+// mode's kernels, which leave the next tokens in `tok` -> gen_carry (by the beam's back-pointers `src`, or a copy); the tokens never
+// leave the device.  gen_read_back: the results come back in ONE copy after the last step.
+inline int gen_batch_begin(Gen* g, vd_model* m, int k) {
+  const int n = m->N * k;
+  std::vector<int32_t> rounds(n);
+  for (int i = 0; i < n; ++i) rounds[i] = i / k;
+  return Gen_begin(g, m, rounds.data(), n);
+}
+template <class Head>
+inline int gen_batch_steps(Gen* g, vd_model* m, int steps, const int32_t* tok, const int32_t* src, int k, Head head) {
+  const int n = g->gen_n;
+  VD_TRY(vd_memset(Wp(m, "embed"), 0, g->E * 4, m->s_main));                       // LookupTableMaskZero pad row
+  for (int step = 1; step <= steps; ++step) {
+    float* logits;
+    VD_TRY(gen_forward(g, m, tok, n, &logits));
+    VD_TRY(head(step, logits));
+    VD_TRY(gen_carry(g, m, n, false, src, k));
+  }
+  return VD_OK;
+}
+inline int gen_read_back(vd_model* m, const void* out, size_t bytes, std::vector<uint8_t>* staged) {
+  staged->resize(bytes);
+  VD_HIP(hipMemcpyAsync(staged->data(), out, bytes, hipMemcpyDeviceToHost, m->s_main));
+  VD_HIP(hipStreamSynchronize(m->s_main));
+  return VD_OK;
+}
+
+// Model:generateAnswers' beam search (model.lua:466-573): N groups of k slots = N * k hypothesis rows.  Per step: fused
+// log-softmax + top-k -> advance (candidate bookkeeping, csrc/beam.hip) -> state select; then the best answer and score per round.
 inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end, int32_t* host_tokens, double* host_scores) {
   VD_CHECK_ARG(m->gen_enc_out && m->N > 0, "vd_model_beam_search: call vd_model_encode first");
   VD_CHECK_ARG(host_tokens && host_scores && L >= 1, "vd_model_beam_search: bad arguments");
   VD_CHECK_ARG(k >= 1 && k <= 32 && k <= g->V, "vd_model_beam_search: beam size %d must be in [1, min(32, vocabSize)]", k);
   const int G = m->N, n = G * k;
-  const long H = g->H, E = g->E, V = g->V, Vp = g->Vp;
-  std::vector<int32_t> rounds(n);
-  for (int i = 0; i < n; ++i) rounds[i] = i / k;                                     // hiddenBeams (model.lua:478-503)
-  VD_TRY(Gen_begin(g, m, rounds.data(), n));
+  VD_TRY(gen_batch_begin(g, m, k));
   hipStream_t s = m->s_main;
   int32_t *tok, *top_idx, *src, *hist[2], *best_len, *best_hist;
   float* top_val;
@@ -500,38 +543,25 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
   VD_TRY(ws_get(m, "beam.best_hist", (size_t)G * L, &best_hist));
   VD_TRY(ws_get(m, "beam.out", tok_bytes + (size_t)G * 8, &out));
   VD_TRY(vd_beam_init(G, k, L, start, hist[0], tok, scores, best_score, best_len, s));
-  VD_TRY(vd_memset(Wp(m, "embed"), 0, E * 4, s));                                   // LookupTableMaskZero pad row
-  int cur = 0;
-  for (int step = 1; step < L; ++step) {
-    float* logits;
-    VD_TRY(gen_forward(g, m, tok, n, &logits));
-    VD_TRY(vd_beam_topk(logits, Vp, n, (int)V, tok, k, top_idx, top_val, s));
-    VD_TRY(vd_beam_advance(top_idx, top_val, G, k, step, L, end, scores, hist[cur], hist[cur ^ 1], src, tok, best_score, best_len,
-                           best_hist, s));
-    for (size_t l = 0; l < g->rnn.size(); ++l) {
-      float *h, *c;
-      VD_TRY(ws_get(m, "gen.h" + std::to_string(l), (size_t)n * H, &h));
-      VD_TRY(ws_get(m, "gen.c" + std::to_string(l), (size_t)n * H, &c));
-      VD_TRY(vd_beam_select_rows(h, g->rnn[l].out_at(0), src, n, k, (int)H, s));
-      VD_TRY(vd_beam_select_rows(c, g->rnn[l].cell_at(0), src, n, k, (int)H, s));
-    }
-    cur ^= 1;
-  }
-  VD_TRY(vd_beam_finish(G, k, L, hist[cur], scores, best_score, best_len, best_hist, reinterpret_cast<int32_t*>(out),
+  VD_TRY(gen_batch_steps(g, m, L - 1, tok, src, k, [&](int step, float* logits) -> int {
+    VD_TRY(vd_beam_topk(logits, g->Vp, n, (int)g->V, tok, k, top_idx, top_val, s));
+    VD_TRY(vd_beam_advance(top_idx, top_val, G, k, step, L, end, scores, hist[0], hist[1], src, tok, best_score, best_len, best_hist,
+                           s));
+    std::swap(hist[0], hist[1]);
+    return VD_OK;
+  }));
+  VD_TRY(vd_beam_finish(G, k, L, hist[0], scores, best_score, best_len, best_hist, reinterpret_cast<int32_t*>(out),
                         reinterpret_cast<double*>(out + tok_bytes), s));
-  std::vector<uint8_t> staged(tok_bytes + (size_t)G * 8);
-  VD_HIP(hipMemcpyAsync(staged.data(), out, staged.size(), hipMemcpyDeviceToHost, s));
-  VD_HIP(hipStreamSynchronize(s));
+  std::vector<uint8_t> staged;
+  VD_TRY(gen_read_back(m, out, tok_bytes + (size_t)G * 8, &staged));
   memcpy(host_tokens, staged.data(), (size_t)G * L * 4);
   memcpy(host_scores, staged.data() + tok_bytes, (size_t)G * 8);
   return VD_OK;
 }
 
-// Model:generateAnswers' temperature sampling (model.lua:576-613) for all N rounds of the last vd_model_encode batch at once:
-// hypothesis row i = round i.  The host's uniforms [L x N] go up in one copy; per step, on s_main only: embedding gather ->
-// LSTM stack -> vocabulary GEMM -> fused log-softmax + inverse-CDF draw (csrc/sample.hip) -> the stepped state becomes the
-// current one (decoderConnect, gen.lua:63-68).  The sampled tokens never leave the device; history, log-likelihoods and the
-// status word share one buffer and come back in ONE copy after the last step.
+// Model:generateAnswers' temperature sampling (model.lua:576-613): hypothesis row i = round i.  The host's uniforms [L x N] go up
+// in one copy; per step: fused log-softmax + inverse-CDF draw (csrc/sample.hip) -> the stepped state becomes the current one.
+// History, log-likelihoods and the status word share one buffer and come back together.
 inline int Gen_sample(Gen* g, vd_model* m, int L, int start, int end, double T, const double* host_u, int32_t* host_tokens,
                       double* host_loglik) {
   VD_CHECK_ARG(m->gen_enc_out && m->N > 0, "vd_model_sample: call vd_model_encode first");
@@ -541,11 +571,8 @@ inline int Gen_sample(Gen* g, vd_model* m, int L, int start, int end, double T, 
   const int n = m->N;
   for (long i = 0; i < (long)L * n; ++i)
     VD_CHECK_ARG(host_u[i] >= 0.0 && host_u[i] < 1.0, "vd_model_sample: uniform %ld = %g is outside [0, 1)", i, host_u[i]);
-  std::vector<int32_t> rounds(n);
-  for (int i = 0; i < n; ++i) rounds[i] = i;
-  VD_TRY(Gen_begin(g, m, rounds.data(), n));
+  VD_TRY(gen_batch_begin(g, m, 1));
   hipStream_t s = m->s_main;
-  const long H = g->H, E = g->E, V = g->V, Vp = g->Vp;
   const size_t cols = (size_t)L + 1, hist_bytes = ((size_t)n * cols * 4 + 7) / 8 * 8, out_bytes = hist_bytes + (size_t)n * 8 + 8;
   uint8_t* out;
   double* u;
@@ -558,22 +585,11 @@ inline int Gen_sample(Gen* g, vd_model* m, int L, int start, int end, double T, 
   int32_t* status = reinterpret_cast<int32_t*>(out + hist_bytes + (size_t)n * 8);
   VD_HIP(hipMemcpyAsync(u, host_u, (size_t)L * n * 8, hipMemcpyHostToDevice, s));
   VD_TRY(vd_sample_init(n, L, start, hist, tok, loglik, status, s));
-  VD_TRY(vd_memset(Wp(m, "embed"), 0, E * 4, s));                                   // LookupTableMaskZero pad row
-  for (int step = 1; step <= L; ++step) {
-    float* logits;
-    VD_TRY(gen_forward(g, m, tok, n, &logits));
-    VD_TRY(vd_sample_draw(logits, Vp, n, (int)V, tok, u + (size_t)(step - 1) * n, T, step, L, end, hist, loglik, status, s));
-    for (size_t l = 0; l < g->rnn.size(); ++l) {
-      float *h, *c;
-      VD_TRY(ws_get(m, "gen.h" + std::to_string(l), (size_t)n * H, &h));
-      VD_TRY(ws_get(m, "gen.c" + std::to_string(l), (size_t)n * H, &c));
-      VD_TRY(vd_memcpy_d2d(h, g->rnn[l].out_at(0), (long)n * H * 4, s));
-      VD_TRY(vd_memcpy_d2d(c, g->rnn[l].cell_at(0), (long)n * H * 4, s));
-    }
-  }
-  std::vector<uint8_t> staged(out_bytes);
-  VD_HIP(hipMemcpyAsync(staged.data(), out, out_bytes, hipMemcpyDeviceToHost, s));
-  VD_HIP(hipStreamSynchronize(s));
+  VD_TRY(gen_batch_steps(g, m, L, tok, nullptr, 1, [&](int step, float* logits) {
+    return vd_sample_draw(logits, g->Vp, n, (int)g->V, tok, u + (size_t)(step - 1) * n, T, step, L, end, hist, loglik, status, s);
+  }));
+  std::vector<uint8_t> staged;
+  VD_TRY(gen_read_back(m, out, out_bytes, &staged));
   int32_t st;
   memcpy(&st, staged.data() + hist_bytes + (size_t)n * 8, 4);
   VD_CHECK_ARG(st == 0, "vd_model_sample: every weight exp(logp / temperature) of a row underflowed at temperature %g: nothing to sample "

@@ -5,9 +5,9 @@
 // path samples what the per-dialog host loops (split_eval.py, lua/model.lua) sample.
 //
 // The per-row rule, for a row whose input token is t and whose raw logits are x[0..V), at step s with uniform u:
-//  1. logp[c] = x[c] - lse in fp32, bit-identical to log_softmax_rows_kernel (loss.hip): 256 strided threads, wave_max /
-//     wave_sum, the four wave partials summed in the same order.  If t == 0 the row is all zeros (MaskZero(LogSoftMax),
-//     decoders/gen.lua:24); sampling never feeds a 0, but the rule is defined.
+//  1. logp[c] = x[c] - lse in fp32 with lse = block_row_lse (common.h), bit-identical to log_softmax_rows_kernel (loss.hip),
+//     which calls the same.  If t == 0 the row is all zeros (MaskZero(LogSoftMax), decoders/gen.lua:24); sampling never feeds a
+//     0, but the rule is defined.
 //  2. w[c] = exp((double)logp[c] / temperature) in fp64 (a division, as the hosts divide).
 //  3. S = the fp64 sum of w.  The token is the first c with w[c] > 0 whose inclusive prefix sum exceeds u * S; if rounding
 //     leaves no such c (u within rounding of 1), the last c with w[c] > 0.  The vocabulary id is c + 1.  Prefix sums: thread t
@@ -57,20 +57,7 @@ sample_draw_kernel(const float* __restrict__ x, long ld, int V, int32_t* __restr
   const float* row = x + r * ld;
   const bool zero_row = tok[r] == 0;
   float lse = 0.f;
-  if (!zero_row) {                       // rule 1: log_softmax_rows_kernel's arithmetic, operation for operation
-    float mx = -INFINITY;
-    for (int c = tid; c < V; c += 256) mx = fmaxf(mx, row[c]);
-    mx = wave_max(mx);
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float sum = 0.f;
-    for (int c = tid; c < V; c += 256) sum += expf(row[c] - mx);
-    sum = wave_sum(sum);
-    if (lane == 0) red[4 + wave] = sum;
-    __syncthreads();
-    lse = mx + logf(red[4] + red[5] + red[6] + red[7]);
-  }
+  if (!zero_row) lse = block_row_lse(row, V, red);   // rule 1
 
   // rules 2-3: chunk sums, then the block's exclusive scan of them
   const int chunk = (V + 255) / 256;
@@ -128,8 +115,6 @@ sample_draw_kernel(const float* __restrict__ x, long ld, int V, int32_t* __restr
   hist[r * cols + step] = c + 1;
   tok[r] = c + 1;
 }
-
-inline unsigned grid_for(long n) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, 4096)); }
 
 }  // namespace
 

@@ -120,39 +120,34 @@ class SplitEval(object):
         answerTable = []
         self._set_training(False)
         img_ids = getattr(dataloader, 'unique_img_' + dtype, None)
-        if beamBatch > 0:
-            for first in range(1, numThreads + 1, beamBatch):
-                convIds = np.arange(first, min(first + beamBatch, numThreads + 1))
-                batch = dataloader.getIndexData(convIds, self.params, dtype)
-                R = batch['ques_fwd'].shape[1]
-                self._gen_encode(batch)
-                tokens, _ = self._gen_beam(beamSize, beamLen, startToken, endToken)   # row = dialog * R + round
-                for i, convId in enumerate(convIds):
-                    threadAnswers = [{'question': utils.idToWords(batch['ques_fwd'][i, it], ind2word),
-                                      'answer': utils.idToWords(tokens[i * R + it], ind2word)} for it in range(R)]
-                    answerTable.append({'image_id': img_ids[convId - 1] if img_ids else int(convId), 'dialog': threadAnswers})
-            self._set_training(True)
-            return answerTable
-        if sampleBatch > 0:
-            for first in range(1, numThreads + 1, sampleBatch):
-                convIds = np.arange(first, min(first + sampleBatch, numThreads + 1))
+
+        def record(convId, questions, answers):
+            """{image_id, dialog: [{question, answer}...]}: one question row and one answer row per round"""
+            return {'image_id': img_ids[convId - 1] if img_ids else int(convId),
+                    'dialog': [{'question': utils.idToWords(q, ind2word), 'answer': utils.idToWords(a, ind2word)}
+                               for q, a in zip(questions, answers)]}
+        chunk = sampleBatch if sampleWords else beamBatch
+        if chunk > 0:
+            for first in range(1, numThreads + 1, chunk):
+                convIds = np.arange(first, min(first + chunk, numThreads + 1))
                 batch = dataloader.getIndexData(convIds, self.params, dtype)
                 B, R = len(convIds), batch['ques_fwd'].shape[1]
                 self._gen_encode(batch)
-                u = rng.random_sample((B, beamLen, R))      # the per-dialog loop's draws: dialog, then step, then round
-                tokens, _ = self._gen_sample(beamLen, startToken, endToken, temperature,
-                                             u.transpose(1, 0, 2).reshape(beamLen, B * R))   # [step x row], row = dialog * R + round
-                for i, convId in enumerate(convIds):
-                    threadAnswers = [{'question': utils.idToWords(batch['ques_fwd'][i, it], ind2word),
-                                      'answer': utils.idToWords(tokens[i * R + it], ind2word)} for it in range(R)]
-                    answerTable.append({'image_id': img_ids[convId - 1] if img_ids else int(convId), 'dialog': threadAnswers})
+                if sampleWords:
+                    u = rng.random_sample((B, beamLen, R))      # the per-dialog loop's draws: dialog, then step, then round
+                    tokens, _ = self._gen_sample(beamLen, startToken, endToken, temperature,
+                                                 u.transpose(1, 0, 2).reshape(beamLen, B * R))   # [step x row]
+                else:
+                    tokens, _ = self._gen_beam(beamSize, beamLen, startToken, endToken)
+                answerTable += [record(convId, batch['ques_fwd'][i], tokens[i * R:(i + 1) * R])    # row = dialog * R + round
+                                for i, convId in enumerate(convIds)]
             self._set_training(True)
             return answerTable
         for convId in range(1, numThreads + 1):
             batch = dataloader.getIndexData(np.array([convId]), self.params, dtype)
             R = batch['ques_fwd'].shape[1]
             self._gen_encode(batch)                                               # forwardBackward(batch, true, true)
-            threadAnswers = []
+            answers = []
             if not sampleWords:
                 for it in range(R):
                     beams = np.zeros((beamLen, beamSize), np.int64)
@@ -182,9 +177,7 @@ class SplitEval(object):
                             beams[:, i] = c['beam']
                             scores[i] = c['score']
                     finish.sort(key=lambda a: -a['score'])
-                    best = finish[0]['beam'] if finish else beams[:, 0]               # (the reference errors if none ended)
-                    threadAnswers.append({'question': utils.idToWords(batch['ques_fwd'][0, it], ind2word),
-                                          'answer': utils.idToWords(best, ind2word)})
+                    answers.append(finish[0]['beam'] if finish else beams[:, 0])      # (the reference errors if none ended)
             else:
                 numQues = R
                 self._gen_begin(np.arange(R, dtype=np.int32))
@@ -198,10 +191,7 @@ class SplitEval(object):
                     nxt = np.array([rng.choice(pr.shape[1], p=pr[i]) + 1 for i in range(numQues)], np.int64)
                     answer.append(nxt[:, None])
                     answerIn = nxt
-                answer = np.concatenate(answer, 1)
-                for it in range(R):
-                    threadAnswers.append({'question': utils.idToWords(batch['ques_fwd'][0, it], ind2word),
-                                          'answer': utils.idToWords(answer[it], ind2word)})
-            answerTable.append({'image_id': img_ids[convId - 1] if img_ids else convId, 'dialog': threadAnswers})
+                answers = np.concatenate(answer, 1)
+            answerTable.append(record(convId, batch['ques_fwd'][0], answers))
         self._set_training(True)
         return answerTable
