@@ -31,10 +31,16 @@ def main():
     ap.add_argument('--numThreads', type=int, default=100, help='synthetic fallback only')
     ap.add_argument('-host', '--host', default='python', choices=['python', 'native'],
                     help="'native' drives the model-level C ABI (what lua/model.lua calls)")
+    ap.add_argument('-fusedLhood', '--fusedLhood', type=int, default=0, choices=[0, 1],
+                    help='gen decoder: score the candidates from their live (non-pad) rows only, through the fused vocabulary '
+                         'projection + online log-sum-exp head (no logits buffer); 0 = the dense head')
     a = ap.parse_args()
     saved = load_checkpoint(a.loadPath)
     p = opts.derive(saved['modelParams'])                    # sets useHistory / useIm / concatHistory (evaluate.lua:69-75)
     p['gpuid'], p['batchSize'], p['useGt'] = a.gpuid, a.batchSize, bool(a.useGt)
+    if a.fusedLhood and p['decoder'] != 'gen':
+        raise SystemExit('-fusedLhood 1: the live-row log-likelihood head is only for a generative model')
+    p['fusedLhood'] = a.fusedLhood
     p.update(inputImg=a.inputImg, inputQues=a.inputQues, inputJson=a.inputJson)
     have = lambda f: os.path.exists(f) or os.path.exists(f[:-3] + '.npz')
     if os.path.exists(a.inputJson) and have(a.inputQues):

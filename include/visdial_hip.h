@@ -35,8 +35,8 @@ const char* vd_last_error(void);
 /* Bumped whenever an exported symbol is removed or the meaning of an argument changes; hosts compare it with the VD_ABI_VERSION they
  * were written against right after loading (visdial_amd/_lib.py, lua/visdial_ffi.lua).  2 = round 4's surface: vd_tune_set /
  * vd_tune_clear / vd_lstm_seq_status removed, vd_model_params.lstmBf16 also takes 3 / 6 / 9 (exact-operand split).  Adding entry points
- * does not bump it: 97 entry points (58 operator-level, 32 model-level, 7 vd_comm_*), vd_beam_* / vd_model_beam_search and
- * vd_sample_* / vd_model_sample added under 2. */
+ * does not bump it: 101 entry points (61 operator-level, 33 model-level, 7 vd_comm_*), vd_beam_* / vd_model_beam_search,
+ * vd_sample_* / vd_model_sample and vd_lhood_* / vd_model_retrieve_lhood added under 2. */
 #define VD_ABI_VERSION 2
 int vd_abi_version(void);
 int vd_device_count(int* count);
@@ -231,6 +231,24 @@ int vd_score_ce(const float* optH, const float* enc, const int32_t* gt, float* s
  * by d loss / d logits (softmax - onehot, zero rows at pads). */
 int vd_logsoftmax_nll(float* logits, int64_t ld, int64_t rows, int V, const int32_t* tok_in,
                       const int32_t* target, float* loss_rows, int write_grad, void* stream);
+/* ---- live-row log-likelihood head of generative retrieval (model.lua:392-420 + utils.computeLhood, utils.lua:86-102;
+ *      csrc/lhood.hip): the candidate scores of vd_gemm_nt + vd_logsoftmax_nll + a sum over time, computed from the rows that
+ *      count only and without a [rows x V] logits buffer.  Deterministic: no atomics, fixed reduction orders.
+ *   live_rows  act = the linear indices i in [0, n) with tok_in[i] != 0 and target[i] > 0, ascending (for time-major
+ *              [T x rows] tokens: step-major, then row); `work` is device int32[(n + 1023) / 1024 + 1]; *host_count = their
+ *              number, returned with ONE stream synchronisation
+ *   nll        nll[i] = logsumexp_v(h[act[i]] . W[v] + bias[v]) - (h[act[i]] . W[target[act[i]] - 1] + bias[...]), i < n_act:
+ *              h [rows x ldh] (H valid columns), act values in [0, rows), target int32[rows] 1-based vocabulary ids, W [V x ldw],
+ *              bias [V] or NULL; fp32 operands on v_mfma_f32, online log-sum-exp.  Two live rows with the same h row and
+ *              target get bit-identical values.  n_act = 0 returns at once.
+ *   sum        out[(r / C) * ldo + r % C] = -(sum over t of the nll of row t * rows + r, in step order), r < rows; a row of
+ *              `act` (ascending, as live_rows writes it) that is absent contributes nothing, a candidate without one scores 0 */
+int vd_lhood_live_rows(const int32_t* tok_in, const int32_t* target, int64_t n, int32_t* act, int32_t* work, int32_t* host_count,
+                       void* stream);
+int vd_lhood_nll(const float* h, int64_t ldh, int64_t rows, const int32_t* act, int64_t n_act, const int32_t* target, const float* W,
+                 int64_t ldw, const float* bias, int V, int H, float* nll, void* stream);
+int vd_lhood_sum(const float* nll, const int32_t* act, int64_t n_act, int T, int64_t rows, int C, float* out, int64_t ldo,
+                 void* stream);
 /* in-place nn.LogSoftMax over `rows` rows of V logits (sampling / beam search, model.lua:432-613) */
 int vd_log_softmax_rows(float* x, int64_t ld, int64_t rows, int V, void* stream);
 /* utils.computeRanks (utils.lua:106-128): 1-based descending-sort position of every option */
@@ -365,6 +383,10 @@ int vd_model_loss(vd_model* m, float* loss);              /* curLoss of the last
 /* Model:retrieveBatch up to the option scores (model.lua:344-425): disc = scores of a forward pass, gen = candidate
  * log-likelihoods (utils.computeLhood, utils.lua:86-102); read with vd_model_scores / vd_model_ranks */
 int vd_model_retrieve(vd_model* m);
+/* the same contract for the generative decoder through the live-row head (vd_lhood_* above): scores within the fp32 rounding of
+ * vd_model_retrieve's, no logits buffer, one host synchronisation per chunk of options (the live-row count).  An argument error
+ * that names the decoder for `disc`. */
+int vd_model_retrieve_lhood(vd_model* m);
 /* wrapperdW*gscale -> clamp(-5,5) -> adam -> lr decay (model.lua:96-105; optim_updates.lua:62-91) */
 int vd_model_update(vd_model* m, float gscale);
 int vd_model_learning_rate(vd_model* m, double* lr, int set);

@@ -180,7 +180,14 @@ end
 function Model:retrieveBatch(batch)
     self:commitW()
     self:upload(batch); self.havePrefetched = false
-    vd.call('vd_model_retrieve', self.h)                               -- disc: option scores; gen: candidate log-likelihoods
+    -- params.fusedLhood = 1 (gen): the candidate log-likelihoods from the live (non-pad) rows only, through the fused vocabulary
+    -- projection + online log-sum-exp head (vd_model_retrieve_lhood: no logits buffer); same scores contract
+    if (self.params.fusedLhood or 0) ~= 0 then
+        if self.params.decoder ~= 'gen' then error('fusedLhood: the live-row log-likelihood head is only for generative model') end
+        vd.call('vd_model_retrieve_lhood', self.h)
+    else
+        vd.call('vd_model_retrieve', self.h)                           -- disc: option scores; gen: candidate log-likelihoods
+    end
     local N = batch['ques_fwd']:size(1) * batch['ques_fwd']:size(2)
     local O = self.numOptions
     local useGt = self.params.useGt and 1 or 0

@@ -65,6 +65,9 @@ PROTOTYPES = {
     "vd_mask_time_backward": [_p, _p, _p, _i, _i, _i, _p],
     "vd_log_softmax_rows": [_p, _l, _l, _i, _p],
     "vd_logsoftmax_nll": [_p, _l, _l, _i, _p, _p, _p, _i, _p],
+    "vd_lhood_live_rows": [_p, _p, _l, _p, _p, _p, _p],
+    "vd_lhood_nll": [_p, _l, _l, _p, _l, _p, _p, _l, _p, _i, _i, _p, _p],
+    "vd_lhood_sum": [_p, _p, _l, _i, _l, _i, _p, _l, _p],
     "vd_gemm_nt": [_p, _l, _p, _l, _p, _p, _l, _i, _i, _i, _i, _i, _p],
     "vd_gemm_nn": [_p, _l, _p, _l, _p, _p, _l, _i, _i, _i, _i, _p],
     "vd_gemm_tn_acc": [_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _p],
@@ -133,6 +136,7 @@ PROTOTYPES = {
     "vd_model_forward_backward": [_p, _i],
     "vd_model_loss": [_p, C.POINTER(C.c_float)],
     "vd_model_retrieve": [_p],
+    "vd_model_retrieve_lhood": [_p],
     "vd_model_encode": [_p],
     "vd_model_decode_begin": [_p, _p, _i],
     "vd_model_decode_step": [_p, _p, _p],

@@ -557,13 +557,14 @@ __device__ __forceinline__ void glds16(unsigned voff, const float* sbase, unsign
       : "memory");
 }
 
-// KMAJ == false: A[M x K] rows, Bt[N x K] rows (k contiguous), tiles [row][16 k] with swizzled chunks.
+// KMAJ == false: A[M x K] rows, Bt[N x K] rows (k contiguous), tiles [row][16 k] with swizzled chunks.  With `brows` (row-major
+//                tiles only) row n of Bt is B[brows[n]]: the operand is gathered through an index list (lhood.hip).
 // KMAJ == true : A[K x M] rows, B[K x N] rows (k = row index: weight gradients X^T * dY), tiles [16 k][128]
 //                dense; fragments are ds_read_b32 (32 consecutive floats per half-wave, conflict-free).
 template <class Cfg, bool KMAJ, class Epi>
 __device__ __forceinline__ void gemm_block_glds(int M, int N, int ks, int ke, int row_base, int col_base,
                                                 int rot_seed, const float* A, long lda, const float* B, long ldb,
-                                                const Epi& epi, float* smem, int tid_in = -1) {
+                                                const Epi& epi, float* smem, int tid_in = -1, const int* brows = nullptr) {
   constexpr int WM = Cfg::WM, NT = Cfg::NT;
   constexpr int BM = Cfg::BM, BN = Cfg::BN;
   constexpr int NIA = (BM / 16) / WM, NIB = (BN / 16) / WM;  // DMA instructions per wave per tile
@@ -617,7 +618,8 @@ __device__ __forceinline__ void gemm_block_glds(int M, int N, int ks, int ke, in
     } else {
       const int r = (i * WM + wm) * 16 + (lane >> 2);
       const int c = (lane & 3) ^ ((r >> 2) & 3);
-      voffb[i] = (unsigned)(((long)min(col_base + r, N - 1) * ldb + c * 4) * 4);
+      const int br = min(col_base + r, N - 1);
+      voffb[i] = (unsigned)(((long)(brows ? brows[br] : br) * ldb + c * 4) * 4);
     }
   }
   float* const sA = smem;

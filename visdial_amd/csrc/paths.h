@@ -47,3 +47,11 @@ static inline bool vd_tn_split_tiles(long M, long N) { return M % VD_SPLIT_TN_BM
 static inline bool vd_img_split_ok(long rows, int H, int Kc) {
   return rows >= 128 && H % 16 == 0 && Kc % 16 == 0 && rows * (H > Kc ? H : Kc) * 4 < (1L << 32);
 }
+
+// ---- live-row log-likelihood head of generative retrieval (lhood.hip vd_lhood_nll; rt_decoders.h Gen::retrieve_lhood) -------------
+// fused MFMA kernel (vocabulary tiles through the LDS-DMA pipeline, online log-sum-exp): K % 16 == 0, 16-byte rows and 32-bit row byte
+// offsets of both operands (h [rows x ldh] gathered by row index, W [V x ldw]), and at least one full 128-wide vocabulary tile.  Every
+// other shape (the small H and V of the test models) takes the one-workgroup-per-row kernel of the same entry point.
+static inline bool vd_lhood_fused_fits(long rows, long ldh, long V, long ldw, int H) {
+  return H >= 64 && H % 16 == 0 && V >= 128 && ldh % 4 == 0 && ldw % 4 == 0 && rows * ldh * 4 < (1L << 32) && V * ldw * 4 < (1L << 32);
+}

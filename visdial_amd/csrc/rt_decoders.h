@@ -13,6 +13,11 @@ struct Decoder {
   virtual int forward_backward(vd_model* m, BatchSlot& b, bool only_forward) = 0;
   // Model:retrieveBatch up to the scores: leaves [N x O] option scores in m->scores
   virtual int retrieve(vd_model* m, BatchSlot& b) = 0;
+  // the same through the live-row log-likelihood head (vd_model_retrieve_lhood); generative decoder only
+  virtual int retrieve_lhood(vd_model*, BatchSlot&) {
+    vd_set_error("vd_model_retrieve_lhood: the live-row log-likelihood head scores candidates of decoder 'gen'; this model's decoder is 'disc'");
+    return VD_ERR_ARG;
+  }
   // Model:generateAnswers device steps (model.lua:432-613); generative decoder only
   virtual int gen_begin(vd_model*, const int32_t*, int) { return no_gen(); }
   virtual int gen_step(vd_model*, const int32_t*, float*) { return no_gen(); }
@@ -317,7 +322,11 @@ struct Gen : Decoder {
   // Model:retrieveBatch gen branch (model.lua:392-420) + utils.computeLhood (utils.lua:86-102).  The reference loops
   // over the 100 options; here chunks of options are ONE decoder batch (rows = round x option) seeded by the replicated
   // encoder state, and the [rows x V] logits only ever exist for one chunk.
-  int retrieve(vd_model* m, BatchSlot& b) override {
+  int retrieve(vd_model* m, BatchSlot& b) override { return retrieve_head(m, b, false); }
+  // vd_model_retrieve_lhood: the same encoder forward, forwardConnect replication, embedding gather and lstm_stack_forward; the head
+  // is vd_lhood_live_rows + vd_lhood_nll + vd_lhood_sum (csrc/lhood.hip) over the live rows of the chunk, with no logits buffer
+  int retrieve_lhood(vd_model* m, BatchSlot& b) override { return retrieve_head(m, b, true); }
+  int retrieve_head(vd_model* m, BatchSlot& b, bool live) {
     VD_CHECK_ARG(b.oin.present && b.oout.present, "retrieval with decoder 'gen' needs batch.option_in / option_out");
     hipStream_t s = m->s_main;
     const int N = b.q.N, O = m->p.numOptions, T = b.oin.T;
@@ -326,8 +335,11 @@ struct Gen : Decoder {
     const int seqLen = m->enc->seqLen(b);
     float* lhood;
     VD_TRY(ws_get(m, "ret.lhood", (size_t)N * O, &lhood));
-    const long per_opt = (long)T * N * Vp;
-    const int oc = (int)std::max<long>(1, std::min<long>(O, (1L << 30) / std::max<long>(1, per_opt)));   // <= 4 GiB of logits
+    // floats one option adds to a chunk's workspace.  Dense head: the [T*N x Vp] logits dominate, <= 4 GiB of them.  Live-row head:
+    // what is still materialised is the decoder's input and saved state, (E + 6 H per layer: gates 4H, h, c) floats per (step, row),
+    // held to the same 4 GiB -- and to the 32-bit row byte offsets of h in the fused kernel (T * rows * H * 4 < 4 GiB, implied).
+    const long per_opt = (long)T * N * (live ? E + 6 * H * (long)rnn.size() : Vp);
+    const int oc = (int)std::max<long>(1, std::min<long>(O, (1L << 30) / std::max<long>(1, per_opt)));
     for (int o0 = 0; o0 < O; o0 += oc) {
       const int C = std::min(O, o0 + oc) - o0;
       const long rows = (long)N * C;
@@ -343,18 +355,27 @@ struct Gen : Decoder {
       VD_TRY(forwardConnect(m, s, encOut, seqLen, idx, rows));
       float *x, *h, *logits, *nll, *acc;
       VD_TRY(ws_get(m, "ret.x", (size_t)T * rows * E, &x));
-      VD_TRY(ws_get(m, "ret.logits", (size_t)T * rows * Vp, &logits));
       VD_TRY(ws_get(m, "ret.nll", (size_t)T * rows, &nll));
-      VD_TRY(ws_get(m, "ret.acc", (size_t)rows, &acc));
       VD_TRY(vd_embed_gather(Wp(m, "embed"), cin, nullptr, x, T * rows, (int)E, 1.f, s));
       VD_TRY(lstm_stack_forward(m, s, rnn, {x}, T, (int)rows, cin, &h));
+      if (live) {
+        int32_t *act, *work, n_act = 0;
+        VD_TRY(ws_get(m, "ret.act", (size_t)T * rows, &act));
+        VD_TRY(ws_get(m, "ret.act_work", (size_t)(T * rows + 1023) / 1024 + 1, &work));
+        VD_TRY(vd_lhood_live_rows(cin, cout, T * rows, act, work, &n_act, s));        // the chunk's one host synchronisation
+        VD_TRY(vd_lhood_nll(h, H, T * rows, act, n_act, cout, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), (int)V, (int)H, nll, s));
+        VD_TRY(vd_lhood_sum(nll, act, n_act, T, rows, C, lhood + o0, O, s));          // log-likelihood = -NLL, summed over time
+        continue;
+      }
+      VD_TRY(ws_get(m, "ret.logits", (size_t)T * rows * Vp, &logits));
+      VD_TRY(ws_get(m, "ret.acc", (size_t)rows, &acc));
       VD_TRY(vd_gemm_nt(h, H, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), logits, Vp, (int)(T * rows), (int)V, (int)H, VD_ACT_NONE, 0, s));
       VD_TRY(vd_logsoftmax_nll(logits, Vp, T * rows, (int)V, cin, cout, nll, 0, s));
       VD_TRY(vd_memset(acc, 0, rows * 4, s));
       VD_TRY(vd_colsum_acc(nll, rows, T, (int)rows, acc, s));                       // sum over time (utils.lua:98)
       VD_TRY(vd_copy_2d(lhood + o0, O, acc, C, N, C, s));
     }
-    VD_TRY(vd_axpby(lhood, nullptr, lhood, (long)N * O, -1.f, 0.f, s));             // log-likelihood = -NLL
+    if (!live) VD_TRY(vd_axpby(lhood, nullptr, lhood, (long)N * O, -1.f, 0.f, s));  // log-likelihood = -NLL
     m->scores = lhood;
     m->prof_valid = false;
     return VD_OK;

@@ -516,6 +516,16 @@ int vd_model_retrieve(vd_model* m) {
   return rc;
 }
 
+// vd_model_retrieve for the generative decoder through the live-row log-likelihood head (csrc/lhood.hip)
+int vd_model_retrieve_lhood(vd_model* m) {
+  VdRange r("vd_model_retrieve_lhood");
+  BatchSlot* b = nullptr;
+  VD_TRY(begin_step(m, false, &b));
+  const int rc = m->dec->retrieve_lhood(m, *b);
+  VD_HIP(hipEventRecord(b->done, m->s_main));
+  return rc;
+}
+
 // Model:generateAnswers, device side (model.lua:432-613).  vd_model_encode = `forwardBackward(batch, true, true)`
 // (model.lua:464): encoder forward of the uploaded batch, state kept for vd_model_decode_begin.
 int vd_model_encode(vd_model* m) {

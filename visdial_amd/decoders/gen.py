@@ -97,7 +97,12 @@ class Decoder(object):
         enc = model.encoder
         layers = getattr(enc, 'rnnLayers', None)
         lhood = ws.get('ret.lhood', (N, O))
-        oc = max(1, min(O, int((1 << 30) // max(1, T * N * Vp))))           # options per chunk: <= 4 GiB of logits
+        # params fusedLhood: the live-row head (csrc/lhood.hip) -- live-row list, fused projection + online log-sum-exp over the live
+        # rows, per-candidate sum; no logits.  A chunk is then sized by what is still materialised: the decoder's input and saved
+        # state, (E + 6 H per layer) floats per (step, row), <= 4 GiB
+        live = bool(int(self.p.get('fusedLhood', 0) or 0))
+        per_opt = T * N * (self.E + 6 * H * len(self.rnnLayers) if live else Vp)
+        oc = max(1, min(O, int((1 << 30) // max(1, per_opt))))              # options per chunk: <= 4 GiB of logits
         tin = option_in.view(T, N, O)
         tout = option_out.view(T, N, O)
         for o0 in range(0, O, oc):
@@ -121,14 +126,23 @@ class Decoder(object):
             x = ws.get('ret.x', (T * rows, self.E))
             ops.embed_gather(self.emb, cin, x)
             h = lstm_stack_forward(self.rnnLayers, x, T, rows, cin).view(T * rows, H)
+            nll = ws.get('ret.nll', (T, rows))
+            if live:
+                act = ws.get('ret.act', (T * rows,), torch.int32)
+                work = ws.get('ret.act_work', ((T * rows + 1023) // 1024 + 1,), torch.int32)
+                n_act = ops.lhood_live_rows(cin.view(-1), cout.view(-1), act, work)
+                ops.lhood_nll(h, act, n_act, cout.view(-1), self.Wv, self.bv, nll.view(-1), V=V, H=H)
+                ops.lhood_sum(nll.view(-1), act, n_act, T, rows, C, lhood, O, dst_off=o0)
+                continue
             logits = ws.get('ret.logits', (T * rows, Vp))
             ops.gemm_nt(h, self.Wv, logits, bias=self.bv, M=T * rows, N=V, K=H, ldc=Vp)
-            nll = ws.get('ret.nll', (T, rows))
             ops.logsoftmax_nll(logits, V, cin.view(-1), cout.view(-1), nll.view(-1), write_grad=False)
             acc = ws.get('ret.acc', (rows,))
             ops.zero(acc)
             ops.colsum_acc(nll, acc, M=T, N=rows)                            # sum over time (utils.lua:98)
             ops.copy_2d(lhood, O, acc, C, N, C, dst_off=o0)
+        if live:
+            return lhood
         return ops.axpby(lhood, None, lhood, -1.0, 0.0)                       # log-likelihood = -NLL
 
 

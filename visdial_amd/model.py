@@ -297,6 +297,9 @@ class Model(SplitEval):
 
     # ------------------------------------------------------------------ retrieval (model.lua:142-246,344-430)
     def retrieveBatch(self, batch):
+        if int(self.params.get('fusedLhood', 0) or 0) and self.params['decoder'] != 'gen':
+            raise ValueError("fusedLhood: the live-row log-likelihood head is only for the generative decoder, not '%s'"
+                             % self.params['decoder'])
         inputs, dec_in = self.prepare_inputs(batch)
         ops.zero(self.fp.w['embed'][0])
         encOut = self.encoder.forward(inputs)

@@ -282,7 +282,8 @@ class NativeModel(SplitEval):
         if useGt is None:
             useGt = bool(self.params.get('useGt', True))
         self.upload(batch)
-        call("vd_model_retrieve", self.h)
+        # params fusedLhood: the generative decoder's candidates through the live-row log-likelihood head (a disc model: argument error)
+        call("vd_model_retrieve_lhood" if int(self.params.get('fusedLhood', 0) or 0) else "vd_model_retrieve", self.h)
         N, O = self._N, int(self.params.get('numOptions', 100))
         out = np.empty(N if useGt else (N, O), np.int32)
         call("vd_model_ranks", self.h, int(useGt), out.ctypes.data)

@@ -112,6 +112,32 @@ def colsum_acc(X, out, M=None, N=None, ld=None):
     return out
 
 
+# ---------------------------------------------------------------- live-row log-likelihood head (csrc/lhood.hip)
+def lhood_live_rows(tok_in, target, act, work):
+    """act[:n] = ascending linear indices i with tok_in[i] != 0 and target[i] > 0; returns n (one stream synchronisation)"""
+    import ctypes
+    n = tok_in.numel()
+    assert target.numel() == n and act.numel() >= n and work.numel() >= (n + 1023) // 1024 + 1
+    count = ctypes.c_int32(0)
+    call("vd_lhood_live_rows", _p(tok_in, I32), _p(target, I32), n, _p(act, I32), _p(work, I32), ctypes.addressof(count), _stream())
+    return int(count.value)
+
+
+def lhood_nll(h, act, n_act, target, W, bias, nll, V=None, H=None):
+    """nll[i] = logsumexp_v(h[act[i]] @ W[v] + bias[v]) - logit of target[act[i]] - 1, i < n_act; no logits in memory"""
+    V = W.shape[0] if V is None else V
+    H = W.shape[1] if H is None else H
+    call("vd_lhood_nll", _p(h, F32), h.stride(0), h.shape[0], _p(act, I32), int(n_act), _p(target, I32), _p(W, F32), W.stride(0),
+         _p(bias, F32), V, H, _p(nll, F32), _stream())
+    return nll
+
+
+def lhood_sum(nll, act, n_act, T, rows, C, out, ldo, dst_off=0):
+    """out[(r // C) * ldo + r % C + dst_off] = -(sum over t of the nll of row t * rows + r), r < rows"""
+    call("vd_lhood_sum", _p(nll, F32), _p(act, I32), int(n_act), T, rows, C, _p(out, F32) + 4 * dst_off, ldo, _stream())
+    return out
+
+
 # ---------------------------------------------------------------- LSTM
 def lstm_forward(xproj, Wh, gates, h, c, T, N, H, x_tstride, x_ld, tok_gather=None, tok_mask=None, h0=None, c0=None,
                  flags=0):
