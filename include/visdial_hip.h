@@ -65,6 +65,15 @@ int vd_copy_2d(float* dst, int64_t dst_ld, const float* src, int64_t src_ld, int
 #define VD_FLAG_SPLIT9 2
 #define VD_FLAG_SPLIT6 4
 #define VD_FLAG_SPLIT3 8
+/* VD_FLAG_LIVE_PREFIX (vd_lstm_forward, with tok_mask): the caller promises that at every step the rows with tok_mask != 0 are a
+ * PREFIX of the N rows (sequences left-aligned and ordered by descending length).  Row groups that hold no live row are then not
+ * computed and their gates / h / c rows are left UNWRITTEN.  A group is the row tile of the step kernel that runs (32 or 128 rows);
+ * VD_LIVE_PREFIX_ROWS is a multiple of every forward step kernel's row tile: rows at or beyond ceil(live rows of the step /
+ * VD_LIVE_PREFIX_ROWS) * VD_LIVE_PREFIX_ROWS are never written, whichever kernel ran.  A group with a live row computes exactly
+ * what it computes without the flag, its pad rows included (zeroed by tok_mask).  Exact fp32 only: together with VD_FLAG_BF16 or a
+ * VD_FLAG_SPLIT* the call is refused with an argument error. */
+#define VD_FLAG_LIVE_PREFIX 16
+#define VD_LIVE_PREFIX_ROWS 128
 
 /* ---- dense contractions (nn.Linear / hoisted SeqLSTM input projection / weight grads) -- */
 /* C[MxN] (+)= act(A[MxK] * W[NxK]^T + bias)   -- nn.Linear:updateOutput (+nn.Tanh),
@@ -97,9 +106,11 @@ int vd_colsum_acc(const float* X, int64_t ld, int M, int N, float* out, void* st
  * Outputs: gates [T x N x 4H] post-activation (i,f,o,g), h and c [T x N x H].
  * Limits: one step's slice of every tensor below 4 GB (N * 4H * 4 bytes; a projection table: its rows * x_ld * 4 bytes --
  * 524 288 table rows at H = 512): the epilogue uses 32-bit byte offsets.  Larger batches: call per row range.
- * Throughput shapes (N >= 2048) run the whole recurrence as ONE persistent launch (tile queues + per-row-tile
- * arrival counters; csrc/lstm.hip) on the LDS-DMA pipeline; its work buffers (4H x H gate-interleaved transpose
- * of Wh, queue heads, counters) are library-owned per (device, stream), so calls on different streams may overlap. */
+ * One kernel launch per step.  Throughput shapes (N >= 2048) take the LDS-DMA pipeline (csrc/lstm.hip), which multiplies
+ * by a gate-interleaved transpose of Wh [4H x H] made once per call; that work buffer is library-owned per (device, stream),
+ * so calls on different streams may overlap.
+ * flags: VD_FLAG_BF16 / VD_FLAG_SPLIT* choose the arithmetic of the recurrent product; VD_FLAG_LIVE_PREFIX (above) skips the
+ * row groups without a live row. */
 int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const int32_t* tok_gather,
                     const int32_t* tok_mask, const float* Wh, const float* h0, const float* c0, float* gates,
                     float* h, float* c, int T, int N, int H, int flags, void* stream);

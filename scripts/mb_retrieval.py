@@ -4,7 +4,10 @@ params fusedLhood = 1: csrc/lhood.hip).  lf-ques-im-hist + gen, H = 512, V = 11 
 options, T = 21, random weights.  Two candidate-length profiles, per profile: live rows / total rows, the executed GEMM FLOPs of both
 heads (from shapes), batches/s of both heads alternated in one process after warm-up with the spread over the repeats, the worst
 |score difference| and the number of rounds whose ground-truth rank differs.
-    python scripts/mb_retrieval.py [--repeats 7] [--only fused --profile uniform|short]   (--only fused: that head alone, for a trace)"""
+    python scripts/mb_retrieval.py [--repeats 7] [--only fused --profile uniform|short]   (--only fused: that head alone, for a trace)
+A/B of two libraries (VD_LIB_PATH selects one): --tag NAME marks the process's lines, every profile also prints option_rows() of the
+last fused call (the rows the candidate recurrence ran), and --save-scores PATH.npz keeps the fused scores per profile so that two
+libraries' scores can be compared afterwards."""
 import argparse
 import os
 import sys
@@ -21,6 +24,8 @@ ap = argparse.ArgumentParser(description='dense vs live-row log-likelihood head 
 ap.add_argument('--repeats', type=int, default=7)
 ap.add_argument('--only', choices=('fused',), help='the live-row head alone, for a kernel trace')
 ap.add_argument('--profile', choices=('uniform', 'short'), help='one length profile only')
+ap.add_argument('--tag', default='', help='printed in front of the per-head lines (A/B of two libraries)')
+ap.add_argument('--save-scores', default='', help='write the fused scores of every profile to this .npz')
 opt = ap.parse_args()
 V, H, R, O, B, L = 11322, 512, 10, 100, 20, 20
 T = L + 1
@@ -65,6 +70,7 @@ def run(fused, batch):
     return time.perf_counter() - t0, gt
 
 
+saved = {}
 for profile in ([opt.profile] if opt.profile else ['uniform', 'short']):
     rng = np.random.RandomState(77)
     lens = lengths(profile, N * O, rng)
@@ -77,6 +83,9 @@ for profile in ([opt.profile] if opt.profile else ['uniform', 'short']):
     for f in heads:                                  # warm-up: workspaces, code objects
         run(f, batch)
         run(f, batch)
+    if 1 in heads:
+        ex, tot = nat.option_rows()
+        print("  %soption_rows after the fused head: executed %d of %d = %.3f" % (opt.tag and opt.tag + ' ', ex, tot, ex / max(tot, 1)))
     times = {f: [] for f in heads}
     res = {}
     for _ in range(opt.repeats):                     # alternated
@@ -86,11 +95,15 @@ for profile in ([opt.profile] if opt.profile else ['uniform', 'short']):
             res[f] = (gt, nat.scores(N, O).copy())
     for f in heads:
         t = np.asarray(times[f])
-        print("  %-8s %7.2f ms per batch (median of %d; min %.2f, max %.2f) = %6.2f batches/s" % (
-            'fused' if f else 'dense', np.median(t) * 1e3, len(t), t.min() * 1e3, t.max() * 1e3, 1.0 / np.median(t)), flush=True)
+        print("  %s%-8s %7.2f ms per batch (median of %d; min %.2f, max %.2f) = %6.2f batches/s" % (
+            opt.tag and opt.tag + ' ', 'fused' if f else 'dense', np.median(t) * 1e3, len(t), t.min() * 1e3, t.max() * 1e3, 1.0 / np.median(t)), flush=True)
+    if opt.save_scores:
+        saved[profile] = res[1][1]
     if not opt.only:
         d, f = res[0], res[1]
         print("  speed-up %.2fx; worst |dense - fused| score %.3e (|score| max %.1f); rounds whose ground-truth rank differs: %d of %d"
               % (np.median(times[0]) / np.median(times[1]), np.abs(d[1].astype(np.float64) - f[1]).max(), np.abs(d[1]).max(),
                  int((d[0] != f[0]).sum()), N))
+if opt.save_scores:
+    np.savez(opt.save_scores, **saved)
 nat.close()

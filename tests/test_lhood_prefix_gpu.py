@@ -1,0 +1,364 @@
+"""Generative retrieval whose candidate recurrence runs only where there are tokens (VD_FLAG_LIVE_PREFIX of vd_lstm_forward, the length
+order of csrc/lhood.hip, vd_model_option_rows after vd_model_retrieve_lhood), on the GPU.
+
+Operator level: vd_lstm_forward with and without the flag on the same length-ordered input, outputs pre-filled with a sentinel -- rows
+inside the live prefix are bit-identical between the two calls, every row at or beyond ceil(nact[t] / G) * G (G = VD_LIVE_PREFIX_ROWS,
+a multiple of every step kernel's row tile) still holds the sentinel.  Both kernel families, dense and table mode, with and without h0.
+
+Model level: the three hosts against the fp64 oracle with the bound of test_fused_lhood_retrieval_matches_oracle_on_every_host, and the
+native host's option_rows(): live_in <= executed <= sum_t min(rows, ceil(nact[t] / G) * G), total = To * N * O.  The length / order
+kernels are library-internal (the C symbol set is frozen), so they are exercised through vd_model_retrieve_lhood: their order decides
+which candidate every score belongs to, their counts decide `executed`, their status word decides the fallback (executed == total).
+
+Worst |new fused - parent's fused| at full size is not asserted (profiles/lhood_retrieval.txt records it)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import visdial_oracle as vo
+from test_lhood_gpu import bound, dev, full_size_params, oracle_case, order_violations, profile_lengths, set_option_lengths
+from test_lhood_prefix_cpu import length_order, rows_run
+from visdial_amd.dataloader import SyntheticDataloader
+from visdial_amd.opts import default_params, derive
+
+pytestmark = pytest.mark.gpu
+SENTINEL = -12345.0
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+
+
+@pytest.fixture(scope="module")
+def private_pool():
+    """This module's device tensors (several of 250 MB) live in a memory pool of their own, released when the module ends: the tensor
+    library's default pool -- and with it which cached block a later module's tensors are carved from -- is left as this module found it.
+    (Hygiene only: where the tensor library offers no such pool the tests run from the default one and say so.)"""
+    pool = None
+    if torch.cuda.is_available():
+        try:
+            pool = torch.cuda.MemPool()
+            with torch.cuda.use_mem_pool(pool):
+                torch.empty(1024, device='cuda')
+        except (AttributeError, RuntimeError, TypeError) as e:
+            print('no private memory pool (%s): allocating from the default pool' % e)
+            pool = None
+    yield pool
+    del pool
+
+
+@pytest.fixture(autouse=True)
+def in_private_pool(private_pool):
+    if private_pool is None:
+        yield
+        return
+    with torch.cuda.use_mem_pool(private_pool):
+        yield
+
+
+# ------------------------------------------------------------------------------------------------------------------ the operator
+def run_lstm(tok, xproj, table, Wh, h0, c0, T, N, H, flags):
+    from visdial_amd import ops
+    gates = torch.full((T, N, 4 * H), SENTINEL, device='cuda')
+    h = torch.full((T, N, H), SENTINEL, device='cuda')
+    c = torch.full((T, N, H), SENTINEL, device='cuda')
+    if table is not None:
+        ops.lstm_forward(table, Wh, gates, h, c, T, N, H, 0, 4 * H, tok_gather=tok, tok_mask=tok, h0=h0, c0=c0, flags=flags)
+    else:
+        ops.lstm_forward(xproj, Wh, gates, h, c, T, N, H, N * 4 * H, 4 * H, tok_mask=tok, h0=h0, c0=c0, flags=flags)
+    torch.cuda.synchronize()
+    return [a.cpu().numpy() for a in (gates, h, c)]
+
+
+CASES = [
+    # name, H, N, nact per step
+    ('small: falls to nothing', 32, 300, [300, 290, 150, 33, 5, 0]),
+    ('small: constant', 32, 300, [300] * 5),
+    ('small: ragged tiles', 64, 203, [203, 97, 96, 31, 1]),
+    ('throughput: 4200 rows to under a tile', 512, 4200, [4200, 3000, 1500, 700, 300, 129, 60, 17]),
+    ('throughput: constant', 512, 4100, [4100] * 3),
+    ('throughput: a step with no live row', 512, 4200, [4200, 130, 0]),
+]
+
+
+@pytest.mark.parametrize("mode", ['dense', 'table'])
+@pytest.mark.parametrize("with_h0", [True, False])
+@pytest.mark.parametrize("name,H,N,nact", CASES)
+def test_lstm_forward_live_prefix_skips_dead_row_groups(gpu, name, H, N, nact, with_h0, mode):
+    from visdial_amd import ops
+    G = ops.LIVE_PREFIX_ROWS
+    rs = np.random.RandomState(11)
+    T, V = len(nact), 50
+    tok = np.zeros((T, N), np.int32)
+    for t, n in enumerate(nact):
+        tok[t, :n] = rs.randint(1, V + 1, size=n)
+    Wh = dev(rs.standard_normal((H, 4 * H)) / np.sqrt(H), torch.float32)
+    h0 = dev(rs.standard_normal((N, H)) * 0.5, torch.float32) if with_h0 else None
+    c0 = dev(rs.standard_normal((N, H)) * 0.5, torch.float32) if with_h0 else None
+    table = xproj = None
+    if mode == 'table':
+        table = dev(rs.standard_normal((V + 1, 4 * H)), torch.float32)
+    else:
+        xproj = torch.randn((T, N, 4 * H), device='cuda', generator=torch.Generator(device='cuda').manual_seed(5))
+    tk = dev(tok, torch.int32)
+    full = run_lstm(tk, xproj, table, Wh, h0, c0, T, N, H, 0)
+    live = run_lstm(tk, xproj, table, Wh, h0, c0, T, N, H, ops.FLAG_LIVE_PREFIX)
+    skipped = 0
+    for what, a, b in zip(('gates', 'h', 'c'), full, live):
+        assert not (a == SENTINEL).any(), what                 # without the flag every row is written
+        for t, n in enumerate(nact):
+            # inside the live prefix: the same kernel, the same tile, the same position -- the same bits
+            assert np.array_equal(a[t, :n].view(np.uint32), b[t, :n].view(np.uint32)), (what, t)
+            end = min(N, -(-n // G) * G)
+            assert (b[t, end:] == SENTINEL).all(), (what, t, 'a skipped row group was written')
+            skipped += N - end
+            # between the prefix and the end of its last row group: either computed as a pad row (zeros, as without the flag) or skipped
+            mid = b[t, n:end]
+            assert ((mid == 0) | (mid == SENTINEL)).all(), (what, t)
+    if nact[-1] == nact[0]:
+        assert skipped == 0                                    # nothing to skip: everything written, everything identical
+        for a, b in zip(full, live):
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    else:
+        assert skipped > 0
+
+
+def test_live_prefix_is_refused_with_other_arithmetic_and_without_a_mask(gpu):
+    from visdial_amd import ops
+    from visdial_amd._lib import VisdialHipError
+    T, N, H = 2, 64, 32
+    tok = torch.ones((T, N), dtype=torch.int32, device='cuda')
+    x = torch.zeros((T, N, 4 * H), device='cuda')
+    Wh = torch.zeros((H, 4 * H), device='cuda')
+    out = [torch.zeros((T, N, 4 * H), device='cuda'), torch.zeros((T, N, H), device='cuda'), torch.zeros((T, N, H), device='cuda')]
+    for other in (ops.FLAG_BF16, ops.FLAG_SPLIT9, ops.FLAG_SPLIT6, ops.FLAG_SPLIT3):
+        with pytest.raises(VisdialHipError, match=r"VD_FLAG_LIVE_PREFIX.*VD_FLAG_BF16 / VD_FLAG_SPLIT"):
+            ops.lstm_forward(x, Wh, out[0], out[1], out[2], T, N, H, N * 4 * H, 4 * H, tok_mask=tok, flags=ops.FLAG_LIVE_PREFIX | other)
+    with pytest.raises(VisdialHipError, match=r"VD_FLAG_LIVE_PREFIX needs tok_mask"):
+        ops.lstm_forward(x, Wh, out[0], out[1], out[2], T, N, H, N * 4 * H, 4 * H, flags=ops.FLAG_LIVE_PREFIX)
+
+
+# ------------------------------------------------------------------------------------------------------------------ model level
+def plant_lengths(batch, lens, vocab, rng):
+    """replace the candidates of a gen retrieval batch by left-aligned ones of the given lengths [N * O] (0 = empty)"""
+    B, R, O, T = batch['option_in'].shape
+    lens = np.asarray(lens)
+    oin = np.zeros((B * R * O, T), np.int32)
+    oout = np.zeros((B * R * O, T), np.int32)
+    body = rng.randint(1, vocab - 1, size=(B * R * O, T - 1)).astype(np.int32) * (np.arange(T - 1)[None, :] < lens[:, None])
+    oin[:, 0] = vocab - 1
+    oin[:, 1:] = body
+    oout[:, :T - 1] = body
+    oout[np.arange(len(lens)), lens] = np.where(lens > 0, vocab, 0)
+    batch['option_in'], batch['option_out'] = oin.reshape(B, R, O, T), oout.reshape(B, R, O, T)
+
+
+def counter_bounds(batch, executed, total, G):
+    """live_in <= executed <= sum_t min(rows, ceil(nact[t] / G) * G) and total = To * N * O, for a batch that is ONE chunk"""
+    B, R, O, T = batch['option_in'].shape
+    oin = batch['option_in'].reshape(B * R * O, T).T
+    perm, nact, holed = length_order(oin)
+    live_in = int((oin != 0).sum())
+    upper = int(rows_run(nact, B * R * O, G).sum())
+    print('option_rows: executed %d of %d (live %d, upper bound %d)' % (executed, total, live_in, upper))
+    assert total == T * B * R * O
+    assert not holed and live_in <= executed <= upper, (live_in, executed, upper)
+    # and exactly: the row groups are the row tiles of the step kernel that ran (32 rows below 2 048 rows, else 128; G is a multiple of both)
+    from visdial_amd import ops
+    assert executed == int(rows_run(nact, B * R * O, ops.lstm_fwd_row_tile(B * R * O)).sum()), (executed, nact.tolist())
+    return live_in, upper
+
+
+@pytest.mark.parametrize("enc", ['lf-ques', 'lf-ques-im-hist', 'mn-att-ques-im-hist', 'hre-ques-im-hist', 'hrea-ques-im-hist'])
+def test_length_ordered_retrieval_matches_oracle_on_every_host(gpu, enc):
+    """test_fused_lhood_retrieval_matches_oracle_on_every_host with candidate lengths that differ, an empty, a duplicate and a
+    full-length candidate: the same checks and the same bound, plus the counters of the native host"""
+    from lua_host import LuaHost, first
+    from luavm import to_py
+    from visdial_amd import _lib, ops, t7
+    from visdial_amd.model import Model
+    from visdial_amd.native import NativeModel
+    p, batch = oracle_case(enc)
+    p['fusedLhood'] = 1
+    B, R, O, T = batch['option_in'].shape
+    N = B * R
+    rng = np.random.RandomState(3)
+    lens = rng.randint(1, T - 1, size=N * O)
+    lens[1] = 0                                                 # the empty candidate of oracle_case (round 0, option 1)
+    lens[R * O // 2 + 7] = T - 1                                # a full-length one
+    plant_lengths(batch, lens, p['vocabSize'], rng)
+    dup = (O + 3, O + 8)                                        # round 1: option 8 is a copy of option 3
+    for k in ('option_in', 'option_out'):
+        flat = batch[k].reshape(-1, T)
+        flat[dup[1]] = flat[dup[0]]
+    assert len(set(np.count_nonzero(batch['option_in'].reshape(-1, T), axis=1).tolist())) > 3
+    gt = batch['answer_ind'].reshape(-1) - 1
+    nat = NativeModel(dict(p), init_seed=3)
+    nat.training(False)
+    Pf = nat.get_parameters_dict()
+    ref = vo.retrieve(enc, 'gen', {k: v.astype(np.float64) for k, v in Pf.items()}, p, batch).reshape(-1)
+
+    def check(who, scores, gt_ranks, all_ranks):
+        err = float(np.abs(scores - ref).max())
+        print('%-26s %-8s worst |score - oracle| %.3e (bound %.3e)' % (enc, who, err, bound(ref)))
+        assert np.isfinite(scores).all() and err < bound(ref), (who, err)
+        assert scores[1] == 0.0, who
+        assert scores[dup[0]].view(np.uint32) == scores[dup[1]].view(np.uint32), who          # ties exactly ...
+        all_ranks = np.asarray(all_ranks).reshape(N, O)
+        assert all_ranks[1, 8] == all_ranks[1, 3] + 1, who                                    # ... and ranks by index
+        np.testing.assert_array_equal(np.asarray(gt_ranks).reshape(-1), vo.compute_ranks(scores.reshape(N, O), gt), err_msg=who)
+        np.testing.assert_array_equal(all_ranks, vo.compute_ranks(scores.reshape(N, O)), err_msg=who)
+
+    g = nat.retrieveBatch(batch, useGt=True)
+    executed, total = nat.option_rows()
+    counter_bounds(batch, executed, total, ops.LIVE_PREFIX_ROWS)
+    s_nat = nat.scores(N, O)
+    check('native', s_nat.reshape(-1), g, nat.retrieveBatch(batch, useGt=False))
+    again = nat.scores(N, O)
+    assert np.array_equal(s_nat.view(np.uint32), again.view(np.uint32))                       # the same call twice
+    py = Model(dict(p))
+    py.set_parameters_dict(Pf)
+    py.wrapper.evaluate()
+    py.params['useGt'] = True
+    g = np.asarray(py.retrieveBatch(batch))
+    s_py = py.scores.cpu().numpy().copy()
+    py.params['useGt'] = False
+    check('python', s_py.reshape(-1), g, np.asarray(py.retrieveBatch(batch)))
+    host = LuaHost(p)
+    m = host.model()
+    host.invoke(m, 'setFlatParameters', host.tensor(t7.named_to_flat(Pf, nat._entries(), enc), 'Float'))
+    host.invoke(m, 'setMode', False)
+    host.get(m, 'params').set('fusedLhood', 1)
+    host.get(m, 'params').set('useGt', True)
+    g = to_py(first(host.invoke(m, 'retrieveBatch', host.batch(batch))))
+    s_lua = np.empty((N, O), np.float32)
+    _lib.call('vd_model_scores', C.c_void_p(host.get(m, 'h').val), s_lua.ctypes.data, s_lua.size)
+    host.get(m, 'params').set('useGt', False)
+    check('lua', s_lua.reshape(-1), g, to_py(first(host.invoke(m, 'retrieveBatch', host.batch(batch)))))
+    nat.close()
+    host.close()
+
+
+def mid_params(**kw):
+    d = dict(encoder='lf-ques-im-hist', decoder='gen', vocabSize=200, embedSize=32, rnnHiddenSize=64, imgFeatureSize=64, numLayers=2,
+             maxQuesCount=10, maxQuesLen=12, maxAnsLen=20, maxHistoryLenPerRound=24, numOptions=100, batchSize=20, gpuid=0)
+    d.update(kw)
+    return derive(default_params(**d))
+
+
+def dense_and_fused(p, batch):
+    """the dense head and the length-ordered live-row head on the same model and batch -> (dense, fused, option_rows after each)"""
+    from visdial_amd.native import NativeModel
+    B, R, O, _ = batch['option_in'].shape
+    nat = NativeModel(dict(p), init_seed=1)
+    nat.training(False)
+    nat.retrieveBatch(batch, useGt=False)
+    dense, rows_dense = nat.scores(B * R, O).copy(), nat.option_rows()
+    nat.params['fusedLhood'] = 1
+    ranks = np.asarray(nat.retrieveBatch(batch, useGt=False)).reshape(B * R, O)
+    fused, rows_fused = nat.scores(B * R, O).copy(), nat.option_rows()
+    nat.retrieveBatch(batch, useGt=False)
+    assert np.array_equal(fused.view(np.uint32), nat.scores(B * R, O).view(np.uint32))          # the same call twice: bit-identical
+    nat.params['fusedLhood'] = 0
+    nat.retrieveBatch(batch, useGt=False)
+    assert nat.option_rows() == rows_dense                     # the answer describes the last step call
+    nat.close()
+    return dense, fused, ranks, rows_dense, rows_fused
+
+
+def test_mid_size_chunk_really_skips(gpu):
+    """H 64, V 200, 20 x 10 x 100 candidates = 20 000 rows in one chunk (the 128-row step kernels), short lengths"""
+    from visdial_amd import ops
+    p = mid_params()
+    rng = np.random.RandomState(21)
+    batch, _ = SyntheticDataloader(p, seed=7, num_threads=20).getTestBatch(1, p, 'val')
+    lens = profile_lengths('short', 20 * 10 * 100, rng)
+    lens[[0, 77, 19999]] = 0
+    plant_lengths(batch, lens, p['vocabSize'], rng)
+    dense, fused, ranks, rows_dense, (executed, total) = dense_and_fused(p, batch)
+    assert rows_dense == (0, 0)                                 # a gen model, dense head: as before
+    live_in, upper = counter_bounds(batch, executed, total, ops.LIVE_PREFIX_ROWS)
+    assert executed < 0.5 * total                               # mean length 3 of 20: most row groups hold no token
+    diff = float(np.abs(dense.astype(np.float64) - fused).max())
+    print('mid size: worst |dense - fused| %.3e (allowed %.3e)' % (diff, 2 * bound(dense)))
+    assert np.isfinite(fused).all() and diff <= 2 * bound(dense)
+    assert (fused.reshape(-1)[[0, 77, 19999]] == 0.0).all()
+    np.testing.assert_array_equal(ranks, vo.compute_ranks(fused))
+
+
+@pytest.mark.parametrize("case", ['all lengths equal', 'mostly empty', 'one long among empties', 'staircase', 'holed'])
+def test_order_kernels_through_retrieval(gpu, case):
+    """3 x 5 rounds x 13 options = 195 rows (no multiple of a counting block, a row tile or a wave).  The order decides which candidate
+    a score belongs to (scores against the dense head, which never reorders), the per-step counts decide `executed` (asserted exactly
+    against numpy: counter_bounds), the status word decides the fallback."""
+    from visdial_amd import ops
+    p = mid_params(batchSize=3, maxQuesCount=5, numOptions=13, maxAnsLen=9)
+    rng = np.random.RandomState(8)
+    batch, _ = SyntheticDataloader(p, seed=7, num_threads=4).getTestBatch(1, p, 'val')
+    B, R, O, T = batch['option_in'].shape
+    rows = B * R * O
+    assert (rows, T) == (195, 10)
+    lens = {'all lengths equal': np.full(rows, 4), 'mostly empty': np.where(rng.rand(rows) < 0.8, 0, rng.randint(1, 10, size=rows)),
+            'one long among empties': np.zeros(rows, np.int64), 'holed': rng.randint(1, 10, size=rows),
+            # every step has its own count and none is a multiple of a 32-row tile: executed pins ceil(nact[t] / 32) of every step
+            'staircase': rng.permutation(np.repeat(np.arange(10), [40, 37, 30, 25, 21, 15, 11, 8, 5, 3]))}[case]
+    if case == 'one long among empties':
+        lens[131] = 9
+    plant_lengths(batch, lens, p['vocabSize'], rng)
+    if case == 'holed':
+        flat = batch['option_in'].reshape(-1, T)
+        r = int(np.flatnonzero(lens >= 4)[0])
+        flat[r, 2] = 0                                          # <START> w1 0 w3 ..: a pad followed by a token
+    dense, fused, ranks, _, (executed, total) = dense_and_fused(p, batch)
+    diff = float(np.abs(dense.astype(np.float64) - fused).max())
+    print('%s: worst |dense - fused| %.3e (allowed %.3e), executed %d of %d' % (case, diff, 2 * bound(dense), executed, total))
+    assert np.isfinite(fused).all() and diff <= 2 * bound(dense)
+    assert (fused.reshape(-1)[lens == 0] == 0.0).all()
+    np.testing.assert_array_equal(ranks, vo.compute_ranks(fused))
+    assert total == T * rows
+    if case == 'holed':
+        assert executed == total                                # the fallback ran: every row of the one chunk
+    elif case == 'all lengths equal':
+        assert executed == 5 * rows                             # <START> + 4 tokens: five steps of all rows, whatever the row tile
+    else:
+        counter_bounds(batch, executed, total, ops.LIVE_PREFIX_ROWS)
+        if case == 'one long among empties':
+            assert executed <= rows + 9 * ops.LIVE_PREFIX_ROWS
+
+
+@pytest.mark.parametrize("profile,cap", [('uniform', 0.60), ('short', 0.25)])
+def test_full_size_length_ordered_against_dense(gpu, profile, cap):
+    """test_full_size_fused_against_dense (same seeds, same planted empties and duplicate) with everything it asserts, and the share of
+    (step, candidate) rows the candidate recurrence ran: the live share is 0.546 / 0.191 with these seeds, group rounding with
+    G <= 256 over the three chunks brings it to at most 0.566 / 0.205"""
+    p = full_size_params()
+    rng = np.random.RandomState(77)
+    batch, _ = SyntheticDataloader(p, seed=7, num_threads=20).getTestBatch(1, p, 'val')
+    lens = profile_lengths(profile, 20 * 10 * 100, rng)
+    empty = [1, 4242, 19999]
+    lens[empty] = 0
+    set_option_lengths(batch, lens, p, rng)
+    dup = (37 * 100 + 3, 37 * 100 + 58)
+    for k in ('option_in', 'option_out'):
+        flat = batch[k].reshape(-1, batch[k].shape[-1])
+        flat[dup[1]] = flat[dup[0]]
+    dense, fused, all_fused, rows_dense, (executed, total) = dense_and_fused(p, batch)
+    tol = 2 * bound(dense)
+    diff = float(np.abs(dense.astype(np.float64) - fused).max())
+    flipped, bad = order_violations(dense, fused, tol)
+    live_in = int((batch['option_in'] != 0).sum())
+    print('full size, %s lengths: executed %d of %d = %.3f (live %.3f), worst |dense - fused| %.3e (allowed %.3e), option pairs in another '
+          'order %d (unexplained %d)' % (profile, executed, total, executed / total, live_in / total, diff, tol, flipped, len(bad)))
+    assert np.isfinite(fused).all() and diff <= tol, (diff, tol)
+    assert not bad, bad[:10]
+    for e in empty:
+        assert dense.reshape(-1)[e] == 0.0 and fused.reshape(-1)[e] == 0.0
+    assert fused.reshape(-1)[dup[0]].view(np.uint32) == fused.reshape(-1)[dup[1]].view(np.uint32)
+    assert all_fused[37, 58] == all_fused[37, 3] + 1
+    np.testing.assert_array_equal(all_fused, vo.compute_ranks(fused))
+    assert rows_dense == (0, 0) and total == 21 * 200 * 100
+    assert live_in <= executed <= cap * total, (executed, total)

@@ -173,6 +173,31 @@ struct EpiDistOf<Epi, std::void_t<typename Epi::DOps>> {
   static constexpr bool value = Epi::HAS_DIST;
 };
 
+// Epilogue functors may declare `static constexpr bool HAS_DEAD = true` + `dead(row_base, BM)`: a workgroup whose row tile
+// [row_base, row_base + BM) holds nothing to compute returns before it loads anything (VD_FLAG_LIVE_PREFIX: lstm.hip, and the layer-2
+// projection of the same rows, gemm_ops.hip).  The answer must be uniform over the workgroup.  Every other epilogue answers "never dead"
+// at compile time: the kernels instantiated with it do not change.
+template <class Epi, class = void>
+struct EpiDeadOf {
+  static constexpr bool value = false;
+};
+template <class Epi>
+struct EpiDeadOf<Epi, std::void_t<decltype(Epi::HAS_DEAD)>> {
+  static constexpr bool value = Epi::HAS_DEAD;
+};
+
+// Workgroup -> tile of a kernel whose epilogue has the predicate: the live row tiles are a PREFIX of the row tiles, and xcd_remap (below)
+// hands every XCD a contiguous range of tiles -- the live ones would all land on the first XCDs while the others retire dead workgroups
+// (that variant, measured with 55 % of the row tiles live: 132 us per step launch against 137 us for all rows; with the map below 89 us,
+// profiles/lhood_retrieval.txt).  Here row tile r runs on XCD r % 8 with all its column tiles (the XCD's L2 still
+// sees each A row tile once), so every XCD holds the same share of the prefix to within one row tile.  The grid is padded to a multiple of
+// 8 row tiles; a workgroup beyond tiles_m returns.
+__device__ __forceinline__ void live_tile(int bid, int tiles_n, int& tile_m, int& tile_n) {
+  const int li = bid >> 3;
+  tile_m = (li / tiles_n) * 8 + (bid & 7);
+  tile_n = li % tiles_n;
+}
+
 // XCD-aware bijective remap of the flat workgroup id (guide T1).
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7;
@@ -526,10 +551,17 @@ gemm_f32_kernel(int M, int N, int K, int kchunk, int tiles_m, int tiles_n, int r
   // recurrences; they share CUs with throughput-shape workgroups of other streams.  Raising their wave
   // priority lets them win MFMA/VALU issue arbitration on the SIMD (priority outranks age).
   if constexpr (Cfg::WK > 1) __builtin_amdgcn_s_setprio(3);
-  const int wg = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile_n = wg % tiles_n;
-  const int tile_m = (wg / tiles_n) % tiles_m;
-  const int split = wg / (tiles_n * tiles_m);
+  int tile_n, tile_m, split;
+  if constexpr (EpiDeadOf<Epi>::value) {   // (launched without split-K)
+    live_tile(blockIdx.x, tiles_n, tile_m, tile_n);
+    split = 0;
+    if (tile_m >= tiles_m || epi.dead(tile_m * Cfg::BM, Cfg::BM)) return;   // in front of the first load and the first barrier
+  } else {
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
+    tile_n = wg % tiles_n;
+    tile_m = (wg / tiles_n) % tiles_m;
+    split = wg / (tiles_n * tiles_m);
+  }
   const int ks = split * kchunk;
   const int ke = min(K, ks + kchunk);
   gemm_block<Cfg>(M, N, ks, ke, tile_m * Cfg::BM, tile_n * Cfg::BN, rotate ? tile_m * 5 + tile_n * 3 + split : -1,
@@ -778,8 +810,15 @@ __global__ void __launch_bounds__(Cfg::THREADS, Cfg::MINW)
 gemm_f32_glds_kernel(int M, int N, int K, int kchunk, int tiles_m, int tiles_n, int rotate, const float* A, long lda,
                      const float* B, long ldb, Epi epi) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int wg = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile_n = wg % tiles_n, tile_m = (wg / tiles_n) % tiles_m, split = wg / (tiles_n * tiles_m);
+  int tile_n, tile_m, split;
+  if constexpr (EpiDeadOf<Epi>::value) {   // (launched without split-K)
+    live_tile(blockIdx.x, tiles_n, tile_m, tile_n);
+    split = 0;
+    if (tile_m >= tiles_m || epi.dead(tile_m * Cfg::BM, Cfg::BM)) return;   // in front of the first DMA request and the first barrier
+  } else {
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
+    tile_n = wg % tiles_n, tile_m = (wg / tiles_n) % tiles_m, split = wg / (tiles_n * tiles_m);
+  }
   const int ks = split * kchunk, ke = min(K, ks + kchunk);
   gemm_block_glds<Cfg, KMAJ>(M, N, ks, ke, tile_m * Cfg::BM, tile_n * Cfg::BN,
                              rotate ? tile_m * 5 + tile_n * 3 + split : -1, A, lda, B, ldb, epi, smem);
@@ -811,7 +850,11 @@ static int launch_gemm_glds(int M, int N, int K, int splits, const float* A, lon
     attr_set = true;
   }
   const int rotate = rotate_in >= 0 ? rotate_in : 1;
-  const int grid = tiles_m * tiles_n * splits;
+  int grid = tiles_m * tiles_n * splits;
+  if constexpr (EpiDeadOf<Epi>::value) {   // live_tile: whole groups of 8 row tiles
+    VD_CHECK_ARG(splits == 1, "launch_gemm_glds: an epilogue with a row-tile predicate takes no split-K");
+    grid = (tiles_m + 7) / 8 * 8 * tiles_n;
+  }
   const int lds = Cfg::LDS_BYTES;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::THREADS), lds, stream, M, N, K,
                      kchunk, tiles_m, tiles_n, rotate, A, lda, B, ldb, e);
@@ -943,7 +986,11 @@ static int launch_gemm(int M, int N, int K, int splits, ASrc a, BSrc b, Epi e, h
                                Cfg::LDS_BYTES));
     attr_set = true;
   }
-  const int grid = tiles_m * tiles_n * splits;
+  int grid = tiles_m * tiles_n * splits;
+  if constexpr (EpiDeadOf<Epi>::value) {   // live_tile: whole groups of 8 row tiles
+    VD_CHECK_ARG(splits == 1, "launch_gemm: an epilogue with a row-tile predicate takes no split-K");
+    grid = (tiles_m + 7) / 8 * 8 * tiles_n;
+  }
   const int rotate = (1);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, M, N, K, kchunk, tiles_m,
                      tiles_n, rotate, a, b, e);

@@ -416,6 +416,37 @@ int vd_gemm_nn(const float* A, int64_t lda, const float* B, int64_t ldb, const f
   return launch_gemm<CfgBig>(M, N, K, 1, a, b, e, s);
 }
 
+}  // extern "C"
+
+// EpiStore + the row-tile predicate of VD_FLAG_LIVE_PREFIX (gemm_core.h EpiDeadOf): the hoisted input projection of a length-ordered
+// recurrence layer skips the row tiles the step kernel skips.  New instantiations only: vd_gemm_nn keeps its kernels.
+template <int NT>
+struct EpiStoreLive : EpiStore<NT> {
+  const int* tok_mask;   // [M], != 0 on a prefix of the rows
+  static constexpr bool HAS_DEAD = true;
+  __device__ __forceinline__ bool dead(int row_base, int /*BM*/) const { return tok_mask[row_base] == 0; }
+};
+static_assert(CfgSmall::BM == VD_LSTM_FWD_TILE_SMALL && CfgBig::BM == VD_LSTM_FWD_TILE_BIG, "the projection's row tiles are the step kernels'");
+
+int vd_gemm_nn_live_p(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C, int64_t ldc, int M, int N, int K,
+                      const int32_t* tok_mask, int row_tile, hipStream_t s) {
+  VD_CHECK_ARG(A && B && C && tok_mask && M >= 0 && N >= 0 && K >= 0 && (K % 4 == 0 || lda >= (K + 3) / 4 * 4) && N % 4 == 0 &&
+                   (row_tile == CfgSmall::BM || row_tile == CfgBig::BM),
+               "vd_gemm_nn (live rows): bad args M=%d N=%d K=%d row tile %d", M, N, K, row_tile);
+  if (int rc = check_align(A, lda, "vd_gemm_nn (live rows) A")) return rc;
+  if (int rc = check_align(B, ldb, "vd_gemm_nn (live rows) B")) return rc;
+  SrcRow a{A, lda};
+  SrcK b{B, ldb};
+  if (row_tile == CfgSmall::BM) {
+    EpiStoreLive<1> e{{C, ldc, bias, VD_ACT_NONE, 0}, tok_mask};
+    return launch_gemm<CfgSmall>(M, N, K, 1, a, b, e, s);
+  }
+  EpiStoreLive<4> e{{C, ldc, bias, VD_ACT_NONE, 0}, tok_mask};
+  return launch_gemm<CfgBig>(M, N, K, 1, a, b, e, s);
+}
+
+extern "C" {
+
 // C[M x N] += A[K x M]^T * B[K x N]   (weight gradients; split-K with float atomics)
 int vd_gemm_tn_acc(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M,
                    int N, int K, int flags, void* stream) {

@@ -8,6 +8,8 @@
 //   vd_lhood_nll        nll[i] = logsumexp_v(h[act[i]] . W[v] + bias[v]) - (h[act[i]] . W[target - 1] + bias[target - 1]):
 //                       fp32 MFMA over the live rows only, online log-sum-exp in registers, no logits in memory
 //   vd_lhood_sum        score[candidate] = -(sum of its rows' nll, in step order)
+// With a length order of the chunk's candidates (lhood_order_*, below) the recurrence in front of the head runs only where there are
+// tokens (VD_FLAG_LIVE_PREFIX) and vd_lhood_sum scatters the scores back to candidate order.
 // Everything is deterministic: no atomics, fixed reduction orders, and a row's arithmetic does not depend on where in a tile it sits.
 #include "gemm_core.h"
 #include "paths.h"
@@ -218,7 +220,7 @@ lhood_live_write_kernel(const int* __restrict__ tok_in, const int* __restrict__ 
 // candidate's terms are added in step order
 __global__ void __launch_bounds__(256)
 lhood_sum_kernel(const float* __restrict__ nll, const int* __restrict__ act, int n_act, int T, long rows, int C, float* __restrict__ out,
-                 long ldo) {
+                 long ldo, const int* __restrict__ perm) {
   const long r = (long)blockIdx.x * 256 + threadIdx.x;
   if (r >= rows) return;
   float sum = 0.f;
@@ -232,7 +234,135 @@ lhood_sum_kernel(const float* __restrict__ nll, const int* __restrict__ act, int
     }
     if (lo < n_act && act[lo] == want) sum += nll[lo];
   }
-  out[(r / C) * ldo + r % C] = 0.f - sum;   // a candidate without a live row scores +0
+  const long cand = perm ? perm[r] : r;   // length-ordered rows: back to candidate order
+  out[(cand / C) * ldo + cand % C] = 0.f - sum;   // a candidate without a live row scores +0
+}
+
+// ---- length order of a chunk's candidates (rows = round x option of tok_in [T x rows]): a STABLE counting sort by descending length, in
+// the style of vd_lhood_live_rows -- a count per block, then block offset + rank inside the block; no atomics, so equal lengths keep
+// their row order from run to run (vd_token_sort's atomic bucket cursor does not).  length = number of leading non-pad steps, key = T -
+// length in [0, T].  Pass 1, one row per thread: length, "hole" (a token behind the first pad: not one left-aligned run), and per block
+// the count of every key (thread k counts key k in the block's LDS key list) and whether a row has a hole.  Pass 2: thread k sums key
+// k's counts over the blocks (before this block / all), thread 0 turns them into the block's first position per key; a row's position =
+// that + the rows of its key before it in the block.  Block 0 also writes info = [holed rows?, nact[0 .. T)], nact[t] = rows longer than
+// t: in this order the non-pad rows of step t are rows [0, nact[t]) and nact falls with t.
+constexpr int ORDER_ROWS = 256;   // rows per block = threads; T + 1 keys <= ORDER_ROWS (paths.h vd_lhood_prefix_fits)
+
+__global__ void __launch_bounds__(ORDER_ROWS)
+lhood_order_count_kernel(const int* __restrict__ tok_in, int T, long rows, int* __restrict__ len_out, int* __restrict__ counts,
+                         int* __restrict__ holes) {
+  __shared__ int keys[ORDER_ROWS];
+  const int tid = threadIdx.x;
+  const long r = (long)blockIdx.x * ORDER_ROWS + tid;
+  int len = 0, hole = 0, key = -1;
+  if (r < rows) {
+    bool run = true;
+    for (int t = 0; t < T; ++t) {
+      const bool tok = tok_in[(long)t * rows + r] != 0;
+      run = run && tok;
+      len += run ? 1 : 0;
+      hole |= (!run && tok) ? 1 : 0;
+    }
+    len_out[r] = len;
+    key = T - len;
+  }
+  keys[tid] = key;
+  const int any_hole = __syncthreads_or(hole);   // (also the barrier behind the key list)
+  if (tid == 0) holes[blockIdx.x] = any_hole ? 1 : 0;
+  if (tid <= T) {
+    int c = 0;
+    for (int j = 0; j < ORDER_ROWS; ++j) c += keys[j] == tid ? 1 : 0;
+    counts[(long)blockIdx.x * (T + 1) + tid] = c;
+  }
+}
+
+__global__ void __launch_bounds__(ORDER_ROWS)
+lhood_order_write_kernel(const int* __restrict__ len, int T, long rows, int C, const int* __restrict__ counts, const int* __restrict__ holes,
+                         int* __restrict__ perm, int* __restrict__ rep, int* __restrict__ info) {
+  __shared__ int keys[ORDER_ROWS], before[ORDER_ROWS], total[ORDER_ROWS], first[ORDER_ROWS];
+  const int tid = threadIdx.x, nb = (int)gridDim.x;
+  const long r = (long)blockIdx.x * ORDER_ROWS + tid;
+  const int key = r < rows ? T - len[r] : -1;
+  keys[tid] = key;
+  if (tid <= T) {
+    int bef = 0, all = 0;
+    for (int b = 0; b < nb; ++b) {
+      const int c = counts[(long)b * (T + 1) + tid];
+      all += c;
+      bef += b < (int)blockIdx.x ? c : 0;
+    }
+    before[tid] = bef;
+    total[tid] = all;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int run = 0;
+    for (int k = 0; k <= T; ++k) {
+      first[k] = run + before[k];
+      run += total[k];
+    }
+    if (blockIdx.x == 0) {
+      int holed = 0;
+      for (int b = 0; b < nb; ++b) holed |= holes[b];
+      info[0] = holed;
+      int longer = 0;   // rows with key < T - t  <=>  length > t
+      for (int t = T - 1; t >= 0; --t) {
+        longer += total[T - 1 - t];
+        info[1 + t] = longer;
+      }
+    }
+  }
+  __syncthreads();
+  if (r >= rows) return;
+  int rank = 0;
+  for (int j = 0; j < tid; ++j) rank += keys[j] == key ? 1 : 0;
+  const int pos = first[key] + rank;
+  perm[pos] = (int)r;
+  rep[pos] = (int)(r / C);   // the round whose encoder state the candidate starts from (forwardConnect replication)
+}
+
+// tokens and targets in that order: dst[t][p] = src[t][perm[p]]
+__global__ void __launch_bounds__(256)
+lhood_order_gather_kernel(const int* __restrict__ a, const int* __restrict__ b, const int* __restrict__ perm, int T, long rows,
+                          int* __restrict__ a_s, int* __restrict__ b_s) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)T * rows) return;
+  const long t = i / rows, src = t * rows + perm[i - t * rows];
+  a_s[i] = a[src];
+  b_s[i] = b[src];
+}
+
+int64_t vd_lhood_order_work_ints(int T, int64_t rows) {
+  const int64_t blocks = (rows + ORDER_ROWS - 1) / ORDER_ROWS;
+  return rows + blocks * (T + 1) + blocks;
+}
+
+int vd_lhood_order_p(const int32_t* tok_in, const int32_t* target, int T, int64_t rows, int C, int32_t* perm, int32_t* rep, int32_t* tok_in_s,
+                     int32_t* target_s, int32_t* work, int32_t* info, hipStream_t s) {
+  VD_CHECK_ARG(tok_in && target && perm && rep && tok_in_s && target_s && work && info && C >= 1 && vd_lhood_prefix_fits(T, rows) &&
+                   (long)T * rows < (1L << 31),
+               "lhood order: bad args T=%d rows=%ld", T, (long)rows);
+  const int blocks = vd_cdiv(rows, ORDER_ROWS);
+  int32_t *len = work, *counts = work + rows, *holes = counts + (long)blocks * (T + 1);
+  hipLaunchKernelGGL(lhood_order_count_kernel, dim3(blocks), dim3(ORDER_ROWS), 0, s, tok_in, T, (long)rows, len, counts, holes);
+  VD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lhood_order_write_kernel, dim3(blocks), dim3(ORDER_ROWS), 0, s, len, T, (long)rows, C, counts, holes, perm, rep, info);
+  VD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lhood_order_gather_kernel, dim3(vd_cdiv((long)T * rows, 256)), dim3(256), 0, s, tok_in, target, perm, T, (long)rows,
+                     tok_in_s, target_s);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+int vd_lhood_sum_p(const float* nll, const int32_t* act, int64_t n_act, int T, int64_t rows, int C, const int32_t* perm, float* out, int64_t ldo,
+                   hipStream_t s) {
+  VD_CHECK_ARG(out && T >= 0 && rows >= 0 && C >= 1 && ldo >= C && n_act >= 0 && n_act < (1L << 31) && (long)T * rows < (1L << 31),
+               "vd_lhood_sum: bad args");
+  VD_CHECK_ARG(n_act == 0 || (nll && act), "vd_lhood_sum: null pointer");
+  if (rows == 0) return VD_OK;
+  hipLaunchKernelGGL(lhood_sum_kernel, dim3(vd_cdiv(rows, 256)), dim3(256), 0, s, nll, act, (int)n_act, T, (long)rows, C, out, (long)ldo, perm);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
 }
 
 extern "C" {
@@ -280,14 +410,7 @@ int vd_lhood_nll(const float* h, int64_t ldh, int64_t rows, const int32_t* act, 
 
 int vd_lhood_sum(const float* nll, const int32_t* act, int64_t n_act, int T, int64_t rows, int C, float* out, int64_t ldo,
                  void* stream) {
-  VD_CHECK_ARG(out && T >= 0 && rows >= 0 && C >= 1 && ldo >= C && n_act >= 0 && n_act < (1L << 31) && (long)T * rows < (1L << 31),
-               "vd_lhood_sum: bad args");
-  VD_CHECK_ARG(n_act == 0 || (nll && act), "vd_lhood_sum: null pointer");
-  if (rows == 0) return VD_OK;
-  hipLaunchKernelGGL(lhood_sum_kernel, dim3(vd_cdiv(rows, 256)), dim3(256), 0, (hipStream_t)stream, nll, act, (int)n_act, T, (long)rows,
-                     C, out, (long)ldo);
-  VD_LAUNCH_CHECK();
-  return VD_OK;
+  return vd_lhood_sum_p(nll, act, n_act, T, rows, C, nullptr, out, ldo, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -320,6 +320,13 @@ struct EpiLstmFwdT {
 };
 
 using EpiLstmFwd = EpiLstmFwdT<0>;
+// VD_FLAG_LIVE_PREFIX: the same epilogue, plus the row-tile predicate of gemm_core.h (EpiDeadOf).  The caller promises that the rows with
+// tok_mask != 0 are a prefix of the step's rows, so a tile whose FIRST row is pad holds no live row.  A type of its own, so that the step
+// kernels without the flag keep their instantiations (and their device code) as they are.
+struct EpiLstmFwdLive : EpiLstmFwd {
+  static constexpr bool HAS_DEAD = true;
+  __device__ __forceinline__ bool dead(int row_base, int /*BM*/) const { return tok_mask[row_base] == 0; }   // row_base < M: the tile was launched
+};
 
 // ---------------------------------------------------------------------------
 // backward epilogue: acc = (da_{t+1} * Wh^T)[row, j]  (zero at the last step)
@@ -590,7 +597,12 @@ static int weights_to_bf16(const float* src, vd_bf16_bits* dst, long n, hipStrea
   return VD_OK;
 }
 
-static int lstm_step_fwd(const float* h_prev, const float* Wh, int N, int H, int K, const EpiLstmFwd& epi,
+static_assert(VD_LIVE_PREFIX_ROWS <= 256 && VD_LIVE_PREFIX_ROWS % CfgF9::BM == 0 && VD_LIVE_PREFIX_ROWS % CfgFwdSmallA::BM == 0 &&
+                  CfgF9::BM == VD_LSTM_FWD_TILE_BIG && CfgFwdSmallA::BM == VD_LSTM_FWD_TILE_SMALL,
+              "VD_LIVE_PREFIX_ROWS is a multiple of every forward step kernel's row tile; paths.h vd_lstm_fwd_row_tile names them");
+
+template <class Epi>
+static int lstm_step_fwd(const float* h_prev, const float* Wh, int N, int H, int K, const Epi& epi,
                          hipStream_t s) {
   SrcRow a{h_prev, H};
   SrcKGate4 b{Wh, 4L * H, H};
@@ -841,6 +853,11 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
   // tensor must stay below 4 GB (gates: N * 4H * 4 bytes; the dense projection: N * x_ld * 4; a projection TABLE: rows * x_ld * 4)
   VD_CHECK_ARG((long)N * 4 * H * 4 < (1L << 32) && (tok_gather || (long)N * x_ld * 4 < (1L << 32)),
                "vd_lstm_forward: N=%d rows x 4H=%d exceed 4 GB per step: split the batch", N, 4 * H);
+  const bool live = (flags & VD_FLAG_LIVE_PREFIX) != 0;
+  VD_CHECK_ARG(!live || !(flags & (VD_FLAG_BF16 | VD_FLAG_SPLIT)),
+               "vd_lstm_forward: VD_FLAG_LIVE_PREFIX skips row groups in the exact fp32 step kernels only; it does not combine with "
+               "VD_FLAG_BF16 / VD_FLAG_SPLIT* (flags = %d)", flags);
+  VD_CHECK_ARG(!live || tok_mask, "vd_lstm_forward: VD_FLAG_LIVE_PREFIX needs tok_mask");
   hipStream_t s = (hipStream_t)stream;
   const long NH = (long)N * H;
   // the step kernel of the pass, chosen once: bf16 operands, the exact-operand split (split_core.h) on the fp32 LDS-DMA pipeline's
@@ -891,7 +908,13 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
     e.H = H;
     e.h16 = h16 ? h16 + t * NH : nullptr;
     int rc;
-    if (!hp)   // first step without h0: no recurrent product
+    if (live) {   // (fp32 only: neither bf16 nor split) the same three paths with the row-tile predicate
+      EpiLstmFwdLive el;
+      static_cast<EpiLstmFwd&>(el) = e;
+      if (!hp) rc = lstm_step_fwd(nullptr, Wh, N, H, 0, el, s);
+      else if (glds) rc = launch_gemm_glds<CfgF9, false>(N, 4 * H, H, 1, hp, (long)H, WhT, (long)H, el, s);
+      else rc = lstm_step_fwd(hp, Wh, N, H, H, el, s);
+    } else if (!hp)   // first step without h0: no recurrent product
       rc = lstm_step_fwd(nullptr, Wh, N, H, 0, e, s);
     else if (bf16 && t > 0)   // the shadow of h_{t-1}
       rc = launch_gemm_glds<CfgF9bf16, false>(N, 4 * H, H / 2, 1, reinterpret_cast<const float*>(h16 + (t - 1) * NH), (long)H / 2,

@@ -25,6 +25,10 @@ static inline int vd_split_nprod(int flags) {
 // rows from which a recurrence step takes the throughput kernels (LDS-DMA pipeline, bf16 operands, exact split) instead of the
 // latency-shape ones
 constexpr long VD_THROUGHPUT_ROWS = 2048;
+// row tile of the fp32 forward step kernel a recurrence over N rows runs (lstm.hip asserts that its tile configurations agree): the
+// height of the row groups VD_FLAG_LIVE_PREFIX skips
+constexpr int VD_LSTM_FWD_TILE_BIG = 128, VD_LSTM_FWD_TILE_SMALL = 32;
+static inline int vd_lstm_fwd_row_tile(long N) { return N >= VD_THROUGHPUT_ROWS ? VD_LSTM_FWD_TILE_BIG : VD_LSTM_FWD_TILE_SMALL; }
 // LDS-DMA step pipeline of the fp32 operands (and of the exact split): K % 16 == 0 and 32-bit row byte offsets of the streamed operand
 // (h [N x H] forward, da [N x 4H] backward)
 static inline bool vd_lstm_glds_fwd_fits(long N, int H) { return N >= VD_THROUGHPUT_ROWS && H % 32 == 0 && N * H * 4 < (1L << 32); }
@@ -55,3 +59,8 @@ static inline bool vd_img_split_ok(long rows, int H, int Kc) {
 static inline bool vd_lhood_fused_fits(long rows, long ldh, long V, long ldw, int H) {
   return H >= 64 && H % 16 == 0 && V >= 128 && ldh % 4 == 0 && ldw % 4 == 0 && rows * ldh * 4 < (1L << 32) && V * ldw * 4 < (1L << 32);
 }
+// length-ordered candidate recurrence of the same retrieval (lhood.hip lhood_order_p; rt_decoders.h): the chunk's candidates go through
+// the decoder in order of descending length and the recurrence takes VD_FLAG_LIVE_PREFIX.  The counting sort holds one key per
+// possible length (0 .. T) in a 256-thread block; the recurrence of retrieval is exact fp32 (flags 0), which is what the flag is
+// implemented for.  Otherwise the chunk runs in candidate order, all rows.
+static inline bool vd_lhood_prefix_fits(int T, long rows) { return T >= 1 && T < 256 && rows >= 1; }

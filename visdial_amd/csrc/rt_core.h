@@ -37,6 +37,18 @@ int vd_img_tr_backward_p(const float* dz, const float* Wc, const float* p, const
 int vd_img_common_wgrad_p(const float* dz, const float* pre, const uint8_t* mask1, const float* xdrop, float* dWc, int N, int R, int S2, int H,
                           int Kc, float scale, int flags, hipStream_t stream);
 
+// gemm_ops.hip: vd_gemm_nn over rows that carry a token id, with the row-group predicate of VD_FLAG_LIVE_PREFIX -- a row tile of
+// `row_tile` (32 or 128) rows whose first row has tok_mask == 0 is not computed and its C rows are left unwritten
+int vd_gemm_nn_live_p(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C, int64_t ldc, int M, int N, int K,
+                      const int32_t* tok_mask, int row_tile, hipStream_t stream);
+// lhood.hip: the length order of a chunk of candidates (stable counting sort, descending length), the tokens / targets / replication
+// index gathered in that order, and vd_lhood_sum with the scores scattered back through `perm`
+int vd_lhood_order_p(const int32_t* tok_in, const int32_t* target, int T, int64_t rows, int C, int32_t* perm, int32_t* rep, int32_t* tok_in_s,
+                     int32_t* target_s, int32_t* work, int32_t* info, hipStream_t stream);
+int64_t vd_lhood_order_work_ints(int T, int64_t rows);
+int vd_lhood_sum_p(const float* nll, const int32_t* act, int64_t n_act, int T, int64_t rows, int C, const int32_t* perm, float* out, int64_t ldo,
+                   hipStream_t stream);
+
 #define VD_TRY(expr)                  \
   do {                                \
     const int rc__ = (expr);          \
@@ -135,6 +147,9 @@ struct vd_model {
   float* gen_enc_out = nullptr;  // encoder output of the last vd_model_encode (generation)
   int gen_seq_len = 0;
   int N = 0, O = 0;
+  // vd_model_option_rows after vd_model_retrieve_lhood: (step, candidate) rows in a row group the candidate recurrence ran, of To * N * O;
+  // -1 = the last step call was another one
+  long lhood_exec = -1, lhood_total = 0;
   // capability flags from the encoder NAME (opts.lua:54-67)
   bool use_im = false, use_hist = false, is_att = false, is_graph = false;
   bool prof_hist = false;   // ev_prof[0..3] bracket the history branch of a Sequential encoder (gen pairs: vd_model_family_ms)
@@ -390,7 +405,8 @@ struct SeqLSTM {
     VD_TRY(ws_get(m, name + ".c", (size_t)T * N * H, &c));
     return VD_OK;
   }
-  int forward(vd_model* m, hipStream_t s, const std::vector<const float*>& x, int T_, int N_, const int32_t* tok, float** h_out) {
+  // hands userPrevOutput / userPrevCell to the pass (h0, c0), the missing one of a pair as zeros
+  int take_state(vd_model* m, hipStream_t s, int N_) {
     h0 = userPrevOutput; c0 = userPrevCell;
     userPrevOutput = userPrevCell = nullptr;                       // consumed once (rnn semantics)
     if (h0 && !c0) {
@@ -405,6 +421,10 @@ struct SeqLSTM {
       VD_TRY(vd_memset(z, 0, (long)N_ * H * 4, s));
       h0 = z;
     }
+    return VD_OK;
+  }
+  int forward(vd_model* m, hipStream_t s, const std::vector<const float*>& x, int T_, int N_, const int32_t* tok, float** h_out) {
+    VD_TRY(take_state(m, s, N_));
     VD_TRY(alloc(m, T_, N_));
     xs = x; tok_mask = tok; rows = nullptr;
     // hoisted input projection, written straight into the gates buffer (the recurrence runs in place)
@@ -415,6 +435,30 @@ struct SeqLSTM {
       roff += parts[i];
     }
     VD_TRY(vd_lstm_forward(gates, (int64_t)N * 4 * H, 4 * H, nullptr, tok, Wh(m), h0, c0, gates, h, c, T, N, (int)H, 0, s));
+    if (h_out) *h_out = h;
+    return VD_OK;
+  }
+  // Forward-only pass over length-ordered candidates (generative retrieval, rt_decoders.h).  `table` (layer 1): xproj = Emb * Wx + b
+  // gathered by token id inside the step kernel; else `x` [T*N x D] is projected here.  flags = VD_FLAG_LIVE_PREFIX: the projection
+  // and the steps skip the row tiles without a live row (the same tiles: one launch per step, the step kernel's tile height), whose
+  // gates / h / c rows are left unwritten.
+  int forward_ordered(vd_model* m, hipStream_t s, const float* table, const float* x, int T_, int N_, const int32_t* tok, int flags,
+                      float** h_out) {
+    VD_TRY(take_state(m, s, N_));
+    VD_TRY(alloc(m, T_, N_));
+    xs.clear(); tok_mask = tok; rows = nullptr;
+    if (table) {
+      VD_TRY(vd_lstm_forward(table, 0, 4 * H, tok, tok, Wh(m), h0, c0, gates, h, c, T, N, (int)H, flags, s));
+    } else {
+      if (flags & VD_FLAG_LIVE_PREFIX) {
+        for (int t = 0; t < T; ++t)
+          VD_TRY(vd_gemm_nn_live_p(x + (long)t * N * D, D, Wx(m), 4 * H, Wp(m, name + ".b"), gates + (long)t * N * 4 * H, 4 * H, N, (int)(4 * H),
+                                   (int)D, tok + (long)t * N, vd_lstm_fwd_row_tile(N), s));
+      } else {
+        VD_TRY(vd_gemm_nn(x, D, Wx(m), 4 * H, Wp(m, name + ".b"), gates, 4 * H, T * N, (int)(4 * H), (int)D, 0, s));
+      }
+      VD_TRY(vd_lstm_forward(gates, (int64_t)N * 4 * H, 4 * H, nullptr, tok, Wh(m), h0, c0, gates, h, c, T, N, (int)H, flags, s));
+    }
     if (h_out) *h_out = h;
     return VD_OK;
   }

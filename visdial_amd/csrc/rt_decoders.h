@@ -323,8 +323,9 @@ struct Gen : Decoder {
   // over the 100 options; here chunks of options are ONE decoder batch (rows = round x option) seeded by the replicated
   // encoder state, and the [rows x V] logits only ever exist for one chunk.
   int retrieve(vd_model* m, BatchSlot& b) override { return retrieve_head(m, b, false); }
-  // vd_model_retrieve_lhood: the same encoder forward, forwardConnect replication, embedding gather and lstm_stack_forward; the head
-  // is vd_lhood_live_rows + vd_lhood_nll + vd_lhood_sum (csrc/lhood.hip) over the live rows of the chunk, with no logits buffer
+  // vd_model_retrieve_lhood: the same encoder forward and forwardConnect replication; the candidates run through the decoder in order of
+  // descending length, the recurrence (SeqLSTM::forward_ordered) only where there are tokens; the head is vd_lhood_live_rows +
+  // vd_lhood_nll + vd_lhood_sum (csrc/lhood.hip) over the live rows of the chunk, with no logits buffer
   int retrieve_lhood(vd_model* m, BatchSlot& b) override { return retrieve_head(m, b, true); }
   int retrieve_head(vd_model* m, BatchSlot& b, bool live) {
     VD_CHECK_ARG(b.oin.present && b.oout.present, "retrieval with decoder 'gen' needs batch.option_in / option_out");
@@ -340,6 +341,19 @@ struct Gen : Decoder {
     // held to the same 4 GiB -- and to the 32-bit row byte offsets of h in the fused kernel (T * rows * H * 4 < 4 GiB, implied).
     const long per_opt = (long)T * N * (live ? E + 6 * H * (long)rnn.size() : Vp);
     const int oc = (int)std::max<long>(1, std::min<long>(O, (1L << 30) / std::max<long>(1, per_opt)));
+    // Live-row head: the chunk's candidates go through the decoder in order of descending length (lhood_order_*, csrc/lhood.hip), so
+    // that the live rows of every step are a prefix of the rows and the recurrence can skip the rest (VD_FLAG_LIVE_PREFIX).  Layer 1
+    // then reads its input projection from the table Emb * Wx + b by token id, made once per retrieval.
+    const bool ordered = live && vd_lhood_prefix_fits(T, (long)N * std::min(O, oc));
+    float* table = nullptr;
+    if (ordered) {
+      VD_TRY(ws_get(m, "ret.table", (size_t)(V + 1) * 4 * H, &table));
+      VD_TRY(vd_gemm_nn(Wp(m, "embed"), E, rnn[0].Wx(m), 4 * H, Wp(m, rnn[0].name + ".b"), table, 4 * H, (int)V + 1, (int)(4 * H), (int)E, 0, s));
+    }
+    if (live) {
+      m->lhood_exec = 0;
+      m->lhood_total = (long)T * N * O;
+    }
     for (int o0 = 0; o0 < O; o0 += oc) {
       const int C = std::min(O, o0 + oc) - o0;
       const long rows = (long)N * C;
@@ -349,13 +363,53 @@ struct Gen : Decoder {
       // [T*N x O] int32 -> columns [o0, o0+C): a strided dword copy
       VD_TRY(vd_copy_2d((float*)cin, C, (const float*)(b.oin.tok + o0), O, (long)T * N, C, s));
       VD_TRY(vd_copy_2d((float*)cout, C, (const float*)(b.oout.tok + o0), O, (long)T * N, C, s));
+      float *x, *h, *logits, *nll, *acc;
+      VD_TRY(ws_get(m, "ret.nll", (size_t)T * rows, &nll));
+      if (ordered) {
+        int32_t *perm, *cin_s, *cout_s, *owork, *info, *act, *work, n_act = 0;
+        void* info_host;
+        VD_TRY(ws_get(m, "ret.perm", (size_t)rows, &perm));
+        VD_TRY(ws_get(m, "ret.rep", (size_t)rows, &idx));
+        VD_TRY(ws_get(m, "ret.cin_s", (size_t)T * rows, &cin_s));
+        VD_TRY(ws_get(m, "ret.cout_s", (size_t)T * rows, &cout_s));
+        VD_TRY(ws_get(m, "ret.order_work", (size_t)vd_lhood_order_work_ints(T, rows), &owork));
+        VD_TRY(ws_get(m, "ret.order_info", (size_t)T + 1, &info));
+        VD_TRY(pin_get(b.pinned, "ret.order_info", ((size_t)T + 1) * sizeof(int32_t), &info_host));
+        VD_TRY(ws_get(m, "ret.act", (size_t)T * rows, &act));
+        VD_TRY(ws_get(m, "ret.act_work", (size_t)(T * rows + 1023) / 1024 + 1, &work));
+        VD_TRY(vd_lhood_order_p(cin, cout, T, rows, C, perm, idx, cin_s, cout_s, owork, info, s));
+        VD_HIP(hipMemcpyAsync(info_host, info, ((size_t)T + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        // the chunk's one host synchronisation, now in front of the recurrence (it depends on the tokens only): the live-row count, and
+        // with it the order's status word and per-step counts
+        VD_TRY(vd_lhood_live_rows(cin_s, cout_s, T * rows, act, work, &n_act, s));
+        const int32_t* hinfo = static_cast<const int32_t*>(info_host);
+        // a candidate that is not one left-aligned run: no prefix promise -- the chunk runs every row, as without the order
+        const int flags = hinfo[0] ? 0 : VD_FLAG_LIVE_PREFIX;
+        int Tl = T;   // steps behind the longest candidate hold no token at all: not launched
+        long ran = (long)T * rows;
+        if (flags) {
+          const long tile = vd_lstm_fwd_row_tile(rows);
+          Tl = 1;
+          ran = 0;
+          for (int t = 0; t < T; ++t) {
+            if (hinfo[1 + t] > 0) Tl = t + 1;
+            ran += std::min<long>(rows, (hinfo[1 + t] + tile - 1) / tile * tile);
+          }
+        }
+        m->lhood_exec += ran;
+        VD_TRY(forwardConnect(m, s, encOut, seqLen, idx, rows));
+        VD_TRY(rnn[0].forward_ordered(m, s, table, nullptr, Tl, (int)rows, cin_s, flags, &h));
+        for (size_t l = 1; l < rnn.size(); ++l) VD_TRY(rnn[l].forward_ordered(m, s, nullptr, h, Tl, (int)rows, cin_s, flags, &h));
+        VD_TRY(vd_lhood_nll(h, H, Tl * rows, act, n_act, cout_s,   // (every live row lies in the Tl steps that ran)
+                             Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), (int)V, (int)H, nll, s));
+        VD_TRY(vd_lhood_sum_p(nll, act, n_act, T, rows, C, perm, lhood + o0, O, s));     // log-likelihood = -NLL, summed over time
+        continue;
+      }
       std::vector<int32_t> hidx(rows);
       for (long r = 0; r < rows; ++r) hidx[r] = (int32_t)(r / C);
       VD_TRY(index_array(m, "idx.ret." + std::to_string(rows) + "." + std::to_string(C), hidx, &idx));
       VD_TRY(forwardConnect(m, s, encOut, seqLen, idx, rows));
-      float *x, *h, *logits, *nll, *acc;
       VD_TRY(ws_get(m, "ret.x", (size_t)T * rows * E, &x));
-      VD_TRY(ws_get(m, "ret.nll", (size_t)T * rows, &nll));
       VD_TRY(vd_embed_gather(Wp(m, "embed"), cin, nullptr, x, T * rows, (int)E, 1.f, s));
       VD_TRY(lstm_stack_forward(m, s, rnn, {x}, T, (int)rows, cin, &h));
       if (live) {
@@ -365,6 +419,7 @@ struct Gen : Decoder {
         VD_TRY(vd_lhood_live_rows(cin, cout, T * rows, act, work, &n_act, s));        // the chunk's one host synchronisation
         VD_TRY(vd_lhood_nll(h, H, T * rows, act, n_act, cout, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), (int)V, (int)H, nll, s));
         VD_TRY(vd_lhood_sum(nll, act, n_act, T, rows, C, lhood + o0, O, s));          // log-likelihood = -NLL, summed over time
+        m->lhood_exec += (long)T * rows;
         continue;
       }
       VD_TRY(ws_get(m, "ret.logits", (size_t)T * rows * Vp, &logits));

@@ -476,6 +476,7 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
   VD_HIP(hipMemcpyAsync(sl.gt, gp, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, s));
   VD_HIP(hipEventRecord(sl.ready, s));
   m->uploaded = (int)(&sl - m->slot);
+  m->lhood_exec = -1;
   return VD_OK;
 }
 
@@ -483,6 +484,7 @@ static int begin_step(vd_model* m, bool zero_grads, BatchSlot** out) {
   VD_CHECK_ARG(m && m->uploaded >= 0, "no batch uploaded");
   m->cur = m->uploaded;
   m->enc_grads_recorded = false;
+  m->lhood_exec = -1;   // vd_model_option_rows describes the last step call (Gen::retrieve_head sets it again)
   BatchSlot& b = m->slot[m->cur];
   m->N = b.q.N;
   m->O = m->p.numOptions;
@@ -651,8 +653,15 @@ int vd_model_family_ms(vd_model* m, float* ms3) {
 
 // rows the option LSTM executed for the batch of the LAST STEP (vd_model_forward_backward / vd_model_retrieve) vs the N * O candidates
 // they stand for (decoder disc); before any step: of the uploaded batch.  In a pipelined loop that is NOT the prefetched batch.
+// After vd_model_retrieve_lhood (decoder gen): the (step, candidate) rows that lay in a row group the candidate recurrence ran, summed
+// over the chunks, vs To * N * O; any other step call or upload afterwards brings the answer above back.
 int vd_model_option_rows(vd_model* m, int64_t* executed, int64_t* total) {
   VD_CHECK_ARG(m && executed && total && (m->cur >= 0 || m->uploaded >= 0), "vd_model_option_rows: no batch uploaded");
+  if (m->lhood_exec >= 0) {   // the last step call was vd_model_retrieve_lhood (decoder gen)
+    *executed = m->lhood_exec;
+    *total = m->lhood_total;
+    return VD_OK;
+  }
   const BatchSlot& b = m->slot[m->cur >= 0 ? m->cur : m->uploaded];
   *executed = b.opt.present ? b.opt.N : 0;
   *total = b.opt.present ? (b.opt_total ? b.opt_total : b.opt.N) : 0;

@@ -105,12 +105,22 @@ class Decoder(object):
         oc = max(1, min(O, int((1 << 30) // max(1, per_opt))))              # options per chunk: <= 4 GiB of logits
         tin = option_in.view(T, N, O)
         tout = option_out.view(T, N, O)
+        # the live-row head runs the chunk's candidates in order of descending length (ties by row), so that the rows with a token are a
+        # prefix of every step and the recurrence skips the rest (ops.FLAG_LIVE_PREFIX); layer 1 gathers Emb*Wx+b by token id
+        table = None
+        if live:
+            l0 = self.rnnLayers[0]
+            table = ws.get('ret.table', (V + 1, 4 * H))
+            ops.gemm_nn(self.emb, l0.Wx, table, bias=l0.b, M=V + 1, N=4 * H, K=self.E)
         for o0 in range(0, O, oc):
             o1 = min(O, o0 + oc)
             C = o1 - o0
             rows = N * C
             cin = tin[:, :, o0:o1].contiguous().view(T, rows)               # plumbing: strided int copies
             cout = tout[:, :, o0:o1].contiguous().view(T, rows)
+            if live:
+                self._chunk_ordered(model, cin, cout, encOut, seqLen, table, lhood, o0, C)
+                continue
             idx = ws.get('ret.idx', (rows,), torch.int32)
             idx.copy_(torch.arange(rows, device=idx.device, dtype=torch.int32) // C)
             # forwardConnect (gen.lua:30-42) with the encoder state replicated over the chunk's options
@@ -127,13 +137,6 @@ class Decoder(object):
             ops.embed_gather(self.emb, cin, x)
             h = lstm_stack_forward(self.rnnLayers, x, T, rows, cin).view(T * rows, H)
             nll = ws.get('ret.nll', (T, rows))
-            if live:
-                act = ws.get('ret.act', (T * rows,), torch.int32)
-                work = ws.get('ret.act_work', ((T * rows + 1023) // 1024 + 1,), torch.int32)
-                n_act = ops.lhood_live_rows(cin.view(-1), cout.view(-1), act, work)
-                ops.lhood_nll(h, act, n_act, cout.view(-1), self.Wv, self.bv, nll.view(-1), V=V, H=H)
-                ops.lhood_sum(nll.view(-1), act, n_act, T, rows, C, lhood, O, dst_off=o0)
-                continue
             logits = ws.get('ret.logits', (T * rows, Vp))
             ops.gemm_nt(h, self.Wv, logits, bias=self.bv, M=T * rows, N=V, K=H, ldc=Vp)
             ops.logsoftmax_nll(logits, V, cin.view(-1), cout.view(-1), nll.view(-1), write_grad=False)
@@ -144,6 +147,58 @@ class Decoder(object):
         if live:
             return lhood
         return ops.axpby(lhood, None, lhood, -1.0, 0.0)                       # log-likelihood = -NLL
+
+
+    def _chunk_ordered(self, model, cin, cout, encOut, seqLen, table, lhood, o0, C):
+        """one chunk of retrieve_lhood through the live-row head: cin / cout [T x rows] in candidate order -> lhood[:, o0:o0+C]"""
+        import torch
+        ws, H, V = self.ws, self.H, self.V
+        T, rows = cin.shape
+        N = rows // C
+        layers = getattr(model.encoder, 'rnnLayers', None)
+        # the order and the gathers are plumbing (torch): length = leading non-pad steps, stable sort by descending length
+        tok = cin != 0
+        lens = torch.cumprod(tok.to(torch.int32), 0).sum(0)
+        holed = (tok.sum(0) != lens).any()                                  # a token behind a pad: no prefix promise for this chunk
+        perm = torch.sort(lens, descending=True, stable=True).indices
+        cin_s = cin[:, perm].contiguous()
+        cout_s = cout[:, perm].contiguous()
+        idx = (perm // C).to(torch.int32).contiguous()
+        act = ws.get('ret.act', (T * rows,), torch.int32)
+        work = ws.get('ret.act_work', ((T * rows + 1023) // 1024 + 1,), torch.int32)
+        n_act = ops.lhood_live_rows(cin_s.view(-1), cout_s.view(-1), act, work)   # the host synchronisation, in front of the recurrence
+        # the status and the per-step counts in ONE more transfer (this host reads them from torch tensors; the native runtime gets them
+        # with the live-row count, csrc/rt_decoders.h)
+        nact_dev = (lens[None, :] > torch.arange(T, device=lens.device)[:, None]).sum(1)
+        info = torch.cat([holed.view(1).to(torch.int64), nact_dev.to(torch.int64)]).cpu().numpy()
+        flags, nrun, Tl = 0, None, T
+        if not info[0]:
+            G = ops.lstm_fwd_row_tile(rows)                                 # the step kernel's row tile: the projection covers its tiles
+            nact = info[1:]
+            flags = ops.FLAG_LIVE_PREFIX
+            nrun = [int(min(rows, -(-int(n) // G) * G)) for n in nact]
+            Tl = max(1, int((nact > 0).sum()))                              # steps behind the longest candidate: nothing to run
+        # forwardConnect (gen.lua:30-42) with the encoder state replicated over the chunk's options, in that order
+        def rep(x, key):
+            return ops.embed_gather(x, idx, ws.get(key, (rows, H)))
+        if layers is not None:
+            for ii in range(len(layers)):
+                self.rnnLayers[ii].userPrevOutput = rep(layers[ii].output[seqLen - 1], 'ret.h0_%d' % ii)
+                self.rnnLayers[ii].userPrevCell = rep(layers[ii].cell[seqLen - 1], 'ret.c0_%d' % ii)
+            self.rnnLayers[len(layers) - 1].userPrevOutput = rep(encOut, 'ret.enc')
+        else:
+            self.rnnLayers[-1].userPrevOutput = rep(encOut, 'ret.enc')
+        tl = cin_s[:Tl]
+        h = self.rnnLayers[0].forward(None, Tl, rows, tl, table=table, flags=flags)
+        for l in self.rnnLayers[1:]:
+            h = l.forward(h.view(Tl * rows, l.D), Tl, rows, tl, flags=flags, nrun=nrun[:Tl] if nrun else None)
+        nll = ws.get('ret.nll', (T, rows))
+        sorted_scores = ws.get('ret.sorted', (rows,))
+        ops.lhood_nll(h.view(Tl * rows, H), act, n_act, cout_s.view(-1), self.Wv, self.bv, nll.view(-1), V=V, H=H)
+        ops.lhood_sum(nll.view(-1), act, n_act, T, rows, rows, sorted_scores, rows)
+        back = torch.empty_like(sorted_scores)
+        back[perm] = sorted_scores                                          # plumbing: back to candidate order
+        lhood[:, o0:o0 + C] = back.view(N, C)
 
 
 def model(params, enc, fp, ws, drop):

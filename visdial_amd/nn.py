@@ -150,11 +150,15 @@ class SeqLSTM(object):
             o += d
         return out
 
-    def forward(self, x, T, N, tok_mask=None):
-        """x: [T*N, D] dense input rows (time-major), or a list of column blocks.  Returns h [T, N, H]."""
+    def forward(self, x, T, N, tok_mask=None, table=None, flags=0, nrun=None):
+        """x: [T*N, D] dense input rows (time-major), or a list of column blocks.  Returns h [T, N, H].
+        The forward-only recurrence over length-ordered candidates (decoders/gen.py retrieve_lhood): `table` = Emb*Wx+b [V+1, 4H] is
+        gathered by tok_mask's ids instead of projecting x (pass x = None); flags = ops.FLAG_LIVE_PREFIX skips the row groups without
+        a token, and with nrun (host list [T]: rows of step t up to the end of its last live row group, groups of
+        ops.lstm_fwd_row_tile(N) rows) the projection is made for exactly the rows the previous layer wrote and this one reads."""
         H, k = self.H, self.key
-        xs = list(x) if isinstance(x, (list, tuple)) else [x]
-        assert len(xs) == len(self.part_dims)
+        xs = [] if x is None else list(x) if isinstance(x, (list, tuple)) else [x]
+        assert table is not None or len(xs) == len(self.part_dims)
         h0, c0 = self.userPrevOutput, self.userPrevCell
         self.userPrevOutput = self.userPrevCell = None          # consumed once (rnn semantics)
         if h0 is not None and c0 is None:
@@ -170,12 +174,25 @@ class SeqLSTM(object):
         self.c = self.ws.get(k + '.c', (T, N, H))
         self.output, self.cell = self.h, self.c
         g2 = self.gates.view(T * N, 4 * H)
+        if table is not None:
+            ops.lstm_forward(table, self.Wh, self.gates, self.h, self.c, T, N, H, 0, 4 * H, tok_gather=tok_mask, tok_mask=tok_mask,
+                             h0=h0, c0=c0, flags=flags)
+            return self.h
+        if nrun is not None:
+            assert len(xs) == 1
+            for t in range(T):
+                if nrun[t] > 0:
+                    ops.gemm_nn(xs[0][t * N:t * N + nrun[t]], self.Wx, g2[t * N:t * N + nrun[t]], bias=self.b, M=int(nrun[t]), N=4 * H,
+                                K=self.D)
+            ops.lstm_forward(g2, self.Wh, self.gates, self.h, self.c, T, N, H, N * 4 * H, 4 * H, tok_mask=tok_mask, h0=h0, c0=c0,
+                             flags=flags)
+            return self.h
         # hoisted input projection, written straight into the gates buffer (the step kernel reads
         # and overwrites each element from the same thread, so the recurrence runs in place)
         for i, (xi, wi, d) in enumerate(zip(xs, self._wx_blocks(self.Wx), self.part_dims)):
             ops.gemm_nn(xi, wi, g2, bias=self.b if i == 0 else None, accumulate=(i > 0), M=T * N, N=4 * H, K=d)
         ops.lstm_forward(g2, self.Wh, self.gates, self.h, self.c, T, N, H, N * 4 * H, 4 * H, tok_mask=tok_mask,
-                         h0=h0, c0=c0)
+                         h0=h0, c0=c0, flags=flags)
         return self.h
 
     def backward(self, dh_seq=None, dh_last=None, need_dx=True):

@@ -80,6 +80,16 @@ def gemm_nn(A, B, C_out, bias=None, accumulate=False, M=None, N=None, K=None, ld
 
 FLAG_BF16 = 1      # VD_FLAG_BF16: bf16 operands / fp32 accumulation (opt-in, BASELINE configs[4])
 FLAG_SPLIT9, FLAG_SPLIT6, FLAG_SPLIT3 = 2, 4, 8   # exact three-way bf16 split of both operands: 9 products = fp32-grade (opt-in)
+# VD_FLAG_LIVE_PREFIX (lstm_forward with tok_mask): per step the rows with a token are a prefix of the rows; row groups without one are not
+# computed and stay unwritten.  LIVE_PREFIX_ROWS = VD_LIVE_PREFIX_ROWS, a multiple of every forward step kernel's row tile
+FLAG_LIVE_PREFIX, LIVE_PREFIX_ROWS = 16, 128
+
+
+def lstm_fwd_row_tile(N):
+    """row tile of the fp32 forward step kernel a recurrence over N rows runs (csrc/paths.h vd_lstm_fwd_row_tile): the height of the row
+    groups FLAG_LIVE_PREFIX skips"""
+    return 128 if N >= 2048 else 32
+
 PRECISION_FLAGS = {'fp32': 0, 'bf16': FLAG_BF16, 'split9': FLAG_SPLIT9, 'split6': FLAG_SPLIT6, 'split3': FLAG_SPLIT3}
 PRECISION_CODES = {'fp32': 0, 'bf16': 1, 'split9': 9, 'split6': 6, 'split3': 3}        # vd_model_params.lstmBf16
 
