@@ -34,6 +34,9 @@ def main():
     ap.add_argument('-fusedLhood', '--fusedLhood', type=int, default=0, choices=[0, 1],
                     help='gen decoder: score the candidates from their live (non-pad) rows only, through the fused vocabulary '
                          'projection + online log-sum-exp head (no logits buffer); 0 = the dense head')
+    ap.add_argument('-optionCache', '--optionCache', type=int, default=0,
+                    help='disc decoder: keep the encoding of every distinct candidate answer on the device while the split is ranked and run '
+                         'the option LSTM over the answers not seen before only (0 = off, 1 = on, larger = capacity in rows)')
     a = ap.parse_args()
     saved = load_checkpoint(a.loadPath)
     p = opts.derive(saved['modelParams'])                    # sets useHistory / useIm / concatHistory (evaluate.lua:69-75)
@@ -41,6 +44,9 @@ def main():
     if a.fusedLhood and p['decoder'] != 'gen':
         raise SystemExit('-fusedLhood 1: the live-row log-likelihood head is only for a generative model')
     p['fusedLhood'] = a.fusedLhood
+    if a.optionCache and p['decoder'] != 'disc':
+        raise SystemExit('-optionCache: the answer-encoding cache is only for a discriminative model')
+    p['optionCache'] = a.optionCache
     p.update(inputImg=a.inputImg, inputQues=a.inputQues, inputJson=a.inputJson)
     have = lambda f: os.path.exists(f) or os.path.exists(f[:-3] + '.npz')
     if os.path.exists(a.inputJson) and have(a.inputQues):
@@ -63,6 +69,9 @@ def main():
         metrics, records = model.retrieve(dl, a.split)
     else:
         records = model.predict(dl, a.split)
+    if a.optionCache:
+        ex, tot = model.optionCacheRows
+        print('optionCache: the option LSTM ran %d of %d candidate rows (%.1f %%)' % (ex, tot, 100.0 * ex / max(tot, 1)))
     if a.saveRanks:
         print('Writing ranks to %s' % a.saveRankPath)
         os.makedirs(os.path.dirname(os.path.abspath(a.saveRankPath)), exist_ok=True)

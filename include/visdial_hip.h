@@ -74,6 +74,14 @@ int vd_copy_2d(float* dst, int64_t dst_ld, const float* src, int64_t src_ld, int
  * VD_FLAG_SPLIT* the call is refused with an argument error. */
 #define VD_FLAG_LIVE_PREFIX 16
 #define VD_LIVE_PREFIX_ROWS 128
+/* VD_FLAG_STATE_ONLY (vd_lstm_forward): a forward pass that no backward follows.  `gates` must be NULL and `h` / `c` are
+ * [2 x N x H] ping-pong buffers: step t reads slot (t - 1) & 1 (h0 / c0 / zeros at t = 0) and writes slot t & 1, so on return the
+ * final state lies in slot (T - 1) & 1.  The gate activations and the cell update stay in registers: no gate value reaches memory
+ * (4 KB instead of 12 KB written per row and step at H = 512).  Same step kernels, tile shapes and arithmetic as the saving call:
+ * for equal (T, N, H, flags) and inputs the final h and c equal the saving call's last step bit for bit.  Combines with flags 0
+ * and VD_FLAG_SPLIT*, dense and table mode, tok_mask; refused (argument error) with VD_FLAG_BF16, with VD_FLAG_LIVE_PREFIX and
+ * with a non-NULL `gates`.  Without the flag a NULL `gates` is refused. */
+#define VD_FLAG_STATE_ONLY 32
 
 /* ---- dense contractions (nn.Linear / hoisted SeqLSTM input projection / weight grads) -- */
 /* C[MxN] (+)= act(A[MxK] * W[NxK]^T + bias)   -- nn.Linear:updateOutput (+nn.Tanh),
@@ -110,7 +118,7 @@ int vd_colsum_acc(const float* X, int64_t ld, int M, int N, float* out, void* st
  * by a gate-interleaved transpose of Wh [4H x H] made once per call; that work buffer is library-owned per (device, stream),
  * so calls on different streams may overlap.
  * flags: VD_FLAG_BF16 / VD_FLAG_SPLIT* choose the arithmetic of the recurrent product; VD_FLAG_LIVE_PREFIX (above) skips the
- * row groups without a live row. */
+ * row groups without a live row; VD_FLAG_STATE_ONLY (above) keeps only the running state (gates NULL, h / c [2 x N x H]). */
 int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const int32_t* tok_gather,
                     const int32_t* tok_mask, const float* Wh, const float* h0, const float* c0, float* gates,
                     float* h, float* c, int T, int N, int H, int flags, void* stream);
@@ -392,7 +400,16 @@ int vd_model_forward_backward(vd_model* m, int only_forward);
 int vd_model_loss(vd_model* m, float* loss);              /* curLoss of the last forward (waits for it): disc = mean
                                                              cross-entropy, gen = summed NLL (model.lua:309-311,330) */
 /* Model:retrieveBatch up to the option scores (model.lua:344-425): disc = scores of a forward pass, gen = candidate
- * log-likelihoods (utils.computeLhood, utils.lua:86-102); read with vd_model_scores / vd_model_ranks */
+ * log-likelihoods (utils.computeLhood, utils.lua:86-102); read with vd_model_scores / vd_model_ranks.
+ * Answer-encoding cache (decoder disc, opt-in): with the environment variable VD_OPTION_CACHE set when vd_model_create runs
+ * (0 / unset = off, 1 = on with 262 144 rows, a larger value = the capacity in rows) and training off, vd_model_retrieve and
+ * vd_model_forward_backward(only_forward = 1) keep the final hidden state of every distinct candidate row (key: its tokens and
+ * To) in a device table and run the option recurrence (VD_FLAG_STATE_ONLY) over the rows not seen before only.  The table is
+ * emptied by vd_model_set_training(on != 0), vd_model_set_tensor, vd_model_init_params, vd_model_update,
+ * vd_model_forward_backward(only_forward = 0) and vd_model_flat_pointers; a host that writes the weights through the pointers of
+ * the latter must call one of these afterwards.  A batch uploaded while the cache is on and training is off carries the unseen
+ * rows only: it serves these two calls, not a backward pass.  vd_model_create refuses the variable for decoder gen and for
+ * lstmBf16 = 1. */
 int vd_model_retrieve(vd_model* m);
 /* the same contract for the generative decoder through the live-row head (vd_lhood_* above): scores within the fp32 rounding of
  * vd_model_retrieve's, no logits buffer, one host synchronisation per chunk of options (the live-row count).  An argument error
@@ -432,7 +449,9 @@ int vd_model_scores(vd_model* m, float* host_scores, int64_t n);        /* [N x 
 int vd_model_ranks(vd_model* m, int use_gt, int32_t* host_ranks);       /* utils.computeRanks (utils.lua:106-128) */
 /* decoder disc: rows the option LSTM executed for the batch of the LAST STEP (before any step: of the uploaded batch) vs the N * O
  * candidates they stand for -- the upload encodes every DISTINCT candidate row once (decoders/disc.lua:4-15: the encoding depends on
- * the tokens only).  In a pipelined loop this is the batch that was stepped, not the one prefetched behind it. */
+ * the tokens only).  In a pipelined loop this is the batch that was stepped, not the one prefetched behind it.  With the
+ * answer-encoding cache (vd_model_retrieve) `executed` counts the rows the recurrence ran in that step -- the rows the cache did
+ * not hold, possibly 0. */
 int vd_model_option_rows(vd_model* m, int64_t* executed, int64_t* total);
 int vd_model_family_ms(vd_model* m, float* ms3);          /* device ms of option-LSTM fwd, bwd, dWh in the last step */
 int vd_model_synchronize(vd_model* m);

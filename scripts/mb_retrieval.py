@@ -7,7 +7,17 @@ heads (from shapes), batches/s of both heads alternated in one process after war
     python scripts/mb_retrieval.py [--repeats 7] [--only fused --profile uniform|short]   (--only fused: that head alone, for a trace)
 A/B of two libraries (VD_LIB_PATH selects one): --tag NAME marks the process's lines, every profile also prints option_rows() of the
 last fused call (the rows the candidate recurrence ran), and --save-scores PATH.npz keeps the fused scores per profile so that two
-libraries' scores can be compared afterwards."""
+libraries' scores can be compared afterwards.
+
+--mode disc: discriminative evaluation with and without the answer-encoding cache (params optionCache) at full
+size: mn-att-ques-im-hist + disc, 20 dialogs x 10 rounds x 100 options, To = 20, split9.  The synthetic loader has no repeats, so the
+candidates of --batches batches are drawn from a pool of --pool distinct answers.  Per case batches/s over one pass of those batches
+(upload + retrieve + ranks per batch, as evaluate.py runs it), median over --repeats with min / max: uncached; cached and cold (first
+pass after a flush); cached and warm (second pass), with the rows the recurrence ran and the device memory the process holds after
+each case.  --cases uncached runs the first alone (the parent commit's library through VD_LIB_PATH knows no cache), --cases cached the other two
+(for a kernel trace).
+--mode step: the option recurrence alone (vd_lstm_forward, table mode, 20 000 x 512, 20 steps), saving against VD_FLAG_STATE_ONLY,
+alternated, device time by events."""
 import argparse
 import os
 import sys
@@ -26,7 +36,124 @@ ap.add_argument('--only', choices=('fused',), help='the live-row head alone, for
 ap.add_argument('--profile', choices=('uniform', 'short'), help='one length profile only')
 ap.add_argument('--tag', default='', help='printed in front of the per-head lines (A/B of two libraries)')
 ap.add_argument('--save-scores', default='', help='write the fused scores of every profile to this .npz')
+ap.add_argument('--mode', choices=('gen', 'disc', 'step'), default='gen')
+ap.add_argument('--pool', type=int, default=2000, help='--mode disc: distinct answers the candidates are drawn from')
+ap.add_argument('--batches', type=int, default=6, help='--mode disc: batches per pass')
+ap.add_argument('--cases', choices=('all', 'uncached', 'cached'), default='all', help='--mode disc')
 opt = ap.parse_args()
+
+
+def held_mb():
+    """device memory in use on the card, MB (the library allocates with hipMalloc, outside the tensor library's pool)"""
+    import torch
+    free, total = torch.cuda.mem_get_info()
+    return (total - free) / 1e6
+
+
+def disc_mode():
+    B, R, O, To, H = 20, 10, 100, 20, 512
+    p = derive(default_params(encoder='mn-att-ques-im-hist', decoder='disc', vocabSize=11322, imgFeatureSize=512, imgSpatialSize=14,
+                              maxHistoryLenPerRound=40, batchSize=B, numOptions=O, maxQuesCount=R, maxAnsLen=To, lstmPrecision='split9',
+                              gpuid=0))
+    tag = opt.tag and opt.tag + ' '
+    rng = np.random.RandomState(5)
+    lens = rng.randint(1, To + 1, size=opt.pool)
+    pool = (rng.randint(1, p['vocabSize'], size=(opt.pool, To)) * (np.arange(To)[None, :] < lens[:, None])).astype(np.int32)
+    pool = np.unique(pool, axis=0)
+    dl = SyntheticDataloader(p, seed=7, num_threads=B * opt.batches)
+    batches, start = [], 1
+    for _ in range(opt.batches):
+        b, start = dl.getTestBatch(start, p, 'val')
+        b['options'] = pool[rng.randint(0, pool.shape[0], size=B * R * O)].reshape(B * R, O, To)
+        batches.append(b)
+    distinct = len({r.tobytes() for b in batches for r in b['options'].reshape(-1, To)})
+    print("%smn-att-ques-im-hist + disc, H %d, %d dialogs x %d rounds x %d options, To %d, split9, native host, random weights; pool of %d "
+          "distinct answers, %d batches per pass = %d candidate rows, %d distinct" % (tag, H, B, R, O, To, pool.shape[0], opt.batches,
+                                                                                  opt.batches * B * R * O, distinct), flush=True)
+    base_mb = held_mb()
+
+    def one_pass(nat):
+        rows, t0 = 0, time.perf_counter()
+        for b in batches:
+            nat.retrieveBatch(b, useGt=True)
+            rows += nat.option_rows()[0]
+        return (time.perf_counter() - t0) / len(batches), rows
+
+    def report(name, ts, rows, mb):
+        t = np.asarray(ts)
+        print("  %s%-14s %7.2f ms per batch (median of %d; min %.2f, max %.2f) = %6.2f batches/s; rows the recurrence ran per pass %d; "
+              "device memory held %.0f MB" % (tag, name, np.median(t) * 1e3, len(t), t.min() * 1e3, t.max() * 1e3, 1.0 / np.median(t), rows,
+                                             mb), flush=True)
+    scores = {}
+    for cached in {'uncached': (0,), 'cached': (1,), 'all': (0, 1)}[opt.cases]:
+        nat = NativeModel(dict(p, optionCache=cached), init_seed=1)
+        nat.training(False)
+        one_pass(nat)                                   # warm-up: workspaces, code objects
+        one_pass(nat)
+        cold, warm, rows_c, rows_w = [], [], 0, 0
+        for _ in range(opt.repeats):
+            if cached:
+                nat.training(True)                      # flush
+                nat.training(False)
+            t, rows_c = one_pass(nat)
+            cold.append(t)
+            t, rows_w = one_pass(nat)
+            warm.append(t)
+        scores[cached] = nat.scores(B * R, O).copy()
+        mb = held_mb() - base_mb
+        if cached:
+            report('cached cold', cold, rows_c, mb)
+            report('cached warm', warm, rows_w, mb)
+        else:
+            report('uncached', cold + warm, rows_c, mb)
+        nat.close()
+    if len(scores) == 2:
+        print("  worst |cached - uncached| score of the last batch %.3e (|score| max %.2f)"
+              % (np.abs(scores[0].astype(np.float64) - scores[1]).max(), np.abs(scores[0]).max()))
+
+
+def step_mode():
+    import torch
+    from visdial_amd import ops
+    N, H, T, Vt = 20000, 512, 20, 11323
+    g = torch.Generator(device='cuda').manual_seed(1)
+    table = torch.randn(Vt, 4 * H, device='cuda', generator=g) * 0.5
+    Wh = torch.randn(H, 4 * H, device='cuda', generator=g) / H ** 0.5
+    tok = torch.randint(1, Vt, (T, N), device='cuda', dtype=torch.int32, generator=g)
+    gates, h, c = (torch.empty(T, N, k * H, device='cuda') for k in (4, 1, 1))
+    h2, c2 = torch.empty(2, N, H, device='cuda'), torch.empty(2, N, H, device='cuda')
+    for name, flags in (('split9', ops.FLAG_SPLIT9), ('fp32', 0)):
+        def run(state):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            if state:
+                ops.lstm_forward(table, Wh, None, h2, c2, T, N, H, 0, 4 * H, tok_gather=tok, flags=flags | ops.FLAG_STATE_ONLY)
+            else:
+                ops.lstm_forward(table, Wh, gates, h, c, T, N, H, 0, 4 * H, tok_gather=tok, flags=flags)
+            b.record()
+            b.synchronize()
+            return a.elapsed_time(b)
+        for st in (0, 1, 0, 1):
+            run(st)
+        ts = {0: [], 1: []}
+        for _ in range(opt.repeats):
+            for st in (0, 1):
+                ts[st].append(run(st))
+        same = bool((h2[(T - 1) & 1] == h[T - 1]).all()) and bool((c2[(T - 1) & 1] == c[T - 1]).all())
+        for st in (0, 1):
+            t = np.asarray(ts[st])
+            print("  %s%s %-10s %d x %d, %d steps: %7.3f ms per pass (median of %d; min %.3f, max %.3f) = %.3f ms per step"
+                  % (opt.tag and opt.tag + ' ', name, 'state-only' if st else 'saving', N, H, T, np.median(t), len(t), t.min(), t.max(),
+                     np.median(t) / T), flush=True)
+        print("  %s: final h and c bit-identical: %s" % (name, same))
+
+
+if opt.mode == 'disc':
+    disc_mode()
+    sys.exit(0)
+if opt.mode == 'step':
+    step_mode()
+    sys.exit(0)
 V, H, R, O, B, L = 11322, 512, 10, 100, 20, 20
 T = L + 1
 

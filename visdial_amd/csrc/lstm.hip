@@ -122,6 +122,11 @@ struct EpiLstmFwdT {
   }
   // a[g] = the reduced pre-activation sums of gate g for this lane's (row, 4 hidden units)
   __device__ __forceinline__ void dist_store(const float4 (&a)[4], const DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
+    dist_store_t<true>(a, q, row0, vcol0, lane, grp, M);
+  }
+  // GATES = false (EpiLstmFwdState): the activations stay in registers, only c and h are stored
+  template <bool GATES>
+  __device__ __forceinline__ void dist_store_t(const float4 (&a)[4], const DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
     const int j = (vcol0 >> 7) * 32 + (lane & 7) * 4;
     const int row = row0 + grp * 8 + (lane >> 3);
     if (row >= M || j >= H) return;
@@ -136,11 +141,13 @@ struct EpiLstmFwdT {
     h.E = go.E * vd_tanh(c.E);
     VD_CELLD(x) VD_CELLD(y) VD_CELLD(z) VD_CELLD(w)
 #undef VD_CELLD
+    if constexpr (GATES) {
     float* gr = gates + (long)row * 4 * H + j;
     *reinterpret_cast<float4*>(gr) = gi;
     *reinterpret_cast<float4*>(gr + H) = gf;
     *reinterpret_cast<float4*>(gr + 2 * H) = go;
     *reinterpret_cast<float4*>(gr + 3 * H) = gg;
+    }
     *reinterpret_cast<float4*>(c_out + (long)row * H + j) = c;
     *reinterpret_cast<float4*>(h_out + (long)row * H + j) = h;
     if (h16) vd_st4_bf16(h16 + (long)row * H + j, h);
@@ -173,7 +180,12 @@ struct EpiLstmFwdT {
     }
   }
   __device__ __forceinline__ void operator()(const f32x16 (&acc)[4], int row0, int vcol0, int lane, int M,
-                                             int /*Nv*/, float* scr, const Pre* pre = nullptr) const {
+                                             int Nv, float* scr, const Pre* pre = nullptr) const {
+    run<true>(acc, row0, vcol0, lane, M, Nv, scr, pre);
+  }
+  template <bool GATES>
+  __device__ __forceinline__ void run(const f32x16 (&acc)[4], int row0, int vcol0, int lane, int M,
+                                      int /*Nv*/, float* scr, const Pre* pre) const {
     if constexpr (SEQ == 1) {
       sequential(acc, row0, vcol0, lane, M, scr);
       return;
@@ -306,10 +318,12 @@ struct EpiLstmFwdT {
           if (h_out) vd_buf_st4(rh, vrow, sp, h);
           vd_buf_st4_bf16(rh16, vrow >> 1, sp >> 1, h);
         } else {
+        if constexpr (GATES) {
         vd_buf_st4(rg, vg, 4u * sp, gi);                              // saved for the backward pass
         vd_buf_st4(rg, vg, 4u * sp + uH4, gf);
         vd_buf_st4(rg, vg, 4u * sp + 2 * uH4, go);
         vd_buf_st4(rg, vg, 4u * sp + 3 * uH4, gg);
+        }
         vd_buf_st4(rco, vrow, sp, c);
         vd_buf_st4(rh, vrow, sp, h);
         if (h16) vd_buf_st4_bf16(rh16, vrow >> 1, sp >> 1, h);
@@ -326,6 +340,19 @@ using EpiLstmFwd = EpiLstmFwdT<0>;
 struct EpiLstmFwdLive : EpiLstmFwd {
   static constexpr bool HAS_DEAD = true;
   __device__ __forceinline__ bool dead(int row_base, int /*BM*/) const { return tok_mask[row_base] == 0; }   // row_base < M: the tile was launched
+};
+
+// VD_FLAG_STATE_ONLY: the same arithmetic with the four gate stores left out -- a forward pass that no backward follows keeps i, f, o, g in
+// registers and writes c and h only (4 KB instead of 12 KB per row and step at H = 512).  `gates` is null.  A type of its own for the same
+// reason as EpiLstmFwdLive: the saving step kernels keep their instantiations.
+struct EpiLstmFwdState : EpiLstmFwd {
+  __device__ __forceinline__ void dist_store(const float4 (&a)[4], const DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
+    dist_store_t<false>(a, q, row0, vcol0, lane, grp, M);
+  }
+  __device__ __forceinline__ void operator()(const f32x16 (&acc)[4], int row0, int vcol0, int lane, int M, int Nv, float* scr,
+                                             const Pre* pre = nullptr) const {
+    run<false>(acc, row0, vcol0, lane, M, Nv, scr, pre);
+  }
 };
 
 // ---------------------------------------------------------------------------
@@ -846,7 +873,14 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
                     const int32_t* tok_mask, const float* Wh, const float* h0, const float* c0, float* gates,
                     float* h, float* c, int T, int N, int H, int flags, void* stream) {
   VD_CHECK_ARG(T >= 0 && N >= 0 && H > 0 && H % 32 == 0, "vd_lstm_forward: bad dims T=%d N=%d H=%d", T, N, H);
-  VD_CHECK_ARG(xproj && Wh && gates && h && c, "vd_lstm_forward: null pointer");
+  VD_CHECK_ARG(xproj && Wh && h && c, "vd_lstm_forward: null pointer");
+  const bool state_only = (flags & VD_FLAG_STATE_ONLY) != 0;
+  VD_CHECK_ARG(state_only || gates, "vd_lstm_forward: null pointer (gates may be NULL only with VD_FLAG_STATE_ONLY)");
+  VD_CHECK_ARG(!state_only || !gates, "vd_lstm_forward: VD_FLAG_STATE_ONLY saves no gate activations: gates must be NULL");
+  VD_CHECK_ARG(!state_only || !(flags & VD_FLAG_BF16),
+               "vd_lstm_forward: VD_FLAG_STATE_ONLY does not combine with VD_FLAG_BF16 (the bf16 recurrence reads the saved bf16 copy of h; flags = %d)", flags);
+  VD_CHECK_ARG(!state_only || !(flags & VD_FLAG_LIVE_PREFIX),
+               "vd_lstm_forward: VD_FLAG_STATE_ONLY does not combine with VD_FLAG_LIVE_PREFIX (flags = %d)", flags);
   VD_CHECK_ARG((h0 == nullptr) == (c0 == nullptr), "vd_lstm_forward: h0 and c0 must both be set or both null");
   VD_CHECK_ARG(x_ld % 4 == 0, "vd_lstm_forward: x_ld must be a multiple of 4");
   // the step epilogue addresses its tensors with 32-bit byte offsets (buffer descriptors, common.h): one step's slice of every
@@ -884,9 +918,9 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
   if (bf16) {
     if (int rc0 = vd_bf16_shadow_get(0, h, (size_t)T * NH, &h16)) return rc0;
   } else {
-    vd_bf16_shadow_invalidate(h, (size_t)T * NH);
+    vd_bf16_shadow_invalidate(h, (size_t)(state_only ? 2 : T) * NH);
   }
-  vd_bf16_shadow_invalidate(gates, (size_t)T * 4 * NH);     // this pass overwrites `gates`: a da shadow registered over it (last backward) is stale
+  if (gates) vd_bf16_shadow_invalidate(gates, (size_t)T * 4 * NH);     // this pass overwrites `gates`: a da shadow registered over it (last backward) is stale
   // ... and READ the shadow of h_{t-1} and a bf16 copy of the transposed weights through the LDS-DMA pipeline
   vd_bf16_bits* WhT16 = nullptr;
   if (bf16 && T > 1) {
@@ -894,21 +928,32 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
     if (int rc0 = weights_to_bf16(WhT, WhT16, 4L * H * H, s)) return rc0;
   }
   for (int t = 0; t < T; ++t) {
-    const float* hp = t ? h + (t - 1) * NH : h0;
-    const float* cp = t ? c + (t - 1) * NH : c0;
+    // VD_FLAG_STATE_ONLY: h and c are [2 x N x H] ping-pong buffers, step t reads slot (t - 1) & 1 and writes slot t & 1
+    const long so = state_only ? (long)(t & 1) * NH : t * NH, sp = state_only ? (long)((t - 1) & 1) * NH : (t - 1) * NH;
+    const float* hp = t ? h + sp : h0;
+    const float* cp = t ? c + sp : c0;
     EpiLstmFwd e;
     e.xproj = xproj + (long)t * x_tstride;
     e.xld = x_ld;
     e.tok_gather = tok_gather ? tok_gather + (long)t * N : nullptr;
     e.tok_mask = tok_mask ? tok_mask + (long)t * N : nullptr;
     e.c_prev = cp;
-    e.gates = gates + (long)t * 4 * NH;
-    e.c_out = c + t * NH;
-    e.h_out = h + t * NH;
+    e.gates = gates ? gates + (long)t * 4 * NH : nullptr;
+    e.c_out = c + so;
+    e.h_out = h + so;
     e.H = H;
     e.h16 = h16 ? h16 + t * NH : nullptr;
     int rc;
-    if (live) {   // (fp32 only: neither bf16 nor split) the same three paths with the row-tile predicate
+    if (state_only) {   // (neither bf16 nor the live prefix) the paths of the saving pass with the epilogue that stores c and h only
+      EpiLstmFwdState es;
+      static_cast<EpiLstmFwd&>(es) = e;
+      if (!hp) rc = lstm_step_fwd(nullptr, Wh, N, H, 0, es, s);
+      else if (split == 9) rc = launch_gemm_split<9>(N, 4 * H, H, hp, (long)H, W3, (long)H, 4L * H * H, es, s);
+      else if (split == 6) rc = launch_gemm_split<6>(N, 4 * H, H, hp, (long)H, W3, (long)H, 4L * H * H, es, s);
+      else if (split == 3) rc = launch_gemm_split<3>(N, 4 * H, H, hp, (long)H, W3, (long)H, 4L * H * H, es, s);
+      else if (glds) rc = launch_gemm_glds<CfgF9, false>(N, 4 * H, H, 1, hp, (long)H, WhT, (long)H, es, s);
+      else rc = lstm_step_fwd(hp, Wh, N, H, H, es, s);
+    } else if (live) {   // (fp32 only: neither bf16 nor split) the same three paths with the row-tile predicate
       EpiLstmFwdLive el;
       static_cast<EpiLstmFwd&>(el) = e;
       if (!hp) rc = lstm_step_fwd(nullptr, Wh, N, H, 0, el, s);

@@ -96,12 +96,82 @@ struct BatchSlot {
   // counting sort of the option tokens (the table gradient's row order), done on the copy stream at upload time: it depends on the
   // batch alone, and inside the step it stood in front of the encoder backward in the side streams' in-order hardware queue
   int32_t *opt_sort_off = nullptr, *opt_sort_perm = nullptr;
+  // answer-encoding cache (OptionCache): the slot was resolved against the cache -- opt = the MISS rows only, opt_uid = table row of every
+  // candidate; miss_keys [opt.N x To] wait for the step's commit, opt_host keeps the batch's rows for a second resolution
+  bool cached = false;
+  uint64_t cache_stamp = 0;
+  std::vector<int32_t> miss_keys, opt_host;
   hipEvent_t ready = nullptr;  // recorded on the copy stream when the upload has landed
   hipEvent_t done = nullptr;   // recorded on the main stream behind the last reader of this slot
   bool used = false;      // a step has read this slot (done is recorded)
   bool uploaded = false;  // ready is recorded (an upload has been issued into this slot)
   std::map<std::string, DevBuf> bufs, pinned;
 };
+
+// Host index of distinct token rows (open addressing over the rows' tokens): id = order of insertion.  The option de-duplication of one
+// batch and the answer-encoding cache (OptionCache) both key candidate rows with it.
+struct RowIndex {
+  int T = 0;
+  std::vector<int32_t> keys;    // [size x T]
+  std::vector<int32_t> table;   // power of two, -1 = empty
+  int32_t size() const { return T ? (int32_t)(keys.size() / (size_t)T) : 0; }
+  void reset(int T_) {
+    T = T_;
+    keys.clear();
+    table.assign(1024, -1);
+  }
+  size_t home(const int32_t* row) const {
+    uint64_t h = 1469598103934665603ull;
+    for (int t = 0; t < T; ++t) h = (h ^ (uint32_t)row[t]) * 1099511628211ull;
+    return (size_t)(h ^ (h >> 29)) & (table.size() - 1);
+  }
+  int32_t find(const int32_t* row) const {
+    for (size_t pos = home(row);; pos = (pos + 1) & (table.size() - 1)) {
+      const int32_t u = table[pos];
+      if (u < 0) return -1;
+      if (memcmp(keys.data() + (size_t)u * T, row, (size_t)T * sizeof(int32_t)) == 0) return u;
+    }
+  }
+  int32_t add(const int32_t* row) {   // the row is not in the index
+    if ((size_t)(size() + 1) * 2 > table.size()) {
+      table.assign(table.size() * 2, -1);
+      for (int32_t u = 0; u < size(); ++u) place(keys.data() + (size_t)u * T, u);
+    }
+    const int32_t id = size();
+    keys.insert(keys.end(), row, row + T);
+    place(keys.data() + (size_t)id * T, id);
+    return id;
+  }
+  void place(const int32_t* row, int32_t id) {
+    size_t pos = home(row);
+    while (table[pos] >= 0) pos = (pos + 1) & (table.size() - 1);
+    table[pos] = id;
+  }
+};
+
+// Answer-encoding cache of the discriminative decoder (VD_OPTION_CACHE; include/visdial_hip.h at vd_model_retrieve).  A candidate's
+// encoding depends on its tokens, on To (trailing pads advance the state) and on the weights only, so while the weights stand still
+// the final h of every distinct (row, To) is kept in `table` [rows x H]; slot = RowIndex id.  The index flushes when To changes.
+//   * upload (copy stream, ahead of the step): resolves the N * O rows against the COMMITTED index; rows it does not hold are
+//     de-duplicated inside the batch and numbered count, count + 1, ... (the slot's miss_keys); nothing is inserted yet, so a batch
+//     that is replaced or never stepped leaves no entry behind
+//   * step: runs the state-only recurrence over the misses, copies their final h to table rows [count, count + misses) and only then
+//     inserts the first (capacity - count) of them.  Misses beyond the capacity stay in the tail of the table for this step alone.
+//   * `stamp` moves with every flush and every step; a slot resolved under another stamp (stepped twice, flushed in between) is
+//     resolved again from the host copy of its rows at step time.
+struct OptionCache {
+  long capacity = 0;       // rows; 0 = off
+  RowIndex index;
+  float* table = nullptr;
+  long table_rows = 0;     // allocated; grows geometrically up to capacity + the largest batch's misses
+  uint64_t stamp = 1;
+  void flush() {
+    index.reset(index.T);
+    ++stamp;
+  }
+};
+static constexpr long VD_OPTION_CACHE_DEFAULT_ROWS = 262144;   // 512 MiB of fp32 state at H = 512
+static constexpr long VD_OPTION_CACHE_FIRST_ROWS = 16384;      // first allocation; doubles from there
 
 struct Encoder;
 struct Decoder;
@@ -152,6 +222,7 @@ struct vd_model {
   long lhood_exec = -1, lhood_total = 0;
   // capability flags from the encoder NAME (opts.lua:54-67)
   bool use_im = false, use_hist = false, is_att = false, is_graph = false;
+  vdrt::OptionCache ocache;
   bool prof_hist = false;   // ev_prof[0..3] bracket the history branch of a Sequential encoder (gen pairs: vd_model_family_ms)
   ~vd_model();
 };

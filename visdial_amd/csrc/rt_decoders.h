@@ -6,6 +6,8 @@
 
 namespace vdrt {
 
+int option_cache_resolve(vd_model* m, BatchSlot& sl, const int32_t* options, long NO, int To, hipStream_t s);   // runtime.hip
+
 struct Decoder {
   virtual ~Decoder() {}
   virtual void declare(vd_model* m) = 0;
@@ -68,6 +70,7 @@ struct Disc : Decoder {
   int forward_backward(vd_model* m, BatchSlot& b, bool only_forward) override {
     VD_CHECK_ARG(b.opt.present, "decoder 'disc' needs batch.options");
     VD_CHECK_ARG(only_forward || b.has_gt, "training decoder 'disc' needs batch.answer_ind");
+    if (b.cached) return forward_cached(m, b, only_forward);
     // NO = rows the option LSTM executes: N * O, or the number of DISTINCT candidates when the upload de-duplicated them
     const int N = b.q.N, O = m->p.numOptions, NOfull = N * O, NO = b.opt.N, To = b.opt.T;
     const bool dedup = b.opt_uid != nullptr;
@@ -199,6 +202,77 @@ struct Disc : Decoder {
     return VD_OK;
   }
   int retrieve(vd_model* m, BatchSlot& b) override { return forward_backward(m, b, true); }   // model.lua:421-425
+
+  // Evaluation through the answer-encoding cache (OptionCache, rt_core.h): b.opt holds the rows the cache did not have at upload time
+  // (possibly none) and b.opt_uid the table row of every candidate.  The state-only recurrence runs over those rows alone, their final h
+  // goes to the table, and the scores read the table through one gather -- a batch of known answers launches no recurrence kernel.
+  int forward_cached(vd_model* m, BatchSlot& b, bool only_forward) {
+    if (!only_forward || m->training) {
+      vd_set_error("decoder 'disc': this batch was uploaded for cached evaluation (VD_OPTION_CACHE with training off) and carries only the "
+                   "candidate rows the cache did not hold; upload it again after vd_model_set_training(1) for a training step");
+      return VD_ERR_STATE;
+    }
+    OptionCache& oc = m->ocache;
+    const int N = b.q.N, O = m->p.numOptions, NOfull = N * O, To = b.opt.T;
+    const long H = m->p.rnnHiddenSize, E = m->p.embedSize, V = m->p.vocabSize;
+    hipStream_t s = m->s_main;
+    hipStream_t se = side_stream(m, m->s_enc, s);
+    if (b.cache_stamp != oc.stamp) {   // flushed or stepped since the upload: resolve again (the copy out of the staging buffers has to land first)
+      VD_HIP(hipEventSynchronize(b.ready));
+      VD_TRY(option_cache_resolve(m, b, b.opt_host.data(), NOfull, To, s));
+      VD_HIP(hipStreamSynchronize(s));   // (the next upload into this slot waits for `ready` only before it rewrites the staging buffers)
+    }
+    const int U = b.opt.N;
+    const long count = oc.index.size();
+    VD_CHECK_ARG(b.opt_total == NOfull && (long)b.miss_keys.size() == (long)U * To && count <= oc.capacity,
+                 "decoder 'disc': inconsistent cached batch (%d candidates, %d misses)", b.opt_total, U);
+    if (oc.table_rows < count + U) {   // grow: doubling up to the capacity (+ this batch's rows beyond it)
+      const long want = std::min(std::max(2 * oc.table_rows, VD_OPTION_CACHE_FIRST_ROWS), oc.capacity);
+      const long rows = std::max(want, count + U);
+      float* nt = nullptr;
+      VD_HIP(hipMalloc((void**)&nt, (size_t)rows * H * sizeof(float)));
+      if (oc.table) {
+        if (count > 0) VD_HIP(hipMemcpyAsync(nt, oc.table, (size_t)count * H * sizeof(float), hipMemcpyDeviceToDevice, s));
+        VD_HIP(hipStreamSynchronize(s));   // earlier steps' gathers read the old table
+        VD_HIP(hipFree(oc.table));
+      }
+      oc.table = nt;
+      oc.table_rows = rows;
+    }
+    float *scores, *loss_rows, *full;
+    VD_TRY(ws_get(m, "opt.scores", (size_t)N * O, &scores));
+    VD_TRY(ws_get(m, "crit.loss_rows", (size_t)N, &loss_rows));
+    VD_TRY(ws_get(m, "opt.h_full", (size_t)NOfull * H, &full));
+    VD_TRY(fork_stream(m, s, se));
+    if (U > 0) {
+      VdRange r("disc: option LSTM forward (state only, cache misses)");
+      float *table, *h, *c;
+      VD_TRY(ws_get(m, "opt.table", (size_t)(V + 1) * 4 * H, &table));
+      VD_TRY(ws_get(m, "opt.h2", (size_t)2 * U * H, &h));
+      VD_TRY(ws_get(m, "opt.c2", (size_t)2 * U * H, &c));
+      float* Wopt = Wp(m, "opt.W");
+      VD_TRY(vd_gemm_nn(Wp(m, "embed"), E, Wopt, 4 * H, Wp(m, "opt.b"), table, 4 * H, (int)V + 1, (int)(4 * H), (int)E, 0, s));
+      VD_TRY(vd_lstm_forward(table, 0, 4 * H, b.opt.tok, nullptr, Wopt + E * 4 * H, nullptr, nullptr, nullptr, h, c, To, U, (int)H,
+                             m->flags | VD_FLAG_STATE_ONLY, s));
+      VD_HIP(hipMemcpyAsync(oc.table + count * H, h + (long)((To - 1) & 1) * U * H, (size_t)U * H * sizeof(float), hipMemcpyDeviceToDevice, s));
+      // the fill is enqueued: the rows that fit become entries (slot = count + i, the numbering the upload used)
+      const long fit = std::min<long>(U, oc.capacity - count);
+      for (long i = 0; i < fit; ++i) oc.index.add(b.miss_keys.data() + (size_t)i * To);
+    }
+    ++oc.stamp;   // this slot's resolution is spent: rows beyond the capacity live in the table's tail for this step only
+    float* enc_out = nullptr;
+    {
+      VdRange r("encoder forward");
+      VD_TRY(m->enc->forward(m, se, b, &enc_out));
+    }
+    VD_TRY(join_stream(m, se, s));
+    VD_TRY(vd_embed_gather(oc.table, b.opt_uid, nullptr, full, NOfull, (int)H, 1.f, s));
+    VD_TRY(vd_score_ce(full, enc_out, b.gt, scores, loss_rows, nullptr, nullptr, N, O, (int)H, 1.0f / N, s));
+    VD_TRY(stage_loss(m, loss_rows, N, false, s));
+    m->scores = scores;
+    m->prof_valid = false;
+    return VD_OK;
+  }
 };
 
 // ------------------------------------------------------------------------------------------------------------

@@ -108,6 +108,48 @@ bool has(const std::string& s, const char* sub) { return s.find(sub) != std::str
 
 }  // namespace
 
+// OptionCache (rt_core.h): resolve the NO candidate rows of a batch against the committed index and stage the rows it does not hold
+int vdrt::option_cache_resolve(vd_model* m, BatchSlot& sl, const int32_t* options, long NO, int To, hipStream_t s) {
+  OptionCache& oc = m->ocache;
+  if (oc.index.T != To) {   // To is part of the key: the same tokens behind another number of trailing pads are another encoding
+    oc.index.reset(To);
+    ++oc.stamp;
+  }
+  const int32_t count = oc.index.size();
+  RowIndex miss;
+  miss.reset(To);
+  int32_t* up = nullptr;
+  VD_TRY(pin_get(sl.pinned, "opt.uid.stage", (size_t)NO * sizeof(int32_t), (void**)&up));
+  for (long r = 0; r < NO; ++r) {
+    const int32_t* row = options + (size_t)r * To;
+    int32_t u = oc.index.find(row);
+    if (u < 0) {
+      int32_t l = miss.find(row);
+      if (l < 0) l = miss.add(row);
+      u = count + l;   // the table row the step fills for it
+    }
+    up[r] = u;
+  }
+  const int U = miss.size();
+  sl.miss_keys.swap(miss.keys);
+  sl.cached = true;
+  sl.cache_stamp = oc.stamp;
+  sl.opt_total = (int)NO;
+  if (U > 0) {
+    VD_TRY(upload_tokens(sl, sl.opt, "opt", sl.miss_keys.data(), U, To, false, s));
+  } else {
+    sl.opt.T = To;
+    sl.opt.N = 0;
+    sl.opt.present = true;
+    sl.opt.sorted = false;
+    sl.opt.tok = nullptr;
+  }
+  VD_TRY(dev_get(sl.bufs, "opt.uid", (size_t)NO * sizeof(int32_t), (void**)&sl.opt_uid));
+  VD_HIP(hipMemcpyAsync(sl.opt_uid, up, (size_t)NO * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  sl.opt_sort_off = sl.opt_sort_perm = nullptr;   // no backward follows: the table gradient's token sort is not made
+  return VD_OK;
+}
+
 extern "C" {
 
 int vd_model_create(const vd_model_params* p, const char* encoder, const char* decoder, vd_model** out) {
@@ -136,9 +178,22 @@ int vd_model_create(const vd_model_params* p, const char* encoder, const char* d
   VD_CHECK_ARG(p->dropout >= 0.f && p->dropout < 1.f, "vd_model_create: dropout must lie in [0, 1)");
   const int flags = vd_precision_flags(p->lstmBf16);
   VD_CHECK_ARG(flags >= 0, "vd_model_create: lstmBf16 must be 0, 1, 3, 6 or 9 (got %d)", p->lstmBf16);
+  // answer-encoding cache (include/visdial_hip.h at vd_model_retrieve): 0 / unset = off, 1 = default capacity, larger = rows
+  long cache_rows = 0;
+  if (const char* e = getenv("VD_OPTION_CACHE")) {
+    const long v = atol(e);
+    cache_rows = v <= 0 ? 0 : v == 1 ? VD_OPTION_CACHE_DEFAULT_ROWS : v;
+  }
+  VD_CHECK_ARG(!cache_rows || std::string(decoder) == "disc",
+               "vd_model_create: VD_OPTION_CACHE caches the candidate encodings of decoder 'disc'; this model's decoder is '%s'", decoder);
+  VD_CHECK_ARG(!cache_rows || p->lstmBf16 != 1,
+               "vd_model_create: VD_OPTION_CACHE needs the state-only option recurrence, which the compact bf16 recurrence (lstmBf16 = 1) "
+               "does not have");
+  VD_CHECK_ARG(cache_rows < (1L << 30), "vd_model_create: VD_OPTION_CACHE = %ld rows is out of range", cache_rows);
   vd_model* m = new vd_model();
   m->p = *p;
   m->flags = flags;
+  m->ocache.capacity = cache_rows;
   if (m->p.numAttentionLayers < 1 || has(en, "lf-att")) m->p.numAttentionLayers = 1;   // (lf-att-ques-im-hist.lua:49 hard-codes one hop)
   if (m->p.numLayers < 1) m->p.numLayers = 2;        // opts.lua:27
   m->enc_name = encoder;
@@ -219,6 +274,7 @@ void vd_model_destroy(vd_model* m) {
     if (kv.second.p) (void)hipFree(kv.second.p);
   for (auto& kv : m->ext_masks)
     if (kv.second.p) (void)hipFree(kv.second.p);
+  if (m->ocache.table) (void)hipFree(m->ocache.table);
   for (auto& sl : m->slot) {
     for (auto& kv : sl.bufs)
       if (kv.second.p) (void)hipFree(kv.second.p);
@@ -260,6 +316,7 @@ int vd_model_tensor_info(const vd_model* m, int64_t i, char* name64, int64_t* of
 
 int vd_model_flat_pointers(vd_model* m, float** W, float** dW, float** adam_m, float** adam_v) {
   VD_CHECK_ARG(m, "vd_model_flat_pointers: null model");
+  m->ocache.flush();   // the host may write the weights through W
   if (W) *W = m->W;
   if (dW) *dW = m->G;
   if (adam_m) *adam_m = m->M;
@@ -313,6 +370,7 @@ int vd_model_init_params(vd_model* m, uint64_t seed) {
     }
   }
   VD_HIP(hipMemcpy(m->W, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+  m->ocache.flush();
   return VD_OK;
 }
 
@@ -322,6 +380,7 @@ int vd_model_set_tensor(vd_model* m, const char* name, const float* host, int64_
   VD_CHECK_ARG(n == t.numel(), "vd_model_set_tensor: '%s' holds %ld values, got %ld", name, t.numel(), (long)n);
   VD_HIP(hipStreamSynchronize(m->s_main));
   VD_HIP(hipMemcpy(m->W + t.off, host, n * sizeof(float), hipMemcpyHostToDevice));
+  m->ocache.flush();
   return VD_OK;
 }
 
@@ -338,6 +397,7 @@ int vd_model_get_tensor(vd_model* m, const char* name, int which, float* host, i
 int vd_model_set_training(vd_model* m, int on) {
   VD_CHECK_ARG(m, "vd_model_set_training: null model");
   m->training = on != 0;
+  if (on) m->ocache.flush();   // training steps move the weights (and a host that wrote them itself announces it this way)
   return VD_OK;
 }
 
@@ -405,9 +465,13 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
     // one forward value and their gradients add).  Synthetic batches have no repeats: the plain path, no extra kernels.
     sl.opt_uid = nullptr;
     sl.opt_total = (int)NO;
+    sl.cached = false;
     const int To = hb->To;
     bool dedup = false;
-    if (NO > 1) {
+    if (m->ocache.capacity > 0 && !m->training) {   // evaluation with the answer-encoding cache: only the rows it does not hold
+      sl.opt_host.assign(hb->options, hb->options + (size_t)NO * To);
+      VD_TRY(option_cache_resolve(m, sl, sl.opt_host.data(), NO, To, s));
+    } else if (NO > 1) {
       std::vector<int32_t> uid((size_t)NO), uniq;
       uniq.reserve((size_t)NO * To);
       const size_t cap = (size_t)1 << (64 - __builtin_clzll((unsigned long long)(2 * NO)));   // power of two >= 2 NO
@@ -443,9 +507,9 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
         VD_HIP(hipMemcpyAsync(sl.opt_uid, up, (size_t)NO * sizeof(int32_t), hipMemcpyHostToDevice, s));
       }
     }
-    if (!dedup) VD_TRY(upload_tokens(sl, sl.opt, "opt", hb->options, (int)NO, hb->To, false, s));   // [N x O x To] -> [To x N*O]
+    if (!dedup && !sl.cached) VD_TRY(upload_tokens(sl, sl.opt, "opt", hb->options, (int)NO, hb->To, false, s));   // [N x O x To] -> [To x N*O]
     sl.opt_sort_off = sl.opt_sort_perm = nullptr;
-    {   // counting sort of the option tokens on the copy stream (the table gradient's row order depends on the batch alone)
+    if (!sl.cached) {   // counting sort of the option tokens on the copy stream (the table gradient's row order depends on the batch alone)
       const long V1 = (long)m->p.vocabSize + 1, n = (long)sl.opt.T * sl.opt.N;
       int32_t* work;
       VD_TRY(dev_get(sl.bufs, "opt.sort_off", (size_t)(V1 + 1) * sizeof(int32_t), (void**)&sl.opt_sort_off));
@@ -502,6 +566,7 @@ int vd_model_forward_backward(vd_model* m, int only_forward) {
   VdRange r(only_forward ? "vd_model_forward" : "vd_model_forward_backward");
   BatchSlot* b = nullptr;
   VD_TRY(begin_step(m, !only_forward, &b));
+  if (!only_forward) m->ocache.flush();   // gradients are about to move the weights
   const int rc = m->dec->forward_backward(m, *b, only_forward != 0);
   VD_HIP(hipEventRecord(b->done, m->s_main));
   return rc;
@@ -584,6 +649,7 @@ int vd_model_update(vd_model* m, float gscale) {
   VD_CHECK_ARG(m, "vd_model_update: null model");
   VdRange r("vd_model_update: clamp + adam");
   m->adam_t += 1;
+  m->ocache.flush();
   const double t = m->adam_t;
   const float step = (float)(m->lr * sqrt(1.0 - pow(0.999, t)) / (1.0 - pow(0.9, t)));
   VD_TRY(vd_clamp_adam(m->W, m->G, m->M, m->V, m->numel, gscale, 5.0f, 0.9f, 0.999f, 1e-8f, step, m->s_main));

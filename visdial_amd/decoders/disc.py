@@ -8,6 +8,7 @@ clones ARE one batch of N*100 option sequences: the option LSTM runs as a single
 gradients are one wave-reduction kernel.
 """
 
+import numpy as np
 import torch
 
 from .. import ops
@@ -30,6 +31,56 @@ class Decoder(object):
         self.streams = StreamPool(ws.device, enabled=False)     # Model attaches its own pool
         # arithmetic of the option recurrence (opts.py): default = the exact 3 x bf16 split (fp32-grade), 'fp32' = v_mfma_f32, 'bf16' = configs[4]
         self.flags = ops.PRECISION_FLAGS[params.get('lstmPrecision', 'split9')]
+        # answer-encoding cache (params optionCache; visdial_amd/option_cache.py): evaluation only, off by default
+        self.oindex, self.otable = None, None
+        self.rows_executed = None        # (rows the option recurrence ran, N * O) of the last forward
+        cap = int(params.get('optionCache', 0) or 0)
+        if cap:
+            from ..option_cache import DEFAULT_ROWS, OptionIndex
+            if self.flags & ops.FLAG_BF16:
+                raise ValueError("optionCache: the bf16 option recurrence (lstmPrecision = 'bf16') has no state-only form")
+            self.oindex = OptionIndex(DEFAULT_ROWS if cap == 1 else cap)
+
+    def flush_cache(self):
+        """the weights changed (or may have): forget every cached encoding"""
+        if self.oindex is not None:
+            self.oindex.flush()
+
+    def forward_cached(self, inputs):
+        """inputs = {candidate rows [N*O x To] int32 ON THE HOST, encOut [N x H]} -> scores [N x O] without a backward: the
+        state-only recurrence (ops.FLAG_STATE_ONLY) runs over the rows the cache does not hold, their final h goes to table rows
+        [count, count + misses), and the scores read the table through one gather.  A batch of known answers launches no
+        recurrence kernel."""
+        rows, enc_out = inputs
+        ws, H, V, dev = self.ws, self.H, self.V, self.ws.device
+        NO, To = rows.shape
+        N = enc_out.shape[0]
+        O = NO // N
+        slots, miss = self.oindex.resolve(rows)
+        base, U = self.oindex.count, miss.shape[0]
+        if self.otable is None or self.otable.shape[0] < base + U:      # grow: doubling up to the capacity (+ this batch's tail)
+            old = self.otable
+            want = min(max(2 * (old.shape[0] if old is not None else 0), 16384), self.oindex.capacity)
+            self.otable = torch.empty(max(want, base + U), H, dtype=torch.float32, device=dev)
+            if old is not None and base:
+                self.otable[:base].copy_(old[:base])
+        if U:
+            self.table = ws.get('opt.table', (V + 1, 4 * H))
+            ops.gemm_nn(self.emb, self.Wx, self.table, bias=self.b, M=V + 1, N=4 * H, K=self.E)
+            otok = torch.from_numpy(np.ascontiguousarray(miss.T)).to(dev)                 # [To x U] time-major
+            h2, c2 = ws.get('opt.h2', (2, U, H)), ws.get('opt.c2', (2, U, H))
+            t0 = ops.prof_begin('opt_lstm_fwd')
+            ops.lstm_forward(self.table, self.Wh, None, h2, c2, To, U, H, 0, 4 * H, tok_gather=otok,
+                             flags=self.flags | ops.FLAG_STATE_ONLY)
+            ops.prof_end('opt_lstm_fwd', t0, 1)
+            self.otable[base:base + U].copy_(h2[(To - 1) & 1])
+        self.oindex.commit()                                                              # the fill is enqueued
+        idx = torch.from_numpy(self.oindex.gather_rows(slots, base)).to(dev)
+        self.optH = ops.embed_gather(self.otable, idx, ws.get('opt.h_full', (NO, H)))
+        self.uid, self.To, self.NO, self.N, self.O = None, To, U, N, O
+        self.rows_executed = (U, NO)
+        self.output = ws.get('opt.scores', (N, O))
+        return DiscDecoderOutput(self.optH, enc_out, self.output, N, O, H)
 
     def forward(self, inputs):
         """inputs = {options [To x N*O] int32 time-major, encOut [N x H]} -> scores [N x O]"""
@@ -40,6 +91,7 @@ class Decoder(object):
         self.uid = getattr(otok, 'vd_uid', None)
         O = (otok.vd_total if self.uid is not None else NO) // N
         self.To, self.NO, self.N, self.O = To, NO, N, O
+        self.rows_executed = (NO, N * O)
         self.table = ws.get('opt.table', (V + 1, 4 * H))
         ops.gemm_nn(self.emb, self.Wx, self.table, bias=self.b, M=V + 1, N=4 * H, K=self.E)
         self.gates = ws.get('opt.gates', (To, NO, 4 * H))

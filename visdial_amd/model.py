@@ -27,6 +27,7 @@ class Wrapper(object):
 
     def training(self):
         self._m.drop.training = True
+        self._m._flush_option_cache()      # training steps move the weights; a host that wrote wrapperW itself announces it this way
 
     def evaluate(self):
         self._m.drop.training = False
@@ -70,6 +71,9 @@ class Model(SplitEval):
         self.encoder = self.encFile.model(params, self.fp, self.ws, self.drop, self.streams)
         self.decoder = self.decFile.model(params, self.encoder, self.fp, self.ws, self.drop)
         self.decoder.streams = self.streams
+        if int(params.get('optionCache', 0) or 0) and params['decoder'] != 'disc':
+            raise ValueError("optionCache: the answer-encoding cache holds the candidate encodings of the discriminative decoder, not '%s'"
+                             % params['decoder'])
         # decoder hooks (model.lua:28-29)
         self.forwardConnect = self.decFile.forwardConnect
         self.backwardConnect = self.decFile.backwardConnect
@@ -145,22 +149,12 @@ class Model(SplitEval):
         dec_in = {}
         if 'answer_ind' in batch:
             dec_in['gt'] = self._dev(np.asarray(batch['answer_ind']).reshape(-1) - 1, np.int32)       # 0-based
-        if p['decoder'] == 'disc':
+        if p['decoder'] == 'disc' and self._option_cache_active():
+            # evaluation with the answer-encoding cache: the rows stay on the host, the decoder uploads the ones it has not seen
             o = batch['options']
-            rows = np.ascontiguousarray(o.reshape(-1, o.shape[2]), dtype=np.int32)   # [N*O x To]
-            uid = None
-            if rows.shape[0] > 1:
-                # encode every DISTINCT candidate once (decoders/disc.lua:4-15: the encoding depends on the tokens only);
-                # same rule as the native runtime (csrc/runtime.hip: vd_model_upload_batch)
-                # (rows compared as opaque byte strings: np.unique(axis=0) sorts lexicographically over To columns and took 31 ms on
-                #  the 32 000 x 20 headline batch, longer than the device step; the 1-D void view takes a quarter of that)
-                key = rows.view(np.dtype((np.void, rows.dtype.itemsize * rows.shape[1]))).reshape(-1)
-                _, first, inv = np.unique(key, return_index=True, return_inverse=True)
-                if first.shape[0] <= 0.95 * rows.shape[0]:
-                    uid, total, rows = self._dev(inv.reshape(-1), np.int32), rows.shape[0], rows[first]
-            dec_in['options'] = self._dev(rows.T, np.int32)                          # [To x rows]
-            if uid is not None:
-                dec_in['options'].vd_uid, dec_in['options'].vd_total = uid, total
+            dec_in['option_rows'] = np.ascontiguousarray(o.reshape(-1, o.shape[2]), dtype=np.int32)
+        elif p['decoder'] == 'disc':
+            dec_in['options'] = self._options_tensor(batch['options'])
         else:
             for k in ('answer_in', 'answer_out'):
                 if k in batch:
@@ -171,6 +165,36 @@ class Model(SplitEval):
                     a = batch[k]
                     dec_in[k] = self._dev(a.reshape(-1, a.shape[3]).T, np.int32)       # [T x N*O], row = n*O + o
         return inputs, dec_in
+
+    def _option_cache_active(self):
+        return getattr(self.decoder, 'oindex', None) is not None and not self.drop.training
+
+    def _flush_option_cache(self):
+        dec = getattr(self, 'decoder', None)
+        if dec is not None and getattr(dec, 'oindex', None) is not None:
+            dec.flush_cache()
+
+    def option_rows(self):
+        """(rows the option LSTM executed, N * O candidates) of the last disc forward; with optionCache the rows the cache did not hold"""
+        return tuple(self.decoder.rows_executed)
+
+    def _options_tensor(self, o):
+        """[N x O x To] (or [N*O x To]) candidates -> time-major device tokens [To x rows] of the DISTINCT rows (+ vd_uid / vd_total)"""
+        rows = np.ascontiguousarray(o.reshape(-1, o.shape[-1]), dtype=np.int32)  # [N*O x To]
+        uid = None
+        if rows.shape[0] > 1:
+            # encode every DISTINCT candidate once (decoders/disc.lua:4-15: the encoding depends on the tokens only);
+            # same rule as the native runtime (csrc/runtime.hip: vd_model_upload_batch)
+            # (rows compared as opaque byte strings: np.unique(axis=0) sorts lexicographically over To columns and took 31 ms on
+            #  the 32 000 x 20 headline batch, longer than the device step; the 1-D void view takes a quarter of that)
+            key = rows.view(np.dtype((np.void, rows.dtype.itemsize * rows.shape[1]))).reshape(-1)
+            _, first, inv = np.unique(key, return_index=True, return_inverse=True)
+            if first.shape[0] <= 0.95 * rows.shape[0]:
+                uid, total, rows = self._dev(inv.reshape(-1), np.int32), rows.shape[0], rows[first]
+        t = self._dev(rows.T, np.int32)                                          # [To x rows]
+        if uid is not None:
+            t.vd_uid, t.vd_total = uid, total
+        return t
 
     # ------------------------------------------------------------------ training
     def _fetch(self, dataloader):
@@ -224,6 +248,7 @@ class Model(SplitEval):
                 self._enc_bucket_work = None
             else:
                 gscale, _ = reduce_gradients(self.wrapperdW, self.dist_group)   # RCCL sum over xGMI
+        self._flush_option_cache()
         o = self.optims
         o['t'] += 1
         t = o['t']
@@ -240,6 +265,11 @@ class Model(SplitEval):
         """model.lua:249-342.  Returns curLoss (python float); with deferLoss a callable that waits for the
         device and returns it (everything is enqueued when forwardBackward returns)."""
         inputs, dec_in = prepared if prepared is not None else self.prepare_inputs(batch)
+        if not onlyForward and not encOutOnly:
+            self._flush_option_cache()         # gradients are about to move the weights
+        if 'option_rows' in dec_in and 'options' not in dec_in and (not onlyForward or not self._option_cache_active()):
+            # prepared for cached evaluation, stepped otherwise: the uncached path needs every distinct row on the device
+            dec_in['options'] = self._options_tensor(dec_in['option_rows'])
         # LookupTableMaskZero zeroes the pad row on every forward
         ops.zero(self.fp.w['embed'][0])
         if self.params['decoder'] == 'disc' and not encOutOnly:
@@ -265,10 +295,11 @@ class Model(SplitEval):
         # ones -- the big chain goes to the main stream first so the GPU is busy while the host is
         # still enqueueing the encoder on the side streams.
         enc_out_buf = self.encoder.output_buffer(inputs)
-        d_in = (dec_in['options'], enc_out_buf)
+        cached = 'options' not in dec_in
+        d_in = (dec_in['option_rows'] if cached else dec_in['options'], enc_out_buf)
         start = torch.cuda.Event()
         start.record()
-        decOut = self.decoder.forward(d_in)                                       # model.lua:329
+        decOut = self.decoder.forward_cached(d_in) if cached else self.decoder.forward(d_in)   # model.lua:329
         with st.fork('enc', after=start):
             encOut = self.encoder.forward(inputs)                                 # model.lua:297
         assert encOut.data_ptr() == enc_out_buf.data_ptr()
@@ -308,7 +339,10 @@ class Model(SplitEval):
                                                  inputs[0].shape[0])
             self.scores = scores
         else:
-            scores = self.decoder.forward((dec_in['options'], encOut)).materialize()
+            if 'option_rows' in dec_in:            # params optionCache (evaluation mode): only the answers not seen before are encoded
+                scores = self.decoder.forward_cached((dec_in['option_rows'], encOut)).materialize()
+            else:
+                scores = self.decoder.forward((dec_in['options'], encOut)).materialize()
             self.scores = scores
         gt = dec_in.get('gt') if self.params.get('useGt') else None
         return utils.computeRanks(scores, gt, self.ws)
@@ -427,6 +461,7 @@ class Model(SplitEval):
 
     def set_parameters_dict(self, d):
         self.fp.load_host(d)
+        self._flush_option_cache()
 
     def load_flat_parameters(self, modelW):
         """`model.wrapperW:copy(savedModel.modelW)` (train.lua:79, evaluate.lua:91) for a flat vector in the

@@ -67,7 +67,19 @@ class NativeModel(SplitEval):
             dropout=float(p.get('dropout', 0.5)))
         self.params = p
         h = C.c_void_p()
-        call("vd_model_create", C.byref(mp), p['encoder'].encode(), p['decoder'].encode(), C.byref(h))
+        # params optionCache (0 = off, 1 = on, larger = capacity in rows): the answer-encoding cache of disc evaluation.  The library reads
+        # its switch from the environment when the model is created (the Lua host sets the same variable); the previous value comes
+        # back right after, so two models of one process can differ.
+        import os
+        prev = os.environ.get('VD_OPTION_CACHE')
+        os.environ['VD_OPTION_CACHE'] = str(int(p.get('optionCache', 0) or 0))
+        try:
+            call("vd_model_create", C.byref(mp), p['encoder'].encode(), p['decoder'].encode(), C.byref(h))
+        finally:
+            if prev is None:
+                del os.environ['VD_OPTION_CACHE']
+            else:
+                os.environ['VD_OPTION_CACHE'] = prev
         self.h = h
         lib = _lib.load()
         self.tensors = []
@@ -139,7 +151,8 @@ class NativeModel(SplitEval):
 
     def load_flat_parameters(self, modelW):
         """`model.wrapperW:copy(savedModel.modelW)` for a flat vector in the REFERENCE's getParameters() layout
-        (see visdial_amd.model.Model.load_flat_parameters)"""
+        (see visdial_amd.model.Model.load_flat_parameters).  Goes through vd_model_set_tensor, which also empties the answer-encoding
+        cache; a host that writes through `wrapperW` instead must call training(True) afterwards."""
         from . import t7
         self.set_parameters_dict(t7.flat_to_named(np.asarray(modelW), self._entries(), self.params['encoder']))
 
@@ -337,7 +350,8 @@ class NativeModel(SplitEval):
         return tokens, loglik
 
     def option_rows(self):
-        """(rows the option LSTM executes, N * O candidates) of the current batch: the upload de-duplicates candidates"""
+        """(rows the option LSTM executes, N * O candidates) of the current batch: the upload de-duplicates candidates; with
+        params optionCache in evaluation mode the rows the cache did not hold (possibly 0)"""
         a, b = C.c_int64(), C.c_int64()
         call("vd_model_option_rows", self.h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)

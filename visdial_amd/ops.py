@@ -83,6 +83,9 @@ FLAG_SPLIT9, FLAG_SPLIT6, FLAG_SPLIT3 = 2, 4, 8   # exact three-way bf16 split o
 # VD_FLAG_LIVE_PREFIX (lstm_forward with tok_mask): per step the rows with a token are a prefix of the rows; row groups without one are not
 # computed and stay unwritten.  LIVE_PREFIX_ROWS = VD_LIVE_PREFIX_ROWS, a multiple of every forward step kernel's row tile
 FLAG_LIVE_PREFIX, LIVE_PREFIX_ROWS = 16, 128
+# VD_FLAG_STATE_ONLY (lstm_forward with gates=None): a forward pass no backward follows -- h and c are [2 x N x H] ping-pong buffers, step t
+# writes slot t & 1, the final state lies in slot (T - 1) & 1 and no gate value reaches memory
+FLAG_STATE_ONLY = 32
 
 
 def lstm_fwd_row_tile(N):

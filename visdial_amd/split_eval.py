@@ -16,6 +16,17 @@ from . import utils
 
 
 class SplitEval(object):
+    optionCacheRows = (0, 0)     # params optionCache: (rows the option LSTM ran, candidate rows) summed over the last retrieve / predict
+
+    def _ranked(self, batch, tally):
+        """retrieveBatch + the tally of the answer-encoding cache (params optionCache; decoder disc)"""
+        ranks = np.asarray(self.retrieveBatch(batch))
+        if int(self.params.get('optionCache', 0) or 0):
+            ex, tot = self.option_rows()
+            tally[0] += ex
+            tally[1] += tot
+        return ranks
+
     def evaluate(self, dataloader, dtype):
         """model.lua:109-139: validation loss / perplexity over a split: the sum over batches of `forwardBackward(batch, true)` (gen:
         summed token NLL; disc: the batch's MEAN cross-entropy) divided by the number of non-pad target tokens -- for both decoders,
@@ -65,11 +76,12 @@ class SplitEval(object):
         R = int(self.params['maxQuesCount'])
         O = int(self.params.get('numOptions', 100))
         ranks = np.full((n, R), O + 1.0)                               # model.lua:153-154
-        start = 1
+        start, tally = 1, [0, 0]
         while start <= n:
             batch, nxt = dataloader.getTestBatch(start, self.params, dtype)
-            ranks[start - 1:nxt - 1] = np.asarray(self.retrieveBatch(batch)).reshape(-1, R)
+            ranks[start - 1:nxt - 1] = self._ranked(batch, tally).reshape(-1, R)
             start = nxt
+        self.optionCacheRows = tuple(tally)
         print('\n%s - Retrieval:' % dtype)
         metrics = utils.processRanks(ranks)
         self._set_training(True)
@@ -83,11 +95,12 @@ class SplitEval(object):
         R = int(self.params['maxQuesCount'])
         O = int(self.params.get('numOptions', 100))
         ranks = np.full((n, R, O), O + 1.0)
-        start = 1
+        start, tally = 1, [0, 0]
         while start <= n:
             batch, nxt = dataloader.getTestBatch(start, self.params, dtype)
-            ranks[start - 1:nxt - 1] = np.asarray(self.retrieveBatch(batch)).reshape(-1, R, O)
+            ranks[start - 1:nxt - 1] = self._ranked(batch, tally).reshape(-1, R, O)
             start = nxt
+        self.optionCacheRows = tuple(tally)
         self._set_training(True)
         return self._rank_records(dataloader, dtype, ranks, dtype == 'test')
 
