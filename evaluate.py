@@ -31,9 +31,10 @@ def main():
     ap.add_argument('--numThreads', type=int, default=100, help='synthetic fallback only')
     ap.add_argument('-host', '--host', default='python', choices=['python', 'native'],
                     help="'native' drives the model-level C ABI (what lua/model.lua calls)")
-    ap.add_argument('-fusedLhood', '--fusedLhood', type=int, default=0, choices=[0, 1],
+    ap.add_argument('-fusedLhood', '--fusedLhood', type=int, default=0, choices=[0, 1, 2],
                     help='gen decoder: score the candidates from their live (non-pad) rows only, through the fused vocabulary '
-                         'projection + online log-sum-exp head (no logits buffer); 0 = the dense head')
+                         'projection + online log-sum-exp head (no logits buffer); 0 = the dense head; 2 = the same scores over a '
+                         'prefix tree of the candidates\' tokens (a shared beginning is computed once; needs -host native)')
     ap.add_argument('-optionCache', '--optionCache', type=int, default=0,
                     help='disc decoder: keep the encoding of every distinct candidate answer on the device while the split is ranked and run '
                          'the option LSTM over the answers not seen before only (0 = off, 1 = on, larger = capacity in rows)')
@@ -42,7 +43,9 @@ def main():
     p = opts.derive(saved['modelParams'])                    # sets useHistory / useIm / concatHistory (evaluate.lua:69-75)
     p['gpuid'], p['batchSize'], p['useGt'] = a.gpuid, a.batchSize, bool(a.useGt)
     if a.fusedLhood and p['decoder'] != 'gen':
-        raise SystemExit('-fusedLhood 1: the live-row log-likelihood head is only for a generative model')
+        raise SystemExit('-fusedLhood %d: the live-row log-likelihood head is only for a generative model' % a.fusedLhood)
+    if a.fusedLhood == 2 and a.host != 'native':
+        raise SystemExit('-fusedLhood 2: the prefix-tree head runs in the model-level runtime only: add -host native')
     p['fusedLhood'] = a.fusedLhood
     if a.optionCache and p['decoder'] != 'disc':
         raise SystemExit('-optionCache: the answer-encoding cache is only for a discriminative model')
@@ -60,7 +63,10 @@ def main():
         from visdial_amd.native import NativeModel
         model = NativeModel(p)
     else:
-        model = Model(p)
+        try:
+            model = Model(p)
+        except ValueError as e:
+            raise SystemExit(str(e))
     restore_weights(model, saved, a.paramOrder or None)          # evaluate.lua:91
     print('Evaluating..')
     if a.perplexity:
@@ -69,6 +75,11 @@ def main():
         metrics, records = model.retrieve(dl, a.split)
     else:
         records = model.predict(dl, a.split)
+    if a.fusedLhood == 2:
+        st = model.lhoodTreeStats
+        print('fusedLhood 2: %d nodes for %d live rows (%.3f); the candidate recurrence ran %d of %d (step, candidate) rows (%.1f %%)'
+              % (st['nodes'], st['live'], st['nodes'] / max(st['live'], 1), st['executed'], st['total'],
+                 100.0 * st['executed'] / max(st['total'], 1)))
     if a.optionCache:
         ex, tot = model.optionCacheRows
         print('optionCache: the option LSTM ran %d of %d candidate rows (%.1f %%)' % (ex, tot, 100.0 * ex / max(tot, 1)))

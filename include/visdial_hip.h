@@ -82,6 +82,20 @@ int vd_copy_2d(float* dst, int64_t dst_ld, const float* src, int64_t src_ld, int
  * and VD_FLAG_SPLIT*, dense and table mode, tok_mask; refused (argument error) with VD_FLAG_BF16, with VD_FLAG_LIVE_PREFIX and
  * with a non-NULL `gates`.  Without the flag a NULL `gates` is refused. */
 #define VD_FLAG_STATE_ONLY 32
+/* VD_FLAG_TREE (vd_lstm_forward): a level-by-level recurrence over a forest -- every row of step t continues the state of a PARENT ROW
+ * of step t - 1, not of the same row (the candidates of generative retrieval as a prefix tree of their tokens: a shared beginning is
+ * computed once).  tok_mask is required and is [2 x T x N]: plane 0 is the mask (in table mode also passed as tok_gather: the token),
+ * non-zero = a node, and the nodes of step t are a PREFIX of the N rows (level widths may grow or shrink from step to step); plane 1
+ * is the parent row of node (t, n) -- for t >= 1 a row of step t - 1, for t = 0 a row of h0 / c0, which may then have any number of
+ * rows R (R * H * 4 bytes below 4 GB; with NULL h0 / c0 the parent state is zero).  Parent entries of rows without a node are not
+ * read as rows.  Forward only: `gates` must be NULL and no gate activation reaches memory (as with VD_FLAG_STATE_ONLY); h and c are
+ * [T x N x H], every level is kept.  Row tiles without a node return before loading anything and their rows stay unwritten, with the
+ * guarantee of VD_FLAG_LIVE_PREFIX: rows at or beyond ceil(nodes of the step / VD_LIVE_PREFIX_ROWS) * VD_LIVE_PREFIX_ROWS are never
+ * written; the other rows without a node in a tile with one are written as zeros.  Dense and table mode; a second layer reads layer
+ * 1's h of the same node row as dense xproj input.  Same step kernels, tiles and K order as VD_FLAG_LIVE_PREFIX: with identity parents
+ * h and c equal that flag's bit for bit.  Exact fp32 only: refused (argument error) with VD_FLAG_BF16, any VD_FLAG_SPLIT*,
+ * VD_FLAG_STATE_ONLY, a non-NULL `gates` or a NULL tok_mask. */
+#define VD_FLAG_TREE 64
 
 /* ---- dense contractions (nn.Linear / hoisted SeqLSTM input projection / weight grads) -- */
 /* C[MxN] (+)= act(A[MxK] * W[NxK]^T + bias)   -- nn.Linear:updateOutput (+nn.Tanh),
@@ -118,7 +132,8 @@ int vd_colsum_acc(const float* X, int64_t ld, int M, int N, float* out, void* st
  * by a gate-interleaved transpose of Wh [4H x H] made once per call; that work buffer is library-owned per (device, stream),
  * so calls on different streams may overlap.
  * flags: VD_FLAG_BF16 / VD_FLAG_SPLIT* choose the arithmetic of the recurrent product; VD_FLAG_LIVE_PREFIX (above) skips the
- * row groups without a live row; VD_FLAG_STATE_ONLY (above) keeps only the running state (gates NULL, h / c [2 x N x H]). */
+ * row groups without a live row; VD_FLAG_STATE_ONLY (above) keeps only the running state (gates NULL, h / c [2 x N x H]);
+ * VD_FLAG_TREE (above) runs a forest level by level (gates NULL, tok_mask [2 x T x N] = mask | parent row). */
 int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const int32_t* tok_gather,
                     const int32_t* tok_mask, const float* Wh, const float* h0, const float* c0, float* gates,
                     float* h, float* c, int T, int N, int H, int flags, void* stream);
@@ -413,7 +428,18 @@ int vd_model_loss(vd_model* m, float* loss);              /* curLoss of the last
 int vd_model_retrieve(vd_model* m);
 /* the same contract for the generative decoder through the live-row head (vd_lhood_* above): scores within the fp32 rounding of
  * vd_model_retrieve's, no logits buffer, one host synchronisation per chunk of options (the live-row count).  An argument error
- * that names the decoder for `disc`. */
+ * that names the decoder for `disc`.
+ * Prefix tree (opt-in): with the environment variable VD_LHOOD_TREE set to 1 when vd_model_create runs (0 / unset = off), this call
+ * scores the candidates over a prefix tree of their tokens: the decoder state after a candidate's first t tokens depends on the
+ * round's encoder state and on those tokens only, so every distinct (round, token prefix) is ONE node -- computed once by the
+ * level-by-level recurrence (VD_FLAG_TREE; <START>, shared by the 100 candidates of a round, is one row per round) and projected on
+ * the vocabulary once (its log-sum-exp); a candidate's score is the sum over its steps of target logit - log-sum-exp of the node,
+ * in step order, so two identical candidates tie exactly and an empty one scores 0.0.  vd_model_upload_batch builds the tree on the
+ * host from option_in / option_out, one per chunk of options sized by the nodes it holds; the call adds no host synchronisation.
+ * A batch with a token behind a pad in any candidate takes the path without the variable, unchanged.  vd_model_option_rows then
+ * reports executed = sum over the levels of min(N, ceil(n_t / G) * G) (n_t = nodes of level t, N = the widest level, G = the step
+ * kernel's row tile for N), total = To * rounds * options.  vd_model_retrieve is unaffected.  vd_model_create refuses the variable
+ * for decoder disc and for lstmBf16 = 1. */
 int vd_model_retrieve_lhood(vd_model* m);
 /* wrapperdW*gscale -> clamp(-5,5) -> adam -> lr decay (model.lua:96-105; optim_updates.lua:62-91) */
 int vd_model_update(vd_model* m, float gscale);

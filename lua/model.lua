@@ -181,7 +181,8 @@ function Model:retrieveBatch(batch)
     self:commitW()
     self:upload(batch); self.havePrefetched = false
     -- params.fusedLhood = 1 (gen): the candidate log-likelihoods from the live (non-pad) rows only, through the fused vocabulary
-    -- projection + online log-sum-exp head (vd_model_retrieve_lhood: no logits buffer); same scores contract
+    -- projection + online log-sum-exp head (vd_model_retrieve_lhood: no logits buffer); same scores contract.  fusedLhood = 2: the same
+    -- call; a model created with VD_LHOOD_TREE=1 in the environment scores the candidates over a prefix tree of their tokens
     if (self.params.fusedLhood or 0) ~= 0 then
         if self.params.decoder ~= 'gen' then error('fusedLhood: the live-row log-likelihood head is only for generative model') end
         vd.call('vd_model_retrieve_lhood', self.h)

@@ -9,6 +9,13 @@ A/B of two libraries (VD_LIB_PATH selects one): --tag NAME marks the process's l
 last fused call (the rows the candidate recurrence ran), and --save-scores PATH.npz keeps the fused scores per profile so that two
 libraries' scores can be compared afterwards.
 
+Third leg (--tree): the same batches through a second model created with params fusedLhood = 2 (VD_LHOOD_TREE: the candidates over a
+prefix tree of their tokens), alternated with the other heads; per profile nodes / live rows, the rows the tree recurrence ran, and
+the host time of the upload with and without the tree build.  A library that does not know the switch (the parent commit's through
+VD_LIB_PATH) is run without --tree.  --profile pooled: every candidate drawn from a pool of --gen-pool answers (lengths 1 +
+Poisson(2) capped at 20, every third answer continuing the one before it) with probability ~ 1 / (rank + 1), so that beginnings repeat
+inside a round; nobody has measured how often they do on the real VisDial splits.
+
 --mode disc: discriminative evaluation with and without the answer-encoding cache (params optionCache) at full
 size: mn-att-ques-im-hist + disc, 20 dialogs x 10 rounds x 100 options, To = 20, split9.  The synthetic loader has no repeats, so the
 candidates of --batches batches are drawn from a pool of --pool distinct answers.  Per case batches/s over one pass of those batches
@@ -32,8 +39,10 @@ from visdial_amd.opts import default_params, derive  # noqa: E402
 
 ap = argparse.ArgumentParser(description='dense vs live-row log-likelihood head of generative retrieval at full size')
 ap.add_argument('--repeats', type=int, default=7)
-ap.add_argument('--only', choices=('fused',), help='the live-row head alone, for a kernel trace')
-ap.add_argument('--profile', choices=('uniform', 'short'), help='one length profile only')
+ap.add_argument('--only', choices=('fused', 'tree'), help='one head alone, for a kernel trace')
+ap.add_argument('--profile', choices=('uniform', 'short', 'pooled'), help='one length profile only')
+ap.add_argument('--tree', action='store_true', help='--mode gen: also the prefix-tree head (params fusedLhood = 2)')
+ap.add_argument('--gen-pool', type=int, default=2000, help='--profile pooled: answers the candidates are drawn from')
 ap.add_argument('--tag', default='', help='printed in front of the per-head lines (A/B of two libraries)')
 ap.add_argument('--save-scores', default='', help='write the fused scores of every profile to this .npz')
 ap.add_argument('--mode', choices=('gen', 'disc', 'step'), default='gen')
@@ -180,8 +189,32 @@ def with_lengths(batch, lens, rng):
     return dict(batch, option_in=oin.reshape(B, R, O, T), option_out=oout.reshape(B, R, O, T))
 
 
+def pooled(batch, rng):
+    """candidates drawn from a pool with a heavy tail (see the module docstring)"""
+    answers = [[int(w) for w in rng.randint(1, V - 1, size=min(L, 1 + rng.poisson(2.0)))] for _ in range(opt.gen_pool)]
+    for k in range(1, opt.gen_pool, 3):
+        answers[k] = (answers[k - 1] + answers[k])[:L]
+    w = 1.0 / (1.0 + np.arange(opt.gen_pool))
+    pick = rng.choice(opt.gen_pool, size=B * R * O, p=w / w.sum())
+    oin = np.zeros((B * R * O, T), np.int32)
+    oout = np.zeros((B * R * O, T), np.int32)
+    oin[:, 0] = V - 1
+    for r, k in enumerate(pick):
+        a = answers[k]
+        oin[r, 1:1 + len(a)] = a
+        oout[r, :len(a)] = a
+        oout[r, len(a)] = V
+    lens = np.array([len(answers[k]) for k in pick])
+    return dict(batch, option_in=oin.reshape(B, R, O, T), option_out=oout.reshape(B, R, O, T)), lens
+
+
+use_tree = opt.tree or opt.only == 'tree'
 nat = NativeModel(p, init_seed=1)
 nat.training(False)
+nat_tree = None
+if use_tree:
+    nat_tree = NativeModel(dict(p, fusedLhood=2), init_seed=1)       # the same weights (same seed), created with VD_LHOOD_TREE
+    nat_tree.training(False)
 base, _ = SyntheticDataloader(p, seed=7, num_threads=B).getTestBatch(1, p, 'val')
 N = B * R
 print("lf-ques-im-hist + gen, H %d, V %d, %d layers, %d dialogs x %d rounds x %d options, T %d, native host, random weights"
@@ -191,41 +224,71 @@ print("('short' stands in for the real answer-length distribution -- the dataset
 
 
 def run(fused, batch):
-    nat.params['fusedLhood'] = int(fused)
+    model = nat_tree if fused == 2 else nat
+    model.params['fusedLhood'] = int(fused)
     t0 = time.perf_counter()
-    gt = np.asarray(nat.retrieveBatch(batch, useGt=True)).reshape(-1)       # upload + retrieve + ranks: one evaluate.py batch
+    gt = np.asarray(model.retrieveBatch(batch, useGt=True)).reshape(-1)     # upload + retrieve + ranks: one evaluate.py batch
     return time.perf_counter() - t0, gt
 
 
+def upload_ms(model, batch, n=5):
+    ts = []
+    for _ in range(n):
+        model.synchronize()
+        t0 = time.perf_counter()
+        model.upload(batch)
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
 saved = {}
-for profile in ([opt.profile] if opt.profile else ['uniform', 'short']):
+NAMES = {0: 'dense', 1: 'fused', 2: 'tree'}
+for profile in ([opt.profile] if opt.profile else ['uniform', 'short', 'pooled']):
     rng = np.random.RandomState(77)
-    lens = lengths(profile, N * O, rng)
-    batch = with_lengths(base, lens, rng)
+    if profile == 'pooled':
+        batch, lens = pooled(base, rng)
+    else:
+        lens = lengths(profile, N * O, rng)
+        batch = with_lengths(base, lens, rng)
     live = int(((batch['option_in'] != 0) & (batch['option_out'] > 0)).sum())
     total = T * N * O
     print("\n%s lengths (mean %.2f): live rows %d / %d = %.3f" % (profile, lens.mean(), live, total, live / total))
     print("  vocabulary GEMM executed: dense %.3f TFLOP, live-row %.3f TFLOP" % (2.0 * total * V * H / 1e12, 2.0 * live * V * H / 1e12))
-    heads = (1,) if opt.only else (0, 1)
+    heads = ({'fused': (1,), 'tree': (2,)}[opt.only] if opt.only else (0, 1)) + ((2,) if opt.tree and opt.only != 'tree' else ())
     for f in heads:                                  # warm-up: workspaces, code objects
         run(f, batch)
         run(f, batch)
     if 1 in heads:
+        run(1, batch)
         ex, tot = nat.option_rows()
         print("  %soption_rows after the fused head: executed %d of %d = %.3f" % (opt.tag and opt.tag + ' ', ex, tot, ex / max(tot, 1)))
+    if 2 in heads:
+        from visdial_amd import prefix_tree
+        st = prefix_tree.stats(batch['option_in'])
+        ex, tot = nat_tree.option_rows()
+        print("  %stree: %d nodes for %d rows with a token = %.3f; option_rows executed %d of %d = %.3f; widest level %d"
+              % (opt.tag and opt.tag + ' ', st['nodes'], st['live'], st['nodes'] / max(st['live'], 1), ex, tot, ex / max(tot, 1),
+                 max(st['widths'])))
+        print("  %shost time of one upload: %.2f ms with the tree build, %.2f ms without" % (opt.tag and opt.tag + ' ',
+                                                                                           upload_ms(nat_tree, batch), upload_ms(nat, batch)))
     times = {f: [] for f in heads}
     res = {}
     for _ in range(opt.repeats):                     # alternated
         for f in heads:
             dt, gt = run(f, batch)
             times[f].append(dt)
-            res[f] = (gt, nat.scores(N, O).copy())
+            res[f] = (gt, (nat_tree if f == 2 else nat).scores(N, O).copy())
     for f in heads:
         t = np.asarray(times[f])
         print("  %s%-8s %7.2f ms per batch (median of %d; min %.2f, max %.2f) = %6.2f batches/s" % (
-            opt.tag and opt.tag + ' ', 'fused' if f else 'dense', np.median(t) * 1e3, len(t), t.min() * 1e3, t.max() * 1e3, 1.0 / np.median(t)), flush=True)
-    if opt.save_scores:
+            opt.tag and opt.tag + ' ', NAMES[f], np.median(t) * 1e3, len(t), t.min() * 1e3, t.max() * 1e3, 1.0 / np.median(t)), flush=True)
+    if opt.save_scores and 1 in res:
         saved[profile] = res[1][1]
+    if 2 in res and 0 in res:
+        d, f = res[0], res[2]
+        print("  tree: speed-up over dense %.2fx, over fused %.2fx; worst |dense - tree| score %.3e; rounds whose ground-truth rank differs: %d of %d"
+              % (np.median(times[0]) / np.median(times[2]), np.median(times[1]) / np.median(times[2]),
+                 np.abs(d[1].astype(np.float64) - f[1]).max(), int((d[0] != f[0]).sum()), N))
     if not opt.only:
         d, f = res[0], res[1]
         print("  speed-up %.2fx; worst |dense - fused| score %.3e (|score| max %.1f); rounds whose ground-truth rank differs: %d of %d"
@@ -234,3 +297,5 @@ for profile in ([opt.profile] if opt.profile else ['uniform', 'short']):
 if opt.save_scores:
     np.savez(opt.save_scores, **saved)
 nat.close()
+if nat_tree is not None:
+    nat_tree.close()

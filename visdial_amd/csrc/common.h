@@ -16,6 +16,7 @@
 #define VD_FLAG_SPLIT (VD_FLAG_SPLIT9 | VD_FLAG_SPLIT6 | VD_FLAG_SPLIT3)
 #define VD_FLAG_LIVE_PREFIX 16
 #define VD_FLAG_STATE_ONLY 32
+#define VD_FLAG_TREE 64
 #define VD_LIVE_PREFIX_ROWS 128
 
 // thread-local message returned by vd_last_error()

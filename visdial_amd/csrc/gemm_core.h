@@ -186,6 +186,18 @@ struct EpiDeadOf<Epi, std::void_t<decltype(Epi::HAS_DEAD)>> {
   static constexpr bool value = Epi::HAS_DEAD;
 };
 
+// Epilogue functors may declare `static constexpr bool HAS_AROWS = true` + `arow(r)`: output row r of the LDS-DMA pipeline multiplies
+// row arow(r) of A instead of row r (VD_FLAG_TREE, lstm.hip: a node continues its parent's state).  Same tiles, same K order.  Every
+// other epilogue answers "no" at compile time: the kernels instantiated with it do not change.
+template <class Epi, class = void>
+struct EpiARowsOf {
+  static constexpr bool value = false;
+};
+template <class Epi>
+struct EpiARowsOf<Epi, std::void_t<decltype(Epi::HAS_AROWS)>> {
+  static constexpr bool value = Epi::HAS_AROWS;
+};
+
 // Workgroup -> tile of a kernel whose epilogue has the predicate: the live row tiles are a PREFIX of the row tiles, and xcd_remap (below)
 // hands every XCD a contiguous range of tiles -- the live ones would all land on the first XCDs while the others retire dead workgroups
 // (that variant, measured with 55 % of the row tiles live: 132 us per step launch against 137 us for all rows; with the map below 89 us,
@@ -639,7 +651,8 @@ __device__ __forceinline__ void gemm_block_glds(int M, int N, int ks, int ke, in
     } else {
       const int r = (i * WM + wm) * 16 + (lane >> 2);
       const int c = (lane & 3) ^ ((r >> 2) & 3);  // chunk index swizzled on the source side
-      voffa[i] = (unsigned)(((long)min(row_base + r, M - 1) * lda + c * 4) * 4);
+      if constexpr (EpiARowsOf<Epi>::value) voffa[i] = (unsigned)(((long)epi.arow(min(row_base + r, M - 1)) * lda + c * 4) * 4);
+      else voffa[i] = (unsigned)(((long)min(row_base + r, M - 1) * lda + c * 4) * 4);
     }
   }
 #pragma unroll

@@ -158,6 +158,119 @@ lhood_nll_rows_kernel(const float* __restrict__ h, long ldh, const int* __restri
   nll[blockIdx.x] = (mx + logf(sum)) - pk;
 }
 
+// ---- the prefix-tree head (vd_lhood_lse_p below): the twin of lhood_nll_mfma_kernel without a target -- the same tiles, the same
+// pipeline, the same online max / sum (EpiLhood with every target at -1) and the same combine; lse[i] is the listed row's
+// log-sum-exp.  A kernel of its own, so that lhood_nll_mfma_kernel stays as it is.
+__global__ void __launch_bounds__(LhoodCfg::THREADS, LhoodCfg::MINW)
+lhood_lse_mfma_kernel(const float* __restrict__ h, long ldh, const int* __restrict__ act, int n_act, const float* __restrict__ W, long ldw,
+                      const float* __restrict__ bias, int V, int K, float* __restrict__ lse) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col_base = blockIdx.x * LhoodCfg::BN;
+  LhoodState st;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    st.m[j] = -INFINITY;
+    st.s[j] = 0.f;
+    st.pick[j] = 0.f;
+    st.tgt[j] = -1;
+  }
+  const EpiLhood epi{bias, &st};
+  const int tiles_v = (V + LhoodCfg::BM - 1) / LhoodCfg::BM;
+  for (int vt = 0; vt < tiles_v; ++vt) {
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));   // per-lane address terms are re-derived per tile, not kept live across the epilogue
+    gemm_block_glds<LhoodCfg, false>(V, n_act, 0, K, vt * LhoodCfg::BM, col_base, -1, W, ldw, h, ldh, epi, smem, tid, act);
+  }
+  // combine the 8 partial states of each of the 128 listed rows, partial p = wave * 2 + lane half, in the order p = 0..7
+  __syncthreads();
+  float* red = smem;   // [2][8][128]
+  const int p = wave * 2 + (lane >> 5);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = j * 32 + (lane & 31);
+    red[(0 * 8 + p) * 128 + c] = st.m[j];
+    red[(1 * 8 + p) * 128 + c] = st.s[j];
+  }
+  __syncthreads();
+  const int c = threadIdx.x, col = col_base + c;
+  if (c >= 128 || col >= n_act) return;
+  float mx = -INFINITY;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) mx = fmaxf(mx, red[(0 * 8 + q) * 128 + c]);
+  float sum = 0.f;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const float mq = red[(0 * 8 + q) * 128 + c];
+    if (mq > -INFINITY) sum += red[(1 * 8 + q) * 128 + c] * expf(mq - mx);
+  }
+  lse[col] = mx + logf(sum);
+}
+
+// the twin of lhood_nll_rows_kernel without a target (small shapes of the prefix-tree head)
+__global__ void __launch_bounds__(256)
+lhood_lse_rows_kernel(const float* __restrict__ h, long ldh, const int* __restrict__ act, const float* __restrict__ W, long ldw,
+                      const float* __restrict__ bias, int V, int K, float* __restrict__ lse) {
+  extern __shared__ __attribute__((aligned(16))) float hs[];
+  __shared__ float red[2][4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long row = act[blockIdx.x];
+  for (int k = tid; k < K; k += 256) hs[k] = h[row * ldh + k];
+  __syncthreads();
+  float m = -INFINITY, s = 0.f;
+  for (int v = tid; v < V; v += 256) {
+    const float* w = W + (long)v * ldw;
+    float x = bias ? bias[v] : 0.f;
+    for (int k = 0; k < K; ++k) x = fmaf(hs[k], w[k], x);
+    const float mn = fmaxf(m, x);
+    s = s * expf(m - mn) + expf(x - mn);   // m = -inf at first: s = 0 * 0
+    m = mn;
+  }
+  const float mw = wave_max(m);
+  s = wave_sum(m > -INFINITY ? s * expf(m - mw) : 0.f);
+  if (lane == 0) {
+    red[0][wave] = mw;
+    red[1][wave] = s;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  const float mx = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+  float sum = 0.f;
+  for (int q = 0; q < 4; ++q)
+    if (red[0][q] > -INFINITY) sum += red[1][q] * expf(red[0][q] - mx);
+  lse[blockIdx.x] = mx + logf(sum);
+}
+
+// ---- edge sum of the prefix-tree head: candidate r walks its (node, target) edges in step order,
+//   score[r] = sum_t ( W[target_t - 1] . h[row of node(r, t)] + bias[target_t - 1] - lse[node(r, t)] ).
+// One wave per candidate: the 64 lanes read the W row and the h row in 16-byte pieces (coalesced), a butterfly adds the lanes' partial
+// dot products in a fixed order, lane 0 adds the terms in step order and stores straight into candidate order.  No atomics; two
+// identical candidates walk the same nodes and tie exactly; a candidate without an edge scores +0.
+__global__ void __launch_bounds__(256)
+lhood_edge_sum_kernel(const float* __restrict__ h, long ldh, const int* __restrict__ node_row, const float* __restrict__ lse,
+                      const int* __restrict__ enode, const int* __restrict__ etgt, int T, long rows, int C, const float* __restrict__ W,
+                      long ldw, const float* __restrict__ bias, int K, float* __restrict__ out, long ldo) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  float sum = 0.f;
+  for (int t = 0; t < T; ++t) {
+    const int tgt = etgt[t * rows + r];
+    if (tgt <= 0) continue;   // (uniform over the wave)
+    const int nd = enode[t * rows + r];
+    const float* hr = h + (long)node_row[nd] * ldh;
+    const float* wr = W + (long)(tgt - 1) * ldw;
+    float d = 0.f;
+    for (int k = lane * 4; k < K; k += 256) {
+      const float4 a = *reinterpret_cast<const float4*>(hr + k), w = *reinterpret_cast<const float4*>(wr + k);
+      d = fmaf(a.x, w.x, d); d = fmaf(a.y, w.y, d); d = fmaf(a.z, w.z, d); d = fmaf(a.w, w.w, d);
+    }
+    d = wave_sum(d);
+    sum += (d + (bias ? bias[tgt - 1] : 0.f)) - lse[nd];
+  }
+  if (lane == 0) out[(r / C) * ldo + r % C] = sum;
+}
+
 // ---- vd_lhood_live_rows: stream compaction in index order.  Pass 1 counts the live rows of every 1024-row block; pass 2 gives each
 // block the sum of the counts before it and each thread its rank inside the block (wave prefix by shuffles + the waves' totals).
 __device__ __forceinline__ bool lhood_live(const int* tok_in, const int* target, long i, long n) {
@@ -350,6 +463,44 @@ int vd_lhood_order_p(const int32_t* tok_in, const int32_t* target, int T, int64_
   VD_LAUNCH_CHECK();
   hipLaunchKernelGGL(lhood_order_gather_kernel, dim3(vd_cdiv((long)T * rows, 256)), dim3(256), 0, s, tok_in, target, perm, T, (long)rows,
                      tok_in_s, target_s);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+// log-sum-exp of the rows of h listed in `act` (the nodes of a prefix tree): the kernels of vd_lhood_nll without a target
+int vd_lhood_lse_p(const float* h, int64_t ldh, int64_t rows, const int32_t* act, int64_t n_act, const float* W, int64_t ldw, const float* bias,
+                   int V, int H, float* lse, hipStream_t s) {
+  VD_CHECK_ARG(n_act >= 0 && n_act < (1L << 31) && rows >= 0 && V >= 1 && H >= 1 && ldh >= H && ldw >= H, "lhood lse: bad args");
+  if (n_act == 0) return VD_OK;
+  VD_CHECK_ARG(h && act && W && lse, "lhood lse: null pointer");
+  if (vd_lhood_fused_fits(rows, ldh, V, ldw, H) && ((uintptr_t)h & 15) == 0 && ((uintptr_t)W & 15) == 0) {
+    auto kern = lhood_lse_mfma_kernel;
+    static bool attr_set = false;
+    if (!attr_set) {
+      VD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LhoodCfg::LDS_BYTES));
+      attr_set = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(vd_cdiv(n_act, LhoodCfg::BN)), dim3(LhoodCfg::THREADS), LhoodCfg::LDS_BYTES, s, h, (long)ldh, act,
+                       (int)n_act, W, (long)ldw, bias, V, H, lse);
+    VD_LAUNCH_CHECK();
+    return VD_OK;
+  }
+  VD_CHECK_ARG((size_t)H * 4 <= 48 * 1024, "lhood lse: H = %d too large for the row kernel", H);
+  hipLaunchKernelGGL(lhood_lse_rows_kernel, dim3((unsigned)n_act), dim3(256), (size_t)H * 4, s, h, (long)ldh, act, W, (long)ldw, bias, V, H,
+                     lse);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+// score of every candidate of a chunk from its edges: enode / etgt [T x rows] (node id into node_row / lse, 1-based target, 0 = no edge)
+int vd_lhood_edge_sum_p(const float* h, int64_t ldh, const int32_t* node_row, const float* lse, const int32_t* enode, const int32_t* etgt, int T,
+                        int64_t rows, int C, const float* W, int64_t ldw, const float* bias, int H, float* out, int64_t ldo, hipStream_t s) {
+  VD_CHECK_ARG(out && T >= 0 && rows >= 0 && C >= 1 && ldo >= C && (long)T * rows < (1L << 31) && H % 4 == 0 && ldh % 4 == 0 && ldw % 4 == 0,
+               "lhood edge sum: bad args");
+  if (rows == 0) return VD_OK;
+  VD_CHECK_ARG(T == 0 || (h && node_row && lse && enode && etgt && W), "lhood edge sum: null pointer");
+  hipLaunchKernelGGL(lhood_edge_sum_kernel, dim3(vd_cdiv(rows, 4)), dim3(256), 0, s, h, (long)ldh, node_row, lse, enode, etgt, T, (long)rows, C,
+                     W, (long)ldw, bias, H, out, (long)ldo);
   VD_LAUNCH_CHECK();
   return VD_OK;
 }

@@ -183,9 +183,11 @@ struct EpiLstmFwdT {
                                              int Nv, float* scr, const Pre* pre = nullptr) const {
     run<true>(acc, row0, vcol0, lane, M, Nv, scr, pre);
   }
-  template <bool GATES>
+  // TREE (EpiLstmFwdTree): c_{t-1} of row r is read from row prow[r] (row 0 for a masked row) instead of row r.  The index of row group
+  // p + 1 is requested together with the operands of group p -- one register, a whole group ahead of the load that needs it
+  template <bool GATES, bool TREE = false>
   __device__ __forceinline__ void run(const f32x16 (&acc)[4], int row0, int vcol0, int lane, int M,
-                                      int /*Nv*/, float* scr, const Pre* pre) const {
+                                      int /*Nv*/, float* scr, const Pre* pre, const int* prow = nullptr) const {
     if constexpr (SEQ == 1) {
       sequential(acc, row0, vcol0, lane, M, scr);
       return;
@@ -218,6 +220,9 @@ struct EpiLstmFwdT {
         for (int p = 0; p < 4; ++p) keep[p] = tok_mask[rowc[p]];
       }
     }
+    int cn = 0;
+    const __amdgpu_buffer_rsrc_t rp = vd_rsrc(prow);
+    if constexpr (TREE) cn = __builtin_amdgcn_raw_buffer_load_b32(rp, (unsigned)rowc[0] * 4u, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
     float4 a[4][4];  // [gate][p]
     float4 x[4], cp;
@@ -260,7 +265,12 @@ struct EpiLstmFwdT {
         x[2] = vd_buf_ld4(rx, xo, 2 * uH4);
         x[3] = vd_buf_ld4(rx, xo, 3 * uH4);
         cp = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (TREE) {
+          if (c_prev) cp = vd_buf_ld4(rc, (unsigned)(keep[p] != 0 ? cn : 0) * uH4 + uj4, 0);
+          if (p + 1 < 4) cn = __builtin_amdgcn_raw_buffer_load_b32(rp, (unsigned)rowc[p + 1] * 4u, 0, 0);
+        } else {
         if (c_prev) cp = vd_buf_ld4(rc, (unsigned)rowc[p] * uH4 + uj4, 0);
+        }
       }
     };
     if constexpr (!C16) issue(0);
@@ -353,6 +363,55 @@ struct EpiLstmFwdState : EpiLstmFwd {
                                              const Pre* pre = nullptr) const {
     run<false>(acc, row0, vcol0, lane, M, Nv, scr, pre);
   }
+};
+
+// VD_FLAG_TREE: a level-by-level recurrence over a forest.  Row n of step t continues the state of row parent[n] of the step before
+// (of h0 / c0 at the first step), not of row n: the recurrent product's h_{t-1} operand is gathered through `parent` by the step
+// kernels (gemm_core.h EpiARowsOf, SrcRowTree below) and c_{t-1} is read through it here.  Forward only: c and h are stored, no gate
+// value reaches memory (as EpiLstmFwdState), and the nodes of a step are a prefix of its rows (the predicate of EpiLstmFwdLive).  A row
+// without a node inside a live tile reads parent row 0 -- a node whenever the step has one -- and stores zeros.  A type of its own: the
+// other step kernels keep their instantiations.
+struct EpiLstmFwdTree : EpiLstmFwd {
+  const int* parent;   // [N] rows of the previous step's state (plane 1 of tok_mask)
+  static constexpr bool HAS_DEAD = true;
+  static constexpr bool HAS_AROWS = true;
+  __device__ __forceinline__ bool dead(int row_base, int /*BM*/) const { return tok_mask[row_base] == 0; }
+  // row of the A operand (h_{t-1}) that output row r < M multiplies
+  __device__ __forceinline__ int arow(int r) const {
+    const int m = tok_mask[r], q = parent[r];
+    return m != 0 ? q : 0;
+  }
+  __device__ __forceinline__ void dist_load(DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
+    const int j = (vcol0 >> 7) * 32 + (lane & 7) * 4;
+    const int row = row0 + grp * 8 + (lane >> 3);
+    const int rc = row < M ? row : M - 1;
+    q.keep = tok_mask[rc] != 0;
+    const int pr = q.keep ? parent[rc] : 0;
+    const float* xr = xproj + (tok_gather ? (long)tok_gather[rc] : (long)rc) * xld + j;
+    q.x[0] = *reinterpret_cast<const float4*>(xr);
+    q.x[1] = *reinterpret_cast<const float4*>(xr + H);
+    q.x[2] = *reinterpret_cast<const float4*>(xr + 2 * H);
+    q.x[3] = *reinterpret_cast<const float4*>(xr + 3 * H);
+    q.cp = c_prev ? *reinterpret_cast<const float4*>(c_prev + (long)pr * H + j) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  __device__ __forceinline__ void dist_store(const float4 (&a)[4], const DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
+    dist_store_t<false>(a, q, row0, vcol0, lane, grp, M);
+  }
+  __device__ __forceinline__ void operator()(const f32x16 (&acc)[4], int row0, int vcol0, int lane, int M, int Nv, float* scr,
+                                             const Pre* pre = nullptr) const {
+    run<false, true>(acc, row0, vcol0, lane, M, Nv, scr, pre, parent);
+  }
+};
+// h_{t-1} rows seen through the parent list of EpiLstmFwdTree: the A operand of the generic step kernels
+struct SrcRowTree {
+  static constexpr bool KMAJOR = false;
+  static constexpr bool PLAIN = true;
+  const float* p;
+  long ld;
+  const int* mask;
+  const int* parent;
+  __device__ __forceinline__ const float* ptr(int r, int k) const { return p + (mask[r] != 0 ? (long)parent[r] : 0L) * ld + k; }
+  __device__ __forceinline__ long kstep() const { return 1; }
 };
 
 // ---------------------------------------------------------------------------
@@ -637,6 +696,14 @@ static int lstm_step_fwd(const float* h_prev, const float* Wh, int N, int H, int
   return launch_gemm<CfgFwdSmallA>(N, 4 * H, K, 1, a, b, epi, s);
 }
 
+// VD_FLAG_TREE: the same two kernels with h_{t-1} gathered through the parent list (same tiles, same K order)
+static int lstm_step_fwd_tree(const float* h_prev, const float* Wh, int N, int H, const EpiLstmFwdTree& epi, hipStream_t s) {
+  SrcRowTree a{h_prev, H, epi.tok_mask, epi.parent};
+  SrcKGate4 b{Wh, 4L * H, H};
+  if (N >= VD_THROUGHPUT_ROWS) return launch_gemm<CfgF9>(N, 4 * H, H, 1, a, b, epi, s);
+  return launch_gemm<CfgFwdSmallA>(N, 4 * H, H, 1, a, b, epi, s);
+}
+
 // one backward step with the kernels vd_lstm_backward chose for the pass: the exact split (split = products per step, W3 the weight
 // planes), bf16 operands (da16 = this step's shadow), or fp32
 static int lstm_step_bwd(const float* da_next, const float* Wh, int N, int H, int K, const float* dh_a,
@@ -874,8 +941,17 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
                     float* h, float* c, int T, int N, int H, int flags, void* stream) {
   VD_CHECK_ARG(T >= 0 && N >= 0 && H > 0 && H % 32 == 0, "vd_lstm_forward: bad dims T=%d N=%d H=%d", T, N, H);
   VD_CHECK_ARG(xproj && Wh && h && c, "vd_lstm_forward: null pointer");
+  // VD_FLAG_TREE (include/visdial_hip.h): forward only, exact fp32, [2 x T x N] tok_mask (mask | parent row)
+  const bool tree = (flags & VD_FLAG_TREE) != 0;
+  VD_CHECK_ARG(!tree || !(flags & (VD_FLAG_BF16 | VD_FLAG_SPLIT)),
+               "vd_lstm_forward: VD_FLAG_TREE runs the exact fp32 step kernels only; it does not combine with VD_FLAG_BF16 / "
+               "VD_FLAG_SPLIT* (flags = %d)", flags);
+  VD_CHECK_ARG(!tree || !(flags & VD_FLAG_STATE_ONLY),
+               "vd_lstm_forward: VD_FLAG_TREE keeps h and c of every level; it does not combine with VD_FLAG_STATE_ONLY (flags = %d)", flags);
+  VD_CHECK_ARG(!tree || !gates, "vd_lstm_forward: VD_FLAG_TREE is forward only and saves no gate activations: gates must be NULL");
+  VD_CHECK_ARG(!tree || tok_mask, "vd_lstm_forward: VD_FLAG_TREE needs tok_mask ([2 x T x N]: mask and parent row)");
   const bool state_only = (flags & VD_FLAG_STATE_ONLY) != 0;
-  VD_CHECK_ARG(state_only || gates, "vd_lstm_forward: null pointer (gates may be NULL only with VD_FLAG_STATE_ONLY)");
+  VD_CHECK_ARG(state_only || tree || gates, "vd_lstm_forward: null pointer (gates may be NULL only with VD_FLAG_STATE_ONLY)");
   VD_CHECK_ARG(!state_only || !gates, "vd_lstm_forward: VD_FLAG_STATE_ONLY saves no gate activations: gates must be NULL");
   VD_CHECK_ARG(!state_only || !(flags & VD_FLAG_BF16),
                "vd_lstm_forward: VD_FLAG_STATE_ONLY does not combine with VD_FLAG_BF16 (the bf16 recurrence reads the saved bf16 copy of h; flags = %d)", flags);
@@ -944,7 +1020,14 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
     e.H = H;
     e.h16 = h16 ? h16 + t * NH : nullptr;
     int rc;
-    if (state_only) {   // (neither bf16 nor the live prefix) the paths of the saving pass with the epilogue that stores c and h only
+    if (tree) {   // (fp32 only) the live prefix's paths with the parent gather; plane 1 of tok_mask holds the parent rows
+      EpiLstmFwdTree et;
+      static_cast<EpiLstmFwd&>(et) = e;
+      et.parent = tok_mask + ((long)T + t) * N;
+      if (!hp) rc = lstm_step_fwd(nullptr, Wh, N, H, 0, et, s);
+      else if (glds) rc = launch_gemm_glds<CfgF9, false>(N, 4 * H, H, 1, hp, (long)H, WhT, (long)H, et, s);
+      else rc = lstm_step_fwd_tree(hp, Wh, N, H, et, s);
+    } else if (state_only) {   // (neither bf16 nor the live prefix) the paths of the saving pass with the epilogue that stores c and h only
       EpiLstmFwdState es;
       static_cast<EpiLstmFwd&>(es) = e;
       if (!hp) rc = lstm_step_fwd(nullptr, Wh, N, H, 0, es, s);

@@ -49,6 +49,13 @@ int64_t vd_lhood_order_work_ints(int T, int64_t rows);
 int vd_lhood_sum_p(const float* nll, const int32_t* act, int64_t n_act, int T, int64_t rows, int C, const int32_t* perm, float* out, int64_t ldo,
                    hipStream_t stream);
 
+// lhood.hip, prefix-tree head (VD_LHOOD_TREE): the log-sum-exp of the listed rows of h (the kernels of vd_lhood_nll without a target), and
+// every candidate's score as the sum over its (node, target) edges, in step order, written in candidate order
+int vd_lhood_lse_p(const float* h, int64_t ldh, int64_t rows, const int32_t* act, int64_t n_act, const float* W, int64_t ldw, const float* bias,
+                   int V, int H, float* lse, hipStream_t stream);
+int vd_lhood_edge_sum_p(const float* h, int64_t ldh, const int32_t* node_row, const float* lse, const int32_t* enode, const int32_t* etgt, int T,
+                        int64_t rows, int C, const float* W, int64_t ldw, const float* bias, int H, float* out, int64_t ldo, hipStream_t stream);
+
 #define VD_TRY(expr)                  \
   do {                                \
     const int rc__ = (expr);          \
@@ -82,8 +89,24 @@ struct SeqTok {
   int n_act = 0, n_act1 = 0;
 };
 
+// Prefix tree of a chunk of candidates (generative retrieval with VD_LHOOD_TREE; built on the host at upload time, runtime.hip): the
+// candidates of options [o0, o0 + C) of every round as a forest over the rounds' encoder states.  Nodes are numbered level-major; a
+// level's nodes are rows [0, widths[t]) of step t of a [Tl x Nw] recurrence (VD_FLAG_TREE).
+struct TreeChunk {
+  int o0 = 0, C = 0, Tl = 0, Nw = 0;
+  long n_nodes = 0;
+  std::vector<int32_t> widths;   // [Tl]
+  int32_t* mask2 = nullptr;      // device [2 x Tl x Nw]: token (0 = no node) | parent row (level 0: the round)
+  int32_t* node_row = nullptr;   // device [n_nodes]: t * Nw + n, ascending -- the row list of the head
+  int32_t *enode = nullptr, *etgt = nullptr;   // device [T x N*C]: node id and 1-based target of candidate r's edge at step t (target 0 = none)
+};
+
 struct BatchSlot {
   int B = 0;
+  // VD_LHOOD_TREE: the prefix trees of the batch's option_in / option_out, one per chunk of options; tree_ok = false for a batch with a
+  // token behind a pad (or out of the vocabulary) in any candidate, which takes the length-ordered path instead
+  bool tree_ok = false;
+  std::vector<TreeChunk> tree;
   SeqTok q, h, opt, ain, aout, oin, oout;
   float* img = nullptr;
   int32_t* gt = nullptr;  // [N] 0-based
@@ -223,6 +246,7 @@ struct vd_model {
   // capability flags from the encoder NAME (opts.lua:54-67)
   bool use_im = false, use_hist = false, is_att = false, is_graph = false;
   vdrt::OptionCache ocache;
+  bool lhood_tree = false;   // VD_LHOOD_TREE at vd_model_create: vd_model_retrieve_lhood scores over a prefix tree of the candidates
   bool prof_hist = false;   // ev_prof[0..3] bracket the history branch of a Sequential encoder (gen pairs: vd_model_family_ms)
   ~vd_model();
 };
@@ -529,6 +553,28 @@ struct SeqLSTM {
         VD_TRY(vd_gemm_nn(x, D, Wx(m), 4 * H, Wp(m, name + ".b"), gates, 4 * H, T * N, (int)(4 * H), (int)D, 0, s));
       }
       VD_TRY(vd_lstm_forward(gates, (int64_t)N * 4 * H, 4 * H, nullptr, tok, Wh(m), h0, c0, gates, h, c, T, N, (int)H, flags, s));
+    }
+    if (h_out) *h_out = h;
+    return VD_OK;
+  }
+  // Forward-only pass over a forest, level by level (generative retrieval over a prefix tree, rt_decoders.h): mask2 [2 x T x N] = token |
+  // parent row (VD_FLAG_TREE); the parents of level 0 are rows of the R-row state in userPrevOutput / userPrevCell.  Layer 1 gathers
+  // `table` by token id; a higher layer projects `x` (the h of the layer below, same node rows) per step into its projection buffer,
+  // skipping the row tiles without a node.  Only h and c of every level are kept: no gate value is stored.
+  int forward_tree(vd_model* m, hipStream_t s, const float* table, const float* x, int T_, int N_, int R_, const int32_t* mask2, float** h_out) {
+    VD_TRY(take_state(m, s, R_));
+    T = T_; N = N_;
+    VD_TRY(ws_get(m, name + ".h", (size_t)T * N * H, &h));
+    VD_TRY(ws_get(m, name + ".c", (size_t)T * N * H, &c));
+    xs.clear(); tok_mask = mask2; rows = nullptr;
+    if (table) {
+      VD_TRY(vd_lstm_forward(table, 0, 4 * H, mask2, mask2, Wh(m), h0, c0, nullptr, h, c, T, N, (int)H, VD_FLAG_TREE, s));
+    } else {
+      VD_TRY(ws_get(m, name + ".gates", (size_t)T * N * 4 * H, &gates));
+      for (int t = 0; t < T; ++t)
+        VD_TRY(vd_gemm_nn_live_p(x + (long)t * N * D, D, Wx(m), 4 * H, Wp(m, name + ".b"), gates + (long)t * N * 4 * H, 4 * H, N, (int)(4 * H),
+                                 (int)D, mask2 + (long)t * N, vd_lstm_fwd_row_tile(N), s));
+      VD_TRY(vd_lstm_forward(gates, (int64_t)N * 4 * H, 4 * H, nullptr, mask2, Wh(m), h0, c0, nullptr, h, c, T, N, (int)H, VD_FLAG_TREE, s));
     }
     if (h_out) *h_out = h;
     return VD_OK;

@@ -400,7 +400,50 @@ struct Gen : Decoder {
   // vd_model_retrieve_lhood: the same encoder forward and forwardConnect replication; the candidates run through the decoder in order of
   // descending length, the recurrence (SeqLSTM::forward_ordered) only where there are tokens; the head is vd_lhood_live_rows +
   // vd_lhood_nll + vd_lhood_sum (csrc/lhood.hip) over the live rows of the chunk, with no logits buffer
-  int retrieve_lhood(vd_model* m, BatchSlot& b) override { return retrieve_head(m, b, true); }
+  // With VD_LHOOD_TREE (third mode): over a prefix tree of the candidates' tokens, retrieve_tree below; a batch the tree was not built
+  // for (a token behind a pad) takes the length-ordered path unchanged, and the counters then report that path
+  int retrieve_lhood(vd_model* m, BatchSlot& b) override {
+    if (m->lhood_tree && b.tree_ok) return retrieve_tree(m, b);
+    return retrieve_head(m, b, true);
+  }
+  // The decoder state after a candidate's first t tokens depends on the round's encoder state and on those tokens only, so the chunk's
+  // candidates run as a forest: one node per distinct (round, token prefix), levels packed densely (no pad rows, no length order), the
+  // depth-0 parents are the rounds' rows of the encoder state (no forwardConnect replication).  The head runs once per NODE
+  // (vd_lhood_lse_p: the log-sum-exp belongs to the prefix), and a candidate's score is the sum over its edges of target logit - lse
+  // (vd_lhood_edge_sum_p), written straight into candidate order.  The host built every list at upload time (runtime.hip
+  // build_lhood_tree): the step needs no host synchronisation.
+  int retrieve_tree(vd_model* m, BatchSlot& b) {
+    VD_CHECK_ARG(b.oin.present && b.oout.present, "retrieval with decoder 'gen' needs batch.option_in / option_out");
+    hipStream_t s = m->s_main;
+    const int N = b.q.N, O = m->p.numOptions, T = b.oin.T;
+    float* encOut;
+    VD_TRY(m->enc->forward(m, s, b, &encOut));
+    const int seqLen = m->enc->seqLen(b);
+    float *lhood, *table;
+    VD_TRY(ws_get(m, "ret.lhood", (size_t)N * O, &lhood));
+    VD_TRY(ws_get(m, "ret.table", (size_t)(V + 1) * 4 * H, &table));
+    VD_TRY(vd_gemm_nn(Wp(m, "embed"), E, rnn[0].Wx(m), 4 * H, Wp(m, rnn[0].name + ".b"), table, 4 * H, (int)V + 1, (int)(4 * H), (int)E, 0, s));
+    m->lhood_exec = 0;
+    m->lhood_total = (long)T * N * O;
+    for (const TreeChunk& tc : b.tree) {
+      const long rows = (long)N * tc.C;
+      const long tile = vd_lstm_fwd_row_tile(tc.Nw);
+      for (int t = 0; t < tc.Tl; ++t) m->lhood_exec += std::min<long>(tc.Nw, (tc.widths[t] + tile - 1) / tile * tile);
+      float *h = nullptr, *lse;
+      VD_TRY(ws_get(m, "ret.lse", (size_t)std::max<long>(1, tc.n_nodes), &lse));
+      if (tc.Tl > 0) {
+        VD_TRY(forwardConnect(m, s, encOut, seqLen, nullptr, N));
+        VD_TRY(rnn[0].forward_tree(m, s, table, nullptr, tc.Tl, tc.Nw, N, tc.mask2, &h));
+        for (size_t l = 1; l < rnn.size(); ++l) VD_TRY(rnn[l].forward_tree(m, s, nullptr, h, tc.Tl, tc.Nw, N, tc.mask2, &h));
+        VD_TRY(vd_lhood_lse_p(h, H, (long)tc.Tl * tc.Nw, tc.node_row, tc.n_nodes, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), (int)V, (int)H, lse, s));
+      }
+      VD_TRY(vd_lhood_edge_sum_p(h, H, tc.node_row, lse, tc.enode, tc.etgt, tc.Tl, rows, tc.C, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), (int)H,
+                                 lhood + tc.o0, O, s));
+    }
+    m->scores = lhood;
+    m->prof_valid = false;
+    return VD_OK;
+  }
   int retrieve_head(vd_model* m, BatchSlot& b, bool live) {
     VD_CHECK_ARG(b.oin.present && b.oout.present, "retrieval with decoder 'gen' needs batch.option_in / option_out");
     hipStream_t s = m->s_main;

@@ -150,6 +150,129 @@ int vdrt::option_cache_resolve(vd_model* m, BatchSlot& sl, const int32_t* option
   return VD_OK;
 }
 
+// ---- prefix trees of a batch's candidates (VD_LHOOD_TREE; rt_core.h TreeChunk, rt_decoders.h Gen::retrieve_tree) --------------------
+// option_in / option_out [N x O x T] host rows.  One tree per chunk of options [o0, o0 + C): level t holds one node per distinct
+// (parent node, token) among the candidates still running at step t -- one open-addressing map per level keyed by (parent row, token);
+// a parent row belongs to one round, so this is one map per (dialog, round) folded into one table.  Nodes are numbered in order of
+// first occurrence inside their level (round-major), levels in step order.
+struct TreeHost {
+  int Tl = 0, Nw = 0;
+  long n_nodes = 0;
+  std::vector<int32_t> widths, enode, etgt;
+  std::vector<std::vector<int32_t>> tok, par;   // per level
+};
+
+static void tree_build_range(const int32_t* oin, const int32_t* oout, int N, int O, int T, int o0, int C, TreeHost& th) {
+  const long rows = (long)N * C;
+  std::vector<int32_t> cur((size_t)rows);
+  std::vector<uint8_t> alive((size_t)rows, 1);
+  for (long r = 0; r < rows; ++r) cur[r] = (int32_t)(r / C);
+  th = TreeHost();
+  th.enode.assign((size_t)T * rows, 0);
+  th.etgt.assign((size_t)T * rows, 0);
+  std::vector<uint64_t> keys;
+  std::vector<int32_t> vals;
+  for (int t = 0; t < T; ++t) {
+    long cnt = 0;
+    for (long r = 0; r < rows; ++r) {
+      if (alive[r] && oin[((size_t)(r / C) * O + o0 + r % C) * T + t] == 0) alive[r] = 0;
+      cnt += alive[r];
+    }
+    if (cnt == 0) break;
+    size_t cap = 16;
+    while (cap < 2 * (size_t)cnt) cap <<= 1;
+    keys.assign(cap, ~0ull);
+    vals.assign(cap, -1);
+    std::vector<int32_t> ltok, lpar;
+    for (long r = 0; r < rows; ++r) {
+      if (!alive[r]) continue;
+      const size_t src = ((size_t)(r / C) * O + o0 + r % C) * T + t;
+      const uint64_t key = ((uint64_t)(uint32_t)cur[r] << 32) | (uint32_t)oin[src];
+      size_t pos = (size_t)((key * 0x9E3779B97F4A7C15ull) >> 20) & (cap - 1);
+      while (keys[pos] != ~0ull && keys[pos] != key) pos = (pos + 1) & (cap - 1);
+      if (keys[pos] == ~0ull) {
+        keys[pos] = key;
+        vals[pos] = (int32_t)ltok.size();
+        ltok.push_back(oin[src]);
+        lpar.push_back(cur[r]);
+      }
+      cur[r] = vals[pos];
+      if (oout[src] != 0) {
+        th.enode[(size_t)t * rows + r] = (int32_t)(th.n_nodes + cur[r]);
+        th.etgt[(size_t)t * rows + r] = oout[src];
+      }
+    }
+    th.widths.push_back((int32_t)ltok.size());
+    th.n_nodes += (long)ltok.size();
+    th.Nw = std::max<int>(th.Nw, (int)ltok.size());
+    th.tok.push_back(std::move(ltok));
+    th.par.push_back(std::move(lpar));
+    th.Tl = t + 1;
+  }
+}
+
+// the chunk's workspace by the nodes it actually holds: h and c of every level and layer (2H floats per node slot), the hoisted input
+// projection of the layers above the first (4H), held to 4 GiB like the other heads' chunks; and the 32-bit byte offsets the kernels
+// document -- the head's h rows (Tl * Nw * H * 4 bytes), one step's projection slice (Nw * 4H * 4 bytes), row indices below 2^31
+static bool tree_chunk_fits(const TreeHost& th, long H, long layers) {
+  const long slots = (long)th.Tl * th.Nw;
+  return slots * (2 * H * layers + 4 * H * (layers - 1)) <= (1L << 30) && slots * H * 4 < (1L << 32) && (long)th.Nw * 4 * H * 4 < (1L << 32) &&
+         slots < (1L << 31);
+}
+
+static int tree_chunks(vd_model* m, BatchSlot& sl, const int32_t* oin, const int32_t* oout, int N, int O, int T, int o0, int C, hipStream_t s) {
+  TreeHost th;
+  tree_build_range(oin, oout, N, O, T, o0, C, th);
+  if (!tree_chunk_fits(th, m->p.rnnHiddenSize, m->p.numLayers) && C > 1) {   // does not fit: halve the option range
+    VD_TRY(tree_chunks(m, sl, oin, oout, N, O, T, o0, C / 2, s));
+    return tree_chunks(m, sl, oin, oout, N, O, T, o0 + C / 2, C - C / 2, s);
+  }
+  TreeChunk tc;
+  tc.o0 = o0; tc.C = C; tc.Tl = th.Tl; tc.Nw = th.Nw; tc.n_nodes = th.n_nodes; tc.widths = th.widths;
+  const size_t slots = (size_t)th.Tl * th.Nw, edges = (size_t)T * N * C;
+  const size_t total = 2 * slots + (size_t)th.n_nodes + 2 * edges;
+  const std::string tag = "tree." + std::to_string(sl.tree.size());
+  int32_t *stage = nullptr, *dev = nullptr;
+  VD_TRY(pin_get(sl.pinned, tag + ".stage", total * sizeof(int32_t), (void**)&stage));
+  VD_TRY(dev_get(sl.bufs, tag, total * sizeof(int32_t), (void**)&dev));
+  memset(stage, 0, 2 * slots * sizeof(int32_t));
+  int32_t* nr = stage + 2 * slots;
+  for (int t = 0; t < th.Tl; ++t) {
+    const size_t w = th.tok[t].size();
+    memcpy(stage + (size_t)t * th.Nw, th.tok[t].data(), w * sizeof(int32_t));
+    memcpy(stage + slots + (size_t)t * th.Nw, th.par[t].data(), w * sizeof(int32_t));
+    for (size_t n = 0; n < w; ++n) *nr++ = (int32_t)((size_t)t * th.Nw + n);
+  }
+  memcpy(nr, th.enode.data(), edges * sizeof(int32_t));
+  memcpy(nr + edges, th.etgt.data(), edges * sizeof(int32_t));
+  if (total) VD_HIP(hipMemcpyAsync(dev, stage, total * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  tc.mask2 = dev;
+  tc.node_row = dev + 2 * slots;
+  tc.enode = tc.node_row + th.n_nodes;
+  tc.etgt = tc.enode + edges;
+  sl.tree.push_back(std::move(tc));
+  return VD_OK;
+}
+
+static int build_lhood_tree(vd_model* m, BatchSlot& sl, const int32_t* oin, const int32_t* oout, int N, int O, int T, hipStream_t s) {
+  sl.tree.clear();
+  sl.tree_ok = false;
+  // an ill-formed batch -- a token behind a pad in any candidate (not one left-aligned run), or a token / target outside the vocabulary --
+  // gets no tree: vd_model_retrieve_lhood then takes the length-ordered path, whose order kernels report the same condition
+  const long V = m->p.vocabSize;
+  for (size_t r = 0; r < (size_t)N * O; ++r) {
+    bool run = true;
+    for (int t = 0; t < T; ++t) {
+      const int32_t a = oin[r * T + t], b = oout[r * T + t];
+      if (a < 0 || a > V || b < 0 || b > V || (a != 0 && !run)) return VD_OK;
+      run = run && a != 0;
+    }
+  }
+  VD_TRY(tree_chunks(m, sl, oin, oout, N, O, T, 0, O, s));
+  sl.tree_ok = true;
+  return VD_OK;
+}
+
 extern "C" {
 
 int vd_model_create(const vd_model_params* p, const char* encoder, const char* decoder, vd_model** out) {
@@ -190,10 +313,19 @@ int vd_model_create(const vd_model_params* p, const char* encoder, const char* d
                "vd_model_create: VD_OPTION_CACHE needs the state-only option recurrence, which the compact bf16 recurrence (lstmBf16 = 1) "
                "does not have");
   VD_CHECK_ARG(cache_rows < (1L << 30), "vd_model_create: VD_OPTION_CACHE = %ld rows is out of range", cache_rows);
+  // prefix-tree scoring of generative retrieval (include/visdial_hip.h at vd_model_retrieve_lhood): 0 / unset = off
+  bool lhood_tree = false;
+  if (const char* e = getenv("VD_LHOOD_TREE")) lhood_tree = atol(e) > 0;
+  VD_CHECK_ARG(!lhood_tree || std::string(decoder) == "gen",
+               "vd_model_create: VD_LHOOD_TREE scores the candidates of decoder 'gen' over a prefix tree; this model's decoder is '%s'", decoder);
+  VD_CHECK_ARG(!lhood_tree || p->lstmBf16 != 1,
+               "vd_model_create: VD_LHOOD_TREE runs the exact fp32 tree recurrence (VD_FLAG_TREE), which the compact bf16 recurrence "
+               "(lstmBf16 = 1) does not have");
   vd_model* m = new vd_model();
   m->p = *p;
   m->flags = flags;
   m->ocache.capacity = cache_rows;
+  m->lhood_tree = lhood_tree;
   if (m->p.numAttentionLayers < 1 || has(en, "lf-att")) m->p.numAttentionLayers = 1;   // (lf-att-ques-im-hist.lua:49 hard-codes one hop)
   if (m->p.numLayers < 1) m->p.numLayers = 2;        // opts.lua:27
   m->enc_name = encoder;
@@ -522,9 +654,11 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
     VD_TRY(upload_tokens(sl, sl.ain, "ain", hb->answer_in, N, hb->Ta, false, s));
     VD_TRY(upload_tokens(sl, sl.aout, "aout", hb->answer_out, N, hb->Ta, false, s));
   }
+  sl.tree_ok = false;
   if (!disc && hb->option_in && hb->option_out) {                                               // model.lua:393-399
     VD_TRY(upload_tokens(sl, sl.oin, "oin", hb->option_in, (int)NO, hb->To, false, s));
     VD_TRY(upload_tokens(sl, sl.oout, "oout", hb->option_out, (int)NO, hb->To, false, s));
+    if (m->lhood_tree) VD_TRY(build_lhood_tree(m, sl, hb->option_in, hb->option_out, N, O, hb->To, s));
   }
   sl.has_gt = hb->answer_ind != nullptr;
   sl.gt_host.assign(N, 0);

@@ -100,6 +100,8 @@ class Decoder(object):
         # params fusedLhood: the live-row head (csrc/lhood.hip) -- live-row list, fused projection + online log-sum-exp over the live
         # rows, per-candidate sum; no logits.  A chunk is then sized by what is still materialised: the decoder's input and saved
         # state, (E + 6 H per layer) floats per (step, row), <= 4 GiB
+        if int(self.p.get('fusedLhood', 0) or 0) == 2:            # (the parameter was changed after Model() refused it)
+            raise ValueError("fusedLhood = 2 (prefix tree) runs in the model-level runtime only: use -host native")
         live = bool(int(self.p.get('fusedLhood', 0) or 0))
         per_opt = T * N * (self.E + 6 * H * len(self.rnnLayers) if live else Vp)
         oc = max(1, min(O, int((1 << 30) // max(1, per_opt))))              # options per chunk: <= 4 GiB of logits

@@ -45,6 +45,10 @@ class Wrapper(object):
 class Model(SplitEval):
     def __init__(self, params, dist_group=None):
         self.params = params
+        if int(params.get('fusedLhood', 0) or 0) == 2:
+            # the prefix-tree head is internal to the library (its C symbol set is frozen): only the model-level runtime reaches it
+            raise ValueError("fusedLhood = 2 (generative retrieval over a prefix tree of the candidates) runs in the model-level runtime only: "
+                             "use -host native (visdial_amd.native.NativeModel); the operator-level host takes fusedLhood = 0 or 1")
         if not torch.cuda.is_available():
             raise RuntimeError("visdial_amd.Model needs an MI355X (HIP device); there is no CPU path")
         gpuid = int(params.get('gpuid', 0))

@@ -70,16 +70,21 @@ class NativeModel(SplitEval):
         # params optionCache (0 = off, 1 = on, larger = capacity in rows): the answer-encoding cache of disc evaluation.  The library reads
         # its switch from the environment when the model is created (the Lua host sets the same variable); the previous value comes
         # back right after, so two models of one process can differ.
+        # params fusedLhood = 2: generative retrieval over a prefix tree of the candidates' tokens (VD_LHOOD_TREE, read the same way);
+        # fusedLhood = 1 and 0 create the model without it
         import os
-        prev = os.environ.get('VD_OPTION_CACHE')
-        os.environ['VD_OPTION_CACHE'] = str(int(p.get('optionCache', 0) or 0))
+        switches = {'VD_OPTION_CACHE': str(int(p.get('optionCache', 0) or 0)),
+                    'VD_LHOOD_TREE': '1' if int(p.get('fusedLhood', 0) or 0) == 2 else '0'}
+        prev = {k: os.environ.get(k) for k in switches}
+        os.environ.update(switches)
         try:
             call("vd_model_create", C.byref(mp), p['encoder'].encode(), p['decoder'].encode(), C.byref(h))
         finally:
-            if prev is None:
-                del os.environ['VD_OPTION_CACHE']
-            else:
-                os.environ['VD_OPTION_CACHE'] = prev
+            for k, v in prev.items():
+                if v is None:
+                    del os.environ[k]
+                else:
+                    os.environ[k] = v
         self.h = h
         lib = _lib.load()
         self.tensors = []
@@ -295,7 +300,8 @@ class NativeModel(SplitEval):
         if useGt is None:
             useGt = bool(self.params.get('useGt', True))
         self.upload(batch)
-        # params fusedLhood: the generative decoder's candidates through the live-row log-likelihood head (a disc model: argument error)
+        # params fusedLhood: the generative decoder's candidates through the live-row log-likelihood head (a disc model: argument error);
+        # a model created with fusedLhood = 2 scores them over the prefix tree behind the same call
         call("vd_model_retrieve_lhood" if int(self.params.get('fusedLhood', 0) or 0) else "vd_model_retrieve", self.h)
         N, O = self._N, int(self.params.get('numOptions', 100))
         out = np.empty(N if useGt else (N, O), np.int32)

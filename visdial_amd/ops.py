@@ -86,6 +86,10 @@ FLAG_LIVE_PREFIX, LIVE_PREFIX_ROWS = 16, 128
 # VD_FLAG_STATE_ONLY (lstm_forward with gates=None): a forward pass no backward follows -- h and c are [2 x N x H] ping-pong buffers, step t
 # writes slot t & 1, the final state lies in slot (T - 1) & 1 and no gate value reaches memory
 FLAG_STATE_ONLY = 32
+# VD_FLAG_TREE (lstm_forward with gates=None and a [2 x T x N] tok_mask): a forest run level by level -- plane 0 of tok_mask is the mask
+# (non-zero = a node; the nodes of a step are a prefix of its rows), plane 1 the parent row of the step before (of h0 / c0 at step 0);
+# h and c are [T x N x H], forward only, exact fp32 only
+FLAG_TREE = 64
 
 
 def lstm_fwd_row_tile(N):
@@ -154,6 +158,9 @@ def lhood_sum(nll, act, n_act, T, rows, C, out, ldo, dst_off=0):
 # ---------------------------------------------------------------- LSTM
 def lstm_forward(xproj, Wh, gates, h, c, T, N, H, x_tstride, x_ld, tok_gather=None, tok_mask=None, h0=None, c0=None,
                  flags=0):
+    if int(flags) & FLAG_TREE and tok_mask is not None and tok_mask.numel() != 2 * T * N:
+        raise ValueError("lstm_forward: FLAG_TREE takes a two-plane tok_mask [2 x T x N] (mask, parent row); got %d elements for T=%d N=%d"
+                         % (tok_mask.numel(), T, N))
     call("vd_lstm_forward", _p(xproj, F32), x_tstride, x_ld, _p(tok_gather, I32), _p(tok_mask, I32), _p(Wh, F32),
          _p(h0, F32), _p(c0, F32), _p(gates, F32), _p(h, F32), _p(c, F32), T, N, H, int(flags), _stream())
 

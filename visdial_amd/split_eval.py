@@ -17,10 +17,20 @@ from . import utils
 
 class SplitEval(object):
     optionCacheRows = (0, 0)     # params optionCache: (rows the option LSTM ran, candidate rows) summed over the last retrieve / predict
+    # params fusedLhood = 2: nodes of the prefix trees, live (candidate, step) rows, rows the tree recurrence ran, (step, candidate) rows
+    # of the batches, summed over the last retrieve / predict
+    lhoodTreeStats = dict(nodes=0, live=0, executed=0, total=0)
 
     def _ranked(self, batch, tally):
         """retrieveBatch + the tally of the answer-encoding cache (params optionCache; decoder disc)"""
         ranks = np.asarray(self.retrieveBatch(batch))
+        if int(self.params.get('fusedLhood', 0) or 0) == 2:
+            from . import prefix_tree
+            st = prefix_tree.stats(batch['option_in'])
+            ex, tot = self.option_rows()
+            tally += [0] * (6 - len(tally))
+            for i, v in enumerate((st['nodes'], st['live'], ex, tot)):
+                tally[2 + i] += v
         if int(self.params.get('optionCache', 0) or 0):
             ex, tot = self.option_rows()
             tally[0] += ex
@@ -81,7 +91,8 @@ class SplitEval(object):
             batch, nxt = dataloader.getTestBatch(start, self.params, dtype)
             ranks[start - 1:nxt - 1] = self._ranked(batch, tally).reshape(-1, R)
             start = nxt
-        self.optionCacheRows = tuple(tally)
+        self.optionCacheRows = tuple(tally[:2])
+        self.lhoodTreeStats = dict(zip(('nodes', 'live', 'executed', 'total'), (tally + [0] * 4)[2:6]))
         print('\n%s - Retrieval:' % dtype)
         metrics = utils.processRanks(ranks)
         self._set_training(True)
@@ -100,7 +111,8 @@ class SplitEval(object):
             batch, nxt = dataloader.getTestBatch(start, self.params, dtype)
             ranks[start - 1:nxt - 1] = self._ranked(batch, tally).reshape(-1, R, O)
             start = nxt
-        self.optionCacheRows = tuple(tally)
+        self.optionCacheRows = tuple(tally[:2])
+        self.lhoodTreeStats = dict(zip(('nodes', 'live', 'executed', 'total'), (tally + [0] * 4)[2:6]))
         self._set_training(True)
         return self._rank_records(dataloader, dtype, ranks, dtype == 'test')
 
