@@ -116,15 +116,15 @@ struct BatchSlot {
   // the encoding depends on the tokens only); opt_uid[n * O + o] = its row among the opt.N unique rows, or null
   int32_t* opt_uid = nullptr;
   int opt_total = 0;           // N * O
-  // counting sort of the option tokens (the table gradient's row order), done on the copy stream at upload time: it depends on the
-  // batch alone, and inside the step it stood in front of the encoder backward in the side streams' in-order hardware queue
+  // counting sort of the option tokens (the table gradient's row order), done with the upload on the side lane: it depends on the
+  // batch alone, and inside the step it stood in front of the encoder backward on that in-order lane
   int32_t *opt_sort_off = nullptr, *opt_sort_perm = nullptr;
   // answer-encoding cache (OptionCache): the slot was resolved against the cache -- opt = the MISS rows only, opt_uid = table row of every
   // candidate; miss_keys [opt.N x To] wait for the step's commit, opt_host keeps the batch's rows for a second resolution
   bool cached = false;
   uint64_t cache_stamp = 0;
   std::vector<int32_t> miss_keys, opt_host;
-  hipEvent_t ready = nullptr;  // recorded on the copy stream when the upload has landed
+  hipEvent_t ready = nullptr;  // recorded on the side lane when the upload has landed
   hipEvent_t done = nullptr;   // recorded on the main stream behind the last reader of this slot
   bool used = false;      // a step has read this slot (done is recorded)
   bool uploaded = false;  // ready is recorded (an upload has been issued into this slot)
@@ -175,7 +175,7 @@ struct RowIndex {
 // Answer-encoding cache of the discriminative decoder (VD_OPTION_CACHE; include/visdial_hip.h at vd_model_retrieve).  A candidate's
 // encoding depends on its tokens, on To (trailing pads advance the state) and on the weights only, so while the weights stand still
 // the final h of every distinct (row, To) is kept in `table` [rows x H]; slot = RowIndex id.  The index flushes when To changes.
-//   * upload (copy stream, ahead of the step): resolves the N * O rows against the COMMITTED index; rows it does not hold are
+//   * upload (side lane, ahead of the step): resolves the N * O rows against the COMMITTED index; rows it does not hold are
 //     de-duplicated inside the batch and numbered count, count + 1, ... (the slot's miss_keys); nothing is inserted yet, so a batch
 //     that is replaced or never stepped leaves no entry behind
 //   * step: runs the state-only recurrence over the misses, copies their final h to table rows [count, count + misses) and only then
@@ -211,10 +211,12 @@ struct vd_model {
   float *W = nullptr, *G = nullptr, *M = nullptr, *V = nullptr;
   std::map<std::string, vdrt::DevBuf> ws;
   std::map<std::string, vdrt::DevBuf> ext_masks;
-  hipStream_t s_main = nullptr, s_enc = nullptr, s_img = nullptr, s_hist = nullptr, s_tab = nullptr, s_copy = nullptr;
+  // two lanes (runtime.hip vd_model_create): the throughput work on s_main, everything that runs beside it -- encoder chains, image
+  // prefetch / history branch, table-gradient chain, batch uploads -- on s_side, in the host's enqueue order
+  hipStream_t s_main = nullptr, s_side = nullptr;
   // parameter-gradient work of the nngraph encoders that nothing downstream in the backward pass waits for (image-attention
-  // weight gradients, the recurrences' weight / input gradients): middle priority = its own hardware queue beside the in-order
-  // queue of the other side streams (runtime.hip).  wg_active: the current backward uses it; wg_used: it holds un-joined work
+  // weight gradients, the recurrences' weight / input gradients): middle priority = its own hardware queue beside the side
+  // lane (runtime.hip).  wg_active: the current backward uses it; wg_used: it holds un-joined work
   hipStream_t s_wg = nullptr;
   bool wg_active = false, wg_used = false;
   std::vector<hipEvent_t> ev_pool;
@@ -311,7 +313,8 @@ inline int fork_stream(vd_model* m, hipStream_t from, hipStream_t side) {
   return VD_OK;
 }
 inline int join_stream(vd_model* m, hipStream_t side, hipStream_t to) { return fork_stream(m, side, to); }
-inline hipStream_t side_stream(vd_model* m, hipStream_t wanted, hipStream_t cur) { return m->streams ? wanted : cur; }
+// the side lane (`cur` itself with useStreams = 0).  A caller that already runs on it gets `cur` back, and its fork / join are no-ops
+inline hipStream_t side_stream(vd_model* m, hipStream_t cur) { return m->streams ? m->s_side : cur; }
 // the stream for off-chain parameter-gradient work enqueued after everything on `cur` so far (cur itself when the feature is off)
 inline int wg_fork(vd_model* m, hipStream_t cur, hipStream_t* out) {
   *out = cur;

@@ -77,8 +77,7 @@ struct Disc : Decoder {
     VD_CHECK_ARG(dedup ? NO <= NOfull : NO == NOfull, "decoder 'disc': %d option rows for %d x %d candidates", NO, N, O);
     const long H = m->p.rnnHiddenSize, E = m->p.embedSize, V = m->p.vocabSize;
     hipStream_t s = m->s_main;
-    hipStream_t se = side_stream(m, m->s_enc, s);
-    hipStream_t st = side_stream(m, m->s_tab, s);
+    hipStream_t sd = side_stream(m, s);   // encoder, then the table-gradient chain, in this function's enqueue order
     float *table, *gates, *h, *c, *scores, *loss_rows;
     VD_TRY(ws_get(m, "opt.table", (size_t)(V + 1) * 4 * H, &table));
     VD_TRY(ws_get(m, "opt.gates", (size_t)To * NO * 4 * H, &gates));
@@ -88,7 +87,7 @@ struct Disc : Decoder {
     VD_TRY(ws_get(m, "crit.loss_rows", (size_t)N, &loss_rows));
     float* Wopt = Wp(m, "opt.W");
     const int flags = m->flags;
-    VD_TRY(fork_stream(m, s, se));
+    VD_TRY(fork_stream(m, s, sd));
     float* enc_out = nullptr;
     VD_TRY(vd_gemm_nn(Wp(m, "embed"), E, Wopt, 4 * H, Wp(m, "opt.b"), table, 4 * H, (int)V + 1, (int)(4 * H), (int)E, 0, s));
     // bf16 pass at a throughput shape: COMPACT state (common.h) -- gates / da only as bf16 (in the first half of `gates`), the
@@ -112,10 +111,10 @@ struct Disc : Decoder {
     VD_HIP(hipEventRecord(m->ev_prof[1], s));
     {
       VdRange r("encoder forward");
-      VD_TRY(m->enc->forward(m, se, b, &enc_out));                                 // model.lua:297
-      VD_PROBE_REC(0, se);
+      VD_TRY(m->enc->forward(m, sd, b, &enc_out));                                 // model.lua:297
+      VD_PROBE_REC(0, sd);
     }
-    VD_TRY(join_stream(m, se, s));
+    VD_TRY(join_stream(m, sd, s));
     // criterion (+ nn.MM backward) in one kernel (model.lua:330-335)
     const float* optH = c16 ? h_last : h + (long)(To - 1) * NO * H;
     float *d_optH = nullptr, *d_enc = nullptr, *d_optH_full = nullptr;
@@ -140,31 +139,30 @@ struct Disc : Decoder {
     m->prof_valid = !only_forward;
     if (only_forward) return VD_OK;
     // decoder backward on the main stream, encoder backward beside it (model.lua:335-337)
-    VD_TRY(fork_stream(m, s, se));
+    VD_TRY(fork_stream(m, s, sd));
     float *dc, *dtab;
     int32_t* perm = b.opt_sort_perm;               // sorted at upload time (runtime.hip)
     VD_TRY(ws_get(m, "opt.dc", (size_t)NO * H, &dc));
     VD_TRY(ws_get(m, "opt.dtable", (size_t)(V + 1) * 4 * H, &dtab));
     VD_CHECK_ARG(perm, "decoder 'disc': the batch slot carries no option-token sort");
-    VD_TRY(fork_stream(m, s, st));
-    VD_TRY(vd_memset(dtab, 0, (V + 1) * 4 * H * 4, st));
+    VD_TRY(vd_memset(dtab, 0, (V + 1) * 4 * H * 4, sd));
     VD_HIP(hipEventRecord(m->ev_prof[2], s));
     // off-chain parameter-gradient work of the encoder on its own (middle-priority) stream = its own hardware queue in a bf16 pass
     // (the encoder chain is that step's critical path: 12.34 -> 12.02 ms, profiles/r03_experiments.txt section 21); in fp32 the step
-    // is work-conserving on the matrix pipe and it stays on the encoder stream.  Never joined into `se`: a wait there would be a
+    // is work-conserving on the matrix pipe and it stays on the side lane.  Never joined into `sd`: a wait there would be a
     // barrier packet in front of the table-gradient chain.
     m->wg_active = m->streams && m->s_wg && (flags & VD_FLAG_BF16) != 0;
     m->wg_used = false;
     auto enc_bwd = [&]() -> int {
       VdRange r("encoder backward");
-      VD_TRY(m->enc->backward(m, se, b, d_enc));
-      VD_PROBE_REC(1, se);
+      VD_TRY(m->enc->backward(m, sd, b, d_enc));
+      VD_PROBE_REC(1, sd);
       if (m->wg_used) VD_PROBE_REC(2, m->s_wg);
-      if (m->wg_used) {   // encoder tensors final = the chain on `se` AND the gradient work on s_wg
-        VD_TRY(fork_stream(m, se, m->s_wg));
+      if (m->wg_used) {   // encoder tensors final = the chain on `sd` AND the gradient work on s_wg
+        VD_TRY(fork_stream(m, sd, m->s_wg));
         VD_HIP(hipEventRecord(m->ev_enc_grads, m->s_wg));
       } else {
-        VD_HIP(hipEventRecord(m->ev_enc_grads, se));                                // encoder tensors final (data-parallel bucket 1)
+        VD_HIP(hipEventRecord(m->ev_enc_grads, sd));                                // encoder tensors final (data-parallel bucket 1)
       }
       m->enc_grads_recorded = true;
       return VD_OK;
@@ -175,14 +173,16 @@ struct Disc : Decoder {
       else VD_TRY(vd_lstm_backward(Wopt + E * 4 * H, gates, c, nullptr, nullptr, d_optH, nullptr, dc, nullptr, nullptr, nullptr, To, NO, (int)H, flags, s));
     }
     VD_HIP(hipEventRecord(m->ev_prof[3], s));
-    VD_TRY(enc_bwd());       // enqueued behind the option recurrence: it runs beside it on the encoder stream
-    // table gradient + its consumers beside the dWh contraction
+    VD_TRY(enc_bwd());       // enqueued behind the option recurrence: it runs beside it on the side lane
+    // table gradient + its consumers beside the dWh contraction.  This fork stays BEHIND the encoder backward's enqueue: the lane runs
+    // in order, so the HBM-bound row sum starts when the encoder chain has drained, not with the MFMA-bound dWh contraction, where it
+    // takes 2.9 ms instead of 0.7 and dWh 6.9 instead of 6.1 (profiles/r03_experiments.txt section 9)
     VdRange rwg("disc: table gradient + dWh");
-    VD_TRY(fork_stream(m, s, st));
-    if (c16) VD_TRY(vd_segment_rowsum_acc_bf16(gates16, 4 * H, b.opt.tok, perm, (long)To * NO, (int)(4 * H), dtab, 4 * H, st));
-    else VD_TRY(vd_segment_rowsum_acc(gates, 4 * H, b.opt.tok, perm, (long)To * NO, (int)(4 * H), dtab, 4 * H, st));
-    VD_TRY(vd_colsum_acc(dtab, 4 * H, (int)V + 1, (int)(4 * H), Gp(m, "opt.b"), st));
-    VD_TRY(vd_gemm_tn_acc(Wp(m, "embed"), E, dtab, 4 * H, Gp(m, "opt.W"), 4 * H, (int)E, (int)(4 * H), (int)V + 1, 0, st));
+    VD_TRY(fork_stream(m, s, sd));
+    if (c16) VD_TRY(vd_segment_rowsum_acc_bf16(gates16, 4 * H, b.opt.tok, perm, (long)To * NO, (int)(4 * H), dtab, 4 * H, sd));
+    else VD_TRY(vd_segment_rowsum_acc(gates, 4 * H, b.opt.tok, perm, (long)To * NO, (int)(4 * H), dtab, 4 * H, sd));
+    VD_TRY(vd_colsum_acc(dtab, 4 * H, (int)V + 1, (int)(4 * H), Gp(m, "opt.b"), sd));
+    VD_TRY(vd_gemm_tn_acc(Wp(m, "embed"), E, dtab, 4 * H, Gp(m, "opt.W"), 4 * H, (int)E, (int)(4 * H), (int)V + 1, 0, sd));
     VD_HIP(hipEventRecord(m->ev_prof[4], s));
     if (To > 1 && c16)
       VD_TRY(vd_gemm_tn_acc_bf16(h16, gates16 + (long)NO * 4 * H, Gp(m, "opt.W") + E * 4 * H, 4 * H, (int)H, (int)(4 * H), (To - 1) * NO, s));
@@ -190,14 +190,13 @@ struct Disc : Decoder {
       VD_TRY(vd_gemm_tn_acc(h, H, gates + (long)NO * 4 * H, 4 * H, Gp(m, "opt.W") + E * 4 * H, 4 * H, (int)H, (int)(4 * H), (To - 1) * NO,
                             flags & (VD_FLAG_BF16 | VD_FLAG_SPLIT9), s));
     VD_HIP(hipEventRecord(m->ev_prof[5], s));
-    // dEmb += dTable * Wx^T on the table stream, with float atomics: the SHARED embedding gradient has concurrent atomic
+    // dEmb += dTable * Wx^T behind the table gradient on the side lane, with float atomics: the SHARED embedding gradient has concurrent atomic
     // writers (the encoder's scatters), and the product is off the main stream's critical path this way
-    VD_TRY(vd_gemm_nt(dtab, 4 * H, Wopt, 4 * H, nullptr, Gp(m, "embed"), E, (int)V + 1, (int)E, (int)(4 * H), VD_ACT_NONE, 2, st));
-    VD_PROBE_REC(3, st);
-    VD_TRY(join_stream(m, se, s));
+    VD_TRY(vd_gemm_nt(dtab, 4 * H, Wopt, 4 * H, nullptr, Gp(m, "embed"), E, (int)V + 1, (int)E, (int)(4 * H), VD_ACT_NONE, 2, sd));
+    VD_PROBE_REC(3, sd);
+    VD_TRY(join_stream(m, sd, s));         // encoder backward and table-gradient chain: one lane, one event
     if (m->wg_used) VD_TRY(join_stream(m, m->s_wg, s));
     m->wg_active = m->wg_used = false;
-    VD_TRY(join_stream(m, st, s));
     VD_PROBE_REC(4, s);
     return VD_OK;
   }
@@ -216,7 +215,7 @@ struct Disc : Decoder {
     const int N = b.q.N, O = m->p.numOptions, NOfull = N * O, To = b.opt.T;
     const long H = m->p.rnnHiddenSize, E = m->p.embedSize, V = m->p.vocabSize;
     hipStream_t s = m->s_main;
-    hipStream_t se = side_stream(m, m->s_enc, s);
+    hipStream_t sd = side_stream(m, s);
     if (b.cache_stamp != oc.stamp) {   // flushed or stepped since the upload: resolve again (the copy out of the staging buffers has to land first)
       VD_HIP(hipEventSynchronize(b.ready));
       VD_TRY(option_cache_resolve(m, b, b.opt_host.data(), NOfull, To, s));
@@ -243,7 +242,7 @@ struct Disc : Decoder {
     VD_TRY(ws_get(m, "opt.scores", (size_t)N * O, &scores));
     VD_TRY(ws_get(m, "crit.loss_rows", (size_t)N, &loss_rows));
     VD_TRY(ws_get(m, "opt.h_full", (size_t)NOfull * H, &full));
-    VD_TRY(fork_stream(m, s, se));
+    VD_TRY(fork_stream(m, s, sd));
     if (U > 0) {
       VdRange r("disc: option LSTM forward (state only, cache misses)");
       float *table, *h, *c;
@@ -263,9 +262,9 @@ struct Disc : Decoder {
     float* enc_out = nullptr;
     {
       VdRange r("encoder forward");
-      VD_TRY(m->enc->forward(m, se, b, &enc_out));
+      VD_TRY(m->enc->forward(m, sd, b, &enc_out));
     }
-    VD_TRY(join_stream(m, se, s));
+    VD_TRY(join_stream(m, sd, s));
     VD_TRY(vd_embed_gather(oc.table, b.opt_uid, nullptr, full, NOfull, (int)H, 1.f, s));
     VD_TRY(vd_score_ce(full, enc_out, b.gt, scores, loss_rows, nullptr, nullptr, N, O, (int)H, 1.0f / N, s));
     VD_TRY(stage_loss(m, loss_rows, N, false, s));

@@ -9,7 +9,7 @@ namespace vdrt {
 struct Encoder {
   virtual ~Encoder() {}
   virtual void declare(vd_model* m) = 0;
-  // returns the encoder output [N x H] (a workspace buffer); everything is enqueued on `s` and library side streams
+  // returns the encoder output [N x H] (a workspace buffer); everything is enqueued on `s` and the library's side lane
   // that are joined back into `s` before returning
   virtual int forward(vd_model* m, hipStream_t s, BatchSlot& b, float** out) = 0;
   virtual int backward(vd_model* m, hipStream_t s, BatchSlot& b, const float* grad_out) = 0;
@@ -298,7 +298,7 @@ struct SANBlock {
   // per-image projection + this step's dropout masks: independent of the text branches -> own stream
   int prefetch(vd_model* m, hipStream_t s, BatchSlot& b, int N_) {
     N = N_;
-    hipStream_t si = side_stream(m, m->s_img, s);
+    hipStream_t si = side_stream(m, s);
     VD_TRY(fork_stream(m, s, si));
     VD_TRY(img_proj.forward(m, si, b.img, (long)b.B * S2, true, &pre));           // mn-att:74-78 (pre-dropout)
     VD_TRY(drop_mask(m, "img_tr", (size_t)N * S2 * H, 0.5f, si, &m1));
@@ -315,7 +315,7 @@ struct SANBlock {
     return VD_OK;
   }
   int forward(vd_model* m, hipStream_t s, const float* u0, float** y) {
-    VD_TRY(join_stream(m, side_stream(m, m->s_img, s), s));
+    VD_TRY(join_stream(m, side_stream(m, s), s));
     u_in.assign(L, nullptr); iqc.assign(L, nullptr); patt.assign(L, nullptr);
     const float* u = u0;
     for (int i = 0; i < L; ++i) {
@@ -490,7 +490,7 @@ struct LateFusion : Encoder {
   std::vector<SeqLSTM>* rnnLayers() override { return &rnn; }
   int forward(vd_model* m, hipStream_t s, BatchSlot& b, float** out) override {
     const int N = b.q.N, Tq = b.q.T, R = m->p.maxQuesCount;
-    hipStream_t sh = side_stream(m, m->s_hist, s);
+    hipStream_t sh = side_stream(m, s);
     const float* hh_last = nullptr;
     if (use_hist) {
       VD_TRY(fork_stream(m, s, sh));
@@ -535,7 +535,7 @@ struct LateFusion : Encoder {
     if (use_hist) need.push_back(true);
     std::vector<float*> g;
     VD_TRY(fuse.backward(m, s, grad_out, need, &g));
-    hipStream_t sh = side_stream(m, m->s_hist, s);
+    hipStream_t sh = side_stream(m, s);
     if (use_hist) {
       VD_TRY(fork_stream(m, s, sh));
       const bool prof = m->dec_name == "gen";
@@ -613,7 +613,7 @@ struct Hre : Encoder {
     const int N = b.q.N, Tq = b.q.T, Th = b.h.T, B = N / R;
     int32_t *rep, *to_rb, *to_n;
     VD_TRY(indices(m, N, &rep, &to_rb, &to_n));
-    hipStream_t sh = side_stream(m, m->s_hist, s);
+    hipStream_t sh = side_stream(m, s);
     VD_TRY(fork_stream(m, s, sh));
     if (HistWave::usable(b, hist)) {
       const float* last;
@@ -702,7 +702,7 @@ struct Hre : Encoder {
       dq = dqq;
       dh = dhh;
     }
-    hipStream_t sh = side_stream(m, m->s_hist, s);
+    hipStream_t sh = side_stream(m, s);
     VD_TRY(fork_stream(m, s, sh));
     if (HistWave::usable(b, hist)) {
       VD_TRY(wave.backward(m, sh, b, hist[0], hist[1], dh));

@@ -360,27 +360,23 @@ int vd_model_create(const vd_model_params* p, const char* encoder, const char* d
     }
     (void)hipMemset(*v, 0, off * sizeof(float));
   }
-  // throughput work (option LSTM, criterion, optimiser) at the LEAST priority, the latency-bound encoder chains and
-  // uploads at the GREATEST: their small workgroups take free slots ahead of the next big-kernel workgroup
+  // Two lanes.  s_main (LEAST priority) carries the throughput work: option LSTM, criterion, optimiser.  s_side (GREATEST) carries
+  // everything that runs beside it, in the host's enqueue order: the latency-bound encoder chains with their image prefetch / history
+  // branch, the table-gradient chain and the batch uploads.  Their small workgroups take free slots ahead of the next big-kernel
+  // workgroup.  The side work is ONE stream because its order is part of the schedule (profiles/r03_experiments.txt section 9): HIP gives
+  // every priority class its own pool of GPU_MAX_HW_QUEUES hardware queues, and packets of one queue start in submission order.  As four
+  // streams the side work ran in that order only where the four shared a queue (GPU_MAX_HW_QUEUES=1).  With a queue each, the side chains
+  // ran beside each other as well as beside the main stream (in round 3 the HBM-bound table-gradient row sum beside the MFMA-bound dWh
+  // contraction instead of behind the encoder backward), every option family took 5-7 % longer and the headline step 24.2 ms instead of
+  // 22.3 (profiles/side_lane.txt).  One stream is one queue at any setting the host process chose.
   int least = 0, greatest = 0;
   (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
   if (hipStreamCreateWithPriority(&m->s_main, hipStreamNonBlocking, least) != hipSuccess) return fail(VD_ERR_HIP);
-  for (hipStream_t* s : {&m->s_enc, &m->s_img, &m->s_copy})
-    if (hipStreamCreateWithPriority(s, hipStreamNonBlocking, greatest) != hipSuccess) return fail(VD_ERR_HIP);
-  // the table-gradient stream shares the `greatest` class (one hardware queue per priority class): on a queue of its own its
-  // HBM-bound row sum would start beside the MFMA-bound dWh contraction and cost 0.5 ms per step (profiles/r03_experiments.txt)
-  const int tab_prio = greatest;
-  if (hipStreamCreateWithPriority(&m->s_tab, hipStreamNonBlocking, tab_prio) != hipSuccess) return fail(VD_ERR_HIP);
+  if (hipStreamCreateWithPriority(&m->s_side, hipStreamNonBlocking, greatest) != hipSuccess) return fail(VD_ERR_HIP);
+  // off-chain parameter-gradient work of a bf16 pass: middle priority = a queue of its own (rt_core.h, profiles/r03_experiments.txt section 21)
   if (least - greatest >= 2 &&
       hipStreamCreateWithPriority(&m->s_wg, hipStreamNonBlocking, (least + greatest) / 2) != hipSuccess)
     return fail(VD_ERR_HIP);
-  // No encoder uses both side branches, so the history branch of lf-* / hre-* shares the image-branch stream: HIP
-  // multiplexes streams onto a handful of hardware queues (GPU_MAX_HW_QUEUES, default 4), and a sixth stream put the
-  // table-gradient stream on the main stream's queue (measured: +0.75 ms per headline step).  Hosts that own the
-  // process should go further and export GPU_MAX_HW_QUEUES=1 before HIP initialises (bench.py does): with every stream
-  // of the step multiplexed onto ONE hardware queue the cross-stream event waits resolve inside the command processor
-  // and the headline step is 0.75-1.0 ms (3-4 %) faster (profiles/r02_hw_queues.txt).
-  m->s_hist = m->s_img;
   m->ev_pool.resize(64);
   for (auto& e : m->ev_pool)
     if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(VD_ERR_HIP);
@@ -423,7 +419,7 @@ void vd_model_destroy(vd_model* m) {
   if (m->ev_updated) (void)hipEventDestroy(m->ev_updated);
   for (auto& e : m->ev_prof)
     if (e) (void)hipEventDestroy(e);
-  for (hipStream_t s : {m->s_main, m->s_enc, m->s_img, m->s_tab, m->s_copy, m->s_wg})
+  for (hipStream_t s : {m->s_main, m->s_side, m->s_wg})
     if (s) {
       (void)hipStreamDestroy(s);
     }
@@ -460,7 +456,7 @@ void* vd_model_stream(vd_model* m) { return m ? (void*)m->s_main : nullptr; }
 
 // Data-parallel gradient bucketing: the encoder's own tensors occupy the flat element range [lo, hi)
 // (everything between the shared embedding and the decoder's tensors).  Under a `disc` decoder they are final when
-// the encoder backward ends on its side stream, long before the option-LSTM backward does: a host makes its
+// the encoder backward ends on the side lane, long before the option-LSTM backward does: a host makes its
 // communication stream wait for that point and all-reduces the range underneath the rest of the step.
 int vd_model_encoder_range(const vd_model* m, int64_t* lo, int64_t* hi) {
   VD_CHECK_ARG(m && lo && hi, "vd_model_encoder_range: null");
@@ -552,7 +548,7 @@ int vd_model_set_dropout_mask(vd_model* m, const char* site, const uint8_t* host
 }
 
 // Upload a batch in the dataloader's layout (dataloader.lua:324-339,378-475) into the free slot, asynchronously on the
-// copy stream: it may be called while the previous step is still executing.  Host buffers are consumed before return
+// side lane: it may be called while the previous step is still executing.  Host buffers are consumed before return
 // (staged into pinned memory), the device copy completes in the background.  Which fields are read follows the
 // plug-in pair: hist / img_feat by the encoder name (opts.lua:54-67), options by `disc`, answer_in/out (training) and
 // option_in/out (retrieval) by `gen`; fields the pair does not use may be NULL.
@@ -565,8 +561,11 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
   // (decoder gen: answer_in/answer_out for training, option_in/option_out for retrieval, neither for generation)
   VdRange r("vd_model_upload_batch");
   BatchSlot& sl = m->slot[m->cur < 0 ? 0 : (m->cur ^ 1)];   // the slot the running step does not read
-  hipStream_t s = m->s_copy;
-  // the step that last read this slot may still be executing (the host runs ahead of the device)
+  // The side lane, behind whatever side work the host has enqueued for the running step: the prefetch of the pipelined loop follows that
+  // step's table-gradient chain.  (Its place matters: profiles/r03_experiments.txt section 23b.)
+  hipStream_t s = m->s_side;
+  // the step that last read this slot may still be executing (the host runs ahead of the device): `done` is a main-stream event of an
+  // EARLIER step call, so this wait holds up nothing on the lane that main is waiting for
   if (sl.used) VD_HIP(hipStreamWaitEvent(s, sl.done, 0));
   // ... and the previous upload INTO this slot may still be queued behind that wait, reading the slot's pinned staging
   // buffers: a host that runs two or more steps ahead without reading a loss (forward_backward loops, deferred loss)
@@ -641,7 +640,7 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
     }
     if (!dedup && !sl.cached) VD_TRY(upload_tokens(sl, sl.opt, "opt", hb->options, (int)NO, hb->To, false, s));   // [N x O x To] -> [To x N*O]
     sl.opt_sort_off = sl.opt_sort_perm = nullptr;
-    if (!sl.cached) {   // counting sort of the option tokens on the copy stream (the table gradient's row order depends on the batch alone)
+    if (!sl.cached) {   // counting sort of the option tokens behind the copies (the table gradient's row order depends on the batch alone)
       const long V1 = (long)m->p.vocabSize + 1, n = (long)sl.opt.T * sl.opt.N;
       int32_t* work;
       VD_TRY(dev_get(sl.bufs, "opt.sort_off", (size_t)(V1 + 1) * sizeof(int32_t), (void**)&sl.opt_sort_off));
@@ -870,7 +869,7 @@ int vd_model_option_rows(vd_model* m, int64_t* executed, int64_t* total) {
 
 int vd_model_synchronize(vd_model* m) {
   VD_CHECK_ARG(m, "vd_model_synchronize: null model");
-  for (hipStream_t s : {m->s_copy, m->s_enc, m->s_img, m->s_tab, m->s_wg, m->s_main})
+  for (hipStream_t s : {m->s_side, m->s_wg, m->s_main})
     if (s) VD_HIP(hipStreamSynchronize(s));
   return VD_OK;
 }
