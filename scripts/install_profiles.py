@@ -47,8 +47,8 @@ for f in ('_stream_timeline_bench.txt', '_hbm_kernels.txt', '_roctx_ranges.txt')
 
 txt = open(G + TAG + '_pmc_option_lstm_kernels.txt').read()
 S3 = 'SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES'
-KERN = {('fp32', 'fwd'): r'gemm_f32_glds_kernel<[^\n]*false, EpiLstmFwdT<0', ('fp32', 'bwd'): r'gemm_f32_glds_kernel<[^\n]*false, EpiLstmBwd<2,',
-        ('fp32', 'dWh'): r'gemm_f32_glds_kernel<[^\n]*true, EpiAtomic<4>', ('split9', 'fwd'): r'gemm_split_kernel<9, EpiLstmFwdT<0',
+KERN = {('fp32', 'fwd'): r'gemm_f32_glds_kernel<[^\n]*false, EpiLstmFwdT<false', ('fp32', 'bwd'): r'gemm_f32_glds_kernel<[^\n]*false, EpiLstmBwd<2,',
+        ('fp32', 'dWh'): r'gemm_f32_glds_kernel<[^\n]*true, EpiAtomic<4>', ('split9', 'fwd'): r'gemm_split_kernel<9, EpiLstmFwdT<false',
         ('split9', 'bwd'): r'gemm_split_kernel<9, EpiLstmBwd<4,', ('split9', 'dWh'): r'gemm_split_tn_kernel<9>'}
 ALG = {'fwd': 496, 'bwd': 660, 'dWh': 3900}     # algorithmic MB per launch
 

@@ -21,10 +21,23 @@ extern "C" int vd_gemm_tn_acc(const float* A, int64_t lda, const float* B, int64
 // ---------------------------------------------------------------------------
 // forward epilogue: acc[g] = (h_prev*Wh)[row, g*H + j]
 // ---------------------------------------------------------------------------
+// The cell update of hidden unit E (x, y, z, w: the four of a lane) -- the one definition, for the hand-scheduled epilogue (run) and the
+// distributed one (dist_store_t), which bind its operands.  PI .. PG = pre-activations of the gates (recurrent product + input projection),
+// CP = c_{t-1}; `km` = 0 for a pad row, else 1 (maskZero(): h = c = gates = 0).  Writes gi, gf, go, gg, c, h.
+#define VD_LSTM_CELL(E, PI, PF, PO, PG, CP)   \
+  gi.E = km * vd_sigmoid(PI);                 \
+  gf.E = km * vd_sigmoid(PF);                 \
+  go.E = km * vd_sigmoid(PO);                 \
+  gg.E = km * vd_tanh(PG);                    \
+  c.E = gf.E * (CP) + gi.E * gg.E;            \
+  h.E = go.E * vd_tanh(c.E);
+#define VD_XYZW(M) M(x) M(y) M(z) M(w)
+#define VD_ADD4(a, b) a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+
 // C16 (bf16 pass of the model-level runtime, configs[4]): COMPACT state -- `xproj` is a bf16 projection table (xld in bf16
 // elements), `gates` a bf16 buffer [N x 4H], `h_out` may be null (only the last step's fp32 h has a reader; the recurrence and the
 // weight gradient read the bf16 copy h16): 291 instead of 496 MB of epilogue traffic per launch at the headline shape
-template <int SEQ, bool C16 = false>
+template <bool C16 = false>
 struct EpiLstmFwdT {
   const float* xproj;  // dense: [N x 4H] rows (ld = xld); table mode: table base [V+1 x 4H]
   long xld;
@@ -36,67 +49,9 @@ struct EpiLstmFwdT {
   float* h_out;           // [N x H]
   int H;
   vd_bf16_bits* h16 = nullptr;   // nullable: bf16 copy of h_out (bf16 pass: operand of the weight-gradient contraction)
-  // SEQ = 1: compiler-scheduled epilogue (the encoder tick kernels: 3 spilled VGPRs in the persistent kernel at the 128-register cap,
-  // 12 with the hand-scheduled one below); 0: hand-scheduled (the throughput kernels)
-  // The four accumulator tiles are i,f,o,g of hidden units [j0, j0+32).  Each is staged through the wave's LDS
-  // scratch so that a lane ends up with 4 consecutive hidden units of one row: every global access of the cell
-  // update is a 16-byte one (8 lanes = one 128-byte segment of a row).
-  //
-  // Memory-level parallelism is scheduled by hand: a lane serves 4 rows (p = 0..3) and every row needs a dependent
-  // chain token id -> projection row -> math -> stores.  Left to the compiler this became 4 x (id load, wait, 5 row
-  // loads, wait, math, stores): 8 serialised round trips, about as long as the whole K loop of the tile (the
-  // workgroup's matrix pipe share sits idle meanwhile).  Here the 4 token / mask ids are fetched in ONE batch whose
-  // latency hides under the LDS transposes, and the row loads of p+1 are issued as soon as the loaded values of p
-  // have been folded into the pre-activations (one buffer of 20 VGPRs, reused), so they fly under the
-  // transcendental math and the stores of p.
-  // round-1 form: one row at a time, loads / waits / math / stores in the order the compiler picks
-  __device__ __forceinline__ void sequential(const f32x16 (&acc)[4], int row0, int vcol0, int lane, int M, float* scr) const {
-    // The four accumulator tiles are i,f,o,g of hidden units [j0, j0+32).  Each is staged through the
-    // wave's LDS scratch so that a lane ends up with 4 consecutive hidden units of one row: every global
-    // access of the cell update is then a 16-byte one (8 lanes = one 128-byte segment of a row).
-    const int j = (vcol0 >> 7) * 32 + (lane & 7) * 4;
-    float4 ai[4], af[4], ao[4], ag[4];
-    tile_to_rows(acc[0], scr, lane, ai);
-    tile_to_rows(acc[1], scr, lane, af);
-    tile_to_rows(acc[2], scr, lane, ao);
-    tile_to_rows(acc[3], scr, lane, ag);
-    VD_T(3);
-    if (j >= H) return;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int row = row0 + p * 8 + (lane >> 3);
-      if (row >= M) continue;
-      float4 gi, gf, go, gg, c, h;
-      if (tok_mask && tok_mask[row] == 0) {
-        gi = gf = go = gg = c = h = make_float4(0.f, 0.f, 0.f, 0.f);
-      } else {
-        const float* xr = xproj + (tok_gather ? (long)tok_gather[row] : (long)row) * xld + j;
-        const float4 xi = *reinterpret_cast<const float4*>(xr);
-        const float4 xf = *reinterpret_cast<const float4*>(xr + H);
-        const float4 xo = *reinterpret_cast<const float4*>(xr + 2 * H);
-        const float4 xg = *reinterpret_cast<const float4*>(xr + 3 * H);
-        float4 cp = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c_prev) cp = *reinterpret_cast<const float4*>(c_prev + (long)row * H + j);
-#define VD_CELL(E)                                        \
-        gi.E = vd_sigmoid(ai[p].E + xi.E);                \
-        gf.E = vd_sigmoid(af[p].E + xf.E);                \
-        go.E = vd_sigmoid(ao[p].E + xo.E);                \
-        gg.E = vd_tanh(ag[p].E + xg.E);                   \
-        c.E = gf.E * cp.E + gi.E * gg.E;                  \
-        h.E = go.E * vd_tanh(c.E);
-        VD_CELL(x) VD_CELL(y) VD_CELL(z) VD_CELL(w)
-#undef VD_CELL
-      }
-      float* gr = gates + (long)row * 4 * H + j;
-      *reinterpret_cast<float4*>(gr) = gi;
-      *reinterpret_cast<float4*>(gr + H) = gf;
-      *reinterpret_cast<float4*>(gr + 2 * H) = go;
-      *reinterpret_cast<float4*>(gr + 3 * H) = gg;
-      *reinterpret_cast<float4*>(c_out + (long)row * H + j) = c;
-      *reinterpret_cast<float4*>(h_out + (long)row * H + j) = h;
-      if (h16) vd_st4_bf16(h16 + (long)row * H + j, h);
-    }
-  }
+  // the arithmetics that have step kernels with this epilogue besides exact fp32 (lstm_step_fwd instantiates no others); the derived
+  // types below narrow them
+  static constexpr bool STEP_BF16 = true, STEP_SPLIT = true;
   // Split-K latency shapes (one 32-row tile, four waves each holding a K slice of it): the cell update DISTRIBUTED over the four waves.
   // Wave g takes row group g (8 rows x 32 hidden units, one row x 4 units per lane): it requests its operands (mask id, the four projection
   // pieces, c_{t-1}) right after the K loop -- the round trip hides under the cross-wave reduction through LDS (gemm_block) -- and does
@@ -109,16 +64,27 @@ struct EpiLstmFwdT {
   };
   __device__ __forceinline__ bool dist_ok() const { return true; }
   __device__ __forceinline__ void dist_load(DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
+    dist_load_t<false>(q, row0, vcol0, lane, grp, M, nullptr);
+  }
+  // TREE (EpiLstmFwdTree; tok_mask is set): c_{t-1} comes from row prow[row], from row 0 for a masked row
+  template <bool TREE>
+  __device__ __forceinline__ void dist_load_t(DOps& q, int row0, int vcol0, int lane, int grp, int M, const int* prow) const {
     const int j = (vcol0 >> 7) * 32 + (lane & 7) * 4;
     const int row = row0 + grp * 8 + (lane >> 3);
     const int rc = row < M ? row : M - 1;
-    q.keep = tok_mask ? (tok_mask[rc] != 0) : 1;
+    int pr = rc;
+    if constexpr (TREE) {
+      q.keep = tok_mask[rc] != 0;
+      pr = q.keep ? prow[rc] : 0;
+    } else {
+      q.keep = tok_mask ? (tok_mask[rc] != 0) : 1;
+    }
     const float* xr = xproj + (tok_gather ? (long)tok_gather[rc] : (long)rc) * xld + j;
     q.x[0] = *reinterpret_cast<const float4*>(xr);
     q.x[1] = *reinterpret_cast<const float4*>(xr + H);
     q.x[2] = *reinterpret_cast<const float4*>(xr + 2 * H);
     q.x[3] = *reinterpret_cast<const float4*>(xr + 3 * H);
-    q.cp = c_prev ? *reinterpret_cast<const float4*>(c_prev + (long)rc * H + j) : make_float4(0.f, 0.f, 0.f, 0.f);
+    q.cp = c_prev ? *reinterpret_cast<const float4*>(c_prev + (long)pr * H + j) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
   // a[g] = the reduced pre-activation sums of gate g for this lane's (row, 4 hidden units)
   __device__ __forceinline__ void dist_store(const float4 (&a)[4], const DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
@@ -130,17 +96,11 @@ struct EpiLstmFwdT {
     const int j = (vcol0 >> 7) * 32 + (lane & 7) * 4;
     const int row = row0 + grp * 8 + (lane >> 3);
     if (row >= M || j >= H) return;
-    const float km = q.keep ? 1.f : 0.f;  // maskZero(): h = c = gates = 0 for pad rows
+    const float km = q.keep ? 1.f : 0.f;
     float4 gi, gf, go, gg, c, h;
-#define VD_CELLD(E)                                   \
-    gi.E = km * vd_sigmoid(a[0].E + q.x[0].E);        \
-    gf.E = km * vd_sigmoid(a[1].E + q.x[1].E);        \
-    go.E = km * vd_sigmoid(a[2].E + q.x[2].E);        \
-    gg.E = km * vd_tanh(a[3].E + q.x[3].E);           \
-    c.E = gf.E * q.cp.E + gi.E * gg.E;                \
-    h.E = go.E * vd_tanh(c.E);
-    VD_CELLD(x) VD_CELLD(y) VD_CELLD(z) VD_CELLD(w)
-#undef VD_CELLD
+#define VD_CELL(E) VD_LSTM_CELL(E, a[0].E + q.x[0].E, a[1].E + q.x[1].E, a[2].E + q.x[2].E, a[3].E + q.x[3].E, q.cp.E)
+    VD_XYZW(VD_CELL)
+#undef VD_CELL
     if constexpr (GATES) {
     float* gr = gates + (long)row * 4 * H + j;
     *reinterpret_cast<float4*>(gr) = gi;
@@ -183,15 +143,23 @@ struct EpiLstmFwdT {
                                              int Nv, float* scr, const Pre* pre = nullptr) const {
     run<true>(acc, row0, vcol0, lane, M, Nv, scr, pre);
   }
+  // The four accumulator tiles are i,f,o,g of hidden units [j0, j0+32).  Each is staged through the wave's LDS
+  // scratch so that a lane ends up with 4 consecutive hidden units of one row: every global access of the cell
+  // update is a 16-byte one (8 lanes = one 128-byte segment of a row).
+  //
+  // Memory-level parallelism is scheduled by hand: a lane serves 4 rows (p = 0..3) and every row needs a dependent
+  // chain token id -> projection row -> math -> stores.  Left to the compiler this became 4 x (id load, wait, 5 row
+  // loads, wait, math, stores): 8 serialised round trips, about as long as the whole K loop of the tile (the
+  // workgroup's matrix pipe share sits idle meanwhile).  Here the 4 token / mask ids are fetched in ONE batch whose
+  // latency hides under the LDS transposes, and the row loads of p+1 are issued as soon as the loaded values of p
+  // have been folded into the pre-activations (one buffer of 20 VGPRs, reused), so they fly under the
+  // transcendental math and the stores of p.
+  // GATES = false (EpiLstmFwdState, EpiLstmFwdTree): the activations stay in registers, only c and h are stored.
   // TREE (EpiLstmFwdTree): c_{t-1} of row r is read from row prow[r] (row 0 for a masked row) instead of row r.  The index of row group
   // p + 1 is requested together with the operands of group p -- one register, a whole group ahead of the load that needs it
   template <bool GATES, bool TREE = false>
   __device__ __forceinline__ void run(const f32x16 (&acc)[4], int row0, int vcol0, int lane, int M,
                                       int /*Nv*/, float* scr, const Pre* pre, const int* prow = nullptr) const {
-    if constexpr (SEQ == 1) {
-      sequential(acc, row0, vcol0, lane, M, scr);
-      return;
-    }
     const int j = (vcol0 >> 7) * 32 + (lane & 7) * 4;  // < H: H % 32 == 0 and vcol0 < 4H
     const int rl = lane >> 3;
     int rowc[4], tk[4], keep[4];
@@ -283,10 +251,7 @@ struct EpiLstmFwdT {
         for (int gk = 0; gk < 4; ++gk) x[gk] = vd_bf16x4_unpack(xs[p & 1][gk]);
         cp = cs[p & 1];
       }
-      pi.x += x[0].x; pi.y += x[0].y; pi.z += x[0].z; pi.w += x[0].w;
-      pf.x += x[1].x; pf.y += x[1].y; pf.z += x[1].z; pf.w += x[1].w;
-      po.x += x[2].x; po.y += x[2].y; po.z += x[2].z; po.w += x[2].w;
-      pg.x += x[3].x; pg.y += x[3].y; pg.z += x[3].z; pg.w += x[3].w;
+      VD_ADD4(pi, x[0]) VD_ADD4(pf, x[1]) VD_ADD4(po, x[2]) VD_ADD4(pg, x[3])
       const float4 cq = cp;
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (C16) {
@@ -295,16 +260,10 @@ struct EpiLstmFwdT {
         if (p + 1 < 4) issue(p + 1);  // in flight under the math and stores below
       }
       __builtin_amdgcn_sched_barrier(0);
-      const float km = keep[p] != 0 ? 1.f : 0.f;  // maskZero(): h = c = gates = 0 for pad rows
+      const float km = keep[p] != 0 ? 1.f : 0.f;
       float4 gi, gf, go, gg, c, h;
-#define VD_CELL(E)                                  \
-      gi.E = km * vd_sigmoid(pi.E);                 \
-      gf.E = km * vd_sigmoid(pf.E);                 \
-      go.E = km * vd_sigmoid(po.E);                 \
-      gg.E = km * vd_tanh(pg.E);                    \
-      c.E = gf.E * cq.E + gi.E * gg.E;              \
-      h.E = go.E * vd_tanh(c.E);
-      VD_CELL(x) VD_CELL(y) VD_CELL(z) VD_CELL(w)
+#define VD_CELL(E) VD_LSTM_CELL(E, pi.E, pf.E, po.E, pg.E, cq.E)
+      VD_XYZW(VD_CELL)
 #undef VD_CELL
       const int row = row0 + p * 8 + rl;
       if (row < M) {
@@ -343,11 +302,12 @@ struct EpiLstmFwdT {
   }
 };
 
-using EpiLstmFwd = EpiLstmFwdT<0>;
+using EpiLstmFwd = EpiLstmFwdT<>;
 // VD_FLAG_LIVE_PREFIX: the same epilogue, plus the row-tile predicate of gemm_core.h (EpiDeadOf).  The caller promises that the rows with
 // tok_mask != 0 are a prefix of the step's rows, so a tile whose FIRST row is pad holds no live row.  A type of its own, so that the step
 // kernels without the flag keep their instantiations (and their device code) as they are.
 struct EpiLstmFwdLive : EpiLstmFwd {
+  static constexpr bool STEP_BF16 = false, STEP_SPLIT = false;
   static constexpr bool HAS_DEAD = true;
   __device__ __forceinline__ bool dead(int row_base, int /*BM*/) const { return tok_mask[row_base] == 0; }   // row_base < M: the tile was launched
 };
@@ -356,6 +316,7 @@ struct EpiLstmFwdLive : EpiLstmFwd {
 // registers and writes c and h only (4 KB instead of 12 KB per row and step at H = 512).  `gates` is null.  A type of its own for the same
 // reason as EpiLstmFwdLive: the saving step kernels keep their instantiations.
 struct EpiLstmFwdState : EpiLstmFwd {
+  static constexpr bool STEP_BF16 = false;   // (the bf16 recurrence reads the saved bf16 copy of h)
   __device__ __forceinline__ void dist_store(const float4 (&a)[4], const DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
     dist_store_t<false>(a, q, row0, vcol0, lane, grp, M);
   }
@@ -373,6 +334,7 @@ struct EpiLstmFwdState : EpiLstmFwd {
 // other step kernels keep their instantiations.
 struct EpiLstmFwdTree : EpiLstmFwd {
   const int* parent;   // [N] rows of the previous step's state (plane 1 of tok_mask)
+  static constexpr bool STEP_BF16 = false, STEP_SPLIT = false;
   static constexpr bool HAS_DEAD = true;
   static constexpr bool HAS_AROWS = true;
   __device__ __forceinline__ bool dead(int row_base, int /*BM*/) const { return tok_mask[row_base] == 0; }
@@ -382,17 +344,7 @@ struct EpiLstmFwdTree : EpiLstmFwd {
     return m != 0 ? q : 0;
   }
   __device__ __forceinline__ void dist_load(DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
-    const int j = (vcol0 >> 7) * 32 + (lane & 7) * 4;
-    const int row = row0 + grp * 8 + (lane >> 3);
-    const int rc = row < M ? row : M - 1;
-    q.keep = tok_mask[rc] != 0;
-    const int pr = q.keep ? parent[rc] : 0;
-    const float* xr = xproj + (tok_gather ? (long)tok_gather[rc] : (long)rc) * xld + j;
-    q.x[0] = *reinterpret_cast<const float4*>(xr);
-    q.x[1] = *reinterpret_cast<const float4*>(xr + H);
-    q.x[2] = *reinterpret_cast<const float4*>(xr + 2 * H);
-    q.x[3] = *reinterpret_cast<const float4*>(xr + 3 * H);
-    q.cp = c_prev ? *reinterpret_cast<const float4*>(c_prev + (long)pr * H + j) : make_float4(0.f, 0.f, 0.f, 0.f);
+    dist_load_t<true>(q, row0, vcol0, lane, grp, M, parent);
   }
   __device__ __forceinline__ void dist_store(const float4 (&a)[4], const DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
     dist_store_t<false>(a, q, row0, vcol0, lane, grp, M);
@@ -422,6 +374,30 @@ struct SrcRowTree {
 //   dc_next <- dc*f
 // da_t overwrites the saved gates of step t in place.
 // ---------------------------------------------------------------------------
+// The gate gradients of hidden unit E -- the one definition, for the hand-scheduled epilogue (operator()) and the distributed one
+// (dist_store).  G[0..3] = the saved gates i, f, o, g; CT = c_t, CP = c_{t-1}, DCV = dc_next, `dh` = the summed incoming gradient.
+// Writes ai, af, ao, ag (da_t) and dn (dc for step t - 1).
+// LTR: the two forms had drifted apart in how they associate the sigmoid derivative -- the distributed one multiplies left to right,
+// (d * g) * i * (1 - i), the hand-scheduled one d * g * (i (1 - i)) -- and each keeps its rounding here (a compile-time constant).
+#define VD_LSTM_GRAD(E, G, CT, CP, DCV, LTR)                                                                   \
+  {                                                                                                            \
+    float gi_ = G[0].E, gf_ = G[1].E, go_ = G[2].E;                                                            \
+    float pi_ = 0.f, pf_ = 0.f, po_ = 0.f;   /* the sigmoid derivatives s (1 - s) */                           \
+    if constexpr (!(LTR)) pi_ = gi_ * (1.f - gi_), pf_ = gf_ * (1.f - gf_), po_ = go_ * (1.f - go_);           \
+    if constexpr (C16) {   /* stored s <= 1/2 as s, s > 1/2 as s - 1 (see the forward epilogue) */             \
+      pi_ = gi_ < 0.f ? (1.f + gi_) * -gi_ : pi_;  gi_ = gi_ < 0.f ? 1.f + gi_ : gi_;                          \
+      pf_ = gf_ < 0.f ? (1.f + gf_) * -gf_ : pf_;  gf_ = gf_ < 0.f ? 1.f + gf_ : gf_;                          \
+      po_ = go_ < 0.f ? (1.f + go_) * -go_ : po_;  go_ = go_ < 0.f ? 1.f + go_ : go_;                          \
+    }                                                                                                          \
+    const float tc = vd_tanh(CT.E);                                                                            \
+    const float d = DCV.E + dh.E * go_ * (1.f - tc * tc);                                                      \
+    ai.E = LTR ? d * G[3].E * gi_ * (1.f - gi_) : d * G[3].E * pi_;                                            \
+    af.E = LTR ? d * CP.E * gf_ * (1.f - gf_) : d * CP.E * pf_;                                                \
+    ao.E = LTR ? dh.E * tc * go_ * (1.f - go_) : dh.E * tc * po_;                                              \
+    ag.E = d * gi_ * (1.f - G[3].E * G[3].E);                                                                  \
+    dn.E = d * gf_;                                                                                            \
+  }
+
 // BATCH = slots whose loads are issued together before any is consumed (1 or 2; see the comment inside).
 // TWO = false: the caller guarantees at most ONE incoming-gradient operand (dh_b == nullptr: every step but the last of a
 // recurrence).  The second operand is fetched inside the consume phase, and the s_waitcnt behind that (uniformly skipped) load
@@ -444,10 +420,9 @@ struct EpiLstmBwd {
   // the compiler the slots ran back to back, each behind its own s_waitcnt vmcnt(0) (plus one more round trip per
   // optional dh operand): 8-24 serialised round trips per tile.  Here every operand of a slot (optional ones included)
   // is requested in one batch, and with BATCH = 2 the loads of TWO slots are issued before any of them is consumed
-  // (half the round trips).  BATCH = 2 needs ~140 VGPRs next to the second accumulator tile of the 128x64
-  // throughput shape (it spills at the 128-register cap), so that shape has two builds: <=128 VGPRs with BATCH = 1
-  // (a latency-shape workgroup of another stream still fits beside three of these on a SIMD) and <=168 VGPRs with
-  // BATCH = 2; the single-tile latency shapes (NT = 1) fit BATCH = 2 inside 128.
+  // (half the round trips).  BATCH = 2 needs ~140 VGPRs next to the second accumulator tile of the 128x64 throughput
+  // shape (it spills at the 128-register cap), so that shape takes BATCH = 1 where a step may have two incoming operands
+  // and BATCH = 2 only with TWO = false (lstm_step_bwd); the single-tile latency shapes (NT = 1) fit BATCH = 2 inside 128.
   // split-K latency shape (NT = 1: a 32 x 32 tile, four K-slice waves): the gate gradients DISTRIBUTED over the four waves like the forward
   // cell update (EpiLstmFwdT::dist_load): wave g finishes rows g*8 .. g*8+7, one (row, 4 hidden units) slot per lane, ONE round trip
   static constexpr bool HAS_DIST = NT == 1 && !C16;
@@ -478,19 +453,9 @@ struct EpiLstmBwd {
     if (row >= M || j >= H) return;
     float4 dh = a[0], ai, af, ao, ag, dn;
     dh.x += q.dha.x + q.dhb.x; dh.y += q.dha.y + q.dhb.y; dh.z += q.dha.z + q.dhb.z; dh.w += q.dha.w + q.dhb.w;
-#define VD_CELLBD(E)                                                      \
-    {                                                                     \
-      const float gi_ = q.g[0].E, gf_ = q.g[1].E, go_ = q.g[2].E;         \
-      const float tc = vd_tanh(q.ct.E);                                   \
-      const float d = q.dcv.E + dh.E * go_ * (1.f - tc * tc);             \
-      ai.E = d * q.g[3].E * gi_ * (1.f - gi_);                            \
-      af.E = d * q.cp.E * gf_ * (1.f - gf_);                              \
-      ao.E = dh.E * tc * go_ * (1.f - go_);                               \
-      ag.E = d * gi_ * (1.f - q.g[3].E * q.g[3].E);                       \
-      dn.E = d * gf_;                                                     \
-    }
-    VD_CELLBD(x) VD_CELLBD(y) VD_CELLBD(z) VD_CELLBD(w)
-#undef VD_CELLBD
+#define VD_GRAD(E) VD_LSTM_GRAD(E, q.g, q.ct, q.cp, q.dcv, true)
+    VD_XYZW(VD_GRAD)
+#undef VD_GRAD
     float* gr = gates + (long)row * 4 * H + j;
     *reinterpret_cast<float4*>(gr) = ai;
     *reinterpret_cast<float4*>(gr + H) = af;
@@ -565,34 +530,18 @@ struct EpiLstmBwd {
             for (int gk = 0; gk < 4; ++gk) C.g[gk] = vd_bf16x4_unpack(C.g16[gk]);
           }
           float4 dh = d4[pp + q];
-          dh.x += C.dhx.x; dh.y += C.dhx.y; dh.z += C.dhx.z; dh.w += C.dhx.w;
+          VD_ADD4(dh, C.dhx)
           const int row = row0 + (pp + q) * 8 + rl;
           if constexpr (TWO) {
             if (two_dh) {
               const float4 t = vd_buf_ld4(R.dh2, o4[q], 0);
-              dh.x += t.x; dh.y += t.y; dh.z += t.z; dh.w += t.w;
+              VD_ADD4(dh, t)
             }
           }
           float4 ai, af, ao, ag, dn;
-#define VD_CELLB(E)                                                       \
-          {                                                               \
-            float gi_ = C.g[0].E, gf_ = C.g[1].E, go_ = C.g[2].E;         \
-            float pi_ = gi_ * (1.f - gi_), pf_ = gf_ * (1.f - gf_), po_ = go_ * (1.f - go_);   \
-            if constexpr (C16) {   /* stored s <= 1/2 as s, s > 1/2 as s - 1 (see the forward epilogue) */   \
-              pi_ = gi_ < 0.f ? (1.f + gi_) * -gi_ : pi_;  gi_ = gi_ < 0.f ? 1.f + gi_ : gi_;   \
-              pf_ = gf_ < 0.f ? (1.f + gf_) * -gf_ : pf_;  gf_ = gf_ < 0.f ? 1.f + gf_ : gf_;   \
-              po_ = go_ < 0.f ? (1.f + go_) * -go_ : po_;  go_ = go_ < 0.f ? 1.f + go_ : go_;   \
-            }                                                             \
-            const float tc = vd_tanh(C.ct.E);                             \
-            const float d = C.dcv.E + dh.E * go_ * (1.f - tc * tc);       \
-            ai.E = d * C.g[3].E * pi_;                                    \
-            af.E = d * C.cp.E * pf_;                                      \
-            ao.E = dh.E * tc * po_;                                       \
-            ag.E = d * gi_ * (1.f - C.g[3].E * C.g[3].E);                 \
-            dn.E = d * gf_;                                               \
-          }
-          VD_CELLB(x) VD_CELLB(y) VD_CELLB(z) VD_CELLB(w)
-#undef VD_CELLB
+#define VD_GRAD(E) VD_LSTM_GRAD(E, C.g, C.ct, C.cp, C.dcv, false)
+          VD_XYZW(VD_GRAD)
+#undef VD_GRAD
           if (row < M && j < N) {
             // (row < M and j < N here: the clamped offsets of the loads are the true ones)
             if constexpr (C16) {
@@ -687,67 +636,122 @@ static_assert(VD_LIVE_PREFIX_ROWS <= 256 && VD_LIVE_PREFIX_ROWS % CfgF9::BM == 0
                   CfgF9::BM == VD_LSTM_FWD_TILE_BIG && CfgFwdSmallA::BM == VD_LSTM_FWD_TILE_SMALL,
               "VD_LIVE_PREFIX_ROWS is a multiple of every forward step kernel's row tile; paths.h vd_lstm_fwd_row_tile names them");
 
-template <class Epi>
-static int lstm_step_fwd(const float* h_prev, const float* Wh, int N, int H, int K, const Epi& epi,
-                         hipStream_t s) {
-  SrcRow a{h_prev, H};
-  SrcKGate4 b{Wh, 4L * H, H};
-  if (N >= VD_THROUGHPUT_ROWS) return launch_gemm<CfgF9>(N, 4 * H, K, 1, a, b, epi, s);   // (throughput shapes normally take the LDS-DMA drivers)
-  return launch_gemm<CfgFwdSmallA>(N, 4 * H, K, 1, a, b, epi, s);
-}
-
-// VD_FLAG_TREE: the same two kernels with h_{t-1} gathered through the parent list (same tiles, same K order)
-static int lstm_step_fwd_tree(const float* h_prev, const float* Wh, int N, int H, const EpiLstmFwdTree& epi, hipStream_t s) {
-  SrcRowTree a{h_prev, H, epi.tok_mask, epi.parent};
-  SrcKGate4 b{Wh, 4L * H, H};
-  if (N >= VD_THROUGHPUT_ROWS) return launch_gemm<CfgF9>(N, 4 * H, H, 1, a, b, epi, s);
-  return launch_gemm<CfgFwdSmallA>(N, 4 * H, H, 1, a, b, epi, s);
-}
-
-// one backward step with the kernels vd_lstm_backward chose for the pass: the exact split (split = products per step, W3 the weight
-// planes), bf16 operands (da16 = this step's shadow), or fp32
-static int lstm_step_bwd(const float* da_next, const float* Wh, int N, int H, int K, const float* dh_a,
-                         const float* dh_b, float* gates, const float* c_t, const float* c_prev, float* dc,
-                         int dc_first, hipStream_t s, int split = 0, const vd_bf16_bits* W3 = nullptr, vd_bf16_bits* da16 = nullptr,
-                         const vd_bf16_bits* da16_next = nullptr, const vd_bf16_bits* Wh16 = nullptr) {
-  SrcRow a{da_next, 4L * H};
-  SrcRow b{Wh, 4L * H};  // B[k][n] = Wh[n][k]
-  if (split && K > 0 && !(dh_a && dh_b)) {   // exact-operand split: da_{t+1} stays fp32 in memory, Wh as three bf16 planes
-    EpiLstmBwd<4, 2, false> e{dh_a, dh_b, gates, c_t, c_prev, dc, dc_first, H};   // 128 x 128 tiles: half the A re-reads of the fp32 kernel's 128 x 64
-    if (split == 9) return launch_gemm_split<9>(N, H, K, da_next, 4L * H, W3, 4L * H, 4L * H * H, e, s);
-    if (split == 6) return launch_gemm_split<6>(N, H, K, da_next, 4L * H, W3, 4L * H, 4L * H * H, e, s);
-    return launch_gemm_split<3>(N, H, K, da_next, 4L * H, W3, 4L * H, 4L * H * H, e, s);
+// The step kernels' copies of the recurrent weights, made once per pass in the stream's scratch: [4H x H] floats for the forward pass's
+// gate-interleaved transpose (the backward pass multiplies by Wh as it lies and leaves them alone), and behind them EITHER the three bf16
+// planes of the exact split OR one bf16 copy of the same matrix.
+struct LstmWeights {
+  const float* WhT = nullptr;         // forward: wh_gate_transpose_kernel
+  const vd_bf16_bits* W3 = nullptr;   // split: planes hi / mid / lo, 4 H^2 elements apart
+  const vd_bf16_bits* W16 = nullptr;  // bf16
+};
+static int lstm_weights(const float* Wh, int H, bool transpose, int split, bool bf16, hipStream_t s, LstmWeights* w) {
+  *w = LstmWeights{};
+  if (!transpose && !split && !bf16) return VD_OK;
+  const size_t n = (size_t)4 * H * H;
+  VdStreamScratch scr;
+  if (int rc = vd_stream_scratch(s, n * (split ? 10 : bf16 ? 6 : 4), 0, &scr)) return rc;
+  const float* src = Wh;
+  if (transpose) {
+    hipLaunchKernelGGL(wh_gate_transpose_kernel, dim3(4 * H / 32, H / 32), dim3(256), 0, s, Wh, scr.wht, H);
+    VD_LAUNCH_CHECK();
+    src = w->WhT = scr.wht;
   }
-  if (da16 && K > 0) {
-    EpiLstmBwd<2> e{dh_a, dh_b, gates, c_t, c_prev, dc, dc_first, H, da16};
+  vd_bf16_bits* low = reinterpret_cast<vd_bf16_bits*>(scr.wht + n);
+  if (split) {
+    if (int rc = weights_to_bf16x3(src, low, (long)n, s)) return rc;
+    w->W3 = low;
+  } else if (bf16) {
+    if (int rc = weights_to_bf16(src, low, (long)n, s)) return rc;
+    w->W16 = low;
+  }
+  return VD_OK;
+}
+
+// what vd_lstm_forward chose for the pass: bf16 operands, the exact-operand split (split_core.h) on the fp32 LDS-DMA pipeline's shapes,
+// that pipeline, or the generic kernel.  All but the last multiply by the transposed copy of Wh.
+struct LstmFwdPlan {
+  int N, H;
+  const float* Wh;
+  bool bf16, glds;
+  int split;                 // products per step (9 / 6 / 3), 0 = none
+  LstmWeights w;
+  const vd_bf16_bits* h16;   // bf16: the shadow of h [T x N x H] that the steps write and the next step reads
+};
+
+// One forward step.  THE place where a step's kernel is chosen, for every epilogue: the first rung that applies of
+//   first step without h0 (no recurrent product) -> generic kernel, K = 0
+//   bf16, t > 0 -> LDS-DMA pipeline over bf16 rows | bf16, h0 (fp32 rows) -> generic bf16 kernel
+//   split -> split_core.h | LDS-DMA pipeline | generic kernel
+// Epi::STEP_BF16 / STEP_SPLIT say at compile time which arithmetics an epilogue type has step kernels for: no others are instantiated.
+template <class Epi>
+static int lstm_step_fwd(const LstmFwdPlan& P, int t, const float* h_prev, const Epi& epi, hipStream_t s) {
+  const int N = P.N, H = P.H;
+  if (h_prev) {
+    if constexpr (Epi::STEP_BF16) {
+      if (P.bf16 && t > 0)   // the shadow of h_{t-1} and the bf16 copy of WhT as they lie in memory; K counts bf16 pairs
+        return launch_gemm_glds<CfgF9bf16, false>(N, 4 * H, H / 2, 1, reinterpret_cast<const float*>(P.h16 + (long)(t - 1) * N * H), (long)H / 2,
+                                                  reinterpret_cast<const float*>(P.w.W16), (long)H / 2, epi, s);
+      if (P.bf16) return launch_gemm<CfgFbf16>(N, 4 * H, H, 1, SrcRow{h_prev, H}, SrcRow{P.w.WhT, H}, epi, s);
+    }
+    if constexpr (Epi::STEP_SPLIT) {
+      if (P.split) return launch_gemm_split(P.split, N, 4 * H, H, h_prev, (long)H, P.w.W3, (long)H, 4L * H * H, epi, s);
+    }
+    if (P.glds) return launch_gemm_glds<CfgF9, false>(N, 4 * H, H, 1, h_prev, (long)H, P.w.WhT, (long)H, epi, s);
+  }
+  // (throughput shapes normally take the LDS-DMA drivers)
+  auto generic = [&](auto a) {
+    SrcKGate4 b{P.Wh, 4L * H, H};
+    if (N >= VD_THROUGHPUT_ROWS) return launch_gemm<CfgF9>(N, 4 * H, h_prev ? H : 0, 1, a, b, epi, s);
+    return launch_gemm<CfgFwdSmallA>(N, 4 * H, h_prev ? H : 0, 1, a, b, epi, s);
+  };
+  if constexpr (EpiARowsOf<Epi>::value) {   // VD_FLAG_TREE: h_{t-1} gathered through the parent list (same tiles, same K order)
+    if (h_prev) return generic(SrcRowTree{h_prev, H, epi.tok_mask, epi.parent});
+  }
+  return generic(SrcRow{h_prev, H});
+}
+
+// what vd_lstm_backward chose for the pass: the exact split (W3 = the planes of Wh), bf16 operands (W16, and the steps write the bf16
+// shadow of da), or fp32
+struct LstmBwdPlan {
+  int N, H;
+  const float* Wh;
+  int split;             // products per step (9 / 6 / 3), 0 = none
+  LstmWeights w;
+  vd_bf16_bits* da16;    // bf16: base of the da shadow [T x N x 4H]
+};
+template <class E>
+static E lstm_bwd_epi(const EpiLstmBwd<2>& e) {
+  return E{e.dh_a, e.dh_b, e.gates, e.c_t, e.c_prev, e.dc, e.dc_first, e.H, e.da16};
+}
+
+// One backward step with the kernels of the pass.  `e` holds the step's operands (da16 = this step's slice of the shadow in a bf16 pass);
+// da_next / da16_next = da_{t+1} and its shadow, null at the last step (no recurrent product)
+static int lstm_step_bwd(const LstmBwdPlan& P, const float* da_next, const vd_bf16_bits* da16_next, const EpiLstmBwd<2>& e, hipStream_t s) {
+  const int N = P.N, H = P.H, K = da_next ? 4 * H : 0;
+  const bool one_dh = !(e.dh_a && e.dh_b);   // at most one incoming-gradient operand (vd_lstm_backward: every step but the last)
+  SrcRow a{da_next, 4L * H};
+  SrcRow b{P.Wh, 4L * H};  // B[k][n] = Wh[n][k]
+  if (P.split && K > 0 && one_dh)   // exact-operand split: da_{t+1} stays fp32 in memory, Wh as three bf16 planes; 128 x 128 tiles: half the
+                                    // A re-reads of the fp32 kernel's 128 x 64
+    return launch_gemm_split(P.split, N, H, K, da_next, 4L * H, P.w.W3, 4L * H, 4L * H * H, lstm_bwd_epi<EpiLstmBwd<4, 2, false>>(e), s);
+  if (N < VD_THROUGHPUT_ROWS)   // two register stages, like the backward ticks (27 vs 31 us per launch alone)
+    return launch_gemm<CfgBwdSmallD>(N, H, K, 1, a, b, lstm_bwd_epi<EpiLstmBwd<1>>(e), s);
+  if (e.da16 && K > 0) {
     // shadows on: da_{t+1} and Wh are read as the bf16 rows their producers wrote (half the operand bytes, no conversion
     // while staging, LDS-DMA pipeline); K counts bf16 pairs
-    if (da16_next && Wh16 && K % 32 == 0)
+    if (da16_next && P.w.W16 && K % 32 == 0)
       return launch_gemm_glds<CfgB11bf16, false>(N, H, K / 2, 1, reinterpret_cast<const float*>(da16_next), 2L * H,
-                                                 reinterpret_cast<const float*>(Wh16), 2L * H, e, s);
+                                                 reinterpret_cast<const float*>(P.w.W16), 2L * H, e, s);
     return launch_gemm<CfgBbf16>(N, H, K, 1, a, b, e, s);
   }
-  if (da16) {   // bf16 pass, step without a recurrent product (the last one): same shadow, generic kernel
-    EpiLstmBwd<2> e{dh_a, dh_b, gates, c_t, c_prev, dc, dc_first, H, da16};
-    return launch_gemm<CfgB11>(N, H, K, 1, a, b, e, s);
+  if (!e.da16 && K > 0 && vd_lstm_glds_bwd_fits(N, H)) {
+    // LDS-DMA pipeline: A = da_{t+1} rows, Bt = Wh rows (both contiguous in k = the 4H gate columns).  The two-slot epilogue
+    // (loads of two slots in flight before either is consumed: half the serialised round trips) fits the 128-VGPR build with
+    // buffer addressing when the step has at most one incoming-gradient operand
+    if (one_dh) return launch_gemm_glds<CfgB11, false>(N, H, K, 1, da_next, 4L * H, P.Wh, 4L * H, lstm_bwd_epi<EpiLstmBwd<2, 2, false>>(e), s);
+    return launch_gemm_glds<CfgB11, false>(N, H, K, 1, da_next, 4L * H, P.Wh, 4L * H, e, s);
   }
-  if (N >= VD_THROUGHPUT_ROWS) {
-    if (vd_lstm_glds_bwd_fits(N, H) && K > 0) {
-      // LDS-DMA pipeline: A = da_{t+1} rows, Bt = Wh rows (both contiguous in k = the 4H gate columns).  The two-slot epilogue
-      // (loads of two slots in flight before either is consumed: half the serialised round trips) fits the 128-VGPR build with
-      // buffer addressing; a step with a recurrent product has at most one incoming-gradient operand
-      if (!(dh_a && dh_b)) {
-        EpiLstmBwd<2, 2, false> e2c{dh_a, dh_b, gates, c_t, c_prev, dc, dc_first, H};
-        return launch_gemm_glds<CfgB11, false>(N, H, K, 1, da_next, 4L * H, Wh, 4L * H, e2c, s);
-      }
-      EpiLstmBwd<2> e{dh_a, dh_b, gates, c_t, c_prev, dc, dc_first, H};
-      return launch_gemm_glds<CfgB11, false>(N, H, K, 1, da_next, 4L * H, Wh, 4L * H, e, s);
-    }
-    EpiLstmBwd<2> e2{dh_a, dh_b, gates, c_t, c_prev, dc, dc_first, H};
-    return launch_gemm<CfgB11>(N, H, K, 1, a, b, e2, s);
-  }
-  EpiLstmBwd<1> e{dh_a, dh_b, gates, c_t, c_prev, dc, dc_first, H};
-  return launch_gemm<CfgBwdSmallD>(N, H, K, 1, a, b, e, s);   // two register stages, like the backward ticks (27 vs 31 us per launch alone)
+  return launch_gemm<CfgB11>(N, H, K, 1, a, b, e, s);   // no recurrent product (the last step), or a shape off the pipeline
 }
 
 // ---------------------------------------------------------------------------
@@ -776,21 +780,14 @@ struct SrcKSel {
     return p + (long)k * ld + col;
   }
   __device__ __forceinline__ long kstep() const { return ld; }
-  __device__ __forceinline__ float4 ld4(int vc, int k) const {
-    int col = vc;
-    if (gate4) {
-      const int jb = vc >> 7, g = (vc >> 5) & 3, jj = vc & 31;
-      col = g * H + jb * 32 + jj;
-    }
-    return *reinterpret_cast<const float4*>(p + (long)k * ld + col);
-  }
+  __device__ __forceinline__ float4 ld4(int vc, int k) const { return *reinterpret_cast<const float4*>(ptr(vc, k)); }
 };
 struct EpiTickFwd {
   int kind;  // 0 = LSTM cell update, 1 = plain store (+bias)
-  EpiLstmFwdT<1> f;
+  EpiLstmFwdT<> f;
   EpiStore<4> s;
   static constexpr bool HAS_DIST = true;      // both kinds finish distributed over the four K-slice waves (gemm_block): no one-wave path is compiled
-  using DOps = EpiLstmFwdT<1>::DOps;
+  using DOps = EpiLstmFwdT<>::DOps;
   __device__ __forceinline__ bool dist_ok() const { return true; }
   __device__ __forceinline__ void dist_load(DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
     if (kind == 0) f.dist_load(q, row0, vcol0, lane, grp, M);
@@ -827,13 +824,12 @@ struct TickFwdProb {
   SrcKSel b;
   EpiTickFwd e;
 };
-template <int NT>   // column tiles per wave: 1 = 32 x 32 tiles, 2 = 32 (or 64) x 64 tiles (less operand traffic per FLOP)
-struct EpiTickBwdT {
-  int kind;
-  EpiLstmBwd<NT> f;      // (default BATCH: 2 slots in flight for NT = 1, 1 for NT >= 2)
-  EpiStore<NT> s;
-  static constexpr bool HAS_DIST = NT == 1;   // 32 x 32 split-K tiles: both kinds finish distributed over the four waves (gemm_block)
-  using DOps = typename EpiLstmBwd<NT>::DOps;
+struct EpiTickBwd {
+  int kind;  // 0 = gate gradients, 1 = plain store
+  EpiLstmBwd<1> f;
+  EpiStore<1> s;
+  static constexpr bool HAS_DIST = true;      // 32 x 32 split-K tiles: both kinds finish distributed over the four waves (gemm_block)
+  using DOps = EpiLstmBwd<1>::DOps;
   __device__ __forceinline__ bool dist_ok() const { return true; }
   __device__ __forceinline__ void dist_load(DOps& q, int row0, int col0, int lane, int grp, int M) const {
     if (kind == 0) f.dist_load(q, row0, col0, lane, grp, M);
@@ -846,21 +842,17 @@ struct EpiTickBwdT {
     const int row = row0 + grp * 8 + (lane >> 3), col = col0 + (lane & 7) * 4;      // plain store: dh1[t] = da2[t] * Wx2^T
     if (row < M) *reinterpret_cast<float4*>(s.C + (long)row * s.ldc + col) = a[0];
   }
-  __device__ __forceinline__ void operator()(const f32x16 (&acc)[NT], int row0, int col0, int lane, int M,
+  __device__ __forceinline__ void operator()(const f32x16 (&acc)[1], int row0, int col0, int lane, int M,
                                              int N, float* scr) const {
-    if (kind == 0) f(acc, row0, col0, lane, M, N, scr);
-    else s(acc, row0, col0, lane, M, N);
+    __builtin_trap();   // never reached, as in EpiTickFwd: the backward tick shape always takes the distributed form
   }
 };
-template <int NT>
-struct TickBwdProbT {
+struct TickBwdProb {
   int M, N, K, tiles_n;
   SrcRow a;
   SrcRow b;
-  EpiTickBwdT<NT> e;
+  EpiTickBwd e;
 };
-using EpiTickBwd = EpiTickBwdT<1>;
-using TickBwdProb = TickBwdProbT<1>;
 
 struct vd_lstm2_fwd_t {
   int T, N;
@@ -884,11 +876,11 @@ struct vd_lstm2_bwd_t {
 
 #define VD_MAX_STACKS 2
 
-// the per-tick grouped launches of the backward direction, for one tile configuration (NT = column tiles per wave)
-template <class Cfg, int NT>
+// the per-tick grouped launches of the backward direction, for one tile configuration
+template <class Cfg>
 static int lstm2_backward_ticks(const vd_lstm2_bwd_t* st, int nstacks, int H, int Tmax, hipStream_t stream) {
   for (int tau = 0; tau < Tmax + 2; ++tau) {
-    GroupArgs<TickBwdProbT<NT>, 3 * VD_MAX_STACKS> g;
+    GroupArgs<TickBwdProb, 3 * VD_MAX_STACKS> g;
     g.nprob = 0;
     for (int s = 0; s < nstacks; ++s) {
       const vd_lstm2_bwd_t& S = st[s];
@@ -901,7 +893,7 @@ static int lstm2_backward_ticks(const vd_lstm2_bwd_t* st, int nstacks, int H, in
         const bool last = (t == S.T - 1);
         const int rows = S.nact ? S.nact[t] : S.N;
         if (rows <= 0) continue;
-        TickBwdProbT<NT>& P = g.p[g.nprob++];
+        TickBwdProb& P = g.p[g.nprob++];
         P.M = rows; P.N = H; P.K = last ? 0 : 4 * H;
         P.a = SrcRow{last ? gates : gates + (long)(t + 1) * 4 * NH, 4L * H};
         P.b = SrcRow{layer == 2 ? S.Wh2 : S.Wh1, 4L * H};
@@ -914,17 +906,17 @@ static int lstm2_backward_ticks(const vd_lstm2_bwd_t* st, int nstacks, int H, in
         P.e.f.dc = layer == 2 ? S.dc2 : S.dc1;
         P.e.f.dc_first = last ? 1 : 0;
         P.e.f.H = H;
-        P.e.s = EpiStore<NT>{nullptr, 0, nullptr, 0, 0};
+        P.e.s = EpiStore<1>{nullptr, 0, nullptr, 0, 0};
       }
       const int t = S.T - tau;  // dh1[t] = da2[t] * Wx2^T
       if (t >= 0 && t < S.T && (S.nact ? S.nact[t] : S.N) > 0) {
-        TickBwdProbT<NT>& P = g.p[g.nprob++];
+        TickBwdProb& P = g.p[g.nprob++];
         P.M = S.nact ? S.nact[t] : S.N; P.N = H; P.K = 4 * H;
         P.a = SrcRow{S.gates2 + (long)t * 4 * NH, 4L * H};
         P.b = SrcRow{S.Wx2, 4L * H};
         P.e.kind = 1;
-        P.e.s = EpiStore<NT>{S.dh1_seq + t * NH, H, nullptr, VD_ACT_NONE, 0};
-        P.e.f = EpiLstmBwd<NT>{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, H};
+        P.e.s = EpiStore<1>{S.dh1_seq + t * NH, H, nullptr, VD_ACT_NONE, 0};
+        P.e.f = EpiLstmBwd<1>{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, H};
       }
     }
     if (g.nprob == 0) continue;
@@ -970,95 +962,35 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
   VD_CHECK_ARG(!live || tok_mask, "vd_lstm_forward: VD_FLAG_LIVE_PREFIX needs tok_mask");
   hipStream_t s = (hipStream_t)stream;
   const long NH = (long)N * H;
-  // the step kernel of the pass, chosen once: bf16 operands, the exact-operand split (split_core.h) on the fp32 LDS-DMA pipeline's
-  // shapes, that pipeline, or the generic kernel.  All but the last multiply by a transposed copy of Wh made here.
-  const bool bf16 = (flags & VD_FLAG_BF16) && vd_lstm_bf16_fits(N, H);
-  const bool glds = !bf16 && T > 1 && vd_lstm_glds_fwd_fits(N, H);
-  const int split = glds ? vd_split_nprod(flags) : 0;
-  const bool transposed = glds || (bf16 && (T > 1 || h0));
-  float* WhT = nullptr;
-  VdStreamScratch scr;
-  vd_bf16_bits* W3 = nullptr;
-  if (transposed) {
-    if (int rc0 = vd_stream_scratch(s, (size_t)4 * H * H * (split ? 10 : bf16 ? 6 : 4), 0, &scr)) return rc0;
-    WhT = scr.wht;
-    hipLaunchKernelGGL(wh_gate_transpose_kernel, dim3(4 * H / 32, H / 32), dim3(256), 0, s, Wh, WhT, H);
-    VD_LAUNCH_CHECK();
-    if (split) {   // the transposed weights as three bf16 planes (hi / mid / lo), once per pass
-      W3 = reinterpret_cast<vd_bf16_bits*>(scr.wht + (size_t)4 * H * H);
-      if (int rc0 = weights_to_bf16x3(WhT, W3, 4L * H * H, s)) return rc0;
-    }
-  }
-  // bf16 pass: the step kernels also write a bf16 copy of h (the operand of the dWh contraction of the same pass) ...
+  // the step kernel of the pass, chosen once (LstmFwdPlan; lstm_step_fwd reads it)
+  LstmFwdPlan P{N, H, Wh};
+  P.bf16 = (flags & VD_FLAG_BF16) && vd_lstm_bf16_fits(N, H);
+  P.glds = !P.bf16 && T > 1 && vd_lstm_glds_fwd_fits(N, H);
+  P.split = P.glds ? vd_split_nprod(flags) : 0;
+  if (int rc0 = lstm_weights(Wh, H, P.glds || (P.bf16 && (T > 1 || h0)), P.split, P.bf16 && T > 1, s, &P.w)) return rc0;
+  // bf16 pass: the step kernels also write a bf16 copy of h (the operand of the dWh contraction of the same pass), and read it as h_{t-1}
   vd_bf16_bits* h16 = nullptr;
-  if (bf16) {
+  if (P.bf16) {
     if (int rc0 = vd_bf16_shadow_get(0, h, (size_t)T * NH, &h16)) return rc0;
   } else {
     vd_bf16_shadow_invalidate(h, (size_t)(state_only ? 2 : T) * NH);
   }
+  P.h16 = h16;
   if (gates) vd_bf16_shadow_invalidate(gates, (size_t)T * 4 * NH);     // this pass overwrites `gates`: a da shadow registered over it (last backward) is stale
-  // ... and READ the shadow of h_{t-1} and a bf16 copy of the transposed weights through the LDS-DMA pipeline
-  vd_bf16_bits* WhT16 = nullptr;
-  if (bf16 && T > 1) {
-    WhT16 = reinterpret_cast<vd_bf16_bits*>(scr.wht + (size_t)4 * H * H);
-    if (int rc0 = weights_to_bf16(WhT, WhT16, 4L * H * H, s)) return rc0;
-  }
   for (int t = 0; t < T; ++t) {
     // VD_FLAG_STATE_ONLY: h and c are [2 x N x H] ping-pong buffers, step t reads slot (t - 1) & 1 and writes slot t & 1
     const long so = state_only ? (long)(t & 1) * NH : t * NH, sp = state_only ? (long)((t - 1) & 1) * NH : (t - 1) * NH;
     const float* hp = t ? h + sp : h0;
-    const float* cp = t ? c + sp : c0;
-    EpiLstmFwd e;
-    e.xproj = xproj + (long)t * x_tstride;
-    e.xld = x_ld;
-    e.tok_gather = tok_gather ? tok_gather + (long)t * N : nullptr;
-    e.tok_mask = tok_mask ? tok_mask + (long)t * N : nullptr;
-    e.c_prev = cp;
-    e.gates = gates ? gates + (long)t * 4 * NH : nullptr;
-    e.c_out = c + so;
-    e.h_out = h + so;
-    e.H = H;
-    e.h16 = h16 ? h16 + t * NH : nullptr;
+    const EpiLstmFwd e{xproj + (long)t * x_tstride, x_ld, tok_gather ? tok_gather + (long)t * N : nullptr,
+                       tok_mask ? tok_mask + (long)t * N : nullptr, /*c_prev*/ t ? c + sp : c0, gates ? gates + (long)t * 4 * NH : nullptr,
+                       /*c_out*/ c + so, /*h_out*/ h + so, H, h16 ? h16 + t * NH : nullptr};
+    // the four modes differ in the epilogue only (the entry checks keep tree / state_only / live apart, and off bf16 and the split where
+    // the type has no such kernels)
     int rc;
-    if (tree) {   // (fp32 only) the live prefix's paths with the parent gather; plane 1 of tok_mask holds the parent rows
-      EpiLstmFwdTree et;
-      static_cast<EpiLstmFwd&>(et) = e;
-      et.parent = tok_mask + ((long)T + t) * N;
-      if (!hp) rc = lstm_step_fwd(nullptr, Wh, N, H, 0, et, s);
-      else if (glds) rc = launch_gemm_glds<CfgF9, false>(N, 4 * H, H, 1, hp, (long)H, WhT, (long)H, et, s);
-      else rc = lstm_step_fwd_tree(hp, Wh, N, H, et, s);
-    } else if (state_only) {   // (neither bf16 nor the live prefix) the paths of the saving pass with the epilogue that stores c and h only
-      EpiLstmFwdState es;
-      static_cast<EpiLstmFwd&>(es) = e;
-      if (!hp) rc = lstm_step_fwd(nullptr, Wh, N, H, 0, es, s);
-      else if (split == 9) rc = launch_gemm_split<9>(N, 4 * H, H, hp, (long)H, W3, (long)H, 4L * H * H, es, s);
-      else if (split == 6) rc = launch_gemm_split<6>(N, 4 * H, H, hp, (long)H, W3, (long)H, 4L * H * H, es, s);
-      else if (split == 3) rc = launch_gemm_split<3>(N, 4 * H, H, hp, (long)H, W3, (long)H, 4L * H * H, es, s);
-      else if (glds) rc = launch_gemm_glds<CfgF9, false>(N, 4 * H, H, 1, hp, (long)H, WhT, (long)H, es, s);
-      else rc = lstm_step_fwd(hp, Wh, N, H, H, es, s);
-    } else if (live) {   // (fp32 only: neither bf16 nor split) the same three paths with the row-tile predicate
-      EpiLstmFwdLive el;
-      static_cast<EpiLstmFwd&>(el) = e;
-      if (!hp) rc = lstm_step_fwd(nullptr, Wh, N, H, 0, el, s);
-      else if (glds) rc = launch_gemm_glds<CfgF9, false>(N, 4 * H, H, 1, hp, (long)H, WhT, (long)H, el, s);
-      else rc = lstm_step_fwd(hp, Wh, N, H, H, el, s);
-    } else if (!hp)   // first step without h0: no recurrent product
-      rc = lstm_step_fwd(nullptr, Wh, N, H, 0, e, s);
-    else if (bf16 && t > 0)   // the shadow of h_{t-1}
-      rc = launch_gemm_glds<CfgF9bf16, false>(N, 4 * H, H / 2, 1, reinterpret_cast<const float*>(h16 + (t - 1) * NH), (long)H / 2,
-                                              reinterpret_cast<const float*>(WhT16), (long)H / 2, e, s);
-    else if (bf16)            // h0 (fp32)
-      rc = launch_gemm<CfgFbf16>(N, 4 * H, H, 1, SrcRow{hp, H}, SrcRow{WhT, H}, e, s);
-    else if (split == 9)
-      rc = launch_gemm_split<9>(N, 4 * H, H, hp, (long)H, W3, (long)H, 4L * H * H, e, s);
-    else if (split == 6)
-      rc = launch_gemm_split<6>(N, 4 * H, H, hp, (long)H, W3, (long)H, 4L * H * H, e, s);
-    else if (split == 3)
-      rc = launch_gemm_split<3>(N, 4 * H, H, hp, (long)H, W3, (long)H, 4L * H * H, e, s);
-    else if (glds)
-      rc = launch_gemm_glds<CfgF9, false>(N, 4 * H, H, 1, hp, (long)H, WhT, (long)H, e, s);
-    else
-      rc = lstm_step_fwd(hp, Wh, N, H, H, e, s);
+    if (tree) rc = lstm_step_fwd(P, t, hp, EpiLstmFwdTree{e, tok_mask + ((long)T + t) * N}, s);   // plane 1 of tok_mask: the parent rows
+    else if (state_only) rc = lstm_step_fwd(P, t, hp, EpiLstmFwdState{e}, s);
+    else if (live) rc = lstm_step_fwd(P, t, hp, EpiLstmFwdLive{e}, s);
+    else rc = lstm_step_fwd(P, t, hp, e, s);
     if (rc) return rc;
   }
   return VD_OK;
@@ -1074,37 +1006,25 @@ int vd_lstm_backward(const float* Wh, float* gates, const float* c, const float*
   hipStream_t s = (hipStream_t)stream;
   const long NH = (long)N * H;
   if (dc_last && dc_last != dc_work) VD_HIP(hipMemcpyAsync(dc_work, dc_last, NH * sizeof(float), hipMemcpyDeviceToDevice, s));
-  // the step kernels of the pass, chosen once: bf16 operands, the exact-operand split on the fp32 LDS-DMA pipeline's shapes, or fp32
+  // the step kernels of the pass, chosen once (LstmBwdPlan): bf16 operands, the exact-operand split on the fp32 LDS-DMA pipeline's shapes,
+  // or fp32.  Their copies of Wh lie behind the forward pass's transposed copy in the stream's scratch
   const bool bf16 = (flags & VD_FLAG_BF16) && vd_lstm_bf16_fits(N, H);
-  const int split = !bf16 && T > 1 && vd_lstm_glds_bwd_fits(N, H) ? vd_split_nprod(flags) : 0;
+  LstmBwdPlan P{N, H, Wh};
+  P.split = !bf16 && T > 1 && vd_lstm_glds_bwd_fits(N, H) ? vd_split_nprod(flags) : 0;
   // bf16 pass: the step kernels also write a bf16 copy of da (the other operand of the dWh contraction)
-  vd_bf16_bits* da16 = nullptr;
-  vd_bf16_bits* Wh16 = nullptr;
   if (bf16) {
-    if (int rc0 = vd_bf16_shadow_get(1, gates, (size_t)T * 4 * NH, &da16)) return rc0;
-    if (T > 1) {
-      VdStreamScratch wscr;
-      if (int rc0 = vd_stream_scratch(s, (size_t)4 * H * H * 6, 0, &wscr)) return rc0;
-      Wh16 = reinterpret_cast<vd_bf16_bits*>(wscr.wht + (size_t)4 * H * H);
-      if (int rc0 = weights_to_bf16(Wh, Wh16, 4L * H * H, s)) return rc0;
-    }
+    if (int rc0 = vd_bf16_shadow_get(1, gates, (size_t)T * 4 * NH, &P.da16)) return rc0;
   } else {
     vd_bf16_shadow_invalidate(gates, (size_t)T * 4 * NH);
   }
-  const vd_bf16_bits* W3 = nullptr;
-  if (split) {
-    VdStreamScratch wscr;
-    if (int rc0 = vd_stream_scratch(s, (size_t)4 * H * H * 10, 0, &wscr)) return rc0;
-    vd_bf16_bits* w3 = reinterpret_cast<vd_bf16_bits*>(wscr.wht + (size_t)4 * H * H);    // (behind the forward pass's transposed copy)
-    if (int rc0 = weights_to_bf16x3(Wh, w3, 4L * H * H, s)) return rc0;
-    W3 = w3;
-  }
+  if (int rc0 = lstm_weights(Wh, H, false, P.split, bf16 && T > 1, s, &P.w)) return rc0;
   for (int t = T - 1; t >= 0; --t) {
     const bool last = (t == T - 1);
-    const float* da_next = last ? nullptr : gates + (long)(t + 1) * 4 * NH;
-    const int rc = lstm_step_bwd(da_next, Wh, N, H, last ? 0 : 4 * H, dh_seq ? dh_seq + t * NH : nullptr, (last && dh_last) ? dh_last : nullptr,
-                                 gates + (long)t * 4 * NH, c + t * NH, t ? c + (t - 1) * NH : c0, dc_work, (last && !dc_last) ? 1 : 0, s, split,
-                                 W3, da16 ? da16 + (long)t * 4 * NH : nullptr, (da16 && !last) ? da16 + (long)(t + 1) * 4 * NH : nullptr, Wh16);
+    float* g_t = gates + (long)t * 4 * NH;
+    vd_bf16_bits* da16_t = P.da16 ? P.da16 + (long)t * 4 * NH : nullptr;
+    const EpiLstmBwd<2> e{dh_seq ? dh_seq + t * NH : nullptr, (last && dh_last) ? dh_last : nullptr, g_t, c + t * NH, t ? c + (t - 1) * NH : c0,
+                          dc_work, (last && !dc_last) ? 1 : 0, H, da16_t};
+    const int rc = lstm_step_bwd(P, last ? nullptr : g_t + 4 * NH, (da16_t && !last) ? da16_t + 4 * NH : nullptr, e, s);
     if (rc) return rc;
   }
   int rc = VD_OK;
@@ -1162,7 +1082,7 @@ static int lstm2_forward_ticks(const vd_lstm2_fwd_t* st, int nstacks, int H, int
         P.b = SrcKSel{S.Wx2, 4L * H, H, 0};
         P.e.kind = 1;
         P.e.s = EpiStore<4>{S.gates2 + (long)t * 4 * NH, 4L * H, S.b2, VD_ACT_NONE, 0};
-        P.e.f = EpiLstmFwdT<1>{nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, H};
+        P.e.f = EpiLstmFwdT<>{nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, H};
       }
     }
     if (g.nprob == 0) continue;
@@ -1197,8 +1117,8 @@ int vd_lstm2_backward_p(const vd_lstm2_bwd_t* st, int nstacks, int H, int flags,
                  "vd_lstm2_backward: stack %d has null/empty fields", s);
     Tmax = st[s].T > Tmax ? st[s].T : Tmax;
   }
-  if (flags & VD_FLAG_BF16) return lstm2_backward_ticks<CfgTickBwdBf16, 1>(st, nstacks, H, Tmax, stream);   // (BK = 128 divides 4H)
-  return lstm2_backward_ticks<CfgBwdSmallD, 1>(st, nstacks, H, Tmax, stream);   // two register stages
+  if (flags & VD_FLAG_BF16) return lstm2_backward_ticks<CfgTickBwdBf16>(st, nstacks, H, Tmax, stream);   // (BK = 128 divides 4H)
+  return lstm2_backward_ticks<CfgBwdSmallD>(st, nstacks, H, Tmax, stream);   // two register stages
 }
 
 extern "C" {
@@ -1217,29 +1137,16 @@ int vd_lstm_forward_c16(const vd_bf16_bits* table16, int64_t tab_ld, const int32
                "vd_lstm_forward_c16: throughput shapes only (N >= %ld, H %% 128 == 0)", VD_THROUGHPUT_ROWS);
   VD_CHECK_ARG((long)N * 4 * H * 4 < (1L << 32), "vd_lstm_forward_c16: N x 4H exceeds 4 GB per step");
   const long NH = (long)N * H;
-  VdStreamScratch scr;
-  if (int rc = vd_stream_scratch(s, (size_t)4 * H * H * 6, 0, &scr)) return rc;
-  float* WhT = scr.wht;
-  vd_bf16_bits* WhT16 = reinterpret_cast<vd_bf16_bits*>(scr.wht + (size_t)4 * H * H);
-  hipLaunchKernelGGL(wh_gate_transpose_kernel, dim3(4 * H / 32, H / 32), dim3(256), 0, s, Wh, WhT, H);
-  VD_LAUNCH_CHECK();
-  if (int rc = weights_to_bf16(WhT, WhT16, 4L * H * H, s)) return rc;
+  LstmWeights w;
+  if (int rc = lstm_weights(Wh, H, true, 0, true, s, &w)) return rc;
   for (int t = 0; t < T; ++t) {
-    EpiLstmFwdT<0, true> e;
-    e.xproj = reinterpret_cast<const float*>(table16);
-    e.xld = tab_ld;
-    e.tok_gather = tok_gather + (long)t * N;
-    e.tok_mask = nullptr;
-    e.c_prev = t ? c + (t - 1) * NH : nullptr;
-    e.gates = reinterpret_cast<float*>(gates16 + (long)t * 4 * NH);
-    e.c_out = c + t * NH;
-    e.h_out = t == T - 1 ? h_last : nullptr;
-    e.H = H;
-    e.h16 = h16 + t * NH;
+    const EpiLstmFwdT<true> e{reinterpret_cast<const float*>(table16), tab_ld, tok_gather + (long)t * N, /*tok_mask*/ nullptr,
+                              t ? c + (t - 1) * NH : nullptr, reinterpret_cast<float*>(gates16 + (long)t * 4 * NH), c + t * NH,
+                              t == T - 1 ? h_last : nullptr, H, h16 + t * NH};
     int rc;
     if (t == 0) rc = launch_gemm<CfgF9>(N, 4 * H, 0, 1, SrcRow{nullptr, H}, SrcKGate4{Wh, 4L * H, H}, e, s);   // no recurrent product yet
     else rc = launch_gemm_glds<CfgF9bf16, false>(N, 4 * H, H / 2, 1, reinterpret_cast<const float*>(h16 + (t - 1) * NH), (long)H / 2,
-                                                 reinterpret_cast<const float*>(WhT16), (long)H / 2, e, s);
+                                                 reinterpret_cast<const float*>(w.W16), (long)H / 2, e, s);
     if (rc) return rc;
   }
   return VD_OK;
@@ -1249,10 +1156,8 @@ int vd_lstm_backward_c16(const float* Wh, vd_bf16_bits* gates16, const float* c,
                          hipStream_t s) {
   VD_CHECK_ARG(Wh && gates16 && c && dh_last && dc_work && T >= 1 && vd_lstm_c16_fits(N, H), "vd_lstm_backward_c16: throughput shapes only");
   const long NH = (long)N * H;
-  VdStreamScratch wscr;
-  if (int rc = vd_stream_scratch(s, (size_t)4 * H * H * 6, 0, &wscr)) return rc;
-  vd_bf16_bits* Wh16 = reinterpret_cast<vd_bf16_bits*>(wscr.wht + (size_t)4 * H * H);
-  if (int rc = weights_to_bf16(Wh, Wh16, 4L * H * H, s)) return rc;
+  LstmWeights w;
+  if (int rc = lstm_weights(Wh, H, false, 0, true, s, &w)) return rc;
   for (int t = T - 1; t >= 0; --t) {
     const bool last = t == T - 1;
     EpiLstmBwd<2, 2, false, true> e{nullptr, last ? dh_last : nullptr, reinterpret_cast<float*>(gates16 + (long)t * 4 * NH), c + t * NH,
@@ -1260,7 +1165,7 @@ int vd_lstm_backward_c16(const float* Wh, vd_bf16_bits* gates16, const float* c,
     int rc;
     if (last) rc = launch_gemm<CfgB11>(N, H, 0, 1, SrcRow{nullptr, 4L * H}, SrcRow{Wh, 4L * H}, e, s);
     else rc = launch_gemm_glds<CfgB11bf16, false>(N, H, 4 * H / 2, 1, reinterpret_cast<const float*>(gates16 + (long)(t + 1) * 4 * NH), 2L * H,
-                                                  reinterpret_cast<const float*>(Wh16), 2L * H, e, s);
+                                                  reinterpret_cast<const float*>(w.W16), 2L * H, e, s);
     if (rc) return rc;
   }
   return VD_OK;

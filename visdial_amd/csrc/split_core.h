@@ -223,6 +223,15 @@ static int launch_gemm_split(int M, int N, int K, const float* A, long lda, cons
   return VD_OK;
 }
 
+// the same with the product count of the pass chosen at run time (paths.h vd_split_nprod: 9, 6 or 3)
+template <class Epi>
+static int launch_gemm_split(int nprod, int M, int N, int K, const float* A, long lda, const vd_bf16_bits* B, long ldb, long bplane,
+                             const Epi& e, hipStream_t stream) {
+  if (nprod == 9) return launch_gemm_split<9>(M, N, K, A, lda, B, ldb, bplane, e, stream);
+  if (nprod == 6) return launch_gemm_split<6>(M, N, K, A, lda, B, ldb, bplane, e, stream);
+  return launch_gemm_split<3>(M, N, K, A, lda, B, ldb, bplane, e, stream);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // The same exact split for the weight-gradient contraction  C[M x N] += A[K x M]^T * B[K x N]  (dWh = h^T * da over all
 // (timestep, row) pairs: K = 380 000 at the headline shape).  Both operands are fp32 rows contracted over their ROW index, so
