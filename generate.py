@@ -14,7 +14,8 @@ from visdial_amd.model import Model
 from visdial_amd.checkpoint import load_checkpoint, restore_weights
 
 
-def main():
+def parse_args(argv=None):
+    """the command line as the `opts` of the results file; refuses top-k / nucleus truncation without -sampleWords 1"""
     ap = argparse.ArgumentParser(description='Test the VisDial model for generation')
     ap.add_argument('-inputImg', '--inputImg', default='data/data_img.h5')
     ap.add_argument('-inputQues', '--inputQues', default='data/visdial_data.h5')
@@ -31,11 +32,25 @@ def main():
                     help='> 0: beam search of that many dialogs at once, all on the device (0 = one dialog at a time, host bookkeeping)')
     ap.add_argument('-sampleBatch', '--sampleBatch', type=int, default=0,
                     help='> 0 (with -sampleWords 1): sample that many dialogs at once, all on the device (0 = one dialog at a time)')
+    ap.add_argument('-topK', '--topK', type=int, default=0,
+                    help='> 0 (with -sampleWords 1): sample among the k most likely words only (0 = off)')
+    ap.add_argument('-topP', '--topP', type=float, default=1.0,
+                    help='< 1 (with -sampleWords 1): sample from the smallest set of most likely words holding that share of the '
+                         'probability (after -topK; 1 = off)')
     ap.add_argument('-seed', '--seed', type=int, default=1234, help='seed of the sampling generator (numpy RandomState)')
     ap.add_argument('-gpuid', '--gpuid', type=int, default=0)
     ap.add_argument('-host', '--host', default='python', choices=['python', 'native'],
                     help="'native' drives the model-level C ABI (what lua/model.lua calls)")
-    a = vars(ap.parse_args())
+    a = vars(ap.parse_args(argv))
+    if a['topK'] < 0 or not (0.0 < a['topP'] <= 1.0):
+        raise ValueError('-topK %d must be >= 0 (0 = off) and -topP %g in (0, 1] (1 = off)' % (a['topK'], a['topP']))
+    if (a['topK'] != 0 or a['topP'] != 1.0) and a['sampleWords'] != 1:
+        raise ValueError('-topK / -topP truncate the sampled distribution: they need -sampleWords 1 (beam search does not truncate)')
+    return a
+
+
+def main():
+    a = parse_args()
     saved = load_checkpoint(a['loadPath'])
     p = opts.derive(saved['modelParams'])                      # generate.lua:57-70
     p['gpuid'] = a['gpuid']
@@ -48,14 +63,15 @@ def main():
         p[k] = getattr(dl, k)
     if a['host'] == 'native':
         from visdial_amd.native import NativeModel
-        model = NativeModel(p)
+        model = NativeModel(dict(p, topK=a['topK'], topP=a['topP']))       # the device sampler takes its truncation at creation
     else:
         model = Model(p)
     restore_weights(model, saved, a['paramOrder'] or None)
     answers = model.generateAnswers(dl, 'val', dict(beamSize=a['beamSize'], beamLen=a['beamLen'],
                                                     maxThreads=a['maxThreads'], sampleWords=a['sampleWords'],
                                                     temperature=a['temperature'], beamBatch=a['beamBatch'],
-                                                    sampleBatch=a['sampleBatch'], seed=a['seed']))
+                                                    sampleBatch=a['sampleBatch'], seed=a['seed'],
+                                                    topK=a['topK'], topP=a['topP']))
     os.makedirs(a['resultPath'], exist_ok=True)
     path = os.path.join(a['resultPath'], 'results.json')
     utils.writeJSON(path, {'opts': a, 'data': answers})

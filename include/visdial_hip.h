@@ -468,7 +468,13 @@ int vd_model_beam_search(vd_model* m, int beam_size, int beam_len, int start_tok
  * host_loglik [N] the fp64 log-likelihood through the first <END>.  The tokens of the host loop over decode_step drawing with
  * RandomState.choice from the same uniforms, up to draws within rounding of a CDF boundary.  Argument errors: no
  * vd_model_encode first, beam_len < 1, a temperature that is not finite and > 0, a uniform outside [0, 1), and a row whose
- * weights exp(logp / temperature) all underflow (nothing to draw from; the host path fails there too). */
+ * weights exp(logp / temperature) all underflow (nothing to draw from; the host path fails there too).
+ * Top-k / nucleus truncation: VD_SAMPLE_TOPK (an integer >= 0; 0 / unset = off) and VD_SAMPLE_TOPP (a real in (0, 1]; 1 / unset = off)
+ * are read once by vd_model_create, which refuses any other value by name (both are ignored for decoder disc).  A model created with
+ * one of them draws each token from the kept set only: candidates by descending fp32 log-probability, equal values by ascending id, the
+ * first k of them, then the shortest prefix of those whose weights reach the share p of their sum.  host_loglik still adds the
+ * UNtruncated log-probability of every drawn token, so truncated, untruncated and per-dialog runs report comparable numbers.  Two calls
+ * on the same inputs return the same arrays.  The rule: csrc/sample.hip, visdial_amd/split_eval.py truncated_weights. */
 int vd_model_sample(vd_model* m, int beam_len, int start_token, int end_token, double temperature, const double* host_uniforms,
                     int32_t* host_tokens, double* host_loglik);
 int vd_model_scores(vd_model* m, float* host_scores, int64_t n);        /* [N x O] of the last forward / retrieve */

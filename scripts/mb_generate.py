@@ -3,7 +3,9 @@ vd_model_decode_step + a V-wide host sort or draw per explored row) against the 
 vd_model_beam_search / vd_model_sample over every round of 20 dialogs, the host's uniforms uploaded once).  lf-ques-im-hist + gen,
 H = 512, V = 11 322, 2 layers, length 20, random weights; beam 5, or sampling at temperature 1.  Prints dialogs/s per path and how
 many dialogs have identical records.
-    python scripts/mb_generate.py --mode beam|sample [dialogs] [--only batched]   (--only batched: the device path alone, for a trace)"""
+    python scripts/mb_generate.py --mode beam|sample [dialogs] [--only batched]   (--only batched: the device path alone, for a trace)
+    --mode sample --topK k --topP p: top-k / nucleus truncation on both paths (the model is created with the knobs: the device sampler
+    takes them at vd_model_create)"""
 import argparse
 import os
 import sys
@@ -20,7 +22,12 @@ ap = argparse.ArgumentParser(description='batched vs per-dialog answer generatio
 ap.add_argument('dialogs', nargs='?', type=int, default=20)
 ap.add_argument('--mode', choices=('beam', 'sample'), required=True)
 ap.add_argument('--only', choices=('batched',), help='the device path alone, for a kernel trace')
+ap.add_argument('--topK', type=int, default=0, help='--mode sample: sample among the k most likely words (0 = off)')
+ap.add_argument('--topP', type=float, default=1.0, help='--mode sample: nucleus truncation (1 = off)')
 opt = ap.parse_args()
+MODE_KNOBS = opt.topK != 0 or opt.topP != 1.0
+if MODE_KNOBS and opt.mode != 'sample':
+    ap.error('--topK / --topP truncate sampling: use --mode sample')
 MODE, D, ONLY_BATCHED = opt.mode, opt.dialogs, opt.only == 'batched'
 V, R = 11322, 10
 
@@ -43,14 +50,14 @@ class Dialogs(object):
 p = derive(default_params(encoder='lf-ques-im-hist', decoder='gen', vocabSize=V, embedSize=300, rnnHiddenSize=512, imgFeatureSize=4096,
                           numLayers=2, maxQuesCount=R, maxQuesLen=20, maxAnsLen=20, maxHistoryLenPerRound=40, batchSize=20, gpuid=0))
 dl = Dialogs(p, D)
-nat = NativeModel(p, init_seed=1)
+nat = NativeModel(dict(p, topK=opt.topK, topP=opt.topP) if MODE_KNOBS else p, init_seed=1)
 nat.training(False)
 if MODE == 'beam':
     key, cfg = 'beamBatch', dict(beamSize=5, beamLen=20, maxThreads=D)
     what = 'beam %d' % cfg['beamSize']
 else:
-    key, cfg = 'sampleBatch', dict(sampleWords=1, beamLen=20, temperature=1.0, maxThreads=D, seed=1234)
-    what = 'sampling'
+    key, cfg = 'sampleBatch', dict(sampleWords=1, beamLen=20, temperature=1.0, maxThreads=D, seed=1234, topK=opt.topK, topP=opt.topP)
+    what = 'sampling' + (' (topK %d, topP %g)' % (opt.topK, opt.topP) if MODE_KNOBS else '')
 print("lf-ques-im-hist + gen, H %d, V %d, %d layers, %s, length %d%s, %d dialogs x %d rounds" % (
     p['rnnHiddenSize'], V, p['numLayers'], what, cfg['beamLen'],
     ', temperature %g' % cfg['temperature'] if MODE == 'sample' else '', D, R), flush=True)

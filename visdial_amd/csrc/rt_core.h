@@ -56,6 +56,11 @@ int vd_lhood_lse_p(const float* h, int64_t ldh, int64_t rows, const int32_t* act
 int vd_lhood_edge_sum_p(const float* h, int64_t ldh, const int32_t* node_row, const float* lse, const int32_t* enode, const int32_t* etgt, int T,
                         int64_t rows, int C, const float* W, int64_t ldw, const float* bias, int H, float* out, int64_t ldo, hipStream_t stream);
 
+// sample.hip: vd_sample_draw over the top-k / nucleus kept set (VD_SAMPLE_TOPK / VD_SAMPLE_TOPP; the rule is sample.hip's header T1-T4)
+int vd_sample_draw_trunc_p(const float* logits, int64_t ld, int64_t rows, int V, int32_t* tok, const double* uniforms, double temperature,
+                           int top_k, double top_p, int step, int beam_len, int end_token, int32_t* hist, double* loglik, int32_t* status,
+                           hipStream_t stream);
+
 #define VD_TRY(expr)                  \
   do {                                \
     const int rc__ = (expr);          \
@@ -248,6 +253,9 @@ struct vd_model {
   // capability flags from the encoder NAME (opts.lua:54-67)
   bool use_im = false, use_hist = false, is_att = false, is_graph = false;
   vdrt::OptionCache ocache;
+  // VD_SAMPLE_TOPK / VD_SAMPLE_TOPP at vd_model_create (decoder gen): vd_model_sample draws from the top-k / nucleus kept set; 0 / 1 = off
+  int sample_topk = 0;
+  double sample_topp = 1.0;
   bool lhood_tree = false;   // VD_LHOOD_TREE at vd_model_create: vd_model_retrieve_lhood scores over a prefix tree of the candidates
   bool prof_hist = false;   // ev_prof[0..3] bracket the history branch of a Sequential encoder (gen pairs: vd_model_family_ms)
   ~vd_model();

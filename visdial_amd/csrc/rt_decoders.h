@@ -752,7 +752,8 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
 }
 
 // Model:generateAnswers' temperature sampling (model.lua:576-613): hypothesis row i = round i.  The host's uniforms [L x N] go up
-// in one copy; per step: fused log-softmax + inverse-CDF draw (csrc/sample.hip) -> the stepped state becomes the current one.
+// in one copy; per step: fused log-softmax + inverse-CDF draw (csrc/sample.hip; over the top-k / nucleus kept set for a model created with
+// VD_SAMPLE_TOPK / VD_SAMPLE_TOPP) -> the stepped state becomes the current one.
 // History, log-likelihoods and the status word share one buffer and come back together.
 inline int Gen_sample(Gen* g, vd_model* m, int L, int start, int end, double T, const double* host_u, int32_t* host_tokens,
                       double* host_loglik) {
@@ -777,7 +778,12 @@ inline int Gen_sample(Gen* g, vd_model* m, int L, int start, int end, double T, 
   int32_t* status = reinterpret_cast<int32_t*>(out + hist_bytes + (size_t)n * 8);
   VD_HIP(hipMemcpyAsync(u, host_u, (size_t)L * n * 8, hipMemcpyHostToDevice, s));
   VD_TRY(vd_sample_init(n, L, start, hist, tok, loglik, status, s));
+  const int top_k = m->sample_topk >= g->V ? 0 : m->sample_topk;   // k >= V keeps every column: off
+  const double top_p = m->sample_topp;
   VD_TRY(gen_batch_steps(g, m, L, tok, nullptr, 1, [&](int step, float* logits) {
+    if (top_k > 0 || top_p < 1.0)
+      return vd_sample_draw_trunc_p(logits, g->Vp, n, (int)g->V, tok, u + (size_t)(step - 1) * n, T, top_k, top_p, step, L, end, hist, loglik,
+                                    status, s);
     return vd_sample_draw(logits, g->Vp, n, (int)g->V, tok, u + (size_t)(step - 1) * n, T, step, L, end, hist, loglik, status, s);
   }));
   std::vector<uint8_t> staged;

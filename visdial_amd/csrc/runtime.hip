@@ -15,6 +15,8 @@
 // Streams: main (option LSTM, criterion, decoder, optimiser), enc (encoder chains under a disc decoder), img (per-image
 // projection + masks; also the history branch of lf-* / hre-*), tab (token sort + table gradient), copy (H2D uploads
 // of the NEXT batch; two batch slots).
+#include <errno.h>
+
 #include "rt_decoders.h"
 
 using namespace vdrt;
@@ -321,8 +323,31 @@ int vd_model_create(const vd_model_params* p, const char* encoder, const char* d
   VD_CHECK_ARG(!lhood_tree || p->lstmBf16 != 1,
                "vd_model_create: VD_LHOOD_TREE runs the exact fp32 tree recurrence (VD_FLAG_TREE), which the compact bf16 recurrence "
                "(lstmBf16 = 1) does not have");
+  // top-k / nucleus truncation of vd_model_sample (include/visdial_hip.h there): VD_SAMPLE_TOPK = an integer >= 0 (0 / unset = off),
+  // VD_SAMPLE_TOPP = a real in (0, 1] (1 / unset = off); anything else is refused.  Decoder disc has no sampling: ignored there.
+  int sample_topk = 0;
+  double sample_topp = 1.0;
+  if (std::string(decoder) == "gen") {
+    if (const char* e = getenv("VD_SAMPLE_TOPK")) {
+      char* end = nullptr;
+      errno = 0;
+      const long v = strtol(e, &end, 10);
+      VD_CHECK_ARG(*e && end && !*end && errno == 0 && v >= 0 && v <= INT32_MAX,
+                   "vd_model_create: VD_SAMPLE_TOPK = '%s' must be an integer >= 0 (0 = off)", e);
+      sample_topk = (int)v;
+    }
+    if (const char* e = getenv("VD_SAMPLE_TOPP")) {
+      char* end = nullptr;
+      const double v = strtod(e, &end);
+      VD_CHECK_ARG(*e && end && !*end && v > 0.0 && v <= 1.0,   // a NaN fails both comparisons
+                   "vd_model_create: VD_SAMPLE_TOPP = '%s' must be a real in (0, 1] (1 = off)", e);
+      sample_topp = v;
+    }
+  }
   vd_model* m = new vd_model();
   m->p = *p;
+  m->sample_topk = sample_topk;
+  m->sample_topp = sample_topp;
   m->flags = flags;
   m->ocache.capacity = cache_rows;
   m->lhood_tree = lhood_tree;

@@ -427,6 +427,12 @@ class Model(SplitEval):
         ops.beam_finish(G, k, L, hist[cur], scores, best_score, best_len, best_hist, out_tok, out_score)
         return out_tok.cpu().numpy(), out_score.cpu().numpy()
 
+    def _sample_truncation(self, topK, topP):
+        # the truncating draw kernel is internal to the library (its C symbol set is frozen): only the model-level runtime reaches it
+        raise ValueError("sampleBatch > 0 with topK = %d / topP = %g: the device sampler truncates in the model-level runtime only: use "
+                         "-host native (visdial_amd.native.NativeModel); the operator-level host truncates with sampleBatch = 0"
+                         % (topK, topP))
+
     def _gen_sample(self, beamLen, startToken, endToken, temperature, uniforms):
         """the batched temperature sampling (sampleBatch > 0, model.lua:576-613) of every round of the last `_gen_encode` batch on
         the device with the host's uniforms [beamLen x N]: per step the decoder step (decoders/gen.py step_logits) -> fused

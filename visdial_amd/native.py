@@ -72,19 +72,30 @@ class NativeModel(SplitEval):
         # back right after, so two models of one process can differ.
         # params fusedLhood = 2: generative retrieval over a prefix tree of the candidates' tokens (VD_LHOOD_TREE, read the same way);
         # fusedLhood = 1 and 0 create the model without it
+        # params topK / topP: top-k / nucleus truncation inside vd_model_sample (VD_SAMPLE_TOPK / VD_SAMPLE_TOPP, read the same way).  The
+        # values go through as written -- the library is the one that refuses a negative k, a p outside (0, 1] or text (decoder gen) -- and a
+        # params without them creates the model with the variables unset.  generateAnswers(sampleBatch > 0) checks its knobs against these.
         import os
         switches = {'VD_OPTION_CACHE': str(int(p.get('optionCache', 0) or 0)),
-                    'VD_LHOOD_TREE': '1' if int(p.get('fusedLhood', 0) or 0) == 2 else '0'}
+                    'VD_LHOOD_TREE': '1' if int(p.get('fusedLhood', 0) or 0) == 2 else '0',
+                    'VD_SAMPLE_TOPK': None if p.get('topK') is None else str(p['topK']),
+                    'VD_SAMPLE_TOPP': None if p.get('topP') is None else str(p['topP'])}
         prev = {k: os.environ.get(k) for k in switches}
-        os.environ.update(switches)
         try:
+            for k, v in switches.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
             call("vd_model_create", C.byref(mp), p['encoder'].encode(), p['decoder'].encode(), C.byref(h))
         finally:
             for k, v in prev.items():
                 if v is None:
-                    del os.environ[k]
+                    os.environ.pop(k, None)
                 else:
                     os.environ[k] = v
+        gen = p['decoder'] == 'gen'
+        self._sample_knobs = (int(p.get('topK') or 0) if gen else 0, float(1.0 if p.get('topP') is None or not gen else p['topP']))
         self.h = h
         lib = _lib.load()
         self.tensors = []
@@ -342,9 +353,15 @@ class NativeModel(SplitEval):
              scores.ctypes.data)
         return tokens, scores
 
+    def _sample_truncation(self, topK, topP):
+        if (int(topK), float(topP)) != self._sample_knobs:
+            raise ValueError("sampleBatch > 0 with topK = %d / topP = %g, but this model was created with topK = %d / topP = %g: the "
+                             "device sampler takes its truncation when the model is created (params topK / topP of NativeModel)"
+                             % ((int(topK), float(topP)) + self._sample_knobs))
+
     def _gen_sample(self, beamLen, startToken, endToken, temperature, uniforms):
         """the batched temperature sampling (sampleBatch > 0) of every round of the last `_gen_encode` batch with the host's
-        uniforms [beamLen x N]: vd_model_sample.  Returns (tokens [N x (beamLen + 1)], fp64 log-likelihoods [N])."""
+        uniforms [beamLen x N]: vd_model_sample; over the top-k / nucleus kept set if the model was created with params topK / topP.  Returns (tokens [N x (beamLen + 1)], fp64 log-likelihoods [N])."""
         N, L = int(self._N), int(beamLen)
         u = np.ascontiguousarray(uniforms, dtype=np.float64)
         if u.shape != (L, N):

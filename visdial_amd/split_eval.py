@@ -7,12 +7,43 @@ Model:generateAnswers the four device steps `_gen_encode(batch)`, `_gen_begin(ro
 batched beam search (params beamBatch > 0) `_gen_beam(beamSize, beamLen, startToken, endToken) -> (tokens [N x beamLen], scores
 [N])` over every round of the last `_gen_encode` batch (= vd_model_beam_search; the operator-level host composes the vd_beam_*
 kernels), and for batched sampling (params sampleBatch > 0) `_gen_sample(beamLen, startToken, endToken, temperature, uniforms
-[beamLen x N]) -> (tokens [N x (beamLen + 1)], log-likelihoods [N])` (= vd_model_sample; vd_sample_* for the operator-level host)."""
+[beamLen x N]) -> (tokens [N x (beamLen + 1)], log-likelihoods [N])` (= vd_model_sample; vd_sample_* for the operator-level host), with
+`_sample_truncation(topK, topP)` raising unless that sampler truncates with exactly these knobs."""
 import math
 
 import numpy as np
 
 from . import utils
+
+
+def truncated_weights(logp, temperature, topK=0, topP=1.0):
+    """The sampling weights of ONE row of fp32 log-probabilities under top-k / nucleus truncation: the rule the per-dialog loop below
+    applies and the device sampler (csrc/sample.hip, T1-T4) is held to.
+      1. w[c] = exp(float64(logp[c]) / temperature)
+      2. candidate order: logp descending as fp32 values, equal values by ascending index
+      3. topK > 0: the first min(topK, V) of that order stay
+      4. topP < 1: S_k = the fp64 sum of w over what 3. kept; the shortest prefix of the order whose running sum is >= topP * S_k
+         stays -- at least one column, and none with w == 0 unless there is nothing else (every weight underflowed: the draw fails
+         as it does without truncation)
+      5. every other column gets weight 0.
+    topK = 0 with topP = 1 returns w of 1. untouched.  The weights are not normalised; the drawn token's log-likelihood is its
+    UNtruncated logp."""
+    topK, topP = int(topK), float(topP)
+    if topK < 0 or not (0.0 < topP <= 1.0):
+        raise ValueError('topK = %r must be an integer >= 0 (0 = off) and topP = %r a real in (0, 1] (1 = off)' % (topK, topP))
+    lp = np.asarray(logp, np.float32).reshape(-1)
+    w = np.exp(lp.astype(np.float64) / temperature)
+    if topK == 0 and topP == 1.0:
+        return w
+    order = np.argsort(-lp, kind='stable')
+    n = min(topK, w.size) if topK > 0 else w.size
+    if topP < 1.0:
+        cum = np.cumsum(w[order[:n]])
+        reach = int(np.searchsorted(cum, topP * cum[-1], side='left')) + 1     # the first prefix whose sum is >= topP * S_k
+        n = max(1, min(reach, n, int((w[order[:n]] > 0).sum())))
+    out = np.zeros_like(w)
+    out[order[:n]] = w[order[:n]]
+    return out
 
 
 class SplitEval(object):
@@ -124,7 +155,9 @@ class SplitEval(object):
         control flow.  params beamBatch = B > 0: the beam search of dialogs [s, s+B) runs together on the device, every round of
         the chunk at once (one encode + one `_gen_beam` per chunk); same records.  params sampleBatch = B > 0 (with sampleWords = 1):
         the same for temperature sampling (one encode + one `_gen_sample` per chunk); the host still draws every uniform, in the
-        per-dialog loop's order, so the records are the same up to draws within rounding of a CDF boundary.
+        per-dialog loop's order, so the records are the same up to draws within rounding of a CDF boundary.  params topK / topP (with
+        sampleWords = 1): top-k / nucleus truncation of the sampled distribution, `truncated_weights` above; the batched path needs a
+        host whose device sampler truncates (`_sample_truncation`).
         Returns [{image_id, dialog: [{question, answer}...]}]."""
         if self.params['decoder'] == 'disc':
             raise SystemExit('Sampling/beam search only for generative model')
@@ -137,6 +170,14 @@ class SplitEval(object):
         if sampleBatch > 0 and not sampleWords:
             raise ValueError('sampleBatch > 0 is batched sampling: it needs sampleWords = 1')
         temperature = float(params.get('temperature', 1.0))
+        topK, topP = int(params.get('topK', 0) or 0), float(params.get('topP', 1.0))
+        truncate = topK != 0 or topP != 1.0
+        if truncate and not sampleWords:
+            raise ValueError('topK / topP truncate the sampled distribution: they need sampleWords = 1 (beam search does not truncate)')
+        if truncate:
+            truncated_weights(np.zeros(1, np.float32), temperature, topK, topP)       # refuses a bad knob before any device work
+            if sampleBatch > 0:
+                self._sample_truncation(topK, topP)
         beamSize, beamLen = int(params.get('beamSize', 5)), int(params.get('beamLen', 20))
         startToken, endToken = dataloader.word2ind['<START>'], dataloader.word2ind['<END>']
         numThreads = int(params.get('maxThreads') or dataloader.numThreads[dtype])
@@ -211,7 +252,10 @@ class SplitEval(object):
                 for timeStep in range(beamLen):
                     logp = self._gen_step(answerIn)
                     self._gen_select(np.arange(numQues, dtype=np.int32), numQues)
-                    pr = np.exp(logp.astype(np.float64) / temperature)
+                    if truncate:
+                        pr = np.stack([truncated_weights(logp[i], temperature, topK, topP) for i in range(numQues)])
+                    else:
+                        pr = np.exp(logp.astype(np.float64) / temperature)
                     pr /= pr.sum(1, keepdims=True)
                     nxt = np.array([rng.choice(pr.shape[1], p=pr[i]) + 1 for i in range(numQues)], np.int64)
                     answer.append(nxt[:, None])
