@@ -61,17 +61,20 @@ def in_private_pool(private_pool):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the operator
-def run_lstm(tok, xproj, table, Wh, h0, c0, T, N, H, flags):
+def run_lstm(mask, xproj, table, Wh, h0, c0, T, N, H, flags, gates=True):
+    """mask: [T x N] (plain / live prefix) or [2 x T x N] (tree) int32 on the device; every output pre-filled with the sentinel.
+    Returns [gates (None without `gates`), h, c]."""
     from visdial_amd import ops
-    gates = torch.full((T, N, 4 * H), SENTINEL, device='cuda')
+    g = torch.full((T, N, 4 * H), SENTINEL, device='cuda') if gates else None
     h = torch.full((T, N, H), SENTINEL, device='cuda')
     c = torch.full((T, N, H), SENTINEL, device='cuda')
+    tok = mask.reshape(-1)[:T * N]
     if table is not None:
-        ops.lstm_forward(table, Wh, gates, h, c, T, N, H, 0, 4 * H, tok_gather=tok, tok_mask=tok, h0=h0, c0=c0, flags=flags)
+        ops.lstm_forward(table, Wh, g, h, c, T, N, H, 0, 4 * H, tok_gather=tok, tok_mask=mask, h0=h0, c0=c0, flags=flags)
     else:
-        ops.lstm_forward(xproj, Wh, gates, h, c, T, N, H, N * 4 * H, 4 * H, tok_mask=tok, h0=h0, c0=c0, flags=flags)
+        ops.lstm_forward(xproj, Wh, g, h, c, T, N, H, N * 4 * H, 4 * H, tok_mask=mask, h0=h0, c0=c0, flags=flags)
     torch.cuda.synchronize()
-    return [a.cpu().numpy() for a in (gates, h, c)]
+    return [a.cpu().numpy() if a is not None else None for a in (g, h, c)]
 
 
 CASES = [

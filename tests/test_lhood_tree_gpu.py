@@ -18,6 +18,7 @@ import torch
 
 from oracle import visdial_oracle as vo
 from test_lhood_gpu import dev
+from test_lhood_prefix_gpu import in_private_pool, private_pool, run_lstm  # noqa: F401 (the pool fixtures act by being here)
 from test_ops_gpu import relerr
 
 pytestmark = pytest.mark.gpu
@@ -30,48 +31,7 @@ def gpu():
         pytest.skip("needs a GPU")
 
 
-@pytest.fixture(scope="module")
-def private_pool():
-    """This module's device tensors live in a memory pool of their own, released when the module ends (as tests/test_lhood_prefix_gpu.py):
-    the tensor library's default pool is left as this module found it."""
-    pool = None
-    if torch.cuda.is_available():
-        try:
-            pool = torch.cuda.MemPool()
-            with torch.cuda.use_mem_pool(pool):
-                torch.empty(1024, device='cuda')
-        except (AttributeError, RuntimeError, TypeError) as e:
-            print('no private memory pool (%s): allocating from the default pool' % e)
-            pool = None
-    yield pool
-    del pool
-
-
-@pytest.fixture(autouse=True)
-def in_private_pool(private_pool):
-    if private_pool is None:
-        yield
-        return
-    with torch.cuda.use_mem_pool(private_pool):
-        yield
-
-
 # ------------------------------------------------------------------------------------------------------------------ the operator
-def run_lstm(mask, xproj, table, Wh, h0, c0, T, N, H, flags, gates=True):
-    """mask: [T x N] (plain / live prefix) or [2 x T x N] (tree) int32 on the device; every output pre-filled with the sentinel"""
-    from visdial_amd import ops
-    g = torch.full((T, N, 4 * H), SENTINEL, device='cuda') if gates else None
-    h = torch.full((T, N, H), SENTINEL, device='cuda')
-    c = torch.full((T, N, H), SENTINEL, device='cuda')
-    tok = mask.reshape(-1)[:T * N]
-    if table is not None:
-        ops.lstm_forward(table, Wh, g, h, c, T, N, H, 0, 4 * H, tok_gather=tok, tok_mask=mask, h0=h0, c0=c0, flags=flags)
-    else:
-        ops.lstm_forward(xproj, Wh, g, h, c, T, N, H, N * 4 * H, 4 * H, tok_mask=mask, h0=h0, c0=c0, flags=flags)
-    torch.cuda.synchronize()
-    return h.cpu().numpy(), c.cpu().numpy()
-
-
 IDENTITY_CASES = [
     # name, H, N, nodes per step
     ('small kernels, ragged tiles', 64, 203, [203, 97, 96, 31, 1]),
@@ -101,8 +61,8 @@ def test_tree_with_identity_parents_equals_live_prefix(gpu, name, H, N, widths, 
     else:
         xproj = torch.randn((T, N, 4 * H), device='cuda', generator=torch.Generator(device='cuda').manual_seed(5))
     tk = dev(tok, torch.int32)
-    live = run_lstm(tk[0].contiguous(), xproj, table, Wh, h0, c0, T, N, H, ops.FLAG_LIVE_PREFIX)
-    tree = run_lstm(tk, xproj, table, Wh, h0, c0, T, N, H, ops.FLAG_TREE, gates=False)
+    live = run_lstm(tk[0].contiguous(), xproj, table, Wh, h0, c0, T, N, H, ops.FLAG_LIVE_PREFIX)[1:]
+    tree = run_lstm(tk, xproj, table, Wh, h0, c0, T, N, H, ops.FLAG_TREE, gates=False)[1:]
     for what, a, b in zip(('h', 'c'), live, tree):
         for t, n in enumerate(widths):
             assert not (a[t, :n] == SENTINEL).any(), (what, t)
@@ -187,10 +147,10 @@ def test_tree_forest_matches_fp64_oracle_over_every_path(gpu, name, mode):
     table = dev(case['table'], torch.float32)
     mask = dev(np.stack([tok, par]), torch.int32)
     if mode == 'table':
-        h, c = run_lstm(mask, None, table, Wh, h0, c0, T, N, H, ops.FLAG_TREE, gates=False)
+        _, h, c = run_lstm(mask, None, table, Wh, h0, c0, T, N, H, ops.FLAG_TREE, gates=False)
     else:
         xproj = table[dev(tok, torch.int64)].contiguous()         # [T x N x 4H]
-        h, c = run_lstm(mask, xproj, None, Wh, h0, c0, T, N, H, ops.FLAG_TREE, gates=False)
+        _, h, c = run_lstm(mask, xproj, None, Wh, h0, c0, T, N, H, ops.FLAG_TREE, gates=False)
     for t, n in enumerate(widths):
         eh, ec = relerr(h[t, :n], case['ref'][0][t]), relerr(c[t, :n], case['ref'][1][t])
         print('%s %s level %d (%d nodes): relerr h %.2e c %.2e' % (name, mode, t, n, eh, ec))

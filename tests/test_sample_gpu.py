@@ -15,6 +15,7 @@ from conftest import ROOT
 from oracle import visdial_oracle as vo
 from test_beam_search_gpu import tiny
 from visdial_amd.opts import default_params, derive
+from visdial_amd.split_eval import truncated_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -30,14 +31,29 @@ def dev(a, dtype):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the kernel
-def host_draw(logp, u, T):
-    """split_eval.py's per-dialog draw: exp(logp / T) normalised, RandomState.choice(V, p) = cdf.searchsorted(u, 'right') with
-    cdf = cumsum(p) / cdf[-1].  Returns (index, fp64 distance of u to the nearest CDF boundary)."""
-    pr = np.exp(logp.astype(np.float64) / T)
-    pr /= pr.sum()
+def nucleus_margin(logp, T, k, p):
+    """the fp64 distance of the nucleus target to the nearest prefix sum of the host rule, relative to the target (inf without a nucleus)"""
+    if p >= 1.0:
+        return np.inf
+    order = np.argsort(-logp, kind='stable')
+    n = min(k, logp.size) if k > 0 else logp.size
+    cum = np.cumsum(np.exp(logp[order[:n]].astype(np.float64) / T))
+    target = p * cum[-1]
+    return float(np.abs(cum - target).min() / target)
+
+
+def host_draw(logp, u, T, k=0, p=1.0):
+    """split_eval.py's per-dialog draw: exp(logp / T) -- with top-k `k` / nucleus `p` on, split_eval.truncated_weights -- normalised,
+    RandomState.choice(V, p) = cdf.searchsorted(u, 'right') with cdf = cumsum(p) / cdf[-1].  Returns (index, margin): the smaller of
+    the fp64 distance of u to the nearest CDF boundary and the relative distance of the nucleus target to the nearest prefix sum."""
+    if k == 0 and p == 1.0:
+        pr = np.exp(logp.astype(np.float64) / T)             # stated here, not taken from the code under test
+    else:
+        pr = truncated_weights(logp, T, k, p)
+    pr = pr / pr.sum()
     cdf = np.cumsum(pr)
     cdf /= cdf[-1]
-    return int(cdf.searchsorted(u, side='right')), float(np.abs(cdf - u).min())
+    return int(cdf.searchsorted(u, side='right')), min(float(np.abs(cdf - u).min()), nucleus_margin(logp, T, k, p))
 
 
 @pytest.mark.parametrize("V", [5, 256, 257, 11322])
@@ -105,10 +121,10 @@ def test_sample_draw_flags_an_all_underflow_row(gpu):
 
 # ---------------------------------------------------------------------------------------------------------------- model level
 def replay_margins(model, dl, p, cfg, uniform):
-    """the per-dialog sampling loop of split_eval.py replayed through `_gen_step` with the uniforms `uniform()` hands out in the
-    loop's order: {(dialog index, round): [fp64 distance of u to the nearest CDF boundary, per step]}"""
-    START, END = dl.word2ind['<START>'], dl.word2ind['<END>']
-    L, T = cfg['beamLen'], cfg.get('temperature', 1.0)
+    """the per-dialog sampling loop of split_eval.py (with cfg's topK / topP, if any) replayed through `_gen_step` with the uniforms
+    `uniform()` hands out in the loop's order: {(dialog index, round): [margin of host_draw, per step]}"""
+    START = dl.word2ind['<START>']
+    L, T, k, pp = cfg['beamLen'], cfg.get('temperature', 1.0), cfg.get('topK', 0), cfg.get('topP', 1.0)
     model._set_training(False)
     out = {}
     for conv in range(cfg['maxThreads']):
@@ -121,7 +137,7 @@ def replay_margins(model, dl, p, cfg, uniform):
             logp = model._gen_step(tok)
             model._gen_select(np.arange(R, dtype=np.int32), R)
             for i in range(R):
-                c, margin = host_draw(logp[i], uniform(), T)
+                c, margin = host_draw(logp[i], uniform(), T, k, pp)
                 out.setdefault((conv, i), []).append(margin)
                 tok[i] = c + 1
     model._set_training(True)
@@ -129,7 +145,7 @@ def replay_margins(model, dl, p, cfg, uniform):
 
 
 def check_records(got, ref, margins, tol, what):
-    """equal records, or every differing round has a draw within `tol` of a CDF boundary at or before its first differing word"""
+    """equal records, or every differing round has a margin below `tol` at or before its first differing word; returns how many differ"""
     assert len(got) == len(ref) and [d['image_id'] for d in got] == [d['image_id'] for d in ref], what
     explained = 0
     for conv, (a, b) in enumerate(zip(got, ref)):

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+from test_sample_gpu import check_records, host_draw, nucleus_margin, replay_margins
 from visdial_amd.opts import default_params, derive
 from visdial_amd.split_eval import truncated_weights
 
@@ -69,17 +70,6 @@ def crafted_logits(V):
     head = np.repeat([4.0, 3.0, 2.0, 1.0, 0.0], [2, 3, 6, 9, 20])
     x = np.concatenate([head, rng.uniform(-8.0, -0.5, size=V - head.size)]).astype(np.float32)
     return x[rng.permutation(V)]
-
-
-def nucleus_margin(logp, T, k, p):
-    """the fp64 distance of the nucleus target to the nearest prefix sum of the host rule, relative to the target (inf without a nucleus)"""
-    if p >= 1.0:
-        return np.inf
-    order = np.argsort(-logp, kind='stable')
-    n = min(k, logp.size) if k > 0 else logp.size
-    cum = np.cumsum(np.exp(logp[order[:n]].astype(np.float64) / T))
-    target = p * cum[-1]
-    return float(np.abs(cum - target).min() / target)
 
 
 def pinned(V, k, p):
@@ -217,57 +207,6 @@ def test_two_calls_give_the_same_arrays(gpu, V, k, p):
 
 
 # ------------------------------------------------------------------------------------------------------------ the per-dialog loops
-def host_draw(logp, u, T, k, p):
-    """split_eval.py's per-dialog draw from the truncated weights: RandomState.choice(V, p) = cdf.searchsorted(u, 'right').  Returns
-    (index, margin): the smaller of the fp64 distance of u to the nearest CDF boundary of the truncated distribution and the relative
-    distance of the nucleus target to the nearest prefix sum."""
-    pr = truncated_weights(logp, T, k, p)
-    pr = pr / pr.sum()
-    cdf = np.cumsum(pr)
-    cdf /= cdf[-1]
-    return int(cdf.searchsorted(u, side='right')), min(float(np.abs(cdf - u).min()), nucleus_margin(logp, T, k, p))
-
-
-def replay_margins(model, dl, p, cfg, uniform):
-    """the per-dialog sampling loop replayed through `_gen_step` with the uniforms `uniform()` hands out in the loop's order:
-    {(dialog index, round): [margin per step]}"""
-    START = dl.word2ind['<START>']
-    L, T, k, pp = cfg['beamLen'], cfg.get('temperature', 1.0), cfg.get('topK', 0), cfg.get('topP', 1.0)
-    model._set_training(False)
-    out = {}
-    for conv in range(cfg['maxThreads']):
-        batch = dl.getIndexData(np.array([conv + 1]), p, 'val')
-        R = batch['ques_fwd'].shape[1]
-        model._gen_encode(batch)
-        model._gen_begin(np.arange(R, dtype=np.int32))
-        tok = np.full(R, START, np.int64)
-        for _ in range(L):
-            logp = model._gen_step(tok)
-            model._gen_select(np.arange(R, dtype=np.int32), R)
-            for i in range(R):
-                c, margin = host_draw(logp[i], uniform(), T, k, pp)
-                out.setdefault((conv, i), []).append(margin)
-                tok[i] = c + 1
-    return out
-
-
-def check_records(got, ref, margins, what):
-    """equal records, or every differing round has a margin below TOL at or before its first differing word; returns how many differ"""
-    assert len(got) == len(ref) and [d['image_id'] for d in got] == [d['image_id'] for d in ref], what
-    explained = 0
-    for conv, (a, b) in enumerate(zip(got, ref)):
-        for it, (x, y) in enumerate(zip(a['dialog'], b['dialog'])):
-            assert x['question'] == y['question'], (what, conv, it)
-            if x['answer'] == y['answer']:
-                continue
-            wa, wb = x['answer'].split(), y['answer'].split()
-            first = next((i for i, (s, t) in enumerate(zip(wa, wb)) if s != t), min(len(wa), len(wb)))
-            m = min(margins[conv, it][:first + 1])
-            assert m < TOL, (what, conv, it, m, x['answer'], y['answer'])
-            explained += 1
-    return explained
-
-
 @pytest.fixture(scope="module")
 def fixture_model(gpu):
     """the committed prepro fixture (4 val dialogs x 10 rounds) as generate.py loads it, and a randomly initialised lf-ques + gen
@@ -302,12 +241,12 @@ def test_batched_truncated_sampling_equals_the_per_dialog_loops(fixture_model):
     print("seed %d: %d of %d rounds have a margin below %g in the host replay" % (SEED, near, rounds, TOL))
     assert rounds == 40 and near <= 0.02 * rounds
     for sb in (1, 3):
-        explained = check_records(nat.generateAnswers(dl, 'val', dict(cfg, sampleBatch=sb)), ref, margins, sb)
+        explained = check_records(nat.generateAnswers(dl, 'val', dict(cfg, sampleBatch=sb)), ref, margins, TOL, sb)
         assert explained <= 0.02 * rounds, (sb, explained)
     # the operator-level host: its per-dialog loop truncates; its device sampler does not and says where to go
     py = Model(p)
     py.set_parameters_dict(nat.get_parameters_dict())
-    assert check_records(py.generateAnswers(dl, 'val', cfg), ref, margins, 'python') <= 0.02 * rounds
+    assert check_records(py.generateAnswers(dl, 'val', cfg), ref, margins, TOL, 'python') <= 0.02 * rounds
     with pytest.raises(ValueError, match='-host native'):
         py.generateAnswers(dl, 'val', dict(cfg, sampleBatch=2))
     assert len(py.generateAnswers(dl, 'val', dict(cfg, sampleBatch=2, topK=0, topP=1.0))) == 4     # untruncated: as before
@@ -332,7 +271,7 @@ def test_generate_py_top_k_top_p_writes_the_per_dialog_results(fixture_model, tm
     cfg = dict(beamLen=8, maxThreads=4, temperature=1.0, topK=5, topP=0.9)
     margins = replay_margins(nat, dl, p, cfg, np.random.RandomState(1234).random_sample)           # generate.py's default -seed
     assert len(res['0']['data']) == 4
-    assert check_records(res['2']['data'], res['0']['data'], margins, 'generate.py') <= 0.02 * len(margins)
+    assert check_records(res['2']['data'], res['0']['data'], margins, TOL, 'generate.py') <= 0.02 * len(margins)
 
 
 # ------------------------------------------------------------------------------------------------------------ refusals

@@ -544,48 +544,38 @@ struct SeqLSTM {
     if (h_out) *h_out = h;
     return VD_OK;
   }
-  // Forward-only pass over length-ordered candidates (generative retrieval, rt_decoders.h).  `table` (layer 1): xproj = Emb * Wx + b
-  // gathered by token id inside the step kernel; else `x` [T*N x D] is projected here.  flags = VD_FLAG_LIVE_PREFIX: the projection
-  // and the steps skip the row tiles without a live row (the same tiles: one launch per step, the step kernel's tile height), whose
-  // gates / h / c rows are left unwritten.
-  int forward_ordered(vd_model* m, hipStream_t s, const float* table, const float* x, int T_, int N_, const int32_t* tok, int flags,
-                      float** h_out) {
-    VD_TRY(take_state(m, s, N_));
-    VD_TRY(alloc(m, T_, N_));
-    xs.clear(); tok_mask = tok; rows = nullptr;
-    if (table) {
-      VD_TRY(vd_lstm_forward(table, 0, 4 * H, tok, tok, Wh(m), h0, c0, gates, h, c, T, N, (int)H, flags, s));
+  // Forward-only pass of generative retrieval (rt_decoders.h).  `table` (layer 1): xproj = Emb * Wx + b gathered by token id inside the
+  // step kernel; else `x` [T*N x D] (the h of the layer below) is projected here.  `mask` and `flags` go to the step kernel:
+  //   0                    tokens [T x N], every row runs
+  //   VD_FLAG_LIVE_PREFIX  tokens of length-ordered candidates: the projection and the steps skip the row tiles without a live row (the
+  //                        same tiles: one launch per step, the step kernel's tile height), whose gates / h / c rows are left unwritten
+  //   VD_FLAG_TREE         a forest, level by level: mask [2 x T x N] = token | parent row; the parents of level 0 are rows of the state
+  //                        in userPrevOutput / userPrevCell, which holds `state_rows` rows; the row tiles without a node are skipped
+  // keep_gates = false: only h and c of every step are kept, no gate value is stored (and with a table there is no gates buffer).
+  int forward_only(vd_model* m, hipStream_t s, const float* table, const float* x, int T_, int N_, const int32_t* mask, int flags,
+                   int state_rows, bool keep_gates, float** h_out) {
+    VD_TRY(take_state(m, s, state_rows));
+    if (keep_gates) {
+      VD_TRY(alloc(m, T_, N_));
     } else {
-      if (flags & VD_FLAG_LIVE_PREFIX) {
+      T = T_; N = N_;
+      VD_TRY(ws_get(m, name + ".h", (size_t)T * N * H, &h));
+      VD_TRY(ws_get(m, name + ".c", (size_t)T * N * H, &c));
+      if (!table) VD_TRY(ws_get(m, name + ".gates", (size_t)T * N * 4 * H, &gates));   // the projection's buffer only
+    }
+    xs.clear(); tok_mask = mask; rows = nullptr;
+    float* gates_out = keep_gates ? gates : nullptr;
+    if (table) {
+      VD_TRY(vd_lstm_forward(table, 0, 4 * H, mask, mask, Wh(m), h0, c0, gates_out, h, c, T, N, (int)H, flags, s));
+    } else {
+      if (flags & (VD_FLAG_LIVE_PREFIX | VD_FLAG_TREE)) {
         for (int t = 0; t < T; ++t)
           VD_TRY(vd_gemm_nn_live_p(x + (long)t * N * D, D, Wx(m), 4 * H, Wp(m, name + ".b"), gates + (long)t * N * 4 * H, 4 * H, N, (int)(4 * H),
-                                   (int)D, tok + (long)t * N, vd_lstm_fwd_row_tile(N), s));
+                                   (int)D, mask + (long)t * N, vd_lstm_fwd_row_tile(N), s));
       } else {
         VD_TRY(vd_gemm_nn(x, D, Wx(m), 4 * H, Wp(m, name + ".b"), gates, 4 * H, T * N, (int)(4 * H), (int)D, 0, s));
       }
-      VD_TRY(vd_lstm_forward(gates, (int64_t)N * 4 * H, 4 * H, nullptr, tok, Wh(m), h0, c0, gates, h, c, T, N, (int)H, flags, s));
-    }
-    if (h_out) *h_out = h;
-    return VD_OK;
-  }
-  // Forward-only pass over a forest, level by level (generative retrieval over a prefix tree, rt_decoders.h): mask2 [2 x T x N] = token |
-  // parent row (VD_FLAG_TREE); the parents of level 0 are rows of the R-row state in userPrevOutput / userPrevCell.  Layer 1 gathers
-  // `table` by token id; a higher layer projects `x` (the h of the layer below, same node rows) per step into its projection buffer,
-  // skipping the row tiles without a node.  Only h and c of every level are kept: no gate value is stored.
-  int forward_tree(vd_model* m, hipStream_t s, const float* table, const float* x, int T_, int N_, int R_, const int32_t* mask2, float** h_out) {
-    VD_TRY(take_state(m, s, R_));
-    T = T_; N = N_;
-    VD_TRY(ws_get(m, name + ".h", (size_t)T * N * H, &h));
-    VD_TRY(ws_get(m, name + ".c", (size_t)T * N * H, &c));
-    xs.clear(); tok_mask = mask2; rows = nullptr;
-    if (table) {
-      VD_TRY(vd_lstm_forward(table, 0, 4 * H, mask2, mask2, Wh(m), h0, c0, nullptr, h, c, T, N, (int)H, VD_FLAG_TREE, s));
-    } else {
-      VD_TRY(ws_get(m, name + ".gates", (size_t)T * N * 4 * H, &gates));
-      for (int t = 0; t < T; ++t)
-        VD_TRY(vd_gemm_nn_live_p(x + (long)t * N * D, D, Wx(m), 4 * H, Wp(m, name + ".b"), gates + (long)t * N * 4 * H, 4 * H, N, (int)(4 * H),
-                                 (int)D, mask2 + (long)t * N, vd_lstm_fwd_row_tile(N), s));
-      VD_TRY(vd_lstm_forward(gates, (int64_t)N * 4 * H, 4 * H, nullptr, mask2, Wh(m), h0, c0, nullptr, h, c, T, N, (int)H, VD_FLAG_TREE, s));
+      VD_TRY(vd_lstm_forward(gates, (int64_t)N * 4 * H, 4 * H, nullptr, mask, Wh(m), h0, c0, gates_out, h, c, T, N, (int)H, flags, s));
     }
     if (h_out) *h_out = h;
     return VD_OK;

@@ -394,16 +394,182 @@ struct Gen : Decoder {
   }
   // Model:retrieveBatch gen branch (model.lua:392-420) + utils.computeLhood (utils.lua:86-102).  The reference loops
   // over the 100 options; here chunks of options are ONE decoder batch (rows = round x option) seeded by the replicated
-  // encoder state, and the [rows x V] logits only ever exist for one chunk.
-  int retrieve(vd_model* m, BatchSlot& b) override { return retrieve_head(m, b, false); }
-  // vd_model_retrieve_lhood: the same encoder forward and forwardConnect replication; the candidates run through the decoder in order of
-  // descending length, the recurrence (SeqLSTM::forward_ordered) only where there are tokens; the head is vd_lhood_live_rows +
-  // vd_lhood_nll + vd_lhood_sum (csrc/lhood.hip) over the live rows of the chunk, with no logits buffer
-  // With VD_LHOOD_TREE (third mode): over a prefix tree of the candidates' tokens, retrieve_tree below; a batch the tree was not built
+  // encoder state, and the [rows x V] logits only ever exist for one chunk (retrieve_dense).
+  int retrieve(vd_model* m, BatchSlot& b) override {
+    Retrieval r;
+    VD_TRY(retrieve_begin(m, b, false, &r));
+    VD_TRY(retrieve_dense(m, b, r));
+    return retrieve_end(m, r);
+  }
+  // vd_model_retrieve_lhood: the same encoder forward; the head is csrc/lhood.hip's, with no logits buffer.  Where the chunk fits the
+  // order kernels the candidates run in order of descending length (retrieve_ordered), else as they come (retrieve_live).
+  // With VD_LHOOD_TREE (third mode): over a prefix tree of the candidates' tokens (retrieve_tree); a batch the tree was not built
   // for (a token behind a pad) takes the length-ordered path unchanged, and the counters then report that path
   int retrieve_lhood(vd_model* m, BatchSlot& b) override {
-    if (m->lhood_tree && b.tree_ok) return retrieve_tree(m, b);
-    return retrieve_head(m, b, true);
+    Retrieval r;
+    VD_TRY(retrieve_begin(m, b, true, &r));
+    if (m->lhood_tree && b.tree_ok) VD_TRY(retrieve_tree(m, b, r));
+    else if (vd_lhood_prefix_fits(r.T, (long)r.N * std::min(r.O, r.oc))) VD_TRY(retrieve_ordered(m, b, r));
+    else VD_TRY(retrieve_live(m, b, r));
+    return retrieve_end(m, r);
+  }
+
+  // What every retrieval mode starts from: the encoder forward on the main stream, the [N x O] score buffer, the options per chunk, and
+  // (log-likelihood head) the counters of vd_model_option_rows, which the mode adds its executed rows to.
+  struct Retrieval {
+    hipStream_t s;
+    int N, O, T, seqLen, oc;
+    float *encOut, *lhood;
+  };
+  int retrieve_begin(vd_model* m, BatchSlot& b, bool live, Retrieval* r) {
+    VD_CHECK_ARG(b.oin.present && b.oout.present, "retrieval with decoder 'gen' needs batch.option_in / option_out");
+    r->s = m->s_main;
+    r->N = b.q.N; r->O = m->p.numOptions; r->T = b.oin.T;
+    VD_TRY(m->enc->forward(m, r->s, b, &r->encOut));
+    r->seqLen = m->enc->seqLen(b);
+    VD_TRY(ws_get(m, "ret.lhood", (size_t)r->N * r->O, &r->lhood));
+    // floats one option adds to a chunk's workspace.  Dense head: the [T*N x Vp] logits dominate, <= 4 GiB of them.  Live-row head:
+    // what is still materialised is the decoder's input and saved state, (E + 6 H per layer: gates 4H, h, c) floats per (step, row),
+    // held to the same 4 GiB -- and to the 32-bit row byte offsets of h in the fused kernel (T * rows * H * 4 < 4 GiB, implied).
+    const long per_opt = (long)r->T * r->N * (live ? E + 6 * H * (long)rnn.size() : Vp);
+    r->oc = (int)std::max<long>(1, std::min<long>(r->O, (1L << 30) / std::max<long>(1, per_opt)));
+    if (live) {
+      m->lhood_exec = 0;
+      m->lhood_total = (long)r->T * r->N * r->O;
+    }
+    return VD_OK;
+  }
+  int retrieve_end(vd_model* m, const Retrieval& r) {
+    m->scores = r.lhood;
+    m->prof_valid = false;
+    return VD_OK;
+  }
+  // layer 1's input projection of every token id, Emb * Wx + b, made once per retrieval (the ordered and the tree recurrence gather it)
+  int retrieve_table(vd_model* m, hipStream_t s, float** table) {
+    VD_TRY(ws_get(m, "ret.table", (size_t)(V + 1) * 4 * H, table));
+    return vd_gemm_nn(Wp(m, "embed"), E, rnn[0].Wx(m), 4 * H, Wp(m, rnn[0].name + ".b"), *table, 4 * H, (int)V + 1, (int)(4 * H), (int)E, 0, s);
+  }
+  // options [o0, o0 + C) of the batch as one decoder batch: cin / cout [T x rows] = those columns of option_in / option_out
+  // [T*N x O] (a strided dword copy), nll [T x rows] for the chunk's head
+  struct Chunk {
+    int o0, C;
+    long rows;
+    int32_t *cin, *cout;
+    float* nll;
+  };
+  int retrieve_chunk(vd_model* m, BatchSlot& b, const Retrieval& r, int o0, Chunk* k) {
+    k->o0 = o0;
+    k->C = std::min(r.O, o0 + r.oc) - o0;
+    k->rows = (long)r.N * k->C;
+    VD_TRY(ws_get(m, "ret.cin", (size_t)r.T * k->rows, &k->cin));
+    VD_TRY(ws_get(m, "ret.cout", (size_t)r.T * k->rows, &k->cout));
+    VD_TRY(vd_copy_2d((float*)k->cin, k->C, (const float*)(b.oin.tok + o0), r.O, (long)r.T * r.N, k->C, r.s));
+    VD_TRY(vd_copy_2d((float*)k->cout, k->C, (const float*)(b.oout.tok + o0), r.O, (long)r.T * r.N, k->C, r.s));
+    return ws_get(m, "ret.nll", (size_t)r.T * k->rows, &k->nll);
+  }
+  // forwardConnect replication over the chunk in candidate order, the embedded tokens, the decoder stack over every (step, row)
+  int retrieve_chunk_forward(vd_model* m, const Retrieval& r, const Chunk& k, float** h) {
+    std::vector<int32_t> hidx(k.rows);
+    for (long i = 0; i < k.rows; ++i) hidx[i] = (int32_t)(i / k.C);
+    int32_t* idx;
+    float* x;
+    VD_TRY(index_array(m, "idx.ret." + std::to_string(k.rows) + "." + std::to_string(k.C), hidx, &idx));
+    VD_TRY(forwardConnect(m, r.s, r.encOut, r.seqLen, idx, k.rows));
+    VD_TRY(ws_get(m, "ret.x", (size_t)r.T * k.rows * E, &x));
+    VD_TRY(vd_embed_gather(Wp(m, "embed"), k.cin, nullptr, x, r.T * k.rows, (int)E, 1.f, r.s));
+    return lstm_stack_forward(m, r.s, rnn, {x}, r.T, (int)k.rows, k.cin, h);
+  }
+  // the live-row list of a chunk and the scratch of vd_lhood_live_rows
+  int retrieve_act(vd_model* m, const Retrieval& r, const Chunk& k, int32_t** act, int32_t** work) {
+    VD_TRY(ws_get(m, "ret.act", (size_t)r.T * k.rows, act));
+    return ws_get(m, "ret.act_work", (size_t)(r.T * k.rows + 1023) / 1024 + 1, work);
+  }
+
+  // vocabulary projection of every (step, row) into logits + log-softmax NLL, summed over time
+  int retrieve_dense(vd_model* m, BatchSlot& b, const Retrieval& r) {
+    hipStream_t s = r.s;
+    for (int o0 = 0; o0 < r.O; o0 += r.oc) {
+      Chunk k;
+      float *h, *logits, *acc;
+      VD_TRY(retrieve_chunk(m, b, r, o0, &k));
+      VD_TRY(retrieve_chunk_forward(m, r, k, &h));
+      VD_TRY(ws_get(m, "ret.logits", (size_t)r.T * k.rows * Vp, &logits));
+      VD_TRY(ws_get(m, "ret.acc", (size_t)k.rows, &acc));
+      VD_TRY(vd_gemm_nt(h, H, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), logits, Vp, (int)(r.T * k.rows), (int)V, (int)H, VD_ACT_NONE, 0, s));
+      VD_TRY(vd_logsoftmax_nll(logits, Vp, r.T * k.rows, (int)V, k.cin, k.cout, k.nll, 0, s));
+      VD_TRY(vd_memset(acc, 0, k.rows * 4, s));
+      VD_TRY(vd_colsum_acc(k.nll, k.rows, r.T, (int)k.rows, acc, s));                // sum over time (utils.lua:98)
+      VD_TRY(vd_copy_2d(r.lhood + o0, r.O, acc, k.C, r.N, k.C, s));
+    }
+    return vd_axpby(r.lhood, nullptr, r.lhood, (long)r.N * r.O, -1.f, 0.f, s);       // log-likelihood = -NLL
+  }
+  // the same decoder pass; the head is vd_lhood_live_rows + vd_lhood_nll + vd_lhood_sum over the live rows of the chunk
+  int retrieve_live(vd_model* m, BatchSlot& b, const Retrieval& r) {
+    for (int o0 = 0; o0 < r.O; o0 += r.oc) {
+      Chunk k;
+      float* h;
+      int32_t *act, *work, n_act = 0;
+      VD_TRY(retrieve_chunk(m, b, r, o0, &k));
+      VD_TRY(retrieve_chunk_forward(m, r, k, &h));
+      VD_TRY(retrieve_act(m, r, k, &act, &work));
+      VD_TRY(vd_lhood_live_rows(k.cin, k.cout, r.T * k.rows, act, work, &n_act, r.s));   // the chunk's one host synchronisation
+      VD_TRY(vd_lhood_nll(h, H, r.T * k.rows, act, n_act, k.cout, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), (int)V, (int)H, k.nll, r.s));
+      VD_TRY(vd_lhood_sum(k.nll, act, n_act, r.T, k.rows, k.C, r.lhood + o0, r.O, r.s));   // log-likelihood = -NLL, summed over time
+      m->lhood_exec += (long)r.T * k.rows;
+    }
+    return VD_OK;
+  }
+  // The chunk's candidates go through the decoder in order of descending length (lhood_order_*, csrc/lhood.hip), so that the live rows
+  // of every step are a prefix of the rows and the recurrence can skip the rest (VD_FLAG_LIVE_PREFIX).  Layer 1 then reads its input
+  // projection from the table by token id; vd_lhood_sum_p scatters the scores back to candidate order.
+  int retrieve_ordered(vd_model* m, BatchSlot& b, const Retrieval& r) {
+    hipStream_t s = r.s;
+    const int T = r.T;
+    float* table;
+    VD_TRY(retrieve_table(m, s, &table));
+    for (int o0 = 0; o0 < r.O; o0 += r.oc) {
+      Chunk k;
+      VD_TRY(retrieve_chunk(m, b, r, o0, &k));
+      const long rows = k.rows;
+      int32_t *perm, *rep, *cin_s, *cout_s, *owork, *info, *act, *work, n_act = 0;
+      void* info_host;
+      VD_TRY(ws_get(m, "ret.perm", (size_t)rows, &perm));
+      VD_TRY(ws_get(m, "ret.rep", (size_t)rows, &rep));
+      VD_TRY(ws_get(m, "ret.cin_s", (size_t)T * rows, &cin_s));
+      VD_TRY(ws_get(m, "ret.cout_s", (size_t)T * rows, &cout_s));
+      VD_TRY(ws_get(m, "ret.order_work", (size_t)vd_lhood_order_work_ints(T, rows), &owork));
+      VD_TRY(ws_get(m, "ret.order_info", (size_t)T + 1, &info));
+      VD_TRY(pin_get(b.pinned, "ret.order_info", ((size_t)T + 1) * sizeof(int32_t), &info_host));
+      VD_TRY(retrieve_act(m, r, k, &act, &work));
+      VD_TRY(vd_lhood_order_p(k.cin, k.cout, T, rows, k.C, perm, rep, cin_s, cout_s, owork, info, s));
+      VD_HIP(hipMemcpyAsync(info_host, info, ((size_t)T + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      // the chunk's one host synchronisation, in front of the recurrence (it depends on the tokens only): the live-row count, and
+      // with it the order's status word and per-step counts
+      VD_TRY(vd_lhood_live_rows(cin_s, cout_s, T * rows, act, work, &n_act, s));
+      const int32_t* hinfo = static_cast<const int32_t*>(info_host);
+      // a candidate that is not one left-aligned run: no prefix promise -- the chunk runs every row, as without the order
+      const int flags = hinfo[0] ? 0 : VD_FLAG_LIVE_PREFIX;
+      int Tl = T;   // steps behind the longest candidate hold no token at all: not launched
+      long ran = (long)T * rows;
+      if (flags) {
+        const long tile = vd_lstm_fwd_row_tile(rows);
+        Tl = 1;
+        ran = 0;
+        for (int t = 0; t < T; ++t) {
+          if (hinfo[1 + t] > 0) Tl = t + 1;
+          ran += std::min<long>(rows, (hinfo[1 + t] + tile - 1) / tile * tile);
+        }
+      }
+      m->lhood_exec += ran;
+      float* h;
+      VD_TRY(forwardConnect(m, s, r.encOut, r.seqLen, rep, rows));
+      VD_TRY(rnn[0].forward_only(m, s, table, nullptr, Tl, (int)rows, cin_s, flags, (int)rows, true, &h));
+      for (size_t l = 1; l < rnn.size(); ++l) VD_TRY(rnn[l].forward_only(m, s, nullptr, h, Tl, (int)rows, cin_s, flags, (int)rows, true, &h));
+      VD_TRY(vd_lhood_nll(h, H, Tl * rows, act, n_act, cout_s,   // (every live row lies in the Tl steps that ran)
+                           Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), (int)V, (int)H, k.nll, s));
+      VD_TRY(vd_lhood_sum_p(k.nll, act, n_act, T, rows, k.C, perm, r.lhood + o0, r.O, s));   // log-likelihood = -NLL, summed over time
+    }
+    return VD_OK;
   }
   // The decoder state after a candidate's first t tokens depends on the round's encoder state and on those tokens only, so the chunk's
   // candidates run as a forest: one node per distinct (round, token prefix), levels packed densely (no pad rows, no length order), the
@@ -411,19 +577,11 @@ struct Gen : Decoder {
   // (vd_lhood_lse_p: the log-sum-exp belongs to the prefix), and a candidate's score is the sum over its edges of target logit - lse
   // (vd_lhood_edge_sum_p), written straight into candidate order.  The host built every list at upload time (runtime.hip
   // build_lhood_tree): the step needs no host synchronisation.
-  int retrieve_tree(vd_model* m, BatchSlot& b) {
-    VD_CHECK_ARG(b.oin.present && b.oout.present, "retrieval with decoder 'gen' needs batch.option_in / option_out");
-    hipStream_t s = m->s_main;
-    const int N = b.q.N, O = m->p.numOptions, T = b.oin.T;
-    float* encOut;
-    VD_TRY(m->enc->forward(m, s, b, &encOut));
-    const int seqLen = m->enc->seqLen(b);
-    float *lhood, *table;
-    VD_TRY(ws_get(m, "ret.lhood", (size_t)N * O, &lhood));
-    VD_TRY(ws_get(m, "ret.table", (size_t)(V + 1) * 4 * H, &table));
-    VD_TRY(vd_gemm_nn(Wp(m, "embed"), E, rnn[0].Wx(m), 4 * H, Wp(m, rnn[0].name + ".b"), table, 4 * H, (int)V + 1, (int)(4 * H), (int)E, 0, s));
-    m->lhood_exec = 0;
-    m->lhood_total = (long)T * N * O;
+  int retrieve_tree(vd_model* m, BatchSlot& b, const Retrieval& r) {
+    hipStream_t s = r.s;
+    const int N = r.N;
+    float* table;
+    VD_TRY(retrieve_table(m, s, &table));
     for (const TreeChunk& tc : b.tree) {
       const long rows = (long)N * tc.C;
       const long tile = vd_lstm_fwd_row_tile(tc.Nw);
@@ -431,124 +589,14 @@ struct Gen : Decoder {
       float *h = nullptr, *lse;
       VD_TRY(ws_get(m, "ret.lse", (size_t)std::max<long>(1, tc.n_nodes), &lse));
       if (tc.Tl > 0) {
-        VD_TRY(forwardConnect(m, s, encOut, seqLen, nullptr, N));
-        VD_TRY(rnn[0].forward_tree(m, s, table, nullptr, tc.Tl, tc.Nw, N, tc.mask2, &h));
-        for (size_t l = 1; l < rnn.size(); ++l) VD_TRY(rnn[l].forward_tree(m, s, nullptr, h, tc.Tl, tc.Nw, N, tc.mask2, &h));
+        VD_TRY(forwardConnect(m, s, r.encOut, r.seqLen, nullptr, N));
+        VD_TRY(rnn[0].forward_only(m, s, table, nullptr, tc.Tl, tc.Nw, tc.mask2, VD_FLAG_TREE, N, false, &h));
+        for (size_t l = 1; l < rnn.size(); ++l) VD_TRY(rnn[l].forward_only(m, s, nullptr, h, tc.Tl, tc.Nw, tc.mask2, VD_FLAG_TREE, N, false, &h));
         VD_TRY(vd_lhood_lse_p(h, H, (long)tc.Tl * tc.Nw, tc.node_row, tc.n_nodes, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), (int)V, (int)H, lse, s));
       }
       VD_TRY(vd_lhood_edge_sum_p(h, H, tc.node_row, lse, tc.enode, tc.etgt, tc.Tl, rows, tc.C, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), (int)H,
-                                 lhood + tc.o0, O, s));
+                                 r.lhood + tc.o0, r.O, s));
     }
-    m->scores = lhood;
-    m->prof_valid = false;
-    return VD_OK;
-  }
-  int retrieve_head(vd_model* m, BatchSlot& b, bool live) {
-    VD_CHECK_ARG(b.oin.present && b.oout.present, "retrieval with decoder 'gen' needs batch.option_in / option_out");
-    hipStream_t s = m->s_main;
-    const int N = b.q.N, O = m->p.numOptions, T = b.oin.T;
-    float* encOut;
-    VD_TRY(m->enc->forward(m, s, b, &encOut));
-    const int seqLen = m->enc->seqLen(b);
-    float* lhood;
-    VD_TRY(ws_get(m, "ret.lhood", (size_t)N * O, &lhood));
-    // floats one option adds to a chunk's workspace.  Dense head: the [T*N x Vp] logits dominate, <= 4 GiB of them.  Live-row head:
-    // what is still materialised is the decoder's input and saved state, (E + 6 H per layer: gates 4H, h, c) floats per (step, row),
-    // held to the same 4 GiB -- and to the 32-bit row byte offsets of h in the fused kernel (T * rows * H * 4 < 4 GiB, implied).
-    const long per_opt = (long)T * N * (live ? E + 6 * H * (long)rnn.size() : Vp);
-    const int oc = (int)std::max<long>(1, std::min<long>(O, (1L << 30) / std::max<long>(1, per_opt)));
-    // Live-row head: the chunk's candidates go through the decoder in order of descending length (lhood_order_*, csrc/lhood.hip), so
-    // that the live rows of every step are a prefix of the rows and the recurrence can skip the rest (VD_FLAG_LIVE_PREFIX).  Layer 1
-    // then reads its input projection from the table Emb * Wx + b by token id, made once per retrieval.
-    const bool ordered = live && vd_lhood_prefix_fits(T, (long)N * std::min(O, oc));
-    float* table = nullptr;
-    if (ordered) {
-      VD_TRY(ws_get(m, "ret.table", (size_t)(V + 1) * 4 * H, &table));
-      VD_TRY(vd_gemm_nn(Wp(m, "embed"), E, rnn[0].Wx(m), 4 * H, Wp(m, rnn[0].name + ".b"), table, 4 * H, (int)V + 1, (int)(4 * H), (int)E, 0, s));
-    }
-    if (live) {
-      m->lhood_exec = 0;
-      m->lhood_total = (long)T * N * O;
-    }
-    for (int o0 = 0; o0 < O; o0 += oc) {
-      const int C = std::min(O, o0 + oc) - o0;
-      const long rows = (long)N * C;
-      int32_t *cin, *cout, *idx;
-      VD_TRY(ws_get(m, "ret.cin", (size_t)T * rows, &cin));
-      VD_TRY(ws_get(m, "ret.cout", (size_t)T * rows, &cout));
-      // [T*N x O] int32 -> columns [o0, o0+C): a strided dword copy
-      VD_TRY(vd_copy_2d((float*)cin, C, (const float*)(b.oin.tok + o0), O, (long)T * N, C, s));
-      VD_TRY(vd_copy_2d((float*)cout, C, (const float*)(b.oout.tok + o0), O, (long)T * N, C, s));
-      float *x, *h, *logits, *nll, *acc;
-      VD_TRY(ws_get(m, "ret.nll", (size_t)T * rows, &nll));
-      if (ordered) {
-        int32_t *perm, *cin_s, *cout_s, *owork, *info, *act, *work, n_act = 0;
-        void* info_host;
-        VD_TRY(ws_get(m, "ret.perm", (size_t)rows, &perm));
-        VD_TRY(ws_get(m, "ret.rep", (size_t)rows, &idx));
-        VD_TRY(ws_get(m, "ret.cin_s", (size_t)T * rows, &cin_s));
-        VD_TRY(ws_get(m, "ret.cout_s", (size_t)T * rows, &cout_s));
-        VD_TRY(ws_get(m, "ret.order_work", (size_t)vd_lhood_order_work_ints(T, rows), &owork));
-        VD_TRY(ws_get(m, "ret.order_info", (size_t)T + 1, &info));
-        VD_TRY(pin_get(b.pinned, "ret.order_info", ((size_t)T + 1) * sizeof(int32_t), &info_host));
-        VD_TRY(ws_get(m, "ret.act", (size_t)T * rows, &act));
-        VD_TRY(ws_get(m, "ret.act_work", (size_t)(T * rows + 1023) / 1024 + 1, &work));
-        VD_TRY(vd_lhood_order_p(cin, cout, T, rows, C, perm, idx, cin_s, cout_s, owork, info, s));
-        VD_HIP(hipMemcpyAsync(info_host, info, ((size_t)T + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        // the chunk's one host synchronisation, now in front of the recurrence (it depends on the tokens only): the live-row count, and
-        // with it the order's status word and per-step counts
-        VD_TRY(vd_lhood_live_rows(cin_s, cout_s, T * rows, act, work, &n_act, s));
-        const int32_t* hinfo = static_cast<const int32_t*>(info_host);
-        // a candidate that is not one left-aligned run: no prefix promise -- the chunk runs every row, as without the order
-        const int flags = hinfo[0] ? 0 : VD_FLAG_LIVE_PREFIX;
-        int Tl = T;   // steps behind the longest candidate hold no token at all: not launched
-        long ran = (long)T * rows;
-        if (flags) {
-          const long tile = vd_lstm_fwd_row_tile(rows);
-          Tl = 1;
-          ran = 0;
-          for (int t = 0; t < T; ++t) {
-            if (hinfo[1 + t] > 0) Tl = t + 1;
-            ran += std::min<long>(rows, (hinfo[1 + t] + tile - 1) / tile * tile);
-          }
-        }
-        m->lhood_exec += ran;
-        VD_TRY(forwardConnect(m, s, encOut, seqLen, idx, rows));
-        VD_TRY(rnn[0].forward_ordered(m, s, table, nullptr, Tl, (int)rows, cin_s, flags, &h));
-        for (size_t l = 1; l < rnn.size(); ++l) VD_TRY(rnn[l].forward_ordered(m, s, nullptr, h, Tl, (int)rows, cin_s, flags, &h));
-        VD_TRY(vd_lhood_nll(h, H, Tl * rows, act, n_act, cout_s,   // (every live row lies in the Tl steps that ran)
-                             Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), (int)V, (int)H, nll, s));
-        VD_TRY(vd_lhood_sum_p(nll, act, n_act, T, rows, C, perm, lhood + o0, O, s));     // log-likelihood = -NLL, summed over time
-        continue;
-      }
-      std::vector<int32_t> hidx(rows);
-      for (long r = 0; r < rows; ++r) hidx[r] = (int32_t)(r / C);
-      VD_TRY(index_array(m, "idx.ret." + std::to_string(rows) + "." + std::to_string(C), hidx, &idx));
-      VD_TRY(forwardConnect(m, s, encOut, seqLen, idx, rows));
-      VD_TRY(ws_get(m, "ret.x", (size_t)T * rows * E, &x));
-      VD_TRY(vd_embed_gather(Wp(m, "embed"), cin, nullptr, x, T * rows, (int)E, 1.f, s));
-      VD_TRY(lstm_stack_forward(m, s, rnn, {x}, T, (int)rows, cin, &h));
-      if (live) {
-        int32_t *act, *work, n_act = 0;
-        VD_TRY(ws_get(m, "ret.act", (size_t)T * rows, &act));
-        VD_TRY(ws_get(m, "ret.act_work", (size_t)(T * rows + 1023) / 1024 + 1, &work));
-        VD_TRY(vd_lhood_live_rows(cin, cout, T * rows, act, work, &n_act, s));        // the chunk's one host synchronisation
-        VD_TRY(vd_lhood_nll(h, H, T * rows, act, n_act, cout, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), (int)V, (int)H, nll, s));
-        VD_TRY(vd_lhood_sum(nll, act, n_act, T, rows, C, lhood + o0, O, s));          // log-likelihood = -NLL, summed over time
-        m->lhood_exec += (long)T * rows;
-        continue;
-      }
-      VD_TRY(ws_get(m, "ret.logits", (size_t)T * rows * Vp, &logits));
-      VD_TRY(ws_get(m, "ret.acc", (size_t)rows, &acc));
-      VD_TRY(vd_gemm_nt(h, H, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), logits, Vp, (int)(T * rows), (int)V, (int)H, VD_ACT_NONE, 0, s));
-      VD_TRY(vd_logsoftmax_nll(logits, Vp, T * rows, (int)V, cin, cout, nll, 0, s));
-      VD_TRY(vd_memset(acc, 0, rows * 4, s));
-      VD_TRY(vd_colsum_acc(nll, rows, T, (int)rows, acc, s));                       // sum over time (utils.lua:98)
-      VD_TRY(vd_copy_2d(lhood + o0, O, acc, C, N, C, s));
-    }
-    if (!live) VD_TRY(vd_axpby(lhood, nullptr, lhood, (long)N * O, -1.f, 0.f, s));  // log-likelihood = -NLL
-    m->scores = lhood;
-    m->prof_valid = false;
     return VD_OK;
   }
 };

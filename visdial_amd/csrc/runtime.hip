@@ -706,7 +706,7 @@ static int begin_step(vd_model* m, bool zero_grads, BatchSlot** out) {
   VD_CHECK_ARG(m && m->uploaded >= 0, "no batch uploaded");
   m->cur = m->uploaded;
   m->enc_grads_recorded = false;
-  m->lhood_exec = -1;   // vd_model_option_rows describes the last step call (Gen::retrieve_head sets it again)
+  m->lhood_exec = -1;   // vd_model_option_rows describes the last step call (Gen::retrieve_begin sets it again)
   BatchSlot& b = m->slot[m->cur];
   m->N = b.q.N;
   m->O = m->p.numOptions;

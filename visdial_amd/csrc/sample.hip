@@ -22,7 +22,7 @@
 //     (double)logp[c] unless an earlier column 1..s-1 holds <END> (the <END> itself counts).
 // The stepped LSTM state becoming the current one (decoderConnect, gen.lua:63-68) is the caller's copy.
 //
-// Top-k / nucleus truncation (a model created with VD_SAMPLE_TOPK / VD_SAMPLE_TOPP; sample_draw_trunc_kernel, reached only through
+// Top-k / nucleus truncation (a model created with VD_SAMPLE_TOPK / VD_SAMPLE_TOPP; sample_draw_kernel<true>, reached only through
 // vd_model_sample): between rules 2 and 3 every column outside the kept set gets weight 0, rules 3-5 run on what is left and the
 // log-likelihood still adds the UNtruncated logp[c].  The host statement is split_eval.truncated_weights.  The kept set:
 //  T1. order: logp descending as fp32 values (-0 = +0), equal values by ascending column.  key(c) = the bits of logp[c] for a
@@ -65,78 +65,6 @@ __global__ void sample_init_kernel(long rows, int cols, int start, int32_t* __re
 __device__ __forceinline__ double sample_weight(const float* row, int c, float lse, bool zero_row, double temperature) {
   const float lp = zero_row ? 0.f : row[c] - lse;
   return exp((double)lp / temperature);
-}
-
-// rules 1-5 for one row per workgroup
-__global__ void __launch_bounds__(256)
-sample_draw_kernel(const float* __restrict__ x, long ld, int V, int32_t* __restrict__ tok, const double* __restrict__ u,
-                   double temperature, int step, int cols, int end_tok, int32_t* __restrict__ hist, double* __restrict__ loglik,
-                   int32_t* __restrict__ status) {
-  __shared__ float red[8];
-  __shared__ double wtot[4];
-  __shared__ int owner, last_pos, pick;
-  const long r = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* row = x + r * ld;
-  const bool zero_row = tok[r] == 0;
-  float lse = 0.f;
-  if (!zero_row) lse = block_row_lse(row, V, red);   // rule 1
-
-  // rules 2-3: chunk sums, then the block's exclusive scan of them
-  const int chunk = (V + 255) / 256;
-  const int c0 = min(V, tid * chunk), c1 = min(V, c0 + chunk);
-  double part = 0.0;
-  for (int c = c0; c < c1; ++c) part += sample_weight(row, c, lse, zero_row, temperature);
-  double incl = part;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double y = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += y;
-  }
-  double excl = __shfl_up(incl, 1, 64);
-  if (lane == 0) excl = 0.0;
-  if (lane == 63) wtot[wave] = incl;
-  if (tid == 0) { owner = 256; last_pos = -1; pick = -1; }
-  __syncthreads();
-  double off = 0.0;
-  for (int w = 0; w < wave; ++w) off += wtot[w];
-  excl = off + excl;
-  const double S = (wtot[0] + wtot[1]) + (wtot[2] + wtot[3]);
-  if (S == 0.0) {                        // rule 4 (block-uniform)
-    if (tid == 0) { *status = 1; hist[r * cols + step] = 0; tok[r] = 0; }
-    return;
-  }
-  const double target = u[r] * S;
-  if (part > 0.0 && excl + part > target) atomicMin(&owner, tid);
-  if (part > 0.0) atomicMax(&last_pos, tid);
-  __syncthreads();
-  if (owner < 256) {
-    if (tid == owner) {
-      double run = 0.0;
-      for (int c = c0; c < c1; ++c) {
-        const double w = sample_weight(row, c, lse, zero_row, temperature);
-        run += w;
-        if (w > 0.0 && excl + run > target) { pick = c; break; }
-      }
-    }
-  } else if (tid == last_pos) {          // u within rounding of 1
-    for (int c = c1 - 1; c >= c0; --c)
-      if (sample_weight(row, c, lse, zero_row, temperature) > 0.0) { pick = c; break; }
-  }
-  __syncthreads();
-  if (tid != 0) return;
-  const int c = pick;
-  if (c < 0) {                           // rule 4: NaN weights leave nothing to draw from
-    *status = 1; hist[r * cols + step] = 0; tok[r] = 0;
-    return;
-  }
-  const float lp = zero_row ? 0.f : row[c] - lse;
-  const int32_t* h = hist + r * cols;
-  bool ended = false;
-  for (int p = 1; p < step; ++p) ended = ended || h[p] == end_tok;
-  if (!ended) loglik[r] += (double)lp;
-  hist[r * cols + step] = c + 1;
-  tok[r] = c + 1;
 }
 
 // ---- top-k / nucleus truncation (T1-T4 of the header) ----------------------------------------------------------------------------
@@ -220,16 +148,15 @@ __device__ __forceinline__ void trunc_pick_bin(unsigned long long mine, bool wit
   __syncthreads();
 }
 
-// rules 1-5 with T1-T4 for one row per workgroup
+// rules 1-5 for one row per workgroup; TRUNC: with T1-T4 between rules 2 and 3 (top_k / top_p are read with TRUNC only)
+template <bool TRUNC>
 __global__ void __launch_bounds__(256)
-sample_draw_trunc_kernel(const float* __restrict__ x, long ld, int V, int32_t* __restrict__ tok, const double* __restrict__ u,
-                         double temperature, int top_k, double top_p, int step, int cols, int end_tok, int32_t* __restrict__ hist,
-                         double* __restrict__ loglik, int32_t* __restrict__ status) {
+sample_draw_kernel(const float* __restrict__ x, long ld, int V, int32_t* __restrict__ tok, const double* __restrict__ u,
+                   double temperature, int top_k, double top_p, int step, int cols, int end_tok, int32_t* __restrict__ hist,
+                   double* __restrict__ loglik, int32_t* __restrict__ status) {
   __shared__ float red[8];
   __shared__ double wtot[4];
   __shared__ int owner, last_pos, pick;
-  __shared__ TruncShared sh;
-  __shared__ int tie_col;
   const long r = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* row = x + r * ld;
@@ -237,78 +164,88 @@ sample_draw_trunc_kernel(const float* __restrict__ x, long ld, int V, int32_t* _
   float lse = 0.f, lp_max = 0.f;
   if (!zero_row) {
     lse = block_row_lse(row, V, red);   // rule 1
-    lp_max = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) - lse;   // the row maximum block_row_lse left behind
+    if constexpr (TRUNC) lp_max = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) - lse;   // the row maximum block_row_lse left behind
   }
-
-  // T4, first pass: shared by both selects, each thread keeps its bin
-  const bool with_mass = top_p < 1.0;
-  if (tid == 0) { sh.bin = 255; sh.rem = 0; sh.below = 0; tie_col = V - 1; }
-  trunc_histogram(row, V, lse, zero_row, lp_max, temperature, with_mass, 0u, 24, sh);
-  const uint32_t cnt1 = sh.cnt[tid];
-  const unsigned long long mass1 = sh.mass[tid];
-  uint32_t B = 0xffffffffu;          // boundary key and how many of its ties are kept
-  unsigned long long ties = 0;
-  bool cut = false;
-  unsigned long long Q;
-  {
-    unsigned long long t;
-    (void)block_scan_u64(mass1, sh.wt, &t);
-    Q = t;
-  }
-  if (top_k > 0) {                   // T2 (block-uniform: kernel arguments only)
-    uint32_t prefix = 0;
-    unsigned long long target = (unsigned long long)top_k;
-    for (int pass = 0; pass < 4; ++pass) {
-      const int shift = 24 - 8 * pass;
-      if (pass) trunc_histogram(row, V, lse, zero_row, lp_max, temperature, with_mass, prefix, shift, sh);
-      trunc_pick_bin(pass ? sh.cnt[tid] : cnt1, with_mass, pass ? sh.mass[tid] : mass1, target, sh);
-      prefix |= sh.bin << shift;
-      target = sh.rem;
-    }
-    B = prefix;
-    ties = target;
-    cut = true;
-    Q = sh.below + ties * trunc_mass(trunc_key_value(B), lp_max, temperature);
-  }
-  if (top_p < 1.0 && Q > 0) {        // T3 (block-uniform: Q comes from shared memory)
-    const double want = ceil(top_p * (double)Q);
-    unsigned long long target = want >= 1.0 ? (unsigned long long)want : 1ull;
-    if (target > Q) target = Q;
-    uint32_t prefix = 0;
-    for (int pass = 0; pass < 4; ++pass) {
-      const int shift = 24 - 8 * pass;
-      if (pass) trunc_histogram(row, V, lse, zero_row, lp_max, temperature, with_mass, prefix, shift, sh);
-      trunc_pick_bin(pass ? sh.mass[tid] : mass1, false, 0ull, target, sh);
-      prefix |= sh.bin << shift;
-      target = sh.rem;
-    }
-    B = prefix;
-    const unsigned long long qb = trunc_mass(trunc_key_value(B), lp_max, temperature);
-    ties = qb ? (target + qb - 1) / qb : 1ull;
-    cut = true;
-  }
-
-  // rules 2-3 on the kept set; chunks as in sample_draw_kernel
-  const int chunk = (V + 255) / 256;
+  const int chunk = (V + 255) / 256;   // thread t owns the columns [c0, c1)
   const int c0 = min(V, tid * chunk), c1 = min(V, c0 + chunk);
-  if (cut) {                         // T4: the column of the last tie kept
-    unsigned long long mine = 0;
-    for (int c = c0; c < c1; ++c) mine += trunc_key(zero_row ? 0.f : row[c] - lse) == B;
-    unsigned long long tot;
-    const unsigned long long incl = block_scan_u64(mine, sh.wt, &tot);
-    if (incl - mine < ties && ties <= incl) {
-      unsigned long long seen = incl - mine;
-      for (int c = c0; c < c1; ++c)
-        if (trunc_key(zero_row ? 0.f : row[c] - lse) == B && ++seen == ties) { tie_col = c; break; }
+
+  uint32_t B = 0xffffffffu;            // the kept set {key < B} + {key = B and c <= I}: every column unless T2 / T3 cut
+  int I = V - 1;
+  if constexpr (TRUNC) {
+    __shared__ TruncShared sh;
+    __shared__ int tie_col;
+    // T4, first pass: shared by both selects, each thread keeps its bin
+    const bool with_mass = top_p < 1.0;
+    if (tid == 0) { sh.bin = 255; sh.rem = 0; sh.below = 0; tie_col = V - 1; }
+    trunc_histogram(row, V, lse, zero_row, lp_max, temperature, with_mass, 0u, 24, sh);
+    const uint32_t cnt1 = sh.cnt[tid];
+    const unsigned long long mass1 = sh.mass[tid];
+    unsigned long long ties = 0;       // how many of the boundary key's ties are kept
+    bool cut = false;
+    unsigned long long Q;
+    {
+      unsigned long long t;
+      (void)block_scan_u64(mass1, sh.wt, &t);
+      Q = t;
     }
-    __syncthreads();
+    if (top_k > 0) {                   // T2 (block-uniform: kernel arguments only)
+      uint32_t prefix = 0;
+      unsigned long long target = (unsigned long long)top_k;
+      for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        if (pass) trunc_histogram(row, V, lse, zero_row, lp_max, temperature, with_mass, prefix, shift, sh);
+        trunc_pick_bin(pass ? sh.cnt[tid] : cnt1, with_mass, pass ? sh.mass[tid] : mass1, target, sh);
+        prefix |= sh.bin << shift;
+        target = sh.rem;
+      }
+      B = prefix;
+      ties = target;
+      cut = true;
+      Q = sh.below + ties * trunc_mass(trunc_key_value(B), lp_max, temperature);
+    }
+    if (top_p < 1.0 && Q > 0) {        // T3 (block-uniform: Q comes from shared memory)
+      const double want = ceil(top_p * (double)Q);
+      unsigned long long target = want >= 1.0 ? (unsigned long long)want : 1ull;
+      if (target > Q) target = Q;
+      uint32_t prefix = 0;
+      for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        if (pass) trunc_histogram(row, V, lse, zero_row, lp_max, temperature, with_mass, prefix, shift, sh);
+        trunc_pick_bin(pass ? sh.mass[tid] : mass1, false, 0ull, target, sh);
+        prefix |= sh.bin << shift;
+        target = sh.rem;
+      }
+      B = prefix;
+      const unsigned long long qb = trunc_mass(trunc_key_value(B), lp_max, temperature);
+      ties = qb ? (target + qb - 1) / qb : 1ull;
+      cut = true;
+    }
+    if (cut) {                         // T4: the column of the last tie kept
+      unsigned long long mine = 0;
+      for (int c = c0; c < c1; ++c) mine += trunc_key(zero_row ? 0.f : row[c] - lse) == B;
+      unsigned long long tot;
+      const unsigned long long incl = block_scan_u64(mine, sh.wt, &tot);
+      if (incl - mine < ties && ties <= incl) {
+        unsigned long long seen = incl - mine;
+        for (int c = c0; c < c1; ++c)
+          if (trunc_key(zero_row ? 0.f : row[c] - lse) == B && ++seen == ties) { tie_col = c; break; }
+      }
+      __syncthreads();
+    }
+    I = tie_col;
   }
-  const int I = tie_col;
+  // rule 2 on the kept set
   auto weight = [&](int c) -> double {
-    const float lp = zero_row ? 0.f : row[c] - lse;
-    const uint32_t k = trunc_key(lp);
-    return (k < B || (k == B && c <= I)) ? exp((double)lp / temperature) : 0.0;
+    if constexpr (TRUNC) {
+      const float lp = zero_row ? 0.f : row[c] - lse;
+      const uint32_t k = trunc_key(lp);
+      return (k < B || (k == B && c <= I)) ? exp((double)lp / temperature) : 0.0;
+    } else {
+      return sample_weight(row, c, lse, zero_row, temperature);
+    }
   };
+
+  // rules 2-3: chunk sums, then the block's exclusive scan of them
   double part = 0.0;
   for (int c = c0; c < c1; ++c) part += weight(c);
   double incl = part;
@@ -363,6 +300,24 @@ sample_draw_trunc_kernel(const float* __restrict__ x, long ld, int V, int32_t* _
   tok[r] = c + 1;
 }
 
+// vd_sample_draw and vd_sample_draw_trunc_p (TRUNC) behind their argument lists; `who` prefixes the error texts
+template <bool TRUNC>
+int sample_draw(const char* who, const float* logits, int64_t ld, int64_t rows, int V, int32_t* tok, const double* uniforms, double temperature,
+                int top_k, double top_p, int step, int beam_len, int end_token, int32_t* hist, double* loglik, int32_t* status,
+                hipStream_t stream) {
+  VD_CHECK_ARG(logits && tok && uniforms && hist && loglik && status && rows >= 0 && V >= 1 && ld >= V, "%s: bad args", who);
+  VD_CHECK_ARG(std::isfinite(temperature) && temperature > 0, "%s: temperature %g must be finite and > 0", who, temperature);
+  VD_CHECK_ARG(step >= 1 && step <= beam_len, "%s: step %d outside [1, %d]", who, step, beam_len);
+  if constexpr (TRUNC)
+    VD_CHECK_ARG(top_k >= 0 && top_k < V && top_p > 0.0 && top_p <= 1.0 && (top_k > 0 || top_p < 1.0) && V < (1 << 23),
+                 "%s: top_k %d must lie in [0, V = %d), top_p %g in (0, 1], one of them on, V below 2^23", who, top_k, V, top_p);
+  if (rows == 0) return VD_OK;
+  hipLaunchKernelGGL(sample_draw_kernel<TRUNC>, dim3((unsigned)rows), dim3(256), 0, stream, logits, (long)ld, V, tok, uniforms, temperature,
+                     top_k, top_p, step, beam_len + 1, end_token, hist, loglik, status);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -378,14 +333,8 @@ int vd_sample_init(int64_t rows, int beam_len, int start_token, int32_t* hist, i
 
 int vd_sample_draw(const float* logits, int64_t ld, int64_t rows, int V, int32_t* tok, const double* uniforms, double temperature,
                    int step, int beam_len, int end_token, int32_t* hist, double* loglik, int32_t* status, void* stream) {
-  VD_CHECK_ARG(logits && tok && uniforms && hist && loglik && status && rows >= 0 && V >= 1 && ld >= V, "vd_sample_draw: bad args");
-  VD_CHECK_ARG(std::isfinite(temperature) && temperature > 0, "vd_sample_draw: temperature %g must be finite and > 0", temperature);
-  VD_CHECK_ARG(step >= 1 && step <= beam_len, "vd_sample_draw: step %d outside [1, %d]", step, beam_len);
-  if (rows == 0) return VD_OK;
-  hipLaunchKernelGGL(sample_draw_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, V, tok, uniforms,
-                     temperature, step, beam_len + 1, end_token, hist, loglik, status);
-  VD_LAUNCH_CHECK();
-  return VD_OK;
+  return sample_draw<false>("vd_sample_draw", logits, ld, rows, V, tok, uniforms, temperature, 0, 1.0, step, beam_len, end_token, hist, loglik,
+                            status, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -395,14 +344,6 @@ int vd_sample_draw(const float* logits, int64_t ld, int64_t rows, int V, int32_t
 int vd_sample_draw_trunc_p(const float* logits, int64_t ld, int64_t rows, int V, int32_t* tok, const double* uniforms, double temperature,
                            int top_k, double top_p, int step, int beam_len, int end_token, int32_t* hist, double* loglik, int32_t* status,
                            hipStream_t stream) {
-  VD_CHECK_ARG(logits && tok && uniforms && hist && loglik && status && rows >= 0 && V >= 1 && ld >= V, "vd_sample_draw_trunc_p: bad args");
-  VD_CHECK_ARG(std::isfinite(temperature) && temperature > 0, "vd_sample_draw_trunc_p: temperature %g must be finite and > 0", temperature);
-  VD_CHECK_ARG(step >= 1 && step <= beam_len, "vd_sample_draw_trunc_p: step %d outside [1, %d]", step, beam_len);
-  VD_CHECK_ARG(top_k >= 0 && top_k < V && top_p > 0.0 && top_p <= 1.0 && (top_k > 0 || top_p < 1.0) && V < (1 << 23),
-               "vd_sample_draw_trunc_p: top_k %d must lie in [0, V = %d), top_p %g in (0, 1], one of them on, V below 2^23", top_k, V, top_p);
-  if (rows == 0) return VD_OK;
-  hipLaunchKernelGGL(sample_draw_trunc_kernel, dim3((unsigned)rows), dim3(256), 0, stream, logits, (long)ld, V, tok, uniforms, temperature,
-                     top_k, top_p, step, beam_len + 1, end_token, hist, loglik, status);
-  VD_LAUNCH_CHECK();
-  return VD_OK;
+  return sample_draw<true>("vd_sample_draw_trunc_p", logits, ld, rows, V, tok, uniforms, temperature, top_k, top_p, step, beam_len, end_token,
+                           hist, loglik, status, stream);
 }
