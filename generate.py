@@ -12,10 +12,12 @@ from visdial_amd import opts, utils
 from visdial_amd.dataloader import Dataloader
 from visdial_amd.model import Model
 from visdial_amd.checkpoint import load_checkpoint, restore_weights
+from visdial_amd.split_eval import check_beam_groups
 
 
 def parse_args(argv=None):
-    """the command line as the `opts` of the results file; refuses top-k / nucleus truncation without -sampleWords 1"""
+    """the command line as the `opts` of the results file; refuses top-k / nucleus truncation without -sampleWords 1 and beam groups
+    that do not divide -beamSize, with a bad -beamDiversity or with -sampleWords 1"""
     ap = argparse.ArgumentParser(description='Test the VisDial model for generation')
     ap.add_argument('-inputImg', '--inputImg', default='data/data_img.h5')
     ap.add_argument('-inputQues', '--inputQues', default='data/visdial_data.h5')
@@ -37,6 +39,11 @@ def parse_args(argv=None):
     ap.add_argument('-topP', '--topP', type=float, default=1.0,
                     help='< 1 (with -sampleWords 1): sample from the smallest set of most likely words holding that share of the '
                          'probability (after -topK; 1 = off)')
+    ap.add_argument('-beamGroups', '--beamGroups', type=int, default=1,
+                    help='> 1: diverse beam search -- the -beamSize slots search in that many groups (it must divide -beamSize), '
+                         'every round also gets `answers`, one per group (1 = off)')
+    ap.add_argument('-beamDiversity', '--beamDiversity', type=float, default=0.5,
+                    help='(with -beamGroups > 1) what a word costs a group for every earlier group that chose it at that step')
     ap.add_argument('-seed', '--seed', type=int, default=1234, help='seed of the sampling generator (numpy RandomState)')
     ap.add_argument('-gpuid', '--gpuid', type=int, default=0)
     ap.add_argument('-host', '--host', default='python', choices=['python', 'native'],
@@ -46,6 +53,9 @@ def parse_args(argv=None):
         raise ValueError('-topK %d must be >= 0 (0 = off) and -topP %g in (0, 1] (1 = off)' % (a['topK'], a['topP']))
     if (a['topK'] != 0 or a['topP'] != 1.0) and a['sampleWords'] != 1:
         raise ValueError('-topK / -topP truncate the sampled distribution: they need -sampleWords 1 (beam search does not truncate)')
+    check_beam_groups(a['beamSize'], a['beamGroups'], a['beamDiversity'])
+    if a['beamGroups'] > 1 and a['sampleWords'] == 1:
+        raise ValueError('-beamGroups > 1 is diverse beam search: sampling (-sampleWords 1) has no groups')
     return a
 
 
@@ -63,7 +73,8 @@ def main():
         p[k] = getattr(dl, k)
     if a['host'] == 'native':
         from visdial_amd.native import NativeModel
-        model = NativeModel(dict(p, topK=a['topK'], topP=a['topP']))       # the device sampler takes its truncation at creation
+        # the device sampler takes its truncation, the device search its groups, at creation
+        model = NativeModel(dict(p, topK=a['topK'], topP=a['topP'], beamGroups=a['beamGroups'], beamDiversity=a['beamDiversity']))
     else:
         model = Model(p)
     restore_weights(model, saved, a['paramOrder'] or None)
@@ -71,7 +82,8 @@ def main():
                                                     maxThreads=a['maxThreads'], sampleWords=a['sampleWords'],
                                                     temperature=a['temperature'], beamBatch=a['beamBatch'],
                                                     sampleBatch=a['sampleBatch'], seed=a['seed'],
-                                                    topK=a['topK'], topP=a['topP']))
+                                                    topK=a['topK'], topP=a['topP'], beamGroups=a['beamGroups'],
+                                                    beamDiversity=a['beamDiversity']))
     os.makedirs(a['resultPath'], exist_ok=True)
     path = os.path.join(a['resultPath'], 'results.json')
     utils.writeJSON(path, {'opts': a, 'data': answers})

@@ -458,7 +458,17 @@ int vd_model_decode_select(vd_model* m, const int32_t* src, int n_keep);
 /* the whole beam search of Model:generateAnswers (model.lua:466-573) for EVERY round of the last vd_model_encode batch at once,
  * on the device (the vd_beam_* kernels above): N = B*R groups of beam_size hypotheses, beam_len-1 steps enqueued without a host
  * synchronisation, then one copy back.  host_tokens [N x beam_len] = each round's answer (best finished column, else column 0;
- * zero-padded), host_scores [N] its fp64 score.  Same answers as the host loop over decode_begin / step / select. */
+ * zero-padded), host_scores [N] its fp64 score.  Same answers as the host loop over decode_begin / step / select.
+ *
+ * !! LAYOUT CHANGE UNDER VD_BEAM_GROUPS !!  A model created with the environment variable VD_BEAM_GROUPS = G > 1 (decoder gen; an
+ * integer >= 1, 1 / unset = off) runs DIVERSE beam search (Vijayakumar et al. 2016, Hamming diversity; the rule is D1-D7 at the top of
+ * csrc/beam.hip): the beam_size slots of a round are G groups of beam_size / G, searched one after another within a step, a group's
+ * log-probabilities lowered by VD_BEAM_DIVERSITY (a finite real >= 0, unset = 0.5) for every slot of an earlier group that took the
+ * same word at that step.  Such a model REFUSES a beam_size that G does not divide and writes EVERY group's answer:
+ *   host_tokens [N x G x beam_len], host_scores [N x G]   (round-major, then group) -- G times the buffers of a plain model.
+ * A score is the answer's true (unpenalised) log-likelihood.  The caller picks the round's answer: the highest score among the
+ * groups whose answer holds end_token, ties to the lower group; group 0's if none does.  vd_model_create reads both variables once
+ * and refuses any other value by name; both are ignored for decoder disc.  decode_begin / step / select need nothing new. */
 int vd_model_beam_search(vd_model* m, int beam_size, int beam_len, int start_token, int end_token, int32_t* host_tokens,
                          double* host_scores);
 /* temperature sampling of Model:generateAnswers (sampleWords = 1, model.lua:576-613) for EVERY round of the last vd_model_encode

@@ -5,7 +5,10 @@ H = 512, V = 11 322, 2 layers, length 20, random weights; beam 5, or sampling at
 many dialogs have identical records.
     python scripts/mb_generate.py --mode beam|sample [dialogs] [--only batched]   (--only batched: the device path alone, for a trace)
     --mode sample --topK k --topP p: top-k / nucleus truncation on both paths (the model is created with the knobs: the device sampler
-    takes them at vd_model_create)"""
+    takes them at vd_model_create)
+    --mode beam --beamSize k --beamGroups G --beamDiversity l: diverse beam search on both paths (the model is created with the knobs);
+    also prints the share of rounds whose G answers are not all the same.  --vocabScale s multiplies the vocabulary projection of the
+    random model (60 = the peaked rows of test_beam_search_gpu.full_size_fixture; near-uniform rows otherwise)"""
 import argparse
 import os
 import sys
@@ -24,10 +27,17 @@ ap.add_argument('--mode', choices=('beam', 'sample'), required=True)
 ap.add_argument('--only', choices=('batched',), help='the device path alone, for a kernel trace')
 ap.add_argument('--topK', type=int, default=0, help='--mode sample: sample among the k most likely words (0 = off)')
 ap.add_argument('--topP', type=float, default=1.0, help='--mode sample: nucleus truncation (1 = off)')
+ap.add_argument('--beamSize', type=int, default=5, help='--mode beam: slots per round')
+ap.add_argument('--beamGroups', type=int, default=1, help='--mode beam: diverse beam search in that many groups (1 = off)')
+ap.add_argument('--beamDiversity', type=float, default=0.5, help='--mode beam with --beamGroups > 1: the penalty per earlier choice')
+ap.add_argument('--vocabScale', type=float, default=1.0, help='multiply vocab.W of the random model (peaked rows)')
 opt = ap.parse_args()
 MODE_KNOBS = opt.topK != 0 or opt.topP != 1.0
 if MODE_KNOBS and opt.mode != 'sample':
     ap.error('--topK / --topP truncate sampling: use --mode sample')
+GROUPS = opt.beamGroups
+if (GROUPS != 1 or opt.beamSize != 5) and opt.mode != 'beam':
+    ap.error('--beamSize / --beamGroups belong to beam search: use --mode beam')
 MODE, D, ONLY_BATCHED = opt.mode, opt.dialogs, opt.only == 'batched'
 V, R = 11322, 10
 
@@ -50,11 +60,21 @@ class Dialogs(object):
 p = derive(default_params(encoder='lf-ques-im-hist', decoder='gen', vocabSize=V, embedSize=300, rnnHiddenSize=512, imgFeatureSize=4096,
                           numLayers=2, maxQuesCount=R, maxQuesLen=20, maxAnsLen=20, maxHistoryLenPerRound=40, batchSize=20, gpuid=0))
 dl = Dialogs(p, D)
-nat = NativeModel(dict(p, topK=opt.topK, topP=opt.topP) if MODE_KNOBS else p, init_seed=1)
+knobs = dict(topK=opt.topK, topP=opt.topP) if MODE_KNOBS else {}
+if GROUPS != 1:
+    knobs.update(beamGroups=GROUPS, beamDiversity=opt.beamDiversity)
+nat = NativeModel(dict(p, **knobs), init_seed=1)
 nat.training(False)
+if opt.vocabScale != 1.0:
+    P = nat.get_parameters_dict()
+    P['vocab.W'] = P['vocab.W'] * np.float32(opt.vocabScale)
+    nat.set_parameters_dict(P)
 if MODE == 'beam':
-    key, cfg = 'beamBatch', dict(beamSize=5, beamLen=20, maxThreads=D)
+    key, cfg = 'beamBatch', dict(beamSize=opt.beamSize, beamLen=20, maxThreads=D)
     what = 'beam %d' % cfg['beamSize']
+    if GROUPS != 1:
+        cfg.update(beamGroups=GROUPS, beamDiversity=opt.beamDiversity)
+        what += ' in %d groups (diversity %g)' % (GROUPS, opt.beamDiversity)
 else:
     key, cfg = 'sampleBatch', dict(sampleWords=1, beamLen=20, temperature=1.0, maxThreads=D, seed=1234, topK=opt.topK, topP=opt.topP)
     what = 'sampling' + (' (topK %d, topP %g)' % (opt.topK, opt.topP) if MODE_KNOBS else '')
@@ -75,4 +95,8 @@ for b in ((20,) if ONLY_BATCHED else (0, 20)):
 if not ONLY_BATCHED:
     same = sum(a == b for a, b in zip(res[0], res[20]))
     print("speed-up %.1fx; dialogs with identical records: %d of %d" % (res[0, 't'] / res[20, 't'], same, D))
+if GROUPS > 1:
+    rounds = [e['answers'] for d in out for e in d['dialog']]
+    print("rounds whose %d answers are not all the same: %d of %d; distinct answers per round on average: %.2f" % (
+        GROUPS, sum(len(set(a)) > 1 for a in rounds), len(rounds), float(np.mean([len(set(a)) for a in rounds]))))
 nat.close()

@@ -19,9 +19,38 @@
 //  3. the answer is the finished candidate with the highest score, ties to the earliest inserted (step, then w, then rank);
 //     if nothing finished, column 0 (the reference errors there).
 //  4. all beamLen-1 steps run: zero rows can still add finished candidates.
+//
+// Diverse beam search (Vijayakumar et al. 2016, Hamming diversity) extends rules 1-4.  (In D1-D7 a "group" is one of the G beam groups
+// WITHIN a round; the `groups` argument of the kernels and entry points below counts the units that keep one finished set: rounds in
+// the plain search, (round, beam group) pairs in the grouped one.)  beamGroups G >= 1 divides k, k' = k / G, group
+// g owns slots g k' .. g k' + k' - 1 of its round, beamDiversity lambda is a finite real >= 0; G = 1 is rules 1-4 unchanged.
+// split_eval.py:beam_search_round restates D1-D7 on the host.
+//  D1. rule 1 for every slot: every group starts from <START>, the round's encoder state and score 0.
+//  D2. at step s = 1 .. beamLen-1 the groups run in the order g = 0 .. G-1.  count[v] = the number of slots of groups 0 .. g-1 of the
+//      same round that were FILLED (slot i < n_keep of D6) with word v at this step: all zero for group 0, from zero at every step.
+//      <END> never enters a slot, so it is never counted and never penalised.
+//  D3. a group explores its first slot only at s == 1, all k' slots after that.  An explored slot's row is rule 2's: log-softmax, or
+//      all zero if the slot's input token is 0.
+//  D4. the row is penalised in fp32: a[v] = logp[v] - (float)lambda * (float)count[v], product and difference rounded separately (no
+//      fused multiply-add: __fmul_rn / __fsub_rn).  The slot's candidates are the top k' of a, value descending, index ascending.  An
+//      all-zero row is penalised the same way.
+//  D5. a candidate of slot w with word v carries two fp64 sums: the KEY scores[w] + (double)a[v], which only orders the unfinished
+//      candidates of this group at this step, and the SCORE scores[w] + (double)logp[v], the true log-likelihood, which is carried
+//      into the slot and reported.
+//  D6. rule 2 within the group: insertion order (w, rank in D4); <END> candidates go to the group's own finished set with their score;
+//      the rest are sorted stably by descending key and the first n_keep = min(#cands, k') fill the group's slots 0 .. n_keep-1 with
+//      column, score and the stepped state of the source slot; slots >= n_keep keep column, score and pre-step state.
+//  D7. a group's answer is its best finished candidate by score, ties to the earliest inserted; its first slot's column and score if
+//      it finished nothing.  The round's answer is the highest-scoring answer among the groups that finished something, ties to the
+//      lower group; group 0's if none did.  All beamLen-1 steps run.
+// A penalty only lowers a value, and at most (G-1) k' distinct words are penalised, so the top k' of a penalised row lie within the
+// top k of the unpenalised one: beam_topk_kernel at the full k delivers everything a grouped step needs.  Per (round, group) the best
+// finished candidate, the initial state and the answer are rule 1 / rule 3 of N * G groups of k' slots, so beam_init_kernel and
+// beam_finish_kernel serve as they are.
 #include "common.h"
 
 #define VD_BEAM_KMAX 32
+#define VD_BEAM_GKMAX (VD_BEAM_KMAX / 2)   // k' = k / G of a grouped search (G >= 2)
 
 namespace {
 
@@ -173,6 +202,110 @@ beam_advance_kernel(const int32_t* __restrict__ top_idx, const float* __restrict
   }
 }
 
+// D2-D6 for one round per workgroup, its G groups one after another (a group's penalties need the earlier groups' slots).  `count` is
+// a list of (word, multiplicity) pairs, at most one per slot.  Per group: the k candidates of every explored slot (beam_topk_kernel's,
+// unpenalised order) get their penalised value and their rank under it; the ranks < k' are the slot's candidates, candidate
+// c = w * k' + rank (insertion order), and from there on this is beam_advance_kernel on the group's k' slots with the key ordering the
+// unfinished candidates and the score carried.  best_* are per (round, group); `src` stays a round-local slot index.
+__global__ void __launch_bounds__(256)
+beam_advance_grouped_kernel(const int32_t* __restrict__ top_idx, const float* __restrict__ top_val, int k, int G, float lambda, int step,
+                            int L, int end_tok, double* __restrict__ scores, const int32_t* __restrict__ hist_in,
+                            int32_t* __restrict__ hist_out, int32_t* __restrict__ src, int32_t* __restrict__ next_tok,
+                            double* __restrict__ best_score, int32_t* __restrict__ best_len, int32_t* __restrict__ best_hist) {
+  __shared__ float pen[VD_BEAM_GKMAX * VD_BEAM_KMAX];
+  __shared__ double ckey[VD_BEAM_GKMAX * VD_BEAM_GKMAX], csc[VD_BEAM_GKMAX * VD_BEAM_GKMAX];
+  __shared__ int ctok[VD_BEAM_GKMAX * VD_BEAM_GKMAX];
+  __shared__ double slot_sc[VD_BEAM_GKMAX];
+  __shared__ int slot_src[VD_BEAM_GKMAX], slot_tok[VD_BEAM_GKMAX];
+  __shared__ int cnt_word[VD_BEAM_KMAX], cnt_mult[VD_BEAM_KMAX];
+  __shared__ int n_cnt, n_cands, best_c;
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const long r0 = (long)r * k;
+  const int kp = k / G, explore = step == 1 ? 1 : kp, C = explore * kp, E = explore * k;
+  if (tid == 0) n_cnt = 0;
+  for (int g = 0; g < G; ++g) {
+    const long g0 = r0 + (long)g * kp;                             // the group's first hypothesis row
+    __syncthreads();                                               // the earlier group is done with the tables; its counts are in
+    if (tid == 0) { n_cands = 0; best_c = -1; }
+    if (tid < VD_BEAM_GKMAX) { slot_src[tid] = 0; slot_tok[tid] = 0; slot_sc[tid] = 0.0; }   // valid even if a NaN left a place unfilled
+    for (int c = tid; c < C; c += blockDim.x) { ctok[c] = 0; ckey[c] = 0.0; csc[c] = 0.0; }
+    for (int e = tid; e < E; e += blockDim.x) {                    // D4
+      const int w = e / k, q = e - w * k;
+      const long t = (g0 + w) * k + q;
+      const int v = top_idx[t];
+      int mult = 0;
+      for (int j = 0; j < n_cnt; ++j) mult = cnt_word[j] == v ? cnt_mult[j] : mult;
+      pen[e] = __fsub_rn(top_val[t], __fmul_rn(lambda, (float)mult));
+    }
+    __syncthreads();
+    for (int e = tid; e < E; e += blockDim.x) {
+      const int w = e / k, q = e - w * k;
+      const long t0 = (g0 + w) * k;
+      const float av = pen[e];
+      const int ai = top_idx[t0 + q];
+      int rank = 0;
+      for (int q2 = 0; q2 < k; ++q2) rank += beam_better(pen[w * k + q2], top_idx[t0 + q2], av, ai) ? 1 : 0;
+      if (rank < kp) {                                             // D5
+        const int c = w * kp + rank;
+        const double s = scores[g0 + w];
+        ctok[c] = ai + 1;
+        ckey[c] = s + (double)av;
+        csc[c] = s + (double)top_val[t0 + q];
+      }
+    }
+    __syncthreads();
+    for (int c = tid; c < C; c += blockDim.x) {                    // D6
+      const bool fin = ctok[c] == end_tok;
+      const double v = fin ? csc[c] : ckey[c];
+      int pos = 0;
+      for (int c2 = 0; c2 < C; ++c2) {
+        if ((ctok[c2] == end_tok) != fin) continue;
+        const double v2 = fin ? csc[c2] : ckey[c2];
+        pos += (v2 > v || (v2 == v && c2 < c)) ? 1 : 0;
+      }
+      if (fin) {
+        if (pos == 0) best_c = c;
+      } else {
+        atomicAdd(&n_cands, 1);
+        if (pos < kp) { slot_sc[pos] = csc[c]; slot_src[pos] = c / kp; slot_tok[pos] = ctok[c]; }
+      }
+    }
+    __syncthreads();
+    const int n_keep = min(n_cands, kp);
+    if (tid == 0) {
+      const long bg = (long)r * G + g;
+      if (best_c >= 0) {
+        const double sc = csc[best_c];
+        if (best_len[bg] == 0 || sc > best_score[bg]) {
+          const int32_t* col = hist_in + (g0 + best_c / kp) * L;
+          best_score[bg] = sc;
+          best_len[bg] = step + 1;
+          for (int p = 0; p < L; ++p) best_hist[bg * L + p] = p < step ? col[p] : p == step ? end_tok : 0;
+        }
+      }
+      for (int i = 0; i < n_keep; ++i) {                           // D2: the filled slots' words, for the groups after this one
+        const int v = slot_tok[i] - 1;
+        int j = 0;
+        while (j < n_cnt && cnt_word[j] != v) ++j;
+        if (j == n_cnt) { cnt_word[j] = v; cnt_mult[j] = 0; n_cnt = j + 1; }
+        cnt_mult[j] += 1;
+      }
+    }
+    for (int e = tid; e < kp * L; e += blockDim.x) {
+      const int i = e / L, p = e - i * L;
+      int v;
+      if (i < n_keep) v = p == step ? slot_tok[i] : hist_in[(g0 + slot_src[i]) * L + p];
+      else v = hist_in[(g0 + i) * L + p];
+      hist_out[(g0 + i) * L + p] = v;
+      if (p == step) next_tok[g0 + i] = v;
+    }
+    for (int i = tid; i < kp; i += blockDim.x) {
+      src[g0 + i] = i < n_keep ? g * kp + slot_src[i] : -1;
+      if (i < n_keep) scores[g0 + i] = slot_sc[i];                 // the group's reads of `scores` are two barriers back
+    }
+  }
+}
+
 // cur[r] = stepped[group(r) * k + src[r]] where src[r] >= 0; the row is left alone otherwise
 __global__ void beam_select_rows_kernel(float* __restrict__ cur, const float* __restrict__ stepped, const int32_t* __restrict__ src,
                                         long rows, int k, int H) {
@@ -197,6 +330,23 @@ __global__ void beam_finish_kernel(int groups, int k, int L, const int32_t* __re
 }
 
 }  // namespace
+
+// the grouped vd_beam_advance (rt_core.h): `rounds` rounds of G groups of k / G slots; best_* are [rounds x G]
+int vd_beam_advance_grouped_p(const int32_t* top_idx, const float* top_val, int rounds, int k, int G, float lambda, int step, int beam_len,
+                              int end_token, double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok,
+                              double* best_score, int32_t* best_len, int32_t* best_hist, hipStream_t stream) {
+  VD_CHECK_ARG(top_idx && top_val && scores && hist_in && hist_out && src && next_tok && best_score && best_len && best_hist &&
+               rounds >= 0 && hist_in != hist_out, "vd_beam_advance_grouped: bad args");
+  VD_CHECK_ARG(k >= 2 && k <= VD_BEAM_KMAX && G >= 2 && k % G == 0, "vd_beam_advance_grouped: G = %d must be >= 2 and divide k = %d in [2, %d]",
+               G, k, VD_BEAM_KMAX);
+  VD_CHECK_ARG(lambda >= 0.f && lambda < INFINITY, "vd_beam_advance_grouped: lambda = %g must be finite and >= 0", (double)lambda);
+  VD_CHECK_ARG(step >= 1 && step < beam_len, "vd_beam_advance_grouped: step %d outside [1, %d)", step, beam_len);
+  if (rounds == 0) return VD_OK;
+  hipLaunchKernelGGL(beam_advance_grouped_kernel, dim3((unsigned)rounds), dim3(256), 0, stream, top_idx, top_val, k, G, lambda, step,
+                     beam_len, end_token, scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
 
 extern "C" {
 

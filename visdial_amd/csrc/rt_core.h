@@ -61,6 +61,12 @@ int vd_sample_draw_trunc_p(const float* logits, int64_t ld, int64_t rows, int V,
                            int top_k, double top_p, int step, int beam_len, int end_token, int32_t* hist, double* loglik, int32_t* status,
                            hipStream_t stream);
 
+// beam.hip: vd_beam_advance for a search in G >= 2 groups per round (VD_BEAM_GROUPS / VD_BEAM_DIVERSITY; the rule is beam.hip's header
+// D1-D7): `rounds` rounds of k slots, group g of a round owns slots g k/G .. ; best_score / best_len / best_hist are [rounds x G]
+int vd_beam_advance_grouped_p(const int32_t* top_idx, const float* top_val, int rounds, int k, int G, float lambda, int step, int beam_len,
+                              int end_token, double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok,
+                              double* best_score, int32_t* best_len, int32_t* best_hist, hipStream_t stream);
+
 #define VD_TRY(expr)                  \
   do {                                \
     const int rc__ = (expr);          \
@@ -256,6 +262,10 @@ struct vd_model {
   // VD_SAMPLE_TOPK / VD_SAMPLE_TOPP at vd_model_create (decoder gen): vd_model_sample draws from the top-k / nucleus kept set; 0 / 1 = off
   int sample_topk = 0;
   double sample_topp = 1.0;
+  // VD_BEAM_GROUPS / VD_BEAM_DIVERSITY at vd_model_create (decoder gen): vd_model_beam_search searches in that many groups per round
+  // with that Hamming diversity and returns every group's answer; 1 = the plain search
+  int beam_groups = 1;
+  double beam_diversity = 0.5;
   bool lhood_tree = false;   // VD_LHOOD_TREE at vd_model_create: vd_model_retrieve_lhood scores over a prefix tree of the candidates
   bool prof_hist = false;   // ev_prof[0..3] bracket the history branch of a Sequential encoder (gen pairs: vd_model_family_ms)
   ~vd_model();

@@ -757,13 +757,18 @@ inline int gen_read_back(vd_model* m, const void* out, size_t bytes, std::vector
   return VD_OK;
 }
 
-// Model:generateAnswers' beam search (model.lua:466-573): N groups of k slots = N * k hypothesis rows.  Per step: fused
+// Model:generateAnswers' beam search (model.lua:466-573): N rounds of k slots = N * k hypothesis rows.  Per step: fused
 // log-softmax + top-k -> advance (candidate bookkeeping, csrc/beam.hip) -> state select; then the best answer and score per round.
+// A model created with VD_BEAM_GROUPS = G > 1 searches every round in G groups of k / G slots (beam.hip D1-D7): the same top-k at the
+// full k, the grouped advance, the same select; the best-finished state, the start and the answers are those of N * G groups of k / G
+// slots, so init and finish take (N * G, k / G) and the answers come back [N x G x L] / [N x G].  G = 1 launches what it always did.
 inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end, int32_t* host_tokens, double* host_scores) {
   VD_CHECK_ARG(m->gen_enc_out && m->N > 0, "vd_model_beam_search: call vd_model_encode first");
   VD_CHECK_ARG(host_tokens && host_scores && L >= 1, "vd_model_beam_search: bad arguments");
   VD_CHECK_ARG(k >= 1 && k <= 32 && k <= g->V, "vd_model_beam_search: beam size %d must be in [1, min(32, vocabSize)]", k);
-  const int G = m->N, n = G * k;
+  const int groups = m->beam_groups;
+  VD_CHECK_ARG(k % groups == 0, "vd_model_beam_search: VD_BEAM_GROUPS = %d does not divide beam size %d", groups, k);
+  const int N = m->N, n = N * k, G = N * groups, kg = k / groups;           // G answers, each the best of kg slots
   VD_TRY(gen_batch_begin(g, m, k));
   hipStream_t s = m->s_main;
   int32_t *tok, *top_idx, *src, *hist[2], *best_len, *best_hist;
@@ -782,15 +787,19 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
   VD_TRY(ws_get(m, "beam.best_len", (size_t)G, &best_len));
   VD_TRY(ws_get(m, "beam.best_hist", (size_t)G * L, &best_hist));
   VD_TRY(ws_get(m, "beam.out", tok_bytes + (size_t)G * 8, &out));
-  VD_TRY(vd_beam_init(G, k, L, start, hist[0], tok, scores, best_score, best_len, s));
+  VD_TRY(vd_beam_init(G, kg, L, start, hist[0], tok, scores, best_score, best_len, s));
   VD_TRY(gen_batch_steps(g, m, L - 1, tok, src, k, [&](int step, float* logits) -> int {
     VD_TRY(vd_beam_topk(logits, g->Vp, n, (int)g->V, tok, k, top_idx, top_val, s));
-    VD_TRY(vd_beam_advance(top_idx, top_val, G, k, step, L, end, scores, hist[0], hist[1], src, tok, best_score, best_len, best_hist,
-                           s));
+    if (groups > 1)
+      VD_TRY(vd_beam_advance_grouped_p(top_idx, top_val, N, k, groups, (float)m->beam_diversity, step, L, end, scores, hist[0], hist[1], src,
+                                       tok, best_score, best_len, best_hist, s));
+    else
+      VD_TRY(vd_beam_advance(top_idx, top_val, G, k, step, L, end, scores, hist[0], hist[1], src, tok, best_score, best_len, best_hist,
+                             s));
     std::swap(hist[0], hist[1]);
     return VD_OK;
   }));
-  VD_TRY(vd_beam_finish(G, k, L, hist[0], scores, best_score, best_len, best_hist, reinterpret_cast<int32_t*>(out),
+  VD_TRY(vd_beam_finish(G, kg, L, hist[0], scores, best_score, best_len, best_hist, reinterpret_cast<int32_t*>(out),
                         reinterpret_cast<double*>(out + tok_bytes), s));
   std::vector<uint8_t> staged;
   VD_TRY(gen_read_back(m, out, tok_bytes + (size_t)G * 8, &staged));

@@ -16,6 +16,7 @@
 // projection + masks; also the history branch of lf-* / hre-*), tab (token sort + table gradient), copy (H2D uploads
 // of the NEXT batch; two batch slots).
 #include <errno.h>
+#include <float.h>
 
 #include "rt_decoders.h"
 
@@ -344,10 +345,33 @@ int vd_model_create(const vd_model_params* p, const char* encoder, const char* d
       sample_topp = v;
     }
   }
+  // diverse beam search of vd_model_beam_search (include/visdial_hip.h there): VD_BEAM_GROUPS = an integer >= 1 (1 / unset = off),
+  // VD_BEAM_DIVERSITY = a finite real >= 0 (unset = 0.5); anything else is refused.  Decoder disc has no beam search: ignored there.
+  int beam_groups = 1;
+  double beam_diversity = 0.5;
+  if (std::string(decoder) == "gen") {
+    if (const char* e = getenv("VD_BEAM_GROUPS")) {
+      char* end = nullptr;
+      errno = 0;
+      const long v = strtol(e, &end, 10);
+      VD_CHECK_ARG(*e && end && !*end && errno == 0 && v >= 1 && v <= INT32_MAX,
+                   "vd_model_create: VD_BEAM_GROUPS = '%s' must be an integer >= 1 (1 = off)", e);
+      beam_groups = (int)v;
+    }
+    if (const char* e = getenv("VD_BEAM_DIVERSITY")) {
+      char* end = nullptr;
+      const double v = strtod(e, &end);
+      VD_CHECK_ARG(*e && end && !*end && v >= 0.0 && v <= (double)FLT_MAX,   // a NaN fails both comparisons; lambda is applied in fp32
+                   "vd_model_create: VD_BEAM_DIVERSITY = '%s' must be a finite real >= 0", e);
+      beam_diversity = v;
+    }
+  }
   vd_model* m = new vd_model();
   m->p = *p;
   m->sample_topk = sample_topk;
   m->sample_topp = sample_topp;
+  m->beam_groups = beam_groups;
+  m->beam_diversity = beam_diversity;
   m->flags = flags;
   m->ocache.capacity = cache_rows;
   m->lhood_tree = lhood_tree;

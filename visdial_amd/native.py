@@ -75,11 +75,15 @@ class NativeModel(SplitEval):
         # params topK / topP: top-k / nucleus truncation inside vd_model_sample (VD_SAMPLE_TOPK / VD_SAMPLE_TOPP, read the same way).  The
         # values go through as written -- the library is the one that refuses a negative k, a p outside (0, 1] or text (decoder gen) -- and a
         # params without them creates the model with the variables unset.  generateAnswers(sampleBatch > 0) checks its knobs against these.
+        # params beamGroups / beamDiversity: diverse beam search inside vd_model_beam_search (VD_BEAM_GROUPS / VD_BEAM_DIVERSITY, read and
+        # refused the same way); generateAnswers(beamBatch > 0) checks its knobs against these.
         import os
         switches = {'VD_OPTION_CACHE': str(int(p.get('optionCache', 0) or 0)),
                     'VD_LHOOD_TREE': '1' if int(p.get('fusedLhood', 0) or 0) == 2 else '0',
                     'VD_SAMPLE_TOPK': None if p.get('topK') is None else str(p['topK']),
-                    'VD_SAMPLE_TOPP': None if p.get('topP') is None else str(p['topP'])}
+                    'VD_SAMPLE_TOPP': None if p.get('topP') is None else str(p['topP']),
+                    'VD_BEAM_GROUPS': None if p.get('beamGroups') is None else str(p['beamGroups']),
+                    'VD_BEAM_DIVERSITY': None if p.get('beamDiversity') is None else str(p['beamDiversity'])}
         prev = {k: os.environ.get(k) for k in switches}
         try:
             for k, v in switches.items():
@@ -96,6 +100,7 @@ class NativeModel(SplitEval):
                     os.environ[k] = v
         gen = p['decoder'] == 'gen'
         self._sample_knobs = (int(p.get('topK') or 0) if gen else 0, float(1.0 if p.get('topP') is None or not gen else p['topP']))
+        self._beam_knobs = (int(p.get('beamGroups') or 1) if gen else 1, float(0.5 if p.get('beamDiversity') is None else p['beamDiversity']))
         self.h = h
         lib = _lib.load()
         self.tensors = []
@@ -345,13 +350,24 @@ class NativeModel(SplitEval):
         call("vd_model_decode_select", self.h, s_.ctypes.data, int(n_keep))
 
     def _gen_beam(self, beamSize, beamLen, startToken, endToken):
-        """the batched beam search (beamBatch > 0) of every round of the last `_gen_encode` batch: vd_model_beam_search"""
-        N = int(self._N)
-        tokens = np.zeros((N, int(beamLen)), np.int32)
-        scores = np.zeros(N, np.float64)
+        """the batched beam search (beamBatch > 0) of every round of the last `_gen_encode` batch: vd_model_beam_search.  Returns (tokens
+        [N x beamLen], scores [N]); a model created with params beamGroups = G > 1 returns every group's answer, (tokens
+        [N x G x beamLen], scores [N x G])."""
+        N, G = int(self._N), self._beam_knobs[0]
+        tokens = np.zeros((N * G, int(beamLen)), np.int32)
+        scores = np.zeros(N * G, np.float64)
         call("vd_model_beam_search", self.h, int(beamSize), int(beamLen), int(startToken), int(endToken), tokens.ctypes.data,
              scores.ctypes.data)
+        if G > 1:
+            return tokens.reshape(N, G, int(beamLen)), scores.reshape(N, G)
         return tokens, scores
+
+    def _beam_grouping(self, groups, diversity):
+        G, lam = self._beam_knobs
+        if int(groups) != G or (G > 1 and float(diversity) != lam):
+            raise ValueError("beamBatch > 0 with beamGroups = %d / beamDiversity = %g, but this model was created with beamGroups = %d / "
+                             "beamDiversity = %g: the device search takes its groups when the model is created (params beamGroups / "
+                             "beamDiversity of NativeModel)" % (int(groups), float(diversity), G, lam))
 
     def _sample_truncation(self, topK, topP):
         if (int(topK), float(topP)) != self._sample_knobs:

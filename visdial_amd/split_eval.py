@@ -8,7 +8,9 @@ batched beam search (params beamBatch > 0) `_gen_beam(beamSize, beamLen, startTo
 [N])` over every round of the last `_gen_encode` batch (= vd_model_beam_search; the operator-level host composes the vd_beam_*
 kernels), and for batched sampling (params sampleBatch > 0) `_gen_sample(beamLen, startToken, endToken, temperature, uniforms
 [beamLen x N]) -> (tokens [N x (beamLen + 1)], log-likelihoods [N])` (= vd_model_sample; vd_sample_* for the operator-level host), with
-`_sample_truncation(topK, topP)` raising unless that sampler truncates with exactly these knobs."""
+`_sample_truncation(topK, topP)` raising unless that sampler truncates with exactly these knobs.  Diverse beam search (params
+beamGroups = G > 1): `_beam_grouping(groups, diversity)` raises unless that `_gen_beam` searches in exactly these groups, and it then
+returns every group's answer, (tokens [N x G x beamLen], scores [N x G])."""
 import math
 
 import numpy as np
@@ -43,6 +45,100 @@ def truncated_weights(logp, temperature, topK=0, topP=1.0):
         n = max(1, min(reach, n, int((w[order[:n]] > 0).sum())))
     out = np.zeros_like(w)
     out[order[:n]] = w[order[:n]]
+    return out
+
+
+def check_beam_groups(beamSize, groups, diversity):
+    """the refusals of diverse beam search (csrc/beam.hip D1-D7): G >= 1 divides beamSize, lambda (unused at G = 1) is a finite real >= 0"""
+    if groups < 1 or beamSize % groups != 0:
+        raise ValueError('beamGroups = %d must be >= 1 and divide beamSize = %d' % (groups, beamSize))
+    if groups > 1 and not (np.isfinite(np.float32(diversity)) and diversity >= 0.0):     # applied in fp32
+        raise ValueError('beamDiversity = %r must be a finite real >= 0' % (diversity,))
+
+
+def pick_answer(answers, endToken):
+    """D7: the round's answer among its groups' (tokens, score): the highest score of the groups that finished something (a finished
+    answer holds <END>, a slot's column never does), ties to the lower group; group 0's if none finished"""
+    best = None
+    for tokens, score in answers:
+        if endToken in np.asarray(tokens) and (best is None or score > best[1]):
+            best = (tokens, score)
+    return best if best is not None else answers[0]
+
+
+def beam_search_round(step_fn, select_fn, k, L, start, end, groups=1, diversity=0.5):
+    """The beam search of ONE round on the host (model.lua:466-573): `step_fn(tokens [k]) -> logp [k x V]` is one decoder step of the k
+    slots (a slot whose token is 0 gets an all-zero row), `select_fn(src, n_keep)` makes slot i < n_keep continue from the stepped
+    state of slot src[i]; the slots start from the round's encoder state (`_gen_begin`).  Returns one (tokens [L], score) per group.
+    groups = 1 is the reference's search (rules 1-4 of csrc/beam.hip); groups = G > 1 is diverse beam search with Hamming diversity
+    `diversity`, D1-D7 there: group g owns slots g k' .. g k' + k' - 1 (k' = k / G), the groups of a step run in order, a group's row
+    is penalised in fp32 by diversity * (the number of earlier groups' slots filled with that word at this step), the penalised
+    values pick and order the candidates (the key), the unpenalised sum is the score that is carried and reported."""
+    check_beam_groups(k, groups, diversity)
+    beamSize, beamLen, startToken, endToken = k, L, start, end
+    beams = np.zeros((beamLen, beamSize), np.int64)
+    beams[0] = startToken
+    scores = np.zeros(beamSize)
+    if groups == 1:
+        finish = []
+        for step in range(1, beamLen):
+            exploreSize = 1 if step == 1 else beamSize                    # all beams are <START> at first
+            logp = step_fn(beams[step - 1])
+            cands = []
+            for wordId in range(exploreSize):
+                top = np.argsort(-logp[wordId], kind='stable')[:beamSize]  # torch.topk(..., true)
+                for cid in top:
+                    cb = beams[:, wordId].copy()
+                    cb[step] = cid + 1                                     # vocabulary ids are 1-based
+                    sc = scores[wordId] + float(logp[wordId, cid])
+                    if cid + 1 == endToken:
+                        finish.append(dict(beam=cb, length=step + 1, score=sc))
+                    else:
+                        cands.append(dict(score=sc, beam=cb, src=wordId))
+            cands.sort(key=lambda a: -a['score'])                         # (stable; Lua's table.sort is not)
+            keep = cands[:beamSize]
+            if keep:                                                      # untouched slots keep their old state
+                select_fn(np.array([c['src'] for c in keep], np.int32), len(keep))
+            for i, c in enumerate(keep):
+                beams[:, i] = c['beam']
+                scores[i] = c['score']
+        finish.sort(key=lambda a: -a['score'])
+        if finish:
+            return [(finish[0]['beam'], finish[0]['score'])]
+        return [(beams[:, 0], scores[0])]                                 # (the reference errors if none ended)
+    kp, lam = beamSize // groups, np.float32(diversity)
+    finish = [[] for _ in range(groups)]
+    for step in range(1, beamLen):
+        exploreSize = 1 if step == 1 else kp                              # D3
+        logp = np.asarray(step_fn(beams[step - 1]), np.float32)
+        count = np.zeros(logp.shape[1], np.int64)                         # D2: from zero at every step
+        # An untouched slot (D6) names itself: `select_fn` fills a prefix of the slots, and the state such a slot holds is never
+        # observed -- its next token is 0, and a token-0 step zeroes the state whatever it was (maskZero)
+        src = np.arange(beamSize, dtype=np.int32)
+        for g in range(groups):
+            base = g * kp
+            cands = []
+            for w in range(base, base + exploreSize):
+                a = logp[w] - lam * count.astype(np.float32)              # D4: fp32, product and difference rounded separately
+                for cid in np.argsort(-a, kind='stable')[:kp]:
+                    cb = beams[:, w].copy()
+                    cb[step] = cid + 1
+                    sc = scores[w] + float(logp[w, cid])                  # D5: the true log-likelihood
+                    if cid + 1 == endToken:
+                        finish[g].append(dict(beam=cb, score=sc))
+                    else:
+                        cands.append(dict(key=scores[w] + float(a[cid]), score=sc, beam=cb, src=w))
+            cands.sort(key=lambda c: -c['key'])                           # D6 (stable)
+            for i, c in enumerate(cands[:kp]):
+                beams[:, base + i] = c['beam']
+                scores[base + i] = c['score']
+                src[base + i] = c['src']
+                count[c['beam'][step] - 1] += 1
+        select_fn(src, beamSize)
+    out = []
+    for g in range(groups):                                               # D7
+        finish[g].sort(key=lambda c: -c['score'])
+        out.append((finish[g][0]['beam'], finish[g][0]['score']) if finish[g] else (beams[:, g * kp], scores[g * kp]))
     return out
 
 
@@ -148,6 +244,12 @@ class SplitEval(object):
         return self._rank_records(dataloader, dtype, ranks, dtype == 'test')
 
     # ------------------------------------------------------------------ generation (model.lua:432-613)
+    def _beam_grouping(self, groups, diversity):
+        """raises unless this host's `_gen_beam` searches with exactly these diverse-beam knobs (the plain search here)"""
+        if groups > 1:
+            raise ValueError("beamBatch > 0 with beamGroups = %d: the grouped device search runs in the model-level runtime only: use "
+                             "-host native (visdial_amd.native.NativeModel); this host searches in groups with beamBatch = 0" % groups)
+
     def generateAnswers(self, dataloader, dtype, params=None):
         """Beam search (default) or temperature sampling with the generative decoder, one dialog at a time,
         exactly as the reference drives it from the host: the decoder step (embedding, LSTM stack, vocabulary
@@ -157,7 +259,10 @@ class SplitEval(object):
         the same for temperature sampling (one encode + one `_gen_sample` per chunk); the host still draws every uniform, in the
         per-dialog loop's order, so the records are the same up to draws within rounding of a CDF boundary.  params topK / topP (with
         sampleWords = 1): top-k / nucleus truncation of the sampled distribution, `truncated_weights` above; the batched path needs a
-        host whose device sampler truncates (`_sample_truncation`).
+        host whose device sampler truncates (`_sample_truncation`).  params beamGroups = G > 1 (beam search only): diverse beam search,
+        `beam_search_round` above, with Hamming diversity params beamDiversity (default 0.5): every dialog entry gains `answers`, the
+        G groups' answers in group order, and `answer` is the best of them (`pick_answer`); with beamBatch > 0 it needs a host
+        whose device search runs in groups (`_beam_grouping`).
         Returns [{image_id, dialog: [{question, answer}...]}]."""
         if self.params['decoder'] == 'disc':
             raise SystemExit('Sampling/beam search only for generative model')
@@ -179,6 +284,14 @@ class SplitEval(object):
             if sampleBatch > 0:
                 self._sample_truncation(topK, topP)
         beamSize, beamLen = int(params.get('beamSize', 5)), int(params.get('beamLen', 20))
+        beamGroups = int(1 if params.get('beamGroups') is None else params['beamGroups'])
+        beamDiversity = float(0.5 if params.get('beamDiversity') is None else params['beamDiversity'])
+        if beamGroups != 1:
+            check_beam_groups(beamSize, beamGroups, beamDiversity)
+            if sampleWords:
+                raise ValueError('beamGroups > 1 is diverse beam search: sampling (sampleWords = 1) has no groups')
+        if beamBatch > 0:
+            self._beam_grouping(beamGroups, beamDiversity)
         startToken, endToken = dataloader.word2ind['<START>'], dataloader.word2ind['<END>']
         numThreads = int(params.get('maxThreads') or dataloader.numThreads[dtype])
         rng = np.random.RandomState(int(params.get('seed', 1234)))
@@ -187,11 +300,15 @@ class SplitEval(object):
         self._set_training(False)
         img_ids = getattr(dataloader, 'unique_img_' + dtype, None)
 
-        def record(convId, questions, answers):
-            """{image_id, dialog: [{question, answer}...]}: one question row and one answer row per round"""
-            return {'image_id': img_ids[convId - 1] if img_ids else int(convId),
-                    'dialog': [{'question': utils.idToWords(q, ind2word), 'answer': utils.idToWords(a, ind2word)}
-                               for q, a in zip(questions, answers)]}
+        def record(convId, questions, answers, groups=None):
+            """{image_id, dialog: [{question, answer}...]}: one question row and one answer row per round; with `groups` (per round,
+            the G groups' token rows) every entry also gets `answers`"""
+            rec = {'image_id': img_ids[convId - 1] if img_ids else int(convId),
+                   'dialog': [{'question': utils.idToWords(q, ind2word), 'answer': utils.idToWords(a, ind2word)}
+                              for q, a in zip(questions, answers)]}
+            for entry, rows in zip(rec['dialog'], [] if groups is None else groups):
+                entry['answers'] = [utils.idToWords(a, ind2word) for a in rows]
+            return rec
         chunk = sampleBatch if sampleWords else beamBatch
         if chunk > 0:
             for first in range(1, numThreads + 1, chunk):
@@ -203,6 +320,12 @@ class SplitEval(object):
                     u = rng.random_sample((B, beamLen, R))      # the per-dialog loop's draws: dialog, then step, then round
                     tokens, _ = self._gen_sample(beamLen, startToken, endToken, temperature,
                                                  u.transpose(1, 0, 2).reshape(beamLen, B * R))   # [step x row]
+                elif beamGroups > 1:                            # tokens [N x G x beamLen], scores [N x G]
+                    grouped, sc = self._gen_beam(beamSize, beamLen, startToken, endToken)
+                    tokens = [pick_answer(list(zip(t, s_)), endToken)[0] for t, s_ in zip(grouped, sc)]
+                    answerTable += [record(convId, batch['ques_fwd'][i], tokens[i * R:(i + 1) * R], grouped[i * R:(i + 1) * R])
+                                    for i, convId in enumerate(convIds)]
+                    continue
                 else:
                     tokens, _ = self._gen_beam(beamSize, beamLen, startToken, endToken)
                 answerTable += [record(convId, batch['ques_fwd'][i], tokens[i * R:(i + 1) * R])    # row = dialog * R + round
@@ -213,37 +336,14 @@ class SplitEval(object):
             batch = dataloader.getIndexData(np.array([convId]), self.params, dtype)
             R = batch['ques_fwd'].shape[1]
             self._gen_encode(batch)                                               # forwardBackward(batch, true, true)
-            answers = []
+            answers, grouped = [], []
             if not sampleWords:
                 for it in range(R):
-                    beams = np.zeros((beamLen, beamSize), np.int64)
                     self._gen_begin(np.full(beamSize, it, np.int32))              # hiddenBeams, model.lua:478-503
-                    beams[0] = startToken
-                    scores = np.zeros(beamSize)
-                    finish = []
-                    for step in range(1, beamLen):
-                        exploreSize = 1 if step == 1 else beamSize                    # all beams are <START> at first
-                        logp = self._gen_step(beams[step - 1])
-                        cands = []
-                        for wordId in range(exploreSize):
-                            top = np.argsort(-logp[wordId], kind='stable')[:beamSize]  # torch.topk(..., true)
-                            for cid in top:
-                                cb = beams[:, wordId].copy()
-                                cb[step] = cid + 1                                     # vocabulary ids are 1-based
-                                sc = scores[wordId] + float(logp[wordId, cid])
-                                if cid + 1 == endToken:
-                                    finish.append(dict(beam=cb, length=step + 1, score=sc))
-                                else:
-                                    cands.append(dict(score=sc, beam=cb, src=wordId))
-                        cands.sort(key=lambda a: -a['score'])                         # (stable; Lua's table.sort is not)
-                        keep = cands[:beamSize]
-                        if keep:                                                      # untouched slots keep their old state
-                            self._gen_select(np.array([c['src'] for c in keep], np.int32), len(keep))
-                        for i, c in enumerate(keep):
-                            beams[:, i] = c['beam']
-                            scores[i] = c['score']
-                    finish.sort(key=lambda a: -a['score'])
-                    answers.append(finish[0]['beam'] if finish else beams[:, 0])      # (the reference errors if none ended)
+                    found = beam_search_round(self._gen_step, self._gen_select, beamSize, beamLen, startToken, endToken, beamGroups,
+                                              beamDiversity)
+                    answers.append(pick_answer(found, endToken)[0] if beamGroups > 1 else found[0][0])
+                    grouped.append([tokens for tokens, _ in found])
             else:
                 numQues = R
                 self._gen_begin(np.arange(R, dtype=np.int32))
@@ -261,6 +361,6 @@ class SplitEval(object):
                     answer.append(nxt[:, None])
                     answerIn = nxt
                 answers = np.concatenate(answer, 1)
-            answerTable.append(record(convId, batch['ques_fwd'][0], answers))
+            answerTable.append(record(convId, batch['ques_fwd'][0], answers, grouped if beamGroups > 1 else None))
         self._set_training(True)
         return answerTable
