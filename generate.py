@@ -12,12 +12,13 @@ from visdial_amd import opts, utils
 from visdial_amd.dataloader import Dataloader
 from visdial_amd.model import Model
 from visdial_amd.checkpoint import load_checkpoint, restore_weights
-from visdial_amd.split_eval import check_beam_groups
+from visdial_amd.split_eval import check_beam_constraints, check_beam_groups
 
 
 def parse_args(argv=None):
     """the command line as the `opts` of the results file; refuses top-k / nucleus truncation without -sampleWords 1 and beam groups
-    that do not divide -beamSize, with a bad -beamDiversity or with -sampleWords 1"""
+    that do not divide -beamSize, with a bad -beamDiversity or with -sampleWords 1, and a bad -minLen / -noRepeatNgram / -lengthPenalty
+    or one of them with -sampleWords 1"""
     ap = argparse.ArgumentParser(description='Test the VisDial model for generation')
     ap.add_argument('-inputImg', '--inputImg', default='data/data_img.h5')
     ap.add_argument('-inputQues', '--inputQues', default='data/visdial_data.h5')
@@ -44,6 +45,11 @@ def parse_args(argv=None):
                          'every round also gets `answers`, one per group (1 = off)')
     ap.add_argument('-beamDiversity', '--beamDiversity', type=float, default=0.5,
                     help='(with -beamGroups > 1) what a word costs a group for every earlier group that chose it at that step')
+    ap.add_argument('-minLen', '--minLen', type=int, default=0, help='beam search: no answer of fewer than that many words (0 = off)')
+    ap.add_argument('-noRepeatNgram', '--noRepeatNgram', type=int, default=0,
+                    help='beam search: no n-gram of that many words occurs twice in a hypothesis (0 = off)')
+    ap.add_argument('-lengthPenalty', '--lengthPenalty', type=float, default=0.0,
+                    help='beam search: finished hypotheses compete on score / length^that (length = words + <END>; 0 = off)')
     ap.add_argument('-seed', '--seed', type=int, default=1234, help='seed of the sampling generator (numpy RandomState)')
     ap.add_argument('-gpuid', '--gpuid', type=int, default=0)
     ap.add_argument('-host', '--host', default='python', choices=['python', 'native'],
@@ -56,6 +62,9 @@ def parse_args(argv=None):
     check_beam_groups(a['beamSize'], a['beamGroups'], a['beamDiversity'])
     if a['beamGroups'] > 1 and a['sampleWords'] == 1:
         raise ValueError('-beamGroups > 1 is diverse beam search: sampling (-sampleWords 1) has no groups')
+    check_beam_constraints(a['beamSize'], a['beamLen'], a['minLen'], a['noRepeatNgram'], a['lengthPenalty'])
+    if (a['minLen'] != 0 or a['noRepeatNgram'] != 0 or a['lengthPenalty'] != 0.0) and a['sampleWords'] == 1:
+        raise ValueError('-minLen / -noRepeatNgram / -lengthPenalty constrain beam search: sampling (-sampleWords 1) has none')
     return a
 
 
@@ -73,8 +82,9 @@ def main():
         p[k] = getattr(dl, k)
     if a['host'] == 'native':
         from visdial_amd.native import NativeModel
-        # the device sampler takes its truncation, the device search its groups, at creation
-        model = NativeModel(dict(p, topK=a['topK'], topP=a['topP'], beamGroups=a['beamGroups'], beamDiversity=a['beamDiversity']))
+        # the device sampler takes its truncation, the device search its groups and constraints, at creation
+        model = NativeModel(dict(p, topK=a['topK'], topP=a['topP'], beamGroups=a['beamGroups'], beamDiversity=a['beamDiversity'],
+                                 beamMinLen=a['minLen'], beamNoRepeat=a['noRepeatNgram'], beamLengthPenalty=a['lengthPenalty']))
     else:
         model = Model(p)
     restore_weights(model, saved, a['paramOrder'] or None)
@@ -83,7 +93,8 @@ def main():
                                                     temperature=a['temperature'], beamBatch=a['beamBatch'],
                                                     sampleBatch=a['sampleBatch'], seed=a['seed'],
                                                     topK=a['topK'], topP=a['topP'], beamGroups=a['beamGroups'],
-                                                    beamDiversity=a['beamDiversity']))
+                                                    beamDiversity=a['beamDiversity'], beamMinLen=a['minLen'],
+                                                    beamNoRepeat=a['noRepeatNgram'], beamLengthPenalty=a['lengthPenalty']))
     os.makedirs(a['resultPath'], exist_ok=True)
     path = os.path.join(a['resultPath'], 'results.json')
     utils.writeJSON(path, {'opts': a, 'data': answers})

@@ -468,7 +468,21 @@ int vd_model_decode_select(vd_model* m, const int32_t* src, int n_keep);
  *   host_tokens [N x G x beam_len], host_scores [N x G]   (round-major, then group) -- G times the buffers of a plain model.
  * A score is the answer's true (unpenalised) log-likelihood.  The caller picks the round's answer: the highest score among the
  * groups whose answer holds end_token, ties to the lower group; group 0's if none does.  vd_model_create reads both variables once
- * and refuses any other value by name; both are ignored for decoder disc.  decode_begin / step / select need nothing new. */
+ * and refuses any other value by name; both are ignored for decoder disc.  decode_begin / step / select need nothing new.
+ *
+ * Constraints (decoder gen; the rule is C1-C6 at the top of csrc/beam.hip; each 0 / unset = off, and with all three off the call
+ * launches the kernels with the arguments it always did; they combine freely with VD_BEAM_GROUPS).  vd_model_create reads them once,
+ * refuses any other value with an argument error that names the variable, and ignores all three for decoder disc:
+ *   VD_BEAM_MIN_LEN = m         an integer >= 0: no answer of fewer than m words -- end_token is banned at every step <= m
+ *   VD_BEAM_NO_REPEAT = n       an integer >= 0: no n-gram of words occurs twice in a hypothesis (start_token is not a word)
+ *   VD_BEAM_LENGTH_PENALTY = a  a finite real >= 0: finished hypotheses compete on score / length^a, length = words + end_token;
+ *                               decided without a division on a table length^a computed on the host in fp64
+ * A banned word counts as -inf in its row; nothing is renormalised, so every other value and every returned score (the true
+ * log-likelihood) is what it was.  With m or n on, vd_model_beam_search REFUSES, naming the variable,
+ *   vocabSize < beam_size + beam_len - 1   (a row must keep beam_size unbanned words),
+ *   m > beam_len - 2                       (end_token must be allowed at the last step),
+ *   beam_len > VD_BEAM_LMAX = 64 with n on (the column and its ban list sit in LDS).
+ * A host that keeps the bookkeeping itself over decode_begin / step / select follows split_eval.beam_search_round. */
 int vd_model_beam_search(vd_model* m, int beam_size, int beam_len, int start_token, int end_token, int32_t* host_tokens,
                          double* host_scores);
 /* temperature sampling of Model:generateAnswers (sampleWords = 1, model.lua:576-613) for EVERY round of the last vd_model_encode

@@ -8,7 +8,9 @@ many dialogs have identical records.
     takes them at vd_model_create)
     --mode beam --beamSize k --beamGroups G --beamDiversity l: diverse beam search on both paths (the model is created with the knobs);
     also prints the share of rounds whose G answers are not all the same.  --vocabScale s multiplies the vocabulary projection of the
-    random model (60 = the peaked rows of test_beam_search_gpu.full_size_fixture; near-uniform rows otherwise)"""
+    random model (60 = the peaked rows of test_beam_search_gpu.full_size_fixture; near-uniform rows otherwise)
+    --mode beam --minLen m --noRepeatNgram n --lengthPenalty a: the beam constraints (csrc/beam.hip C1-C6) on both paths (the model is
+    created with the knobs)"""
 import argparse
 import os
 import sys
@@ -30,6 +32,9 @@ ap.add_argument('--topP', type=float, default=1.0, help='--mode sample: nucleus 
 ap.add_argument('--beamSize', type=int, default=5, help='--mode beam: slots per round')
 ap.add_argument('--beamGroups', type=int, default=1, help='--mode beam: diverse beam search in that many groups (1 = off)')
 ap.add_argument('--beamDiversity', type=float, default=0.5, help='--mode beam with --beamGroups > 1: the penalty per earlier choice')
+ap.add_argument('--minLen', type=int, default=0, help='--mode beam: no answer of fewer than that many words (0 = off)')
+ap.add_argument('--noRepeatNgram', type=int, default=0, help='--mode beam: no n-gram of that many words twice in a hypothesis (0 = off)')
+ap.add_argument('--lengthPenalty', type=float, default=0.0, help='--mode beam: finished hypotheses compete on score / length^that (0 = off)')
 ap.add_argument('--vocabScale', type=float, default=1.0, help='multiply vocab.W of the random model (peaked rows)')
 opt = ap.parse_args()
 MODE_KNOBS = opt.topK != 0 or opt.topP != 1.0
@@ -38,6 +43,10 @@ if MODE_KNOBS and opt.mode != 'sample':
 GROUPS = opt.beamGroups
 if (GROUPS != 1 or opt.beamSize != 5) and opt.mode != 'beam':
     ap.error('--beamSize / --beamGroups belong to beam search: use --mode beam')
+LIMITS = {} if (opt.minLen, opt.noRepeatNgram, opt.lengthPenalty) == (0, 0, 0.0) else dict(
+    beamMinLen=opt.minLen, beamNoRepeat=opt.noRepeatNgram, beamLengthPenalty=opt.lengthPenalty)
+if LIMITS and opt.mode != 'beam':
+    ap.error('--minLen / --noRepeatNgram / --lengthPenalty belong to beam search: use --mode beam')
 MODE, D, ONLY_BATCHED = opt.mode, opt.dialogs, opt.only == 'batched'
 V, R = 11322, 10
 
@@ -63,6 +72,7 @@ dl = Dialogs(p, D)
 knobs = dict(topK=opt.topK, topP=opt.topP) if MODE_KNOBS else {}
 if GROUPS != 1:
     knobs.update(beamGroups=GROUPS, beamDiversity=opt.beamDiversity)
+knobs.update(LIMITS)
 nat = NativeModel(dict(p, **knobs), init_seed=1)
 nat.training(False)
 if opt.vocabScale != 1.0:
@@ -75,6 +85,9 @@ if MODE == 'beam':
     if GROUPS != 1:
         cfg.update(beamGroups=GROUPS, beamDiversity=opt.beamDiversity)
         what += ' in %d groups (diversity %g)' % (GROUPS, opt.beamDiversity)
+    if LIMITS:
+        cfg.update(LIMITS)
+        what += ' (minLen %d, noRepeatNgram %d, lengthPenalty %g)' % (opt.minLen, opt.noRepeatNgram, opt.lengthPenalty)
 else:
     key, cfg = 'sampleBatch', dict(sampleWords=1, beamLen=20, temperature=1.0, maxThreads=D, seed=1234, topK=opt.topK, topP=opt.topP)
     what = 'sampling' + (' (topK %d, topP %g)' % (opt.topK, opt.topP) if MODE_KNOBS else '')

@@ -47,10 +47,33 @@
 // top k of the unpenalised one: beam_topk_kernel at the full k delivers everything a grouped step needs.  Per (round, group) the best
 // finished candidate, the initial state and the answer are rule 1 / rule 3 of N * G groups of k' slots, so beam_init_kernel and
 // beam_finish_kernel serve as they are.
+//
+// Constraints (behind rules 1-4 and D1-D7; all off by default, and then everything above is unchanged): minimum length m >= 0, no-repeat
+// n-gram size n >= 0, length penalty alpha >= 0 (finite).  split_eval.py restates them (beam_banned, beam_search_round, pick_answer).
+//  C1. the words of a slot's column at step s are g_1 .. g_(s-1), positions 1 .. s-1 of the column.  Position 0, <START>, is not a word.
+//      An n-gram that holds a 0 is ignored (a 0 stands in the column of a slot that was never filled).
+//  C2. minimum length: at every step s <= m, <END> is banned (a candidate that ends at step s has s - 1 words).
+//  C3. no-repeat n-gram, for n >= 1 once s >= n: p = the last n - 1 words (empty for n = 1); for every i in 1 .. s - n with
+//      g_i .. g_(i+n-2) = p the word g_(i+n-1) is banned.  A column yields at most s - 1 bans: at most beamLen - 1 with <END>.
+//  C4. a banned word's value is -inf in the explored row, the log-softmax row and the all-zero row of a token-0 slot alike.  Nothing is
+//      renormalised: the log-sum-exp is the full row's, so every other value is bit-identical.  The top-k stays rule 2 over what remains
+//      (value descending, index ascending); D4 penalises what remains.  vd_model_beam_search refuses vocabSize < beamSize + beamLen - 1
+//      while a ban is on, so that k finite candidates always exist, and m > beamLen - 2 (<END> must be allowed at the last step).
+//  C5. scores stay the true log-likelihood, carried and reported as before.
+//  C6. length penalty: a finished candidate that ends at step s has length s (its words plus <END>).  Within one step the best finished
+//      candidate is chosen by score as before (one length).  Across steps a new best x replaces the incumbent y iff
+//      x.score * lp[y.len] > y.score * lp[x.len], lp[s] = s^alpha computed ON THE HOST in fp64 (std::pow here, float(s) ** alpha in
+//      Python: one libm) and uploaded as a table; each product is one IEEE fp64 multiplication (__dmul_rn).  No division and no device
+//      pow: host and device decide bit for bit alike.  Ties stay with the earliest inserted.  D7's choice among the groups of a round
+//      uses the same comparison, ties to the lower group, the length being the position of <END> in the answer.  "Nothing finished"
+//      falls back as before.
+// On the device C2-C4 are the constrained form of the top-k kernel (it reads the row's column from the PRE-advance history), C6 one more
+// argument of the advance kernels; with every knob off the search launches the plain kernels with the arguments it always passed.
 #include "common.h"
 
 #define VD_BEAM_KMAX 32
 #define VD_BEAM_GKMAX (VD_BEAM_KMAX / 2)   // k' = k / G of a grouped search (G >= 2)
+// VD_BEAM_LMAX (common.h): the longest beamLen while n-gram blocking is on -- a column and its ban list sit in LDS
 
 namespace {
 
@@ -61,31 +84,81 @@ __device__ __forceinline__ bool beam_better(float av, int ai, float bv, int bi) 
 // log_softmax_rows_kernel (loss.hip) calls too, so every value is bit-identical to that kernel's output row[c] - lse.  Each
 // thread keeps a sorted list of its KM best (value, index) pairs in registers (compile-time indices only: no scratch), then
 // k rounds of a workgroup arg-max over the list heads pop the row's top-k in order.
-template <int KM>
-__global__ void __launch_bounds__(256)
-beam_topk_kernel(const float* __restrict__ x, long ld, int V, const int32_t* __restrict__ tok, int k,
-                 int32_t* __restrict__ top_idx, float* __restrict__ top_val) {
+//
+// BAN (C1-C4): `hist` is the PRE-advance history [rows x L], `step` the step being taken.  Wave 0 builds the row's ban list (word
+// indices, at most L - 1 <= VD_BEAM_LMAX - 1 of them) in LDS: lane i tests the window that starts at word i against the last n - 1
+// words.  A thread scans the columns c = tid (mod 256), so it first notes whether any banned index is one of its own; only such a
+// thread (almost none: the list is short) asks the list again, for a column that would enter its sorted list.  The token-0 row returns
+// the k lowest unbanned indices at value 0.
+template <int KM, bool BAN>
+__device__ __forceinline__ void
+beam_topk_body(const float* x, long ld, int V, const int32_t* tok, int k, const int32_t* hist, int L,
+               int step, int min_len, int no_repeat, int end_tok, int32_t* top_idx, float* top_val) {
   __shared__ float red[8];
   __shared__ float wv[4];
   __shared__ int wi[4];
+  __shared__ int col[BAN ? VD_BEAM_LMAX : 1], ban[BAN ? VD_BEAM_LMAX : 1];
+  __shared__ int n_ban;
   const long r = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int32_t* oi = top_idx + r * k;
   float* ov = top_val + r * k;
+  int nb = 0;
+  if constexpr (BAN) {
+    const bool ngram = no_repeat >= 1 && step >= no_repeat;        // C3; the entry point holds L <= VD_BEAM_LMAX while n >= 1
+    if (ngram && tid < step) col[tid] = hist[r * L + tid];         // positions 0 .. s-1
+    if (tid == 0) {
+      n_ban = 0;
+      if (step <= min_len) { ban[0] = end_tok - 1; n_ban = 1; }    // C2
+    }
+    __syncthreads();
+    if (ngram && tid >= 1 && tid <= step - no_repeat) {            // the window g_tid .. g_(tid+n-2) against p = g_(s-n+1) .. g_(s-1)
+      const int w = col[tid + no_repeat - 1];
+      bool hit = w != 0;                                           // C1: an n-gram that holds a 0 is ignored
+      for (int j = 0; j < no_repeat - 1; ++j) {
+        const int a = col[tid + j], b = col[step - no_repeat + 1 + j];
+        hit = hit && a == b && b != 0;
+      }
+      if (hit) ban[atomicAdd(&n_ban, 1)] = w - 1;                  // at most s - n <= L - 2 of these next to <END>
+    }
+    __syncthreads();
+    nb = n_ban;
+  }
+  auto banned = [&](int c) {
+    bool b = false;
+    for (int j = 0; j < nb; ++j) b = b || ban[j] == c;
+    return b;
+  };
   if (tok[r] == 0) {                     // MaskZero(LogSoftMax): an all-zero row, ties to the lower index
-    if (tid < k) { oi[tid] = tid; ov[tid] = 0.f; }
+    if constexpr (BAN) {
+      if (wave == 0) {                   // the k lowest unbanned indices: 64 columns at a time, a lane's place from the ballot
+        int q0 = 0;
+        for (int base = 0; q0 < k && base < V; base += 64) {
+          const int c = base + lane;
+          const bool ok = c < V && !banned(c);
+          const unsigned long long mask = __ballot(ok);
+          const int q = q0 + __popcll(mask & ((1ull << lane) - 1ull));
+          if (ok && q < k) { oi[q] = c; ov[q] = 0.f; }
+          q0 += __popcll(mask);
+        }
+      }
+    } else {
+      if (tid < k) { oi[tid] = tid; ov[tid] = 0.f; }
+    }
     return;
   }
   const float* row = x + r * ld;
   const float lse = block_row_lse(row, V, red);
 
+  bool mine = false;                     // BAN: does a banned index fall among this thread's columns
+  for (int j = 0; j < nb; ++j) mine = mine || (ban[j] & 255) == tid;
   float lv[KM];
   int li[KM];
 #pragma unroll
   for (int j = 0; j < KM; ++j) { lv[j] = -INFINITY; li[j] = INT_MAX; }
   for (int c = tid; c < V; c += 256) {   // ascending c: an equal value never overtakes an earlier index
     const float v = row[c] - lse;
-    if (beam_better(v, c, lv[KM - 1], li[KM - 1])) {
+    if (beam_better(v, c, lv[KM - 1], li[KM - 1]) && !(BAN && mine && banned(c))) {
       lv[KM - 1] = v;
       li[KM - 1] = c;
 #pragma unroll
@@ -123,6 +196,21 @@ beam_topk_kernel(const float* __restrict__ x, long ld, int V, const int32_t* __r
   }
 }
 
+template <int KM>
+__global__ void __launch_bounds__(256)
+beam_topk_kernel(const float* __restrict__ x, long ld, int V, const int32_t* __restrict__ tok, int k,
+                 int32_t* __restrict__ top_idx, float* __restrict__ top_val) {
+  beam_topk_body<KM, false>(x, ld, V, tok, k, nullptr, 0, 0, 0, 0, 0, top_idx, top_val);
+}
+
+template <int KM>
+__global__ void __launch_bounds__(256)
+beam_topk_ban_kernel(const float* __restrict__ x, long ld, int V, const int32_t* __restrict__ tok, int k, const int32_t* __restrict__ hist,
+                     int L, int step, int min_len, int no_repeat, int end_tok, int32_t* __restrict__ top_idx,
+                     float* __restrict__ top_val) {
+  beam_topk_body<KM, true>(x, ld, V, tok, k, hist, L, step, min_len, no_repeat, end_tok, top_idx, top_val);
+}
+
 // rule 1 for every group: history column <START>, 0, ..., next token <START>, scores 0, no finished candidate
 __global__ void beam_init_kernel(int groups, int k, int L, int start, int32_t* __restrict__ hist, int32_t* __restrict__ tok,
                                  double* __restrict__ scores, double* __restrict__ best_score, int32_t* __restrict__ best_len) {
@@ -138,12 +226,18 @@ __global__ void beam_init_kernel(int groups, int k, int L, int start, int32_t* _
 // (unfinished / finished) is the number of that kind with a higher score or an equal score inserted earlier: for the
 // unfinished ones that is the stable sort's position, for the finished ones place 0 is this step's best.  The best finished
 // candidate so far is kept per group (score, length, column); a later one replaces it only with a strictly higher score, so
-// ties stay with the earliest inserted (rule 3).
-__global__ void __launch_bounds__(256)
-beam_advance_kernel(const int32_t* __restrict__ top_idx, const float* __restrict__ top_val, int k, int step, int L, int end_tok,
-                    double* __restrict__ scores, const int32_t* __restrict__ hist_in, int32_t* __restrict__ hist_out,
-                    int32_t* __restrict__ src, int32_t* __restrict__ next_tok, double* __restrict__ best_score,
-                    int32_t* __restrict__ best_len, int32_t* __restrict__ best_hist) {
+// ties stay with the earliest inserted (rule 3).  LP (C6): `lp` [L] holds s^alpha at index s, the length of a candidate that ends at
+// step s; best_len - 1 is the incumbent's.
+__device__ __forceinline__ bool beam_replaces(double x_score, int x_len, double y_score, int y_len, const double* __restrict__ lp) {
+  return __dmul_rn(x_score, lp[y_len]) > __dmul_rn(y_score, lp[x_len]);
+}
+
+template <bool LP>
+__device__ __forceinline__ void
+beam_advance_body(const int32_t* top_idx, const float* top_val, int k, int step, int L, int end_tok,
+                  double* scores, const int32_t* hist_in, int32_t* hist_out,
+                  int32_t* src, int32_t* next_tok, double* best_score,
+                  int32_t* best_len, int32_t* best_hist, const double* lp) {
   __shared__ double csc[VD_BEAM_KMAX * VD_BEAM_KMAX];
   __shared__ int ctok[VD_BEAM_KMAX * VD_BEAM_KMAX];
   __shared__ double slot_sc[VD_BEAM_KMAX];
@@ -181,7 +275,7 @@ beam_advance_kernel(const int32_t* __restrict__ top_idx, const float* __restrict
   const int n_keep = min(n_cands, k);
   if (tid == 0 && best_c >= 0) {
     const double sc = csc[best_c];
-    if (best_len[g] == 0 || sc > best_score[g]) {
+    if (best_len[g] == 0 || (LP ? beam_replaces(sc, step, best_score[g], best_len[g] - 1, lp) : sc > best_score[g])) {
       const int32_t* col = hist_in + (g0 + best_c / k) * L;
       best_score[g] = sc;
       best_len[g] = step + 1;
@@ -202,16 +296,36 @@ beam_advance_kernel(const int32_t* __restrict__ top_idx, const float* __restrict
   }
 }
 
+__global__ void __launch_bounds__(256)
+beam_advance_kernel(const int32_t* __restrict__ top_idx, const float* __restrict__ top_val, int k, int step, int L, int end_tok,
+                    double* __restrict__ scores, const int32_t* __restrict__ hist_in, int32_t* __restrict__ hist_out,
+                    int32_t* __restrict__ src, int32_t* __restrict__ next_tok, double* __restrict__ best_score,
+                    int32_t* __restrict__ best_len, int32_t* __restrict__ best_hist) {
+  beam_advance_body<false>(top_idx, top_val, k, step, L, end_tok, scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist,
+                           nullptr);
+}
+
+__global__ void __launch_bounds__(256)
+beam_advance_lp_kernel(const int32_t* __restrict__ top_idx, const float* __restrict__ top_val, int k, int step, int L, int end_tok,
+                       double* __restrict__ scores, const int32_t* __restrict__ hist_in, int32_t* __restrict__ hist_out,
+                       int32_t* __restrict__ src, int32_t* __restrict__ next_tok, double* __restrict__ best_score,
+                       int32_t* __restrict__ best_len, int32_t* __restrict__ best_hist, const double* __restrict__ lp) {
+  beam_advance_body<true>(top_idx, top_val, k, step, L, end_tok, scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist,
+                          lp);
+}
+
 // D2-D6 for one round per workgroup, its G groups one after another (a group's penalties need the earlier groups' slots).  `count` is
 // a list of (word, multiplicity) pairs, at most one per slot.  Per group: the k candidates of every explored slot (beam_topk_kernel's,
 // unpenalised order) get their penalised value and their rank under it; the ranks < k' are the slot's candidates, candidate
 // c = w * k' + rank (insertion order), and from there on this is beam_advance_kernel on the group's k' slots with the key ordering the
 // unfinished candidates and the score carried.  best_* are per (round, group); `src` stays a round-local slot index.
-__global__ void __launch_bounds__(256)
-beam_advance_grouped_kernel(const int32_t* __restrict__ top_idx, const float* __restrict__ top_val, int k, int G, float lambda, int step,
-                            int L, int end_tok, double* __restrict__ scores, const int32_t* __restrict__ hist_in,
-                            int32_t* __restrict__ hist_out, int32_t* __restrict__ src, int32_t* __restrict__ next_tok,
-                            double* __restrict__ best_score, int32_t* __restrict__ best_len, int32_t* __restrict__ best_hist) {
+template <bool LP>
+__device__ __forceinline__ void
+beam_advance_grouped_body(const int32_t* top_idx, const float* top_val, int k, int G, float lambda, int step,
+                          int L, int end_tok, double* scores, const int32_t* hist_in,
+                          int32_t* hist_out, int32_t* src, int32_t* next_tok,
+                          double* best_score, int32_t* best_len, int32_t* best_hist,
+                          const double* lp) {
   __shared__ float pen[VD_BEAM_GKMAX * VD_BEAM_KMAX];
   __shared__ double ckey[VD_BEAM_GKMAX * VD_BEAM_GKMAX], csc[VD_BEAM_GKMAX * VD_BEAM_GKMAX];
   __shared__ int ctok[VD_BEAM_GKMAX * VD_BEAM_GKMAX];
@@ -276,7 +390,7 @@ beam_advance_grouped_kernel(const int32_t* __restrict__ top_idx, const float* __
       const long bg = (long)r * G + g;
       if (best_c >= 0) {
         const double sc = csc[best_c];
-        if (best_len[bg] == 0 || sc > best_score[bg]) {
+        if (best_len[bg] == 0 || (LP ? beam_replaces(sc, step, best_score[bg], best_len[bg] - 1, lp) : sc > best_score[bg])) {
           const int32_t* col = hist_in + (g0 + best_c / kp) * L;
           best_score[bg] = sc;
           best_len[bg] = step + 1;
@@ -306,6 +420,25 @@ beam_advance_grouped_kernel(const int32_t* __restrict__ top_idx, const float* __
   }
 }
 
+__global__ void __launch_bounds__(256)
+beam_advance_grouped_kernel(const int32_t* __restrict__ top_idx, const float* __restrict__ top_val, int k, int G, float lambda, int step,
+                            int L, int end_tok, double* __restrict__ scores, const int32_t* __restrict__ hist_in,
+                            int32_t* __restrict__ hist_out, int32_t* __restrict__ src, int32_t* __restrict__ next_tok,
+                            double* __restrict__ best_score, int32_t* __restrict__ best_len, int32_t* __restrict__ best_hist) {
+  beam_advance_grouped_body<false>(top_idx, top_val, k, G, lambda, step, L, end_tok, scores, hist_in, hist_out, src, next_tok, best_score,
+                                   best_len, best_hist, nullptr);
+}
+
+__global__ void __launch_bounds__(256)
+beam_advance_grouped_lp_kernel(const int32_t* __restrict__ top_idx, const float* __restrict__ top_val, int k, int G, float lambda, int step,
+                               int L, int end_tok, double* __restrict__ scores, const int32_t* __restrict__ hist_in,
+                               int32_t* __restrict__ hist_out, int32_t* __restrict__ src, int32_t* __restrict__ next_tok,
+                               double* __restrict__ best_score, int32_t* __restrict__ best_len, int32_t* __restrict__ best_hist,
+                               const double* __restrict__ lp) {
+  beam_advance_grouped_body<true>(top_idx, top_val, k, G, lambda, step, L, end_tok, scores, hist_in, hist_out, src, next_tok, best_score,
+                                  best_len, best_hist, lp);
+}
+
 // cur[r] = stepped[group(r) * k + src[r]] where src[r] >= 0; the row is left alone otherwise
 __global__ void beam_select_rows_kernel(float* __restrict__ cur, const float* __restrict__ stepped, const int32_t* __restrict__ src,
                                         long rows, int k, int H) {
@@ -331,10 +464,11 @@ __global__ void beam_finish_kernel(int groups, int k, int L, const int32_t* __re
 
 }  // namespace
 
-// the grouped vd_beam_advance (rt_core.h): `rounds` rounds of G groups of k / G slots; best_* are [rounds x G]
+// the grouped vd_beam_advance (rt_core.h): `rounds` rounds of G groups of k / G slots; best_* are [rounds x G]; lp = nullptr: no length
+// penalty, the kernel and the arguments of before
 int vd_beam_advance_grouped_p(const int32_t* top_idx, const float* top_val, int rounds, int k, int G, float lambda, int step, int beam_len,
                               int end_token, double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok,
-                              double* best_score, int32_t* best_len, int32_t* best_hist, hipStream_t stream) {
+                              double* best_score, int32_t* best_len, int32_t* best_hist, const double* lp, hipStream_t stream) {
   VD_CHECK_ARG(top_idx && top_val && scores && hist_in && hist_out && src && next_tok && best_score && best_len && best_hist &&
                rounds >= 0 && hist_in != hist_out, "vd_beam_advance_grouped: bad args");
   VD_CHECK_ARG(k >= 2 && k <= VD_BEAM_KMAX && G >= 2 && k % G == 0, "vd_beam_advance_grouped: G = %d must be >= 2 and divide k = %d in [2, %d]",
@@ -342,8 +476,51 @@ int vd_beam_advance_grouped_p(const int32_t* top_idx, const float* top_val, int 
   VD_CHECK_ARG(lambda >= 0.f && lambda < INFINITY, "vd_beam_advance_grouped: lambda = %g must be finite and >= 0", (double)lambda);
   VD_CHECK_ARG(step >= 1 && step < beam_len, "vd_beam_advance_grouped: step %d outside [1, %d)", step, beam_len);
   if (rounds == 0) return VD_OK;
-  hipLaunchKernelGGL(beam_advance_grouped_kernel, dim3((unsigned)rounds), dim3(256), 0, stream, top_idx, top_val, k, G, lambda, step,
-                     beam_len, end_token, scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist);
+  if (lp)
+    hipLaunchKernelGGL(beam_advance_grouped_lp_kernel, dim3((unsigned)rounds), dim3(256), 0, stream, top_idx, top_val, k, G, lambda, step,
+                       beam_len, end_token, scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist, lp);
+  else
+    hipLaunchKernelGGL(beam_advance_grouped_kernel, dim3((unsigned)rounds), dim3(256), 0, stream, top_idx, top_val, k, G, lambda, step,
+                       beam_len, end_token, scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+// vd_beam_topk under C1-C4 (rt_core.h): `hist` [rows x beam_len] is the PRE-advance history, `step` the step being taken
+int vd_beam_topk_ban_p(const float* logits, int64_t ld, int64_t rows, int V, const int32_t* tok, int k, const int32_t* hist, int beam_len,
+                       int step, int min_len, int no_repeat, int end_token, int32_t* top_idx, float* top_val, hipStream_t stream) {
+  VD_CHECK_ARG(logits && tok && hist && top_idx && top_val && rows >= 0 && V >= 1 && ld >= V, "vd_beam_topk_ban: bad args");
+  VD_CHECK_ARG(k >= 1 && k <= VD_BEAM_KMAX, "vd_beam_topk_ban: k = %d must be in [1, %d]", k, VD_BEAM_KMAX);
+  VD_CHECK_ARG(step >= 1 && step < beam_len, "vd_beam_topk_ban: step %d outside [1, %d)", step, beam_len);
+  VD_CHECK_ARG(min_len >= 0 && no_repeat >= 0 && end_token >= 1 && end_token <= V,
+               "vd_beam_topk_ban: min_len = %d and no_repeat = %d must be >= 0 and end_token = %d in [1, V = %d]", min_len, no_repeat,
+               end_token, V);
+  VD_CHECK_ARG(no_repeat == 0 || beam_len <= VD_BEAM_LMAX, "vd_beam_topk_ban: beam_len = %d exceeds VD_BEAM_LMAX = %d with no_repeat = %d",
+               beam_len, VD_BEAM_LMAX, no_repeat);
+  VD_CHECK_ARG((long)V >= (long)k + beam_len - 1, "vd_beam_topk_ban: V = %d is below k + beam_len - 1 = %ld: a row could run out of unbanned words",
+               V, (long)k + beam_len - 1);
+  if (rows == 0) return VD_OK;
+  if (k <= 8)
+    hipLaunchKernelGGL(beam_topk_ban_kernel<8>, dim3((unsigned)rows), dim3(256), 0, stream, logits, (long)ld, V, tok, k, hist, beam_len,
+                       step, min_len, no_repeat, end_token, top_idx, top_val);
+  else
+    hipLaunchKernelGGL(beam_topk_ban_kernel<VD_BEAM_KMAX>, dim3((unsigned)rows), dim3(256), 0, stream, logits, (long)ld, V, tok, k, hist,
+                       beam_len, step, min_len, no_repeat, end_token, top_idx, top_val);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+// vd_beam_advance under C6 (rt_core.h): lp [beam_len] on the device, lp[s] = s^alpha
+int vd_beam_advance_lp_p(const int32_t* top_idx, const float* top_val, int groups, int k, int step, int beam_len, int end_token,
+                         double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok, double* best_score,
+                         int32_t* best_len, int32_t* best_hist, const double* lp, hipStream_t stream) {
+  VD_CHECK_ARG(top_idx && top_val && scores && hist_in && hist_out && src && next_tok && best_score && best_len && best_hist && lp &&
+               groups >= 0 && hist_in != hist_out, "vd_beam_advance_lp: bad args");
+  VD_CHECK_ARG(k >= 1 && k <= VD_BEAM_KMAX, "vd_beam_advance_lp: k = %d must be in [1, %d]", k, VD_BEAM_KMAX);
+  VD_CHECK_ARG(step >= 1 && step < beam_len, "vd_beam_advance_lp: step %d outside [1, %d)", step, beam_len);
+  if (groups == 0) return VD_OK;
+  hipLaunchKernelGGL(beam_advance_lp_kernel, dim3((unsigned)groups), dim3(256), 0, stream, top_idx, top_val, k, step, beam_len, end_token,
+                     scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist, lp);
   VD_LAUNCH_CHECK();
   return VD_OK;
 }

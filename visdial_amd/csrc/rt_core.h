@@ -62,10 +62,21 @@ int vd_sample_draw_trunc_p(const float* logits, int64_t ld, int64_t rows, int V,
                            hipStream_t stream);
 
 // beam.hip: vd_beam_advance for a search in G >= 2 groups per round (VD_BEAM_GROUPS / VD_BEAM_DIVERSITY; the rule is beam.hip's header
-// D1-D7): `rounds` rounds of k slots, group g of a round owns slots g k/G .. ; best_score / best_len / best_hist are [rounds x G]
+// D1-D7): `rounds` rounds of k slots, group g of a round owns slots g k/G .. ; best_score / best_len / best_hist are [rounds x G].
+// lp: the length-penalty table of C6 below on the device, or nullptr = off (the kernel and the arguments of before)
 int vd_beam_advance_grouped_p(const int32_t* top_idx, const float* top_val, int rounds, int k, int G, float lambda, int step, int beam_len,
                               int end_token, double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok,
-                              double* best_score, int32_t* best_len, int32_t* best_hist, hipStream_t stream);
+                              double* best_score, int32_t* best_len, int32_t* best_hist, const double* lp, hipStream_t stream);
+// beam.hip, the constrained forms (VD_BEAM_MIN_LEN / VD_BEAM_NO_REPEAT / VD_BEAM_LENGTH_PENALTY; the rule is beam.hip's header C1-C6).
+// vd_beam_topk_ban_p: vd_beam_topk with the words banned that minimum length and n-gram blocking ban for the row's column, read from
+// the PRE-advance history `hist` [rows x beam_len] at `step`; needs V >= k + beam_len - 1, and beam_len <= VD_BEAM_LMAX while
+// no_repeat >= 1.  vd_beam_advance_lp_p: vd_beam_advance whose best finished candidate is replaced across steps by
+// x.score * lp[y.len] > y.score * lp[x.len]; lp [beam_len] on the device, lp[s] = s^alpha computed on the host in fp64.
+int vd_beam_topk_ban_p(const float* logits, int64_t ld, int64_t rows, int V, const int32_t* tok, int k, const int32_t* hist, int beam_len,
+                       int step, int min_len, int no_repeat, int end_token, int32_t* top_idx, float* top_val, hipStream_t stream);
+int vd_beam_advance_lp_p(const int32_t* top_idx, const float* top_val, int groups, int k, int step, int beam_len, int end_token,
+                         double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok, double* best_score,
+                         int32_t* best_len, int32_t* best_hist, const double* lp, hipStream_t stream);
 
 #define VD_TRY(expr)                  \
   do {                                \
@@ -266,6 +277,12 @@ struct vd_model {
   // with that Hamming diversity and returns every group's answer; 1 = the plain search
   int beam_groups = 1;
   double beam_diversity = 0.5;
+  // VD_BEAM_MIN_LEN / VD_BEAM_NO_REPEAT / VD_BEAM_LENGTH_PENALTY at vd_model_create (decoder gen): the constraints of vd_model_beam_search
+  // (beam.hip C1-C6); 0 = off.  beam_lp: the host copy of the table s^alpha, s < beamLen, built by the search once beamLen is known and
+  // kept here until the upload into workspace "beam.lp" has run
+  int beam_min_len = 0, beam_no_repeat = 0;
+  double beam_length_penalty = 0.0;
+  std::vector<double> beam_lp;
   bool lhood_tree = false;   // VD_LHOOD_TREE at vd_model_create: vd_model_retrieve_lhood scores over a prefix tree of the candidates
   bool prof_hist = false;   // ev_prof[0..3] bracket the history branch of a Sequential encoder (gen pairs: vd_model_family_ms)
   ~vd_model();

@@ -762,6 +762,8 @@ inline int gen_read_back(vd_model* m, const void* out, size_t bytes, std::vector
 // A model created with VD_BEAM_GROUPS = G > 1 searches every round in G groups of k / G slots (beam.hip D1-D7): the same top-k at the
 // full k, the grouped advance, the same select; the best-finished state, the start and the answers are those of N * G groups of k / G
 // slots, so init and finish take (N * G, k / G) and the answers come back [N x G x L] / [N x G].  G = 1 launches what it always did.
+// VD_BEAM_MIN_LEN / VD_BEAM_NO_REPEAT (beam.hip C1-C4) swap the top-k for its constrained form, VD_BEAM_LENGTH_PENALTY (C6) the advance for
+// the one that takes the table s^alpha; with all three off the launches and their arguments are the ones of before.
 inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end, int32_t* host_tokens, double* host_scores) {
   VD_CHECK_ARG(m->gen_enc_out && m->N > 0, "vd_model_beam_search: call vd_model_encode first");
   VD_CHECK_ARG(host_tokens && host_scores && L >= 1, "vd_model_beam_search: bad arguments");
@@ -769,6 +771,17 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
   const int groups = m->beam_groups;
   VD_CHECK_ARG(k % groups == 0, "vd_model_beam_search: VD_BEAM_GROUPS = %d does not divide beam size %d", groups, k);
   const int N = m->N, n = N * k, G = N * groups, kg = k / groups;           // G answers, each the best of kg slots
+  const int min_len = m->beam_min_len, no_repeat = m->beam_no_repeat;
+  const bool ban = min_len > 0 || no_repeat > 0, penalty = m->beam_length_penalty > 0.0;
+  if (ban) {
+    VD_CHECK_ARG(no_repeat == 0 || L <= VD_BEAM_LMAX, "vd_model_beam_search: VD_BEAM_NO_REPEAT = %d needs a beam length %d <= VD_BEAM_LMAX = %d",
+                 no_repeat, L, VD_BEAM_LMAX);
+    VD_CHECK_ARG((long)g->V >= (long)k + L - 1,
+                 "vd_model_beam_search: VD_BEAM_MIN_LEN = %d / VD_BEAM_NO_REPEAT = %d need vocabSize %ld >= beam size %d + beam length %d - 1, "
+                 "so that a row never runs out of unbanned words", min_len, no_repeat, (long)g->V, k, L);
+    VD_CHECK_ARG(min_len <= L - 2, "vd_model_beam_search: VD_BEAM_MIN_LEN = %d exceeds beam length %d - 2: <END> must be allowed at the last step",
+                 min_len, L);
+  }
   VD_TRY(gen_batch_begin(g, m, k));
   hipStream_t s = m->s_main;
   int32_t *tok, *top_idx, *src, *hist[2], *best_len, *best_hist;
@@ -787,12 +800,25 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
   VD_TRY(ws_get(m, "beam.best_len", (size_t)G, &best_len));
   VD_TRY(ws_get(m, "beam.best_hist", (size_t)G * L, &best_hist));
   VD_TRY(ws_get(m, "beam.out", tok_bytes + (size_t)G * 8, &out));
+  double* lp = nullptr;
+  if (penalty) {                                                            // C6: s^alpha on the host in fp64, uploaded as a table
+    m->beam_lp.resize((size_t)L);
+    for (int i = 0; i < L; ++i) m->beam_lp[i] = std::pow((double)i, m->beam_length_penalty);
+    VD_TRY(ws_get(m, "beam.lp", (size_t)L, &lp));
+    VD_HIP(hipMemcpyAsync(lp, m->beam_lp.data(), (size_t)L * 8, hipMemcpyHostToDevice, s));
+  }
   VD_TRY(vd_beam_init(G, kg, L, start, hist[0], tok, scores, best_score, best_len, s));
   VD_TRY(gen_batch_steps(g, m, L - 1, tok, src, k, [&](int step, float* logits) -> int {
-    VD_TRY(vd_beam_topk(logits, g->Vp, n, (int)g->V, tok, k, top_idx, top_val, s));
+    if (ban)
+      VD_TRY(vd_beam_topk_ban_p(logits, g->Vp, n, (int)g->V, tok, k, hist[0], L, step, min_len, no_repeat, end, top_idx, top_val, s));
+    else
+      VD_TRY(vd_beam_topk(logits, g->Vp, n, (int)g->V, tok, k, top_idx, top_val, s));
     if (groups > 1)
       VD_TRY(vd_beam_advance_grouped_p(top_idx, top_val, N, k, groups, (float)m->beam_diversity, step, L, end, scores, hist[0], hist[1], src,
-                                       tok, best_score, best_len, best_hist, s));
+                                       tok, best_score, best_len, best_hist, lp, s));
+    else if (penalty)
+      VD_TRY(vd_beam_advance_lp_p(top_idx, top_val, G, k, step, L, end, scores, hist[0], hist[1], src, tok, best_score, best_len, best_hist,
+                                  lp, s));
     else
       VD_TRY(vd_beam_advance(top_idx, top_val, G, k, step, L, end, scores, hist[0], hist[1], src, tok, best_score, best_len, best_hist,
                              s));

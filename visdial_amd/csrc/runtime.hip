@@ -366,12 +366,40 @@ int vd_model_create(const vd_model_params* p, const char* encoder, const char* d
       beam_diversity = v;
     }
   }
+  // the constraints of vd_model_beam_search (beam.hip C1-C6): VD_BEAM_MIN_LEN / VD_BEAM_NO_REPEAT = an integer >= 0, VD_BEAM_LENGTH_PENALTY
+  // = a finite real >= 0; 0 / unset = off, anything else is refused.  Ignored for decoder disc.
+  int beam_min_len = 0, beam_no_repeat = 0;
+  double beam_length_penalty = 0.0;
+  if (std::string(decoder) == "gen") {
+    const char* const names[2] = {"VD_BEAM_MIN_LEN", "VD_BEAM_NO_REPEAT"};
+    int* const into[2] = {&beam_min_len, &beam_no_repeat};
+    for (int i = 0; i < 2; ++i) {
+      if (const char* e = getenv(names[i])) {
+        char* end = nullptr;
+        errno = 0;
+        const long v = strtol(e, &end, 10);
+        VD_CHECK_ARG(*e && end && !*end && errno == 0 && v >= 0 && v <= INT32_MAX, "vd_model_create: %s = '%s' must be an integer >= 0 (0 = off)",
+                     names[i], e);
+        *into[i] = (int)v;
+      }
+    }
+    if (const char* e = getenv("VD_BEAM_LENGTH_PENALTY")) {
+      char* end = nullptr;
+      const double v = strtod(e, &end);
+      VD_CHECK_ARG(*e && end && !*end && v >= 0.0 && v <= DBL_MAX,           // a NaN fails both comparisons
+                   "vd_model_create: VD_BEAM_LENGTH_PENALTY = '%s' must be a finite real >= 0 (0 = off)", e);
+      beam_length_penalty = v;
+    }
+  }
   vd_model* m = new vd_model();
   m->p = *p;
   m->sample_topk = sample_topk;
   m->sample_topp = sample_topp;
   m->beam_groups = beam_groups;
   m->beam_diversity = beam_diversity;
+  m->beam_min_len = beam_min_len;
+  m->beam_no_repeat = beam_no_repeat;
+  m->beam_length_penalty = beam_length_penalty;
   m->flags = flags;
   m->ocache.capacity = cache_rows;
   m->lhood_tree = lhood_tree;

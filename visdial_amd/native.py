@@ -77,13 +77,18 @@ class NativeModel(SplitEval):
         # params without them creates the model with the variables unset.  generateAnswers(sampleBatch > 0) checks its knobs against these.
         # params beamGroups / beamDiversity: diverse beam search inside vd_model_beam_search (VD_BEAM_GROUPS / VD_BEAM_DIVERSITY, read and
         # refused the same way); generateAnswers(beamBatch > 0) checks its knobs against these.
+        # params beamMinLen / beamNoRepeat / beamLengthPenalty: the constraints of vd_model_beam_search (VD_BEAM_MIN_LEN / VD_BEAM_NO_REPEAT /
+        # VD_BEAM_LENGTH_PENALTY), the same way again.
         import os
         switches = {'VD_OPTION_CACHE': str(int(p.get('optionCache', 0) or 0)),
                     'VD_LHOOD_TREE': '1' if int(p.get('fusedLhood', 0) or 0) == 2 else '0',
                     'VD_SAMPLE_TOPK': None if p.get('topK') is None else str(p['topK']),
                     'VD_SAMPLE_TOPP': None if p.get('topP') is None else str(p['topP']),
                     'VD_BEAM_GROUPS': None if p.get('beamGroups') is None else str(p['beamGroups']),
-                    'VD_BEAM_DIVERSITY': None if p.get('beamDiversity') is None else str(p['beamDiversity'])}
+                    'VD_BEAM_DIVERSITY': None if p.get('beamDiversity') is None else str(p['beamDiversity']),
+                    'VD_BEAM_MIN_LEN': None if p.get('beamMinLen') is None else str(p['beamMinLen']),
+                    'VD_BEAM_NO_REPEAT': None if p.get('beamNoRepeat') is None else str(p['beamNoRepeat']),
+                    'VD_BEAM_LENGTH_PENALTY': None if p.get('beamLengthPenalty') is None else str(p['beamLengthPenalty'])}
         prev = {k: os.environ.get(k) for k in switches}
         try:
             for k, v in switches.items():
@@ -101,6 +106,8 @@ class NativeModel(SplitEval):
         gen = p['decoder'] == 'gen'
         self._sample_knobs = (int(p.get('topK') or 0) if gen else 0, float(1.0 if p.get('topP') is None or not gen else p['topP']))
         self._beam_knobs = (int(p.get('beamGroups') or 1) if gen else 1, float(0.5 if p.get('beamDiversity') is None else p['beamDiversity']))
+        self._beam_limits = (int(p.get('beamMinLen') or 0), int(p.get('beamNoRepeat') or 0), float(p.get('beamLengthPenalty') or 0.0)) if gen \
+            else (0, 0, 0.0)
         self.h = h
         lib = _lib.load()
         self.tensors = []
@@ -368,6 +375,13 @@ class NativeModel(SplitEval):
             raise ValueError("beamBatch > 0 with beamGroups = %d / beamDiversity = %g, but this model was created with beamGroups = %d / "
                              "beamDiversity = %g: the device search takes its groups when the model is created (params beamGroups / "
                              "beamDiversity of NativeModel)" % (int(groups), float(diversity), G, lam))
+
+    def _beam_constraints(self, minLen, noRepeat, lengthPenalty):
+        if (int(minLen), int(noRepeat), float(lengthPenalty)) != self._beam_limits:
+            raise ValueError("beamBatch > 0 with beamMinLen = %d / beamNoRepeat = %d / beamLengthPenalty = %g, but this model was created "
+                             "with beamMinLen = %d / beamNoRepeat = %d / beamLengthPenalty = %g: the device search takes its constraints "
+                             "when the model is created (params beamMinLen / beamNoRepeat / beamLengthPenalty of NativeModel)"
+                             % ((int(minLen), int(noRepeat), float(lengthPenalty)) + self._beam_limits))
 
     def _sample_truncation(self, topK, topP):
         if (int(topK), float(topP)) != self._sample_knobs:

@@ -10,7 +10,8 @@ kernels), and for batched sampling (params sampleBatch > 0) `_gen_sample(beamLen
 [beamLen x N]) -> (tokens [N x (beamLen + 1)], log-likelihoods [N])` (= vd_model_sample; vd_sample_* for the operator-level host), with
 `_sample_truncation(topK, topP)` raising unless that sampler truncates with exactly these knobs.  Diverse beam search (params
 beamGroups = G > 1): `_beam_grouping(groups, diversity)` raises unless that `_gen_beam` searches in exactly these groups, and it then
-returns every group's answer, (tokens [N x G x beamLen], scores [N x G])."""
+returns every group's answer, (tokens [N x G x beamLen], scores [N x G]).  Beam constraints (params beamMinLen / beamNoRepeat /
+beamLengthPenalty): `_beam_constraints(minLen, noRepeat, lengthPenalty)` raises unless that `_gen_beam` searches under exactly these."""
 import math
 
 import numpy as np
@@ -56,25 +57,114 @@ def check_beam_groups(beamSize, groups, diversity):
         raise ValueError('beamDiversity = %r must be a finite real >= 0' % (diversity,))
 
 
-def pick_answer(answers, endToken):
-    """D7: the round's answer among its groups' (tokens, score): the highest score of the groups that finished something (a finished
-    answer holds <END>, a slot's column never does), ties to the lower group; group 0's if none finished"""
+def check_beam_constraints(beamSize, beamLen, minLen, noRepeat, lengthPenalty, vocabSize=None):
+    """the refusals of the beam constraints (csrc/beam.hip C1-C6): minLen and noRepeat are integers >= 0, lengthPenalty a finite real
+    >= 0 (0 = off each); minLen <= beamLen - 2, because <END> must be allowed at the last step; while a ban is on a row must keep
+    beamSize unbanned words: vocabSize >= beamSize + beamLen - 1 (checked where the vocabulary is known)"""
+    for name, v in (('beamMinLen', minLen), ('beamNoRepeat', noRepeat)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError('%s = %r must be an integer >= 0 (0 = off)' % (name, v))
+    if isinstance(lengthPenalty, (bool, str)) or not (np.isfinite(lengthPenalty) and lengthPenalty >= 0.0):
+        raise ValueError('beamLengthPenalty = %r must be a finite real >= 0 (0 = off)' % (lengthPenalty,))
+    if minLen > 0 and minLen > beamLen - 2:
+        raise ValueError('beamMinLen = %d exceeds beamLen - 2 = %d: <END> must be allowed at the last step' % (minLen, beamLen - 2))
+    if (minLen > 0 or noRepeat > 0) and vocabSize is not None and vocabSize < beamSize + beamLen - 1:
+        raise ValueError('beamMinLen = %d / beamNoRepeat = %d need vocabSize = %d >= beamSize + beamLen - 1 = %d, so that a row never '
+                         'runs out of unbanned words' % (minLen, noRepeat, vocabSize, beamSize + beamLen - 1))
+
+
+def beam_banned(column, step, minLen, noRepeat, endToken):
+    """C1-C3 of csrc/beam.hip: the tokens (1-based ids, ascending) a slot with this column may not take at step `step`.  The words of
+    the column are positions 1 .. step-1 (position 0, <START>, is not a word); an n-gram that holds a 0 is ignored.  minLen = m: <END>
+    is banned at every step <= m.  noRepeat = n >= 1, once step >= n: with p the last n - 1 words, every word that followed an earlier
+    occurrence of p is banned (n = 1: every word of the column)."""
+    banned = set()
+    if step <= minLen:
+        banned.add(int(endToken))
+    n = int(noRepeat)
+    if n >= 1 and step >= n:
+        g = [int(t) for t in column[:step]]                       # g[i] = word i for i >= 1
+        p = g[step - n + 1:step]
+        if 0 not in p:
+            for i in range(1, step - n + 1):
+                if g[i:i + n - 1] == p and g[i + n - 1] != 0:
+                    banned.add(g[i + n - 1])
+    return sorted(banned)
+
+
+def length_penalty_table(beamLen, lengthPenalty):
+    """C6: lp[s] = s^alpha for the lengths s < beamLen, in fp64 over libm's pow, as the library builds the table it uploads"""
+    return [float(s) ** float(lengthPenalty) for s in range(beamLen)]
+
+
+def beam_replaces(x_score, x_len, y_score, y_len, lp):
+    """C6: a finished candidate x of another length replaces the incumbent y iff x.score / x.len^alpha > y.score / y.len^alpha, decided
+    without a division: one fp64 product on either side"""
+    return x_score * lp[y_len] > y_score * lp[x_len]
+
+
+def best_finished(finish, lp):
+    """C6 over a finished set in insertion order (dicts with `score` and `step`, the length): per step the best by score, ties to the
+    earliest; across steps `beam_replaces` against the incumbent, ties staying with it.  None if nothing finished."""
     best = None
+    for step in sorted(set(c['step'] for c in finish)):
+        x = None
+        for c in finish:
+            if c['step'] == step and (x is None or c['score'] > x['score']):
+                x = c
+        if best is None or beam_replaces(x['score'], x['step'], best['score'], best['step'], lp):
+            best = x
+    return best
+
+
+def pick_answer(answers, endToken, lengthPenalty=0.0):
+    """D7: the round's answer among its groups' (tokens, score): the highest score of the groups that finished something (a finished
+    answer holds <END>, a slot's column never does), ties to the lower group; group 0's if none finished.  lengthPenalty > 0 (C6): a
+    later group's answer replaces the incumbent by `beam_replaces`, its length the position of <END>."""
+    best = None
+    lp = None
     for tokens, score in answers:
-        if endToken in np.asarray(tokens) and (best is None or score > best[1]):
+        toks = np.asarray(tokens).tolist()
+        if endToken not in toks:
+            continue
+        if best is None:
+            best = (tokens, score)
+        elif lengthPenalty > 0.0:
+            lp = lp or length_penalty_table(len(toks), lengthPenalty)
+            if beam_replaces(score, toks.index(endToken), best[1], np.asarray(best[0]).tolist().index(endToken), lp):
+                best = (tokens, score)
+        elif score > best[1]:
             best = (tokens, score)
     return best if best is not None else answers[0]
 
 
-def beam_search_round(step_fn, select_fn, k, L, start, end, groups=1, diversity=0.5):
+def beam_search_round(step_fn, select_fn, k, L, start, end, groups=1, diversity=0.5, minLen=0, noRepeat=0, lengthPenalty=0.0):
     """The beam search of ONE round on the host (model.lua:466-573): `step_fn(tokens [k]) -> logp [k x V]` is one decoder step of the k
     slots (a slot whose token is 0 gets an all-zero row), `select_fn(src, n_keep)` makes slot i < n_keep continue from the stepped
     state of slot src[i]; the slots start from the round's encoder state (`_gen_begin`).  Returns one (tokens [L], score) per group.
     groups = 1 is the reference's search (rules 1-4 of csrc/beam.hip); groups = G > 1 is diverse beam search with Hamming diversity
     `diversity`, D1-D7 there: group g owns slots g k' .. g k' + k' - 1 (k' = k / G), the groups of a step run in order, a group's row
     is penalised in fp32 by diversity * (the number of earlier groups' slots filled with that word at this step), the penalised
-    values pick and order the candidates (the key), the unpenalised sum is the score that is carried and reported."""
+    values pick and order the candidates (the key), the unpenalised sum is the score that is carried and reported.
+    minLen / noRepeat / lengthPenalty are the constraints C1-C6 there, each off at 0: a banned word (`beam_banned` of the slot's column)
+    counts as -inf in the explored row, every other value and every score is untouched; with a length penalty the best finished
+    candidate is `best_finished`'s instead of the highest-scoring one."""
     check_beam_groups(k, groups, diversity)
+    check_beam_constraints(k, L, minLen, noRepeat, lengthPenalty)
+    ban = minLen > 0 or noRepeat > 0
+    lp = length_penalty_table(L, lengthPenalty) if lengthPenalty > 0.0 else None
+
+    def unbanned(row, column, step):
+        """C4: the explored row with its banned words at -inf"""
+        if row.shape[0] < k + L - 1:
+            raise ValueError('beamMinLen = %d / beamNoRepeat = %d need vocabSize = %d >= beamSize + beamLen - 1 = %d'
+                             % (minLen, noRepeat, row.shape[0], k + L - 1))
+        banned = beam_banned(column, step, minLen, noRepeat, end)
+        if not banned:
+            return row
+        row = np.array(row, np.float32)
+        row[np.asarray(banned) - 1] = -np.inf
+        return row
     beamSize, beamLen, startToken, endToken = k, L, start, end
     beams = np.zeros((beamLen, beamSize), np.int64)
     beams[0] = startToken
@@ -86,13 +176,14 @@ def beam_search_round(step_fn, select_fn, k, L, start, end, groups=1, diversity=
             logp = step_fn(beams[step - 1])
             cands = []
             for wordId in range(exploreSize):
-                top = np.argsort(-logp[wordId], kind='stable')[:beamSize]  # torch.topk(..., true)
+                row = unbanned(np.asarray(logp[wordId]), beams[:, wordId], step) if ban else logp[wordId]
+                top = np.argsort(-row, kind='stable')[:beamSize]           # torch.topk(..., true)
                 for cid in top:
                     cb = beams[:, wordId].copy()
                     cb[step] = cid + 1                                     # vocabulary ids are 1-based
                     sc = scores[wordId] + float(logp[wordId, cid])
                     if cid + 1 == endToken:
-                        finish.append(dict(beam=cb, length=step + 1, score=sc))
+                        finish.append(dict(beam=cb, length=step + 1, score=sc, step=step))
                     else:
                         cands.append(dict(score=sc, beam=cb, src=wordId))
             cands.sort(key=lambda a: -a['score'])                         # (stable; Lua's table.sort is not)
@@ -102,6 +193,9 @@ def beam_search_round(step_fn, select_fn, k, L, start, end, groups=1, diversity=
             for i, c in enumerate(keep):
                 beams[:, i] = c['beam']
                 scores[i] = c['score']
+        if lp is not None and finish:                                     # C6
+            best = best_finished(finish, lp)
+            return [(best['beam'], best['score'])]
         finish.sort(key=lambda a: -a['score'])
         if finish:
             return [(finish[0]['beam'], finish[0]['score'])]
@@ -120,12 +214,14 @@ def beam_search_round(step_fn, select_fn, k, L, start, end, groups=1, diversity=
             cands = []
             for w in range(base, base + exploreSize):
                 a = logp[w] - lam * count.astype(np.float32)              # D4: fp32, product and difference rounded separately
+                if ban:
+                    a = unbanned(a, beams[:, w], step)                    # C4: a penalty leaves -inf where it is
                 for cid in np.argsort(-a, kind='stable')[:kp]:
                     cb = beams[:, w].copy()
                     cb[step] = cid + 1
                     sc = scores[w] + float(logp[w, cid])                  # D5: the true log-likelihood
                     if cid + 1 == endToken:
-                        finish[g].append(dict(beam=cb, score=sc))
+                        finish[g].append(dict(beam=cb, score=sc, step=step))
                     else:
                         cands.append(dict(key=scores[w] + float(a[cid]), score=sc, beam=cb, src=w))
             cands.sort(key=lambda c: -c['key'])                           # D6 (stable)
@@ -137,6 +233,10 @@ def beam_search_round(step_fn, select_fn, k, L, start, end, groups=1, diversity=
         select_fn(src, beamSize)
     out = []
     for g in range(groups):                                               # D7
+        if lp is not None and finish[g]:                                  # C6
+            best = best_finished(finish[g], lp)
+            out.append((best['beam'], best['score']))
+            continue
         finish[g].sort(key=lambda c: -c['score'])
         out.append((finish[g][0]['beam'], finish[g][0]['score']) if finish[g] else (beams[:, g * kp], scores[g * kp]))
     return out
@@ -250,6 +350,14 @@ class SplitEval(object):
             raise ValueError("beamBatch > 0 with beamGroups = %d: the grouped device search runs in the model-level runtime only: use "
                              "-host native (visdial_amd.native.NativeModel); this host searches in groups with beamBatch = 0" % groups)
 
+    def _beam_constraints(self, minLen, noRepeat, lengthPenalty):
+        """raises unless this host's `_gen_beam` searches under exactly these constraints (none here: the operator-level device search
+        goes through the frozen vd_beam_* operators)"""
+        if minLen > 0 or noRepeat > 0 or lengthPenalty > 0.0:
+            raise ValueError("beamBatch > 0 with beamMinLen = %d / beamNoRepeat = %d / beamLengthPenalty = %g: the constrained device "
+                             "search runs in the model-level runtime only: use -host native (visdial_amd.native.NativeModel); this "
+                             "host applies the constraints with beamBatch = 0" % (minLen, noRepeat, lengthPenalty))
+
     def generateAnswers(self, dataloader, dtype, params=None):
         """Beam search (default) or temperature sampling with the generative decoder, one dialog at a time,
         exactly as the reference drives it from the host: the decoder step (embedding, LSTM stack, vocabulary
@@ -262,7 +370,10 @@ class SplitEval(object):
         host whose device sampler truncates (`_sample_truncation`).  params beamGroups = G > 1 (beam search only): diverse beam search,
         `beam_search_round` above, with Hamming diversity params beamDiversity (default 0.5): every dialog entry gains `answers`, the
         G groups' answers in group order, and `answer` is the best of them (`pick_answer`); with beamBatch > 0 it needs a host
-        whose device search runs in groups (`_beam_grouping`).
+        whose device search runs in groups (`_beam_grouping`).  params beamMinLen / beamNoRepeat / beamLengthPenalty (beam search only,
+        each off at 0): no answer of fewer than beamMinLen words, no n-gram of beamNoRepeat words twice in a hypothesis, finished
+        hypotheses compete on score / length^beamLengthPenalty (csrc/beam.hip C1-C6); with beamBatch > 0 they need a host whose device
+        search applies them (`_beam_constraints`).
         Returns [{image_id, dialog: [{question, answer}...]}]."""
         if self.params['decoder'] == 'disc':
             raise SystemExit('Sampling/beam search only for generative model')
@@ -290,8 +401,16 @@ class SplitEval(object):
             check_beam_groups(beamSize, beamGroups, beamDiversity)
             if sampleWords:
                 raise ValueError('beamGroups > 1 is diverse beam search: sampling (sampleWords = 1) has no groups')
+        minLen, noRepeat, lengthPenalty = (0 if params.get(key) is None else params[key]
+                                           for key in ('beamMinLen', 'beamNoRepeat', 'beamLengthPenalty'))
+        if minLen != 0 or noRepeat != 0 or lengthPenalty != 0:
+            check_beam_constraints(beamSize, beamLen, minLen, noRepeat, lengthPenalty, self.params.get('vocabSize'))
+            if sampleWords:
+                raise ValueError('beamMinLen / beamNoRepeat / beamLengthPenalty constrain beam search: sampling (sampleWords = 1) has none')
+        minLen, noRepeat, lengthPenalty = int(minLen), int(noRepeat), float(lengthPenalty)
         if beamBatch > 0:
             self._beam_grouping(beamGroups, beamDiversity)
+            self._beam_constraints(minLen, noRepeat, lengthPenalty)
         startToken, endToken = dataloader.word2ind['<START>'], dataloader.word2ind['<END>']
         numThreads = int(params.get('maxThreads') or dataloader.numThreads[dtype])
         rng = np.random.RandomState(int(params.get('seed', 1234)))
@@ -322,7 +441,7 @@ class SplitEval(object):
                                                  u.transpose(1, 0, 2).reshape(beamLen, B * R))   # [step x row]
                 elif beamGroups > 1:                            # tokens [N x G x beamLen], scores [N x G]
                     grouped, sc = self._gen_beam(beamSize, beamLen, startToken, endToken)
-                    tokens = [pick_answer(list(zip(t, s_)), endToken)[0] for t, s_ in zip(grouped, sc)]
+                    tokens = [pick_answer(list(zip(t, s_)), endToken, lengthPenalty)[0] for t, s_ in zip(grouped, sc)]
                     answerTable += [record(convId, batch['ques_fwd'][i], tokens[i * R:(i + 1) * R], grouped[i * R:(i + 1) * R])
                                     for i, convId in enumerate(convIds)]
                     continue
@@ -341,8 +460,8 @@ class SplitEval(object):
                 for it in range(R):
                     self._gen_begin(np.full(beamSize, it, np.int32))              # hiddenBeams, model.lua:478-503
                     found = beam_search_round(self._gen_step, self._gen_select, beamSize, beamLen, startToken, endToken, beamGroups,
-                                              beamDiversity)
-                    answers.append(pick_answer(found, endToken)[0] if beamGroups > 1 else found[0][0])
+                                              beamDiversity, minLen, noRepeat, lengthPenalty)
+                    answers.append(pick_answer(found, endToken, lengthPenalty)[0] if beamGroups > 1 else found[0][0])
                     grouped.append([tokens for tokens, _ in found])
             else:
                 numQues = R
