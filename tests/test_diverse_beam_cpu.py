@@ -14,7 +14,7 @@ from visdial_amd import split_eval
 from visdial_amd.split_eval import SplitEval, beam_search_round, pick_answer
 
 V, L, START, END = 40, 8, 1, 2
-GRID = [(4, 2, 0.5), (6, 3, 0.5), (6, 6, 1e4), (12, 3, 0.3), (32, 8, 0.5)]
+GRID = [(4, 2, 0.5), (6, 3, 0.5), (6, 6, 1e4), (12, 3, 0.3), (32, 8, 0.5), (32, 2, 0.5)]
 SEEDS = range(6)
 
 
@@ -177,18 +177,32 @@ def test_one_slot_groups_under_a_large_penalty_hold_different_words():
     assert several > 0
 
 
+class RecordingDecoder(TableDecoder):
+    """a TableDecoder that keeps the (src, n_keep) of every select call"""
+
+    def begin(self, k):
+        TableDecoder.begin(self, k)
+        self.selects = []
+
+    def select(self, src, n_keep):
+        self.selects.append((np.asarray(src).tolist(), n_keep))
+        TableDecoder.select(self, src, n_keep)
+
+
 def test_one_group_is_todays_loop():
     for seed in SEEDS:
         for k in (1, 3, 5):
-            dec = TableDecoder(seed)
+            dec = RecordingDecoder(seed)
             dec.begin(k)
             beam, score = todays_loop(dec, k, L, START, END)
             got, _ = search(seed, k, 1, 0.5)
             assert got == [(beam.tolist(), score)], (seed, k)
-            dec2 = TableDecoder(seed)
+            dec2 = RecordingDecoder(seed)
             dec2.begin(k)
             (t3, s3), = beam_search_round(dec2.step, dec2.select, k, L, START, END)      # the knobs default to off
             assert (np.asarray(t3).tolist(), s3) == got[0]
+            assert dec2.selects == dec.selects and dec.selects, (seed, k)                # the kept prefix, and only when there is one
+    assert any(n_keep < k for _, n_keep in dec.selects)                                  # an <END> among step 1's k candidates keeps k - 1
 
 
 def test_pick_answer_is_d7():

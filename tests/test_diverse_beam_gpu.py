@@ -18,7 +18,7 @@ from visdial_amd.opts import default_params, derive
 
 pytestmark = pytest.mark.gpu
 
-GRID = [(4, 2, 0.5), (6, 3, 0.5), (6, 6, 1e4), (12, 3, 0.3), (32, 8, 0.5)]
+GRID = [(4, 2, 0.5), (6, 3, 0.5), (6, 6, 1e4), (12, 3, 0.3), (32, 8, 0.5), (32, 2, 0.5)]
 ENC, L = 'lf-ques-im-hist', 6
 SEED, SCALE, END_BIAS = 8, 4.0, 0.5
 

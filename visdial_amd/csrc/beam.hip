@@ -44,9 +44,9 @@
 //      it finished nothing.  The round's answer is the highest-scoring answer among the groups that finished something, ties to the
 //      lower group; group 0's if none did.  All beamLen-1 steps run.
 // A penalty only lowers a value, and at most (G-1) k' distinct words are penalised, so the top k' of a penalised row lie within the
-// top k of the unpenalised one: beam_topk_kernel at the full k delivers everything a grouped step needs.  Per (round, group) the best
-// finished candidate, the initial state and the answer are rule 1 / rule 3 of N * G groups of k' slots, so beam_init_kernel and
-// beam_finish_kernel serve as they are.
+// top k of the unpenalised one: beam_topk_kernel at the full k delivers everything a step needs, and ONE beam_advance_kernel takes G as
+// an argument (G = 1 ranks nothing anew and penalises nothing).  Per (round, group) the best finished candidate, the initial state and
+// the answer are rule 1 / rule 3 of N * G groups of k' slots, so beam_init_kernel and beam_finish_kernel take (N * G, k').
 //
 // Constraints (behind rules 1-4 and D1-D7; all off by default, and then everything above is unchanged): minimum length m >= 0, no-repeat
 // n-gram size n >= 0, length penalty alpha >= 0 (finite).  split_eval.py restates them (beam_banned, beam_search_round, pick_answer).
@@ -67,12 +67,12 @@
 //      pow: host and device decide bit for bit alike.  Ties stay with the earliest inserted.  D7's choice among the groups of a round
 //      uses the same comparison, ties to the lower group, the length being the position of <END> in the answer.  "Nothing finished"
 //      falls back as before.
-// On the device C2-C4 are the constrained form of the top-k kernel (it reads the row's column from the PRE-advance history), C6 one more
-// argument of the advance kernels; with every knob off the search launches the plain kernels with the arguments it always passed.
+// On the device C2-C4 are the constrained form of the top-k kernel (it reads the row's column from the PRE-advance history), C6 the
+// advance kernel's `lp` argument (nullptr = off); with every knob off the top-k is the plain kernel with the arguments it always had.
 #include "common.h"
 
 #define VD_BEAM_KMAX 32
-#define VD_BEAM_GKMAX (VD_BEAM_KMAX / 2)   // k' = k / G of a grouped search (G >= 2)
+#define VD_BEAM_GKMAX (VD_BEAM_KMAX / 2)   // the largest k' = k / G at G >= 2
 // VD_BEAM_LMAX (common.h): the longest beamLen while n-gram blocking is on -- a column and its ban list sit in LDS
 
 namespace {
@@ -222,149 +222,79 @@ __global__ void beam_init_kernel(int groups, int k, int L, int start, int32_t* _
   }
 }
 
-// rule 2 for one group per workgroup.  Candidate c = w * k + rank (insertion order).  A candidate's place among its kind
-// (unfinished / finished) is the number of that kind with a higher score or an equal score inserted earlier: for the
-// unfinished ones that is the stable sort's position, for the finished ones place 0 is this step's best.  The best finished
-// candidate so far is kept per group (score, length, column); a later one replaces it only with a strictly higher score, so
-// ties stay with the earliest inserted (rule 3).  LP (C6): `lp` [L] holds s^alpha at index s, the length of a candidate that ends at
-// step s; best_len - 1 is the incumbent's.
+// C6: `lp` [L] holds s^alpha at index s, the length of a candidate that ends at step s
 __device__ __forceinline__ bool beam_replaces(double x_score, int x_len, double y_score, int y_len, const double* __restrict__ lp) {
   return __dmul_rn(x_score, lp[y_len]) > __dmul_rn(y_score, lp[x_len]);
 }
 
-template <bool LP>
-__device__ __forceinline__ void
-beam_advance_body(const int32_t* top_idx, const float* top_val, int k, int step, int L, int end_tok,
-                  double* scores, const int32_t* hist_in, int32_t* hist_out,
-                  int32_t* src, int32_t* next_tok, double* best_score,
-                  int32_t* best_len, int32_t* best_hist, const double* lp) {
-  __shared__ double csc[VD_BEAM_KMAX * VD_BEAM_KMAX];
-  __shared__ int ctok[VD_BEAM_KMAX * VD_BEAM_KMAX];
-  __shared__ double slot_sc[VD_BEAM_KMAX];
-  __shared__ int slot_src[VD_BEAM_KMAX], slot_tok[VD_BEAM_KMAX];
-  __shared__ int n_cands, best_c;
-  const int g = blockIdx.x, tid = threadIdx.x;
-  const long g0 = (long)g * k;
-  const int explore = step == 1 ? 1 : k, C = explore * k;
-  if (tid == 0) { n_cands = 0; best_c = -1; }
-  if (tid < VD_BEAM_KMAX) slot_src[tid] = 0;                      // a valid source row even if a NaN score left a place unfilled
-  for (int c = tid; c < C; c += blockDim.x) {
-    const int w = c / k, q = c - w * k;
-    const long e = (g0 + w) * k + q;
-    ctok[c] = top_idx[e] + 1;                                      // vocabulary ids are 1-based
-    csc[c] = scores[g0 + w] + (double)top_val[e];                  // fp64, as the hosts add
-  }
-  __syncthreads();
-  for (int c = tid; c < C; c += blockDim.x) {
-    const bool fin = ctok[c] == end_tok;
-    const double sc = csc[c];
-    int pos = 0;
-    for (int c2 = 0; c2 < C; ++c2) {
-      if ((ctok[c2] == end_tok) != fin) continue;
-      const double s2 = csc[c2];
-      pos += (s2 > sc || (s2 == sc && c2 < c)) ? 1 : 0;
-    }
-    if (fin) {
-      if (pos == 0) best_c = c;
-    } else {
-      atomicAdd(&n_cands, 1);
-      if (pos < k) { slot_sc[pos] = sc; slot_src[pos] = c / k; slot_tok[pos] = ctok[c]; }
-    }
-  }
-  __syncthreads();
-  const int n_keep = min(n_cands, k);
-  if (tid == 0 && best_c >= 0) {
-    const double sc = csc[best_c];
-    if (best_len[g] == 0 || (LP ? beam_replaces(sc, step, best_score[g], best_len[g] - 1, lp) : sc > best_score[g])) {
-      const int32_t* col = hist_in + (g0 + best_c / k) * L;
-      best_score[g] = sc;
-      best_len[g] = step + 1;
-      for (int p = 0; p < L; ++p) best_hist[(long)g * L + p] = p < step ? col[p] : p == step ? end_tok : 0;
-    }
-  }
-  for (int e = tid; e < k * L; e += blockDim.x) {
-    const int i = e / L, p = e - i * L;
-    int v;
-    if (i < n_keep) v = p == step ? slot_tok[i] : hist_in[(g0 + slot_src[i]) * L + p];
-    else v = hist_in[(g0 + i) * L + p];
-    hist_out[(g0 + i) * L + p] = v;
-    if (p == step) next_tok[g0 + i] = v;
-  }
-  for (int i = tid; i < k; i += blockDim.x) {
-    src[g0 + i] = i < n_keep ? slot_src[i] : -1;
-    if (i < n_keep) scores[g0 + i] = slot_sc[i];                  // every read of `scores` happened before the first barrier
-  }
-}
-
+// Rule 2 / D2-D6 for one round per workgroup, its G groups of k' = k / G slots one after another (a group's penalties need the earlier
+// groups' slots).  Candidate c = w * k' + rank (insertion order) carries a KEY and a SCORE (D5).  A candidate's place among its kind is
+// the number of that kind with a higher value or an equal value inserted earlier: for the unfinished ones, by key, that is the stable
+// sort's position; for the finished ones, by score, place 0 is this step's best.  The best finished candidate so far is kept per
+// (round, group) (score, length + 1, column); a later one replaces it only with a strictly higher score -- under `lp` (C6, nullptr =
+// off) by beam_replaces, best_len - 1 the incumbent's length -- so ties stay with the earliest inserted (rule 3).
+//  G == 1: a candidate's rank is its position in the row the caller handed over (vd_beam_advance takes rows in any order), and its key
+//          IS its score: the candidate tables are filled straight from top_idx / top_val, and `ckey` aliases `csc`.
+//  G >= 2: `count` is a list of (word, multiplicity) pairs, at most one per slot of the earlier groups.  The k candidates of every
+//          explored slot (beam_topk_kernel's, unpenalised order) get their penalised value and their rank under it (D4); the ranks
+//          < k' are the slot's candidates.  k' <= VD_BEAM_GKMAX.
+// best_* are indexed round * G + group; `src` is a round-local slot index.  ONE: G == 1 at compile time -- the same source with the G >= 2
+// passes and tables folded away, because the kernel with G read at run time took 6.7 us against 6.0 us (profiles/beam_fold.txt).
+template <bool ONE>
 __global__ void __launch_bounds__(256)
-beam_advance_kernel(const int32_t* __restrict__ top_idx, const float* __restrict__ top_val, int k, int step, int L, int end_tok,
-                    double* __restrict__ scores, const int32_t* __restrict__ hist_in, int32_t* __restrict__ hist_out,
+beam_advance_kernel(const int32_t* __restrict__ top_idx, const float* __restrict__ top_val, int k, int groups, float lambda, int step, int L,
+                    int end_tok, double* __restrict__ scores, const int32_t* __restrict__ hist_in, int32_t* __restrict__ hist_out,
                     int32_t* __restrict__ src, int32_t* __restrict__ next_tok, double* __restrict__ best_score,
-                    int32_t* __restrict__ best_len, int32_t* __restrict__ best_hist) {
-  beam_advance_body<false>(top_idx, top_val, k, step, L, end_tok, scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist,
-                           nullptr);
-}
-
-__global__ void __launch_bounds__(256)
-beam_advance_lp_kernel(const int32_t* __restrict__ top_idx, const float* __restrict__ top_val, int k, int step, int L, int end_tok,
-                       double* __restrict__ scores, const int32_t* __restrict__ hist_in, int32_t* __restrict__ hist_out,
-                       int32_t* __restrict__ src, int32_t* __restrict__ next_tok, double* __restrict__ best_score,
-                       int32_t* __restrict__ best_len, int32_t* __restrict__ best_hist, const double* __restrict__ lp) {
-  beam_advance_body<true>(top_idx, top_val, k, step, L, end_tok, scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist,
-                          lp);
-}
-
-// D2-D6 for one round per workgroup, its G groups one after another (a group's penalties need the earlier groups' slots).  `count` is
-// a list of (word, multiplicity) pairs, at most one per slot.  Per group: the k candidates of every explored slot (beam_topk_kernel's,
-// unpenalised order) get their penalised value and their rank under it; the ranks < k' are the slot's candidates, candidate
-// c = w * k' + rank (insertion order), and from there on this is beam_advance_kernel on the group's k' slots with the key ordering the
-// unfinished candidates and the score carried.  best_* are per (round, group); `src` stays a round-local slot index.
-template <bool LP>
-__device__ __forceinline__ void
-beam_advance_grouped_body(const int32_t* top_idx, const float* top_val, int k, int G, float lambda, int step,
-                          int L, int end_tok, double* scores, const int32_t* hist_in,
-                          int32_t* hist_out, int32_t* src, int32_t* next_tok,
-                          double* best_score, int32_t* best_len, int32_t* best_hist,
-                          const double* lp) {
-  __shared__ float pen[VD_BEAM_GKMAX * VD_BEAM_KMAX];
-  __shared__ double ckey[VD_BEAM_GKMAX * VD_BEAM_GKMAX], csc[VD_BEAM_GKMAX * VD_BEAM_GKMAX];
-  __shared__ int ctok[VD_BEAM_GKMAX * VD_BEAM_GKMAX];
-  __shared__ double slot_sc[VD_BEAM_GKMAX];
-  __shared__ int slot_src[VD_BEAM_GKMAX], slot_tok[VD_BEAM_GKMAX];
+                    int32_t* __restrict__ best_len, int32_t* __restrict__ best_hist, const double* __restrict__ lp) {
+  constexpr int KP = ONE ? VD_BEAM_KMAX : VD_BEAM_GKMAX;          // the largest k'
+  __shared__ float pen[ONE ? 1 : KP * VD_BEAM_KMAX];
+  __shared__ double key_tab[ONE ? 1 : KP * KP], csc[KP * KP];
+  __shared__ int ctok[KP * KP];
+  __shared__ double slot_sc[KP];
+  __shared__ int slot_src[KP], slot_tok[KP];
   __shared__ int cnt_word[VD_BEAM_KMAX], cnt_mult[VD_BEAM_KMAX];
   __shared__ int n_cnt, n_cands, best_c;
   const int r = blockIdx.x, tid = threadIdx.x;
   const long r0 = (long)r * k;
-  const int kp = k / G, explore = step == 1 ? 1 : kp, C = explore * kp, E = explore * k;
+  const int G = ONE ? 1 : groups, kp = k / G, explore = step == 1 ? 1 : kp, C = explore * kp, E = explore * k;
+  double* ckey = ONE ? csc : key_tab;
   if (tid == 0) n_cnt = 0;
   for (int g = 0; g < G; ++g) {
     const long g0 = r0 + (long)g * kp;                             // the group's first hypothesis row
     __syncthreads();                                               // the earlier group is done with the tables; its counts are in
     if (tid == 0) { n_cands = 0; best_c = -1; }
-    if (tid < VD_BEAM_GKMAX) { slot_src[tid] = 0; slot_tok[tid] = 0; slot_sc[tid] = 0.0; }   // valid even if a NaN left a place unfilled
-    for (int c = tid; c < C; c += blockDim.x) { ctok[c] = 0; ckey[c] = 0.0; csc[c] = 0.0; }
-    for (int e = tid; e < E; e += blockDim.x) {                    // D4
-      const int w = e / k, q = e - w * k;
-      const long t = (g0 + w) * k + q;
-      const int v = top_idx[t];
-      int mult = 0;
-      for (int j = 0; j < n_cnt; ++j) mult = cnt_word[j] == v ? cnt_mult[j] : mult;
-      pen[e] = __fsub_rn(top_val[t], __fmul_rn(lambda, (float)mult));
-    }
-    __syncthreads();
-    for (int e = tid; e < E; e += blockDim.x) {
-      const int w = e / k, q = e - w * k;
-      const long t0 = (g0 + w) * k;
-      const float av = pen[e];
-      const int ai = top_idx[t0 + q];
-      int rank = 0;
-      for (int q2 = 0; q2 < k; ++q2) rank += beam_better(pen[w * k + q2], top_idx[t0 + q2], av, ai) ? 1 : 0;
-      if (rank < kp) {                                             // D5
-        const int c = w * kp + rank;
-        const double s = scores[g0 + w];
-        ctok[c] = ai + 1;
-        ckey[c] = s + (double)av;
-        csc[c] = s + (double)top_val[t0 + q];
+    if (tid < KP) { slot_src[tid] = 0; slot_tok[tid] = 0; slot_sc[tid] = 0.0; }   // valid even if a NaN left a place unfilled
+    if (ONE) {
+      for (int c = tid; c < C; c += blockDim.x) {
+        const int w = c / k;
+        ctok[c] = top_idx[g0 * k + c] + 1;                         // vocabulary ids are 1-based
+        csc[c] = scores[g0 + w] + (double)top_val[g0 * k + c];     // fp64, as the hosts add
+      }
+    } else {
+      for (int c = tid; c < C; c += blockDim.x) { ctok[c] = 0; ckey[c] = 0.0; csc[c] = 0.0; }
+      for (int e = tid; e < E; e += blockDim.x) {                  // D4
+        const int w = e / k, q = e - w * k;
+        const long t = (g0 + w) * k + q;
+        const int v = top_idx[t];
+        int mult = 0;
+        for (int j = 0; j < n_cnt; ++j) mult = cnt_word[j] == v ? cnt_mult[j] : mult;
+        pen[e] = __fsub_rn(top_val[t], __fmul_rn(lambda, (float)mult));
+      }
+      __syncthreads();
+      for (int e = tid; e < E; e += blockDim.x) {
+        const int w = e / k, q = e - w * k;
+        const long t0 = (g0 + w) * k;
+        const float av = pen[e];
+        const int ai = top_idx[t0 + q];
+        int rank = 0;
+        for (int q2 = 0; q2 < k; ++q2) rank += beam_better(pen[w * k + q2], top_idx[t0 + q2], av, ai) ? 1 : 0;
+        if (rank < kp) {                                           // D5
+          const int c = w * kp + rank;
+          const double s = scores[g0 + w];
+          ctok[c] = ai + 1;
+          ckey[c] = s + (double)av;
+          csc[c] = s + (double)top_val[t0 + q];
+        }
       }
     }
     __syncthreads();
@@ -390,14 +320,14 @@ beam_advance_grouped_body(const int32_t* top_idx, const float* top_val, int k, i
       const long bg = (long)r * G + g;
       if (best_c >= 0) {
         const double sc = csc[best_c];
-        if (best_len[bg] == 0 || (LP ? beam_replaces(sc, step, best_score[bg], best_len[bg] - 1, lp) : sc > best_score[bg])) {
+        if (best_len[bg] == 0 || (lp ? beam_replaces(sc, step, best_score[bg], best_len[bg] - 1, lp) : sc > best_score[bg])) {
           const int32_t* col = hist_in + (g0 + best_c / kp) * L;
           best_score[bg] = sc;
           best_len[bg] = step + 1;
           for (int p = 0; p < L; ++p) best_hist[bg * L + p] = p < step ? col[p] : p == step ? end_tok : 0;
         }
       }
-      for (int i = 0; i < n_keep; ++i) {                           // D2: the filled slots' words, for the groups after this one
+      for (int i = 0; g + 1 < G && i < n_keep; ++i) {              // D2: the filled slots' words, for the groups after this one
         const int v = slot_tok[i] - 1;
         int j = 0;
         while (j < n_cnt && cnt_word[j] != v) ++j;
@@ -415,28 +345,9 @@ beam_advance_grouped_body(const int32_t* top_idx, const float* top_val, int k, i
     }
     for (int i = tid; i < kp; i += blockDim.x) {
       src[g0 + i] = i < n_keep ? g * kp + slot_src[i] : -1;
-      if (i < n_keep) scores[g0 + i] = slot_sc[i];                 // the group's reads of `scores` are two barriers back
+      if (i < n_keep) scores[g0 + i] = slot_sc[i];                 // the group's reads of `scores` are a barrier or more back
     }
   }
-}
-
-__global__ void __launch_bounds__(256)
-beam_advance_grouped_kernel(const int32_t* __restrict__ top_idx, const float* __restrict__ top_val, int k, int G, float lambda, int step,
-                            int L, int end_tok, double* __restrict__ scores, const int32_t* __restrict__ hist_in,
-                            int32_t* __restrict__ hist_out, int32_t* __restrict__ src, int32_t* __restrict__ next_tok,
-                            double* __restrict__ best_score, int32_t* __restrict__ best_len, int32_t* __restrict__ best_hist) {
-  beam_advance_grouped_body<false>(top_idx, top_val, k, G, lambda, step, L, end_tok, scores, hist_in, hist_out, src, next_tok, best_score,
-                                   best_len, best_hist, nullptr);
-}
-
-__global__ void __launch_bounds__(256)
-beam_advance_grouped_lp_kernel(const int32_t* __restrict__ top_idx, const float* __restrict__ top_val, int k, int G, float lambda, int step,
-                               int L, int end_tok, double* __restrict__ scores, const int32_t* __restrict__ hist_in,
-                               int32_t* __restrict__ hist_out, int32_t* __restrict__ src, int32_t* __restrict__ next_tok,
-                               double* __restrict__ best_score, int32_t* __restrict__ best_len, int32_t* __restrict__ best_hist,
-                               const double* __restrict__ lp) {
-  beam_advance_grouped_body<true>(top_idx, top_val, k, G, lambda, step, L, end_tok, scores, hist_in, hist_out, src, next_tok, best_score,
-                                  best_len, best_hist, lp);
 }
 
 // cur[r] = stepped[group(r) * k + src[r]] where src[r] >= 0; the row is left alone otherwise
@@ -464,24 +375,20 @@ __global__ void beam_finish_kernel(int groups, int k, int L, const int32_t* __re
 
 }  // namespace
 
-// the grouped vd_beam_advance (rt_core.h): `rounds` rounds of G groups of k / G slots; best_* are [rounds x G]; lp = nullptr: no length
-// penalty, the kernel and the arguments of before
-int vd_beam_advance_grouped_p(const int32_t* top_idx, const float* top_val, int rounds, int k, int G, float lambda, int step, int beam_len,
-                              int end_token, double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok,
-                              double* best_score, int32_t* best_len, int32_t* best_hist, const double* lp, hipStream_t stream) {
+// vd_beam_advance (rt_core.h): `rounds` rounds of G groups of k / G slots
+int vd_beam_advance_p(const int32_t* top_idx, const float* top_val, int rounds, int k, int G, float lambda, int step, int beam_len,
+                      int end_token, double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok,
+                      double* best_score, int32_t* best_len, int32_t* best_hist, const double* lp, hipStream_t stream) {
   VD_CHECK_ARG(top_idx && top_val && scores && hist_in && hist_out && src && next_tok && best_score && best_len && best_hist &&
-               rounds >= 0 && hist_in != hist_out, "vd_beam_advance_grouped: bad args");
-  VD_CHECK_ARG(k >= 2 && k <= VD_BEAM_KMAX && G >= 2 && k % G == 0, "vd_beam_advance_grouped: G = %d must be >= 2 and divide k = %d in [2, %d]",
-               G, k, VD_BEAM_KMAX);
-  VD_CHECK_ARG(lambda >= 0.f && lambda < INFINITY, "vd_beam_advance_grouped: lambda = %g must be finite and >= 0", (double)lambda);
-  VD_CHECK_ARG(step >= 1 && step < beam_len, "vd_beam_advance_grouped: step %d outside [1, %d)", step, beam_len);
+               rounds >= 0 && hist_in != hist_out, "vd_beam_advance: bad args");
+  VD_CHECK_ARG(k >= 1 && k <= VD_BEAM_KMAX, "vd_beam_advance: k = %d must be in [1, %d]", k, VD_BEAM_KMAX);
+  VD_CHECK_ARG(G >= 1 && k % G == 0, "vd_beam_advance: G = %d must be >= 1 and divide k = %d", G, k);
+  VD_CHECK_ARG(lambda >= 0.f && lambda < INFINITY, "vd_beam_advance: lambda = %g must be finite and >= 0", (double)lambda);
+  VD_CHECK_ARG(step >= 1 && step < beam_len, "vd_beam_advance: step %d outside [1, %d)", step, beam_len);
   if (rounds == 0) return VD_OK;
-  if (lp)
-    hipLaunchKernelGGL(beam_advance_grouped_lp_kernel, dim3((unsigned)rounds), dim3(256), 0, stream, top_idx, top_val, k, G, lambda, step,
-                       beam_len, end_token, scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist, lp);
-  else
-    hipLaunchKernelGGL(beam_advance_grouped_kernel, dim3((unsigned)rounds), dim3(256), 0, stream, top_idx, top_val, k, G, lambda, step,
-                       beam_len, end_token, scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist);
+  auto kern = G == 1 ? beam_advance_kernel<true> : beam_advance_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)rounds), dim3(256), 0, stream, top_idx, top_val, k, G, lambda, step, beam_len, end_token, scores,
+                     hist_in, hist_out, src, next_tok, best_score, best_len, best_hist, lp);
   VD_LAUNCH_CHECK();
   return VD_OK;
 }
@@ -506,21 +413,6 @@ int vd_beam_topk_ban_p(const float* logits, int64_t ld, int64_t rows, int V, con
   else
     hipLaunchKernelGGL(beam_topk_ban_kernel<VD_BEAM_KMAX>, dim3((unsigned)rows), dim3(256), 0, stream, logits, (long)ld, V, tok, k, hist,
                        beam_len, step, min_len, no_repeat, end_token, top_idx, top_val);
-  VD_LAUNCH_CHECK();
-  return VD_OK;
-}
-
-// vd_beam_advance under C6 (rt_core.h): lp [beam_len] on the device, lp[s] = s^alpha
-int vd_beam_advance_lp_p(const int32_t* top_idx, const float* top_val, int groups, int k, int step, int beam_len, int end_token,
-                         double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok, double* best_score,
-                         int32_t* best_len, int32_t* best_hist, const double* lp, hipStream_t stream) {
-  VD_CHECK_ARG(top_idx && top_val && scores && hist_in && hist_out && src && next_tok && best_score && best_len && best_hist && lp &&
-               groups >= 0 && hist_in != hist_out, "vd_beam_advance_lp: bad args");
-  VD_CHECK_ARG(k >= 1 && k <= VD_BEAM_KMAX, "vd_beam_advance_lp: k = %d must be in [1, %d]", k, VD_BEAM_KMAX);
-  VD_CHECK_ARG(step >= 1 && step < beam_len, "vd_beam_advance_lp: step %d outside [1, %d)", step, beam_len);
-  if (groups == 0) return VD_OK;
-  hipLaunchKernelGGL(beam_advance_lp_kernel, dim3((unsigned)groups), dim3(256), 0, stream, top_idx, top_val, k, step, beam_len, end_token,
-                     scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist, lp);
   VD_LAUNCH_CHECK();
   return VD_OK;
 }
@@ -557,15 +449,8 @@ int vd_beam_init(int groups, int k, int beam_len, int start_token, int32_t* hist
 int vd_beam_advance(const int32_t* top_idx, const float* top_val, int groups, int k, int step, int beam_len, int end_token,
                     double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok, double* best_score,
                     int32_t* best_len, int32_t* best_hist, void* stream) {
-  VD_CHECK_ARG(top_idx && top_val && scores && hist_in && hist_out && src && next_tok && best_score && best_len && best_hist &&
-               groups >= 0 && hist_in != hist_out, "vd_beam_advance: bad args");
-  VD_CHECK_ARG(k >= 1 && k <= VD_BEAM_KMAX, "vd_beam_advance: k = %d must be in [1, %d]", k, VD_BEAM_KMAX);
-  VD_CHECK_ARG(step >= 1 && step < beam_len, "vd_beam_advance: step %d outside [1, %d)", step, beam_len);
-  if (groups == 0) return VD_OK;
-  hipLaunchKernelGGL(beam_advance_kernel, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, top_idx, top_val, k, step,
-                     beam_len, end_token, scores, hist_in, hist_out, src, next_tok, best_score, best_len, best_hist);
-  VD_LAUNCH_CHECK();
-  return VD_OK;
+  return vd_beam_advance_p(top_idx, top_val, groups, k, 1, 0.f, step, beam_len, end_token, scores, hist_in, hist_out, src, next_tok,
+                           best_score, best_len, best_hist, nullptr, (hipStream_t)stream);
 }
 
 int vd_beam_select_rows(float* cur, const float* stepped, const int32_t* src, int64_t rows, int k, int H, void* stream) {

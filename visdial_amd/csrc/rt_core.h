@@ -61,22 +61,19 @@ int vd_sample_draw_trunc_p(const float* logits, int64_t ld, int64_t rows, int V,
                            int top_k, double top_p, int step, int beam_len, int end_token, int32_t* hist, double* loglik, int32_t* status,
                            hipStream_t stream);
 
-// beam.hip: vd_beam_advance for a search in G >= 2 groups per round (VD_BEAM_GROUPS / VD_BEAM_DIVERSITY; the rule is beam.hip's header
-// D1-D7): `rounds` rounds of k slots, group g of a round owns slots g k/G .. ; best_score / best_len / best_hist are [rounds x G].
-// lp: the length-penalty table of C6 below on the device, or nullptr = off (the kernel and the arguments of before)
-int vd_beam_advance_grouped_p(const int32_t* top_idx, const float* top_val, int rounds, int k, int G, float lambda, int step, int beam_len,
-                              int end_token, double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok,
-                              double* best_score, int32_t* best_len, int32_t* best_hist, const double* lp, hipStream_t stream);
-// beam.hip, the constrained forms (VD_BEAM_MIN_LEN / VD_BEAM_NO_REPEAT / VD_BEAM_LENGTH_PENALTY; the rule is beam.hip's header C1-C6).
-// vd_beam_topk_ban_p: vd_beam_topk with the words banned that minimum length and n-gram blocking ban for the row's column, read from
-// the PRE-advance history `hist` [rows x beam_len] at `step`; needs V >= k + beam_len - 1, and beam_len <= VD_BEAM_LMAX while
-// no_repeat >= 1.  vd_beam_advance_lp_p: vd_beam_advance whose best finished candidate is replaced across steps by
-// x.score * lp[y.len] > y.score * lp[x.len]; lp [beam_len] on the device, lp[s] = s^alpha computed on the host in fp64.
+// beam.hip: vd_beam_advance with the knobs of the search.  `rounds` rounds of k slots in G >= 1 groups (VD_BEAM_GROUPS / VD_BEAM_DIVERSITY;
+// the rule is beam.hip's header D1-D7): group g of a round owns slots g k/G .. , G divides k, lambda is finite and >= 0 (unused at G = 1);
+// best_score / best_len / best_hist are [rounds x G].  lp (VD_BEAM_LENGTH_PENALTY, C6 there): the best finished candidate is replaced
+// across steps by x.score * lp[y.len] > y.score * lp[x.len], lp [beam_len] on the device, lp[s] = s^alpha computed on the host in fp64;
+// nullptr = off.  vd_beam_advance is G = 1, lambda = 0, lp = nullptr.
+int vd_beam_advance_p(const int32_t* top_idx, const float* top_val, int rounds, int k, int G, float lambda, int step, int beam_len,
+                      int end_token, double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok,
+                      double* best_score, int32_t* best_len, int32_t* best_hist, const double* lp, hipStream_t stream);
+// beam.hip: vd_beam_topk with the words banned that minimum length and n-gram blocking ban for the row's column (VD_BEAM_MIN_LEN /
+// VD_BEAM_NO_REPEAT; C1-C4 there), read from the PRE-advance history `hist` [rows x beam_len] at `step`; needs V >= k + beam_len - 1, and
+// beam_len <= VD_BEAM_LMAX while no_repeat >= 1
 int vd_beam_topk_ban_p(const float* logits, int64_t ld, int64_t rows, int V, const int32_t* tok, int k, const int32_t* hist, int beam_len,
                        int step, int min_len, int no_repeat, int end_token, int32_t* top_idx, float* top_val, hipStream_t stream);
-int vd_beam_advance_lp_p(const int32_t* top_idx, const float* top_val, int groups, int k, int step, int beam_len, int end_token,
-                         double* scores, const int32_t* hist_in, int32_t* hist_out, int32_t* src, int32_t* next_tok, double* best_score,
-                         int32_t* best_len, int32_t* best_hist, const double* lp, hipStream_t stream);
 
 #define VD_TRY(expr)                  \
   do {                                \

@@ -760,10 +760,10 @@ inline int gen_read_back(vd_model* m, const void* out, size_t bytes, std::vector
 // Model:generateAnswers' beam search (model.lua:466-573): N rounds of k slots = N * k hypothesis rows.  Per step: fused
 // log-softmax + top-k -> advance (candidate bookkeeping, csrc/beam.hip) -> state select; then the best answer and score per round.
 // A model created with VD_BEAM_GROUPS = G > 1 searches every round in G groups of k / G slots (beam.hip D1-D7): the same top-k at the
-// full k, the grouped advance, the same select; the best-finished state, the start and the answers are those of N * G groups of k / G
-// slots, so init and finish take (N * G, k / G) and the answers come back [N x G x L] / [N x G].  G = 1 launches what it always did.
-// VD_BEAM_MIN_LEN / VD_BEAM_NO_REPEAT (beam.hip C1-C4) swap the top-k for its constrained form, VD_BEAM_LENGTH_PENALTY (C6) the advance for
-// the one that takes the table s^alpha; with all three off the launches and their arguments are the ones of before.
+// full k, the same advance and select with G as an argument; the best-finished state, the start and the answers are those of N * G
+// groups of k / G slots, so init and finish take (N * G, k / G) and the answers come back [N x G x L] / [N x G].
+// VD_BEAM_MIN_LEN / VD_BEAM_NO_REPEAT (beam.hip C1-C4) swap the top-k for its constrained form, VD_BEAM_LENGTH_PENALTY (C6) hands the
+// advance the table s^alpha.
 inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end, int32_t* host_tokens, double* host_scores) {
   VD_CHECK_ARG(m->gen_enc_out && m->N > 0, "vd_model_beam_search: call vd_model_encode first");
   VD_CHECK_ARG(host_tokens && host_scores && L >= 1, "vd_model_beam_search: bad arguments");
@@ -813,15 +813,8 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
       VD_TRY(vd_beam_topk_ban_p(logits, g->Vp, n, (int)g->V, tok, k, hist[0], L, step, min_len, no_repeat, end, top_idx, top_val, s));
     else
       VD_TRY(vd_beam_topk(logits, g->Vp, n, (int)g->V, tok, k, top_idx, top_val, s));
-    if (groups > 1)
-      VD_TRY(vd_beam_advance_grouped_p(top_idx, top_val, N, k, groups, (float)m->beam_diversity, step, L, end, scores, hist[0], hist[1], src,
-                                       tok, best_score, best_len, best_hist, lp, s));
-    else if (penalty)
-      VD_TRY(vd_beam_advance_lp_p(top_idx, top_val, G, k, step, L, end, scores, hist[0], hist[1], src, tok, best_score, best_len, best_hist,
-                                  lp, s));
-    else
-      VD_TRY(vd_beam_advance(top_idx, top_val, G, k, step, L, end, scores, hist[0], hist[1], src, tok, best_score, best_len, best_hist,
-                             s));
+    VD_TRY(vd_beam_advance_p(top_idx, top_val, N, k, groups, (float)m->beam_diversity, step, L, end, scores, hist[0], hist[1], src, tok,
+                             best_score, best_len, best_hist, lp, s));
     std::swap(hist[0], hist[1]);
     return VD_OK;
   }));

@@ -169,43 +169,15 @@ def beam_search_round(step_fn, select_fn, k, L, start, end, groups=1, diversity=
     beams = np.zeros((beamLen, beamSize), np.int64)
     beams[0] = startToken
     scores = np.zeros(beamSize)
-    if groups == 1:
-        finish = []
-        for step in range(1, beamLen):
-            exploreSize = 1 if step == 1 else beamSize                    # all beams are <START> at first
-            logp = step_fn(beams[step - 1])
-            cands = []
-            for wordId in range(exploreSize):
-                row = unbanned(np.asarray(logp[wordId]), beams[:, wordId], step) if ban else logp[wordId]
-                top = np.argsort(-row, kind='stable')[:beamSize]           # torch.topk(..., true)
-                for cid in top:
-                    cb = beams[:, wordId].copy()
-                    cb[step] = cid + 1                                     # vocabulary ids are 1-based
-                    sc = scores[wordId] + float(logp[wordId, cid])
-                    if cid + 1 == endToken:
-                        finish.append(dict(beam=cb, length=step + 1, score=sc, step=step))
-                    else:
-                        cands.append(dict(score=sc, beam=cb, src=wordId))
-            cands.sort(key=lambda a: -a['score'])                         # (stable; Lua's table.sort is not)
-            keep = cands[:beamSize]
-            if keep:                                                      # untouched slots keep their old state
-                select_fn(np.array([c['src'] for c in keep], np.int32), len(keep))
-            for i, c in enumerate(keep):
-                beams[:, i] = c['beam']
-                scores[i] = c['score']
-        if lp is not None and finish:                                     # C6
-            best = best_finished(finish, lp)
-            return [(best['beam'], best['score'])]
-        finish.sort(key=lambda a: -a['score'])
-        if finish:
-            return [(finish[0]['beam'], finish[0]['score'])]
-        return [(beams[:, 0], scores[0])]                                 # (the reference errors if none ended)
-    kp, lam = beamSize // groups, np.float32(diversity)
+    # groups = 1 is one group of k slots whose key IS the score: nothing is penalised, and `step_fn`'s rows are taken as they come
+    kp, lam, penalise = beamSize // groups, np.float32(diversity), groups > 1
     finish = [[] for _ in range(groups)]
     for step in range(1, beamLen):
-        exploreSize = 1 if step == 1 else kp                              # D3
-        logp = np.asarray(step_fn(beams[step - 1]), np.float32)
-        count = np.zeros(logp.shape[1], np.int64)                         # D2: from zero at every step
+        exploreSize = 1 if step == 1 else kp                              # all beams are <START> at first (D3)
+        logp = step_fn(beams[step - 1])
+        if penalise:
+            logp = np.asarray(logp, np.float32)
+            count = np.zeros(logp.shape[1], np.int64)                     # D2: from zero at every step
         # An untouched slot (D6) names itself: `select_fn` fills a prefix of the slots, and the state such a slot holds is never
         # observed -- its next token is 0, and a token-0 step zeroes the state whatever it was (maskZero)
         src = np.arange(beamSize, dtype=np.int32)
@@ -213,24 +185,31 @@ def beam_search_round(step_fn, select_fn, k, L, start, end, groups=1, diversity=
             base = g * kp
             cands = []
             for w in range(base, base + exploreSize):
-                a = logp[w] - lam * count.astype(np.float32)              # D4: fp32, product and difference rounded separately
+                a = logp[w]
+                if penalise:
+                    a = a - lam * count.astype(np.float32)                # D4: fp32, product and difference rounded separately
                 if ban:
-                    a = unbanned(a, beams[:, w], step)                    # C4: a penalty leaves -inf where it is
-                for cid in np.argsort(-a, kind='stable')[:kp]:
+                    a = unbanned(np.asarray(a), beams[:, w], step)        # C4: a penalty leaves -inf where it is
+                for cid in np.argsort(-a, kind='stable')[:kp]:            # torch.topk(..., true)
                     cb = beams[:, w].copy()
-                    cb[step] = cid + 1
+                    cb[step] = cid + 1                                    # vocabulary ids are 1-based
                     sc = scores[w] + float(logp[w, cid])                  # D5: the true log-likelihood
                     if cid + 1 == endToken:
                         finish[g].append(dict(beam=cb, score=sc, step=step))
                     else:
-                        cands.append(dict(key=scores[w] + float(a[cid]), score=sc, beam=cb, src=w))
-            cands.sort(key=lambda c: -c['key'])                           # D6 (stable)
-            for i, c in enumerate(cands[:kp]):
+                        cands.append(dict(key=scores[w] + float(a[cid]) if penalise else sc, score=sc, beam=cb, src=w))
+            cands.sort(key=lambda c: -c['key'])                           # D6 (stable; Lua's table.sort is not)
+            keep = cands[:kp]
+            for i, c in enumerate(keep):
                 beams[:, base + i] = c['beam']
                 scores[base + i] = c['score']
                 src[base + i] = c['src']
-                count[c['beam'][step] - 1] += 1
-        select_fn(src, beamSize)
+                if penalise:
+                    count[c['beam'][step] - 1] += 1
+        if penalise:
+            select_fn(src, beamSize)
+        elif keep:                                                        # the reference's call: the kept prefix, if there is one
+            select_fn(src[:len(keep)], len(keep))
     out = []
     for g in range(groups):                                               # D7
         if lp is not None and finish[g]:                                  # C6
@@ -238,6 +217,7 @@ def beam_search_round(step_fn, select_fn, k, L, start, end, groups=1, diversity=
             out.append((best['beam'], best['score']))
             continue
         finish[g].sort(key=lambda c: -c['score'])
+        # (the reference errors if none ended)
         out.append((finish[g][0]['beam'], finish[g][0]['score']) if finish[g] else (beams[:, g * kp], scores[g * kp]))
     return out
 
