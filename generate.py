@@ -18,7 +18,7 @@ from visdial_amd.split_eval import check_beam_constraints, check_beam_groups
 def parse_args(argv=None):
     """the command line as the `opts` of the results file; refuses top-k / nucleus truncation without -sampleWords 1 and beam groups
     that do not divide -beamSize, with a bad -beamDiversity or with -sampleWords 1, and a bad -minLen / -noRepeatNgram / -lengthPenalty
-    or one of them with -sampleWords 1"""
+    or one of them with -sampleWords 1, and -rollout 1 with -sampleWords 1 or -beamGroups > 1"""
     ap = argparse.ArgumentParser(description='Test the VisDial model for generation')
     ap.add_argument('-inputImg', '--inputImg', default='data/data_img.h5')
     ap.add_argument('-inputQues', '--inputQues', default='data/visdial_data.h5')
@@ -50,6 +50,9 @@ def parse_args(argv=None):
                     help='beam search: no n-gram of that many words occurs twice in a hypothesis (0 = off)')
     ap.add_argument('-lengthPenalty', '--lengthPenalty', type=float, default=0.0,
                     help='beam search: finished hypotheses compete on score / length^that (length = words + <END>; 0 = off)')
+    ap.add_argument('-rollout', '--rollout', type=int, default=0, choices=[0, 1],
+                    help='1: beam search answers every round on a history of its OWN answers to the rounds before it, not the ground '
+                         'truth\'s (csrc/beam.hip R1-R6; with -beamBatch N it needs -host native; 0 = off)')
     ap.add_argument('-seed', '--seed', type=int, default=1234, help='seed of the sampling generator (numpy RandomState)')
     ap.add_argument('-gpuid', '--gpuid', type=int, default=0)
     ap.add_argument('-host', '--host', default='python', choices=['python', 'native'],
@@ -65,6 +68,11 @@ def parse_args(argv=None):
     check_beam_constraints(a['beamSize'], a['beamLen'], a['minLen'], a['noRepeatNgram'], a['lengthPenalty'])
     if (a['minLen'] != 0 or a['noRepeatNgram'] != 0 or a['lengthPenalty'] != 0.0) and a['sampleWords'] == 1:
         raise ValueError('-minLen / -noRepeatNgram / -lengthPenalty constrain beam search: sampling (-sampleWords 1) has none')
+    if a['rollout'] == 1 and a['sampleWords'] == 1:
+        raise ValueError('-rollout 1 feeds the beam search\'s answers back: with -sampleWords 1 one divergent draw would cascade over the rounds')
+    if a['rollout'] == 1 and a['beamGroups'] > 1:
+        raise ValueError('-rollout 1 with -beamGroups %d: the choice among a round\'s groups is made on the host; a rollout over diverse beam '
+                         'search is left for a follow-up' % a['beamGroups'])
     return a
 
 
@@ -84,7 +92,8 @@ def main():
         from visdial_amd.native import NativeModel
         # the device sampler takes its truncation, the device search its groups and constraints, at creation
         model = NativeModel(dict(p, topK=a['topK'], topP=a['topP'], beamGroups=a['beamGroups'], beamDiversity=a['beamDiversity'],
-                                 beamMinLen=a['minLen'], beamNoRepeat=a['noRepeatNgram'], beamLengthPenalty=a['lengthPenalty']))
+                                 beamMinLen=a['minLen'], beamNoRepeat=a['noRepeatNgram'], beamLengthPenalty=a['lengthPenalty'],
+                                 beamRollout=a['rollout']))
     else:
         model = Model(p)
     restore_weights(model, saved, a['paramOrder'] or None)
@@ -94,7 +103,8 @@ def main():
                                                     sampleBatch=a['sampleBatch'], seed=a['seed'],
                                                     topK=a['topK'], topP=a['topP'], beamGroups=a['beamGroups'],
                                                     beamDiversity=a['beamDiversity'], beamMinLen=a['minLen'],
-                                                    beamNoRepeat=a['noRepeatNgram'], beamLengthPenalty=a['lengthPenalty']))
+                                                    beamNoRepeat=a['noRepeatNgram'], beamLengthPenalty=a['lengthPenalty'],
+                                                    rollout=a['rollout']))
     os.makedirs(a['resultPath'], exist_ok=True)
     path = os.path.join(a['resultPath'], 'results.json')
     utils.writeJSON(path, {'opts': a, 'data': answers})

@@ -482,7 +482,21 @@ int vd_model_decode_select(vd_model* m, const int32_t* src, int n_keep);
  *   vocabSize < beam_size + beam_len - 1   (a row must keep beam_size unbanned words),
  *   m > beam_len - 2                       (end_token must be allowed at the last step),
  *   beam_len > VD_BEAM_LMAX = 64 with n on (the column and its ban list sit in LDS).
- * A host that keeps the bookkeeping itself over decode_begin / step / select follows split_eval.beam_search_round. */
+ * A host that keeps the bookkeeping itself over decode_begin / step / select follows split_eval.beam_search_round.
+ *
+ * Rollout: VD_BEAM_ROLLOUT = 1 (decoder gen; 0 / unset = off; read once by vd_model_create, which refuses any other value by name and
+ * refuses 1 together with VD_BEAM_GROUPS > 1; ignored for decoder disc).  Such a model answers round r of a dialog on a history that
+ * holds ITS OWN answers to rounds < r instead of the uploaded ones (the rule is R1-R6 at the top of csrc/beam.hip): history row 0 is
+ * the uploaded caption row; row r >= 1 is the non-zero tokens of question row r - 1, then the words of the answer returned for round
+ * r - 1 (entries 1, 2, ... of its token row up to the first end_token or 0) as far as they fit, right-aligned in the Th columns.  The
+ * call runs R = maxQuesCount passes over the batch's dialogs -- encoder forward, the search of round r of every dialog, one kernel that
+ * writes history row r + 1 -- with no host synchronisation between passes and one copy back in the layout above: host_tokens
+ * [N x beam_len], host_scores [N], row = dialog * R + round, every score the true log-likelihood under the constraints in force.  The
+ * uploaded contents of history rows >= 1 are ignored and overwritten: after the call the batch's device history holds the generated
+ * rows.  vd_model_upload_batch lays the history rows >= 1 of such a model out at full width and refuses, by name, Th < Tq (a history
+ * row has to hold a whole question); vd_model_sample on such a model is refused by name.  An encoder without a history (lf-ques,
+ * lf-ques-im) accepts the variable and runs the plain single-pass search with the launches it always made.  With the variable 0 or
+ * unset nothing changes.  The host loop it equals: split_eval.py rollout_dialog. */
 int vd_model_beam_search(vd_model* m, int beam_size, int beam_len, int start_token, int end_token, int32_t* host_tokens,
                          double* host_scores);
 /* temperature sampling of Model:generateAnswers (sampleWords = 1, model.lua:576-613) for EVERY round of the last vd_model_encode

@@ -10,7 +10,10 @@ many dialogs have identical records.
     also prints the share of rounds whose G answers are not all the same.  --vocabScale s multiplies the vocabulary projection of the
     random model (60 = the peaked rows of test_beam_search_gpu.full_size_fixture; near-uniform rows otherwise)
     --mode beam --minLen m --noRepeatNgram n --lengthPenalty a: the beam constraints (csrc/beam.hip C1-C6) on both paths (the model is
-    created with the knobs)"""
+    created with the knobs)
+    --mode beam --rollout 1: every round answered on a history of the model's own earlier answers (csrc/beam.hip R1-R6): the per-dialog
+    loop (one encode per round) against the device rollout (the model is created with the knob).  The history is then generate.py's:
+    one row of question + answer per round, maxQuesLen + maxAnsLen = 40 wide, the caption in row 0"""
 import argparse
 import os
 import sys
@@ -35,6 +38,7 @@ ap.add_argument('--beamDiversity', type=float, default=0.5, help='--mode beam wi
 ap.add_argument('--minLen', type=int, default=0, help='--mode beam: no answer of fewer than that many words (0 = off)')
 ap.add_argument('--noRepeatNgram', type=int, default=0, help='--mode beam: no n-gram of that many words twice in a hypothesis (0 = off)')
 ap.add_argument('--lengthPenalty', type=float, default=0.0, help='--mode beam: finished hypotheses compete on score / length^that (0 = off)')
+ap.add_argument('--rollout', type=int, default=0, choices=(0, 1), help='--mode beam: answer on the generated history (0 = off)')
 ap.add_argument('--vocabScale', type=float, default=1.0, help='multiply vocab.W of the random model (peaked rows)')
 opt = ap.parse_args()
 MODE_KNOBS = opt.topK != 0 or opt.topP != 1.0
@@ -47,6 +51,8 @@ LIMITS = {} if (opt.minLen, opt.noRepeatNgram, opt.lengthPenalty) == (0, 0, 0.0)
     beamMinLen=opt.minLen, beamNoRepeat=opt.noRepeatNgram, beamLengthPenalty=opt.lengthPenalty)
 if LIMITS and opt.mode != 'beam':
     ap.error('--minLen / --noRepeatNgram / --lengthPenalty belong to beam search: use --mode beam')
+if opt.rollout and (opt.mode != 'beam' or GROUPS != 1):
+    ap.error('--rollout 1 belongs to beam search without groups: use --mode beam --beamGroups 1')
 MODE, D, ONLY_BATCHED = opt.mode, opt.dialogs, opt.only == 'batched'
 V, R = 11322, 10
 
@@ -57,6 +63,16 @@ class Dialogs(object):
     def __init__(self, p, n):
         q = dict(p, batchSize=n)
         self.b = SyntheticDataloader(q, seed=5).getTrainBatch(q)
+        if opt.rollout:          # generate.py's history (concatHistory = False): caption, then question + ground-truth answer per round
+            from visdial_amd.split_eval import rollout_history_row
+            Th = int(p['maxQuesLen']) + int(p['maxAnsLen'])
+            hist = np.zeros((n, R, Th), np.int32)
+            hist[:, 0] = self.b['hist'][:, 0, -Th:]
+            for i in range(n):
+                for r in range(1, R):
+                    hist[i, r] = rollout_history_row(self.b['ques_fwd'][i, r - 1], self.b['answer_in'][i, r - 1], Th, V)
+            self.b['hist'] = hist
+        self.data = {'val': {'hist': self.b['hist']}}
         self.numThreads = {'val': n}
         self.word2ind = {'<START>': V - 1, '<END>': V}
         self.ind2word = {i: '<START>' if i == V - 1 else '<END>' if i == V else 'w%d' % i for i in range(1, V + 1)}
@@ -73,6 +89,8 @@ knobs = dict(topK=opt.topK, topP=opt.topP) if MODE_KNOBS else {}
 if GROUPS != 1:
     knobs.update(beamGroups=GROUPS, beamDiversity=opt.beamDiversity)
 knobs.update(LIMITS)
+if opt.rollout:
+    knobs.update(beamRollout=1)
 nat = NativeModel(dict(p, **knobs), init_seed=1)
 nat.training(False)
 if opt.vocabScale != 1.0:
@@ -88,6 +106,9 @@ if MODE == 'beam':
     if LIMITS:
         cfg.update(LIMITS)
         what += ' (minLen %d, noRepeatNgram %d, lengthPenalty %g)' % (opt.minLen, opt.noRepeatNgram, opt.lengthPenalty)
+    if opt.rollout:
+        cfg.update(rollout=1)
+        what += ', rollout'
 else:
     key, cfg = 'sampleBatch', dict(sampleWords=1, beamLen=20, temperature=1.0, maxThreads=D, seed=1234, topK=opt.topK, topP=opt.topP)
     what = 'sampling' + (' (topK %d, topP %g)' % (opt.topK, opt.topP) if MODE_KNOBS else '')

@@ -69,6 +69,25 @@
 //      falls back as before.
 // On the device C2-C4 are the constrained form of the top-k kernel (it reads the row's column from the PRE-advance history), C6 the
 // advance kernel's `lp` argument (nullptr = off); with every knob off the top-k is the plain kernel with the arguments it always had.
+//
+// Rollout (VD_BEAM_ROLLOUT = 1 at vd_model_create; generate.py -rollout 1): round r is answered on a history that holds the model's OWN
+// answers to the rounds before it, not the ground truth's.  split_eval.py restates R2 / R3 (rollout_history_row) and the host loop.  Th is
+// the width of the uploaded history, lq the number of non-zero tokens of a question row.
+//  R1. round 0's history row is the uploaded one (the caption).
+//  R2. for r >= 1, history row r of a dialog is the non-zero tokens of question row r - 1, in order, then the first min(la, Th - lq) words
+//      of the answer chosen for round r - 1 (la of them), right-aligned in Th columns with zeros in front.  lq = 0 and no words: an
+//      all-zero row (what the test split's missing rounds produce).  The question is kept whole; the answer is what is cut.
+//  R3. the words of an answer are entries 1, 2, ... of the round's returned token row [beamLen], up to but excluding the first <END> or 0.
+//      Entry 0 is <START> and is not a word.  An answer that never finished (slot 0's column, no <END>) gives all its beamLen - 1 words.
+//  R4. the answer chosen for a round is exactly what the search returns for it: rule 3 (C6 under a length penalty), with C1-C4 in force if
+//      they are on; its score stays the true log-likelihood.  Groups (D1-D7) are refused: the choice among them is the host's.
+//  R5. round r is answered from an encoder pass in which rows 0 .. r of its dialog are as above.  Whatever rows > r hold at that time does
+//      not reach round r: every encoder is causal over the rounds (lf reads its own row, hre runs a forward dialog LSTM, mn attends over
+//      the earlier rounds only).
+//  R6. the uploaded contents of history rows >= 1 are ignored and overwritten; after the call the batch's device history holds the
+//      generated rows.
+// On the device a chunk of B dialogs runs R passes (Gen_beam_search, rt_decoders.h): encoder forward, the search of round r of every dialog
+// (B groups, the kernels above unchanged), beam_rollout_append_kernel for row r + 1.  Nothing waits for the host between passes.
 #include "common.h"
 
 #define VD_BEAM_KMAX 32
@@ -373,7 +392,67 @@ __global__ void beam_finish_kernel(int groups, int k, int L, const int32_t* __re
   }
 }
 
+// R2 / R3 for one pass of a rollout: one wave per dialog writes history row r + 1 from question row r and the answer just chosen for
+// round r.  The wave counts lq with ballots while it compacts the question's non-zero tokens into LDS (a lane's place = the set bits
+// below it), finds the answer's word count as the first lane whose entry is <END>, 0 or past the row, and then makes ONE pass over the Th
+// columns: column c holds 0, a question token or an answer word by its distance from the right edge alone, so every column is written
+// exactly once, with plain vector stores, into the step-major tokens [Th x N] and (inv != nullptr) the length-sorted copy the wavefront
+// masks with.  Both are step-major, so a dialog's columns lie N apart: a wave's stores are strided whatever the lane order, and at
+// B x Th x 4 bytes per pass (1.1 KB at B = 20, Th = 14) the launch is what costs.  Tq <= VD_ROLLOUT_TMAX (the LDS list), lq <= Tq <= Th.
+#define VD_ROLLOUT_TMAX 1024
+__global__ void __launch_bounds__(64)
+beam_rollout_append_kernel(const int32_t* __restrict__ answers, int L, int end_tok, const int32_t* __restrict__ ques, int Tq, long N, int R,
+                           int r, int Th, int32_t* __restrict__ hist_tok, int32_t* __restrict__ hist_sorted,
+                           const int32_t* __restrict__ inv) {
+  __shared__ int32_t qc[VD_ROLLOUT_TMAX];
+  const int lane = threadIdx.x;
+  const long nq = (long)blockIdx.x * R + r, nh = nq + 1;           // the round just answered; the history row it becomes
+  const int32_t* a = answers + (long)blockIdx.x * L;
+  int lq = 0;
+  for (int base = 0; base < Tq; base += 64) {
+    const int t = base + lane;
+    const int32_t v = t < Tq ? ques[(long)t * N + nq] : 0;
+    const unsigned long long mask = __ballot(v != 0);
+    if (v != 0) qc[lq + __popcll(mask & ((1ull << lane) - 1ull))] = v;
+    lq += __popcll(mask);
+  }
+  int la = 0;                                                      // R3: entries 1 .. la are the words
+  for (int base = 1;; base += 64) {
+    const int c = base + lane;
+    const bool stop = c >= L || a[c] == end_tok || a[c] == 0;
+    const unsigned long long mask = __ballot(stop);
+    if (mask) {
+      la = base + __ffsll((long long)mask) - 2;
+      break;
+    }
+  }
+  __syncthreads();
+  const int pad = Th - lq - min(la, Th - lq);                      // R2: zeros in front
+  for (int base = 0; base < Th; base += 64) {
+    const int c = base + lane, j = c - pad;
+    if (c >= Th) break;
+    const int32_t v = j < 0 ? 0 : j < lq ? qc[j] : a[1 + j - lq];
+    hist_tok[(long)c * N + nh] = v;
+    if (hist_sorted) hist_sorted[(long)c * N + inv[nh]] = v;
+  }
+}
+
 }  // namespace
+
+// R2 / R3 (rt_core.h): history row r + 1 of `dialogs` dialogs from question row r and `answers` [dialogs x beam_len]
+int vd_beam_rollout_append_p(const int32_t* answers, int beam_len, int end_token, const int32_t* ques, int Tq, int dialogs, int R, int r,
+                             int32_t* hist_tok, int32_t* hist_sorted, const int32_t* inv, int Th, hipStream_t stream) {
+  VD_CHECK_ARG(answers && ques && hist_tok && beam_len >= 1 && dialogs >= 0 && (hist_sorted == nullptr) == (inv == nullptr),
+               "vd_beam_rollout_append: bad args");
+  VD_CHECK_ARG(R >= 2 && r >= 0 && r + 1 < R, "vd_beam_rollout_append: round %d has no next round among %d", r, R);
+  VD_CHECK_ARG(Tq >= 1 && Tq <= VD_ROLLOUT_TMAX && Th >= Tq, "vd_beam_rollout_append: question width %d must be in [1, %d] and <= history width %d",
+               Tq, VD_ROLLOUT_TMAX, Th);
+  if (dialogs == 0) return VD_OK;
+  hipLaunchKernelGGL(beam_rollout_append_kernel, dim3((unsigned)dialogs), dim3(64), 0, stream, answers, beam_len, end_token, ques, Tq,
+                     (long)dialogs * R, R, r, Th, hist_tok, hist_sorted, inv);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
 
 // vd_beam_advance (rt_core.h): `rounds` rounds of G groups of k / G slots
 int vd_beam_advance_p(const int32_t* top_idx, const float* top_val, int rounds, int k, int G, float lambda, int step, int beam_len,

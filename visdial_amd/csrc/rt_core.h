@@ -75,6 +75,13 @@ int vd_beam_advance_p(const int32_t* top_idx, const float* top_val, int rounds, 
 int vd_beam_topk_ban_p(const float* logits, int64_t ld, int64_t rows, int V, const int32_t* tok, int k, const int32_t* hist, int beam_len,
                        int step, int min_len, int no_repeat, int end_token, int32_t* top_idx, float* top_val, hipStream_t stream);
 
+// beam.hip: one pass of a rollout (VD_BEAM_ROLLOUT; R2 / R3 there): history row r + 1 of every dialog (row dialog * R + r + 1 of the
+// step-major tokens hist_tok [Th x dialogs * R]) = the non-zero tokens of question row r (ques, step-major [Tq x dialogs * R]), then the
+// words of answers [dialogs x beam_len] that fit, right-aligned.  hist_sorted / inv: the length-sorted copy [Th x N] and the place of
+// every row in it, both or neither.  Needs r + 1 < R and Tq <= Th.
+int vd_beam_rollout_append_p(const int32_t* answers, int beam_len, int end_token, const int32_t* ques, int Tq, int dialogs, int R, int r,
+                             int32_t* hist_tok, int32_t* hist_sorted, const int32_t* inv, int Th, hipStream_t stream);
+
 #define VD_TRY(expr)                  \
   do {                                \
     const int rc__ = (expr);          \
@@ -280,6 +287,9 @@ struct vd_model {
   int beam_min_len = 0, beam_no_repeat = 0;
   double beam_length_penalty = 0.0;
   std::vector<double> beam_lp;
+  // VD_BEAM_ROLLOUT at vd_model_create (decoder gen): vd_model_beam_search answers round r on a history of the model's own answers to the
+  // rounds before it (beam.hip R1-R6), and an upload lays out history rows >= 1 at full width (runtime.hip upload_tokens)
+  bool beam_rollout = false;
   bool lhood_tree = false;   // VD_LHOOD_TREE at vd_model_create: vd_model_retrieve_lhood scores over a prefix tree of the candidates
   bool prof_hist = false;   // ev_prof[0..3] bracket the history branch of a Sequential encoder (gen pairs: vd_model_family_ms)
   ~vd_model();

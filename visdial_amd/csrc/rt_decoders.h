@@ -642,12 +642,9 @@ inline int gen_carry(Gen* g, vd_model* m, int n, bool next, const int32_t* src =
   return VD_OK;
 }
 // hiddenBeams (model.lua:478-503): hypothesis i starts from the encoder state of QA round rounds[i]
-inline int Gen_begin(Gen* g, vd_model* m, const int32_t* rounds, int n) {
-  VD_CHECK_ARG(m->gen_enc_out && rounds && n > 0, "vd_model_decode_begin: call vd_model_encode first");
-  for (int i = 0; i < n; ++i) VD_CHECK_ARG(rounds[i] >= 0 && rounds[i] < m->N, "vd_model_decode_begin: round %d out of range", rounds[i]);
+// (gen_begin_rows: the same from round indices that are on the device already -- a rollout's passes, which must not wait for the host)
+inline int gen_begin_rows(Gen* g, vd_model* m, const int32_t* idx, int n) {
   hipStream_t s = m->s_main;
-  int32_t* idx;
-  VD_TRY(gen_rows(m, "gen.idx", rounds, n, &idx));
   std::vector<SeqLSTM>* layers = m->enc->rnnLayers();
   const int L = (int)g->rnn.size(), seqLen = m->gen_seq_len;
   const long H = g->H;
@@ -667,6 +664,13 @@ inline int Gen_begin(Gen* g, vd_model* m, const int32_t* rounds, int n) {
   }
   g->gen_n = n;
   return VD_OK;
+}
+inline int Gen_begin(Gen* g, vd_model* m, const int32_t* rounds, int n) {
+  VD_CHECK_ARG(m->gen_enc_out && rounds && n > 0, "vd_model_decode_begin: call vd_model_encode first");
+  for (int i = 0; i < n; ++i) VD_CHECK_ARG(rounds[i] >= 0 && rounds[i] < m->N, "vd_model_decode_begin: round %d out of range", rounds[i]);
+  int32_t* idx;
+  VD_TRY(gen_rows(m, "gen.idx", rounds, n, &idx));
+  return gen_begin_rows(g, m, idx, n);
 }
 // The device part of one decoder step (model.lua:518-522): the n hypotheses' tokens (device) through embedding, LSTM stack
 // and vocabulary projection from the current state gen.h<l> / gen.c<l> -> logits [n x Vp]; the stepped state is left in
@@ -764,13 +768,21 @@ inline int gen_read_back(vd_model* m, const void* out, size_t bytes, std::vector
 // groups of k / G slots, so init and finish take (N * G, k / G) and the answers come back [N x G x L] / [N x G].
 // VD_BEAM_MIN_LEN / VD_BEAM_NO_REPEAT (beam.hip C1-C4) swap the top-k for its constrained form, VD_BEAM_LENGTH_PENALTY (C6) hands the
 // advance the table s^alpha.
+// VD_BEAM_ROLLOUT (beam.hip R1-R6) over an encoder with a history: R = maxQuesCount passes over the chunk's B dialogs instead of one search
+// of all N = B * R rounds.  Pass r: the encoder forward on the slot (pass 0's is vd_model_encode's -- by R5 round 0 sees its caption row
+// only), the search of round r of every dialog (hypothesis row i = slot i % k of round (i / k) * R + r: B groups through the same
+// kernels), vd_beam_finish into the B rows of pass r of the device output [R x B x L] / [R x B], and the append kernel for history row
+// r + 1.  Every pass is enqueued on s_main behind the one before it and nothing waits for the host in between; the one copy back is
+// re-ordered on the host into the [N x L] / [N] layout (row = dialog * R + round) of the plain call.
 inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end, int32_t* host_tokens, double* host_scores) {
   VD_CHECK_ARG(m->gen_enc_out && m->N > 0, "vd_model_beam_search: call vd_model_encode first");
   VD_CHECK_ARG(host_tokens && host_scores && L >= 1, "vd_model_beam_search: bad arguments");
   VD_CHECK_ARG(k >= 1 && k <= 32 && k <= g->V, "vd_model_beam_search: beam size %d must be in [1, min(32, vocabSize)]", k);
   const int groups = m->beam_groups;
   VD_CHECK_ARG(k % groups == 0, "vd_model_beam_search: VD_BEAM_GROUPS = %d does not divide beam size %d", groups, k);
-  const int N = m->N, n = N * k, G = N * groups, kg = k / groups;           // G answers, each the best of kg slots
+  const bool rollout = m->beam_rollout && m->use_hist;                      // (no history: nothing depends on an answer -- the plain search)
+  const int R = m->p.maxQuesCount, passes = rollout ? R : 1;
+  const int N = m->N / passes, n = N * k, G = N * groups, kg = k / groups;  // per pass: G answers, each the best of kg slots
   const int min_len = m->beam_min_len, no_repeat = m->beam_no_repeat;
   const bool ban = min_len > 0 || no_repeat > 0, penalty = m->beam_length_penalty > 0.0;
   if (ban) {
@@ -782,13 +794,23 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
     VD_CHECK_ARG(min_len <= L - 2, "vd_model_beam_search: VD_BEAM_MIN_LEN = %d exceeds beam length %d - 2: <END> must be allowed at the last step",
                  min_len, L);
   }
-  VD_TRY(gen_batch_begin(g, m, k));
+  BatchSlot& b = m->slot[m->cur];
+  int32_t* pass_rounds = nullptr;
+  if (rollout) {   // the round indices of every pass, cached on the device by shape
+    VD_CHECK_ARG(b.h.present && b.q.present && b.h.N == m->N && b.h.T >= b.q.T, "vd_model_beam_search: VD_BEAM_ROLLOUT = 1 needs the batch's history");
+    std::vector<int32_t> rounds((size_t)R * n);
+    for (int r = 0; r < R; ++r)
+      for (int i = 0; i < n; ++i) rounds[(size_t)r * n + i] = (i / k) * R + r;
+    VD_TRY(index_array(m, "idx.rollout." + std::to_string(N) + "." + std::to_string(k) + "." + std::to_string(R), rounds, &pass_rounds));
+  } else {
+    VD_TRY(gen_batch_begin(g, m, k));
+  }
   hipStream_t s = m->s_main;
   int32_t *tok, *top_idx, *src, *hist[2], *best_len, *best_hist;
   float* top_val;
   double *scores, *best_score;
   uint8_t* out;
-  const size_t tok_bytes = ((size_t)G * L * 4 + 7) / 8 * 8;
+  const size_t Gall = (size_t)G * passes, tok_bytes = (Gall * L * 4 + 7) / 8 * 8;
   VD_TRY(ws_get(m, "beam.tok", (size_t)n, &tok));
   VD_TRY(ws_get(m, "beam.top_idx", (size_t)n * k, &top_idx));
   VD_TRY(ws_get(m, "beam.top_val", (size_t)n * k, &top_val));
@@ -799,7 +821,7 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
   VD_TRY(ws_get(m, "beam.best_score", (size_t)G, &best_score));
   VD_TRY(ws_get(m, "beam.best_len", (size_t)G, &best_len));
   VD_TRY(ws_get(m, "beam.best_hist", (size_t)G * L, &best_hist));
-  VD_TRY(ws_get(m, "beam.out", tok_bytes + (size_t)G * 8, &out));
+  VD_TRY(ws_get(m, "beam.out", tok_bytes + Gall * 8, &out));
   double* lp = nullptr;
   if (penalty) {                                                            // C6: s^alpha on the host in fp64, uploaded as a table
     m->beam_lp.resize((size_t)L);
@@ -807,23 +829,47 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
     VD_TRY(ws_get(m, "beam.lp", (size_t)L, &lp));
     VD_HIP(hipMemcpyAsync(lp, m->beam_lp.data(), (size_t)L * 8, hipMemcpyHostToDevice, s));
   }
-  VD_TRY(vd_beam_init(G, kg, L, start, hist[0], tok, scores, best_score, best_len, s));
-  VD_TRY(gen_batch_steps(g, m, L - 1, tok, src, k, [&](int step, float* logits) -> int {
-    if (ban)
-      VD_TRY(vd_beam_topk_ban_p(logits, g->Vp, n, (int)g->V, tok, k, hist[0], L, step, min_len, no_repeat, end, top_idx, top_val, s));
-    else
-      VD_TRY(vd_beam_topk(logits, g->Vp, n, (int)g->V, tok, k, top_idx, top_val, s));
-    VD_TRY(vd_beam_advance_p(top_idx, top_val, N, k, groups, (float)m->beam_diversity, step, L, end, scores, hist[0], hist[1], src, tok,
-                             best_score, best_len, best_hist, lp, s));
-    std::swap(hist[0], hist[1]);
-    return VD_OK;
-  }));
-  VD_TRY(vd_beam_finish(G, kg, L, hist[0], scores, best_score, best_len, best_hist, reinterpret_cast<int32_t*>(out),
-                        reinterpret_cast<double*>(out + tok_bytes), s));
+  for (int r = 0; r < passes; ++r) {
+    int32_t* out_tok = reinterpret_cast<int32_t*>(out) + (size_t)r * G * L;
+    if (rollout) {
+      if (r > 0) {                                                          // R5: rows 0 .. r of every dialog are final now
+        float* enc_out = nullptr;
+        m->gen_enc_out = nullptr;
+        VD_TRY(m->enc->forward(m, s, b, &enc_out));
+        m->gen_enc_out = enc_out;
+        m->gen_seq_len = m->enc->seqLen(b);
+      }
+      VD_TRY(gen_begin_rows(g, m, pass_rounds + (size_t)r * n, n));
+    }
+    VD_TRY(vd_beam_init(G, kg, L, start, hist[0], tok, scores, best_score, best_len, s));
+    VD_TRY(gen_batch_steps(g, m, L - 1, tok, src, k, [&](int step, float* logits) -> int {
+      if (ban)
+        VD_TRY(vd_beam_topk_ban_p(logits, g->Vp, n, (int)g->V, tok, k, hist[0], L, step, min_len, no_repeat, end, top_idx, top_val, s));
+      else
+        VD_TRY(vd_beam_topk(logits, g->Vp, n, (int)g->V, tok, k, top_idx, top_val, s));
+      VD_TRY(vd_beam_advance_p(top_idx, top_val, N, k, groups, (float)m->beam_diversity, step, L, end, scores, hist[0], hist[1], src, tok,
+                               best_score, best_len, best_hist, lp, s));
+      std::swap(hist[0], hist[1]);
+      return VD_OK;
+    }));
+    VD_TRY(vd_beam_finish(G, kg, L, hist[0], scores, best_score, best_len, best_hist, out_tok,
+                          reinterpret_cast<double*>(out + tok_bytes) + (size_t)r * G, s));
+    if (rollout && r + 1 < R)                                               // R2: the answer becomes history row r + 1
+      VD_TRY(vd_beam_rollout_append_p(out_tok, L, end, b.q.tok, b.q.T, N, R, r, b.h.tok, b.h.sorted ? b.h.tok_sorted : nullptr,
+                                      b.h.sorted ? b.h.inv : nullptr, b.h.T, s));
+  }
   std::vector<uint8_t> staged;
-  VD_TRY(gen_read_back(m, out, tok_bytes + (size_t)G * 8, &staged));
-  memcpy(host_tokens, staged.data(), (size_t)G * L * 4);
-  memcpy(host_scores, staged.data() + tok_bytes, (size_t)G * 8);
+  VD_TRY(gen_read_back(m, out, tok_bytes + Gall * 8, &staged));
+  if (!rollout) {
+    memcpy(host_tokens, staged.data(), Gall * L * 4);
+    memcpy(host_scores, staged.data() + tok_bytes, Gall * 8);
+    return VD_OK;
+  }
+  for (int r = 0; r < R; ++r)                                               // [R x B] -> row = dialog * R + round
+    for (int i = 0; i < N; ++i) {
+      memcpy(host_tokens + ((size_t)i * R + r) * L, staged.data() + ((size_t)r * N + i) * L * 4, (size_t)L * 4);
+      memcpy(host_scores + (size_t)i * R + r, staged.data() + tok_bytes + ((size_t)r * N + i) * 8, 8);
+    }
   return VD_OK;
 }
 
@@ -834,6 +880,8 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
 inline int Gen_sample(Gen* g, vd_model* m, int L, int start, int end, double T, const double* host_u, int32_t* host_tokens,
                       double* host_loglik) {
   VD_CHECK_ARG(m->gen_enc_out && m->N > 0, "vd_model_sample: call vd_model_encode first");
+  VD_CHECK_ARG(!m->beam_rollout, "vd_model_sample: this model was created with VD_BEAM_ROLLOUT = 1: a rollout feeds the beam search's answers "
+               "back, and one divergent draw would cascade over the rounds; create the sampling model without the variable");
   VD_CHECK_ARG(host_u && host_tokens && host_loglik, "vd_model_sample: bad arguments");
   VD_CHECK_ARG(L >= 1, "vd_model_sample: beam_len = %d must be >= 1", L);
   VD_CHECK_ARG(std::isfinite(T) && T > 0, "vd_model_sample: temperature %g must be finite and > 0", T);

@@ -28,7 +28,14 @@ namespace {
 
 // [N x T] dataloader rows -> time-major [T x N] on the device; with `sorted` also the length-sort metadata of
 // nn.py:SeqSort (stable sort by decreasing length, per-step active-row counts, gather indices)
-int upload_tokens(BatchSlot& sl, SeqTok& ss, const std::string& tag, const int32_t* rows_major, int N, int T, bool sorted, hipStream_t s) {
+//
+// rollout_R > 0 (the history of a model created with VD_BEAM_ROLLOUT, R rounds per dialog): rows n with n % R != 0 will be REWRITTEN on
+// the device between the passes of a rollout (beam.hip R2), so their length is not known here.  They are laid out at full width,
+// length T: by the paragraph below a row is skipped only BEFORE its claimed first token and masked per token inside its span, so a
+// claim that covers leading zeros is exact and only costs work.  The sort then puts them in front of the caption rows (n % R == 0),
+// which keep their true length; perm / inv / nact are fixed for every pass, and the pass writes tok and tok_sorted alike.
+int upload_tokens(BatchSlot& sl, SeqTok& ss, const std::string& tag, const int32_t* rows_major, int N, int T, bool sorted, hipStream_t s,
+                  int rollout_R = 0) {
   ss.T = T;
   ss.N = N;
   ss.present = true;
@@ -50,7 +57,7 @@ int upload_tokens(BatchSlot& sl, SeqTok& ss, const std::string& tag, const int32
       tok[(size_t)t * N + n] = v;
       if (v != 0 && first == T) first = t;
     }
-    if (sorted) len[n] = T - first;
+    if (sorted) len[n] = rollout_R > 0 && n % rollout_R != 0 ? T : T - first;
   }
   if (sorted) {
     int32_t* tok_sorted = stage + TN;
@@ -391,8 +398,21 @@ int vd_model_create(const vd_model_params* p, const char* encoder, const char* d
       beam_length_penalty = v;
     }
   }
+  // rollout of vd_model_beam_search (include/visdial_hip.h there; beam.hip R1-R6): VD_BEAM_ROLLOUT = 1 / 0 (0 / unset = off); anything else
+  // is refused, and so is 1 with VD_BEAM_GROUPS > 1 (the choice among a round's groups is the host's).  Ignored for decoder disc.
+  bool beam_rollout = false;
+  if (std::string(decoder) == "gen") {
+    if (const char* e = getenv("VD_BEAM_ROLLOUT")) {
+      VD_CHECK_ARG((e[0] == '0' || e[0] == '1') && !e[1], "vd_model_create: VD_BEAM_ROLLOUT = '%s' must be 1 or 0 (0 = off)", e);
+      beam_rollout = e[0] == '1';
+    }
+    VD_CHECK_ARG(!beam_rollout || beam_groups == 1,
+                 "vd_model_create: VD_BEAM_ROLLOUT = 1 with VD_BEAM_GROUPS = %d: a rollout feeds ONE answer per round back, and the choice "
+                 "among a round's groups is the host's", beam_groups);
+  }
   vd_model* m = new vd_model();
   m->p = *p;
+  m->beam_rollout = beam_rollout;
   m->sample_topk = sample_topk;
   m->sample_topp = sample_topp;
   m->beam_groups = beam_groups;
@@ -656,7 +676,10 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
   VD_TRY(upload_tokens(sl, sl.q, "q", hb->ques_fwd, N, hb->Tq, m->is_graph, s));
   // the history branch of the Sequential encoders runs as a length-sorted two-layer wavefront too (rt_encoders.h: HistWave)
   const bool hist_wave = !m->is_graph && m->p.numLayers == 2;
-  if (m->use_hist) VD_TRY(upload_tokens(sl, sl.h, "h", hb->hist, N, hb->Th, m->is_graph || hist_wave, s));
+  // VD_BEAM_ROLLOUT: history rows >= 1 at full width (upload_tokens), and a history row has to hold a whole question (beam.hip R2)
+  VD_CHECK_ARG(!(m->beam_rollout && m->use_hist) || hb->Th >= hb->Tq,
+               "vd_model_upload_batch: VD_BEAM_ROLLOUT = 1 needs a history width Th = %d >= the question width Tq = %d", hb->Th, hb->Tq);
+  if (m->use_hist) VD_TRY(upload_tokens(sl, sl.h, "h", hb->hist, N, hb->Th, m->is_graph || hist_wave, s, m->beam_rollout ? R : 0));
   if (m->use_im) {
     // [B x S*S x C] for the attention encoders (model.lua:262-265 keeps one map per image), [B x F] otherwise
     const size_t img_n = (size_t)hb->B * (m->is_att ? (size_t)m->p.imgSpatialSize * m->p.imgSpatialSize : 1) * m->p.imgFeatureSize;

@@ -79,6 +79,8 @@ class NativeModel(SplitEval):
         # refused the same way); generateAnswers(beamBatch > 0) checks its knobs against these.
         # params beamMinLen / beamNoRepeat / beamLengthPenalty: the constraints of vd_model_beam_search (VD_BEAM_MIN_LEN / VD_BEAM_NO_REPEAT /
         # VD_BEAM_LENGTH_PENALTY), the same way again.
+        # params beamRollout: vd_model_beam_search rolls the model's own answers into the history (VD_BEAM_ROLLOUT), the same way again;
+        # generateAnswers(beamBatch > 0) checks its `rollout` against it.
         import os
         switches = {'VD_OPTION_CACHE': str(int(p.get('optionCache', 0) or 0)),
                     'VD_LHOOD_TREE': '1' if int(p.get('fusedLhood', 0) or 0) == 2 else '0',
@@ -88,7 +90,8 @@ class NativeModel(SplitEval):
                     'VD_BEAM_DIVERSITY': None if p.get('beamDiversity') is None else str(p['beamDiversity']),
                     'VD_BEAM_MIN_LEN': None if p.get('beamMinLen') is None else str(p['beamMinLen']),
                     'VD_BEAM_NO_REPEAT': None if p.get('beamNoRepeat') is None else str(p['beamNoRepeat']),
-                    'VD_BEAM_LENGTH_PENALTY': None if p.get('beamLengthPenalty') is None else str(p['beamLengthPenalty'])}
+                    'VD_BEAM_LENGTH_PENALTY': None if p.get('beamLengthPenalty') is None else str(p['beamLengthPenalty']),
+                    'VD_BEAM_ROLLOUT': None if p.get('beamRollout') is None else str(p['beamRollout'])}
         prev = {k: os.environ.get(k) for k in switches}
         try:
             for k, v in switches.items():
@@ -108,6 +111,7 @@ class NativeModel(SplitEval):
         self._beam_knobs = (int(p.get('beamGroups') or 1) if gen else 1, float(0.5 if p.get('beamDiversity') is None else p['beamDiversity']))
         self._beam_limits = (int(p.get('beamMinLen') or 0), int(p.get('beamNoRepeat') or 0), float(p.get('beamLengthPenalty') or 0.0)) if gen \
             else (0, 0, 0.0)
+        self._rollout_knob = int(p.get('beamRollout') or 0) if gen else 0
         self.h = h
         lib = _lib.load()
         self.tensors = []
@@ -382,6 +386,11 @@ class NativeModel(SplitEval):
                              "with beamMinLen = %d / beamNoRepeat = %d / beamLengthPenalty = %g: the device search takes its constraints "
                              "when the model is created (params beamMinLen / beamNoRepeat / beamLengthPenalty of NativeModel)"
                              % ((int(minLen), int(noRepeat), float(lengthPenalty)) + self._beam_limits))
+
+    def _beam_rollout(self, rollout):
+        if int(rollout) != self._rollout_knob:
+            raise ValueError("beamBatch > 0 with rollout = %d, but this model was created with beamRollout = %d: the device search takes "
+                             "its rollout when the model is created (params beamRollout of NativeModel)" % (int(rollout), self._rollout_knob))
 
     def _sample_truncation(self, topK, topP):
         if (int(topK), float(topP)) != self._sample_knobs:

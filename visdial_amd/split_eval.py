@@ -11,7 +11,9 @@ kernels), and for batched sampling (params sampleBatch > 0) `_gen_sample(beamLen
 `_sample_truncation(topK, topP)` raising unless that sampler truncates with exactly these knobs.  Diverse beam search (params
 beamGroups = G > 1): `_beam_grouping(groups, diversity)` raises unless that `_gen_beam` searches in exactly these groups, and it then
 returns every group's answer, (tokens [N x G x beamLen], scores [N x G]).  Beam constraints (params beamMinLen / beamNoRepeat /
-beamLengthPenalty): `_beam_constraints(minLen, noRepeat, lengthPenalty)` raises unless that `_gen_beam` searches under exactly these."""
+beamLengthPenalty): `_beam_constraints(minLen, noRepeat, lengthPenalty)` raises unless that `_gen_beam` searches under exactly these.
+Rollout (params rollout = 1): `_beam_rollout(rollout)` raises unless that `_gen_beam` feeds every round's answer into the next round's
+history on the device, R1-R6 below."""
 import math
 
 import numpy as np
@@ -136,6 +138,33 @@ def pick_answer(answers, endToken, lengthPenalty=0.0):
         elif score > best[1]:
             best = (tokens, score)
     return best if best is not None else answers[0]
+
+
+# Rollout (csrc/beam.hip R1-R6; generate.py -rollout 1): round r is answered on a history that holds the model's OWN answers to the rounds
+# before it.  Th = the width of the batch's history, lq = the number of non-zero tokens of a question row.
+#   R1. round 0's history row is the batch's (the caption).
+#   R2. for r >= 1, history row r = the non-zero tokens of question row r - 1, in order, then the first min(la, Th - lq) words of the answer
+#       chosen for round r - 1, right-aligned in Th columns with zeros in front (lq = 0 and no words: all zeros).
+#   R3. an answer's words are entries 1, 2, ... of its token row [beamLen] up to but excluding the first <END> or 0; entry 0 is <START>; an
+#       answer that never finished gives all its beamLen - 1 words.
+#   R4. the answer chosen for a round is what the search returns for it, under whatever constraints are in force (groups are refused).
+#   R5. round r is answered from an encoder pass that holds rows 0 .. r as above; rows > r do not reach it (every encoder is causal).
+#   R6. the batch's history rows >= 1 are ignored and overwritten: after the run the batch holds the generated rows.
+def rollout_history_row(ques_row, answer_row, Th, endToken):
+    """R2 / R3: the history row [Th] that follows a round with question row `ques_row` and answer token row `answer_row`"""
+    q = [int(t) for t in np.asarray(ques_row).reshape(-1) if int(t) != 0]
+    if len(q) > Th:
+        raise ValueError('rollout: a question of %d tokens does not fit a history row of Th = %d' % (len(q), Th))
+    words = []
+    for t in np.asarray(answer_row).reshape(-1)[1:]:
+        if int(t) == int(endToken) or int(t) == 0:
+            break
+        words.append(int(t))
+    row = q + words[:Th - len(q)]
+    out = np.zeros(Th, np.int64)
+    if row:
+        out[Th - len(row):] = row
+    return out
 
 
 def beam_search_round(step_fn, select_fn, k, L, start, end, groups=1, diversity=0.5, minLen=0, noRepeat=0, lengthPenalty=0.0):
@@ -338,6 +367,34 @@ class SplitEval(object):
                              "search runs in the model-level runtime only: use -host native (visdial_amd.native.NativeModel); this "
                              "host applies the constraints with beamBatch = 0" % (minLen, noRepeat, lengthPenalty))
 
+    def _beam_rollout(self, rollout):
+        """raises unless this host's `_gen_beam` rolls out exactly so (never here: the operator-level device search has no entry point
+        that rewrites the history between rounds)"""
+        if rollout:
+            raise ValueError("beamBatch > 0 with rollout = 1: the device rollout runs in the model-level runtime only: use -host native "
+                             "(visdial_amd.native.NativeModel); this host rolls out with beamBatch = 0")
+
+    def rollout_batch(self, dataloader, convIds, dtype):
+        """`getIndexData` with the history at its UNTRIMMED width: getIndexData trims to the ground-truth lengths of the chunk, and a
+        generated answer may be longer"""
+        batch = dataloader.getIndexData(convIds, self.params, dtype)
+        if 'hist' in batch:
+            batch['hist'] = np.ascontiguousarray(dataloader.data[dtype]['hist'][np.asarray(convIds, np.int64) - 1]).astype(np.int32)
+        return batch
+
+    def rollout_dialog(self, batch, search, endToken):
+        """R1-R6 for the ONE dialog of `batch` on the host: `search(r)` is the beam search of round r from the state `_gen_begin` left,
+        returning its groups' (tokens, score) (`beam_search_round`).  Round r >= 1 first gets its history row from round r - 1's answer
+        (batch['hist'] is rewritten in place) and a new `_gen_encode`.  Returns search(r) per round."""
+        R, Th = batch['ques_fwd'].shape[1], batch['hist'].shape[2]
+        found = []
+        for r in range(R):
+            if r > 0:
+                batch['hist'][0, r] = rollout_history_row(batch['ques_fwd'][0, r - 1], found[-1][0][0], Th, endToken)
+            self._gen_encode(batch)
+            found.append(search(r))
+        return found
+
     def generateAnswers(self, dataloader, dtype, params=None):
         """Beam search (default) or temperature sampling with the generative decoder, one dialog at a time,
         exactly as the reference drives it from the host: the decoder step (embedding, LSTM stack, vocabulary
@@ -353,7 +410,10 @@ class SplitEval(object):
         whose device search runs in groups (`_beam_grouping`).  params beamMinLen / beamNoRepeat / beamLengthPenalty (beam search only,
         each off at 0): no answer of fewer than beamMinLen words, no n-gram of beamNoRepeat words twice in a hypothesis, finished
         hypotheses compete on score / length^beamLengthPenalty (csrc/beam.hip C1-C6); with beamBatch > 0 they need a host whose device
-        search applies them (`_beam_constraints`).
+        search applies them (`_beam_constraints`).  params rollout = 1 (beam search, beamGroups = 1): every round is answered on a history
+        of the model's own answers to the rounds before it instead of the ground truth's (R1-R6 above, `rollout_dialog`): one encode per
+        round and dialog with beamBatch = 0; with beamBatch > 0 it needs a host whose device search rolls out (`_beam_rollout`).  An encoder
+        without a history generates as with rollout = 0.
         Returns [{image_id, dialog: [{question, answer}...]}]."""
         if self.params['decoder'] == 'disc':
             raise SystemExit('Sampling/beam search only for generative model')
@@ -388,9 +448,19 @@ class SplitEval(object):
             if sampleWords:
                 raise ValueError('beamMinLen / beamNoRepeat / beamLengthPenalty constrain beam search: sampling (sampleWords = 1) has none')
         minLen, noRepeat, lengthPenalty = int(minLen), int(noRepeat), float(lengthPenalty)
+        rollout = int(params.get('rollout', 0) or 0)
+        if rollout not in (0, 1):
+            raise ValueError('rollout = %r must be 0 or 1' % (params.get('rollout'),))
+        if rollout and sampleWords:
+            raise ValueError('rollout = 1 feeds the beam search\'s answers back: with sampling (sampleWords = 1) one divergent draw would '
+                             'cascade over the rounds')
+        if rollout and beamGroups > 1:
+            raise ValueError('rollout = 1 with beamGroups = %d: the choice among a round\'s groups is made on the host; a rollout over diverse '
+                             'beam search is left for a follow-up' % beamGroups)
         if beamBatch > 0:
             self._beam_grouping(beamGroups, beamDiversity)
             self._beam_constraints(minLen, noRepeat, lengthPenalty)
+            self._beam_rollout(rollout)
         startToken, endToken = dataloader.word2ind['<START>'], dataloader.word2ind['<END>']
         numThreads = int(params.get('maxThreads') or dataloader.numThreads[dtype])
         rng = np.random.RandomState(int(params.get('seed', 1234)))
@@ -412,7 +482,7 @@ class SplitEval(object):
         if chunk > 0:
             for first in range(1, numThreads + 1, chunk):
                 convIds = np.arange(first, min(first + chunk, numThreads + 1))
-                batch = dataloader.getIndexData(convIds, self.params, dtype)
+                batch = self.rollout_batch(dataloader, convIds, dtype) if rollout else dataloader.getIndexData(convIds, self.params, dtype)
                 B, R = len(convIds), batch['ques_fwd'].shape[1]
                 self._gen_encode(batch)
                 if sampleWords:
@@ -432,10 +502,22 @@ class SplitEval(object):
             self._set_training(True)
             return answerTable
         for convId in range(1, numThreads + 1):
-            batch = dataloader.getIndexData(np.array([convId]), self.params, dtype)
+            if rollout:
+                batch = self.rollout_batch(dataloader, np.array([convId]), dtype)
+            else:
+                batch = dataloader.getIndexData(np.array([convId]), self.params, dtype)
             R = batch['ques_fwd'].shape[1]
-            self._gen_encode(batch)                                               # forwardBackward(batch, true, true)
             answers, grouped = [], []
+            if rollout and 'hist' in batch:
+
+                def search(it):
+                    self._gen_begin(np.full(beamSize, it, np.int32))
+                    return beam_search_round(self._gen_step, self._gen_select, beamSize, beamLen, startToken, endToken, 1, beamDiversity,
+                                             minLen, noRepeat, lengthPenalty)
+                answers = [found[0][0] for found in self.rollout_dialog(batch, search, endToken)]
+                answerTable.append(record(convId, batch['ques_fwd'][0], answers))
+                continue
+            self._gen_encode(batch)                                               # forwardBackward(batch, true, true)
             if not sampleWords:
                 for it in range(R):
                     self._gen_begin(np.full(beamSize, it, np.int32))              # hiddenBeams, model.lua:478-503
