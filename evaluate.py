@@ -3,7 +3,8 @@
 (or a reference .t7), rebuilds the model from the SAVED modelParams (evaluate.lua:58-68), initialises the dataloader
 on the chosen split of the REAL data files (evaluate.lua:80-81) and ranks the 100 candidate answers of every round:
 -useGt 1 -> retrieve (R@1/5/10, median/mean rank, MRR), else predict.  Optionally dumps the {image_id, round_id,
-ranks} records as JSON (evaluate.lua:104-107; the EvalAI submission format).  Without data files on disk it falls
+ranks} records as JSON (evaluate.lua:104-107; the EvalAI submission format).  -rollout 1 ranks every round on a history of
+the model's own answers to the rounds before it (visdial_amd/split_eval.py E1-E5): the same ranks, metrics and records.  Without data files on disk it falls
 back to synthetic VisDial-shaped batches (plumbing check only; says so)."""
 import argparse
 import os
@@ -14,7 +15,7 @@ from visdial_amd.dataloader import Dataloader, SyntheticDataloader
 from visdial_amd.model import Model
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='Evaluate the Visual Dialog model')
     ap.add_argument('-inputImg', '--inputImg', default='data/data_img.h5')
     ap.add_argument('-inputQues', '--inputQues', default='data/visdial_data.h5')
@@ -38,7 +39,36 @@ def main():
     ap.add_argument('-optionCache', '--optionCache', type=int, default=0,
                     help='disc decoder: keep the encoding of every distinct candidate answer on the device while the split is ranked and run '
                          'the option LSTM over the answers not seen before only (0 = off, 1 = on, larger = capacity in rows)')
-    a = ap.parse_args()
+    ap.add_argument('-rollout', '--rollout', type=int, default=0, choices=[0, 1],
+                    help='rank every round on a history of the model\'s OWN answers to the rounds before it instead of the ground truth\'s: '
+                         'disc feeds the rank-1 candidate back (-host native: on the device, -host python: a host loop of one retrieval '
+                         'per round), gen the beam search\'s answer, as generate.py -rollout 1 (needs -host native)')
+    ap.add_argument('-beamSize', '--beamSize', type=int, default=5, help='-rollout 1, gen decoder: the beam search that answers')
+    ap.add_argument('-beamLen', '--beamLen', type=int, default=20)
+    ap.add_argument('-minLen', '--minLen', type=int, default=0, help='-rollout 1, gen decoder: as generate.py')
+    ap.add_argument('-noRepeatNgram', '--noRepeatNgram', type=int, default=0)
+    ap.add_argument('-lengthPenalty', '--lengthPenalty', type=float, default=0.0)
+    return ap.parse_args(argv)
+
+
+def check_rollout(a, p):
+    """what -rollout 1 cannot be combined with, for the derived model params `p`: each refusal names its flag"""
+    if not a.rollout:
+        return
+    if a.optionCache:
+        raise SystemExit('-rollout 1 with -optionCache: a cached batch carries only the candidates the cache did not hold, and the rollout '
+                         'reads a picked candidate\'s tokens from the batch; combining the two is left for a follow-up')
+    if a.perplexity:
+        raise SystemExit('-rollout 1 with -perplexity 1: perplexity is defined on the ground-truth history; run it separately')
+    if p.get('useHistory') and p.get('concatHistory'):
+        raise SystemExit("-rollout 1 with encoder '%s': it reads the running concatenation of the rounds (concatHistory), and the rollout's "
+                         "rule describes the per-round history row only; a concatenation rule is left for a follow-up" % p['encoder'])
+    if p['decoder'] == 'gen' and a.host != 'native':
+        raise SystemExit('-rollout 1 with a generative model feeds the beam search\'s answers back on the device: add -host native')
+
+
+def main(argv=None):
+    a = parse_args(argv)
     saved = load_checkpoint(a.loadPath)
     p = opts.derive(saved['modelParams'])                    # sets useHistory / useIm / concatHistory (evaluate.lua:69-75)
     p['gpuid'], p['batchSize'], p['useGt'] = a.gpuid, a.batchSize, bool(a.useGt)
@@ -50,6 +80,8 @@ def main():
     if a.optionCache and p['decoder'] != 'disc':
         raise SystemExit('-optionCache: the answer-encoding cache is only for a discriminative model')
     p['optionCache'] = a.optionCache
+    check_rollout(a, p)
+    p['rollout'] = a.rollout
     p.update(inputImg=a.inputImg, inputQues=a.inputQues, inputJson=a.inputJson)
     have = lambda f: os.path.exists(f) or os.path.exists(f[:-3] + '.npz')
     if os.path.exists(a.inputJson) and have(a.inputQues):
@@ -59,6 +91,14 @@ def main():
     else:
         print('no dataset at %s: ranking SYNTHETIC batches (plumbing check, the metrics mean nothing)' % a.inputQues)
         dl = SyntheticDataloader(p, seed=4321, num_threads=a.numThreads)
+    if a.rollout and p['decoder'] == 'gen':
+        # the device search takes its knobs when the model is created; the answers are the ones generate.py -rollout 1 -beamBatch N writes
+        w2i = getattr(dl, 'word2ind', None)
+        start, end = (w2i['<START>'], w2i['<END>']) if w2i else (dl.startToken, dl.endToken)
+        p.update(beamRollout=1, beamMinLen=a.minLen, beamNoRepeat=a.noRepeatNgram, beamLengthPenalty=a.lengthPenalty,
+                 rolloutBeam=dict(beamSize=a.beamSize, beamLen=a.beamLen, startToken=start, endToken=end))
+    elif a.rollout and a.host == 'native':
+        p['retrieveRollout'] = 1
     if a.host == 'native':
         from visdial_amd.native import NativeModel
         model = NativeModel(p)
@@ -80,6 +120,8 @@ def main():
         print('fusedLhood 2: %d nodes for %d live rows (%.3f); the candidate recurrence ran %d of %d (step, candidate) rows (%.1f %%)'
               % (st['nodes'], st['live'], st['nodes'] / max(st['live'], 1), st['executed'], st['total'],
                  100.0 * st['executed'] / max(st['total'], 1)))
+    if a.rollout:
+        print('rollout: %d of %d history rows differ from the ground truth\'s' % model.rolloutRows)
     if a.optionCache:
         ex, tot = model.optionCacheRows
         print('optionCache: the option LSTM ran %d of %d candidate rows (%.1f %%)' % (ex, tot, 100.0 * ex / max(tot, 1)))

@@ -424,7 +424,27 @@ int vd_model_loss(vd_model* m, float* loss);              /* curLoss of the last
  * vd_model_forward_backward(only_forward = 0) and vd_model_flat_pointers; a host that writes the weights through the pointers of
  * the latter must call one of these afterwards.  A batch uploaded while the cache is on and training is off carries the unseen
  * rows only: it serves these two calls, not a backward pass.  vd_model_create refuses the variable for decoder gen and for
- * lstmBf16 = 1. */
+ * lstmBf16 = 1.
+ * Rollout (decoder disc, opt-in): VD_RETRIEVE_ROLLOUT = 1 (0 / unset = off; read once by vd_model_create, which refuses any other
+ * value by name and refuses 1 together with VD_OPTION_CACHE -- a cached batch carries only the rows the cache did not hold;
+ * ignored for decoder gen, whose rollout is VD_BEAM_ROLLOUT at vd_model_beam_search).  With training off and an encoder that has
+ * a history, this call then ranks round r of a dialog on a history that holds THE MODEL'S OWN answers to rounds < r instead of
+ * the uploaded ones (the rule is E1-E5 at the top of csrc/beam.hip): the answer of a round is the candidate vd_model_ranks would
+ * give rank 1 (the highest score, among equal scores the lowest index); history row r + 1 is the non-zero tokens of question row
+ * r, then the candidate's words (entries 0, 1, ... of its options row up to the first 0) as far as they fit, right-aligned in
+ * the Th columns.  The option recurrence runs ONCE (an option's encoding does not depend on the history); then R = maxQuesCount
+ * passes -- encoder forward, the scoring of all N rounds, one kernel that writes history row r + 1 of every dialog -- with no host
+ * synchronisation between them.  The scores, ranks and loss the call leaves are those of the last pass, which is the result for
+ * every round (rows <= r of a dialog do not change after pass r and every encoder is causal over the rounds); vd_model_scores /
+ * vd_model_ranks / vd_model_loss read them as ever.  The uploaded contents of history rows >= 1 are ignored and overwritten:
+ * after the call the batch's device history holds the generated rows.  vd_model_upload_batch lays the history rows >= 1 of such
+ * a model out at full width and refuses, by name, Th < Tq; pass the history at its untrimmed width, a picked answer may be longer
+ * than the ground truth's.  With training on the call returns a state error that names the variable.  An encoder without a
+ * history ranks as before; vd_model_forward_backward is the plain step in both modes; with the variable 0 or unset nothing
+ * changes.  The host loop it equals: split_eval.py retrieve_rollout_batch.
+ * For decoder gen the same measurement composes existing calls on ONE slot: vd_model_upload_batch (with option_in / option_out),
+ * vd_model_encode, vd_model_beam_search on a model created with VD_BEAM_ROLLOUT = 1 (it leaves the generated history in the
+ * slot), then vd_model_retrieve or vd_model_retrieve_lhood. */
 int vd_model_retrieve(vd_model* m);
 /* the same contract for the generative decoder through the live-row head (vd_lhood_* above): scores within the fp32 rounding of
  * vd_model_retrieve's, no logits buffer, one host synchronisation per chunk of options (the live-row count).  An argument error

@@ -23,6 +23,12 @@ candidates of --batches batches are drawn from a pool of --pool distinct answers
 pass after a flush); cached and warm (second pass), with the rows the recurrence ran and the device memory the process holds after
 each case.  --cases uncached runs the first alone (the parent commit's library through VD_LIB_PATH knows no cache), --cases cached the other two
 (for a kernel trace).
+--mode disc --rollout 1: ranking on a rollout (evaluate.py -rollout 1; csrc/beam.hip E1-E5) at the same full size, the synthetic loader's
+own candidates: per batch (upload + retrieve + ranks, as evaluate.py runs it) the plain retrieval on the ground-truth history (a model
+created without VD_RETRIEVE_ROLLOUT), the device rollout (one upload + one vd_model_retrieve on a model created with it) and the host loop
+(R uploads + retrievals, --host-batches of the batches), alternated.  The device rollout's time over the plain retrieval's is what the
+R - 1 further encoder passes, scorings and picks cost: the option recurrence runs once in both.  --cases plain runs the first alone (the
+parent commit's library through VD_LIB_PATH knows no rollout), --cases device the second (for a kernel trace).
 --mode step: the option recurrence alone (vd_lstm_forward, table mode, 20 000 x 512, 20 steps), saving against VD_FLAG_STATE_ONLY,
 alternated, device time by events."""
 import argparse
@@ -48,7 +54,9 @@ ap.add_argument('--save-scores', default='', help='write the fused scores of eve
 ap.add_argument('--mode', choices=('gen', 'disc', 'step'), default='gen')
 ap.add_argument('--pool', type=int, default=2000, help='--mode disc: distinct answers the candidates are drawn from')
 ap.add_argument('--batches', type=int, default=6, help='--mode disc: batches per pass')
-ap.add_argument('--cases', choices=('all', 'uncached', 'cached'), default='all', help='--mode disc')
+ap.add_argument('--cases', choices=('all', 'uncached', 'cached', 'plain', 'device'), default='all', help='--mode disc')
+ap.add_argument('--rollout', type=int, choices=(0, 1), default=0, help='--mode disc: ranking on a rollout, three paths (see above)')
+ap.add_argument('--host-batches', type=int, default=2, help='--mode disc --rollout 1: batches the host loop ranks per pass')
 opt = ap.parse_args()
 
 
@@ -121,6 +129,69 @@ def disc_mode():
               % (np.abs(scores[0].astype(np.float64) - scores[1]).max(), np.abs(scores[0]).max()))
 
 
+def disc_rollout_mode():
+    from visdial_amd.split_eval import SplitEval
+    B, R, O, To, H = 20, 10, 100, 20, 512
+    p = derive(default_params(encoder='mn-att-ques-im-hist', decoder='disc', vocabSize=11322, imgFeatureSize=512, imgSpatialSize=14,
+                              maxHistoryLenPerRound=40, batchSize=B, numOptions=O, maxQuesCount=R, maxAnsLen=To, lstmPrecision='split9',
+                              gpuid=0))
+    tag = opt.tag and opt.tag + ' '
+    dl = SyntheticDataloader(p, seed=7, num_threads=B * opt.batches)
+    batches, start = [], 1
+    for _ in range(opt.batches):
+        b, start = dl.getTestBatch(start, p, 'val')
+        batches.append(b)
+    print("%smn-att-ques-im-hist + disc, H %d, %d dialogs x %d rounds x %d options, To %d, Th %d, Tq %d, split9, native host, random weights, "
+          "%d batches per pass" % (tag, H, B, R, O, To, batches[0]['hist'].shape[2], batches[0]['ques_fwd'].shape[2], opt.batches), flush=True)
+    want = {'all': ('plain', 'device', 'host'), 'plain': ('plain',), 'device': ('device',)}[opt.cases]
+    plain = roll = None
+    if 'plain' in want or 'host' in want:
+        plain = NativeModel(dict(p), init_seed=1)
+        plain.training(False)
+    if 'device' in want:
+        roll = NativeModel(dict(p, retrieveRollout=1), init_seed=1)
+        roll.training(False)
+
+    def one_pass(case):
+        bs = batches[:opt.host_batches] if case == 'host' else batches
+        out, t0 = None, time.perf_counter()
+        for b in bs:
+            if case == 'plain':
+                out = plain.retrieveBatch(b, useGt=False)
+            elif case == 'device':
+                out = roll.retrieve_rollout_batch(b)
+            else:
+                out = SplitEval.retrieve_rollout_batch(plain, dict(b, hist=np.array(b['hist'])))
+        return (time.perf_counter() - t0) / len(bs), out
+    cases = want
+    for c in cases:                                     # warm-up: workspaces, code objects
+        one_pass(c)
+        one_pass(c)
+    times, last = {c: [] for c in cases}, {}
+    for _ in range(opt.repeats):                        # alternated
+        for c in cases:
+            t, last[c] = one_pass(c)
+            times[c].append(t)
+    for c in cases:
+        t = np.asarray(times[c])
+        print("  %s%-12s %8.2f ms per batch (median of %d; min %.2f, max %.2f) = %7.2f batches/s" % (
+            tag, c, np.median(t) * 1e3, len(t), t.min() * 1e3, t.max() * 1e3, 1.0 / np.median(t)), flush=True)
+    if 'device' in last and 'host' in last:
+        same = np.array_equal(roll.retrieve_rollout_batch(batches[opt.host_batches - 1]), last['host'])
+        print("  device rollout and host loop return the same ranks for batch %d: %s" % (opt.host_batches - 1, same))
+    if 'device' in times and 'plain' in times:
+        d, q = np.median(times['device']), np.median(times['plain'])
+        print("  the R - 1 further encoder passes, scorings and picks: %.2f ms per batch = %.0f %% of the device rollout's batch"
+              % ((d - q) * 1e3, 100.0 * (d - q) / d))
+    if 'device' in last and 'plain' in last:
+        first = lambda r: np.asarray(r).reshape(B * R, O).argmin(1)
+        print("  rounds of the last batch whose rank-1 candidate differs between the rollout and the ground-truth history: %d of %d"
+              % (int((first(last['device']) != first(last['plain'])).sum()), B * R))
+    for m in (plain, roll):
+        if m is not None:
+            m.close()
+
+
 def step_mode():
     import torch
     from visdial_amd import ops
@@ -158,7 +229,7 @@ def step_mode():
 
 
 if opt.mode == 'disc':
-    disc_mode()
+    disc_rollout_mode() if opt.rollout else disc_mode()
     sys.exit(0)
 if opt.mode == 'step':
     step_mode()

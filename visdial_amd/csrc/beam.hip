@@ -88,6 +88,24 @@
 //      generated rows.
 // On the device a chunk of B dialogs runs R passes (Gen_beam_search, rt_decoders.h): encoder forward, the search of round r of every dialog
 // (B groups, the kernels above unchanged), beam_rollout_append_kernel for row r + 1.  Nothing waits for the host between passes.
+//
+// Rollout of the discriminative decoder (VD_RETRIEVE_ROLLOUT = 1 at vd_model_create; evaluate.py -rollout 1): the candidates of round r are
+// RANKED on a history that holds the model's own picks for the rounds before it.  split_eval.py restates E2 - E4 (rollout_pick,
+// rollout_candidate_row, rollout_history_row) and the host loop (retrieve_rollout_batch).  O = numOptions, To = the width of an option row.
+//  E1. round 0's history row is the uploaded one (R1).
+//  E2. the answer chosen for round r is the candidate that vd_ranks gives rank 1 among the round's O scores: the highest score, and among
+//      equal scores the lowest index (duplicate candidates inside one round are common).
+//  E3. the words of a candidate are entries 0, 1, ... of its `options` row [To], up to but excluding the first 0: the rows are left-aligned
+//      and hold neither <START> nor <END>.  An all-zero row is an empty answer.
+//  E4. history row r + 1 is built by R2 from question row r and those words: the question's non-zero tokens first and whole, then the first
+//      min(la, Th - lq) words, right-aligned in Th columns; lq = 0 and no words: an all-zero row.
+//  E5. R5 and R6 hold as written: round r is scored from an encoder pass in which rows 0 .. r are final; the uploaded rows >= 1 are ignored
+//      and overwritten; after the call the slot's device history holds the generated rows.  The scores, ranks and loss the call leaves are
+//      those of the pass after the last append, an ordinary scoring of all N rounds: rows <= r of a dialog do not change after pass r and
+//      every encoder is causal, so that pass scores round r exactly as pass r did.
+// An option's encoding depends on its tokens and the weights only, so the option LSTM runs ONCE; a chunk then runs R passes (Disc::
+// retrieve_rollout, rt_decoders.h): encoder forward, vd_score_ce over all N rounds, disc_rollout_pick_kernel for row r + 1 (not after the
+// last).  Nothing waits for the host between passes.  For decoder gen the answer fed back is the beam search's (R4).
 #include "common.h"
 
 #define VD_BEAM_KMAX 32
@@ -392,22 +410,20 @@ __global__ void beam_finish_kernel(int groups, int k, int L, const int32_t* __re
   }
 }
 
-// R2 / R3 for one pass of a rollout: one wave per dialog writes history row r + 1 from question row r and the answer just chosen for
-// round r.  The wave counts lq with ballots while it compacts the question's non-zero tokens into LDS (a lane's place = the set bits
-// below it), finds the answer's word count as the first lane whose entry is <END>, 0 or past the row, and then makes ONE pass over the Th
-// columns: column c holds 0, a question token or an answer word by its distance from the right edge alone, so every column is written
+// R2 for one history row, by the one wave of the workgroup: row nq + 1 of the step-major tokens from question row nq and `la` words, word i at
+// words[i * stride] (stride 1: a row of answer tokens; the row count of a step-major token table: one of its rows).  The wave counts lq
+// with ballots while it compacts the question's non-zero tokens into LDS (a lane's place = the set bits below it) and then makes ONE pass
+// over the Th columns: column c holds 0, a question token or a word by its distance from the right edge alone, so every column is written
 // exactly once, with plain vector stores, into the step-major tokens [Th x N] and (inv != nullptr) the length-sorted copy the wavefront
 // masks with.  Both are step-major, so a dialog's columns lie N apart: a wave's stores are strided whatever the lane order, and at
 // B x Th x 4 bytes per pass (1.1 KB at B = 20, Th = 14) the launch is what costs.  Tq <= VD_ROLLOUT_TMAX (the LDS list), lq <= Tq <= Th.
 #define VD_ROLLOUT_TMAX 1024
-__global__ void __launch_bounds__(64)
-beam_rollout_append_kernel(const int32_t* __restrict__ answers, int L, int end_tok, const int32_t* __restrict__ ques, int Tq, long N, int R,
-                           int r, int Th, int32_t* __restrict__ hist_tok, int32_t* __restrict__ hist_sorted,
-                           const int32_t* __restrict__ inv) {
+__device__ __forceinline__ void rollout_write_row(const int32_t* __restrict__ ques, int Tq, long N, long nq, const int32_t* __restrict__ words,
+                                                  long stride, int la, int Th, int32_t* __restrict__ hist_tok,
+                                                  int32_t* __restrict__ hist_sorted, const int32_t* __restrict__ inv) {
   __shared__ int32_t qc[VD_ROLLOUT_TMAX];
   const int lane = threadIdx.x;
-  const long nq = (long)blockIdx.x * R + r, nh = nq + 1;           // the round just answered; the history row it becomes
-  const int32_t* a = answers + (long)blockIdx.x * L;
+  const long nh = nq + 1;                                          // the history row the round just answered becomes
   int lq = 0;
   for (int base = 0; base < Tq; base += 64) {
     const int t = base + lane;
@@ -416,6 +432,25 @@ beam_rollout_append_kernel(const int32_t* __restrict__ answers, int L, int end_t
     if (v != 0) qc[lq + __popcll(mask & ((1ull << lane) - 1ull))] = v;
     lq += __popcll(mask);
   }
+  __syncthreads();
+  const int pad = Th - lq - min(la, Th - lq);                      // R2: zeros in front
+  for (int base = 0; base < Th; base += 64) {
+    const int c = base + lane, j = c - pad;
+    if (c >= Th) break;
+    const int32_t v = j < 0 ? 0 : j < lq ? qc[j] : words[(long)(j - lq) * stride];
+    hist_tok[(long)c * N + nh] = v;
+    if (hist_sorted) hist_sorted[(long)c * N + inv[nh]] = v;
+  }
+}
+
+// R2 / R3 for one pass of a rollout: one wave per dialog writes history row r + 1 from question row r and the answer just chosen for
+// round r.  The answer's word count is the first lane whose entry is <END>, 0 or past the row; the words start behind <START>.
+__global__ void __launch_bounds__(64)
+beam_rollout_append_kernel(const int32_t* __restrict__ answers, int L, int end_tok, const int32_t* __restrict__ ques, int Tq, long N, int R,
+                           int r, int Th, int32_t* __restrict__ hist_tok, int32_t* __restrict__ hist_sorted,
+                           const int32_t* __restrict__ inv) {
+  const int lane = threadIdx.x;
+  const int32_t* a = answers + (long)blockIdx.x * L;
   int la = 0;                                                      // R3: entries 1 .. la are the words
   for (int base = 1;; base += 64) {
     const int c = base + lane;
@@ -426,15 +461,46 @@ beam_rollout_append_kernel(const int32_t* __restrict__ answers, int L, int end_t
       break;
     }
   }
-  __syncthreads();
-  const int pad = Th - lq - min(la, Th - lq);                      // R2: zeros in front
-  for (int base = 0; base < Th; base += 64) {
-    const int c = base + lane, j = c - pad;
-    if (c >= Th) break;
-    const int32_t v = j < 0 ? 0 : j < lq ? qc[j] : a[1 + j - lq];
-    hist_tok[(long)c * N + nh] = v;
-    if (hist_sorted) hist_sorted[(long)c * N + inv[nh]] = v;
+  rollout_write_row(ques, Tq, N, (long)blockIdx.x * R + r, a + 1, 1, la, Th, hist_tok, hist_sorted, inv);
+}
+
+// E2 - E4 for one pass of a discriminative rollout: one wave per dialog picks the rank-1 candidate of round r among its O <= 128 scores
+// (two per lane; beam_better IS ranks_kernel's "nothing ranks before it" for finite scores: the highest score, the lowest index among
+// equals), finds its tokens in the option tokens the step already holds -- step-major [To x rows], row = opt_uid[candidate] where the
+// upload de-duplicated, the candidate itself otherwise --, counts its words up to the first 0 with a ballot (E3: left-aligned, no
+// <START>, no <END>) and writes history row r + 1 through rollout_write_row.  Lane 0's result is broadcast: with a NaN among the scores
+// the butterfly's lanes need not agree, and the row must come from ONE candidate.
+#define VD_DISC_PICK_OMAX 128   // loss.hip's MAX_OPT
+__global__ void __launch_bounds__(64)
+disc_rollout_pick_kernel(const float* __restrict__ scores, int O, const int32_t* __restrict__ opt_tok, long rows, int To,
+                         const int32_t* __restrict__ opt_uid, const int32_t* __restrict__ ques, int Tq, long N, int R, int r, int Th,
+                         int32_t* __restrict__ hist_tok, int32_t* __restrict__ hist_sorted, const int32_t* __restrict__ inv) {
+  const int lane = threadIdx.x;
+  const long nq = (long)blockIdx.x * R + r;
+  const float* s = scores + nq * O;
+  float bv = lane < O ? s[lane] : -INFINITY;                       // (a lane without a score never wins: INT_MAX is no index)
+  int bi = lane < O ? lane : INT_MAX;
+  if (lane + 64 < O && beam_better(s[lane + 64], lane + 64, bv, bi)) { bv = s[lane + 64]; bi = lane + 64; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v2 = __shfl_xor(bv, o, 64);
+    const int i2 = __shfl_xor(bi, o, 64);
+    if (beam_better(v2, i2, bv, bi)) { bv = v2; bi = i2; }
   }
+  bi = __shfl(bi, 0, 64);                                          // E2; lane 0 holds an index < O whatever the scores are
+  const long cand = nq * O + bi;
+  const int32_t* w = opt_tok + (opt_uid ? (long)opt_uid[cand] : cand);
+  int la = 0;                                                      // E3: entries 0 .. la - 1 are the words
+  for (int base = 0;; base += 64) {
+    const int t = base + lane;
+    const bool stop = t >= To || w[(long)t * rows] == 0;
+    const unsigned long long mask = __ballot(stop);
+    if (mask) {
+      la = base + __ffsll((long long)mask) - 1;
+      break;
+    }
+  }
+  rollout_write_row(ques, Tq, N, nq, w, rows, la, Th, hist_tok, hist_sorted, inv);
 }
 
 }  // namespace
@@ -450,6 +516,27 @@ int vd_beam_rollout_append_p(const int32_t* answers, int beam_len, int end_token
   if (dialogs == 0) return VD_OK;
   hipLaunchKernelGGL(beam_rollout_append_kernel, dim3((unsigned)dialogs), dim3(64), 0, stream, answers, beam_len, end_token, ques, Tq,
                      (long)dialogs * R, R, r, Th, hist_tok, hist_sorted, inv);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+// E2 - E4 (rt_core.h): history row r + 1 of `dialogs` dialogs from question row r and the rank-1 candidate of scores row dialog * R + r
+int vd_disc_rollout_pick_p(const float* scores, int O, const int32_t* opt_tok, int64_t opt_rows, int To, const int32_t* opt_uid,
+                           const int32_t* ques, int Tq, int dialogs, int R, int r, int32_t* hist_tok, int32_t* hist_sorted,
+                           const int32_t* inv, int Th, hipStream_t stream) {
+  VD_CHECK_ARG(scores && opt_tok && ques && hist_tok && To >= 1 && dialogs >= 0 && (hist_sorted == nullptr) == (inv == nullptr),
+               "vd_disc_rollout_pick: bad args");
+  VD_CHECK_ARG(O >= 1 && O <= VD_DISC_PICK_OMAX, "vd_disc_rollout_pick: O = %d candidates per round must be in [1, MAX_OPT = %d]", O,
+               VD_DISC_PICK_OMAX);
+  VD_CHECK_ARG(R >= 2 && r >= 0 && r + 1 < R, "vd_disc_rollout_pick: round %d has no next round among %d", r, R);
+  VD_CHECK_ARG(Tq >= 1 && Tq <= VD_ROLLOUT_TMAX && Th >= Tq, "vd_disc_rollout_pick: question width %d must be in [1, %d] and <= history width %d",
+               Tq, VD_ROLLOUT_TMAX, Th);
+  // without opt_uid a candidate is its own row: the table has to hold every candidate (with it, the upload numbered the rows it holds)
+  VD_CHECK_ARG(opt_rows >= 1 && (opt_uid || opt_rows == (int64_t)dialogs * R * O),
+               "vd_disc_rollout_pick: %lld option rows for %d x %d x %d candidates", (long long)opt_rows, dialogs, R, O);
+  if (dialogs == 0) return VD_OK;
+  hipLaunchKernelGGL(disc_rollout_pick_kernel, dim3((unsigned)dialogs), dim3(64), 0, stream, scores, O, opt_tok, (long)opt_rows, To, opt_uid,
+                     ques, Tq, (long)dialogs * R, R, r, Th, hist_tok, hist_sorted, inv);
   VD_LAUNCH_CHECK();
   return VD_OK;
 }

@@ -81,6 +81,14 @@ int vd_beam_topk_ban_p(const float* logits, int64_t ld, int64_t rows, int V, con
 // every row in it, both or neither.  Needs r + 1 < R and Tq <= Th.
 int vd_beam_rollout_append_p(const int32_t* answers, int beam_len, int end_token, const int32_t* ques, int Tq, int dialogs, int R, int r,
                              int32_t* hist_tok, int32_t* hist_sorted, const int32_t* inv, int Th, hipStream_t stream);
+// beam.hip: one pass of a discriminative rollout (VD_RETRIEVE_ROLLOUT; E2 - E4 there): history row r + 1 of every dialog = the non-zero tokens
+// of question row r, then the words that fit of the candidate that ranks first among scores row dialog * R + r ([dialogs * R x O], O <= 128:
+// the highest score, ties to the lowest index), right-aligned.  The candidate's tokens are read from opt_tok, step-major [To x opt_rows], at
+// row opt_uid[candidate] (the de-duplicated upload) or, with opt_uid == nullptr, at the candidate's own row (opt_rows = dialogs * R * O);
+// its words end at the first 0.  ques / hist_tok / hist_sorted / inv / Tq / Th as above.
+int vd_disc_rollout_pick_p(const float* scores, int O, const int32_t* opt_tok, int64_t opt_rows, int To, const int32_t* opt_uid,
+                           const int32_t* ques, int Tq, int dialogs, int R, int r, int32_t* hist_tok, int32_t* hist_sorted,
+                           const int32_t* inv, int Th, hipStream_t stream);
 
 #define VD_TRY(expr)                  \
   do {                                \
@@ -290,6 +298,9 @@ struct vd_model {
   // VD_BEAM_ROLLOUT at vd_model_create (decoder gen): vd_model_beam_search answers round r on a history of the model's own answers to the
   // rounds before it (beam.hip R1-R6), and an upload lays out history rows >= 1 at full width (runtime.hip upload_tokens)
   bool beam_rollout = false;
+  // VD_RETRIEVE_ROLLOUT at vd_model_create (decoder disc): vd_model_retrieve ranks round r on a history of the model's own picks for the
+  // rounds before it (beam.hip E1-E5); the same full-width upload
+  bool retrieve_rollout = false;
   bool lhood_tree = false;   // VD_LHOOD_TREE at vd_model_create: vd_model_retrieve_lhood scores over a prefix tree of the candidates
   bool prof_hist = false;   // ev_prof[0..3] bracket the history branch of a Sequential encoder (gen pairs: vd_model_family_ms)
   ~vd_model();

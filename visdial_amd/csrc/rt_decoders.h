@@ -67,6 +67,60 @@ inline hipEvent_t* probe_events() {
 #endif
 struct Disc : Decoder {
   void declare(vd_model* m) override { add_lstm(m, "opt", m->p.embedSize, m->p.rnnHiddenSize); }
+  // The candidates' final states, on the main stream: the projection table, then ONE recurrence over the NO rows the upload kept (N * O, or
+  // the distinct candidates).  They depend on the option tokens and the weights only (decoders/disc.lua:4-15).
+  struct OptStates {
+    bool c16;                 // bf16 pass at a throughput shape: COMPACT state (common.h)
+    float *table, *gates, *h, *c, *h_last;
+    vd_bf16_bits *gates16, *h16;
+    const float* optH;        // [NO x H]
+  };
+  int option_states(vd_model* m, BatchSlot& b, OptStates* o) {
+    const int NO = b.opt.N, To = b.opt.T;
+    const long H = m->p.rnnHiddenSize, E = m->p.embedSize, V = m->p.vocabSize;
+    hipStream_t s = m->s_main;
+    VD_TRY(ws_get(m, "opt.table", (size_t)(V + 1) * 4 * H, &o->table));
+    VD_TRY(ws_get(m, "opt.gates", (size_t)To * NO * 4 * H, &o->gates));
+    VD_TRY(ws_get(m, "opt.h", (size_t)To * NO * H, &o->h));
+    VD_TRY(ws_get(m, "opt.c", (size_t)To * NO * H, &o->c));
+    float* Wopt = Wp(m, "opt.W");
+    const int flags = m->flags;
+    VD_TRY(vd_gemm_nn(Wp(m, "embed"), E, Wopt, 4 * H, Wp(m, "opt.b"), o->table, 4 * H, (int)V + 1, (int)(4 * H), (int)E, 0, s));
+    // bf16 pass at a throughput shape: COMPACT state (common.h) -- gates / da only as bf16 (in the first half of `gates`), the
+    // projection table as bf16 rows, h as bf16 plus the last step's fp32 state; c stays fp32
+    o->c16 = (flags & VD_FLAG_BF16) && vd_lstm_c16_fits(NO, (int)H);
+    o->gates16 = reinterpret_cast<vd_bf16_bits*>(o->gates);
+    o->h16 = reinterpret_cast<vd_bf16_bits*>(o->h);
+    o->h_last = nullptr;
+    vd_bf16_bits* table16 = nullptr;
+    if (o->c16) {
+      float* t16;
+      VD_TRY(ws_get(m, "opt.table16", (size_t)(V + 1) * 2 * H, &t16));
+      VD_TRY(ws_get(m, "opt.h_last", (size_t)NO * H, &o->h_last));
+      table16 = reinterpret_cast<vd_bf16_bits*>(t16);
+      VD_TRY(vd_f32_to_bf16(o->table, table16, (V + 1) * 4 * H, s));
+    }
+    VD_HIP(hipEventRecord(m->ev_prof[0], s));
+    {
+      VdRange r("disc: option LSTM forward");
+      if (o->c16) VD_TRY(vd_lstm_forward_c16(table16, 4 * H, b.opt.tok, Wopt + E * 4 * H, o->gates16, o->h16, o->h_last, o->c, To, NO, (int)H, s));
+      else VD_TRY(vd_lstm_forward(o->table, 0, 4 * H, b.opt.tok, nullptr, Wopt + E * 4 * H, nullptr, nullptr, o->gates, o->h, o->c, To, NO, (int)H, flags, s));
+    }
+    VD_HIP(hipEventRecord(m->ev_prof[1], s));
+    o->optH = o->c16 ? o->h_last : o->h + (long)(To - 1) * NO * H;
+    return VD_OK;
+  }
+  // the state of every candidate (n, o), [N * O x H]: after a de-duplicating upload candidate (n, o) reads the state of its distinct row
+  int option_states_full(vd_model* m, BatchSlot& b, const OptStates& o, const float** optH) {
+    *optH = o.optH;
+    if (!b.opt_uid) return VD_OK;
+    const long NOfull = (long)b.q.N * m->p.numOptions, H = m->p.rnnHiddenSize;
+    float* full;
+    VD_TRY(ws_get(m, "opt.h_full", (size_t)NOfull * H, &full));
+    VD_TRY(vd_embed_gather(o.optH, b.opt_uid, nullptr, full, NOfull, (int)H, 1.f, m->s_main));
+    *optH = full;
+    return VD_OK;
+  }
   int forward_backward(vd_model* m, BatchSlot& b, bool only_forward) override {
     VD_CHECK_ARG(b.opt.present, "decoder 'disc' needs batch.options");
     VD_CHECK_ARG(only_forward || b.has_gt, "training decoder 'disc' needs batch.answer_ind");
@@ -78,37 +132,18 @@ struct Disc : Decoder {
     const long H = m->p.rnnHiddenSize, E = m->p.embedSize, V = m->p.vocabSize;
     hipStream_t s = m->s_main;
     hipStream_t sd = side_stream(m, s);   // encoder, then the table-gradient chain, in this function's enqueue order
-    float *table, *gates, *h, *c, *scores, *loss_rows;
-    VD_TRY(ws_get(m, "opt.table", (size_t)(V + 1) * 4 * H, &table));
-    VD_TRY(ws_get(m, "opt.gates", (size_t)To * NO * 4 * H, &gates));
-    VD_TRY(ws_get(m, "opt.h", (size_t)To * NO * H, &h));
-    VD_TRY(ws_get(m, "opt.c", (size_t)To * NO * H, &c));
+    float *scores, *loss_rows;
     VD_TRY(ws_get(m, "opt.scores", (size_t)N * O, &scores));
     VD_TRY(ws_get(m, "crit.loss_rows", (size_t)N, &loss_rows));
     float* Wopt = Wp(m, "opt.W");
     const int flags = m->flags;
     VD_TRY(fork_stream(m, s, sd));
     float* enc_out = nullptr;
-    VD_TRY(vd_gemm_nn(Wp(m, "embed"), E, Wopt, 4 * H, Wp(m, "opt.b"), table, 4 * H, (int)V + 1, (int)(4 * H), (int)E, 0, s));
-    // bf16 pass at a throughput shape: COMPACT state (common.h) -- gates / da only as bf16 (in the first half of `gates`), the
-    // projection table as bf16 rows, h as bf16 plus the last step's fp32 state; c stays fp32
-    const bool c16 = (flags & VD_FLAG_BF16) && vd_lstm_c16_fits(NO, (int)H);
-    vd_bf16_bits *gates16 = reinterpret_cast<vd_bf16_bits*>(gates), *h16 = reinterpret_cast<vd_bf16_bits*>(h), *table16 = nullptr;
-    float* h_last = nullptr;
-    if (c16) {
-      float* t16;
-      VD_TRY(ws_get(m, "opt.table16", (size_t)(V + 1) * 2 * H, &t16));
-      VD_TRY(ws_get(m, "opt.h_last", (size_t)NO * H, &h_last));
-      table16 = reinterpret_cast<vd_bf16_bits*>(t16);
-      VD_TRY(vd_f32_to_bf16(table, table16, (V + 1) * 4 * H, s));
-    }
-    VD_HIP(hipEventRecord(m->ev_prof[0], s));
-    {
-      VdRange r("disc: option LSTM forward");
-      if (c16) VD_TRY(vd_lstm_forward_c16(table16, 4 * H, b.opt.tok, Wopt + E * 4 * H, gates16, h16, h_last, c, To, NO, (int)H, s));
-      else VD_TRY(vd_lstm_forward(table, 0, 4 * H, b.opt.tok, nullptr, Wopt + E * 4 * H, nullptr, nullptr, gates, h, c, To, NO, (int)H, flags, s));
-    }
-    VD_HIP(hipEventRecord(m->ev_prof[1], s));
+    OptStates os;
+    VD_TRY(option_states(m, b, &os));
+    const bool c16 = os.c16;
+    float *gates = os.gates, *h = os.h, *c = os.c;
+    vd_bf16_bits *gates16 = os.gates16, *h16 = os.h16;
     {
       VdRange r("encoder forward");
       VD_TRY(m->enc->forward(m, sd, b, &enc_out));                                 // model.lua:297
@@ -116,14 +151,9 @@ struct Disc : Decoder {
     }
     VD_TRY(join_stream(m, sd, s));
     // criterion (+ nn.MM backward) in one kernel (model.lua:330-335)
-    const float* optH = c16 ? h_last : h + (long)(To - 1) * NO * H;
+    const float* optH;
+    VD_TRY(option_states_full(m, b, os, &optH));
     float *d_optH = nullptr, *d_enc = nullptr, *d_optH_full = nullptr;
-    if (dedup) {   // candidate (n, o) reads the state of its distinct row
-      float* full;
-      VD_TRY(ws_get(m, "opt.h_full", (size_t)NOfull * H, &full));
-      VD_TRY(vd_embed_gather(optH, b.opt_uid, nullptr, full, NOfull, (int)H, 1.f, s));
-      optH = full;
-    }
     if (!only_forward) {
       VD_TRY(ws_get(m, "crit.d_optH", (size_t)NO * H, &d_optH));
       VD_TRY(ws_get(m, "crit.d_enc", (size_t)N * H, &d_enc));
@@ -200,7 +230,59 @@ struct Disc : Decoder {
     VD_PROBE_REC(4, s);
     return VD_OK;
   }
-  int retrieve(vd_model* m, BatchSlot& b) override { return forward_backward(m, b, true); }   // model.lua:421-425
+  int retrieve(vd_model* m, BatchSlot& b) override {                                          // model.lua:421-425
+    if (m->retrieve_rollout && m->use_hist) return retrieve_rollout(m, b);   // (no history: nothing depends on an answer)
+    return forward_backward(m, b, true);
+  }
+
+  // VD_RETRIEVE_ROLLOUT (beam.hip E1-E5): the candidates' states once, then R = maxQuesCount passes on the main stream: encoder forward
+  // (pass 0's beside the option recurrence, as in the plain step), vd_score_ce over all N rounds, and -- not after the last -- the pick
+  // kernel, which writes history row r + 1 of every dialog from the rank-1 candidate of its round r.  Nothing waits for the host between
+  // passes.  The last pass IS the result for every round: rows <= r of a dialog are final after pass r and every encoder is causal.
+  int retrieve_rollout(vd_model* m, BatchSlot& b) {
+    if (m->training) {
+      vd_set_error("vd_model_retrieve: this model was created with VD_RETRIEVE_ROLLOUT = 1, and a rollout re-runs the encoder once per round: "
+                   "under training-mode dropout the passes would not describe one model; call vd_model_set_training(0) first");
+      return VD_ERR_STATE;
+    }
+    VD_CHECK_ARG(b.opt.present && !b.cached, "decoder 'disc' needs batch.options");
+    const int N = b.q.N, O = m->p.numOptions, NOfull = N * O, NO = b.opt.N, R = m->p.maxQuesCount, B = N / R;
+    const bool dedup = b.opt_uid != nullptr;
+    VD_CHECK_ARG(dedup ? NO <= NOfull : NO == NOfull, "decoder 'disc': %d option rows for %d x %d candidates", NO, N, O);
+    VD_CHECK_ARG(b.h.present && b.q.present && b.h.N == N && N == B * R && b.h.T >= b.q.T,
+                 "vd_model_retrieve: VD_RETRIEVE_ROLLOUT = 1 needs the batch's history, Th >= Tq");
+    const long H = m->p.rnnHiddenSize;
+    hipStream_t s = m->s_main;
+    hipStream_t sd = side_stream(m, s);
+    float *scores, *loss_rows;
+    VD_TRY(ws_get(m, "opt.scores", (size_t)N * O, &scores));
+    VD_TRY(ws_get(m, "crit.loss_rows", (size_t)N, &loss_rows));
+    VD_TRY(fork_stream(m, s, sd));
+    OptStates os;
+    VD_TRY(option_states(m, b, &os));
+    float* enc_out = nullptr;
+    {
+      VdRange r("encoder forward");
+      VD_TRY(m->enc->forward(m, sd, b, &enc_out));
+    }
+    VD_TRY(join_stream(m, sd, s));
+    const float* optH;
+    VD_TRY(option_states_full(m, b, os, &optH));
+    for (int r = 0; r < R; ++r) {
+      if (r > 0) {                                                            // E5: rows 0 .. r of every dialog are final now
+        VdRange rr("encoder forward");
+        VD_TRY(m->enc->forward(m, s, b, &enc_out));
+      }
+      VD_TRY(vd_score_ce(optH, enc_out, b.gt, scores, loss_rows, nullptr, nullptr, N, O, (int)H, 1.0f / N, s));
+      if (r + 1 < R)                                                          // E2 - E4: the pick becomes history row r + 1
+        VD_TRY(vd_disc_rollout_pick_p(scores, O, b.opt.tok, NO, b.opt.T, b.opt_uid, b.q.tok, b.q.T, B, R, r, b.h.tok,
+                                      b.h.sorted ? b.h.tok_sorted : nullptr, b.h.sorted ? b.h.inv : nullptr, b.h.T, s));
+    }
+    VD_TRY(stage_loss(m, loss_rows, N, false, s));
+    m->scores = scores;
+    m->prof_valid = false;
+    return VD_OK;
+  }
 
   // Evaluation through the answer-encoding cache (OptionCache, rt_core.h): b.opt holds the rows the cache did not have at upload time
   // (possibly none) and b.opt_uid the table row of every candidate.  The state-only recurrence runs over those rows alone, their final h

@@ -29,7 +29,7 @@ namespace {
 // [N x T] dataloader rows -> time-major [T x N] on the device; with `sorted` also the length-sort metadata of
 // nn.py:SeqSort (stable sort by decreasing length, per-step active-row counts, gather indices)
 //
-// rollout_R > 0 (the history of a model created with VD_BEAM_ROLLOUT, R rounds per dialog): rows n with n % R != 0 will be REWRITTEN on
+// rollout_R > 0 (the history of a model created with VD_BEAM_ROLLOUT or VD_RETRIEVE_ROLLOUT, R rounds per dialog): rows n with n % R != 0 will be REWRITTEN on
 // the device between the passes of a rollout (beam.hip R2), so their length is not known here.  They are laid out at full width,
 // length T: by the paragraph below a row is skipped only BEFORE its claimed first token and masked per token inside its span, so a
 // claim that covers leading zeros is exact and only costs work.  The sort then puts them in front of the caption rows (n % R == 0),
@@ -410,9 +410,22 @@ int vd_model_create(const vd_model_params* p, const char* encoder, const char* d
                  "vd_model_create: VD_BEAM_ROLLOUT = 1 with VD_BEAM_GROUPS = %d: a rollout feeds ONE answer per round back, and the choice "
                  "among a round's groups is the host's", beam_groups);
   }
+  // rollout of vd_model_retrieve (include/visdial_hip.h there; beam.hip E1-E5): VD_RETRIEVE_ROLLOUT = 1 / 0 (0 / unset = off); anything else
+  // is refused, and so is 1 with VD_OPTION_CACHE.  Ignored for decoder gen, whose rollout is VD_BEAM_ROLLOUT.
+  bool retrieve_rollout = false;
+  if (std::string(decoder) == "disc") {
+    if (const char* e = getenv("VD_RETRIEVE_ROLLOUT")) {
+      VD_CHECK_ARG((e[0] == '0' || e[0] == '1') && !e[1], "vd_model_create: VD_RETRIEVE_ROLLOUT = '%s' must be 1 or 0 (0 = off)", e);
+      retrieve_rollout = e[0] == '1';
+    }
+    VD_CHECK_ARG(!retrieve_rollout || cache_rows == 0,
+                 "vd_model_create: VD_RETRIEVE_ROLLOUT = 1 with VD_OPTION_CACHE: a cached batch carries only the candidate rows the cache did "
+                 "not hold, and the rollout reads a picked candidate's tokens from the batch; combining the two is left for a follow-up");
+  }
   vd_model* m = new vd_model();
   m->p = *p;
   m->beam_rollout = beam_rollout;
+  m->retrieve_rollout = retrieve_rollout;
   m->sample_topk = sample_topk;
   m->sample_topp = sample_topp;
   m->beam_groups = beam_groups;
@@ -676,10 +689,13 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
   VD_TRY(upload_tokens(sl, sl.q, "q", hb->ques_fwd, N, hb->Tq, m->is_graph, s));
   // the history branch of the Sequential encoders runs as a length-sorted two-layer wavefront too (rt_encoders.h: HistWave)
   const bool hist_wave = !m->is_graph && m->p.numLayers == 2;
-  // VD_BEAM_ROLLOUT: history rows >= 1 at full width (upload_tokens), and a history row has to hold a whole question (beam.hip R2)
-  VD_CHECK_ARG(!(m->beam_rollout && m->use_hist) || hb->Th >= hb->Tq,
-               "vd_model_upload_batch: VD_BEAM_ROLLOUT = 1 needs a history width Th = %d >= the question width Tq = %d", hb->Th, hb->Tq);
-  if (m->use_hist) VD_TRY(upload_tokens(sl, sl.h, "h", hb->hist, N, hb->Th, m->is_graph || hist_wave, s, m->beam_rollout ? R : 0));
+  // VD_BEAM_ROLLOUT / VD_RETRIEVE_ROLLOUT: history rows >= 1 at full width (upload_tokens), and a history row has to hold a whole question
+  // (beam.hip R2)
+  const bool rollout = m->beam_rollout || m->retrieve_rollout;
+  VD_CHECK_ARG(!(rollout && m->use_hist) || hb->Th >= hb->Tq,
+               "vd_model_upload_batch: %s = 1 needs a history width Th = %d >= the question width Tq = %d",
+               m->beam_rollout ? "VD_BEAM_ROLLOUT" : "VD_RETRIEVE_ROLLOUT", hb->Th, hb->Tq);
+  if (m->use_hist) VD_TRY(upload_tokens(sl, sl.h, "h", hb->hist, N, hb->Th, m->is_graph || hist_wave, s, rollout ? R : 0));
   if (m->use_im) {
     // [B x S*S x C] for the attention encoders (model.lua:262-265 keeps one map per image), [B x F] otherwise
     const size_t img_n = (size_t)hb->B * (m->is_att ? (size_t)m->p.imgSpatialSize * m->p.imgSpatialSize : 1) * m->p.imgFeatureSize;

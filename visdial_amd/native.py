@@ -81,6 +81,8 @@ class NativeModel(SplitEval):
         # VD_BEAM_LENGTH_PENALTY), the same way again.
         # params beamRollout: vd_model_beam_search rolls the model's own answers into the history (VD_BEAM_ROLLOUT), the same way again;
         # generateAnswers(beamBatch > 0) checks its `rollout` against it.
+        # params retrieveRollout: vd_model_retrieve of decoder disc ranks every round on a history of the model's own picks
+        # (VD_RETRIEVE_ROLLOUT), the same way again; `retrieve_rollout_batch` is then one upload and one call.
         import os
         switches = {'VD_OPTION_CACHE': str(int(p.get('optionCache', 0) or 0)),
                     'VD_LHOOD_TREE': '1' if int(p.get('fusedLhood', 0) or 0) == 2 else '0',
@@ -91,7 +93,8 @@ class NativeModel(SplitEval):
                     'VD_BEAM_MIN_LEN': None if p.get('beamMinLen') is None else str(p['beamMinLen']),
                     'VD_BEAM_NO_REPEAT': None if p.get('beamNoRepeat') is None else str(p['beamNoRepeat']),
                     'VD_BEAM_LENGTH_PENALTY': None if p.get('beamLengthPenalty') is None else str(p['beamLengthPenalty']),
-                    'VD_BEAM_ROLLOUT': None if p.get('beamRollout') is None else str(p['beamRollout'])}
+                    'VD_BEAM_ROLLOUT': None if p.get('beamRollout') is None else str(p['beamRollout']),
+                    'VD_RETRIEVE_ROLLOUT': None if p.get('retrieveRollout') is None else str(p['retrieveRollout'])}
         prev = {k: os.environ.get(k) for k in switches}
         try:
             for k, v in switches.items():
@@ -112,6 +115,7 @@ class NativeModel(SplitEval):
         self._beam_limits = (int(p.get('beamMinLen') or 0), int(p.get('beamNoRepeat') or 0), float(p.get('beamLengthPenalty') or 0.0)) if gen \
             else (0, 0, 0.0)
         self._rollout_knob = int(p.get('beamRollout') or 0) if gen else 0
+        self._retrieve_rollout_knob = 0 if gen else int(p.get('retrieveRollout') or 0)
         self.h = h
         lib = _lib.load()
         self.tensors = []
@@ -334,6 +338,42 @@ class NativeModel(SplitEval):
         out = np.empty(N if useGt else (N, O), np.int32)
         call("vd_model_ranks", self.h, int(useGt), out.ctypes.data)
         return out
+
+    def retrieve_rollout_batch(self, batch):
+        """All ranks [N x O] of `batch` on a history the model wrote itself (split_eval.py E1-E5), the history at its untrimmed width.
+        decoder disc, a model created with params retrieveRollout = 1: ONE upload and ONE vd_model_retrieve, which runs the R passes on
+        the device.  decoder gen, a model created with params beamRollout = 1 and given params rolloutBeam = dict(beamSize, beamLen,
+        startToken, endToken): one upload, vd_model_encode, vd_model_beam_search -- which leaves the generated history in the batch's
+        slot -- and vd_model_retrieve (params fusedLhood: _lhood) on that slot.  Any other model: the host loop."""
+        self._rollout_answers = None
+        gen = self.params['decoder'] == 'gen'
+        if 'hist' not in batch or not (self._rollout_knob if gen else self._retrieve_rollout_knob):
+            return SplitEval.retrieve_rollout_batch(self, batch)
+        self.upload(batch)
+        N, O = self._N, int(self.params.get('numOptions', 100))
+        if gen:
+            beam = self.params.get('rolloutBeam')
+            if not beam:
+                raise ValueError("rollout = 1 with decoder 'gen' needs params rolloutBeam = dict(beamSize, beamLen, startToken, endToken)")
+            call("vd_model_encode", self.h)
+            self._rollout_answers = (self._gen_beam(beam['beamSize'], beam['beamLen'], beam['startToken'], beam['endToken'])[0],
+                                     int(beam['endToken']))
+        call("vd_model_retrieve_lhood" if int(self.params.get('fusedLhood', 0) or 0) else "vd_model_retrieve", self.h)
+        out = np.empty((N, O), np.int32)
+        call("vd_model_ranks", self.h, 0, out.ctypes.data)
+        return out
+
+    def rollout_history(self, batch, ranks):
+        if getattr(self, '_rollout_answers', None) is None:
+            return SplitEval.rollout_history(self, batch, ranks)
+        from .split_eval import rollout_history_row
+        tokens, end = self._rollout_answers                       # decoder gen: the beam search's answers (R2 / R3)
+        B, R, Th = batch['hist'].shape
+        hist = np.array(batch['hist'])
+        for i in range(B):
+            for r in range(R - 1):
+                hist[i, r + 1] = rollout_history_row(batch['ques_fwd'][i, r], tokens[i * R + r], Th, end)
+        return hist
 
     # Model:evaluate / retrieve / predict (model.lua:109-246): visdial_amd/split_eval.py, shared with the Python host
     def _set_training(self, on):

@@ -13,7 +13,8 @@ beamGroups = G > 1): `_beam_grouping(groups, diversity)` raises unless that `_ge
 returns every group's answer, (tokens [N x G x beamLen], scores [N x G]).  Beam constraints (params beamMinLen / beamNoRepeat /
 beamLengthPenalty): `_beam_constraints(minLen, noRepeat, lengthPenalty)` raises unless that `_gen_beam` searches under exactly these.
 Rollout (params rollout = 1): `_beam_rollout(rollout)` raises unless that `_gen_beam` feeds every round's answer into the next round's
-history on the device, R1-R6 below."""
+history on the device, R1-R6 below.  Ranking on a rollout (params rollout = 1 of retrieve / predict; evaluate.py -rollout 1): E1-E5 below
+and `retrieve_rollout_batch`, over the host's own `retrieveBatch`; a host with a device rollout overrides it."""
 import math
 
 import numpy as np
@@ -167,6 +168,49 @@ def rollout_history_row(ques_row, answer_row, Th, endToken):
     return out
 
 
+# Ranking on a rollout (csrc/beam.hip E1-E5; evaluate.py -rollout 1): the candidates of round r of a discriminative model are ranked on a
+# history that holds the model's own picks for the rounds before it.  O = numOptions, To = the width of an `options` row.
+#   E1. round 0's history row is the batch's (R1).
+#   E2. the answer chosen for round r is the candidate that the rank computation (vd_ranks) gives rank 1 among the round's O scores: the
+#       highest score, among equal scores the lowest index.
+#   E3. a candidate's words are entries 0, 1, ... of its `options` row [To] up to but excluding the first 0: the rows are left-aligned and
+#       hold neither <START> nor <END>; an all-zero row is an empty answer.
+#   E4. history row r + 1 is R2 of question row r and those words (the question whole, the first min(la, Th - lq) words, right-aligned).
+#   E5. R5 and R6 hold: round r is scored from a pass in which rows 0 .. r are final; the batch's rows >= 1 are ignored and overwritten.
+#       The pass after the last append scores every round as its own pass did (rows <= r are final after pass r, the encoders are causal).
+# For decoder gen the answer fed back is the beam search's (R4): an evaluation then describes the dialogs generate.py -rollout 1 writes.
+def rollout_candidate_row(option_row):
+    """E3: an `options` row [To] as the answer token row `rollout_history_row` takes, with endToken = 0: an entry in <START>'s place
+    (which is never a word), then the words up to the first 0"""
+    words = []
+    for t in np.asarray(option_row).reshape(-1):
+        if int(t) == 0:
+            break
+        words.append(int(t))
+    return np.array([0] + words + [0], np.int64)
+
+
+def rollout_pick(ranks_row):
+    """E2: the 0-based index of the candidate with rank 1 in one round's ranks [O] (a permutation of 1 .. O: ties went to the lower index
+    when the ranks were computed)"""
+    first = np.flatnonzero(np.asarray(ranks_row).reshape(-1) == 1)
+    if first.size != 1:
+        raise ValueError('rollout: %d candidates of a round have rank 1; the ranks of a round are a permutation of 1 .. O' % first.size)
+    return int(first[0])
+
+
+def rollout_picked_history(batch, picks):
+    """E1 / E4: the history [B x R x Th] of `batch` (ques_fwd [B x R x Tq], hist [B x R x Th], options [B * R x O x To]) when round r of
+    every dialog was answered with candidate picks[dialog * R + r]: row 0 is the batch's, rows >= 1 are rebuilt"""
+    B, R, Th = batch['hist'].shape
+    hist = np.array(batch['hist'])
+    for i in range(B):
+        for r in range(R - 1):
+            cand = batch['options'][i * R + r, int(picks[i * R + r])]
+            hist[i, r + 1] = rollout_history_row(batch['ques_fwd'][i, r], rollout_candidate_row(cand), Th, 0)
+    return hist
+
+
 def beam_search_round(step_fn, select_fn, k, L, start, end, groups=1, diversity=0.5, minLen=0, noRepeat=0, lengthPenalty=0.0):
     """The beam search of ONE round on the host (model.lua:466-573): `step_fn(tokens [k]) -> logp [k x V]` is one decoder step of the k
     slots (a slot whose token is 0 gets an all-zero row), `select_fn(src, n_keep)` makes slot i < n_keep continue from the stepped
@@ -257,9 +301,78 @@ class SplitEval(object):
     # of the batches, summed over the last retrieve / predict
     lhoodTreeStats = dict(nodes=0, live=0, executed=0, total=0)
 
-    def _ranked(self, batch, tally):
-        """retrieveBatch + the tally of the answer-encoding cache (params optionCache; decoder disc)"""
-        ranks = np.asarray(self.retrieveBatch(batch))
+    rolloutRows = (0, 0)         # params rollout: (history rows that differ from the ground truth's, history rows) of the last retrieve / predict
+
+    def _rollout(self):
+        """params rollout (0 / 1) of retrieve / predict, refusing what cannot be ranked on a rollout"""
+        rollout = int(self.params.get('rollout', 0) or 0)
+        if rollout not in (0, 1):
+            raise ValueError('rollout = %r must be 0 or 1' % (self.params.get('rollout'),))
+        if rollout and int(self.params.get('optionCache', 0) or 0):
+            raise ValueError('rollout = 1 with optionCache: a cached batch carries only the candidates the cache did not hold, and the '
+                             'rollout reads a picked candidate\'s tokens from the batch; combining the two is left for a follow-up')
+        if rollout and self.params.get('concatHistory') and self.params.get('useHistory'):
+            raise ValueError("rollout = 1 with encoder '%s' (concatHistory): its history row is the running concatenation of the rounds, "
+                             "and E4 describes the per-round row only; a concatenation rule is left for a follow-up"
+                             % self.params.get('encoder'))
+        return rollout
+
+    def _all_ranks(self, batch):
+        """the host's own retrieval of every candidate's rank, [N x O], whatever params useGt says"""
+        keep = self.params.get('useGt')
+        self.params['useGt'] = False
+        try:
+            ranks = np.asarray(self.retrieveBatch(batch))
+        finally:
+            self.params['useGt'] = keep
+        return ranks.reshape(batch['ques_fwd'].shape[0] * batch['ques_fwd'].shape[1], -1)
+
+    def retrieve_rollout_batch(self, batch):
+        """E1-E5 on the host, the obviously-right path (like beamBatch = 0): R retrievals of the whole batch; before call r + 1 history row
+        r + 1 of every dialog is rewritten IN `batch` from the rank-1 candidate of round r in call r (E2 - E4); round r's ranks are those
+        of call r.  `batch` carries `options` (decoder disc) and the history at its untrimmed width.  Returns all ranks [N x O]; a batch
+        without a history is ranked once, as ever."""
+        if 'hist' not in batch:
+            return self._all_ranks(batch)
+        if 'options' not in batch:
+            raise ValueError("rollout = 1 on this host ranks the candidates of decoder 'disc'; for decoder 'gen' the rollout is the beam "
+                             "search's and runs in the model-level runtime: use -host native (visdial_amd.native.NativeModel)")
+        B, R, Th = batch['hist'].shape
+        out = None
+        for r in range(R):
+            ranks = self._all_ranks(batch)
+            out = np.array(ranks) if out is None else out
+            out[r::R] = ranks[r::R]
+            if r + 1 < R:
+                for i in range(B):
+                    cand = batch['options'][i * R + r, rollout_pick(ranks[i * R + r])]
+                    batch['hist'][i, r + 1] = rollout_history_row(batch['ques_fwd'][i, r], rollout_candidate_row(cand), Th, 0)
+        return out
+
+    def _test_batch(self, dataloader, start, dtype, rollout):
+        """`getTestBatch`; under a rollout with the history at its UNTRIMMED width (as `rollout_batch`) and a copy of the ground truth's"""
+        batch, nxt = dataloader.getTestBatch(start, self.params, dtype)
+        if rollout and 'hist' in batch:
+            data = getattr(dataloader, 'data', None)
+            if data is not None:
+                batch['hist'] = np.ascontiguousarray(data[dtype]['hist'][start - 1:nxt - 1]).astype(np.int32)
+            batch['hist'] = np.array(batch['hist'])
+            batch['hist_gt'] = np.array(batch['hist'])
+        return batch, nxt
+
+    def _ranked(self, batch, tally, rollout=0):
+        """retrieveBatch + the tally of the answer-encoding cache (params optionCache; decoder disc).  rollout: `retrieve_rollout_batch`,
+        the ground-truth ranks taken from all ranks if params useGt, + the tally of the history rows that differ from the ground truth's"""
+        if rollout:
+            truth = batch.pop('hist_gt', None)
+            ranks = np.asarray(self.retrieve_rollout_batch(batch))
+            if truth is not None:
+                hist = self.rollout_history(batch, ranks)
+                tally += [0] * (8 - len(tally))
+                tally[6] += int((hist != truth).any(2).sum())
+                tally[7] += hist.shape[0] * hist.shape[1]
+        else:
+            ranks = np.asarray(self.retrieveBatch(batch))
         if int(self.params.get('fusedLhood', 0) or 0) == 2:
             from . import prefix_tree
             st = prefix_tree.stats(batch['option_in'])
@@ -271,7 +384,13 @@ class SplitEval(object):
             ex, tot = self.option_rows()
             tally[0] += ex
             tally[1] += tot
+        if rollout and self.params.get('useGt'):
+            ranks = ranks[np.arange(ranks.shape[0]), np.asarray(batch['answer_ind']).reshape(-1) - 1]
         return ranks
+
+    def rollout_history(self, batch, ranks):
+        """the history [B x R x Th] a rollout of `batch` generated, given the all ranks [N x O] it returned: rebuilt from the picks (E4)"""
+        return rollout_picked_history(batch, [rollout_pick(row) for row in ranks])
 
     def evaluate(self, dataloader, dtype):
         """model.lua:109-139: validation loss / perplexity over a split: the sum over batches of `forwardBackward(batch, true)` (gen:
@@ -315,40 +434,43 @@ class SplitEval(object):
         return out
 
     def retrieve(self, dataloader, dtype):
-        """model.lua:142-189: ground-truth ranks + metrics.  Returns (metrics, records)."""
+        """model.lua:142-189: ground-truth ranks + metrics.  params rollout = 1: the same on a history of the model's own answers
+        (`retrieve_rollout_batch`, E1-E5 above); `rolloutRows` then counts the history rows that differ.  Returns (metrics, records)."""
         self._set_training(False)
         self.params['useGt'] = True
         n = dataloader.numThreads[dtype]
         R = int(self.params['maxQuesCount'])
         O = int(self.params.get('numOptions', 100))
         ranks = np.full((n, R), O + 1.0)                               # model.lua:153-154
-        start, tally = 1, [0, 0]
+        start, tally, rollout = 1, [0, 0], self._rollout()
         while start <= n:
-            batch, nxt = dataloader.getTestBatch(start, self.params, dtype)
-            ranks[start - 1:nxt - 1] = self._ranked(batch, tally).reshape(-1, R)
+            batch, nxt = self._test_batch(dataloader, start, dtype, rollout)
+            ranks[start - 1:nxt - 1] = self._ranked(batch, tally, rollout).reshape(-1, R)
             start = nxt
         self.optionCacheRows = tuple(tally[:2])
         self.lhoodTreeStats = dict(zip(('nodes', 'live', 'executed', 'total'), (tally + [0] * 4)[2:6]))
+        self.rolloutRows = tuple((tally + [0] * 6)[6:8])
         print('\n%s - Retrieval:' % dtype)
         metrics = utils.processRanks(ranks)
         self._set_training(True)
         return metrics, self._rank_records(dataloader, dtype, ranks, False)
 
     def predict(self, dataloader, dtype):
-        """model.lua:192-246: all 100 ranks per round (val: every existing round; test: the last round only)."""
+        """model.lua:192-246: all 100 ranks per round (val: every existing round; test: the last round only); params rollout as retrieve"""
         self._set_training(False)
         self.params['useGt'] = False
         n = dataloader.numThreads[dtype]
         R = int(self.params['maxQuesCount'])
         O = int(self.params.get('numOptions', 100))
         ranks = np.full((n, R, O), O + 1.0)
-        start, tally = 1, [0, 0]
+        start, tally, rollout = 1, [0, 0], self._rollout()
         while start <= n:
-            batch, nxt = dataloader.getTestBatch(start, self.params, dtype)
-            ranks[start - 1:nxt - 1] = self._ranked(batch, tally).reshape(-1, R, O)
+            batch, nxt = self._test_batch(dataloader, start, dtype, rollout)
+            ranks[start - 1:nxt - 1] = self._ranked(batch, tally, rollout).reshape(-1, R, O)
             start = nxt
         self.optionCacheRows = tuple(tally[:2])
         self.lhoodTreeStats = dict(zip(('nodes', 'live', 'executed', 'total'), (tally + [0] * 4)[2:6]))
+        self.rolloutRows = tuple((tally + [0] * 6)[6:8])
         self._set_training(True)
         return self._rank_records(dataloader, dtype, ranks, dtype == 'test')
 
