@@ -48,7 +48,16 @@ def parse_args(argv=None):
     ap.add_argument('-minLen', '--minLen', type=int, default=0, help='-rollout 1, gen decoder: as generate.py')
     ap.add_argument('-noRepeatNgram', '--noRepeatNgram', type=int, default=0)
     ap.add_argument('-lengthPenalty', '--lengthPenalty', type=float, default=0.0)
-    return ap.parse_args(argv)
+    ap.add_argument('-rolloutEncoder', '--rolloutEncoder', default='full', choices=['full', 'round'],
+                    help='-rollout 1 -host native: round = passes 1 .. R - 1 of the device rollout encode the round they rank alone instead '
+                         'of the whole batch again (csrc/rt_encoders.h forward_round; for gen: the beam-search rollout); same records')
+    a = ap.parse_args(argv)
+    if a.rolloutEncoder == 'round':
+        if not a.rollout:
+            raise SystemExit('-rolloutEncoder round encodes the later passes of a rollout one round at a time: it needs -rollout 1')
+        if a.host != 'native':
+            raise SystemExit('-rolloutEncoder round with -host python: the round pass runs in the model-level runtime only: use -host native')
+    return a
 
 
 def check_rollout(a, p):
@@ -82,6 +91,7 @@ def main(argv=None):
     p['optionCache'] = a.optionCache
     check_rollout(a, p)
     p['rollout'] = a.rollout
+    p['rolloutEncoder'] = a.rolloutEncoder
     p.update(inputImg=a.inputImg, inputQues=a.inputQues, inputJson=a.inputJson)
     have = lambda f: os.path.exists(f) or os.path.exists(f[:-3] + '.npz')
     if os.path.exists(a.inputJson) and have(a.inputQues):

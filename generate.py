@@ -18,7 +18,8 @@ from visdial_amd.split_eval import check_beam_constraints, check_beam_groups
 def parse_args(argv=None):
     """the command line as the `opts` of the results file; refuses top-k / nucleus truncation without -sampleWords 1 and beam groups
     that do not divide -beamSize, with a bad -beamDiversity or with -sampleWords 1, and a bad -minLen / -noRepeatNgram / -lengthPenalty
-    or one of them with -sampleWords 1, and -rollout 1 with -sampleWords 1 or -beamGroups > 1"""
+    or one of them with -sampleWords 1, -rollout 1 with -sampleWords 1 or -beamGroups > 1, and -rolloutEncoder round without -rollout 1
+    -beamBatch N -host native"""
     ap = argparse.ArgumentParser(description='Test the VisDial model for generation')
     ap.add_argument('-inputImg', '--inputImg', default='data/data_img.h5')
     ap.add_argument('-inputQues', '--inputQues', default='data/visdial_data.h5')
@@ -53,6 +54,9 @@ def parse_args(argv=None):
     ap.add_argument('-rollout', '--rollout', type=int, default=0, choices=[0, 1],
                     help='1: beam search answers every round on a history of its OWN answers to the rounds before it, not the ground '
                          'truth\'s (csrc/beam.hip R1-R6; with -beamBatch N it needs -host native; 0 = off)')
+    ap.add_argument('-rolloutEncoder', '--rolloutEncoder', default='full', choices=['full', 'round'],
+                    help='-rollout 1 -beamBatch N -host native: round = passes 1 .. R - 1 encode the round they answer alone instead of '
+                         'the whole chunk again (csrc/rt_encoders.h forward_round); same records')
     ap.add_argument('-seed', '--seed', type=int, default=1234, help='seed of the sampling generator (numpy RandomState)')
     ap.add_argument('-gpuid', '--gpuid', type=int, default=0)
     ap.add_argument('-host', '--host', default='python', choices=['python', 'native'],
@@ -73,6 +77,14 @@ def parse_args(argv=None):
     if a['rollout'] == 1 and a['beamGroups'] > 1:
         raise ValueError('-rollout 1 with -beamGroups %d: the choice among a round\'s groups is made on the host; a rollout over diverse beam '
                          'search is left for a follow-up' % a['beamGroups'])
+    if a['rolloutEncoder'] == 'round':
+        if a['rollout'] != 1:
+            raise ValueError('-rolloutEncoder round encodes the later passes of a rollout one round at a time: it needs -rollout 1')
+        if a['beamBatch'] <= 0:
+            raise ValueError('-rolloutEncoder round belongs to the device rollout: it needs -beamBatch N (> 0); with -beamBatch 0 the host '
+                             'encodes once per round and dialog')
+        if a['host'] != 'native':
+            raise ValueError('-rolloutEncoder round with -host python: the round pass runs in the model-level runtime only: use -host native')
     return a
 
 
@@ -93,7 +105,7 @@ def main():
         # the device sampler takes its truncation, the device search its groups and constraints, at creation
         model = NativeModel(dict(p, topK=a['topK'], topP=a['topP'], beamGroups=a['beamGroups'], beamDiversity=a['beamDiversity'],
                                  beamMinLen=a['minLen'], beamNoRepeat=a['noRepeatNgram'], beamLengthPenalty=a['lengthPenalty'],
-                                 beamRollout=a['rollout']))
+                                 beamRollout=a['rollout'], rolloutEncoder=a['rolloutEncoder']))
     else:
         model = Model(p)
     restore_weights(model, saved, a['paramOrder'] or None)

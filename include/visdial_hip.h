@@ -366,7 +366,14 @@ typedef struct vd_batch {          /* HOST pointers, dataloader layout (dataload
   const int32_t* option_in;        /* [B*R x O x To] <START>+tokens                 (decoder gen, retrieval) */
   const int32_t* option_out;       /* [B*R x O x To] tokens+<END> */
 } vd_batch;
-/* Model:__init (model.lua:10-63): parameter vectors (zeroed), optimiser state, streams */
+/* Model:__init (model.lua:10-63): parameter vectors (zeroed), optimiser state, streams.
+ * Reads the opt-in switches of the calls below from the environment, once (each is described at its call).  One of them belongs to both
+ * rollouts: VD_ROLLOUT_ENCODER = full | round (unset = full; any other value is refused by name).  With `round`, passes 1 .. R - 1 of
+ * vd_model_retrieve under VD_RETRIEVE_ROLLOUT = 1 and of vd_model_beam_search under VD_BEAM_ROLLOUT = 1 encode only the round they rank /
+ * answer -- history row r of every dialog through the history branch at B rows, then the B rows of the encoder's head on the state the
+ * first pass left -- instead of all B * R rounds again: the same picks, answers and ranks, scores within fp32 rounding of the full pass
+ * (a product over B rows may take another tile than over B * R).  Ignored where nothing rolls out (neither rollout variable set, or an
+ * encoder without a history); with training on, both calls refuse it by name. */
 int vd_model_create(const vd_model_params* p, const char* encoder, const char* decoder, vd_model** out);
 void vd_model_destroy(vd_model* m);
 /* wrapper:getParameters() (model.lua:55): flat layout = embed | encoder tensors | decoder tensors, every tensor

@@ -39,6 +39,8 @@ ap.add_argument('--minLen', type=int, default=0, help='--mode beam: no answer of
 ap.add_argument('--noRepeatNgram', type=int, default=0, help='--mode beam: no n-gram of that many words twice in a hypothesis (0 = off)')
 ap.add_argument('--lengthPenalty', type=float, default=0.0, help='--mode beam: finished hypotheses compete on score / length^that (0 = off)')
 ap.add_argument('--rollout', type=int, default=0, choices=(0, 1), help='--mode beam: answer on the generated history (0 = off)')
+ap.add_argument('--rolloutEncoder', default='full', choices=('full', 'round'),
+                help='--rollout 1: round = passes 1 .. R - 1 encode the round they answer alone (VD_ROLLOUT_ENCODER)')
 ap.add_argument('--vocabScale', type=float, default=1.0, help='multiply vocab.W of the random model (peaked rows)')
 opt = ap.parse_args()
 MODE_KNOBS = opt.topK != 0 or opt.topP != 1.0
@@ -53,6 +55,8 @@ if LIMITS and opt.mode != 'beam':
     ap.error('--minLen / --noRepeatNgram / --lengthPenalty belong to beam search: use --mode beam')
 if opt.rollout and (opt.mode != 'beam' or GROUPS != 1):
     ap.error('--rollout 1 belongs to beam search without groups: use --mode beam --beamGroups 1')
+if opt.rolloutEncoder == 'round' and not opt.rollout:
+    ap.error('--rolloutEncoder round belongs to a rollout: use --rollout 1')
 MODE, D, ONLY_BATCHED = opt.mode, opt.dialogs, opt.only == 'batched'
 V, R = 11322, 10
 
@@ -90,7 +94,7 @@ if GROUPS != 1:
     knobs.update(beamGroups=GROUPS, beamDiversity=opt.beamDiversity)
 knobs.update(LIMITS)
 if opt.rollout:
-    knobs.update(beamRollout=1)
+    knobs.update(beamRollout=1, rolloutEncoder=opt.rolloutEncoder)
 nat = NativeModel(dict(p, **knobs), init_seed=1)
 nat.training(False)
 if opt.vocabScale != 1.0:
@@ -108,7 +112,7 @@ if MODE == 'beam':
         what += ' (minLen %d, noRepeatNgram %d, lengthPenalty %g)' % (opt.minLen, opt.noRepeatNgram, opt.lengthPenalty)
     if opt.rollout:
         cfg.update(rollout=1)
-        what += ', rollout'
+        what += ', rollout (encoder: %s)' % opt.rolloutEncoder
 else:
     key, cfg = 'sampleBatch', dict(sampleWords=1, beamLen=20, temperature=1.0, maxThreads=D, seed=1234, topK=opt.topK, topP=opt.topP)
     what = 'sampling' + (' (topK %d, topP %g)' % (opt.topK, opt.topP) if MODE_KNOBS else '')

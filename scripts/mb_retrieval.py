@@ -28,7 +28,9 @@ own candidates: per batch (upload + retrieve + ranks, as evaluate.py runs it) th
 created without VD_RETRIEVE_ROLLOUT), the device rollout (one upload + one vd_model_retrieve on a model created with it) and the host loop
 (R uploads + retrievals, --host-batches of the batches), alternated.  The device rollout's time over the plain retrieval's is what the
 R - 1 further encoder passes, scorings and picks cost: the option recurrence runs once in both.  --cases plain runs the first alone (the
-parent commit's library through VD_LIB_PATH knows no rollout), --cases device the second (for a kernel trace).
+parent commit's library through VD_LIB_PATH knows no rollout), --cases device the second (for a kernel trace).  --rolloutEncoder round creates
+the device rollout's model with VD_ROLLOUT_ENCODER = round (passes 1 .. R - 1 encode the round they rank alone); both adds that model as a
+fourth path `round` beside `device`, alternated with it.
 --mode step: the option recurrence alone (vd_lstm_forward, table mode, 20 000 x 512, 20 steps), saving against VD_FLAG_STATE_ONLY,
 alternated, device time by events."""
 import argparse
@@ -56,6 +58,8 @@ ap.add_argument('--pool', type=int, default=2000, help='--mode disc: distinct an
 ap.add_argument('--batches', type=int, default=6, help='--mode disc: batches per pass')
 ap.add_argument('--cases', choices=('all', 'uncached', 'cached', 'plain', 'device'), default='all', help='--mode disc')
 ap.add_argument('--rollout', type=int, choices=(0, 1), default=0, help='--mode disc: ranking on a rollout, three paths (see above)')
+ap.add_argument('--rolloutEncoder', choices=('full', 'round', 'both'), default='full',
+                help='--mode disc --rollout 1: the encoder of the device rollout\'s later passes; both = the two as separate paths')
 ap.add_argument('--host-batches', type=int, default=2, help='--mode disc --rollout 1: batches the host loop ranks per pass')
 opt = ap.parse_args()
 
@@ -144,13 +148,18 @@ def disc_rollout_mode():
     print("%smn-att-ques-im-hist + disc, H %d, %d dialogs x %d rounds x %d options, To %d, Th %d, Tq %d, split9, native host, random weights, "
           "%d batches per pass" % (tag, H, B, R, O, To, batches[0]['hist'].shape[2], batches[0]['ques_fwd'].shape[2], opt.batches), flush=True)
     want = {'all': ('plain', 'device', 'host'), 'plain': ('plain',), 'device': ('device',)}[opt.cases]
-    plain = roll = None
+    if opt.rolloutEncoder == 'both' and 'device' in want:
+        want = want + ('round',)
+    plain = roll = rnd = None
     if 'plain' in want or 'host' in want:
         plain = NativeModel(dict(p), init_seed=1)
         plain.training(False)
     if 'device' in want:
-        roll = NativeModel(dict(p, retrieveRollout=1), init_seed=1)
+        roll = NativeModel(dict(p, retrieveRollout=1, rolloutEncoder='round' if opt.rolloutEncoder == 'round' else 'full'), init_seed=1)
         roll.training(False)
+    if 'round' in want:
+        rnd = NativeModel(dict(p, retrieveRollout=1, rolloutEncoder='round'), init_seed=1)
+        rnd.training(False)
 
     def one_pass(case):
         bs = batches[:opt.host_batches] if case == 'host' else batches
@@ -160,6 +169,8 @@ def disc_rollout_mode():
                 out = plain.retrieveBatch(b, useGt=False)
             elif case == 'device':
                 out = roll.retrieve_rollout_batch(b)
+            elif case == 'round':
+                out = rnd.retrieve_rollout_batch(b)
             else:
                 out = SplitEval.retrieve_rollout_batch(plain, dict(b, hist=np.array(b['hist'])))
         return (time.perf_counter() - t0) / len(bs), out
@@ -179,6 +190,10 @@ def disc_rollout_mode():
     if 'device' in last and 'host' in last:
         same = np.array_equal(roll.retrieve_rollout_batch(batches[opt.host_batches - 1]), last['host'])
         print("  device rollout and host loop return the same ranks for batch %d: %s" % (opt.host_batches - 1, same))
+    if 'device' in last and 'round' in last:
+        d, q = np.median(times['device']), np.median(times['round'])
+        print("  round against full: %.2fx (%.2f ms per batch less); the same ranks for the last batch: %s"
+              % (d / q, (d - q) * 1e3, np.array_equal(last['device'], last['round'])))
     if 'device' in times and 'plain' in times:
         d, q = np.median(times['device']), np.median(times['plain'])
         print("  the R - 1 further encoder passes, scorings and picks: %.2f ms per batch = %.0f %% of the device rollout's batch"
@@ -187,7 +202,7 @@ def disc_rollout_mode():
         first = lambda r: np.asarray(r).reshape(B * R, O).argmin(1)
         print("  rounds of the last batch whose rank-1 candidate differs between the rollout and the ground-truth history: %d of %d"
               % (int((first(last['device']) != first(last['plain'])).sum()), B * R))
-    for m in (plain, roll):
+    for m in (plain, roll, rnd):
         if m is not None:
             m.close()
 

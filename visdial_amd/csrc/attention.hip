@@ -772,3 +772,187 @@ int vd_img_common_wgrad_p(const float* dz, const float* pre, const uint8_t* mask
   EpiAtomic<4> e{dWc, H};
   return launch_gemm<CfgBig>(Kc, H, (int)(K - K1), 1, a, b, e, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// One round of a rollout (VD_ROLLOUT_ENCODER = round; rt_encoders.h forward_round).  After pass r - 1 only history row r of every dialog
+// has changed, so the encoder output of round r needs row (d, r) of each attention alone.  The two kernels below compute that row with
+// the arithmetic of the full kernels above -- the same per-lane product order and wave reduction of a score, the same max / exp / sum /
+// scale of the softmax over j in ascending order, the same j-ascending weighted sum -- so for identical inputs row (d, r) equals the
+// full kernel's bit for bit: what the full kernel adds for the masked j > r are exact zeros (exp(-9999999 - max) and exp(-inf)
+// underflow to +0).  One workgroup per dialog, B workgroups: the pass is launch-bound, not throughput-bound.
+// ---------------------------------------------------------------------------------------------------------------------------------------
+#define MN_ROUND_THREADS 256
+// Q: the query of dialog d is row d of [B x q_ld] (q_ld = R * H reads round r of a per-round tensor in place: the gather is this load).
+// Hm [B*R x H]: facts (d, 0 .. r).  hAtt [B x H]; Qout [B x H] or null: the staged query, compact; P [B x R] or null.
+__global__ void __launch_bounds__(MN_ROUND_THREADS)
+mn_att_round_kernel(const float* __restrict__ Q, long q_ld, const float* __restrict__ Hm, float* __restrict__ P, float* __restrict__ hAtt,
+                    float* __restrict__ Qout, int R, int r, int H) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // q [H] | h [(r + 1) * H]
+  __shared__ float S[MN_MAX_R];
+  float* q = lds;
+  float* h = lds + H;
+  const int d = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = MN_ROUND_THREADS / 64;
+  const int nf = r + 1;
+  for (int i = tid * 4; i < H; i += MN_ROUND_THREADS * 4) {
+    const float4 v = *reinterpret_cast<const float4*>(Q + (long)d * q_ld + i);
+    *reinterpret_cast<float4*>(q + i) = v;
+    if (Qout) *reinterpret_cast<float4*>(Qout + (long)d * H + i) = v;
+  }
+  for (int i = tid * 4; i < nf * H; i += MN_ROUND_THREADS * 4)
+    *reinterpret_cast<float4*>(h + i) = *reinterpret_cast<const float4*>(Hm + (long)d * R * H + i);
+  __syncthreads();
+  for (int j = wave; j < nf; j += nw) {
+    float s = 0.f;
+    for (int k = lane; k < H; k += 64) s += q[k] * h[j * H + k];
+    s = wave_sum(s);
+    if (lane == 0) S[j] = s;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float mx = -INFINITY;
+    for (int j = 0; j < nf; ++j) mx = fmaxf(mx, S[j]);
+    float sum = 0.f;
+    for (int j = 0; j < nf; ++j) {
+      const float e = expf(S[j] - mx);
+      S[j] = e;
+      sum += e;
+    }
+    const float inv = 1.f / sum;
+    for (int j = 0; j < R; ++j) {
+      const float pv = j < nf ? S[j] * inv : 0.f;
+      if (j < nf) S[j] = pv;
+      if (P) P[(long)d * R + j] = pv;
+    }
+  }
+  __syncthreads();
+  for (int k = tid; k < H; k += MN_ROUND_THREADS) {
+    float a = 0.f;
+    for (int j = 0; j < nf; ++j) a += S[j] * h[j * H + k];
+    hAtt[(long)d * H + k] = a;
+  }
+}
+
+// sq / sh [B*R], Hm [B*R x H]; att [B x H]; P [B x R] or null.  Every fact element is read once, so nothing is staged.
+__global__ void __launch_bounds__(256)
+hrea_att_round_kernel(const float* __restrict__ sq, const float* __restrict__ sh, const float* __restrict__ Hm, float* __restrict__ P,
+                      float* __restrict__ att, int R, int r, int H) {
+  __shared__ float S[MN_MAX_R];
+  const int d = blockIdx.x, tid = threadIdx.x;
+  const float* h = Hm + (long)d * R * H;
+  const int nf = r + 1;
+  if (tid == 0) {
+    float mx = -INFINITY;
+    for (int j = 0; j < nf; ++j) {
+      float v = sq[d * R + r] + sh[d * R + j];
+      v = (v == 0.f) ? -INFINITY : v;
+      S[j] = v;
+      mx = fmaxf(mx, v);
+    }
+    float sum = 0.f;
+    for (int j = 0; j < nf; ++j) {
+      const float e = expf(S[j] - mx);
+      S[j] = e;
+      sum += e;
+    }
+    const float inv = 1.f / sum;
+    for (int j = 0; j < R; ++j) {
+      const float pv = j < nf ? S[j] * inv : 0.f;
+      if (j < nf) S[j] = pv;
+      if (P) P[(long)d * R + j] = pv;
+    }
+  }
+  __syncthreads();
+  for (int k = tid; k < H; k += 256) {
+    float a = 0.f;
+    for (int j = 0; j < nf; ++j) a += S[j] * h[j * H + k];
+    att[(long)d * H + k] = a;
+  }
+}
+
+// History row r of every dialog as a B-row sequence: tok_r [T x B] = tok[t, d * R + r] (tok step-major [T x N], N = B * R), and its
+// embedding rows x [T*B x E].  One thread per float4 of x; the thread of a row's first quad also stores the token.
+__global__ void __launch_bounds__(256)
+round_embed_kernel(const float* __restrict__ emb, const int32_t* __restrict__ tok, int32_t* __restrict__ tok_r, float* __restrict__ x, long rows,
+                   int B, int N, int R, int r, int E) {
+  const int e4 = E >> 2;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= rows * e4) return;
+  const long row = idx / e4;                     // t * B + d
+  const int qd = (int)(idx - row * e4);
+  const long t = row / B;
+  const int d = (int)(row - t * B);
+  const int32_t v = tok[t * N + (long)d * R + r];
+  if (qd == 0) tok_r[row] = v;
+  *reinterpret_cast<float4*>(x + row * E + qd * 4) = *reinterpret_cast<const float4*>(emb + (long)v * E + qd * 4);
+}
+
+// dst [rows x D] (leading dimension dst_ld) = the column blocks src[i] [rows x cols[i]] (leading dimension ld[i]) side by side: one part
+// with a strided source gathers the rows of a round, with a strided destination it scatters them back; several parts are nn.JoinTable.
+struct VdRowParts {
+  const float* src[3];
+  long ld[3];
+  int cols[3];
+  int n;
+};
+__global__ void __launch_bounds__(256) rows_cat_kernel(VdRowParts p, float* __restrict__ dst, long dst_ld, long rows, int D) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= rows * D) return;
+  const long row = idx / D;
+  int c = (int)(idx - row * D);
+  const int cd = c;
+  int i = 0;
+  while (i + 1 < p.n && c >= p.cols[i]) c -= p.cols[i++];
+  dst[row * dst_ld + cd] = p.src[i][row * p.ld[i] + c];
+}
+
+int vd_mn_attention_round_p(const float* Q, int64_t q_ld, const float* Hm, float* P, float* hAtt, float* Qout, int B, int R, int r, int H,
+                            hipStream_t stream) {
+  VD_CHECK_ARG(Q && Hm && hAtt && B >= 0 && R >= 1 && R <= MN_MAX_R && r >= 0 && r < R && H > 0 && H % 4 == 0 && q_ld >= H && q_ld % 4 == 0,
+               "vd_mn_attention_round: bad args (R=%d must be <= %d, 0 <= r=%d < R, H %% 4 == 0)", R, MN_MAX_R, r);
+  if (B == 0) return VD_OK;
+  const size_t lds = (size_t)(r + 2) * H * sizeof(float);
+  VD_CHECK_ARG(lds <= 64 * 1024, "vd_mn_attention_round: (r + 2) * H = %d does not fit the LDS staging", (r + 2) * H);
+  hipLaunchKernelGGL(mn_att_round_kernel, dim3(B), dim3(MN_ROUND_THREADS), lds, stream, Q, (long)q_ld, Hm, P, hAtt, Qout, R, r, H);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+int vd_hrea_attention_round_p(const float* sq, const float* sh, const float* Hm, float* P, float* att, int B, int R, int r, int H,
+                              hipStream_t stream) {
+  VD_CHECK_ARG(sq && sh && Hm && att && B >= 0 && R >= 1 && R <= MN_MAX_R && r >= 0 && r < R && H > 0,
+               "vd_hrea_attention_round: bad args (R=%d must be <= %d, 0 <= r=%d < R)", R, MN_MAX_R, r);
+  if (B == 0) return VD_OK;
+  hipLaunchKernelGGL(hrea_att_round_kernel, dim3(B), dim3(256), 0, stream, sq, sh, Hm, P, att, R, r, H);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+int vd_round_embed_p(const float* emb, const int32_t* tok, int T, int N, int R, int r, int32_t* tok_r, float* x, int E, hipStream_t stream) {
+  VD_CHECK_ARG(emb && tok && tok_r && x && T >= 0 && R >= 1 && N >= 0 && N % R == 0 && r >= 0 && r < R && E > 0 && E % 4 == 0,
+               "vd_round_embed: bad args (N=%d rows in rounds of R=%d, r=%d, E=%d)", N, R, r, E);
+  const int B = N / R;
+  const long rows = (long)T * B;
+  if (rows == 0) return VD_OK;
+  hipLaunchKernelGGL(round_embed_kernel, dim3((unsigned)((rows * (E / 4) + 255) / 256)), dim3(256), 0, stream, emb, tok, tok_r, x, rows, B, N,
+                     R, r, E);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+int vd_rows_cat_p(float* dst, int64_t dst_ld, const float* const* src, const int64_t* ld, const int* cols, int nparts, int64_t rows,
+                  hipStream_t stream) {
+  VD_CHECK_ARG(dst && src && ld && cols && nparts >= 1 && nparts <= 3 && rows >= 0, "vd_rows_cat: bad args (%d parts, at most 3)", nparts);
+  VdRowParts p{};
+  long D = 0;
+  for (int i = 0; i < nparts; ++i) {
+    VD_CHECK_ARG(src[i] && cols[i] >= 1 && ld[i] >= cols[i], "vd_rows_cat: part %d", i);
+    p.src[i] = src[i]; p.ld[i] = (long)ld[i]; p.cols[i] = cols[i];
+    D += cols[i];
+  }
+  p.n = nparts;
+  VD_CHECK_ARG(dst_ld >= D && D <= INT32_MAX, "vd_rows_cat: leading dimension %lld below the %ld joined columns", (long long)dst_ld, D);
+  if (rows == 0) return VD_OK;
+  hipLaunchKernelGGL(rows_cat_kernel, dim3((unsigned)((rows * D + 255) / 256)), dim3(256), 0, stream, p, dst, (long)dst_ld, (long)rows, (int)D);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}

@@ -37,6 +37,21 @@ int vd_img_tr_backward_p(const float* dz, const float* Wc, const float* p, const
 int vd_img_common_wgrad_p(const float* dz, const float* pre, const uint8_t* mask1, const float* xdrop, float* dWc, int N, int R, int S2, int H,
                           int Kc, float scale, int flags, hipStream_t stream);
 
+// attention.hip: one round of a rollout (VD_ROLLOUT_ENCODER = round; rt_encoders.h forward_round).  Row (d, r) of vd_mn_attention_forward /
+// vd_hrea_attention_forward under the causal mask, bit for bit, from facts (d, 0 .. r) alone: hAtt / att [B x H] and P [B x R] (or null) are
+// compact.  The memory query of dialog d is row d of Q [B x q_ld] (q_ld = R * H reads round r of a per-round tensor in place); Qout [B x H]
+// or null receives it compact.
+int vd_mn_attention_round_p(const float* Q, int64_t q_ld, const float* Hm, float* P, float* hAtt, float* Qout, int B, int R, int r, int H,
+                            hipStream_t stream);
+int vd_hrea_attention_round_p(const float* sq, const float* sh, const float* Hm, float* P, float* att, int B, int R, int r, int H,
+                              hipStream_t stream);
+// row r of every dialog of the step-major tokens tok [T x N] (N = B * R) as a B-row sequence tok_r [T x B], with its embedding rows x [T*B x E]
+int vd_round_embed_p(const float* emb, const int32_t* tok, int T, int N, int R, int r, int32_t* tok_r, float* x, int E, hipStream_t stream);
+// dst [rows x sum(cols)] (leading dimension dst_ld) = up to three column blocks src[i] [rows x cols[i]] (leading dimension ld[i]) side by side;
+// one block with a strided source / destination is the gather / scatter of a round's rows
+int vd_rows_cat_p(float* dst, int64_t dst_ld, const float* const* src, const int64_t* ld, const int* cols, int nparts, int64_t rows,
+                  hipStream_t stream);
+
 // gemm_ops.hip: vd_gemm_nn over rows that carry a token id, with the row-group predicate of VD_FLAG_LIVE_PREFIX -- a row tile of
 // `row_tile` (32 or 128) rows whose first row has tok_mask == 0 is not computed and its C rows are left unwritten
 int vd_gemm_nn_live_p(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, float* C, int64_t ldc, int M, int N, int K,
@@ -301,6 +316,9 @@ struct vd_model {
   // VD_RETRIEVE_ROLLOUT at vd_model_create (decoder disc): vd_model_retrieve ranks round r on a history of the model's own picks for the
   // rounds before it (beam.hip E1-E5); the same full-width upload
   bool retrieve_rollout = false;
+  // VD_ROLLOUT_ENCODER = round at vd_model_create: passes 1 .. R - 1 of either rollout encode round r of every dialog alone
+  // (Encoder::forward_round, rt_encoders.h) instead of all N rounds again; false = the full encoder in every pass
+  bool rollout_round = false;
   bool lhood_tree = false;   // VD_LHOOD_TREE at vd_model_create: vd_model_retrieve_lhood scores over a prefix tree of the candidates
   bool prof_hist = false;   // ev_prof[0..3] bracket the history branch of a Sequential encoder (gen pairs: vd_model_family_ms)
   ~vd_model();

@@ -240,6 +240,12 @@ struct Disc : Decoder {
   // kernel, which writes history row r + 1 of every dialog from the rank-1 candidate of its round r.  Nothing waits for the host between
   // passes.  The last pass IS the result for every round: rows <= r of a dialog are final after pass r and every encoder is causal.
   int retrieve_rollout(vd_model* m, BatchSlot& b) {
+    if (m->training && m->rollout_round) {
+      vd_set_error("vd_model_retrieve: this model was created with VD_ROLLOUT_ENCODER = round, which encodes a rollout's later passes one round at "
+                   "a time on the state of the first: under training-mode dropout the passes would not describe one model; call "
+                   "vd_model_set_training(0) first");
+      return VD_ERR_STATE;
+    }
     if (m->training) {
       vd_set_error("vd_model_retrieve: this model was created with VD_RETRIEVE_ROLLOUT = 1, and a rollout re-runs the encoder once per round: "
                    "under training-mode dropout the passes would not describe one model; call vd_model_set_training(0) first");
@@ -271,7 +277,8 @@ struct Disc : Decoder {
     for (int r = 0; r < R; ++r) {
       if (r > 0) {                                                            // E5: rows 0 .. r of every dialog are final now
         VdRange rr("encoder forward");
-        VD_TRY(m->enc->forward(m, s, b, &enc_out));
+        if (m->rollout_round) VD_TRY(m->enc->forward_round(m, s, b, r, &enc_out));   // round r of every dialog alone
+        else VD_TRY(m->enc->forward(m, s, b, &enc_out));
       }
       VD_TRY(vd_score_ce(optH, enc_out, b.gt, scores, loss_rows, nullptr, nullptr, N, O, (int)H, 1.0f / N, s));
       if (r + 1 < R)                                                          // E2 - E4: the pick becomes history row r + 1
@@ -878,6 +885,12 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
   }
   BatchSlot& b = m->slot[m->cur];
   int32_t* pass_rounds = nullptr;
+  if (rollout && m->rollout_round && m->training) {
+    vd_set_error("vd_model_beam_search: this model was created with VD_ROLLOUT_ENCODER = round, which encodes a rollout's later passes one round "
+                 "at a time on the state of the first: under training-mode dropout the passes would not describe one model; call "
+                 "vd_model_set_training(0) first");
+    return VD_ERR_STATE;
+  }
   if (rollout) {   // the round indices of every pass, cached on the device by shape
     VD_CHECK_ARG(b.h.present && b.q.present && b.h.N == m->N && b.h.T >= b.q.T, "vd_model_beam_search: VD_BEAM_ROLLOUT = 1 needs the batch's history");
     std::vector<int32_t> rounds((size_t)R * n);
@@ -917,7 +930,8 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
       if (r > 0) {                                                          // R5: rows 0 .. r of every dialog are final now
         float* enc_out = nullptr;
         m->gen_enc_out = nullptr;
-        VD_TRY(m->enc->forward(m, s, b, &enc_out));
+        if (m->rollout_round) VD_TRY(m->enc->forward_round(m, s, b, r, &enc_out));   // round r of every dialog alone
+        else VD_TRY(m->enc->forward(m, s, b, &enc_out));
         m->gen_enc_out = enc_out;
         m->gen_seq_len = m->enc->seqLen(b);
       }

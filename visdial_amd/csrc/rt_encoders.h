@@ -13,6 +13,17 @@ struct Encoder {
   // that are joined back into `s` before returning
   virtual int forward(vd_model* m, hipStream_t s, BatchSlot& b, float** out) = 0;
   virtual int backward(vd_model* m, hipStream_t s, BatchSlot& b, const float* grad_out) = 0;
+  // One pass r >= 1 of a rollout (VD_ROLLOUT_ENCODER = round), for the encoders with a history, evaluation mode, everything on `s`.
+  //   before: forward() ran on this slot since its upload (pass 0), then forward_round for 1 .. r - 1, and history row r of every dialog
+  //           has just been written into b.h.tok
+  //   after:  *out is the [N x H] buffer forward() returned; rows d * R + r are final, rows of rounds < r are untouched (rows of later
+  //           rounds stay what they were: stale, finite, rewritten by their own pass)
+  // It reads what pass 0 left and does not depend on the history -- the question stacks' states (rnnLayers() / seqLen), q.last, the
+  // SAN's per-image `pre` -- and writes none of it; its own workspace is named rnd.* so that no buffer of pass 0 is resized.
+  virtual int forward_round(vd_model* m, hipStream_t s, BatchSlot& b, int r, float** out) {
+    vd_set_error("encoder '%s' has no history: a rollout never asks it for a round pass", m->enc_name.c_str());
+    return VD_ERR_STATE;
+  }
   // enc.rnnLayers of the Sequential encoders (read by decoders/gen.lua:31-35,46-52); null for the nngraph encoders
   virtual std::vector<SeqLSTM>* rnnLayers() { return nullptr; }
   virtual int seqLen(const BatchSlot& b) const { return b.q.T; }
@@ -211,6 +222,55 @@ struct HistWave {
   }
 };
 
+// The history branch of a round pass (Encoder::forward_round), every encoder family: history row r of the B dialogs as a B-row sequence at
+// full width -- step-major [Th x B], every row active at every step, maskZero per token (a rollout model lays rows >= 1 out at full width
+// anyway, runtime.hip upload_tokens) -- through the branch's layers: the two-layer wavefront, or one recurrence per layer for another
+// depth.  *last = the top layer's final state [B x H].  Th + 4 launches with two layers.
+inline int rows_copy(float* dst, long dst_ld, const float* src, long src_ld, long rows, int cols, hipStream_t s) {
+  const int64_t ld = src_ld;
+  return vd_rows_cat_p(dst, dst_ld, &src, &ld, &cols, 1, rows, s);
+}
+inline int round_linear(vd_model* m, hipStream_t s, const std::string& name, const float* x, long ldx, long in, long out, int rows, bool tanh,
+                        float* y, long ldy) {
+  return vd_gemm_nt(x, ldx, Wp(m, name + ".W"), in, Wp(m, name + ".b"), y, ldy, rows, (int)out, (int)in, tanh ? VD_ACT_TANH : VD_ACT_NONE, 0, s);
+}
+inline int hist_round(vd_model* m, hipStream_t s, BatchSlot& b, const std::vector<const SeqLSTM*>& layers, int r, const float** last) {
+  const int N = b.h.N, Th = b.h.T, R = m->p.maxQuesCount, B = N / R, L = (int)layers.size();
+  const long E = layers[0]->D, H = layers[0]->H, TB = (long)Th * B;
+  VD_CHECK_ARG(b.h.present && N == B * R && r >= 1 && r < R && L >= 1, "round pass %d of %d rounds over %d history rows", r, R, N);
+  int32_t* tok;
+  float* x;
+  VD_TRY(ws_get(m, "rnd.h.tok", (size_t)TB, &tok));
+  VD_TRY(ws_get(m, "rnd.h.x", (size_t)TB * E, &x));
+  VD_TRY(vd_round_embed_p(Wp(m, "embed"), b.h.tok, Th, N, R, r, tok, x, (int)E, s));
+  std::vector<float*> gates(L), h(L), c(L);
+  for (int l = 0; l < L; ++l) {
+    const std::string key = "rnd.h" + std::to_string(l + 1);
+    VD_TRY(ws_get(m, key + ".gates", (size_t)TB * 4 * H, &gates[l]));
+    VD_TRY(ws_get(m, key + ".h", (size_t)TB * H, &h[l]));
+    VD_TRY(ws_get(m, key + ".c", (size_t)TB * H, &c[l]));
+  }
+  VD_TRY(vd_gemm_nn(x, E, layers[0]->Wx(m), 4 * H, Wp(m, layers[0]->name + ".b"), gates[0], 4 * H, (int)TB, (int)(4 * H), (int)E, 0, s));
+  if (L == 2) {
+    vd_lstm2_fwd_t fw;
+    fw.T = Th; fw.N = B;
+    fw.tok_mask = tok;
+    fw.Wh1 = layers[0]->Wh(m); fw.Wx2 = layers[1]->Wx(m); fw.b2 = Wp(m, layers[1]->name + ".b"); fw.Wh2 = layers[1]->Wh(m);
+    fw.gates1 = gates[0]; fw.h1 = h[0]; fw.c1 = c[0]; fw.gates2 = gates[1]; fw.h2 = h[1]; fw.c2 = c[1];
+    fw.nact = nullptr;
+    VD_TRY(vd_lstm2_forward_p(&fw, 1, (int)H, tick_flags(m), s));
+  } else {
+    for (int l = 0; l < L; ++l) {
+      if (l > 0)
+        VD_TRY(vd_gemm_nn(h[l - 1], H, layers[l]->Wx(m), 4 * H, Wp(m, layers[l]->name + ".b"), gates[l], 4 * H, (int)TB, (int)(4 * H), (int)H, 0, s));
+      VD_TRY(vd_lstm_forward(gates[l], (int64_t)B * 4 * H, 4 * H, nullptr, tok, layers[l]->Wh(m), nullptr, nullptr, gates[l], h[l], c[l], Th, B,
+                             (int)H, 0, s));
+    }
+  }
+  *last = h[L - 1] + (long)(Th - 1) * B * H;
+  return VD_OK;
+}
+
 // nn.MM(false,true) -> MaskSoftMax -> nn.MM -> Tanh(Linear(Dropout)) -> Tanh(Linear(hAttTr + query)) (mn-att:48-65)
 struct MemoryBlock {
   Linear mn1, mn2;
@@ -243,6 +303,18 @@ struct MemoryBlock {
     VD_TRY(mn1.forward(m, s, hd, N, true, &hattTr));
     VD_TRY(vd_axpby(hattTr, query, s2, (long)N * H, 1.f, 1.f, s));   // CAddTable
     return mn2.forward(m, s, s2, N, true, out);
+  }
+  // round r of every dialog: the query of dialog d is row d of [B x q_ld], the facts are rows (d, 0 .. r) of h3 [N x H]; y [B x ldy]
+  int forward_round(vd_model* m, hipStream_t s, const float* query_, long q_ld, const float* h3_, int B_, int r, float* y, long ldy) {
+    float *hatt, *qc, *t1, *s2r;
+    VD_TRY(ws_get(m, "rnd.mn.hatt", (size_t)B_ * H, &hatt));
+    VD_TRY(ws_get(m, "rnd.mn.q", (size_t)B_ * H, &qc));
+    VD_TRY(ws_get(m, "rnd.mn.t1", (size_t)B_ * H, &t1));
+    VD_TRY(ws_get(m, "rnd.mn.s2", (size_t)B_ * H, &s2r));
+    VD_TRY(vd_mn_attention_round_p(query_, q_ld, h3_, nullptr, hatt, qc, B_, R, r, (int)H, s));
+    VD_TRY(round_linear(m, s, "mn1", hatt, H, H, H, B_, true, t1, H));
+    VD_TRY(vd_axpby(t1, qc, s2r, (long)B_ * H, 1.f, 1.f, s));   // CAddTable
+    return round_linear(m, s, "mn2", s2r, H, H, H, B_, true, y, ldy);
   }
   int backward(vd_model* m, hipStream_t s, const float* dqh2, float** dquery, float** dh3) {
     float *ds2, *dhatt_d;
@@ -337,6 +409,26 @@ struct SANBlock {
     VD_TRY(dropout_fwd(m, "att.u1_d", u, m_u, 2.f, (long)N * H, s, &ud));
     return out.forward(m, s, ud, N, true, y);                                      // mn-att:106
   }
+  // round r of every dialog: B rows u0 [B x H], one per image (R = 1 in the row -> image map), `pre` from pass 0; y [B x ldy]
+  int forward_round(vd_model* m, hipStream_t s, const float* u0, int B_, float* y, long ldy) {
+    const int fl = (m->flags & VD_FLAG_SPLIT9) && vd_img_split_ok((long)B_ * S2, (int)H, (int)K) ? VD_FLAG_SPLIT9 : 0;
+    const float* u = u0;
+    for (int i = 0; i < L; ++i) {
+      const std::string sf = hop_sfx(i);
+      float *qc, *iq, *pa, *u1;
+      VD_TRY(ws_get(m, "rnd.att.qc" + sf, (size_t)B_ * K, &qc));
+      VD_TRY(ws_get(m, "rnd.att.iqc" + sf, (size_t)B_ * S2 * K, &iq));
+      VD_TRY(ws_get(m, "rnd.att.p" + sf, (size_t)B_ * S2, &pa));
+      VD_TRY(ws_get(m, "rnd.att.u1" + sf, (size_t)B_ * H, &u1));
+      VD_TRY(round_linear(m, s, "ques_common" + sf, u, H, H, K, B_, false, qc, K));
+      // without dropout the per-round image tensor of a B-row pass IS `pre`
+      VD_TRY(vd_img_common_forward_p(pre, nullptr, fl ? pre : nullptr, Wp(m, "img_common" + sf + ".W"), Wp(m, "img_common" + sf + ".b"), qc, nullptr,
+                                     iq, B_, 1, S2, (int)H, (int)K, 1.f, fl, s));
+      VD_TRY(vd_img_att_forward(iq, Wp(m, "att" + sf + ".W"), Wp(m, "att" + sf + ".b"), pre, nullptr, u, pa, u1, B_, 1, S2, (int)H, (int)K, 1.f, s));
+      u = u1;
+    }
+    return round_linear(m, s, "out", u, H, H, H, B_, true, y, ldy);
+  }
   int backward(vd_model* m, hipStream_t s, BatchSlot& b, const float* grad_out, float** du0) {
     float* du1d;
     VD_TRY(out.backward(m, s, grad_out, true, &du1d));
@@ -380,6 +472,7 @@ struct GraphEncoder : Encoder {
   MemoryBlock memory;
   SANBlock san;
   CatLinear qi, qh;
+  float* out_ = nullptr;   // what the last forward() returned: a round pass writes its rows into it
   explicit GraphEncoder(const std::string& name) {
     memory_ = name.rfind("mn", 0) == 0;
     san_ = name.find("att") != std::string::npos;
@@ -420,8 +513,51 @@ struct GraphEncoder : Encoder {
       }
       VD_TRY(memory.forward(m, s, query, h3, N, &u));                              // mn-att:48-65
     }
-    if (san_) return san.forward(m, s, u, out);                                    // mn-att:68-106
-    *out = u;
+    if (san_) VD_TRY(san.forward(m, s, u, &u));                                    // mn-att:68-106
+    *out = out_ = u;
+    return VD_OK;
+  }
+  int forward_round(vd_model* m, hipStream_t s, BatchSlot& b, int r, float** out) override {
+    const int N = b.q.N, R = m->p.maxQuesCount, B = N / R;
+    const long H = text.H, F = m->p.imgFeatureSize;
+    VD_CHECK_ARG(out_ && N == B * R && b.h.N == N, "round pass without a full encoder pass on this batch");
+    const float* hl;
+    VD_TRY(hist_round(m, s, b, {&text.hist1, &text.hist2}, r, &hl));
+    float *hc, *qc;
+    VD_TRY(ws_get(m, "h.last", (size_t)N * H, &hc));
+    VD_TRY(ws_get(m, "q.last", (size_t)N * H, &qc));
+    VD_TRY(rows_copy(hc + (long)r * H, (long)R * H, hl, H, B, (int)H, s));          // the facts of later rounds
+    const float* qr = qc + (long)r * H;                                            // round r of q.last in place: leading dimension R * H
+    float* y = out_ + (long)r * H;
+    float* u = nullptr;
+    if (san_) VD_TRY(ws_get(m, "rnd.u", (size_t)B * H, &u));
+    if (qh_) {                                                                     // lf-att:43
+      float* cat;
+      VD_TRY(ws_get(m, "rnd.qh.cat", (size_t)B * 2 * H, &cat));
+      const float* src[2] = {qr, hl};
+      const int64_t ld[2] = {(int64_t)R * H, H};
+      const int cols[2] = {(int)H, (int)H};
+      VD_TRY(vd_rows_cat_p(cat, 2 * H, src, ld, cols, 2, B, s));
+      VD_TRY(round_linear(m, s, "qh", cat, 2 * H, 2 * H, H, B, true, san_ ? u : y, san_ ? H : (long)R * H));
+    } else {
+      const float* query = qr;
+      long q_ld = (long)R * H;
+      if (qi_) {                                                                   // mn-ques-im-hist.lua:47-48, on the image rows directly
+        float *cat, *qp;
+        VD_TRY(ws_get(m, "rnd.qi.cat", (size_t)B * (H + F), &cat));
+        VD_TRY(ws_get(m, "rnd.qi.y", (size_t)B * H, &qp));
+        const float* src[2] = {qr, b.img};
+        const int64_t ld[2] = {(int64_t)R * H, F};
+        const int cols[2] = {(int)H, (int)F};
+        VD_TRY(vd_rows_cat_p(cat, H + F, src, ld, cols, 2, B, s));
+        VD_TRY(round_linear(m, s, "qi", cat, H + F, H + F, H, B, true, qp, H));
+        query = qp;
+        q_ld = H;
+      }
+      VD_TRY(memory.forward_round(m, s, query, q_ld, hc, B, r, san_ ? u : y, san_ ? H : (long)R * H));
+    }
+    if (san_) VD_TRY(san.forward_round(m, s, u, B, y, (long)R * H));
+    *out = out_;
     return VD_OK;
   }
   int backward(vd_model* m, hipStream_t s, BatchSlot& b, const float* grad_out) override {
@@ -463,6 +599,7 @@ struct LateFusion : Encoder {
   CatLinear fuse;
   long E = 0, H = 0, F = 0;
   float pdrop = 0.5f;
+  float* out_ = nullptr;   // what the last forward() returned: a round pass writes its rows into it
   LateFusion(bool im, bool hs) : use_im(im), use_hist(hs) {}
   void declare(vd_model* m) override {
     E = m->p.embedSize; H = m->p.rnnHiddenSize; F = m->p.imgFeatureSize; pdrop = m->p.dropout;
@@ -527,7 +664,32 @@ struct LateFusion : Encoder {
     }
     uint8_t* mk;
     VD_TRY(drop_mask(m, "fuse", (size_t)N * fuse.D, pdrop, s, &mk));
-    return fuse.forward(m, s, parts, N, mk, pdrop > 0.f ? 1.f / (1.f - pdrop) : 1.f, out);
+    VD_TRY(fuse.forward(m, s, parts, N, mk, pdrop > 0.f ? 1.f / (1.f - pdrop) : 1.f, out));
+    out_ = *out;
+    return VD_OK;
+  }
+  int forward_round(vd_model* m, hipStream_t s, BatchSlot& b, int r, float** out) override {
+    const int N = b.q.N, Tq = b.q.T, R = m->p.maxQuesCount, B = N / R;
+    VD_CHECK_ARG(use_hist && out_ && N == B * R && b.h.N == N, "round pass without a full encoder pass on this batch");
+    std::vector<const SeqLSTM*> layers;
+    for (const SeqLSTM& l : hist) layers.push_back(&l);
+    const float* hl;
+    VD_TRY(hist_round(m, s, b, layers, r, &hl));
+    if (HistWave::usable(b, hist)) {                                               // (the h.last cache exists on the wavefront path only)
+      float* hc;
+      VD_TRY(ws_get(m, "h.last", (size_t)N * H, &hc));
+      VD_TRY(rows_copy(hc + (long)r * H, (long)R * H, hl, H, B, (int)H, s));
+    }
+    // [question state of round r ; image ; history state] gathered by the join itself, then Linear + Tanh into the output rows
+    float* cat;
+    VD_TRY(ws_get(m, "rnd.fuse.cat", (size_t)B * fuse.D, &cat));
+    const float* src[3] = {rnn.back().out_at(Tq - 1) + (long)r * H, use_im ? b.img : hl, hl};
+    const int64_t ld[3] = {(int64_t)R * H, use_im ? F : H, H};
+    const int cols[3] = {(int)H, (int)(use_im ? F : H), (int)H};
+    VD_TRY(vd_rows_cat_p(cat, fuse.D, src, ld, cols, use_im ? 3 : 2, B, s));
+    VD_TRY(round_linear(m, s, "fuse", cat, fuse.D, fuse.D, H, B, true, out_ + (long)r * H, (long)R * H));
+    *out = out_;
+    return VD_OK;
   }
   int backward(vd_model* m, hipStream_t s, BatchSlot& b, const float* grad_out) override {
     std::vector<bool> need = {true};
@@ -570,6 +732,7 @@ struct Hre : Encoder {
   long E = 0, H = 0, F = 0, DI = 0;
   int R = 0;
   float *hh = nullptr, *hq = nullptr, *sq = nullptr, *sh_ = nullptr, *P = nullptr;
+  float* out_ = nullptr;   // what the last forward() returned: a round pass writes its rows into it
   uint8_t* m_img = nullptr;
   Hre(bool im, bool att) : use_im(im), attention(att) {}
   void declare(vd_model* m) override {
@@ -668,7 +831,35 @@ struct Hre : Encoder {
     VD_TRY(vd_embed_gather(second, to_rb, nullptr, s_rb, N, (int)H, 1.f, s));
     VD_TRY(dialog.forward(m, s, {f_rb, s_rb}, R, B, nullptr, &d));                        // hre:90-94 (no maskZero)
     VD_TRY(vd_embed_gather(d, to_n, nullptr, o, N, (int)H, 1.f, s));
-    *out = o;
+    *out = out_ = o;
+    return VD_OK;
+  }
+  int forward_round(vd_model* m, hipStream_t s, BatchSlot& b, int r, float** out) override {
+    const int N = b.q.N, B = N / R;
+    VD_CHECK_ARG(out_ && hh && hq && N == B * R && b.h.N == N && dialog.T == R && dialog.N == B, "round pass without a full encoder pass on this batch");
+    std::vector<const SeqLSTM*> layers;
+    for (const SeqLSTM& l : hist) layers.push_back(&l);
+    const float* hl;
+    VD_TRY(hist_round(m, s, b, layers, r, &hl));
+    VD_TRY(rows_copy(hh + (long)r * H, (long)R * H, hl, H, B, (int)H, s));          // hrea attends over it in later rounds
+    const float *first = hq + (long)r * H, *second = hl;                           // round r of the question state in place
+    long ld1 = (long)R * H, ld2 = H;
+    if (attention) {                                                               // hrea:83-131; sq is pass 0's, sh of the new rows is not
+      float* att;
+      VD_TRY(ws_get(m, "rnd.hrea.att", (size_t)B * H, &att));
+      VD_TRY(vd_rowdot_forward(hh, Wp(m, "att_h.W"), Wp(m, "att_h.b"), sh_, N, (int)H, s));
+      VD_TRY(vd_hrea_attention_round_p(sq, sh_, hh, nullptr, att, B, R, r, (int)H, s));
+      second = first; ld2 = ld1;                                                   // concat4: {att, ques}
+      first = att; ld1 = H;
+    }
+    // ONE step of the dialog LSTM from its step r - 1 state, written in place as step r of pass 0's step-major buffers
+    float* g = dialog.gates + (long)r * B * 4 * H;
+    VD_TRY(vd_gemm_nn(first, ld1, dialog.Wx(m), 4 * H, Wp(m, "dialog.b"), g, 4 * H, B, (int)(4 * H), (int)H, 0, s));
+    VD_TRY(vd_gemm_nn(second, ld2, dialog.Wx(m) + H * 4 * H, 4 * H, nullptr, g, 4 * H, B, (int)(4 * H), (int)H, 1, s));
+    VD_TRY(vd_lstm_forward(g, (int64_t)B * 4 * H, 4 * H, nullptr, nullptr, dialog.Wh(m), dialog.out_at(r - 1), dialog.cell_at(r - 1), g,
+                           dialog.out_at(r), dialog.cell_at(r), 1, B, (int)H, 0, s));
+    VD_TRY(rows_copy(out_ + (long)r * H, (long)R * H, dialog.out_at(r), H, B, (int)H, s));
+    *out = out_;
     return VD_OK;
   }
   int backward(vd_model* m, hipStream_t s, BatchSlot& b, const float* grad_out) override {

@@ -422,10 +422,19 @@ int vd_model_create(const vd_model_params* p, const char* encoder, const char* d
                  "vd_model_create: VD_RETRIEVE_ROLLOUT = 1 with VD_OPTION_CACHE: a cached batch carries only the candidate rows the cache did "
                  "not hold, and the rollout reads a picked candidate's tokens from the batch; combining the two is left for a follow-up");
   }
+  // encoder of a rollout's passes 1 .. R - 1 (rt_encoders.h forward_round): VD_ROLLOUT_ENCODER = full / round (unset = full); anything else
+  // is refused.  `round` is kept only where a rollout applies: with neither rollout variable set, or an encoder without a history, both
+  // calls already run the plain search / retrieval and the value is ignored.
+  bool rollout_round = false;
+  if (const char* e = getenv("VD_ROLLOUT_ENCODER")) {
+    VD_CHECK_ARG(!strcmp(e, "full") || !strcmp(e, "round"), "vd_model_create: VD_ROLLOUT_ENCODER = '%s' must be 'full' or 'round' (unset = full)", e);
+    rollout_round = !strcmp(e, "round") && (beam_rollout || retrieve_rollout) && has(en, "hist");
+  }
   vd_model* m = new vd_model();
   m->p = *p;
   m->beam_rollout = beam_rollout;
   m->retrieve_rollout = retrieve_rollout;
+  m->rollout_round = rollout_round;
   m->sample_topk = sample_topk;
   m->sample_topp = sample_topp;
   m->beam_groups = beam_groups;

@@ -49,6 +49,10 @@ class Model(SplitEval):
             # the prefix-tree head is internal to the library (its C symbol set is frozen): only the model-level runtime reaches it
             raise ValueError("fusedLhood = 2 (generative retrieval over a prefix tree of the candidates) runs in the model-level runtime only: "
                              "use -host native (visdial_amd.native.NativeModel); the operator-level host takes fusedLhood = 0 or 1")
+        if (params.get('rolloutEncoder') or 'full') != 'full':
+            # this host's rollouts are host loops over whole encoder passes; the round pass is internal to the library's runtime
+            raise ValueError("rolloutEncoder = %r: encoding a rollout one round at a time runs in the model-level runtime only: use -host native "
+                             "(visdial_amd.native.NativeModel); the operator-level host takes rolloutEncoder = 'full'" % (params['rolloutEncoder'],))
         if not torch.cuda.is_available():
             raise RuntimeError("visdial_amd.Model needs an MI355X (HIP device); there is no CPU path")
         gpuid = int(params.get('gpuid', 0))

@@ -83,6 +83,8 @@ class NativeModel(SplitEval):
         # generateAnswers(beamBatch > 0) checks its `rollout` against it.
         # params retrieveRollout: vd_model_retrieve of decoder disc ranks every round on a history of the model's own picks
         # (VD_RETRIEVE_ROLLOUT), the same way again; `retrieve_rollout_batch` is then one upload and one call.
+        # params rolloutEncoder ('full' / 'round'): the encoder of passes 1 .. R - 1 of either rollout (VD_ROLLOUT_ENCODER), the same way again:
+        # 'round' encodes the round a pass answers alone; the library refuses any other value and ignores 'round' where nothing rolls out.
         import os
         switches = {'VD_OPTION_CACHE': str(int(p.get('optionCache', 0) or 0)),
                     'VD_LHOOD_TREE': '1' if int(p.get('fusedLhood', 0) or 0) == 2 else '0',
@@ -94,7 +96,8 @@ class NativeModel(SplitEval):
                     'VD_BEAM_NO_REPEAT': None if p.get('beamNoRepeat') is None else str(p['beamNoRepeat']),
                     'VD_BEAM_LENGTH_PENALTY': None if p.get('beamLengthPenalty') is None else str(p['beamLengthPenalty']),
                     'VD_BEAM_ROLLOUT': None if p.get('beamRollout') is None else str(p['beamRollout']),
-                    'VD_RETRIEVE_ROLLOUT': None if p.get('retrieveRollout') is None else str(p['retrieveRollout'])}
+                    'VD_RETRIEVE_ROLLOUT': None if p.get('retrieveRollout') is None else str(p['retrieveRollout']),
+                    'VD_ROLLOUT_ENCODER': None if p.get('rolloutEncoder') is None else str(p['rolloutEncoder'])}
         prev = {k: os.environ.get(k) for k in switches}
         try:
             for k, v in switches.items():
