@@ -312,7 +312,7 @@ def test_the_c_surface_is_where_it_was_and_the_variables_are_documented():
     names = set(re.findall(r'\b(vd_[a-z0-9_]+)\s*\(', code))
     assert len(names) == 101 and '101 entry points' in header and names == set(_lib.PROTOTYPES)
     assert not {'vd_beam_topk_ban_p', 'vd_beam_advance_lp_p'} & names          # internal to the library
-    runtime = open(os.path.join(ROOT, 'visdial_amd', 'csrc', 'runtime.hip')).read()
+    runtime = open(os.path.join(ROOT, 'visdial_amd', 'csrc', 'rt_switches.h')).read()
     integration = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
     for var in ('VD_BEAM_MIN_LEN', 'VD_BEAM_NO_REPEAT', 'VD_BEAM_LENGTH_PENALTY'):
         assert var in header and var in runtime and var in integration

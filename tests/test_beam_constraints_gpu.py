@@ -67,7 +67,7 @@ def test_constrained_device_search_equals_the_per_dialog_search_on_both_hosts(gp
     P32 = weights(p, dl)
     kn = knobs(G, m, n, alpha)
     nat = native(p, P32, **kn)
-    assert nat._beam_limits == (m, n, alpha)
+    assert (nat._knobs['beamMinLen'], nat._knobs['beamNoRepeat'], nat._knobs['beamLengthPenalty']) == (m, n, alpha)
     cfg = dict(kn, beamSize=k, beamLen=beamLen)
     ref = nat.generateAnswers(dl, 'val', dict(cfg, beamBatch=0))
     assert len(ref) == 3
@@ -273,7 +273,7 @@ def test_explicit_zeros_are_the_search_of_a_model_created_without_the_variables(
     got = []
     for kn in (groups, dict(groups, beamMinLen=0, beamNoRepeat=0, beamLengthPenalty=0.0)):
         nat = native(p, P32, **kn)
-        assert nat._beam_limits == (0, 0, 0.0)
+        assert (nat._knobs['beamMinLen'], nat._knobs['beamNoRepeat'], nat._knobs['beamLengthPenalty']) == (0, 0, 0.0)
         nat._gen_encode(batch)
         toks, scores = np.full((9 * G, L), -1, np.int32), np.full(9 * G, np.nan)
         _lib.call("vd_model_beam_search", nat.h, 6, L, START, END, toks.ctypes.data, scores.ctypes.data)

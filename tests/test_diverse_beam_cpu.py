@@ -354,7 +354,7 @@ def test_the_c_surface_is_where_it_was():
     assert len(names) == 101 and '101 entry points' in header
     assert names == set(_lib.PROTOTYPES) == set(re.findall(r"^\s+'(vd_[a-z0-9_]+)',$", lua, re.M))
     assert 'vd_beam_advance_grouped_p' not in names                  # internal to the library: not in the header, not extern "C"
-    runtime = open(os.path.join(ROOT, 'visdial_amd', 'csrc', 'runtime.hip')).read()
+    runtime = open(os.path.join(ROOT, 'visdial_amd', 'csrc', 'rt_switches.h')).read()
     for var in ('VD_BEAM_GROUPS', 'VD_BEAM_DIVERSITY'):
         assert var in header and var in runtime
     assert 'VD_BEAM' not in lua                                      # the Lua host is out of scope

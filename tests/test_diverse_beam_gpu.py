@@ -272,7 +272,7 @@ def test_one_group_or_no_variable_is_the_plain_search(gpu):
     got = []
     for knobs in ({}, dict(beamGroups=1), dict(beamGroups=1, beamDiversity=3.0)):
         nat = native(p, P32, **knobs)
-        assert nat._beam_knobs[0] == 1
+        assert nat._knobs['beamGroups'] == 1
         nat._gen_encode(batch)
         toks, scores = np.full((9, L), -1, np.int32), np.full(9, np.nan)
         _lib.call("vd_model_beam_search", nat.h, 3, L, START, END, toks.ctypes.data, scores.ctypes.data)
@@ -294,7 +294,7 @@ def test_refusals(gpu):
     from visdial_amd.native import NativeModel
     p, dl = tiny()
     nat = native(p, weights(p, dl), beamGroups=3)
-    assert nat._beam_knobs == (3, 0.5)
+    assert (nat._knobs['beamGroups'], nat._knobs['beamDiversity']) == (3, 0.5)
     nat._gen_encode(whole_batch(dl, p))
     toks, scores = np.zeros((27, L), np.int32), np.zeros(27)
     with pytest.raises(_lib.VisdialHipError, match='VD_BEAM_GROUPS = 3 does not divide beam size 4'):

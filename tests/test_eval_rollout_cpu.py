@@ -197,7 +197,7 @@ def test_the_c_surface_is_where_it_was_and_the_variable_is_documented():
     names = set(re.findall(r'\b(vd_[a-z0-9_]+)\s*\(', code))
     assert len(names) == 101 and names == set(_lib.PROTOTYPES)
     assert 'vd_disc_rollout_pick_p' not in header                     # internal to the library
-    for text in (header, read('visdial_amd', 'csrc', 'runtime.hip'), read('INTEGRATION.md'), read('README.md'), read('visdial_amd', 'native.py')):
+    for text in (header, read('visdial_amd', 'csrc', 'rt_switches.h'), read('INTEGRATION.md'), read('README.md'), read('visdial_amd', 'native.py')):
         assert 'VD_RETRIEVE_ROLLOUT' in text
     beam = read('visdial_amd', 'csrc', 'beam.hip')
     assert 'disc_rollout_pick_kernel' in beam and 'vd_disc_rollout_pick_p' in read('visdial_amd', 'csrc', 'rt_core.h')

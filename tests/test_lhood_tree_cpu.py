@@ -138,7 +138,7 @@ def test_flag_value_everywhere_and_the_symbol_set_where_it_was():
     for name in ('vd_lhood_lse_p', 'vd_lhood_edge_sum_p'):
         assert name not in names
     # the switch is an environment variable read at create, documented where VD_OPTION_CACHE is
-    assert 'VD_LHOOD_TREE' in header and 'VD_LHOOD_TREE' in open(os.path.join(ROOT, 'visdial_amd', 'csrc', 'runtime.hip')).read()
+    assert 'VD_LHOOD_TREE' in header and 'VD_LHOOD_TREE' in open(os.path.join(ROOT, 'visdial_amd', 'csrc', 'rt_switches.h')).read()
 
 
 def test_ops_lstm_forward_checks_the_two_plane_mask_before_the_library_call():

@@ -211,7 +211,7 @@ def test_the_c_surface_is_where_it_was_and_the_variable_is_documented():
     assert len(names) == 101 and names == set(_lib.PROTOTYPES)
     assert 'vd_beam_rollout_append_p' not in header                  # internal to the library
     read = lambda *parts: open(os.path.join(ROOT, *parts)).read()
-    for text in (header, read('visdial_amd', 'csrc', 'runtime.hip'), read('INTEGRATION.md'), read('README.md')):
+    for text in (header, read('visdial_amd', 'csrc', 'rt_switches.h'), read('INTEGRATION.md'), read('README.md')):
         assert 'VD_BEAM_ROLLOUT' in text
     beam = read('visdial_amd', 'csrc', 'beam.hip')
     assert 'beam_rollout_append_kernel' in beam and 'vd_beam_rollout_append_p' in read('visdial_amd', 'csrc', 'rt_core.h')

@@ -77,7 +77,7 @@ def test_the_c_surface_is_where_it_was_and_the_variable_is_documented():
     assert len(names) == 101 and names == set(_lib.PROTOTYPES)
     for internal in ('vd_mn_attention_round_p', 'vd_hrea_attention_round_p', 'vd_round_embed_p', 'vd_rows_cat_p'):
         assert internal not in header and internal in read('visdial_amd', 'csrc', 'rt_core.h')
-    for text in (header, read('visdial_amd', 'csrc', 'runtime.hip'), read('INTEGRATION.md'), read('README.md'), read('visdial_amd', 'native.py')):
+    for text in (header, read('visdial_amd', 'csrc', 'rt_switches.h'), read('INTEGRATION.md'), read('README.md'), read('visdial_amd', 'native.py')):
         assert 'VD_ROLLOUT_ENCODER' in text
     att = read('visdial_amd', 'csrc', 'attention.hip')
     assert 'mn_att_round_kernel' in att and 'hrea_att_round_kernel' in att

@@ -290,7 +290,7 @@ def test_create_refuses_bad_values_and_disc_ignores_them(gpu):
     d = dict(p, decoder='disc', numOptions=4)
     for knobs in (dict(topK=5, topP=0.5), dict(topK=-1, topP='abc')):          # decoder disc has no sampling: ignored
         m = NativeModel(dict(d, **knobs))
-        assert m._sample_knobs == (0, 1.0)
+        assert (m._knobs['topK'], m._knobs['topP']) == (0, 1.0)
         m.close()
     # the batched path of a model created without the knob cannot truncate
     m = native(p)

@@ -21,6 +21,9 @@
 #include "../../include/visdial_hip.h"
 #include "common.h"
 #include "paths.h"
+#include "rt_switches.h"
+
+static_assert(VD_OK == 0 && VD_ERR_ARG == -1, "rt_switches.h returns the two as literals: it includes no common.h");
 
 // lstm.hip: the two-layer wavefront with the pass's arithmetic (flags & VD_FLAG_BF16: bf16 operands on the ticks' MFMAs in a bf16 pass;
 // the C-ABI entry points vd_lstm2_forward / vd_lstm2_backward are these with flags = 0)
@@ -242,7 +245,6 @@ struct OptionCache {
     ++stamp;
   }
 };
-static constexpr long VD_OPTION_CACHE_DEFAULT_ROWS = 262144;   // 512 MiB of fp32 state at H = 512
 static constexpr long VD_OPTION_CACHE_FIRST_ROWS = 16384;      // first allocation; doubles from there
 
 struct Encoder;
@@ -297,29 +299,8 @@ struct vd_model {
   // capability flags from the encoder NAME (opts.lua:54-67)
   bool use_im = false, use_hist = false, is_att = false, is_graph = false;
   vdrt::OptionCache ocache;
-  // VD_SAMPLE_TOPK / VD_SAMPLE_TOPP at vd_model_create (decoder gen): vd_model_sample draws from the top-k / nucleus kept set; 0 / 1 = off
-  int sample_topk = 0;
-  double sample_topp = 1.0;
-  // VD_BEAM_GROUPS / VD_BEAM_DIVERSITY at vd_model_create (decoder gen): vd_model_beam_search searches in that many groups per round
-  // with that Hamming diversity and returns every group's answer; 1 = the plain search
-  int beam_groups = 1;
-  double beam_diversity = 0.5;
-  // VD_BEAM_MIN_LEN / VD_BEAM_NO_REPEAT / VD_BEAM_LENGTH_PENALTY at vd_model_create (decoder gen): the constraints of vd_model_beam_search
-  // (beam.hip C1-C6); 0 = off.  beam_lp: the host copy of the table s^alpha, s < beamLen, built by the search once beamLen is known and
-  // kept here until the upload into workspace "beam.lp" has run
-  int beam_min_len = 0, beam_no_repeat = 0;
-  double beam_length_penalty = 0.0;
-  std::vector<double> beam_lp;
-  // VD_BEAM_ROLLOUT at vd_model_create (decoder gen): vd_model_beam_search answers round r on a history of the model's own answers to the
-  // rounds before it (beam.hip R1-R6), and an upload lays out history rows >= 1 at full width (runtime.hip upload_tokens)
-  bool beam_rollout = false;
-  // VD_RETRIEVE_ROLLOUT at vd_model_create (decoder disc): vd_model_retrieve ranks round r on a history of the model's own picks for the
-  // rounds before it (beam.hip E1-E5); the same full-width upload
-  bool retrieve_rollout = false;
-  // VD_ROLLOUT_ENCODER = round at vd_model_create: passes 1 .. R - 1 of either rollout encode round r of every dialog alone
-  // (Encoder::forward_round, rt_encoders.h) instead of all N rounds again; false = the full encoder in every pass
-  bool rollout_round = false;
-  bool lhood_tree = false;   // VD_LHOOD_TREE at vd_model_create: vd_model_retrieve_lhood scores over a prefix tree of the candidates
+  vdrt::Switches sw;   // what vd_model_create read from the environment (rt_switches.h)
+  std::vector<double> beam_lp;   // host copy of the table s^alpha, s < beamLen (VD_BEAM_LENGTH_PENALTY), kept until its upload has run
   bool prof_hist = false;   // ev_prof[0..3] bracket the history branch of a Sequential encoder (gen pairs: vd_model_family_ms)
   ~vd_model();
 };

@@ -46,6 +46,24 @@ inline int stage_loss(vd_model* m, const float* loss_rows, long n, bool is_sum, 
   return VD_OK;
 }
 
+// What the two rollout drivers (Disc::retrieve_rollout, Gen_beam_search) share.  VD_ROLLOUT_ENCODER = round is refused in training mode:
+inline int refuse_round_rollout_in_training(vd_model* m, const char* call) {
+  if (!(m->training && m->sw.rollout_round)) return VD_OK;
+  vd_set_error("%s: this model was created with VD_ROLLOUT_ENCODER = round, which encodes a rollout's later passes one round at a time on the "
+               "state of the first: under training-mode dropout the passes would not describe one model; call vd_model_set_training(0) first",
+               call);
+  return VD_ERR_STATE;
+}
+// the encoder of a pass r >= 1: round r of every dialog alone, or all N rounds again
+inline int rollout_encode(vd_model* m, hipStream_t s, BatchSlot& b, int r, float** enc_out) {
+  return m->sw.rollout_round ? m->enc->forward_round(m, s, b, r, enc_out) : m->enc->forward(m, s, b, enc_out);
+}
+// the history the append / pick kernels write: the uploaded rows and, where the upload sorted them by length, the sorted copy and its index
+struct HistRows {
+  int32_t *tok, *tok_sorted, *inv;
+  explicit HistRows(BatchSlot& b) : tok(b.h.tok), tok_sorted(b.h.sorted ? b.h.tok_sorted : nullptr), inv(b.h.sorted ? b.h.inv : nullptr) {}
+};
+
 // ------------------------------------------------------------------------------------------------------------
 // Discriminative decoder (decoders/disc.lua:3-38): the 100 candidate answers of a round share one embedding and one
 // LSTM; option scores = <last hidden state, encoder output>; criterion = CrossEntropy over the options.
@@ -231,7 +249,7 @@ struct Disc : Decoder {
     return VD_OK;
   }
   int retrieve(vd_model* m, BatchSlot& b) override {                                          // model.lua:421-425
-    if (m->retrieve_rollout && m->use_hist) return retrieve_rollout(m, b);   // (no history: nothing depends on an answer)
+    if (m->sw.retrieve_rollout && m->use_hist) return retrieve_rollout(m, b);   // (no history: nothing depends on an answer)
     return forward_backward(m, b, true);
   }
 
@@ -240,12 +258,7 @@ struct Disc : Decoder {
   // kernel, which writes history row r + 1 of every dialog from the rank-1 candidate of its round r.  Nothing waits for the host between
   // passes.  The last pass IS the result for every round: rows <= r of a dialog are final after pass r and every encoder is causal.
   int retrieve_rollout(vd_model* m, BatchSlot& b) {
-    if (m->training && m->rollout_round) {
-      vd_set_error("vd_model_retrieve: this model was created with VD_ROLLOUT_ENCODER = round, which encodes a rollout's later passes one round at "
-                   "a time on the state of the first: under training-mode dropout the passes would not describe one model; call "
-                   "vd_model_set_training(0) first");
-      return VD_ERR_STATE;
-    }
+    VD_TRY(refuse_round_rollout_in_training(m, "vd_model_retrieve"));
     if (m->training) {
       vd_set_error("vd_model_retrieve: this model was created with VD_RETRIEVE_ROLLOUT = 1, and a rollout re-runs the encoder once per round: "
                    "under training-mode dropout the passes would not describe one model; call vd_model_set_training(0) first");
@@ -274,16 +287,16 @@ struct Disc : Decoder {
     VD_TRY(join_stream(m, sd, s));
     const float* optH;
     VD_TRY(option_states_full(m, b, os, &optH));
+    const HistRows hr(b);
     for (int r = 0; r < R; ++r) {
       if (r > 0) {                                                            // E5: rows 0 .. r of every dialog are final now
         VdRange rr("encoder forward");
-        if (m->rollout_round) VD_TRY(m->enc->forward_round(m, s, b, r, &enc_out));   // round r of every dialog alone
-        else VD_TRY(m->enc->forward(m, s, b, &enc_out));
+        VD_TRY(rollout_encode(m, s, b, r, &enc_out));
       }
       VD_TRY(vd_score_ce(optH, enc_out, b.gt, scores, loss_rows, nullptr, nullptr, N, O, (int)H, 1.0f / N, s));
       if (r + 1 < R)                                                          // E2 - E4: the pick becomes history row r + 1
-        VD_TRY(vd_disc_rollout_pick_p(scores, O, b.opt.tok, NO, b.opt.T, b.opt_uid, b.q.tok, b.q.T, B, R, r, b.h.tok,
-                                      b.h.sorted ? b.h.tok_sorted : nullptr, b.h.sorted ? b.h.inv : nullptr, b.h.T, s));
+        VD_TRY(vd_disc_rollout_pick_p(scores, O, b.opt.tok, NO, b.opt.T, b.opt_uid, b.q.tok, b.q.T, B, R, r, hr.tok, hr.tok_sorted, hr.inv,
+                                      b.h.T, s));
     }
     VD_TRY(stage_loss(m, loss_rows, N, false, s));
     m->scores = scores;
@@ -497,7 +510,7 @@ struct Gen : Decoder {
   int retrieve_lhood(vd_model* m, BatchSlot& b) override {
     Retrieval r;
     VD_TRY(retrieve_begin(m, b, true, &r));
-    if (m->lhood_tree && b.tree_ok) VD_TRY(retrieve_tree(m, b, r));
+    if (m->sw.lhood_tree && b.tree_ok) VD_TRY(retrieve_tree(m, b, r));
     else if (vd_lhood_prefix_fits(r.T, (long)r.N * std::min(r.O, r.oc))) VD_TRY(retrieve_ordered(m, b, r));
     else VD_TRY(retrieve_live(m, b, r));
     return retrieve_end(m, r);
@@ -867,13 +880,13 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
   VD_CHECK_ARG(m->gen_enc_out && m->N > 0, "vd_model_beam_search: call vd_model_encode first");
   VD_CHECK_ARG(host_tokens && host_scores && L >= 1, "vd_model_beam_search: bad arguments");
   VD_CHECK_ARG(k >= 1 && k <= 32 && k <= g->V, "vd_model_beam_search: beam size %d must be in [1, min(32, vocabSize)]", k);
-  const int groups = m->beam_groups;
+  const int groups = m->sw.beam_groups;
   VD_CHECK_ARG(k % groups == 0, "vd_model_beam_search: VD_BEAM_GROUPS = %d does not divide beam size %d", groups, k);
-  const bool rollout = m->beam_rollout && m->use_hist;                      // (no history: nothing depends on an answer -- the plain search)
+  const bool rollout = m->sw.beam_rollout && m->use_hist;                      // (no history: nothing depends on an answer -- the plain search)
   const int R = m->p.maxQuesCount, passes = rollout ? R : 1;
   const int N = m->N / passes, n = N * k, G = N * groups, kg = k / groups;  // per pass: G answers, each the best of kg slots
-  const int min_len = m->beam_min_len, no_repeat = m->beam_no_repeat;
-  const bool ban = min_len > 0 || no_repeat > 0, penalty = m->beam_length_penalty > 0.0;
+  const int min_len = m->sw.beam_min_len, no_repeat = m->sw.beam_no_repeat;
+  const bool ban = min_len > 0 || no_repeat > 0, penalty = m->sw.beam_length_penalty > 0.0;
   if (ban) {
     VD_CHECK_ARG(no_repeat == 0 || L <= VD_BEAM_LMAX, "vd_model_beam_search: VD_BEAM_NO_REPEAT = %d needs a beam length %d <= VD_BEAM_LMAX = %d",
                  no_repeat, L, VD_BEAM_LMAX);
@@ -885,13 +898,8 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
   }
   BatchSlot& b = m->slot[m->cur];
   int32_t* pass_rounds = nullptr;
-  if (rollout && m->rollout_round && m->training) {
-    vd_set_error("vd_model_beam_search: this model was created with VD_ROLLOUT_ENCODER = round, which encodes a rollout's later passes one round "
-                 "at a time on the state of the first: under training-mode dropout the passes would not describe one model; call "
-                 "vd_model_set_training(0) first");
-    return VD_ERR_STATE;
-  }
   if (rollout) {   // the round indices of every pass, cached on the device by shape
+    VD_TRY(refuse_round_rollout_in_training(m, "vd_model_beam_search"));
     VD_CHECK_ARG(b.h.present && b.q.present && b.h.N == m->N && b.h.T >= b.q.T, "vd_model_beam_search: VD_BEAM_ROLLOUT = 1 needs the batch's history");
     std::vector<int32_t> rounds((size_t)R * n);
     for (int r = 0; r < R; ++r)
@@ -920,18 +928,18 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
   double* lp = nullptr;
   if (penalty) {                                                            // C6: s^alpha on the host in fp64, uploaded as a table
     m->beam_lp.resize((size_t)L);
-    for (int i = 0; i < L; ++i) m->beam_lp[i] = std::pow((double)i, m->beam_length_penalty);
+    for (int i = 0; i < L; ++i) m->beam_lp[i] = std::pow((double)i, m->sw.beam_length_penalty);
     VD_TRY(ws_get(m, "beam.lp", (size_t)L, &lp));
     VD_HIP(hipMemcpyAsync(lp, m->beam_lp.data(), (size_t)L * 8, hipMemcpyHostToDevice, s));
   }
+  const HistRows hr(b);
   for (int r = 0; r < passes; ++r) {
     int32_t* out_tok = reinterpret_cast<int32_t*>(out) + (size_t)r * G * L;
     if (rollout) {
       if (r > 0) {                                                          // R5: rows 0 .. r of every dialog are final now
         float* enc_out = nullptr;
         m->gen_enc_out = nullptr;
-        if (m->rollout_round) VD_TRY(m->enc->forward_round(m, s, b, r, &enc_out));   // round r of every dialog alone
-        else VD_TRY(m->enc->forward(m, s, b, &enc_out));
+        VD_TRY(rollout_encode(m, s, b, r, &enc_out));
         m->gen_enc_out = enc_out;
         m->gen_seq_len = m->enc->seqLen(b);
       }
@@ -943,7 +951,7 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
         VD_TRY(vd_beam_topk_ban_p(logits, g->Vp, n, (int)g->V, tok, k, hist[0], L, step, min_len, no_repeat, end, top_idx, top_val, s));
       else
         VD_TRY(vd_beam_topk(logits, g->Vp, n, (int)g->V, tok, k, top_idx, top_val, s));
-      VD_TRY(vd_beam_advance_p(top_idx, top_val, N, k, groups, (float)m->beam_diversity, step, L, end, scores, hist[0], hist[1], src, tok,
+      VD_TRY(vd_beam_advance_p(top_idx, top_val, N, k, groups, (float)m->sw.beam_diversity, step, L, end, scores, hist[0], hist[1], src, tok,
                                best_score, best_len, best_hist, lp, s));
       std::swap(hist[0], hist[1]);
       return VD_OK;
@@ -951,8 +959,7 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
     VD_TRY(vd_beam_finish(G, kg, L, hist[0], scores, best_score, best_len, best_hist, out_tok,
                           reinterpret_cast<double*>(out + tok_bytes) + (size_t)r * G, s));
     if (rollout && r + 1 < R)                                               // R2: the answer becomes history row r + 1
-      VD_TRY(vd_beam_rollout_append_p(out_tok, L, end, b.q.tok, b.q.T, N, R, r, b.h.tok, b.h.sorted ? b.h.tok_sorted : nullptr,
-                                      b.h.sorted ? b.h.inv : nullptr, b.h.T, s));
+      VD_TRY(vd_beam_rollout_append_p(out_tok, L, end, b.q.tok, b.q.T, N, R, r, hr.tok, hr.tok_sorted, hr.inv, b.h.T, s));
   }
   std::vector<uint8_t> staged;
   VD_TRY(gen_read_back(m, out, tok_bytes + Gall * 8, &staged));
@@ -976,7 +983,7 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
 inline int Gen_sample(Gen* g, vd_model* m, int L, int start, int end, double T, const double* host_u, int32_t* host_tokens,
                       double* host_loglik) {
   VD_CHECK_ARG(m->gen_enc_out && m->N > 0, "vd_model_sample: call vd_model_encode first");
-  VD_CHECK_ARG(!m->beam_rollout, "vd_model_sample: this model was created with VD_BEAM_ROLLOUT = 1: a rollout feeds the beam search's answers "
+  VD_CHECK_ARG(!m->sw.beam_rollout, "vd_model_sample: this model was created with VD_BEAM_ROLLOUT = 1: a rollout feeds the beam search's answers "
                "back, and one divergent draw would cascade over the rounds; create the sampling model without the variable");
   VD_CHECK_ARG(host_u && host_tokens && host_loglik, "vd_model_sample: bad arguments");
   VD_CHECK_ARG(L >= 1, "vd_model_sample: beam_len = %d must be >= 1", L);
@@ -998,8 +1005,8 @@ inline int Gen_sample(Gen* g, vd_model* m, int L, int start, int end, double T, 
   int32_t* status = reinterpret_cast<int32_t*>(out + hist_bytes + (size_t)n * 8);
   VD_HIP(hipMemcpyAsync(u, host_u, (size_t)L * n * 8, hipMemcpyHostToDevice, s));
   VD_TRY(vd_sample_init(n, L, start, hist, tok, loglik, status, s));
-  const int top_k = m->sample_topk >= g->V ? 0 : m->sample_topk;   // k >= V keeps every column: off
-  const double top_p = m->sample_topp;
+  const int top_k = m->sw.sample_topk >= g->V ? 0 : m->sw.sample_topk;   // k >= V keeps every column: off
+  const double top_p = m->sw.sample_topp;
   VD_TRY(gen_batch_steps(g, m, L, tok, nullptr, 1, [&](int step, float* logits) {
     if (top_k > 0 || top_p < 1.0)
       return vd_sample_draw_trunc_p(logits, g->Vp, n, (int)g->V, tok, u + (size_t)(step - 1) * n, T, top_k, top_p, step, L, end, hist, loglik,

@@ -11,13 +11,11 @@
 // No arithmetic lives here: every tensor op is one of the operator-level launches of this same library.
 //   rt_core.h      model object, helpers, nn.Linear / CatLinear / nn.SeqLSTM building blocks
 //   rt_encoders.h  the 11 encoder plug-ins        rt_decoders.h  disc, gen + the forwardBackward / retrieve branches
+//   rt_switches.h  the environment's switches of vd_model_create (host-only)
 //
 // Streams: main (option LSTM, criterion, decoder, optimiser), enc (encoder chains under a disc decoder), img (per-image
 // projection + masks; also the history branch of lf-* / hre-*), tab (token sort + table gradient), copy (H2D uploads
 // of the NEXT batch; two batch slots).
-#include <errno.h>
-#include <float.h>
-
 #include "rt_decoders.h"
 
 using namespace vdrt;
@@ -311,140 +309,13 @@ int vd_model_create(const vd_model_params* p, const char* encoder, const char* d
   VD_CHECK_ARG(p->dropout >= 0.f && p->dropout < 1.f, "vd_model_create: dropout must lie in [0, 1)");
   const int flags = vd_precision_flags(p->lstmBf16);
   VD_CHECK_ARG(flags >= 0, "vd_model_create: lstmBf16 must be 0, 1, 3, 6 or 9 (got %d)", p->lstmBf16);
-  // answer-encoding cache (include/visdial_hip.h at vd_model_retrieve): 0 / unset = off, 1 = default capacity, larger = rows
-  long cache_rows = 0;
-  if (const char* e = getenv("VD_OPTION_CACHE")) {
-    const long v = atol(e);
-    cache_rows = v <= 0 ? 0 : v == 1 ? VD_OPTION_CACHE_DEFAULT_ROWS : v;
-  }
-  VD_CHECK_ARG(!cache_rows || std::string(decoder) == "disc",
-               "vd_model_create: VD_OPTION_CACHE caches the candidate encodings of decoder 'disc'; this model's decoder is '%s'", decoder);
-  VD_CHECK_ARG(!cache_rows || p->lstmBf16 != 1,
-               "vd_model_create: VD_OPTION_CACHE needs the state-only option recurrence, which the compact bf16 recurrence (lstmBf16 = 1) "
-               "does not have");
-  VD_CHECK_ARG(cache_rows < (1L << 30), "vd_model_create: VD_OPTION_CACHE = %ld rows is out of range", cache_rows);
-  // prefix-tree scoring of generative retrieval (include/visdial_hip.h at vd_model_retrieve_lhood): 0 / unset = off
-  bool lhood_tree = false;
-  if (const char* e = getenv("VD_LHOOD_TREE")) lhood_tree = atol(e) > 0;
-  VD_CHECK_ARG(!lhood_tree || std::string(decoder) == "gen",
-               "vd_model_create: VD_LHOOD_TREE scores the candidates of decoder 'gen' over a prefix tree; this model's decoder is '%s'", decoder);
-  VD_CHECK_ARG(!lhood_tree || p->lstmBf16 != 1,
-               "vd_model_create: VD_LHOOD_TREE runs the exact fp32 tree recurrence (VD_FLAG_TREE), which the compact bf16 recurrence "
-               "(lstmBf16 = 1) does not have");
-  // top-k / nucleus truncation of vd_model_sample (include/visdial_hip.h there): VD_SAMPLE_TOPK = an integer >= 0 (0 / unset = off),
-  // VD_SAMPLE_TOPP = a real in (0, 1] (1 / unset = off); anything else is refused.  Decoder disc has no sampling: ignored there.
-  int sample_topk = 0;
-  double sample_topp = 1.0;
-  if (std::string(decoder) == "gen") {
-    if (const char* e = getenv("VD_SAMPLE_TOPK")) {
-      char* end = nullptr;
-      errno = 0;
-      const long v = strtol(e, &end, 10);
-      VD_CHECK_ARG(*e && end && !*end && errno == 0 && v >= 0 && v <= INT32_MAX,
-                   "vd_model_create: VD_SAMPLE_TOPK = '%s' must be an integer >= 0 (0 = off)", e);
-      sample_topk = (int)v;
-    }
-    if (const char* e = getenv("VD_SAMPLE_TOPP")) {
-      char* end = nullptr;
-      const double v = strtod(e, &end);
-      VD_CHECK_ARG(*e && end && !*end && v > 0.0 && v <= 1.0,   // a NaN fails both comparisons
-                   "vd_model_create: VD_SAMPLE_TOPP = '%s' must be a real in (0, 1] (1 = off)", e);
-      sample_topp = v;
-    }
-  }
-  // diverse beam search of vd_model_beam_search (include/visdial_hip.h there): VD_BEAM_GROUPS = an integer >= 1 (1 / unset = off),
-  // VD_BEAM_DIVERSITY = a finite real >= 0 (unset = 0.5); anything else is refused.  Decoder disc has no beam search: ignored there.
-  int beam_groups = 1;
-  double beam_diversity = 0.5;
-  if (std::string(decoder) == "gen") {
-    if (const char* e = getenv("VD_BEAM_GROUPS")) {
-      char* end = nullptr;
-      errno = 0;
-      const long v = strtol(e, &end, 10);
-      VD_CHECK_ARG(*e && end && !*end && errno == 0 && v >= 1 && v <= INT32_MAX,
-                   "vd_model_create: VD_BEAM_GROUPS = '%s' must be an integer >= 1 (1 = off)", e);
-      beam_groups = (int)v;
-    }
-    if (const char* e = getenv("VD_BEAM_DIVERSITY")) {
-      char* end = nullptr;
-      const double v = strtod(e, &end);
-      VD_CHECK_ARG(*e && end && !*end && v >= 0.0 && v <= (double)FLT_MAX,   // a NaN fails both comparisons; lambda is applied in fp32
-                   "vd_model_create: VD_BEAM_DIVERSITY = '%s' must be a finite real >= 0", e);
-      beam_diversity = v;
-    }
-  }
-  // the constraints of vd_model_beam_search (beam.hip C1-C6): VD_BEAM_MIN_LEN / VD_BEAM_NO_REPEAT = an integer >= 0, VD_BEAM_LENGTH_PENALTY
-  // = a finite real >= 0; 0 / unset = off, anything else is refused.  Ignored for decoder disc.
-  int beam_min_len = 0, beam_no_repeat = 0;
-  double beam_length_penalty = 0.0;
-  if (std::string(decoder) == "gen") {
-    const char* const names[2] = {"VD_BEAM_MIN_LEN", "VD_BEAM_NO_REPEAT"};
-    int* const into[2] = {&beam_min_len, &beam_no_repeat};
-    for (int i = 0; i < 2; ++i) {
-      if (const char* e = getenv(names[i])) {
-        char* end = nullptr;
-        errno = 0;
-        const long v = strtol(e, &end, 10);
-        VD_CHECK_ARG(*e && end && !*end && errno == 0 && v >= 0 && v <= INT32_MAX, "vd_model_create: %s = '%s' must be an integer >= 0 (0 = off)",
-                     names[i], e);
-        *into[i] = (int)v;
-      }
-    }
-    if (const char* e = getenv("VD_BEAM_LENGTH_PENALTY")) {
-      char* end = nullptr;
-      const double v = strtod(e, &end);
-      VD_CHECK_ARG(*e && end && !*end && v >= 0.0 && v <= DBL_MAX,           // a NaN fails both comparisons
-                   "vd_model_create: VD_BEAM_LENGTH_PENALTY = '%s' must be a finite real >= 0 (0 = off)", e);
-      beam_length_penalty = v;
-    }
-  }
-  // rollout of vd_model_beam_search (include/visdial_hip.h there; beam.hip R1-R6): VD_BEAM_ROLLOUT = 1 / 0 (0 / unset = off); anything else
-  // is refused, and so is 1 with VD_BEAM_GROUPS > 1 (the choice among a round's groups is the host's).  Ignored for decoder disc.
-  bool beam_rollout = false;
-  if (std::string(decoder) == "gen") {
-    if (const char* e = getenv("VD_BEAM_ROLLOUT")) {
-      VD_CHECK_ARG((e[0] == '0' || e[0] == '1') && !e[1], "vd_model_create: VD_BEAM_ROLLOUT = '%s' must be 1 or 0 (0 = off)", e);
-      beam_rollout = e[0] == '1';
-    }
-    VD_CHECK_ARG(!beam_rollout || beam_groups == 1,
-                 "vd_model_create: VD_BEAM_ROLLOUT = 1 with VD_BEAM_GROUPS = %d: a rollout feeds ONE answer per round back, and the choice "
-                 "among a round's groups is the host's", beam_groups);
-  }
-  // rollout of vd_model_retrieve (include/visdial_hip.h there; beam.hip E1-E5): VD_RETRIEVE_ROLLOUT = 1 / 0 (0 / unset = off); anything else
-  // is refused, and so is 1 with VD_OPTION_CACHE.  Ignored for decoder gen, whose rollout is VD_BEAM_ROLLOUT.
-  bool retrieve_rollout = false;
-  if (std::string(decoder) == "disc") {
-    if (const char* e = getenv("VD_RETRIEVE_ROLLOUT")) {
-      VD_CHECK_ARG((e[0] == '0' || e[0] == '1') && !e[1], "vd_model_create: VD_RETRIEVE_ROLLOUT = '%s' must be 1 or 0 (0 = off)", e);
-      retrieve_rollout = e[0] == '1';
-    }
-    VD_CHECK_ARG(!retrieve_rollout || cache_rows == 0,
-                 "vd_model_create: VD_RETRIEVE_ROLLOUT = 1 with VD_OPTION_CACHE: a cached batch carries only the candidate rows the cache did "
-                 "not hold, and the rollout reads a picked candidate's tokens from the batch; combining the two is left for a follow-up");
-  }
-  // encoder of a rollout's passes 1 .. R - 1 (rt_encoders.h forward_round): VD_ROLLOUT_ENCODER = full / round (unset = full); anything else
-  // is refused.  `round` is kept only where a rollout applies: with neither rollout variable set, or an encoder without a history, both
-  // calls already run the plain search / retrieval and the value is ignored.
-  bool rollout_round = false;
-  if (const char* e = getenv("VD_ROLLOUT_ENCODER")) {
-    VD_CHECK_ARG(!strcmp(e, "full") || !strcmp(e, "round"), "vd_model_create: VD_ROLLOUT_ENCODER = '%s' must be 'full' or 'round' (unset = full)", e);
-    rollout_round = !strcmp(e, "round") && (beam_rollout || retrieve_rollout) && has(en, "hist");
-  }
+  Switches sw;   // the environment's switches (rt_switches.h): a refused value touches no device and leaves no model behind
+  VD_TRY(parse_switches(encoder, decoder, p->lstmBf16, &sw));
   vd_model* m = new vd_model();
   m->p = *p;
-  m->beam_rollout = beam_rollout;
-  m->retrieve_rollout = retrieve_rollout;
-  m->rollout_round = rollout_round;
-  m->sample_topk = sample_topk;
-  m->sample_topp = sample_topp;
-  m->beam_groups = beam_groups;
-  m->beam_diversity = beam_diversity;
-  m->beam_min_len = beam_min_len;
-  m->beam_no_repeat = beam_no_repeat;
-  m->beam_length_penalty = beam_length_penalty;
+  m->sw = sw;
   m->flags = flags;
-  m->ocache.capacity = cache_rows;
-  m->lhood_tree = lhood_tree;
+  m->ocache.capacity = sw.option_cache_rows;
   if (m->p.numAttentionLayers < 1 || has(en, "lf-att")) m->p.numAttentionLayers = 1;   // (lf-att-ques-im-hist.lua:49 hard-codes one hop)
   if (m->p.numLayers < 1) m->p.numLayers = 2;        // opts.lua:27
   m->enc_name = encoder;
@@ -700,10 +571,10 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
   const bool hist_wave = !m->is_graph && m->p.numLayers == 2;
   // VD_BEAM_ROLLOUT / VD_RETRIEVE_ROLLOUT: history rows >= 1 at full width (upload_tokens), and a history row has to hold a whole question
   // (beam.hip R2)
-  const bool rollout = m->beam_rollout || m->retrieve_rollout;
+  const bool rollout = m->sw.beam_rollout || m->sw.retrieve_rollout;
   VD_CHECK_ARG(!(rollout && m->use_hist) || hb->Th >= hb->Tq,
                "vd_model_upload_batch: %s = 1 needs a history width Th = %d >= the question width Tq = %d",
-               m->beam_rollout ? "VD_BEAM_ROLLOUT" : "VD_RETRIEVE_ROLLOUT", hb->Th, hb->Tq);
+               m->sw.beam_rollout ? "VD_BEAM_ROLLOUT" : "VD_RETRIEVE_ROLLOUT", hb->Th, hb->Tq);
   if (m->use_hist) VD_TRY(upload_tokens(sl, sl.h, "h", hb->hist, N, hb->Th, m->is_graph || hist_wave, s, rollout ? R : 0));
   if (m->use_im) {
     // [B x S*S x C] for the attention encoders (model.lua:262-265 keeps one map per image), [B x F] otherwise
@@ -782,7 +653,7 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
   if (!disc && hb->option_in && hb->option_out) {                                               // model.lua:393-399
     VD_TRY(upload_tokens(sl, sl.oin, "oin", hb->option_in, (int)NO, hb->To, false, s));
     VD_TRY(upload_tokens(sl, sl.oout, "oout", hb->option_out, (int)NO, hb->To, false, s));
-    if (m->lhood_tree) VD_TRY(build_lhood_tree(m, sl, hb->option_in, hb->option_out, N, O, hb->To, s));
+    if (m->sw.lhood_tree) VD_TRY(build_lhood_tree(m, sl, hb->option_in, hb->option_out, N, O, hb->To, s));
   }
   sl.has_gt = hb->answer_ind != nullptr;
   sl.gt_host.assign(N, 0);

@@ -13,6 +13,37 @@ from .split_eval import SplitEval
 call = _lib.call
 
 
+def _text(v):
+    return None if v is None else str(v)
+
+
+def _int0(v):
+    return int(v or 0)
+
+
+SWITCHES = (
+    # params key, variable, text of the params value, type and default of the resolved value, decoder it applies to (None = both)
+    ('optionCache', 'VD_OPTION_CACHE', lambda v: str(_int0(v)), _int0, 0, None),          # 0 = off, 1 = on, larger = capacity in rows
+    ('fusedLhood', 'VD_LHOOD_TREE', lambda v: '1' if _int0(v) == 2 else '0', _int0, 0, None),   # 2 = retrieval over a prefix tree
+    ('topK', 'VD_SAMPLE_TOPK', _text, int, 0, 'gen'),                                     # truncation inside vd_model_sample
+    ('topP', 'VD_SAMPLE_TOPP', _text, float, 1.0, 'gen'),
+    ('beamGroups', 'VD_BEAM_GROUPS', _text, int, 1, 'gen'),                               # diverse search inside vd_model_beam_search
+    ('beamDiversity', 'VD_BEAM_DIVERSITY', _text, float, 0.5, None),                      # (kept for disc too: only looked at when G > 1)
+    ('beamMinLen', 'VD_BEAM_MIN_LEN', _text, int, 0, 'gen'),                              # the constraints of vd_model_beam_search
+    ('beamNoRepeat', 'VD_BEAM_NO_REPEAT', _text, int, 0, 'gen'),
+    ('beamLengthPenalty', 'VD_BEAM_LENGTH_PENALTY', _text, float, 0.0, 'gen'),
+    ('beamRollout', 'VD_BEAM_ROLLOUT', _text, int, 0, 'gen'),                             # the search rolls its answers into the history
+    ('retrieveRollout', 'VD_RETRIEVE_ROLLOUT', _text, int, 0, 'disc'),                    # vd_model_retrieve rolls its picks into it
+    ('rolloutEncoder', 'VD_ROLLOUT_ENCODER', _text, str, 'full', None),                   # 'round': passes 1 .. R - 1 encode one round
+)
+"""The switches the library reads from the environment inside vd_model_create (csrc/rt_switches.h; the Lua host sets the same variables).
+NativeModel sets every row's variable to the text of its params value -- unset where that is None: a params without the key creates the
+model with the variable unset -- creates the model and puts the previous environment back, also after a failed create, so two models of
+one process can differ.  Python validates nothing: the values go through as written and the library is the one that refuses.  What the
+model was created with stays in `NativeModel._knobs` (the default for a row of the other decoder, which the library does not read);
+generateAnswers checks what it is asked for against it."""
+
+
 class _DevArray(object):
     """a raw device pointer as something torch.as_tensor understands (plumbing for torch.distributed only)"""
 
@@ -67,58 +98,23 @@ class NativeModel(SplitEval):
             dropout=float(p.get('dropout', 0.5)))
         self.params = p
         h = C.c_void_p()
-        # params optionCache (0 = off, 1 = on, larger = capacity in rows): the answer-encoding cache of disc evaluation.  The library reads
-        # its switch from the environment when the model is created (the Lua host sets the same variable); the previous value comes
-        # back right after, so two models of one process can differ.
-        # params fusedLhood = 2: generative retrieval over a prefix tree of the candidates' tokens (VD_LHOOD_TREE, read the same way);
-        # fusedLhood = 1 and 0 create the model without it
-        # params topK / topP: top-k / nucleus truncation inside vd_model_sample (VD_SAMPLE_TOPK / VD_SAMPLE_TOPP, read the same way).  The
-        # values go through as written -- the library is the one that refuses a negative k, a p outside (0, 1] or text (decoder gen) -- and a
-        # params without them creates the model with the variables unset.  generateAnswers(sampleBatch > 0) checks its knobs against these.
-        # params beamGroups / beamDiversity: diverse beam search inside vd_model_beam_search (VD_BEAM_GROUPS / VD_BEAM_DIVERSITY, read and
-        # refused the same way); generateAnswers(beamBatch > 0) checks its knobs against these.
-        # params beamMinLen / beamNoRepeat / beamLengthPenalty: the constraints of vd_model_beam_search (VD_BEAM_MIN_LEN / VD_BEAM_NO_REPEAT /
-        # VD_BEAM_LENGTH_PENALTY), the same way again.
-        # params beamRollout: vd_model_beam_search rolls the model's own answers into the history (VD_BEAM_ROLLOUT), the same way again;
-        # generateAnswers(beamBatch > 0) checks its `rollout` against it.
-        # params retrieveRollout: vd_model_retrieve of decoder disc ranks every round on a history of the model's own picks
-        # (VD_RETRIEVE_ROLLOUT), the same way again; `retrieve_rollout_batch` is then one upload and one call.
-        # params rolloutEncoder ('full' / 'round'): the encoder of passes 1 .. R - 1 of either rollout (VD_ROLLOUT_ENCODER), the same way again:
-        # 'round' encodes the round a pass answers alone; the library refuses any other value and ignores 'round' where nothing rolls out.
         import os
-        switches = {'VD_OPTION_CACHE': str(int(p.get('optionCache', 0) or 0)),
-                    'VD_LHOOD_TREE': '1' if int(p.get('fusedLhood', 0) or 0) == 2 else '0',
-                    'VD_SAMPLE_TOPK': None if p.get('topK') is None else str(p['topK']),
-                    'VD_SAMPLE_TOPP': None if p.get('topP') is None else str(p['topP']),
-                    'VD_BEAM_GROUPS': None if p.get('beamGroups') is None else str(p['beamGroups']),
-                    'VD_BEAM_DIVERSITY': None if p.get('beamDiversity') is None else str(p['beamDiversity']),
-                    'VD_BEAM_MIN_LEN': None if p.get('beamMinLen') is None else str(p['beamMinLen']),
-                    'VD_BEAM_NO_REPEAT': None if p.get('beamNoRepeat') is None else str(p['beamNoRepeat']),
-                    'VD_BEAM_LENGTH_PENALTY': None if p.get('beamLengthPenalty') is None else str(p['beamLengthPenalty']),
-                    'VD_BEAM_ROLLOUT': None if p.get('beamRollout') is None else str(p['beamRollout']),
-                    'VD_RETRIEVE_ROLLOUT': None if p.get('retrieveRollout') is None else str(p['retrieveRollout']),
-                    'VD_ROLLOUT_ENCODER': None if p.get('rolloutEncoder') is None else str(p['rolloutEncoder'])}
+        switches = {var: text(p.get(key)) for key, var, text, _, _, _ in SWITCHES}
+
+        def put(values):
+            for k, v in values.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
         prev = {k: os.environ.get(k) for k in switches}
         try:
-            for k, v in switches.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
+            put(switches)
             call("vd_model_create", C.byref(mp), p['encoder'].encode(), p['decoder'].encode(), C.byref(h))
         finally:
-            for k, v in prev.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
-        gen = p['decoder'] == 'gen'
-        self._sample_knobs = (int(p.get('topK') or 0) if gen else 0, float(1.0 if p.get('topP') is None or not gen else p['topP']))
-        self._beam_knobs = (int(p.get('beamGroups') or 1) if gen else 1, float(0.5 if p.get('beamDiversity') is None else p['beamDiversity']))
-        self._beam_limits = (int(p.get('beamMinLen') or 0), int(p.get('beamNoRepeat') or 0), float(p.get('beamLengthPenalty') or 0.0)) if gen \
-            else (0, 0, 0.0)
-        self._rollout_knob = int(p.get('beamRollout') or 0) if gen else 0
-        self._retrieve_rollout_knob = 0 if gen else int(p.get('retrieveRollout') or 0)
+            put(prev)
+        self._knobs = {key: default if p.get(key) is None or decoder not in (None, p['decoder']) else conv(p[key])
+                       for key, _, _, conv, default, decoder in SWITCHES}
         self.h = h
         lib = _lib.load()
         self.tensors = []
@@ -350,7 +346,7 @@ class NativeModel(SplitEval):
         slot -- and vd_model_retrieve (params fusedLhood: _lhood) on that slot.  Any other model: the host loop."""
         self._rollout_answers = None
         gen = self.params['decoder'] == 'gen'
-        if 'hist' not in batch or not (self._rollout_knob if gen else self._retrieve_rollout_knob):
+        if 'hist' not in batch or not self._knobs['beamRollout' if gen else 'retrieveRollout']:
             return SplitEval.retrieve_rollout_batch(self, batch)
         self.upload(batch)
         N, O = self._N, int(self.params.get('numOptions', 100))
@@ -407,7 +403,7 @@ class NativeModel(SplitEval):
         """the batched beam search (beamBatch > 0) of every round of the last `_gen_encode` batch: vd_model_beam_search.  Returns (tokens
         [N x beamLen], scores [N]); a model created with params beamGroups = G > 1 returns every group's answer, (tokens
         [N x G x beamLen], scores [N x G])."""
-        N, G = int(self._N), self._beam_knobs[0]
+        N, G = int(self._N), self._knobs['beamGroups']
         tokens = np.zeros((N * G, int(beamLen)), np.int32)
         scores = np.zeros(N * G, np.float64)
         call("vd_model_beam_search", self.h, int(beamSize), int(beamLen), int(startToken), int(endToken), tokens.ctypes.data,
@@ -416,30 +412,27 @@ class NativeModel(SplitEval):
             return tokens.reshape(N, G, int(beamLen)), scores.reshape(N, G)
         return tokens, scores
 
+    def _created_with(self, batch, taker, noun, asked, compare=None, say=None):
+        """the values generateAnswers asks for, {params key: value}, against the ones the model was created with"""
+        made = {k: self._knobs[k] for k in asked}
+        asked = {k: type(made[k])(v) for k, v in asked.items()}
+        if any(asked[k] != made[k] for k in compare or asked):
+            show = lambda d, names: ' / '.join(('%s = %d' if isinstance(v, int) else '%s = %g') % (n, v) for n, v in zip(names, d.values()))
+            raise ValueError("%s > 0 with %s, but this model was created with %s: the device %s takes its %s when the model is created "
+                             "(params %s of NativeModel)" % (batch, show(asked, say or asked), show(made, made), taker, noun, ' / '.join(made)))
+
     def _beam_grouping(self, groups, diversity):
-        G, lam = self._beam_knobs
-        if int(groups) != G or (G > 1 and float(diversity) != lam):
-            raise ValueError("beamBatch > 0 with beamGroups = %d / beamDiversity = %g, but this model was created with beamGroups = %d / "
-                             "beamDiversity = %g: the device search takes its groups when the model is created (params beamGroups / "
-                             "beamDiversity of NativeModel)" % (int(groups), float(diversity), G, lam))
+        self._created_with('beamBatch', 'search', 'groups', dict(beamGroups=groups, beamDiversity=diversity),
+                           compare=None if self._knobs['beamGroups'] > 1 else ('beamGroups',))
 
     def _beam_constraints(self, minLen, noRepeat, lengthPenalty):
-        if (int(minLen), int(noRepeat), float(lengthPenalty)) != self._beam_limits:
-            raise ValueError("beamBatch > 0 with beamMinLen = %d / beamNoRepeat = %d / beamLengthPenalty = %g, but this model was created "
-                             "with beamMinLen = %d / beamNoRepeat = %d / beamLengthPenalty = %g: the device search takes its constraints "
-                             "when the model is created (params beamMinLen / beamNoRepeat / beamLengthPenalty of NativeModel)"
-                             % ((int(minLen), int(noRepeat), float(lengthPenalty)) + self._beam_limits))
+        self._created_with('beamBatch', 'search', 'constraints', dict(beamMinLen=minLen, beamNoRepeat=noRepeat, beamLengthPenalty=lengthPenalty))
 
     def _beam_rollout(self, rollout):
-        if int(rollout) != self._rollout_knob:
-            raise ValueError("beamBatch > 0 with rollout = %d, but this model was created with beamRollout = %d: the device search takes "
-                             "its rollout when the model is created (params beamRollout of NativeModel)" % (int(rollout), self._rollout_knob))
+        self._created_with('beamBatch', 'search', 'rollout', dict(beamRollout=rollout), say=('rollout',))
 
     def _sample_truncation(self, topK, topP):
-        if (int(topK), float(topP)) != self._sample_knobs:
-            raise ValueError("sampleBatch > 0 with topK = %d / topP = %g, but this model was created with topK = %d / topP = %g: the "
-                             "device sampler takes its truncation when the model is created (params topK / topP of NativeModel)"
-                             % ((int(topK), float(topP)) + self._sample_knobs))
+        self._created_with('sampleBatch', 'sampler', 'truncation', dict(topK=topK, topP=topP))
 
     def _gen_sample(self, beamLen, startToken, endToken, temperature, uniforms):
         """the batched temperature sampling (sampleBatch > 0) of every round of the last `_gen_encode` batch with the host's
