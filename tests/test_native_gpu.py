@@ -115,22 +115,16 @@ def test_native_refuses_unknown_precision(gpu):
     assert not h.value
 
 
-@pytest.mark.parametrize("enc,dec", [(e, d) for e in ALL_ENC for d in ('disc', 'gen')
-                                     if (e, d) != ('mn-att-ques-im-hist', 'disc')])     # that pair: tests above
-@pytest.mark.parametrize("case", ['tiny', 'mid'])
-def test_native_all_pairs_match_oracle(gpu, enc, dec, case):
-    """every encoder x decoder plug-in pair through the MODEL-LEVEL ABI (what lua/model.lua calls): loss, every gradient
-    tensor, forward-only mode, one Adam step -- against the fp64 oracle.  tiny: training mode with pinned dropout masks;
-    mid: evaluate mode at H = 512 / 100 options."""
+def pair_matches_oracle(p, pinned):
+    """one step of p's encoder x decoder pair through the MODEL-LEVEL ABI (what lua/model.lua calls): loss, every gradient tensor,
+    forward-only mode, one Adam step -- against the fp64 oracle.  pinned: training mode with pinned dropout masks (evaluate mode for a
+    pair without a dropout site), else evaluate mode."""
     from visdial_amd.native import NativeModel
-    kw = dict(WIDE[case])
-    if 'att' in enc:
-        kw.update(imgFeatureSize=32 if case == 'tiny' else 512, imgSpatialSize=3 if case == 'tiny' else 7)
-    p = derive(small_params(encoder=enc, decoder=dec, **kw))
+    enc, dec = p['encoder'], p['decoder']
     batch = SyntheticDataloader(p, seed=21).getTrainBatch(p)
     model = NativeModel(p, init_seed=17)
     assert [t[0] for t in model.tensors] == [e[0] for e in vo.param_spec(enc, dec, p)]
-    masks = fuse_masks(p, batch, np.random.RandomState(8)) if case == 'tiny' else None
+    masks = fuse_masks(p, batch, np.random.RandomState(8)) if pinned else None
     if masks is not None:
         model.set_dropout_masks(masks)
     else:
@@ -141,7 +135,6 @@ def test_native_all_pairs_match_oracle(gpu, enc, dec, case):
     ref = vo.forward_backward(enc, dec, P0, p, batch, drop)
     assert abs(loss - ref['loss']) < 1e-4 * max(1.0, abs(ref['loss']))
     g = model.get_gradients_dict()
-    gnorm = max(np.abs(v).max() for v in ref['grads'].values())
     bad = grad_mismatches(g, ref['grads'])
     assert not bad, bad
     # forward-only (Model:evaluate path, model.lua:128): same loss, gradients untouched
@@ -155,6 +148,29 @@ def test_native_all_pairs_match_oracle(gpu, enc, dec, case):
         w2, _ = vo.clamp_adam(P0[k].reshape(-1), g[k].astype(np.float64).reshape(-1), {}, p['learningRate'])
         assert np.abs(after[k].reshape(-1) - w2).max() < 1e-6, k
     model.close()
+    return P0
+
+
+@pytest.mark.parametrize("enc,dec", [(e, d) for e in ALL_ENC for d in ('disc', 'gen')
+                                     if (e, d) != ('mn-att-ques-im-hist', 'disc')])     # that pair: tests above
+@pytest.mark.parametrize("case", ['tiny', 'mid'])
+def test_native_all_pairs_match_oracle(gpu, enc, dec, case):
+    """every encoder x decoder plug-in pair.  tiny: training mode with pinned dropout masks; mid: evaluate mode at H = 512 / 100
+    options."""
+    kw = dict(WIDE[case])
+    if 'att' in enc:
+        kw.update(imgFeatureSize=32 if case == 'tiny' else 512, imgSpatialSize=3 if case == 'tiny' else 7)
+    pair_matches_oracle(derive(small_params(encoder=enc, decoder=dec, **kw)), pinned=case == 'tiny')
+
+
+@pytest.mark.parametrize("dec", ['disc', 'gen'])
+@pytest.mark.parametrize("L", [1, 3])
+@pytest.mark.parametrize("enc", ['lf-ques-hist', 'lf-ques-im-hist', 'hre-ques-im-hist', 'hrea-ques-im-hist'])
+def test_native_history_branch_at_other_depths_matches_oracle(gpu, enc, L, dec):
+    """numLayers = 1 and 3, where the history branch of the Sequential encoders leaves the two-layer wavefront for one recurrence per
+    layer (csrc/rt_encoders.h HistoryBranch): the 'tiny' case of test_native_all_pairs_match_oracle at those depths"""
+    P0 = pair_matches_oracle(derive(small_params(encoder=enc, decoder=dec, numLayers=L, **WIDE['tiny'])), pinned=True)
+    assert sum(k.startswith('hist') and k.endswith('.W') for k in P0) == L
 
 
 @pytest.mark.parametrize("enc", ['lf-ques', 'lf-ques-im-hist', 'mn-att-ques-im-hist', 'hre-ques-im-hist', 'hrea-ques-im-hist'])

@@ -147,6 +147,19 @@ def test_gen_round_rollout_equals_the_host_loop(gpu, enc):
     assert dev[0].shape == (40, 6) and dev[1].shape == (40,)
 
 
+@pytest.mark.parametrize("enc", ['lf-ques-im-hist', 'hre-ques-hist'])
+def test_gen_round_rollout_at_three_layers_equals_the_host_loop(gpu, enc):
+    """numLayers = 3: the round pass of the history branch runs one vd_lstm_forward per layer instead of the two-layer wavefront"""
+    p, batch, START, END = gen_setting(enc)
+    p = dict(p, numLayers=3)
+    plain = G.native(p)
+    assert 'hist3.W' in plain.get_parameters_dict()
+    host = G.host_rollout(plain, batch, 3, 6, START, END)
+    plain.close()
+    dev = gen_round(p, batch, START, END, host, what='%s, 3 layers, round' % enc)
+    assert dev[0].shape == (40, 6) and dev[1].shape == (40,)
+
+
 @pytest.mark.parametrize("edge", ['constraints', 'Th = Tq', 'missing rounds'])
 def test_gen_round_rollout_at_the_edges(gpu, edge):
     enc = 'lf-ques-im-hist'

@@ -1,6 +1,10 @@
 // Native step runtime, part 2: the encoder plug-ins (reference encoders/<name>.lua, 11 files) as launch orders over the
 // operator-level entry points.  Mirrors visdial_amd/encoders/_blocks.py, _late_fusion.py, _hre.py and the four
 // nngraph encoder files.  Included by runtime.hip only.
+//   WaveStack      one two-layer length-sorted maskZero stack; wave_forward / wave_backward launch n of them as one wavefront
+//   TextBranches   the history + question stacks of the nngraph encoders (n = 2)
+//   HistoryBranch  hist1..histL of the Sequential encoders: the wavefront (n = 1) at two layers, one recurrence per layer otherwise
+//   history_round  the history branch of a round pass, every family
 #pragma once
 #include "rt_core.h"
 
@@ -23,6 +27,13 @@ struct Encoder {
   virtual int forward_round(vd_model* m, hipStream_t s, BatchSlot& b, int r, float** out) {
     vd_set_error("encoder '%s' has no history: a rollout never asks it for a round pass", m->enc_name.c_str());
     return VD_ERR_STATE;
+  }
+  float* out_ = nullptr;   // what the last forward() returned: a round pass writes its rows into it
+  // the precondition of a round pass; `state` = what else the encoder keeps from pass 0
+  int round_ready(vd_model* m, const BatchSlot& b, bool state = true) const {
+    const int N = b.q.N, R = m->p.maxQuesCount;
+    VD_CHECK_ARG(out_ && state && N == N / R * R && b.h.N == N, "round pass without a full encoder pass on this batch");
+    return VD_OK;
   }
   // enc.rnnLayers of the Sequential encoders (read by decoders/gen.lua:31-35,46-52); null for the nngraph encoders
   virtual std::vector<SeqLSTM>* rnnLayers() { return nullptr; }
@@ -51,181 +62,150 @@ inline int causal_mask(vd_model* m, int B, int R, uint8_t** out) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// history + question branches of the nngraph encoders: shared embedding -> Dropout(0.5) -> 2 x SeqLSTM(maskZero) ->
-// Select(1,-1) (mn-att:21-45).  Both stacks advance together as one skewed wavefront on length-sorted rows.
+// One text stack: shared embedding [-> Dropout(0.5)] -> 2 x SeqLSTM(maskZero) -> Select(1,-1), on rows sorted by length at upload
+// (right-aligned input: the leading pad steps of the shorter rows are skipped, maskZero's zero state is what they would produce).  Both
+// layers advance as ONE skewed wavefront (vd_lstm2_forward_p / vd_lstm2_backward_p: T + 1 launches instead of 2 T), several stacks per
+// launch; weight gradients run over the non-pad (t, row) pairs.
+//   the nngraph encoders (mn-att:21-45): history + question stacks in one launch, Dropout behind the embedding (TextBranches)
+//   the Sequential encoders (lf-ques-hist.lua:38-45, lf-ques-im-hist.lua:38-45, hre-*.lua:30-38): the history stack at the default two
+//   layers, no Dropout (HistoryBranch).  At lf-ques-im-hist's Th <= 300 (the concatenated dialog, dataloader.lua:243-255) it IS the step
+//   (configs[1]).
 // ------------------------------------------------------------------------------------------------------------
+struct WaveStack {
+  SeqLSTM *l1 = nullptr, *l2 = nullptr;
+  std::string tag;            // workspace tag: "h" or "q"
+  bool drop = false;          // the nn.Dropout(0.5) behind the shared embedding (mn-att:24-25)
+  uint8_t* mask = nullptr;    // its keep-mask of this step (null without `drop` and in evaluate mode)
+
+  int prepare(vd_model* m, hipStream_t s, const SeqTok& ss) {
+    VD_CHECK_ARG(ss.sorted, "the '%s' stack (%s, %s) runs on length-sorted rows only", tag.c_str(), l1->name.c_str(), l2->name.c_str());
+    const long E = l1->D, H = l1->H;
+    const long TN = (long)ss.T * ss.N;
+    mask = nullptr;
+    if (drop) VD_TRY(drop_mask(m, tag + "_emb", (size_t)TN * E, 0.5f, s, &mask));
+    float *x, *xs;
+    VD_TRY(ws_get(m, tag + ".x", (size_t)TN * E, &x));
+    VD_TRY(ws_get(m, tag + ".xs", (size_t)TN * E, &xs));
+    VD_TRY(l1->alloc(m, ss.T, ss.N));
+    VD_TRY(l2->alloc(m, ss.T, ss.N));
+    l1->h0 = l1->c0 = l2->h0 = l2->c0 = nullptr;
+    VD_TRY(vd_embed_gather(Wp(m, "embed"), ss.tok, mask, x, TN, (int)E, drop ? 2.0f : 1.0f, s));
+    VD_TRY(vd_embed_gather(x, ss.fwd_idx, nullptr, xs, TN, (int)E, 1.0f, s));      // permute rows per step (length sort)
+    VD_TRY(vd_gemm_nn(xs, E, l1->Wx(m), 4 * H, Wp(m, l1->name + ".b"), l1->gates, 4 * H, (int)TN, (int)(4 * H), (int)E, 0, s));
+    // skipped (t, row) pairs must read as zeros: previous state of rows that become active later, da = 0 in the
+    // weight-gradient contractions.  Only the skipped pairs, all six buffers in one launch: the active rows are written by the
+    // recurrence before anything reads them
+    VdZeroSet z{{l1->gates, l1->h, l1->c, l2->h, l2->c, l2->gates}, {(int)(4 * H), (int)H, (int)H, (int)H, (int)H, (int)(4 * H)}, 6, 0};
+    VD_TRY(vd_zero_inactive_multi(z, ss.nact_dev, ss.T, ss.N, s));
+    l1->xs = {xs};
+    l2->xs = {l1->h};
+    l1->rows = l2->rows = &ss;
+    return VD_OK;
+  }
+  // T steps of N rows through the layers' weights on the buffers {layer 1, layer 2} of gates / h / c; nact = null: every row at every step
+  static void fill_fwd(vd_model* m, const SeqLSTM& l1, const SeqLSTM& l2, int T, int N, const int32_t* tok_mask, const int32_t* nact,
+                       float* const* gates, float* const* h, float* const* c, vd_lstm2_fwd_t* o) {
+    o->T = T; o->N = N;
+    o->tok_mask = tok_mask;
+    o->Wh1 = l1.Wh(m); o->Wx2 = l2.Wx(m); o->b2 = Wp(m, l2.name + ".b"); o->Wh2 = l2.Wh(m);
+    o->gates1 = gates[0]; o->h1 = h[0]; o->c1 = c[0]; o->gates2 = gates[1]; o->h2 = h[1]; o->c2 = c[1];
+    o->nact = nact;
+  }
+  void fill_fwd(vd_model* m, const SeqTok& ss, vd_lstm2_fwd_t* o) const {
+    float *gates[2] = {l1->gates, l2->gates}, *h[2] = {l1->h, l2->h}, *c[2] = {l1->c, l2->c};
+    fill_fwd(m, *l1, *l2, ss.T, ss.N, ss.tok_sorted, ss.nact.data(), gates, h, c, o);
+  }
+  // also requests <l1>.dhseq, <l1>.dc and <l2>.dc; dlast = the gradient of the top layer's last state, in sorted row order
+  int fill_bwd(vd_model* m, const SeqTok& ss, const float* dlast, vd_lstm2_bwd_t* o) const {
+    const long H = l1->H;
+    float *dhseq, *dc1, *dc2;
+    VD_TRY(ws_get(m, l1->name + ".dhseq", (size_t)ss.T * ss.N * H, &dhseq));
+    VD_TRY(ws_get(m, l1->name + ".dc", (size_t)ss.N * H, &dc1));
+    VD_TRY(ws_get(m, l2->name + ".dc", (size_t)ss.N * H, &dc2));
+    o->T = ss.T; o->N = ss.N;
+    o->Wh1 = l1->Wh(m); o->Wx2 = l2->Wx(m); o->Wh2 = l2->Wh(m);
+    o->gates1 = l1->gates; o->c1 = l1->c; o->gates2 = l2->gates; o->c2 = l2->c;
+    o->dh_last2 = dlast;
+    o->dh1_seq = dhseq; o->dc1 = dc1; o->dc2 = dc2;
+    o->nact = ss.nact.data();
+    return VD_OK;
+  }
+  // Select(1,-1) of the top layer, back to batch order, into <tag>.last
+  int gather_last(vd_model* m, hipStream_t s, const SeqTok& ss, float** last) const {
+    const long H = l2->H;
+    VD_TRY(ws_get(m, tag + ".last", (size_t)ss.N * H, last));
+    return vd_embed_gather(l2->out_at(ss.T - 1), ss.inv, nullptr, *last, ss.N, (int)H, 1.f, s);
+  }
+  // its gradient, into sorted row order, into <tag>.dlast
+  int gather_dlast(vd_model* m, hipStream_t s, const SeqTok& ss, const float* dlast, float** sorted) const {
+    const long H = l2->H;
+    VD_TRY(ws_get(m, tag + ".dlast", (size_t)ss.N * H, sorted));
+    return vd_embed_gather(dlast, ss.perm, nullptr, *sorted, ss.N, (int)H, 1.f, s);
+  }
+  // behind the recurrences only parameter gradients are left: layer 2, layer 1, the embedding rows
+  int param_tail(vd_model* m, hipStream_t s, const SeqTok& ss) const {
+    const long E = l1->D, TN = (long)ss.T * ss.N;
+    std::vector<float*> dx;
+    float* dxo;
+    VD_TRY(l2->param_grads(m, s, {false}, nullptr));
+    VD_TRY(l1->param_grads(m, s, {true}, &dx));
+    VD_TRY(ws_get(m, tag + ".dxo", (size_t)TN * E, &dxo));
+    VD_TRY(vd_embed_gather(dx[0], ss.inv_idx, nullptr, dxo, TN, (int)E, 1.f, s));     // back to batch order
+    return vd_embed_scatter_acc(Gp(m, "embed"), ss.tok, mask, dxo, TN, (int)E, drop ? 2.f : 1.f, s);
+  }
+};
+
+// n <= 2 stacks as one wavefront.  last[k] / dlast[k]: the top layer's last state of stack k and its gradient [N x H], batch order.
+// wave_backward ends behind the recurrences: the caller runs every stack's param_tail on the stream it chooses.
+inline int wave_forward(vd_model* m, hipStream_t s, WaveStack* const* st, const SeqTok* const* ss, int n, float** last) {
+  vd_lstm2_fwd_t fw[2];
+  for (int k = 0; k < n; ++k) VD_TRY(st[k]->prepare(m, s, *ss[k]));
+  for (int k = 0; k < n; ++k) st[k]->fill_fwd(m, *ss[k], &fw[k]);
+  VD_TRY(vd_lstm2_forward_p(fw, n, (int)st[0]->l1->H, tick_flags(m), s));
+  for (int k = 0; k < n; ++k) VD_TRY(st[k]->gather_last(m, s, *ss[k], &last[k]));
+  return VD_OK;
+}
+inline int wave_backward(vd_model* m, hipStream_t s, WaveStack* const* st, const SeqTok* const* ss, int n, const float* const* dlast) {
+  vd_lstm2_bwd_t bw[2];
+  float* sorted[2];
+  for (int k = 0; k < n; ++k) VD_TRY(st[k]->gather_dlast(m, s, *ss[k], dlast[k], &sorted[k]));
+  for (int k = 0; k < n; ++k) VD_TRY(st[k]->fill_bwd(m, *ss[k], sorted[k], &bw[k]));
+  return vd_lstm2_backward_p(bw, n, (int)st[0]->l1->H, tick_flags(m), s);
+}
+
+// history + question branches of the nngraph encoders (mn-att:21-45)
 struct TextBranches {
   SeqLSTM hist1, hist2, ques1, ques2;
-  long E = 0, H = 0;
-  uint8_t *m_q = nullptr, *m_h = nullptr;
-  float *xs_q = nullptr, *xs_h = nullptr;
+  WaveStack hist{&hist1, &hist2, "h", true}, ques{&ques1, &ques2, "q", true};
   static void declare(vd_model* m) {
     const long E = m->p.embedSize, H = m->p.rnnHiddenSize;
     add_lstm(m, "hist1", E, H); add_lstm(m, "hist2", H, H); add_lstm(m, "ques1", E, H); add_lstm(m, "ques2", H, H);
   }
   void init(vd_model* m) {
-    E = m->p.embedSize; H = m->p.rnnHiddenSize;
+    const long E = m->p.embedSize, H = m->p.rnnHiddenSize;
     hist1.init("hist1", E, H); hist2.init("hist2", H, H); ques1.init("ques1", E, H); ques2.init("ques2", H, H);
   }
-  // drop: the nn.Dropout(0.5) behind the shared embedding of the nngraph encoders (mn-att:24-25); the Sequential encoders have none
-  static int prepare(vd_model* m, hipStream_t s, const SeqTok& ss, const std::string& tag, SeqLSTM& l1, SeqLSTM& l2, uint8_t** mask_out,
-                     float** xs_out, bool drop = true) {
-    const long E = l1.D, H = l1.H;
-    const long TN = (long)ss.T * ss.N;
-    uint8_t* mk = nullptr;
-    if (drop) VD_TRY(drop_mask(m, tag + "_emb", (size_t)TN * E, 0.5f, s, &mk));
-    float *x, *xs;
-    VD_TRY(ws_get(m, tag + ".x", (size_t)TN * E, &x));
-    VD_TRY(ws_get(m, tag + ".xs", (size_t)TN * E, &xs));
-    VD_TRY(l1.alloc(m, ss.T, ss.N));
-    VD_TRY(l2.alloc(m, ss.T, ss.N));
-    l1.h0 = l1.c0 = l2.h0 = l2.c0 = nullptr;
-    VD_TRY(vd_embed_gather(Wp(m, "embed"), ss.tok, mk, x, TN, (int)E, drop ? 2.0f : 1.0f, s));
-    VD_TRY(vd_embed_gather(x, ss.fwd_idx, nullptr, xs, TN, (int)E, 1.0f, s));      // permute rows per step (length sort)
-    VD_TRY(vd_gemm_nn(xs, E, l1.Wx(m), 4 * H, Wp(m, l1.name + ".b"), l1.gates, 4 * H, (int)TN, (int)(4 * H), (int)E, 0, s));
-    // skipped (t, row) pairs must read as zeros: previous state of rows that become active later, da = 0 in the
-    // weight-gradient contractions
-    if (ss.sorted) {
-      // only the skipped pairs, all six buffers in one launch: the active rows are written by the recurrence before anything reads them
-      VdZeroSet z{{l1.gates, l1.h, l1.c, l2.h, l2.c, l2.gates}, {(int)(4 * H), (int)H, (int)H, (int)H, (int)H, (int)(4 * H)}, 6, 0};
-      VD_TRY(vd_zero_inactive_multi(z, ss.nact_dev, ss.T, ss.N, s));
-    } else {
-      VD_TRY(vd_zero_inactive_rows(l1.gates, (int64_t)ss.N * 4 * H, 4 * H, (int)(4 * H), ss.nact_dev, ss.T, ss.N, s));
-      VD_TRY(vd_memset(l1.h, 0, TN * H * 4, s));
-      VD_TRY(vd_memset(l1.c, 0, TN * H * 4, s));
-      VD_TRY(vd_memset(l2.h, 0, TN * H * 4, s));
-      VD_TRY(vd_memset(l2.c, 0, TN * H * 4, s));
-      VD_TRY(vd_memset(l2.gates, 0, TN * 4 * H * 4, s));
-    }
-    l1.xs = {xs};
-    l2.xs = {l1.h};
-    l1.rows = l2.rows = ss.sorted ? &ss : nullptr;
-    *mask_out = mk;
-    *xs_out = xs;
-    return VD_OK;
-  }
-  static void fill_fwd(vd_model* m, const SeqTok& ss, SeqLSTM& l1, SeqLSTM& l2, vd_lstm2_fwd_t* o) {
-    o->T = ss.T; o->N = ss.N;
-    o->tok_mask = ss.tok_sorted;
-    o->Wh1 = l1.Wh(m); o->Wx2 = l2.Wx(m); o->b2 = Wp(m, l2.name + ".b"); o->Wh2 = l2.Wh(m);
-    o->gates1 = l1.gates; o->h1 = l1.h; o->c1 = l1.c; o->gates2 = l2.gates; o->h2 = l2.h; o->c2 = l2.c;
-    o->nact = ss.nact.data();
-  }
   int forward(vd_model* m, hipStream_t s, BatchSlot& b, float** q3, float** h3) {
-    const int N = b.q.N;
-    VD_TRY(prepare(m, s, b.h, "h", hist1, hist2, &m_h, &xs_h));
-    VD_TRY(prepare(m, s, b.q, "q", ques1, ques2, &m_q, &xs_q));
-    vd_lstm2_fwd_t fw[2];
-    fill_fwd(m, b.h, hist1, hist2, &fw[0]);
-    fill_fwd(m, b.q, ques1, ques2, &fw[1]);
-    VD_TRY(vd_lstm2_forward_p(fw, 2, (int)H, tick_flags(m), s));
-    float *hl, *ql;
-    VD_TRY(ws_get(m, "h.last", (size_t)N * H, &hl));
-    VD_TRY(ws_get(m, "q.last", (size_t)N * H, &ql));
-    VD_TRY(vd_embed_gather(hist2.out_at(b.h.T - 1), b.h.inv, nullptr, hl, N, (int)H, 1.f, s));   // Select(1,-1), back to batch order
-    VD_TRY(vd_embed_gather(ques2.out_at(b.q.T - 1), b.q.inv, nullptr, ql, N, (int)H, 1.f, s));
-    *q3 = ql;
-    *h3 = hl;
+    WaveStack* st[2] = {&hist, &ques};
+    const SeqTok* ss[2] = {&b.h, &b.q};
+    float* last[2];
+    VD_TRY(wave_forward(m, s, st, ss, 2, last));
+    *h3 = last[0];
+    *q3 = last[1];
     return VD_OK;
   }
   int backward(vd_model* m, hipStream_t s, BatchSlot& b, const float* dq3, const float* dh3) {
-    const int N = b.q.N;
-    float *dh3s, *dq3s;
-    VD_TRY(ws_get(m, "h.dlast", (size_t)N * H, &dh3s));
-    VD_TRY(ws_get(m, "q.dlast", (size_t)N * H, &dq3s));
-    VD_TRY(vd_embed_gather(dh3, b.h.perm, nullptr, dh3s, N, (int)H, 1.f, s));
-    VD_TRY(vd_embed_gather(dq3, b.q.perm, nullptr, dq3s, N, (int)H, 1.f, s));
-    vd_lstm2_bwd_t bw[2];
-    SeqLSTM* L1[2] = {&hist1, &ques1};
-    SeqLSTM* L2[2] = {&hist2, &ques2};
+    WaveStack* st[2] = {&hist, &ques};
     const SeqTok* ss[2] = {&b.h, &b.q};
-    const float* dl[2] = {dh3s, dq3s};
-    for (int k = 0; k < 2; ++k) {
-      const size_t TN = (size_t)ss[k]->T * N;
-      float *dhseq, *dc1, *dc2;
-      VD_TRY(ws_get(m, L1[k]->name + ".dhseq", TN * H, &dhseq));
-      VD_TRY(ws_get(m, L1[k]->name + ".dc", (size_t)N * H, &dc1));
-      VD_TRY(ws_get(m, L2[k]->name + ".dc", (size_t)N * H, &dc2));
-      bw[k].T = ss[k]->T; bw[k].N = N;
-      bw[k].Wh1 = L1[k]->Wh(m); bw[k].Wx2 = L2[k]->Wx(m); bw[k].Wh2 = L2[k]->Wh(m);
-      bw[k].gates1 = L1[k]->gates; bw[k].c1 = L1[k]->c; bw[k].gates2 = L2[k]->gates; bw[k].c2 = L2[k]->c;
-      bw[k].dh_last2 = dl[k];
-      bw[k].dh1_seq = dhseq; bw[k].dc1 = dc1; bw[k].dc2 = dc2;
-      bw[k].nact = ss[k]->nact.data();
-    }
-    VD_TRY(vd_lstm2_backward_p(bw, 2, (int)H, tick_flags(m), s));
-    const uint8_t* mk[2] = {m_h, m_q};
-    const char* tag[2] = {"h", "q"};
+    const float* dlast[2] = {dh3, dq3};
+    VD_TRY(wave_backward(m, s, st, ss, 2, dlast));
     hipStream_t sw;
     VD_TRY(wg_fork(m, s, &sw));                 // the recurrences are done: only parameter gradients are left
-    for (int k = 0; k < 2; ++k) {
-      const long TN = (long)ss[k]->T * N;
-      std::vector<float*> dx;
-      VD_TRY(L2[k]->param_grads(m, sw, {false}, nullptr));
-      VD_TRY(L1[k]->param_grads(m, sw, {true}, &dx));
-      float* dxo;
-      VD_TRY(ws_get(m, std::string(tag[k]) + ".dxo", (size_t)TN * E, &dxo));
-      VD_TRY(vd_embed_gather(dx[0], ss[k]->inv_idx, nullptr, dxo, TN, (int)E, 1.f, sw));     // back to batch order
-      VD_TRY(vd_embed_scatter_acc(Gp(m, "embed"), ss[k]->tok, mk[k], dxo, TN, (int)E, 2.f, sw));
-    }
+    for (int k = 0; k < 2; ++k) VD_TRY(st[k]->param_tail(m, sw, *ss[k]));
     return VD_OK;
   }
 };
 
-// The history branch of the Sequential encoders (encoders/lf-ques-hist.lua:38-45, lf-ques-im-hist.lua:38-45, hre-*.lua:30-38):
-// numLayers x SeqLSTM:maskZero() whose only consumer is Select(1,-1) of the top layer.  With the default two layers it runs like
-// the text branches of the nngraph encoders: rows sorted by length at upload (right-aligned input: the leading pad steps of the
-// shorter rows are skipped, maskZero's zero state is what they would produce), both layers as ONE skewed wavefront
-// (vd_lstm2_forward / vd_lstm2_backward: T + 1 launches instead of 2 T), weight gradients over the non-pad (t, row) pairs.  At
-// lf-ques-im-hist's Th <= 300 (the concatenated dialog, dataloader.lua:243-255) that branch IS the step (configs[1]).
-struct HistWave {
-  float *xs = nullptr;
-  static bool usable(const BatchSlot& b, const std::vector<SeqLSTM>& hist) { return hist.size() == 2 && b.h.sorted; }
-  int forward(vd_model* m, hipStream_t s, BatchSlot& b, SeqLSTM& l1, SeqLSTM& l2, const float** last) {
-    const int N = b.h.N;
-    const long H = l1.H;
-    uint8_t* mk;
-    VD_TRY(TextBranches::prepare(m, s, b.h, "h", l1, l2, &mk, &xs, false));
-    vd_lstm2_fwd_t fw;
-    TextBranches::fill_fwd(m, b.h, l1, l2, &fw);
-    VD_TRY(vd_lstm2_forward_p(&fw, 1, (int)H, tick_flags(m), s));
-    float* hl;
-    VD_TRY(ws_get(m, "h.last", (size_t)N * H, &hl));
-    VD_TRY(vd_embed_gather(l2.out_at(b.h.T - 1), b.h.inv, nullptr, hl, N, (int)H, 1.f, s));   // Select(1,-1), back to batch order
-    *last = hl;
-    return VD_OK;
-  }
-  int backward(vd_model* m, hipStream_t s, BatchSlot& b, SeqLSTM& l1, SeqLSTM& l2, const float* dlast) {
-    const int N = b.h.N;
-    const long H = l1.H, E = l1.D;
-    const size_t TN = (size_t)b.h.T * N;
-    float *dls, *dhseq, *dc1, *dc2, *dxo;
-    VD_TRY(ws_get(m, "h.dlast", (size_t)N * H, &dls));
-    VD_TRY(vd_embed_gather(dlast, b.h.perm, nullptr, dls, N, (int)H, 1.f, s));
-    VD_TRY(ws_get(m, l1.name + ".dhseq", TN * H, &dhseq));
-    VD_TRY(ws_get(m, l1.name + ".dc", (size_t)N * H, &dc1));
-    VD_TRY(ws_get(m, l2.name + ".dc", (size_t)N * H, &dc2));
-    vd_lstm2_bwd_t bw;
-    bw.T = b.h.T; bw.N = N;
-    bw.Wh1 = l1.Wh(m); bw.Wx2 = l2.Wx(m); bw.Wh2 = l2.Wh(m);
-    bw.gates1 = l1.gates; bw.c1 = l1.c; bw.gates2 = l2.gates; bw.c2 = l2.c;
-    bw.dh_last2 = dls;
-    bw.dh1_seq = dhseq; bw.dc1 = dc1; bw.dc2 = dc2;
-    bw.nact = b.h.nact.data();
-    VD_TRY(vd_lstm2_backward_p(&bw, 1, (int)H, tick_flags(m), s));
-    std::vector<float*> dx;
-    VD_TRY(l2.param_grads(m, s, {false}, nullptr));
-    VD_TRY(l1.param_grads(m, s, {true}, &dx));
-    VD_TRY(ws_get(m, "h.dxo", TN * E, &dxo));
-    VD_TRY(vd_embed_gather(dx[0], b.h.inv_idx, nullptr, dxo, (long)TN, (int)E, 1.f, s));       // back to batch order
-    return vd_embed_scatter_acc(Gp(m, "embed"), b.h.tok, nullptr, dxo, (long)TN, (int)E, 1.f, s);
-  }
-};
-
-// The history branch of a round pass (Encoder::forward_round), every encoder family: history row r of the B dialogs as a B-row sequence at
-// full width -- step-major [Th x B], every row active at every step, maskZero per token (a rollout model lays rows >= 1 out at full width
-// anyway, runtime.hip upload_tokens) -- through the branch's layers: the two-layer wavefront, or one recurrence per layer for another
-// depth.  *last = the top layer's final state [B x H].  Th + 4 launches with two layers.
 inline int rows_copy(float* dst, long dst_ld, const float* src, long src_ld, long rows, int cols, hipStream_t s) {
   const int64_t ld = src_ld;
   return vd_rows_cat_p(dst, dst_ld, &src, &ld, &cols, 1, rows, s);
@@ -234,7 +214,13 @@ inline int round_linear(vd_model* m, hipStream_t s, const std::string& name, con
                         float* y, long ldy) {
   return vd_gemm_nt(x, ldx, Wp(m, name + ".W"), in, Wp(m, name + ".b"), y, ldy, rows, (int)out, (int)in, tanh ? VD_ACT_TANH : VD_ACT_NONE, 0, s);
 }
-inline int hist_round(vd_model* m, hipStream_t s, BatchSlot& b, const std::vector<const SeqLSTM*>& layers, int r, const float** last) {
+// The history branch of a round pass (Encoder::forward_round), every encoder family: history row r of the B dialogs as a B-row sequence at
+// full width -- step-major [Th x B], every row active at every step, maskZero per token (a rollout model lays rows >= 1 out at full width
+// anyway, runtime.hip upload_tokens) -- through the branch's layers: the two-layer wavefront, or one recurrence per layer for another
+// depth.  *last = the top layer's final state [B x H], also copied into rows d * R + r of `cache` [N x H], pass 0's last states (null: no
+// copy).  Th + 4 launches with two layers, and the copy.
+inline int history_round(vd_model* m, hipStream_t s, BatchSlot& b, const std::vector<const SeqLSTM*>& layers, int r, float* cache,
+                         const float** last) {
   const int N = b.h.N, Th = b.h.T, R = m->p.maxQuesCount, B = N / R, L = (int)layers.size();
   const long E = layers[0]->D, H = layers[0]->H, TB = (long)Th * B;
   VD_CHECK_ARG(b.h.present && N == B * R && r >= 1 && r < R && L >= 1, "round pass %d of %d rounds over %d history rows", r, R, N);
@@ -253,11 +239,7 @@ inline int hist_round(vd_model* m, hipStream_t s, BatchSlot& b, const std::vecto
   VD_TRY(vd_gemm_nn(x, E, layers[0]->Wx(m), 4 * H, Wp(m, layers[0]->name + ".b"), gates[0], 4 * H, (int)TB, (int)(4 * H), (int)E, 0, s));
   if (L == 2) {
     vd_lstm2_fwd_t fw;
-    fw.T = Th; fw.N = B;
-    fw.tok_mask = tok;
-    fw.Wh1 = layers[0]->Wh(m); fw.Wx2 = layers[1]->Wx(m); fw.b2 = Wp(m, layers[1]->name + ".b"); fw.Wh2 = layers[1]->Wh(m);
-    fw.gates1 = gates[0]; fw.h1 = h[0]; fw.c1 = c[0]; fw.gates2 = gates[1]; fw.h2 = h[1]; fw.c2 = c[1];
-    fw.nact = nullptr;
+    WaveStack::fill_fwd(m, *layers[0], *layers[1], Th, B, tok, nullptr, gates.data(), h.data(), c.data(), &fw);
     VD_TRY(vd_lstm2_forward_p(&fw, 1, (int)H, tick_flags(m), s));
   } else {
     for (int l = 0; l < L; ++l) {
@@ -268,7 +250,69 @@ inline int hist_round(vd_model* m, hipStream_t s, BatchSlot& b, const std::vecto
     }
   }
   *last = h[L - 1] + (long)(Th - 1) * B * H;
+  if (cache) VD_TRY(rows_copy(cache + (long)r * H, (long)R * H, *last, H, B, (int)H, s));
   return VD_OK;
+}
+
+// The history branch of the Sequential encoders (encoders/lf-ques-hist.lua:38-45, lf-ques-im-hist.lua:38-45, hre-*.lua:30-38):
+// numLayers x SeqLSTM:maskZero() whose only consumer is Select(1,-1) of the top layer.  Two layers, on the rows the upload then sorts
+// (runtime.hip vd_model_upload_batch): one WaveStack, its parameter tail on the caller's stream.  Any other depth: the embedding gathered
+// into "h.x" and one recurrence per layer.  The caller forks and joins the stream it hands in.
+struct HistoryBranch {
+  std::vector<SeqLSTM> hist;
+  WaveStack wave;
+  void declare(vd_model* m) {
+    const long E = m->p.embedSize, H = m->p.rnnHiddenSize;
+    hist.resize(m->p.numLayers);
+    for (size_t l = 0; l < hist.size(); ++l) {
+      add_lstm(m, "hist" + std::to_string(l + 1), l == 0 ? E : H, H);
+      hist[l].init("hist" + std::to_string(l + 1), l == 0 ? E : H, H);
+    }
+    if (hist.size() == 2) wave = WaveStack{&hist[0], &hist[1], "h", false};
+  }
+  bool waved(const BatchSlot& b) const { return hist.size() == 2 && b.h.sorted; }
+  // *last = the top layer's last state [N x H] in batch order: "h.last" on the wavefront path, the top layer's last step otherwise
+  int forward(vd_model* m, hipStream_t s, BatchSlot& b, float** last) {
+    if (waved(b)) {
+      WaveStack* st = &wave;
+      const SeqTok* ss = &b.h;
+      return wave_forward(m, s, &st, &ss, 1, last);
+    }
+    const int N = b.h.N, Th = b.h.T;
+    const long E = hist[0].D;
+    float *hx, *ht;
+    VD_TRY(ws_get(m, "h.x", (size_t)Th * N * E, &hx));
+    VD_TRY(vd_embed_gather(Wp(m, "embed"), b.h.tok, nullptr, hx, (long)Th * N, (int)E, 1.f, s));
+    VD_TRY(lstm_stack_forward(m, s, hist, {hx}, Th, N, b.h.tok, &ht));
+    *last = hist.back().out_at(Th - 1);
+    return VD_OK;
+  }
+  // ends in the scatter into the embedding gradient
+  int backward(vd_model* m, hipStream_t s, BatchSlot& b, const float* dlast) {
+    if (waved(b)) {
+      WaveStack* st = &wave;
+      const SeqTok* ss = &b.h;
+      VD_TRY(wave_backward(m, s, &st, &ss, 1, &dlast));
+      return wave.param_tail(m, s, b.h);
+    }
+    std::vector<float*> dx;
+    VD_TRY(lstm_stack_backward(m, s, hist, dlast, nullptr, &dx));
+    return vd_embed_scatter_acc(Gp(m, "embed"), b.h.tok, nullptr, dx[0], (long)b.h.T * b.h.N, (int)hist[0].D, 1.f, s);
+  }
+  int round(vd_model* m, hipStream_t s, BatchSlot& b, int r, float* cache, const float** hl) {
+    std::vector<const SeqLSTM*> layers;
+    for (const SeqLSTM& l : hist) layers.push_back(&l);
+    return history_round(m, s, b, layers, r, cache, hl);
+  }
+};
+
+// img [B x F] -> "img.rep" [N x F]: the image row of every round (model.lua:262-265)
+inline int image_repeat(vd_model* m, hipStream_t s, const BatchSlot& b, int N, float** out) {
+  const int R = m->p.maxQuesCount, F = m->p.imgFeatureSize;
+  int32_t* rep;
+  VD_TRY(round_index(m, N, R, &rep));
+  VD_TRY(ws_get(m, "img.rep", (size_t)N * F, out));
+  return vd_embed_gather(b.img, rep, nullptr, *out, N, F, 1.f, s);
 }
 
 // nn.MM(false,true) -> MaskSoftMax -> nn.MM -> Tanh(Linear(Dropout)) -> Tanh(Linear(hAttTr + query)) (mn-att:48-65)
@@ -472,7 +516,6 @@ struct GraphEncoder : Encoder {
   MemoryBlock memory;
   SANBlock san;
   CatLinear qi, qh;
-  float* out_ = nullptr;   // what the last forward() returned: a round pass writes its rows into it
   explicit GraphEncoder(const std::string& name) {
     memory_ = name.rfind("mn", 0) == 0;
     san_ = name.find("att") != std::string::npos;
@@ -493,7 +536,7 @@ struct GraphEncoder : Encoder {
     if (qh_) qh.init("qh", {H, H}, H);
   }
   int forward(vd_model* m, hipStream_t s, BatchSlot& b, float** out) override {
-    const int N = b.q.N, R = m->p.maxQuesCount;
+    const int N = b.q.N;
     if (san_) VD_TRY(san.prefetch(m, s, b, N));
     float *q3, *h3;
     VD_TRY(text.forward(m, s, b, &q3, &h3));
@@ -503,11 +546,8 @@ struct GraphEncoder : Encoder {
     } else {
       const float* query = q3;
       if (qi_) {                                                                   // mn-ques-im-hist.lua:47-48
-        int32_t* rep;
         float *img_rep, *qp;
-        VD_TRY(round_index(m, N, R, &rep));
-        VD_TRY(ws_get(m, "img.rep", (size_t)N * m->p.imgFeatureSize, &img_rep));
-        VD_TRY(vd_embed_gather(b.img, rep, nullptr, img_rep, N, m->p.imgFeatureSize, 1.f, s));
+        VD_TRY(image_repeat(m, s, b, N, &img_rep));
         VD_TRY(qi.forward(m, s, {q3, img_rep}, N, nullptr, 1.f, &qp));
         query = qp;
       }
@@ -519,14 +559,13 @@ struct GraphEncoder : Encoder {
   }
   int forward_round(vd_model* m, hipStream_t s, BatchSlot& b, int r, float** out) override {
     const int N = b.q.N, R = m->p.maxQuesCount, B = N / R;
-    const long H = text.H, F = m->p.imgFeatureSize;
-    VD_CHECK_ARG(out_ && N == B * R && b.h.N == N, "round pass without a full encoder pass on this batch");
+    const long H = m->p.rnnHiddenSize, F = m->p.imgFeatureSize;
+    VD_TRY(round_ready(m, b));
     const float* hl;
-    VD_TRY(hist_round(m, s, b, {&text.hist1, &text.hist2}, r, &hl));
     float *hc, *qc;
     VD_TRY(ws_get(m, "h.last", (size_t)N * H, &hc));
     VD_TRY(ws_get(m, "q.last", (size_t)N * H, &qc));
-    VD_TRY(rows_copy(hc + (long)r * H, (long)R * H, hl, H, B, (int)H, s));          // the facts of later rounds
+    VD_TRY(history_round(m, s, b, {&text.hist1, &text.hist2}, r, hc, &hl));         // into h.last too: the facts of later rounds
     const float* qr = qc + (long)r * H;                                            // round r of q.last in place: leading dimension R * H
     float* y = out_ + (long)r * H;
     float* u = nullptr;
@@ -594,12 +633,11 @@ struct GraphEncoder : Encoder {
 // ------------------------------------------------------------------------------------------------------------
 struct LateFusion : Encoder {
   bool use_im, use_hist;
-  std::vector<SeqLSTM> rnn, hist;
-  HistWave wave;
+  std::vector<SeqLSTM> rnn;
+  HistoryBranch hist;
   CatLinear fuse;
   long E = 0, H = 0, F = 0;
   float pdrop = 0.5f;
-  float* out_ = nullptr;   // what the last forward() returned: a round pass writes its rows into it
   LateFusion(bool im, bool hs) : use_im(im), use_hist(hs) {}
   void declare(vd_model* m) override {
     E = m->p.embedSize; H = m->p.rnnHiddenSize; F = m->p.imgFeatureSize; pdrop = m->p.dropout;
@@ -609,13 +647,7 @@ struct LateFusion : Encoder {
       add_lstm(m, "ques" + std::to_string(l + 1), l == 0 ? E : H, H);              // lf-ques-im-hist.lua:19-26
       rnn[l].init("ques" + std::to_string(l + 1), l == 0 ? E : H, H);
     }
-    if (use_hist) {
-      hist.resize(L);
-      for (int l = 0; l < L; ++l) {
-        add_lstm(m, "hist" + std::to_string(l + 1), l == 0 ? E : H, H);            // :38-45
-        hist[l].init("hist" + std::to_string(l + 1), l == 0 ? E : H, H);
-      }
-    }
+    if (use_hist) hist.declare(m);                                                 // :38-45
     std::vector<long> dims = {H};
     if (use_im) dims.push_back(F);
     if (use_hist) dims.push_back(H);
@@ -626,23 +658,14 @@ struct LateFusion : Encoder {
   }
   std::vector<SeqLSTM>* rnnLayers() override { return &rnn; }
   int forward(vd_model* m, hipStream_t s, BatchSlot& b, float** out) override {
-    const int N = b.q.N, Tq = b.q.T, R = m->p.maxQuesCount;
+    const int N = b.q.N, Tq = b.q.T;
     hipStream_t sh = side_stream(m, s);
-    const float* hh_last = nullptr;
+    float* hh_last = nullptr;
     if (use_hist) {
       VD_TRY(fork_stream(m, s, sh));
-      const int Th = b.h.T;
       const bool prof = m->dec_name == "gen";     // (disc pairs: ev_prof belongs to the option-LSTM families)
       if (prof) VD_HIP(hipEventRecord(m->ev_prof[0], sh));
-      if (HistWave::usable(b, hist)) {
-        VD_TRY(wave.forward(m, sh, b, hist[0], hist[1], &hh_last));
-      } else {
-        float *hx, *ht;
-        VD_TRY(ws_get(m, "h.x", (size_t)Th * N * E, &hx));
-        VD_TRY(vd_embed_gather(Wp(m, "embed"), b.h.tok, nullptr, hx, (long)Th * N, (int)E, 1.f, sh));
-        VD_TRY(lstm_stack_forward(m, sh, hist, {hx}, Th, N, b.h.tok, &ht));
-        hh_last = hist.back().out_at(Th - 1);
-      }
+      VD_TRY(hist.forward(m, sh, b, &hh_last));
       if (prof) VD_HIP(hipEventRecord(m->ev_prof[1], sh));
     }
     float *qx, *qt;
@@ -651,11 +674,8 @@ struct LateFusion : Encoder {
     VD_TRY(lstm_stack_forward(m, s, rnn, {qx}, Tq, N, b.q.tok, &qt));
     std::vector<const float*> parts = {rnn.back().out_at(Tq - 1)};
     if (use_im) {
-      int32_t* rep;
       float* img_rep;
-      VD_TRY(round_index(m, N, R, &rep));
-      VD_TRY(ws_get(m, "img.rep", (size_t)N * F, &img_rep));
-      VD_TRY(vd_embed_gather(b.img, rep, nullptr, img_rep, N, (int)F, 1.f, s));    // repeat per round
+      VD_TRY(image_repeat(m, s, b, N, &img_rep));
       parts.push_back(img_rep);
     }
     if (use_hist) {
@@ -670,16 +690,11 @@ struct LateFusion : Encoder {
   }
   int forward_round(vd_model* m, hipStream_t s, BatchSlot& b, int r, float** out) override {
     const int N = b.q.N, Tq = b.q.T, R = m->p.maxQuesCount, B = N / R;
-    VD_CHECK_ARG(use_hist && out_ && N == B * R && b.h.N == N, "round pass without a full encoder pass on this batch");
-    std::vector<const SeqLSTM*> layers;
-    for (const SeqLSTM& l : hist) layers.push_back(&l);
+    VD_TRY(round_ready(m, b, use_hist));
     const float* hl;
-    VD_TRY(hist_round(m, s, b, layers, r, &hl));
-    if (HistWave::usable(b, hist)) {                                               // (the h.last cache exists on the wavefront path only)
-      float* hc;
-      VD_TRY(ws_get(m, "h.last", (size_t)N * H, &hc));
-      VD_TRY(rows_copy(hc + (long)r * H, (long)R * H, hl, H, B, (int)H, s));
-    }
+    float* hc = nullptr;                                                           // (the h.last cache exists on the wavefront path only)
+    if (hist.waved(b)) VD_TRY(ws_get(m, "h.last", (size_t)N * H, &hc));
+    VD_TRY(hist.round(m, s, b, r, hc, &hl));
     // [question state of round r ; image ; history state] gathered by the join itself, then Linear + Tanh into the output rows
     float* cat;
     VD_TRY(ws_get(m, "rnd.fuse.cat", (size_t)B * fuse.D, &cat));
@@ -702,13 +717,7 @@ struct LateFusion : Encoder {
       VD_TRY(fork_stream(m, s, sh));
       const bool prof = m->dec_name == "gen";
       if (prof) VD_HIP(hipEventRecord(m->ev_prof[2], sh));
-      if (HistWave::usable(b, hist)) {
-        VD_TRY(wave.backward(m, sh, b, hist[0], hist[1], g.back()));
-      } else {
-        std::vector<float*> dx;
-        VD_TRY(lstm_stack_backward(m, sh, hist, g.back(), nullptr, &dx));
-        VD_TRY(vd_embed_scatter_acc(Gp(m, "embed"), b.h.tok, nullptr, dx[0], (long)b.h.T * b.h.N, (int)E, 1.f, sh));
-      }
+      VD_TRY(hist.backward(m, sh, b, g.back()));
       if (prof) VD_HIP(hipEventRecord(m->ev_prof[3], sh));
       m->prof_hist = prof;
     }
@@ -725,24 +734,20 @@ struct LateFusion : Encoder {
 // ------------------------------------------------------------------------------------------------------------
 struct Hre : Encoder {
   bool use_im, attention;
-  std::vector<SeqLSTM> rnn, hist;
-  HistWave wave;
+  std::vector<SeqLSTM> rnn;
+  HistoryBranch hist;
   SeqLSTM dialog;
   Linear img_embed;
   long E = 0, H = 0, F = 0, DI = 0;
   int R = 0;
   float *hh = nullptr, *hq = nullptr, *sq = nullptr, *sh_ = nullptr, *P = nullptr;
-  float* out_ = nullptr;   // what the last forward() returned: a round pass writes its rows into it
   uint8_t* m_img = nullptr;
   Hre(bool im, bool att) : use_im(im), attention(att) {}
   void declare(vd_model* m) override {
     E = m->p.embedSize; H = m->p.rnnHiddenSize; F = m->p.imgFeatureSize; DI = use_im ? m->p.imgEmbedSize : 0; R = m->p.maxQuesCount;
     const int L = m->p.numLayers;
-    hist.resize(L); rnn.resize(L);
-    for (int l = 0; l < L; ++l) {
-      add_lstm(m, "hist" + std::to_string(l + 1), l == 0 ? E : H, H);
-      hist[l].init("hist" + std::to_string(l + 1), l == 0 ? E : H, H);
-    }
+    rnn.resize(L);
+    hist.declare(m);
     if (use_im) {
       add_linear(m, "img_embed", F, DI);
       img_embed.init("img_embed", F, DI);
@@ -761,42 +766,30 @@ struct Hre : Encoder {
   }
   std::vector<SeqLSTM>* rnnLayers() override { return &rnn; }
   // round-major <-> dialog-major row permutations (nn.View + nn.Transpose({1,2}), hre:88-93)
-  int indices(vd_model* m, int N, int32_t** rep, int32_t** to_rb, int32_t** to_n) {
+  int indices(vd_model* m, int N, int32_t** to_rb, int32_t** to_n) {
     const int B = N / R;
     std::vector<int32_t> a(N), c(N);
     for (int n = 0; n < N; ++n) {
       a[n] = (n % B) * R + n / B;   // row r*B+b  <- n = b*R + r
       c[n] = (n % R) * B + n / R;   // row b*R+r  <- r*B + b
     }
-    VD_TRY(round_index(m, N, R, rep));
     VD_TRY(index_array(m, "idx.to_rb." + std::to_string(N), a, to_rb));
     return index_array(m, "idx.to_n." + std::to_string(N), c, to_n);
   }
   int forward(vd_model* m, hipStream_t s, BatchSlot& b, float** out) override {
-    const int N = b.q.N, Tq = b.q.T, Th = b.h.T, B = N / R;
-    int32_t *rep, *to_rb, *to_n;
-    VD_TRY(indices(m, N, &rep, &to_rb, &to_n));
+    const int N = b.q.N, Tq = b.q.T, B = N / R;
+    int32_t *to_rb, *to_n;
+    VD_TRY(indices(m, N, &to_rb, &to_n));
     hipStream_t sh = side_stream(m, s);
     VD_TRY(fork_stream(m, s, sh));
-    if (HistWave::usable(b, hist)) {
-      const float* last;
-      VD_TRY(wave.forward(m, sh, b, hist[0], hist[1], &last));
-      hh = const_cast<float*>(last);
-    } else {
-      float *hx, *ht;
-      VD_TRY(ws_get(m, "h.x", (size_t)Th * N * E, &hx));
-      VD_TRY(vd_embed_gather(Wp(m, "embed"), b.h.tok, nullptr, hx, (long)Th * N, (int)E, 1.f, sh));
-      VD_TRY(lstm_stack_forward(m, sh, hist, {hx}, Th, N, b.h.tok, &ht));
-      hh = hist.back().out_at(Th - 1);
-    }
+    VD_TRY(hist.forward(m, sh, b, &hh));
     float* qx;
     VD_TRY(ws_get(m, "q.x", (size_t)Tq * N * E, &qx));
     VD_TRY(vd_embed_gather(Wp(m, "embed"), b.q.tok, nullptr, qx, (long)Tq * N, (int)E, 1.f, s));
     std::vector<const float*> x = {qx};
     if (use_im) {
       float *img_rep, *imgE, *xi;
-      VD_TRY(ws_get(m, "img.rep", (size_t)N * F, &img_rep));
-      VD_TRY(vd_embed_gather(b.img, rep, nullptr, img_rep, N, (int)F, 1.f, s));
+      VD_TRY(image_repeat(m, s, b, N, &img_rep));
       m_img = nullptr;
       if (attention) VD_TRY(drop_mask(m, "img", (size_t)N * F, 0.5f, s, &m_img));          // hrea:47
       const float* img_in;
@@ -836,12 +829,9 @@ struct Hre : Encoder {
   }
   int forward_round(vd_model* m, hipStream_t s, BatchSlot& b, int r, float** out) override {
     const int N = b.q.N, B = N / R;
-    VD_CHECK_ARG(out_ && hh && hq && N == B * R && b.h.N == N && dialog.T == R && dialog.N == B, "round pass without a full encoder pass on this batch");
-    std::vector<const SeqLSTM*> layers;
-    for (const SeqLSTM& l : hist) layers.push_back(&l);
+    VD_TRY(round_ready(m, b, hh && hq && dialog.T == R && dialog.N == B));
     const float* hl;
-    VD_TRY(hist_round(m, s, b, layers, r, &hl));
-    VD_TRY(rows_copy(hh + (long)r * H, (long)R * H, hl, H, B, (int)H, s));          // hrea attends over it in later rounds
+    VD_TRY(hist.round(m, s, b, r, hh, &hl));                                        // into hh too: hrea attends over it in later rounds
     const float *first = hq + (long)r * H, *second = hl;                           // round r of the question state in place
     long ld1 = (long)R * H, ld2 = H;
     if (attention) {                                                               // hrea:83-131; sq is pass 0's, sh of the new rows is not
@@ -864,8 +854,8 @@ struct Hre : Encoder {
   }
   int backward(vd_model* m, hipStream_t s, BatchSlot& b, const float* grad_out) override {
     const int N = b.q.N, Tq = b.q.T, B = N / R;
-    int32_t *rep, *to_rb, *to_n;
-    VD_TRY(indices(m, N, &rep, &to_rb, &to_n));
+    int32_t *to_rb, *to_n;
+    VD_TRY(indices(m, N, &to_rb, &to_n));
     float *g_rb, *dfirst, *dsecond;
     VD_TRY(ws_get(m, "hre.g_rb", (size_t)N * H, &g_rb));
     VD_TRY(ws_get(m, "hre.dfirst", (size_t)N * H, &dfirst));
@@ -895,13 +885,7 @@ struct Hre : Encoder {
     }
     hipStream_t sh = side_stream(m, s);
     VD_TRY(fork_stream(m, s, sh));
-    if (HistWave::usable(b, hist)) {
-      VD_TRY(wave.backward(m, sh, b, hist[0], hist[1], dh));
-    } else {
-      std::vector<float*> dx;
-      VD_TRY(lstm_stack_backward(m, sh, hist, dh, nullptr, &dx));
-      VD_TRY(vd_embed_scatter_acc(Gp(m, "embed"), b.h.tok, nullptr, dx[0], (long)b.h.T * N, (int)E, 1.f, sh));
-    }
+    VD_TRY(hist.backward(m, sh, b, dh));
     std::vector<float*> dx;
     VD_TRY(lstm_stack_backward(m, s, rnn, dq, nullptr, &dx));
     // the two scatters into the shared embedding gradient use float atomics: concurrent streams are fine

@@ -567,7 +567,7 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
   const long NO = (long)N * O;
   for (SeqTok* t : {&sl.q, &sl.h, &sl.opt, &sl.ain, &sl.aout, &sl.oin, &sl.oout}) t->present = false;
   VD_TRY(upload_tokens(sl, sl.q, "q", hb->ques_fwd, N, hb->Tq, m->is_graph, s));
-  // the history branch of the Sequential encoders runs as a length-sorted two-layer wavefront too (rt_encoders.h: HistWave)
+  // the history branch of the Sequential encoders runs as a length-sorted two-layer wavefront too (rt_encoders.h: HistoryBranch)
   const bool hist_wave = !m->is_graph && m->p.numLayers == 2;
   // VD_BEAM_ROLLOUT / VD_RETRIEVE_ROLLOUT: history rows >= 1 at full width (upload_tokens), and a history row has to hold a whole question
   // (beam.hip R2)
