@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import attention_ref as ar
 from oracle import visdial_oracle as vo
 
 pytestmark = pytest.mark.gpu
@@ -384,16 +385,8 @@ def test_image_attention(ops, use_drop):
     u0 = f32(rng, N, H)
     sc = 2.0 if use_drop else 1.0
     d64 = np.float64
-    img_tr = np.repeat(pre.reshape(B, 1, S2, H), R, 1).reshape(N * S2, H).astype(d64)
-    if use_drop:
-        img_tr = img_tr * m1 * 2.0
-    t_iqc = np.tanh(img_tr @ Wc.astype(d64).T + bc + np.repeat(qc.astype(d64), S2, 0))
-    iqc_ref = t_iqc * m2 * 2.0 if use_drop else t_iqc
-    score = (iqc_ref @ wa.astype(d64) + ba[0]).reshape(N, S2)
-    e = np.exp(score - score.max(1, keepdims=True))
-    p_ref = e / e.sum(1, keepdims=True)
-    att = np.einsum('ns,nsh->nh', p_ref, img_tr.reshape(N, S2, H))
-    u1_ref = att + u0
+    fwd = ar.img_forward(pre, m1, m2, Wc, bc, qc, wa, ba, u0, B, R, S2, sc)          # the fp64 restatement (tests/attention_ref.py)
+    img_tr, iqc_ref, p_ref, u1_ref = fwd['img_tr'], fwd['iqc'], fwd['p'], fwd['u1']
 
     pre_d, m1_d, m2_d = dev(pre), (dev(m1) if use_drop else None), (dev(m2) if use_drop else None)
     iqc = torch.empty(N * S2, Kc, device="cuda")
@@ -405,12 +398,8 @@ def test_image_attention(ops, use_drop):
     assert relerr(p, p_ref) < 1e-5 and relerr(u1, u1_ref) < 1e-5
 
     datt = f32(rng, N, H)
-    dp = np.einsum('nh,nsh->ns', datt.astype(d64), img_tr.reshape(N, S2, H))
-    dscore = p_ref * (dp - (p_ref * dp).sum(1, keepdims=True))
-    dwa_ref = np.einsum('ns,nsk->k', dscore, iqc_ref.reshape(N, S2, Kc))
-    diqc = dscore[:, :, None] * wa.astype(d64)[None, None, :]
-    dz_ref = (diqc * (m2.reshape(N, S2, Kc) * 2.0 if use_drop else 1.0)) * (1 - t_iqc.reshape(N, S2, Kc) ** 2)
-    dqc_ref = dz_ref.sum(1)
+    bwd = ar.img_backward(fwd, datt, m1, m2, Wc, wa, B, R, S2, sc)
+    dscore, dwa_ref, dz_ref, dqc_ref = bwd['dscore'], bwd['dwa'], bwd['dz'].reshape(N, S2, Kc), bwd['dqc']
     dwa = torch.zeros(Kc, device="cuda")
     dba = torch.zeros(1, device="cuda")
     dqc = torch.empty(N, Kc, device="cuda")
@@ -419,10 +408,7 @@ def test_image_attention(ops, use_drop):
     assert relerr(iqc, dz_ref.reshape(N * S2, Kc)) < 1e-5
     assert relerr(dwa, dwa_ref) < 1e-5 and relerr(dqc, dqc_ref) < 1e-5
     assert abs(float(dba.item()) - dscore.sum()) < 1e-4
-    dimg = p_ref[:, :, None] * datt.astype(d64)[:, None, :] + (dz_ref.reshape(N * S2, Kc) @ Wc.astype(d64)).reshape(N, S2, H)
-    if use_drop:
-        dimg = dimg * m1.reshape(N, S2, H) * 2.0
-    dpre_ref = dimg.reshape(B, R, S2, H).sum(1).reshape(B * S2, H)
+    dpre_ref = bwd['dpre']
     dpre = torch.zeros(B * S2, H, device="cuda")
     ops.img_tr_backward(iqc, dev(Wc), p, dev(datt), m1_d, dpre, N, R, S2, H, Kc, sc)
     assert relerr(dpre, dpre_ref) < 1e-5

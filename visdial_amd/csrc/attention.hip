@@ -17,6 +17,7 @@
 // Memory-network attention
 // =====================================================================================
 #define MN_MAX_R 16
+typedef float MnScoreTile[MN_MAX_R * MN_MAX_R];   // one R x R score / probability tile in static LDS
 
 // One 16-wave workgroup per dialog.  The R question states and R facts of the dialog (2 x 20 KB) are
 // staged in LDS with one coalesced pass, so the R*R dot products and the R*H weighted sums never touch
@@ -26,7 +27,7 @@ __global__ void __launch_bounds__(MN_THREADS)
 mn_att_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ Hm, const uint8_t* __restrict__ mask,
                   float* __restrict__ P, float* __restrict__ hAtt, int R, int H) {
   extern __shared__ __attribute__((aligned(16))) float lds[];  // q [R*H] | h [R*H]
-  __shared__ float S[MN_MAX_R * MN_MAX_R];
+  __shared__ MnScoreTile S;
   float* q = lds;
   float* h = lds + R * H;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = MN_THREADS / 64;
@@ -79,8 +80,8 @@ mn_att_bwd_kernel(const float* __restrict__ Q, const float* __restrict__ Hm, con
                   const float* __restrict__ dhAtt, float* __restrict__ dQ, float* __restrict__ dHm, int R,
                   int H) {
   extern __shared__ __attribute__((aligned(16))) float lds[];  // q | h | dhAtt, [R*H] each
-  __shared__ float Ps[MN_MAX_R * MN_MAX_R];
-  __shared__ float dS[MN_MAX_R * MN_MAX_R];
+  __shared__ MnScoreTile Ps;
+  __shared__ MnScoreTile dS;
   float* q = lds;
   float* h = lds + R * H;
   float* da = lds + 2 * R * H;
@@ -543,7 +544,8 @@ int vd_mn_attention_forward(const float* Q, const float* Hm, const uint8_t* mask
                "vd_mn_attention_forward: bad args (R=%d must be <= %d, H %% 4 == 0)", R, MN_MAX_R);
   if (B == 0) return VD_OK;
   const size_t lds = (size_t)2 * R * H * sizeof(float);
-  VD_CHECK_ARG(lds <= 64 * 1024, "vd_mn_attention_forward: R*H = %d does not fit the LDS staging", R * H);
+  // the workgroup's LDS is the staging plus the kernel's static tile (S): both must fit the 64 KB a launch gets without an opt-in
+  VD_CHECK_ARG(lds + sizeof(MnScoreTile) <= 64 * 1024, "vd_mn_attention_forward: R*H = %d does not fit the LDS staging", R * H);
   hipLaunchKernelGGL(mn_att_fwd_kernel, dim3(B), dim3(MN_THREADS), lds, (hipStream_t)stream, Q, Hm, mask, P, hAtt,
                      R, H);
   VD_LAUNCH_CHECK();
@@ -556,7 +558,8 @@ int vd_mn_attention_backward(const float* Q, const float* Hm, const float* P, co
                "vd_mn_attention_backward: bad args");
   if (B == 0) return VD_OK;
   const size_t lds = (size_t)3 * R * H * sizeof(float);
-  VD_CHECK_ARG(lds <= 64 * 1024, "vd_mn_attention_backward: R*H = %d does not fit the LDS staging", R * H);
+  // staging plus the kernel's two static tiles (Ps, dS)
+  VD_CHECK_ARG(lds + 2 * sizeof(MnScoreTile) <= 64 * 1024, "vd_mn_attention_backward: R*H = %d does not fit the LDS staging", R * H);
   hipLaunchKernelGGL(mn_att_bwd_kernel, dim3(B), dim3(MN_THREADS), lds, (hipStream_t)stream, Q, Hm, P, dhAtt, dQ,
                      dHm, R, H);
   VD_LAUNCH_CHECK();
