@@ -4,7 +4,8 @@
 on the chosen split of the REAL data files (evaluate.lua:80-81) and ranks the 100 candidate answers of every round:
 -useGt 1 -> retrieve (R@1/5/10, median/mean rank, MRR), else predict.  Optionally dumps the {image_id, round_id,
 ranks} records as JSON (evaluate.lua:104-107; the EvalAI submission format).  -rollout 1 ranks every round on a history of
-the model's own answers to the rounds before it (visdial_amd/split_eval.py E1-E5): the same ranks, metrics and records.  Without data files on disk it falls
+the model's own answers to the rounds before it (visdial_amd/split_eval.py E1-E5; -rolloutHistory concat: CH1-CH6, for the encoders whose
+history is the running concatenation of the dialog): the same ranks, metrics and records.  Without data files on disk it falls
 back to synthetic VisDial-shaped batches (plumbing check only; says so)."""
 import argparse
 import os
@@ -51,7 +52,13 @@ def parse_args(argv=None):
     ap.add_argument('-rolloutEncoder', '--rolloutEncoder', default='full', choices=['full', 'round'],
                     help='-rollout 1 -host native: round = passes 1 .. R - 1 of the device rollout encode the round they rank alone instead '
                          'of the whole batch again (csrc/rt_encoders.h forward_round; for gen: the beam-search rollout); same records')
+    ap.add_argument('-rolloutHistory', '--rolloutHistory', default='row', choices=['row', 'concat'],
+                    help='-rollout 1: row = every history row holds one round (E4); concat = the encoders that read the running concatenation '
+                         'of the dialog (lf-ques-hist, lf-ques-im-hist, lf-att-ques-im-hist) roll out by the concatenation rule '
+                         '(visdial_amd/split_eval.py CH1-CH6): row r + 1 = row r, <END>, the question, the answer, cut at the end where it does not fit')
     a = ap.parse_args(argv)
+    if a.rolloutHistory == 'concat' and not a.rollout:
+        raise SystemExit('-rolloutHistory concat is the history rule of a rollout: it needs -rollout 1')
     if a.rolloutEncoder == 'round':
         if not a.rollout:
             raise SystemExit('-rolloutEncoder round encodes the later passes of a rollout one round at a time: it needs -rollout 1')
@@ -69,9 +76,14 @@ def check_rollout(a, p):
                          'reads a picked candidate\'s tokens from the batch; combining the two is left for a follow-up')
     if a.perplexity:
         raise SystemExit('-rollout 1 with -perplexity 1: perplexity is defined on the ground-truth history; run it separately')
-    if p.get('useHistory') and p.get('concatHistory'):
+    concat = getattr(a, 'rolloutHistory', 'row') == 'concat'
+    if p.get('useHistory') and p.get('concatHistory') and not concat:
         raise SystemExit("-rollout 1 with encoder '%s': it reads the running concatenation of the rounds (concatHistory), and the rollout's "
-                         "rule describes the per-round history row only; a concatenation rule is left for a follow-up" % p['encoder'])
+                         "rule describes the per-round history row only; -rolloutHistory concat lifts the refusal: it rolls out by the "
+                         "concatenation rule" % p['encoder'])
+    if concat and p.get('useHistory') and not p.get('concatHistory'):
+        raise SystemExit("-rolloutHistory concat with encoder '%s': its history is one row per round, not the running concatenation; the "
+                         "concatenation rule is for lf-ques-hist, lf-ques-im-hist and lf-att-ques-im-hist" % p['encoder'])
     if p['decoder'] == 'gen' and a.host != 'native':
         raise SystemExit('-rollout 1 with a generative model feeds the beam search\'s answers back on the device: add -host native')
 
@@ -92,6 +104,8 @@ def main(argv=None):
     check_rollout(a, p)
     p['rollout'] = a.rollout
     p['rolloutEncoder'] = a.rolloutEncoder
+    concat = bool(a.rollout and a.rolloutHistory == 'concat' and p.get('useHistory'))     # (no history: ignored, like the other rollout flags)
+    p['rolloutHistory'] = 'concat' if concat else 'row'
     p.update(inputImg=a.inputImg, inputQues=a.inputQues, inputJson=a.inputJson)
     have = lambda f: os.path.exists(f) or os.path.exists(f[:-3] + '.npz')
     if os.path.exists(a.inputJson) and have(a.inputQues):
@@ -101,6 +115,9 @@ def main(argv=None):
     else:
         print('no dataset at %s: ranking SYNTHETIC batches (plumbing check, the metrics mean nothing)' % a.inputQues)
         dl = SyntheticDataloader(p, seed=4321, num_threads=a.numThreads)
+    if concat:                                                # CH3's <END>: the host loop's and, for -host native, the device rollout's
+        w2i = getattr(dl, 'word2ind', None)
+        p['rolloutConcatEnd'] = int(w2i['<END>'] if w2i else dl.endToken)
     if a.rollout and p['decoder'] == 'gen':
         # the device search takes its knobs when the model is created; the answers are the ones generate.py -rollout 1 -beamBatch N writes
         w2i = getattr(dl, 'word2ind', None)
@@ -132,6 +149,8 @@ def main(argv=None):
                  100.0 * st['executed'] / max(st['total'], 1)))
     if a.rollout:
         print('rollout: %d of %d history rows differ from the ground truth\'s' % model.rolloutRows)
+        if concat:
+            print('rolloutHistory concat: %d generated history rows were cut to the history\'s width (CH4)' % model.rolloutCut)
     if a.optionCache:
         ex, tot = model.optionCacheRows
         print('optionCache: the option LSTM ran %d of %d candidate rows (%.1f %%)' % (ex, tot, 100.0 * ex / max(tot, 1)))

@@ -96,6 +96,16 @@ int vd_copy_2d(float* dst, int64_t dst_ld, const float* src, int64_t src_ld, int
  * h and c equal that flag's bit for bit.  Exact fp32 only: refused (argument error) with VD_FLAG_BF16, any VD_FLAG_SPLIT*,
  * VD_FLAG_STATE_ONLY, a non-NULL `gates` or a NULL tok_mask. */
 #define VD_FLAG_TREE 64
+/* VD_FLAG_HOLD (vd_lstm_forward): a row whose tok_mask entry is 0 at step t KEEPS (h, c) of step t - 1 -- (h0, c0) at t = 0, zero with
+ * NULL h0 / c0 -- instead of being zeroed: the recurrence continued from a carried state over right-aligned windows of new tokens (the
+ * prefix property of a concatenated history, csrc/beam.hip CH6).  A live row is the plain cell.  tok_mask ([T x N]) is required.  Forward
+ * only: `gates` must be NULL and no gate activation reaches memory; h and c are [T x N x H] and hold the running state of every row at
+ * every step (a held row writes what it kept), so row n of h [T - 1] is the state after the row's last token.  Dense and table mode.  It
+ * runs the exact fp32 step kernels at any N -- the distributed split-K epilogue below 2048 rows, the register-staged generic kernel from
+ * there on; the LDS-DMA pipeline has no form of this epilogue and a HOLD pass is routed away from it.  Refused (argument error) with every
+ * other flag -- VD_FLAG_BF16, any VD_FLAG_SPLIT*, VD_FLAG_LIVE_PREFIX, VD_FLAG_STATE_ONLY, VD_FLAG_TREE --, a non-NULL `gates` or a NULL
+ * tok_mask. */
+#define VD_FLAG_HOLD 128
 
 /* ---- dense contractions (nn.Linear / hoisted SeqLSTM input projection / weight grads) -- */
 /* C[MxN] (+)= act(A[MxK] * W[NxK]^T + bias)   -- nn.Linear:updateOutput (+nn.Tanh),
@@ -133,7 +143,8 @@ int vd_colsum_acc(const float* X, int64_t ld, int M, int N, float* out, void* st
  * so calls on different streams may overlap.
  * flags: VD_FLAG_BF16 / VD_FLAG_SPLIT* choose the arithmetic of the recurrent product; VD_FLAG_LIVE_PREFIX (above) skips the
  * row groups without a live row; VD_FLAG_STATE_ONLY (above) keeps only the running state (gates NULL, h / c [2 x N x H]);
- * VD_FLAG_TREE (above) runs a forest level by level (gates NULL, tok_mask [2 x T x N] = mask | parent row). */
+ * VD_FLAG_TREE (above) runs a forest level by level (gates NULL, tok_mask [2 x T x N] = mask | parent row); VD_FLAG_HOLD (above)
+ * holds the state of a masked row instead of zeroing it (gates NULL, alone among the flags). */
 int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const int32_t* tok_gather,
                     const int32_t* tok_mask, const float* Wh, const float* h0, const float* c0, float* gates,
                     float* h, float* c, int T, int N, int H, int flags, void* stream);
@@ -373,7 +384,16 @@ typedef struct vd_batch {          /* HOST pointers, dataloader layout (dataload
  * answer -- history row r of every dialog through the history branch at B rows, then the B rows of the encoder's head on the state the
  * first pass left -- instead of all B * R rounds again: the same picks, answers and ranks, scores within fp32 rounding of the full pass
  * (a product over B rows may take another tile than over B * R).  Ignored where nothing rolls out (neither rollout variable set, or an
- * encoder without a history); with training on, both calls refuse it by name. */
+ * encoder without a history); with training on, both calls refuse it by name.
+ * A second one belongs to both rollouts too: VD_ROLLOUT_CONCAT_END = an integer >= 0 (0 / unset = off; text, a negative value and a value
+ * above vocabSize are refused by name).  Any other value is the <END> token id and means CONCATENATED history rows, for the encoders whose
+ * history row is the running concatenation of the dialog (lf-ques-hist, lf-ques-im-hist, lf-att-ques-im-hist; an encoder with per-round
+ * rows is refused by name): a rollout then writes history row r + 1 as row r's tokens, <END>, the non-zero tokens of question row r and the
+ * answer's words, right-aligned in the Th uploaded columns, cut at the end where they do not fit (csrc/beam.hip CH1-CH6) instead of the
+ * per-round row.  vd_model_beam_search refuses an end_token that differs from it.  With VD_ROLLOUT_ENCODER = round the later passes continue
+ * the two-layer history stack from a carried state over the new tokens alone (vd_lstm_forward with VD_FLAG_HOLD); a model with another
+ * number of history layers or bf16 recurrences gets an argument error from the call, never the full-width pass.  Ignored where nothing
+ * rolls out. */
 int vd_model_create(const vd_model_params* p, const char* encoder, const char* decoder, vd_model** out);
 void vd_model_destroy(vd_model* m);
 /* wrapper:getParameters() (model.lua:55): flat layout = embed | encoder tensors | decoder tensors, every tensor

@@ -28,7 +28,8 @@ own candidates: per batch (upload + retrieve + ranks, as evaluate.py runs it) th
 created without VD_RETRIEVE_ROLLOUT), the device rollout (one upload + one vd_model_retrieve on a model created with it) and the host loop
 (R uploads + retrievals, --host-batches of the batches), alternated.  The device rollout's time over the plain retrieval's is what the
 R - 1 further encoder passes, scorings and picks cost: the option recurrence runs once in both.  --cases plain runs the first alone (the
-parent commit's library through VD_LIB_PATH knows no rollout), --cases device the second (for a kernel trace).  --rolloutEncoder round creates
+parent commit's library through VD_LIB_PATH knows no rollout), --cases device the second (for a kernel trace).  --rolloutHistory concat: the
+same paths for lf-ques-im-hist + disc on its concatenated history (W = 300; CH1-CH6, VD_ROLLOUT_CONCAT_END).  --rolloutEncoder round creates
 the device rollout's model with VD_ROLLOUT_ENCODER = round (passes 1 .. R - 1 encode the round they rank alone); both adds that model as a
 fourth path `round` beside `device`, alternated with it.
 --mode step: the option recurrence alone (vd_lstm_forward, table mode, 20 000 x 512, 20 steps), saving against VD_FLAG_STATE_ONLY,
@@ -60,6 +61,9 @@ ap.add_argument('--cases', choices=('all', 'uncached', 'cached', 'plain', 'devic
 ap.add_argument('--rollout', type=int, choices=(0, 1), default=0, help='--mode disc: ranking on a rollout, three paths (see above)')
 ap.add_argument('--rolloutEncoder', choices=('full', 'round', 'both'), default='full',
                 help='--mode disc --rollout 1: the encoder of the device rollout\'s later passes; both = the two as separate paths')
+ap.add_argument('--rolloutHistory', choices=('row', 'concat'), default='row',
+                help='--mode disc --rollout 1: concat = lf-ques-im-hist + disc on its concatenated history (W = 300), the models created with '
+                     'VD_ROLLOUT_CONCAT_END (csrc/beam.hip CH1-CH6); row = mn-att-ques-im-hist on per-round rows, as ever')
 ap.add_argument('--host-batches', type=int, default=2, help='--mode disc --rollout 1: batches the host loop ranks per pass')
 opt = ap.parse_args()
 
@@ -136,17 +140,23 @@ def disc_mode():
 def disc_rollout_mode():
     from visdial_amd.split_eval import SplitEval
     B, R, O, To, H = 20, 10, 100, 20, 512
-    p = derive(default_params(encoder='mn-att-ques-im-hist', decoder='disc', vocabSize=11322, imgFeatureSize=512, imgSpatialSize=14,
-                              maxHistoryLenPerRound=40, batchSize=B, numOptions=O, maxQuesCount=R, maxAnsLen=To, lstmPrecision='split9',
-                              gpuid=0))
+    concat = opt.rolloutHistory == 'concat'
+    if concat:
+        p = derive(default_params(encoder='lf-ques-im-hist', decoder='disc', vocabSize=11322, imgFeatureSize=4096, batchSize=B, numOptions=O,
+                                  maxQuesCount=R, maxAnsLen=To, lstmPrecision='split9', gpuid=0))
+    else:
+        p = derive(default_params(encoder='mn-att-ques-im-hist', decoder='disc', vocabSize=11322, imgFeatureSize=512, imgSpatialSize=14,
+                                  maxHistoryLenPerRound=40, batchSize=B, numOptions=O, maxQuesCount=R, maxAnsLen=To, lstmPrecision='split9',
+                                  gpuid=0))
     tag = opt.tag and opt.tag + ' '
     dl = SyntheticDataloader(p, seed=7, num_threads=B * opt.batches)
+    rule = dict(rolloutHistory='concat', rolloutConcatEnd=dl.endToken) if concat else {}
     batches, start = [], 1
     for _ in range(opt.batches):
         b, start = dl.getTestBatch(start, p, 'val')
         batches.append(b)
-    print("%smn-att-ques-im-hist + disc, H %d, %d dialogs x %d rounds x %d options, To %d, Th %d, Tq %d, split9, native host, random weights, "
-          "%d batches per pass" % (tag, H, B, R, O, To, batches[0]['hist'].shape[2], batches[0]['ques_fwd'].shape[2], opt.batches), flush=True)
+    print("%s%s + disc, H %d, %d dialogs x %d rounds x %d options, To %d, Th %d, Tq %d, split9, native host, random weights, "
+          "%d batches per pass" % (tag, p['encoder'], H, B, R, O, To, batches[0]['hist'].shape[2], batches[0]['ques_fwd'].shape[2], opt.batches), flush=True)
     want = {'all': ('plain', 'device', 'host'), 'plain': ('plain',), 'device': ('device',)}[opt.cases]
     if opt.rolloutEncoder == 'both' and 'device' in want:
         want = want + ('round',)
@@ -154,11 +164,12 @@ def disc_rollout_mode():
     if 'plain' in want or 'host' in want:
         plain = NativeModel(dict(p), init_seed=1)
         plain.training(False)
+        plain.params.update(rule)                       # the host loop's rule; the model itself is created without the variable
     if 'device' in want:
-        roll = NativeModel(dict(p, retrieveRollout=1, rolloutEncoder='round' if opt.rolloutEncoder == 'round' else 'full'), init_seed=1)
+        roll = NativeModel(dict(p, retrieveRollout=1, rolloutEncoder='round' if opt.rolloutEncoder == 'round' else 'full', **rule), init_seed=1)
         roll.training(False)
     if 'round' in want:
-        rnd = NativeModel(dict(p, retrieveRollout=1, rolloutEncoder='round'), init_seed=1)
+        rnd = NativeModel(dict(p, retrieveRollout=1, rolloutEncoder='round', **rule), init_seed=1)
         rnd.training(False)
 
     def one_pass(case):

@@ -106,6 +106,25 @@
 // An option's encoding depends on its tokens and the weights only, so the option LSTM runs ONCE; a chunk then runs R passes (Disc::
 // retrieve_rollout, rt_decoders.h): encoder forward, vd_score_ce over all N rounds, disc_rollout_pick_kernel for row r + 1 (not after the
 // last).  Nothing waits for the host between passes.  For decoder gen the answer fed back is the beam search's (R4).
+//
+// Rollout on a concatenated history (VD_ROLLOUT_CONCAT_END = the <END> id at vd_model_create, with either rollout above; evaluate.py -rollout 1
+// -rolloutHistory concat): the encoders whose history row is the running concatenation of the dialog (lf-ques-hist, lf-ques-im-hist,
+// lf-att-ques-im-hist; dataloader.lua:243-255).  split_eval.py restates CH2 - CH4 (rollout_concat_row) and the host loops.  W is the width of
+// the uploaded history, END the <END> token id.
+//  CH1. row 0 is the uploaded row (R1).
+//  CH2. lenH(r) = W - (the index of the first non-zero column of row r), and 0 for an all-zero row.  The last lenH columns of row r are its
+//       tokens, carried over as they are (a 0 among them included).
+//  CH3. the new tokens of round r are END, then the non-zero tokens of question row r in order, then the answer's words: R3 for a beam answer,
+//       E2 / E3 for a picked candidate.  END is appended even when the question is empty and there are no words, as dataloader.lua:243-255
+//       does for the missing rounds of the test split.
+//  CH4. row r + 1 is row r's lenH tokens followed by the first min(n_new, W - lenH) new tokens, right-aligned in W columns with zeros in
+//       front.  What does not fit is cut at the end: words first, then question tokens, then END; a full row repeats itself.  (The
+//       reference's loader has no such case: it would index out of range.)  The cut keeps every row a prefix extension of the one before;
+//       CH6 rests on that.
+//  CH5. R5, R6 and E5 hold as written: an lf encoder reads only its own row.
+//  CH6. prefix property: the history stack's state after row r + 1 is its state after row r continued over the kept new tokens.
+// On the device the append and pick kernels below write the row through rollout_concat_row instead of R2's body when the model's END is set;
+// the passes are otherwise the ones above.
 #include "common.h"
 
 #define VD_BEAM_KMAX 32
@@ -443,12 +462,74 @@ __device__ __forceinline__ void rollout_write_row(const int32_t* __restrict__ qu
   }
 }
 
+// CH2 - CH4 for one history row, by the one wave of the workgroup: row nq + 1 from ROW nq, <END>, question row nq and `la` words (as above).
+// The wave compacts the question as above, finds row nq's first non-zero column with a ballot per 64 columns (CH2: lenH = W - that column) and
+// makes ONE pass over the W columns.  With keep = min(1 + lq + la, W - lenH) new tokens kept, the new row is the old one moved `keep` columns
+// to the left with the kept tokens behind it, so column c holds old column c + keep while that lies inside the row (its leading zeros
+// included: lenH + keep <= W, nothing non-zero moves out) and new token c + keep - W otherwise: a value by the distance from the right edge
+// alone, every column written exactly once, plain vector stores into both layouts.  keep = 0: the row repeats itself.  Rows nq and nq + 1
+// are different columns of the table, so nothing read here is written here; the previous pass's stores are visible across the launch.
+// CH2 by the one wave of the workgroup: the first non-zero column of row n of the step-major tokens [W x N], W for an all-zero row
+__device__ __forceinline__ int rollout_first_column(const int32_t* hist_tok, long N, long n, int W) {
+  const int lane = threadIdx.x;
+  for (int base = 0; base < W; base += 64) {
+    const int c = base + lane;
+    const unsigned long long mask = __ballot(c < W && hist_tok[(long)c * N + n] != 0);
+    if (mask) return base + __ffsll((long long)mask) - 1;
+  }
+  return W;
+}
+__device__ __forceinline__ void rollout_concat_row(const int32_t* __restrict__ ques, int Tq, long N, long nq, const int32_t* __restrict__ words,
+                                                   long stride, int la, int W, int end_tok, int32_t* hist_tok,
+                                                   int32_t* __restrict__ hist_sorted, const int32_t* __restrict__ inv) {
+  __shared__ int32_t qn[VD_ROLLOUT_TMAX];
+  const int lane = threadIdx.x;
+  const long nh = nq + 1;
+  int lq = 0;
+  for (int base = 0; base < Tq; base += 64) {
+    const int t = base + lane;
+    const int32_t v = t < Tq ? ques[(long)t * N + nq] : 0;
+    const unsigned long long mask = __ballot(v != 0);
+    if (v != 0) qn[lq + __popcll(mask & ((1ull << lane) - 1ull))] = v;
+    lq += __popcll(mask);
+  }
+  __syncthreads();
+  const int first = rollout_first_column(hist_tok, N, nq, W);     // CH2
+  const int keep = min(1 + lq + la, first);                        // CH4: W - lenH = first columns are free
+  for (int base = 0; base < W; base += 64) {
+    const int c = base + lane;
+    if (c >= W) break;
+    const int i = c + keep - W;                                    // >= 0: new token i (CH3); < 0: old column c + keep
+    const int32_t v = i < 0 ? hist_tok[(long)(c + keep) * N + nq] : i == 0 ? end_tok : i <= lq ? qn[i - 1] : words[(long)(i - 1 - lq) * stride];
+    hist_tok[(long)c * N + nh] = v;
+    if (hist_sorted) hist_sorted[(long)c * N + inv[nh]] = v;
+  }
+}
+
+// CH6 for the round pass (rt_encoders.h history_round_concat): the kept new tokens of history row r of every dialog, right-aligned in a
+// step-major window [Wn x B] with zeros in front.  Row r is row r - 1 moved left with the kept tokens behind it (CH4), so they are its last
+// keep = first(r - 1) - first(r) columns; the append kernels kept at most 1 + Tq + (words of an answer) of them, which the caller's Wn
+// covers -- the clamp below only keeps a caller's mistake inside the window.  One wave per dialog, plain vector stores.
+__global__ void __launch_bounds__(64)
+rollout_concat_window_kernel(const int32_t* __restrict__ hist_tok, long N, int R, int r, int W, int Wn, int B, int32_t* __restrict__ win) {
+  const int lane = threadIdx.x;
+  const long n = (long)blockIdx.x * R + r;
+  const int keep = max(0, min(rollout_first_column(hist_tok, N, n - 1, W) - rollout_first_column(hist_tok, N, n, W), Wn));
+  for (int base = 0; base < Wn; base += 64) {
+    const int c = base + lane;
+    if (c >= Wn) break;
+    const int j = c - (Wn - keep);
+    win[(long)c * B + blockIdx.x] = j < 0 ? 0 : hist_tok[(long)(W - keep + j) * N + n];
+  }
+}
+
 // R2 / R3 for one pass of a rollout: one wave per dialog writes history row r + 1 from question row r and the answer just chosen for
 // round r.  The answer's word count is the first lane whose entry is <END>, 0 or past the row; the words start behind <START>.
+// concat_end != 0 (VD_ROLLOUT_CONCAT_END): the row by CH2 - CH4 instead of R2.
 __global__ void __launch_bounds__(64)
 beam_rollout_append_kernel(const int32_t* __restrict__ answers, int L, int end_tok, const int32_t* __restrict__ ques, int Tq, long N, int R,
-                           int r, int Th, int32_t* __restrict__ hist_tok, int32_t* __restrict__ hist_sorted,
-                           const int32_t* __restrict__ inv) {
+                           int r, int Th, int32_t* hist_tok, int32_t* __restrict__ hist_sorted,
+                           const int32_t* __restrict__ inv, int concat_end) {
   const int lane = threadIdx.x;
   const int32_t* a = answers + (long)blockIdx.x * L;
   int la = 0;                                                      // R3: entries 1 .. la are the words
@@ -461,7 +542,10 @@ beam_rollout_append_kernel(const int32_t* __restrict__ answers, int L, int end_t
       break;
     }
   }
-  rollout_write_row(ques, Tq, N, (long)blockIdx.x * R + r, a + 1, 1, la, Th, hist_tok, hist_sorted, inv);
+  if (concat_end)
+    rollout_concat_row(ques, Tq, N, (long)blockIdx.x * R + r, a + 1, 1, la, Th, concat_end, hist_tok, hist_sorted, inv);
+  else
+    rollout_write_row(ques, Tq, N, (long)blockIdx.x * R + r, a + 1, 1, la, Th, hist_tok, hist_sorted, inv);
 }
 
 // E2 - E4 for one pass of a discriminative rollout: one wave per dialog picks the rank-1 candidate of round r among its O <= 128 scores
@@ -474,7 +558,7 @@ beam_rollout_append_kernel(const int32_t* __restrict__ answers, int L, int end_t
 __global__ void __launch_bounds__(64)
 disc_rollout_pick_kernel(const float* __restrict__ scores, int O, const int32_t* __restrict__ opt_tok, long rows, int To,
                          const int32_t* __restrict__ opt_uid, const int32_t* __restrict__ ques, int Tq, long N, int R, int r, int Th,
-                         int32_t* __restrict__ hist_tok, int32_t* __restrict__ hist_sorted, const int32_t* __restrict__ inv) {
+                         int32_t* hist_tok, int32_t* __restrict__ hist_sorted, const int32_t* __restrict__ inv, int concat_end) {
   const int lane = threadIdx.x;
   const long nq = (long)blockIdx.x * R + r;
   const float* s = scores + nq * O;
@@ -500,22 +584,36 @@ disc_rollout_pick_kernel(const float* __restrict__ scores, int O, const int32_t*
       break;
     }
   }
-  rollout_write_row(ques, Tq, N, nq, w, rows, la, Th, hist_tok, hist_sorted, inv);
+  if (concat_end)                                                  // VD_ROLLOUT_CONCAT_END: CH2 - CH4 instead of E4
+    rollout_concat_row(ques, Tq, N, nq, w, rows, la, Th, concat_end, hist_tok, hist_sorted, inv);
+  else
+    rollout_write_row(ques, Tq, N, nq, w, rows, la, Th, hist_tok, hist_sorted, inv);
 }
 
 }  // namespace
 
 // R2 / R3 (rt_core.h): history row r + 1 of `dialogs` dialogs from question row r and `answers` [dialogs x beam_len]
 int vd_beam_rollout_append_p(const int32_t* answers, int beam_len, int end_token, const int32_t* ques, int Tq, int dialogs, int R, int r,
-                             int32_t* hist_tok, int32_t* hist_sorted, const int32_t* inv, int Th, hipStream_t stream) {
-  VD_CHECK_ARG(answers && ques && hist_tok && beam_len >= 1 && dialogs >= 0 && (hist_sorted == nullptr) == (inv == nullptr),
+                             int32_t* hist_tok, int32_t* hist_sorted, const int32_t* inv, int Th, hipStream_t stream, int concat_end) {
+  VD_CHECK_ARG(answers && ques && hist_tok && beam_len >= 1 && dialogs >= 0 && (hist_sorted == nullptr) == (inv == nullptr) && concat_end >= 0,
                "vd_beam_rollout_append: bad args");
   VD_CHECK_ARG(R >= 2 && r >= 0 && r + 1 < R, "vd_beam_rollout_append: round %d has no next round among %d", r, R);
   VD_CHECK_ARG(Tq >= 1 && Tq <= VD_ROLLOUT_TMAX && Th >= Tq, "vd_beam_rollout_append: question width %d must be in [1, %d] and <= history width %d",
                Tq, VD_ROLLOUT_TMAX, Th);
   if (dialogs == 0) return VD_OK;
   hipLaunchKernelGGL(beam_rollout_append_kernel, dim3((unsigned)dialogs), dim3(64), 0, stream, answers, beam_len, end_token, ques, Tq,
-                     (long)dialogs * R, R, r, Th, hist_tok, hist_sorted, inv);
+                     (long)dialogs * R, R, r, Th, hist_tok, hist_sorted, inv, concat_end);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+// CH6 (rt_core.h): the kept new tokens of history row r of `dialogs` dialogs as a window [Wn x dialogs]
+int vd_rollout_concat_window_p(const int32_t* hist_tok, int dialogs, int R, int r, int W, int Wn, int32_t* win, hipStream_t stream) {
+  VD_CHECK_ARG(hist_tok && win && dialogs >= 0 && R >= 2 && r >= 1 && r < R && Wn >= 1 && Wn <= W,
+               "vd_rollout_concat_window: bad args (round %d of %d, window %d of %d columns)", r, R, Wn, W);
+  if (dialogs == 0) return VD_OK;
+  hipLaunchKernelGGL(rollout_concat_window_kernel, dim3((unsigned)dialogs), dim3(64), 0, stream, hist_tok, (long)dialogs * R, R, r, W, Wn,
+                     dialogs, win);
   VD_LAUNCH_CHECK();
   return VD_OK;
 }
@@ -523,8 +621,8 @@ int vd_beam_rollout_append_p(const int32_t* answers, int beam_len, int end_token
 // E2 - E4 (rt_core.h): history row r + 1 of `dialogs` dialogs from question row r and the rank-1 candidate of scores row dialog * R + r
 int vd_disc_rollout_pick_p(const float* scores, int O, const int32_t* opt_tok, int64_t opt_rows, int To, const int32_t* opt_uid,
                            const int32_t* ques, int Tq, int dialogs, int R, int r, int32_t* hist_tok, int32_t* hist_sorted,
-                           const int32_t* inv, int Th, hipStream_t stream) {
-  VD_CHECK_ARG(scores && opt_tok && ques && hist_tok && To >= 1 && dialogs >= 0 && (hist_sorted == nullptr) == (inv == nullptr),
+                           const int32_t* inv, int Th, hipStream_t stream, int concat_end) {
+  VD_CHECK_ARG(scores && opt_tok && ques && hist_tok && To >= 1 && dialogs >= 0 && (hist_sorted == nullptr) == (inv == nullptr) && concat_end >= 0,
                "vd_disc_rollout_pick: bad args");
   VD_CHECK_ARG(O >= 1 && O <= VD_DISC_PICK_OMAX, "vd_disc_rollout_pick: O = %d candidates per round must be in [1, MAX_OPT = %d]", O,
                VD_DISC_PICK_OMAX);
@@ -536,7 +634,7 @@ int vd_disc_rollout_pick_p(const float* scores, int O, const int32_t* opt_tok, i
                "vd_disc_rollout_pick: %lld option rows for %d x %d x %d candidates", (long long)opt_rows, dialogs, R, O);
   if (dialogs == 0) return VD_OK;
   hipLaunchKernelGGL(disc_rollout_pick_kernel, dim3((unsigned)dialogs), dim3(64), 0, stream, scores, O, opt_tok, (long)opt_rows, To, opt_uid,
-                     ques, Tq, (long)dialogs * R, R, r, Th, hist_tok, hist_sorted, inv);
+                     ques, Tq, (long)dialogs * R, R, r, Th, hist_tok, hist_sorted, inv, concat_end);
   VD_LAUNCH_CHECK();
   return VD_OK;
 }

@@ -17,6 +17,7 @@
 #define VD_FLAG_LIVE_PREFIX 16
 #define VD_FLAG_STATE_ONLY 32
 #define VD_FLAG_TREE 64
+#define VD_FLAG_HOLD 128
 #define VD_LIVE_PREFIX_ROWS 128
 #define VD_BEAM_LMAX 64  // beam.hip: the longest beamLen while n-gram blocking is on (a column and its ban list sit in LDS)
 

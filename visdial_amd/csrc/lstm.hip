@@ -354,6 +354,71 @@ struct EpiLstmFwdTree : EpiLstmFwd {
     run<false, true>(acc, row0, vcol0, lane, M, Nv, scr, pre, parent);
   }
 };
+// VD_FLAG_HOLD: a row whose tok_mask entry is 0 KEEPS the state of the step before (h0 / c0 at the first step) instead of being zeroed: a
+// recurrence continued from a carried state over right-aligned windows of new tokens, where the pad in front of a row's tokens must not
+// touch the state it carries.  A live row is the plain cell (km = 1).  Forward only, c and h are stored and no gate value reaches memory
+// (as EpiLstmFwdState).  The epilogue also reads h_{t-1} of the held rows: `h_prev` (null = zeros, like c_prev).  A held row writes what it
+// read, so h [t] holds the running state of every row and the recurrent product's A operand stays h [t - 1] as it lies.
+// Two forms: the distributed split-K one (N < VD_THROUGHPUT_ROWS), which adds one 16-byte load to the operand batch, and a plain
+// register-staged one (rows of four hidden units per lane, 16-byte accesses, not hand-scheduled: a continuation runs a few rows).  The
+// LDS-DMA pipeline is not instantiated with it: vd_lstm_forward routes a HOLD pass to the generic kernels.  A type of its own: the other
+// step kernels keep their instantiations.
+struct EpiLstmFwdHold : EpiLstmFwd {
+  const float* h_prev;   // [N x H] h_{t-1}, null = zeros
+  static constexpr bool STEP_BF16 = false, STEP_SPLIT = false;
+  struct DOps : EpiLstmFwd::DOps {
+    float4 hp;
+  };
+  __device__ __forceinline__ void dist_load(DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
+    dist_load_t<false>(q, row0, vcol0, lane, grp, M, nullptr);
+    const int j = (vcol0 >> 7) * 32 + (lane & 7) * 4;
+    const int row = row0 + grp * 8 + (lane >> 3);
+    const int rc = row < M ? row : M - 1;
+    q.hp = h_prev ? *reinterpret_cast<const float4*>(h_prev + (long)rc * H + j) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  __device__ __forceinline__ void dist_store(const float4 (&a)[4], const DOps& q, int row0, int vcol0, int lane, int grp, int M) const {
+    const int j = (vcol0 >> 7) * 32 + (lane & 7) * 4;
+    const int row = row0 + grp * 8 + (lane >> 3);
+    if (row >= M || j >= H) return;
+    const float km = 1.f;
+    float4 gi, gf, go, gg, c, h;
+#define VD_CELL(E) VD_LSTM_CELL(E, a[0].E + q.x[0].E, a[1].E + q.x[1].E, a[2].E + q.x[2].E, a[3].E + q.x[3].E, q.cp.E)
+    VD_XYZW(VD_CELL)
+#undef VD_CELL
+    *reinterpret_cast<float4*>(c_out + (long)row * H + j) = q.keep ? c : q.cp;
+    *reinterpret_cast<float4*>(h_out + (long)row * H + j) = q.keep ? h : q.hp;
+  }
+  __device__ __forceinline__ void operator()(const f32x16 (&acc)[4], int row0, int vcol0, int lane, int M, int /*Nv*/, float* scr,
+                                             const Pre* pre = nullptr) const {
+    const int j = (vcol0 >> 7) * 32 + (lane & 7) * 4;  // < H: H % 32 == 0 and vcol0 < 4H
+    const int rl = lane >> 3;
+    float4 a[4][4];  // [gate][p]
+    tile_to_rows(acc[0], scr, lane, a[0]);
+    tile_to_rows(acc[1], scr, lane, a[1]);
+    tile_to_rows(acc[2], scr, lane, a[2]);
+    tile_to_rows(acc[3], scr, lane, a[3]);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int row = row0 + p * 8 + rl;
+      if (row >= M) continue;
+      const int tk = pre ? pre->tk[p] : tok_gather ? tok_gather[row] : row;
+      const bool keep = pre ? ((pre->keepbits >> p) & 1) != 0 : tok_mask[row] != 0;
+      const float* xr = xproj + (long)tk * xld + j;
+      const float4 x0 = *reinterpret_cast<const float4*>(xr), x1 = *reinterpret_cast<const float4*>(xr + H),
+                   x2 = *reinterpret_cast<const float4*>(xr + 2 * H), x3 = *reinterpret_cast<const float4*>(xr + 3 * H);
+      const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 cq = c_prev ? *reinterpret_cast<const float4*>(c_prev + (long)row * H + j) : z;
+      const float4 hq = h_prev ? *reinterpret_cast<const float4*>(h_prev + (long)row * H + j) : z;
+      const float km = 1.f;
+      float4 gi, gf, go, gg, c, h;
+#define VD_CELL(E) VD_LSTM_CELL(E, a[0][p].E + x0.E, a[1][p].E + x1.E, a[2][p].E + x2.E, a[3][p].E + x3.E, cq.E)
+      VD_XYZW(VD_CELL)
+#undef VD_CELL
+      *reinterpret_cast<float4*>(c_out + (long)row * H + j) = keep ? c : cq;
+      *reinterpret_cast<float4*>(h_out + (long)row * H + j) = keep ? h : hq;
+    }
+  }
+};
 // h_{t-1} rows seen through the parent list of EpiLstmFwdTree: the A operand of the generic step kernels
 struct SrcRowTree {
   static constexpr bool KMAJOR = false;
@@ -942,8 +1007,20 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
                "vd_lstm_forward: VD_FLAG_TREE keeps h and c of every level; it does not combine with VD_FLAG_STATE_ONLY (flags = %d)", flags);
   VD_CHECK_ARG(!tree || !gates, "vd_lstm_forward: VD_FLAG_TREE is forward only and saves no gate activations: gates must be NULL");
   VD_CHECK_ARG(!tree || tok_mask, "vd_lstm_forward: VD_FLAG_TREE needs tok_mask ([2 x T x N]: mask and parent row)");
+  // VD_FLAG_HOLD (include/visdial_hip.h): forward only, exact fp32, alone among the flags
+  const bool hold = (flags & VD_FLAG_HOLD) != 0;
+  VD_CHECK_ARG(!hold || !(flags & (VD_FLAG_BF16 | VD_FLAG_SPLIT)),
+               "vd_lstm_forward: VD_FLAG_HOLD runs the exact fp32 step kernels only; it does not combine with VD_FLAG_BF16 / "
+               "VD_FLAG_SPLIT* (flags = %d)", flags);
+  VD_CHECK_ARG(!hold || !(flags & VD_FLAG_LIVE_PREFIX),
+               "vd_lstm_forward: VD_FLAG_HOLD writes the held state of every row; it does not combine with VD_FLAG_LIVE_PREFIX (flags = %d)", flags);
+  VD_CHECK_ARG(!hold || !(flags & VD_FLAG_STATE_ONLY),
+               "vd_lstm_forward: VD_FLAG_HOLD keeps h and c of every step; it does not combine with VD_FLAG_STATE_ONLY (flags = %d)", flags);
+  VD_CHECK_ARG(!hold || !tree, "vd_lstm_forward: VD_FLAG_HOLD does not combine with VD_FLAG_TREE (flags = %d)", flags);
+  VD_CHECK_ARG(!hold || !gates, "vd_lstm_forward: VD_FLAG_HOLD is forward only and saves no gate activations: gates must be NULL");
+  VD_CHECK_ARG(!hold || tok_mask, "vd_lstm_forward: VD_FLAG_HOLD needs tok_mask ([T x N]: 0 = the row keeps its state at that step)");
   const bool state_only = (flags & VD_FLAG_STATE_ONLY) != 0;
-  VD_CHECK_ARG(state_only || tree || gates, "vd_lstm_forward: null pointer (gates may be NULL only with VD_FLAG_STATE_ONLY)");
+  VD_CHECK_ARG(state_only || tree || hold || gates, "vd_lstm_forward: null pointer (gates may be NULL only with VD_FLAG_STATE_ONLY)");
   VD_CHECK_ARG(!state_only || !gates, "vd_lstm_forward: VD_FLAG_STATE_ONLY saves no gate activations: gates must be NULL");
   VD_CHECK_ARG(!state_only || !(flags & VD_FLAG_BF16),
                "vd_lstm_forward: VD_FLAG_STATE_ONLY does not combine with VD_FLAG_BF16 (the bf16 recurrence reads the saved bf16 copy of h; flags = %d)", flags);
@@ -965,7 +1042,7 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
   // the step kernel of the pass, chosen once (LstmFwdPlan; lstm_step_fwd reads it)
   LstmFwdPlan P{N, H, Wh};
   P.bf16 = (flags & VD_FLAG_BF16) && vd_lstm_bf16_fits(N, H);
-  P.glds = !P.bf16 && T > 1 && vd_lstm_glds_fwd_fits(N, H);
+  P.glds = !P.bf16 && !hold && T > 1 && vd_lstm_glds_fwd_fits(N, H);   // (EpiLstmFwdHold has no LDS-DMA form: the generic kernels)
   P.split = P.glds ? vd_split_nprod(flags) : 0;
   if (int rc0 = lstm_weights(Wh, H, P.glds || (P.bf16 && (T > 1 || h0)), P.split, P.bf16 && T > 1, s, &P.w)) return rc0;
   // bf16 pass: the step kernels also write a bf16 copy of h (the operand of the dWh contraction of the same pass), and read it as h_{t-1}
@@ -988,6 +1065,7 @@ int vd_lstm_forward(const float* xproj, int64_t x_tstride, int64_t x_ld, const i
     // the type has no such kernels)
     int rc;
     if (tree) rc = lstm_step_fwd(P, t, hp, EpiLstmFwdTree{e, tok_mask + ((long)T + t) * N}, s);   // plane 1 of tok_mask: the parent rows
+    else if (hold) rc = lstm_step_fwd(P, t, hp, EpiLstmFwdHold{e, hp}, s);
     else if (state_only) rc = lstm_step_fwd(P, t, hp, EpiLstmFwdState{e}, s);
     else if (live) rc = lstm_step_fwd(P, t, hp, EpiLstmFwdLive{e}, s);
     else rc = lstm_step_fwd(P, t, hp, e, s);

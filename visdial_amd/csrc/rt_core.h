@@ -98,7 +98,7 @@ int vd_beam_topk_ban_p(const float* logits, int64_t ld, int64_t rows, int V, con
 // words of answers [dialogs x beam_len] that fit, right-aligned.  hist_sorted / inv: the length-sorted copy [Th x N] and the place of
 // every row in it, both or neither.  Needs r + 1 < R and Tq <= Th.
 int vd_beam_rollout_append_p(const int32_t* answers, int beam_len, int end_token, const int32_t* ques, int Tq, int dialogs, int R, int r,
-                             int32_t* hist_tok, int32_t* hist_sorted, const int32_t* inv, int Th, hipStream_t stream);
+                             int32_t* hist_tok, int32_t* hist_sorted, const int32_t* inv, int Th, hipStream_t stream, int concat_end = 0);
 // beam.hip: one pass of a discriminative rollout (VD_RETRIEVE_ROLLOUT; E2 - E4 there): history row r + 1 of every dialog = the non-zero tokens
 // of question row r, then the words that fit of the candidate that ranks first among scores row dialog * R + r ([dialogs * R x O], O <= 128:
 // the highest score, ties to the lowest index), right-aligned.  The candidate's tokens are read from opt_tok, step-major [To x opt_rows], at
@@ -106,7 +106,12 @@ int vd_beam_rollout_append_p(const int32_t* answers, int beam_len, int end_token
 // its words end at the first 0.  ques / hist_tok / hist_sorted / inv / Tq / Th as above.
 int vd_disc_rollout_pick_p(const float* scores, int O, const int32_t* opt_tok, int64_t opt_rows, int To, const int32_t* opt_uid,
                            const int32_t* ques, int Tq, int dialogs, int R, int r, int32_t* hist_tok, int32_t* hist_sorted,
-                           const int32_t* inv, int Th, hipStream_t stream);
+                           const int32_t* inv, int Th, hipStream_t stream, int concat_end = 0);
+// concat_end != 0 (both; VD_ROLLOUT_CONCAT_END, CH1 - CH6 there): the <END> id; row r + 1 = ROW r's tokens, <END>, the question's non-zero tokens
+// and the words, cut at the end where they do not fit Th columns, right-aligned.  0: the per-round row described above.
+// beam.hip: the round pass of a concatenated history (CH6): win [Wn x dialogs], step-major, = the last first(r - 1) - first(r) columns of
+// history row r of every dialog (the new tokens CH4 kept), right-aligned with zeros in front.  1 <= r < R, 1 <= Wn <= W.
+int vd_rollout_concat_window_p(const int32_t* hist_tok, int dialogs, int R, int r, int W, int Wn, int32_t* win, hipStream_t stream);
 
 #define VD_TRY(expr)                  \
   do {                                \
@@ -300,6 +305,8 @@ struct vd_model {
   bool use_im = false, use_hist = false, is_att = false, is_graph = false;
   vdrt::OptionCache ocache;
   vdrt::Switches sw;   // what vd_model_create read from the environment (rt_switches.h)
+  int rollout_max_words = 0;     // the most words an answer of the running rollout appends (disc: To, gen: beamLen - 1): the round pass of a
+                                 // concatenated history sizes its window of new tokens with it (rt_encoders.h history_round_concat)
   std::vector<double> beam_lp;   // host copy of the table s^alpha, s < beamLen (VD_BEAM_LENGTH_PENALTY), kept until its upload has run
   bool prof_hist = false;   // ev_prof[0..3] bracket the history branch of a Sequential encoder (gen pairs: vd_model_family_ms)
   ~vd_model();

@@ -257,6 +257,7 @@ struct Disc : Decoder {
   // (pass 0's beside the option recurrence, as in the plain step), vd_score_ce over all N rounds, and -- not after the last -- the pick
   // kernel, which writes history row r + 1 of every dialog from the rank-1 candidate of its round r.  Nothing waits for the host between
   // passes.  The last pass IS the result for every round: rows <= r of a dialog are final after pass r and every encoder is causal.
+  // VD_ROLLOUT_CONCAT_END (CH1-CH6): the pick kernel writes the concatenated row instead; the passes are the same.
   int retrieve_rollout(vd_model* m, BatchSlot& b) {
     VD_TRY(refuse_round_rollout_in_training(m, "vd_model_retrieve"));
     if (m->training) {
@@ -288,6 +289,7 @@ struct Disc : Decoder {
     const float* optH;
     VD_TRY(option_states_full(m, b, os, &optH));
     const HistRows hr(b);
+    m->rollout_max_words = b.opt.T;
     for (int r = 0; r < R; ++r) {
       if (r > 0) {                                                            // E5: rows 0 .. r of every dialog are final now
         VdRange rr("encoder forward");
@@ -296,7 +298,7 @@ struct Disc : Decoder {
       VD_TRY(vd_score_ce(optH, enc_out, b.gt, scores, loss_rows, nullptr, nullptr, N, O, (int)H, 1.0f / N, s));
       if (r + 1 < R)                                                          // E2 - E4: the pick becomes history row r + 1
         VD_TRY(vd_disc_rollout_pick_p(scores, O, b.opt.tok, NO, b.opt.T, b.opt_uid, b.q.tok, b.q.T, B, R, r, hr.tok, hr.tok_sorted, hr.inv,
-                                      b.h.T, s));
+                                      b.h.T, s, m->sw.rollout_concat_end));
     }
     VD_TRY(stage_loss(m, loss_rows, N, false, s));
     m->scores = scores;
@@ -901,6 +903,9 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
   if (rollout) {   // the round indices of every pass, cached on the device by shape
     VD_TRY(refuse_round_rollout_in_training(m, "vd_model_beam_search"));
     VD_CHECK_ARG(b.h.present && b.q.present && b.h.N == m->N && b.h.T >= b.q.T, "vd_model_beam_search: VD_BEAM_ROLLOUT = 1 needs the batch's history");
+    VD_CHECK_ARG(m->sw.rollout_concat_end == 0 || end == m->sw.rollout_concat_end,
+                 "vd_model_beam_search: end_token = %d, but this model was created with VD_ROLLOUT_CONCAT_END = %d: the <END> that separates the "
+                 "rounds of a concatenated history row is the one that ends an answer", end, m->sw.rollout_concat_end);
     std::vector<int32_t> rounds((size_t)R * n);
     for (int r = 0; r < R; ++r)
       for (int i = 0; i < n; ++i) rounds[(size_t)r * n + i] = (i / k) * R + r;
@@ -933,6 +938,7 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
     VD_HIP(hipMemcpyAsync(lp, m->beam_lp.data(), (size_t)L * 8, hipMemcpyHostToDevice, s));
   }
   const HistRows hr(b);
+  m->rollout_max_words = L - 1;
   for (int r = 0; r < passes; ++r) {
     int32_t* out_tok = reinterpret_cast<int32_t*>(out) + (size_t)r * G * L;
     if (rollout) {
@@ -959,7 +965,7 @@ inline int Gen_beam_search(Gen* g, vd_model* m, int k, int L, int start, int end
     VD_TRY(vd_beam_finish(G, kg, L, hist[0], scores, best_score, best_len, best_hist, out_tok,
                           reinterpret_cast<double*>(out + tok_bytes) + (size_t)r * G, s));
     if (rollout && r + 1 < R)                                               // R2: the answer becomes history row r + 1
-      VD_TRY(vd_beam_rollout_append_p(out_tok, L, end, b.q.tok, b.q.T, N, R, r, hr.tok, hr.tok_sorted, hr.inv, b.h.T, s));
+      VD_TRY(vd_beam_rollout_append_p(out_tok, L, end, b.q.tok, b.q.T, N, R, r, hr.tok, hr.tok_sorted, hr.inv, b.h.T, s, m->sw.rollout_concat_end));
   }
   std::vector<uint8_t> staged;
   VD_TRY(gen_read_back(m, out, tok_bytes + Gall * 8, &staged));

@@ -214,6 +214,69 @@ inline int round_linear(vd_model* m, hipStream_t s, const std::string& name, con
                         float* y, long ldy) {
   return vd_gemm_nt(x, ldx, Wp(m, name + ".W"), in, Wp(m, name + ".b"), y, ldy, rows, (int)out, (int)in, tanh ? VD_ACT_TANH : VD_ACT_NONE, 0, s);
 }
+// The history branch of a round pass on a CONCATENATED history (VD_ROLLOUT_CONCAT_END; beam.hip CH6): row r of a dialog is row r - 1 followed by
+// the new tokens CH4 kept, so the stack's state after row r is its state after row r - 1 continued over those tokens -- at most 1 + Tq +
+// (words of an answer) columns (41 at full size) instead of Th (300).  Pass 1 first gathers every dialog's row-0 final (h, c) of both layers
+// from what pass 0 left (the rows are length-sorted on the wavefront path: through `inv`) into rnd.carry.* [B x H].  Pass r: the window of new
+// tokens [Wn x B] (vd_rollout_concat_window_p), its embedding, and per layer the input projection and ONE vd_lstm_forward from the carry with
+// VD_FLAG_HOLD (a row's pad in front of its tokens keeps the carried state); the last step is the new carry and *last.  9 + 2 Wn launches and
+// four copies.  Every precondition that fails is an error: the full-width history_round is never substituted.
+// (A wavefront with an initial state -- Wn + 2 launches instead of 2 Wn -- is a follow-up; DESIGN.md "One round per pass" has the contract.)
+inline int history_round_concat(vd_model* m, hipStream_t s, BatchSlot& b, const std::vector<const SeqLSTM*>& layers, int r, float* cache,
+                                const float** last) {
+  const int N = b.h.N, W = b.h.T, R = m->p.maxQuesCount, B = N / R, L = (int)layers.size();
+  VD_CHECK_ARG(b.h.present && b.q.present && N == B * R && r >= 1 && r < R, "round pass %d of %d rounds over %d history rows", r, R, N);
+  VD_CHECK_ARG(L == 2, "VD_ROLLOUT_ENCODER = round on a concatenated history (VD_ROLLOUT_CONCAT_END) continues a two-layer history stack; this "
+               "model has numLayers = %d: use VD_ROLLOUT_ENCODER = full", L);
+  VD_CHECK_ARG(!(m->flags & VD_FLAG_BF16), "VD_ROLLOUT_ENCODER = round on a concatenated history continues the history stack through "
+               "VD_FLAG_HOLD, which runs exact fp32 steps; this model's recurrences run in bf16: use VD_ROLLOUT_ENCODER = full");
+  VD_CHECK_ARG(m->rollout_max_words >= 0 && layers[0]->h && layers[0]->T == W && layers[0]->N == N && layers[1]->T == W && layers[1]->N == N,
+               "round pass on a concatenated history without a full encoder pass on this batch");
+  const long E = layers[0]->D, H = layers[0]->H, BH = (long)B * H;
+  const int Wn = (int)std::min<long>(W, 1L + b.q.T + m->rollout_max_words);
+  const long TB = (long)Wn * B;
+  float* carry[2][2];   // [layer][h, c]
+  for (int l = 0; l < 2; ++l)
+    for (int k = 0; k < 2; ++k)
+      VD_TRY(ws_get(m, std::string("rnd.carry.") + (k ? "c" : "h") + std::to_string(l + 1), (size_t)BH, &carry[l][k]));
+  if (r == 1) {   // the states pass 0 left for row 0 of every dialog: the last step, sorted row inv[d * R] (or row d * R without a sort)
+    float* rows;
+    VD_TRY(ws_get(m, "rnd.carry.rows", (size_t)N * H, &rows));
+    for (int l = 0; l < 2; ++l)
+      for (int k = 0; k < 2; ++k) {
+        const float* src = k ? layers[l]->cell_at(W - 1) : layers[l]->out_at(W - 1);
+        if (b.h.sorted) {
+          VD_TRY(vd_embed_gather(src, b.h.inv, nullptr, rows, N, (int)H, 1.f, s));
+          src = rows;
+        }
+        VD_TRY(rows_copy(carry[l][k], H, src, (long)R * H, B, (int)H, s));
+      }
+  }
+  int32_t* tok;
+  float* x;
+  VD_TRY(ws_get(m, "rnd.cw.tok", (size_t)TB, &tok));
+  VD_TRY(ws_get(m, "rnd.cw.x", (size_t)TB * E, &x));
+  VD_TRY(vd_rollout_concat_window_p(b.h.tok, B, R, r, W, Wn, tok, s));
+  VD_TRY(vd_embed_gather(Wp(m, "embed"), tok, nullptr, x, TB, (int)E, 1.f, s));
+  float *xp, *h[2], *c[2];
+  VD_TRY(ws_get(m, "rnd.cw.xp", (size_t)TB * 4 * H, &xp));
+  for (int l = 0; l < 2; ++l) {
+    VD_TRY(ws_get(m, "rnd.cw.h" + std::to_string(l + 1), (size_t)TB * H, &h[l]));
+    VD_TRY(ws_get(m, "rnd.cw.c" + std::to_string(l + 1), (size_t)TB * H, &c[l]));
+    VD_TRY(vd_gemm_nn(l ? h[0] : x, l ? H : E, layers[l]->Wx(m), 4 * H, Wp(m, layers[l]->name + ".b"), xp, 4 * H, (int)TB, (int)(4 * H),
+                      (int)(l ? H : E), 0, s));
+    VD_TRY(vd_lstm_forward(xp, (int64_t)B * 4 * H, 4 * H, nullptr, tok, layers[l]->Wh(m), carry[l][0], carry[l][1], nullptr, h[l], c[l], Wn, B,
+                           (int)H, VD_FLAG_HOLD, s));
+  }
+  for (int l = 0; l < 2; ++l) {   // the last step is the state after row r (a dialog without a kept token held its carry through)
+    VD_HIP(hipMemcpyAsync(carry[l][0], h[l] + (long)(Wn - 1) * BH, (size_t)BH * 4, hipMemcpyDeviceToDevice, s));
+    VD_HIP(hipMemcpyAsync(carry[l][1], c[l] + (long)(Wn - 1) * BH, (size_t)BH * 4, hipMemcpyDeviceToDevice, s));
+  }
+  *last = carry[1][0];
+  if (cache) VD_TRY(rows_copy(cache + (long)r * H, (long)R * H, *last, H, B, (int)H, s));
+  return VD_OK;
+}
+
 // The history branch of a round pass (Encoder::forward_round), every encoder family: history row r of the B dialogs as a B-row sequence at
 // full width -- step-major [Th x B], every row active at every step, maskZero per token (a rollout model lays rows >= 1 out at full width
 // anyway, runtime.hip upload_tokens) -- through the branch's layers: the two-layer wavefront, or one recurrence per layer for another
@@ -221,6 +284,7 @@ inline int round_linear(vd_model* m, hipStream_t s, const std::string& name, con
 // copy).  Th + 4 launches with two layers, and the copy.
 inline int history_round(vd_model* m, hipStream_t s, BatchSlot& b, const std::vector<const SeqLSTM*>& layers, int r, float* cache,
                          const float** last) {
+  if (m->sw.rollout_concat_end) return history_round_concat(m, s, b, layers, r, cache, last);   // CH6: the new tokens alone
   const int N = b.h.N, Th = b.h.T, R = m->p.maxQuesCount, B = N / R, L = (int)layers.size();
   const long E = layers[0]->D, H = layers[0]->H, TB = (long)Th * B;
   VD_CHECK_ARG(b.h.present && N == B * R && r >= 1 && r < R && L >= 1, "round pass %d of %d rounds over %d history rows", r, R, N);

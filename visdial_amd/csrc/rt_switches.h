@@ -9,7 +9,7 @@
 //  - real switches refuse an empty string and trailing characters, and a NaN fails both comparisons of its range: VD_SAMPLE_TOPP in (0, 1],
 //    VD_BEAM_DIVERSITY in [0, FLT_MAX] (lambda is applied in fp32), VD_BEAM_LENGTH_PENALTY in [0, DBL_MAX].  errno is not looked at.
 //  - the sampling and beam variables and VD_BEAM_ROLLOUT are not read for decoder disc, VD_RETRIEVE_ROLLOUT not for decoder gen: garbage in
-//    them is ignored there.  VD_ROLLOUT_ENCODER is validated for every model.
+//    them is ignored there.  VD_ROLLOUT_ENCODER and VD_ROLLOUT_CONCAT_END are validated for every model.
 #pragma once
 #include <errno.h>
 #include <float.h>
@@ -38,6 +38,9 @@ struct Switches {                     // (decoder the variable is read for) what
   // picks (beam.hip R1-R6 / E1-E5); an upload then lays out history rows >= 1 at full width (runtime.hip upload_tokens)
   bool beam_rollout = false, retrieve_rollout = false;
   bool rollout_round = false;         // VD_ROLLOUT_ENCODER = round: a rollout's passes >= 1 encode one round alone (Encoder::forward_round)
+  // VD_ROLLOUT_CONCAT_END (both): the <END> id; a rollout then writes CONCATENATED history rows (beam.hip CH1-CH6: row r + 1 = row r, <END>, the
+  // question, the answer) instead of per-round rows; 0 = off.  vd_model_create refuses a value above vocabSize (it knows V; this header does not)
+  int rollout_concat_end = 0;
 };
 
 // The typed readers.  An unset variable leaves *out alone; a refusal is "vd_model_create: NAME = 'text' <must>".
@@ -116,6 +119,14 @@ inline int parse_switches(const char* encoder, const char* decoder, int lstmBf16
   if (!read_choice("VD_ROLLOUT_ENCODER", "full", "round", "must be 'full' or 'round' (unset = full)", &round)) return -1;
   // `round` is kept only where a rollout applies: without one, or with an encoder without a history, both calls run the plain search / retrieval
   sw.rollout_round = round && (sw.beam_rollout || sw.retrieve_rollout) && strstr(encoder, "hist");
+  if (!read_int("VD_ROLLOUT_CONCAT_END", 0, "must be an integer >= 0: the <END> token id (0 = off)", &sw.rollout_concat_end)) return -1;
+  // kept, like `round`, only where a rollout applies; there it is for the encoders that read the running concatenation.  With `round` the later
+  // passes continue the history stack from a carried state over the new tokens alone (rt_encoders.h history_round_concat)
+  if (!((sw.beam_rollout || sw.retrieve_rollout) && strstr(encoder, "hist"))) sw.rollout_concat_end = 0;
+  if (sw.rollout_concat_end && strncmp(encoder, "lf-", 3))
+    return vd_set_error("vd_model_create: VD_ROLLOUT_CONCAT_END = %d with encoder '%s': its history is one row per round (beam.hip R2 / E4), not "
+                        "the running concatenation of the dialog; the concatenation rule (CH1-CH6) is for lf-ques-hist, lf-ques-im-hist and "
+                        "lf-att-ques-im-hist", sw.rollout_concat_end, encoder), -1;
   *out = sw;
   return 0;
 }

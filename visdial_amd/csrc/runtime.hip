@@ -311,6 +311,8 @@ int vd_model_create(const vd_model_params* p, const char* encoder, const char* d
   VD_CHECK_ARG(flags >= 0, "vd_model_create: lstmBf16 must be 0, 1, 3, 6 or 9 (got %d)", p->lstmBf16);
   Switches sw;   // the environment's switches (rt_switches.h): a refused value touches no device and leaves no model behind
   VD_TRY(parse_switches(encoder, decoder, p->lstmBf16, &sw));
+  VD_CHECK_ARG(sw.rollout_concat_end <= p->vocabSize, "vd_model_create: VD_ROLLOUT_CONCAT_END = %d is no token id: vocabSize is %d",
+               sw.rollout_concat_end, (int)p->vocabSize);
   vd_model* m = new vd_model();
   m->p = *p;
   m->sw = sw;

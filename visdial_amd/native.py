@@ -35,13 +35,16 @@ SWITCHES = (
     ('beamRollout', 'VD_BEAM_ROLLOUT', _text, int, 0, 'gen'),                             # the search rolls its answers into the history
     ('retrieveRollout', 'VD_RETRIEVE_ROLLOUT', _text, int, 0, 'disc'),                    # vd_model_retrieve rolls its picks into it
     ('rolloutEncoder', 'VD_ROLLOUT_ENCODER', _text, str, 'full', None),                   # 'round': passes 1 .. R - 1 encode one round
+    ('rolloutConcatEnd', 'VD_ROLLOUT_CONCAT_END', _text, int, 0, None),                   # the <END> id: a rollout writes concatenated rows
 )
 """The switches the library reads from the environment inside vd_model_create (csrc/rt_switches.h; the Lua host sets the same variables).
 NativeModel sets every row's variable to the text of its params value -- unset where that is None: a params without the key creates the
 model with the variable unset -- creates the model and puts the previous environment back, also after a failed create, so two models of
 one process can differ.  Python validates nothing: the values go through as written and the library is the one that refuses.  What the
 model was created with stays in `NativeModel._knobs` (the default for a row of the other decoder, which the library does not read);
-generateAnswers checks what it is asked for against it."""
+generateAnswers checks what it is asked for against it.  rolloutConcatEnd (VD_ROLLOUT_CONCAT_END) is the <END> id of a rollout on a
+concatenated history (split_eval.py CH1-CH6): evaluate.py -rolloutHistory concat fills it from the loader, and `retrieve_rollout_batch`
+refuses a device rollout whose params rolloutHistory does not agree with what the model was created with."""
 
 
 class _DevArray(object):
@@ -348,6 +351,10 @@ class NativeModel(SplitEval):
         gen = self.params['decoder'] == 'gen'
         if 'hist' not in batch or not self._knobs['beamRollout' if gen else 'retrieveRollout']:
             return SplitEval.retrieve_rollout_batch(self, batch)
+        if self._knobs['rolloutConcatEnd'] != self._concat_end():
+            raise ValueError("rollout = 1 with rolloutHistory = %r (<END> = %d), but this model was created with rolloutConcatEnd = %d: the device "
+                             "rollout takes its history rule when the model is created (params rolloutConcatEnd of NativeModel)"
+                             % (self.params.get('rolloutHistory', 'row'), self._concat_end(), self._knobs['rolloutConcatEnd']))
         self.upload(batch)
         N, O = self._N, int(self.params.get('numOptions', 100))
         if gen:
@@ -365,13 +372,17 @@ class NativeModel(SplitEval):
     def rollout_history(self, batch, ranks):
         if getattr(self, '_rollout_answers', None) is None:
             return SplitEval.rollout_history(self, batch, ranks)
-        from .split_eval import rollout_history_row
+        from .split_eval import rollout_concat_row, rollout_history_row
         tokens, end = self._rollout_answers                       # decoder gen: the beam search's answers (R2 / R3)
         B, R, Th = batch['hist'].shape
         hist = np.array(batch['hist'])
+        concat, self._cut = self._concat_end(), []
         for i in range(B):
             for r in range(R - 1):
-                hist[i, r + 1] = rollout_history_row(batch['ques_fwd'][i, r], tokens[i * R + r], Th, end)
+                if concat:                                        # CH1 - CH4
+                    hist[i, r + 1] = rollout_concat_row(hist[i, r], batch['ques_fwd'][i, r], tokens[i * R + r], concat, end, self._cut)
+                else:
+                    hist[i, r + 1] = rollout_history_row(batch['ques_fwd'][i, r], tokens[i * R + r], Th, end)
         return hist
 
     # Model:evaluate / retrieve / predict (model.lua:109-246): visdial_amd/split_eval.py, shared with the Python host

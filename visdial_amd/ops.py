@@ -90,6 +90,9 @@ FLAG_STATE_ONLY = 32
 # (non-zero = a node; the nodes of a step are a prefix of its rows), plane 1 the parent row of the step before (of h0 / c0 at step 0);
 # h and c are [T x N x H], forward only, exact fp32 only
 FLAG_TREE = 64
+# VD_FLAG_HOLD (lstm_forward with gates=None and tok_mask): a row whose mask is 0 at a step keeps (h, c) of the step before -- (h0, c0) at the
+# first -- instead of being zeroed; h / c [T x N x H] hold every row's running state.  Forward only, exact fp32, refused with every other flag
+FLAG_HOLD = 128
 
 
 def lstm_fwd_row_tile(N):

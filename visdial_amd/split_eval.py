@@ -168,6 +168,53 @@ def rollout_history_row(ques_row, answer_row, Th, endToken):
     return out
 
 
+
+# Rollout on a concatenated history (csrc/beam.hip CH1-CH6; evaluate.py -rollout 1 -rolloutHistory concat): the encoders whose history row is the
+# running concatenation of the dialog (lf-ques-hist, lf-ques-im-hist, lf-att-ques-im-hist; dataloader.lua:243-255).  W = the width of the
+# batch's history, END = the <END> token id.
+#   CH1. row 0 is the batch's (R1).
+#   CH2. lenH(r) = W - (the index of the first non-zero column of row r), 0 for an all-zero row; the last lenH columns of row r are its
+#        tokens, carried over as they are (a 0 among them included).
+#   CH3. the new tokens of round r are END, then the non-zero tokens of question row r in order, then the answer's words (R3 for a beam
+#        answer, E2 / E3 for a picked candidate).  END is appended even when the question is empty and there are no words, as the loader does
+#        for the missing rounds of the test split.
+#   CH4. row r + 1 = row r's lenH tokens followed by the first min(n_new, W - lenH) new tokens, right-aligned in W columns with zeros in
+#        front.  What does not fit is cut at the END of the new tokens: words first, then question tokens, then END; a full row repeats
+#        itself.  (The reference's loader has no such case: it would index out of range.)  Every row is a prefix extension of the one before.
+#   CH5. R5, R6 and E5 hold as written: an lf encoder reads only its own row.
+#   CH6. prefix property: the history stack's state after row r + 1 is its state after row r continued over the kept new tokens.
+def rollout_concat_new(ques_row, answer_row, endToken, answerEnd):
+    """CH3: the new tokens of a round with question row `ques_row` and answer token row `answer_row` (entry 0 stands in <START>'s place, the
+    words end at the first `answerEnd` or 0: answerEnd = END for a beam answer, 0 for a `rollout_candidate_row`)"""
+    new = [int(endToken)] + [int(t) for t in np.asarray(ques_row).reshape(-1) if int(t) != 0]
+    for t in np.asarray(answer_row).reshape(-1)[1:]:
+        if int(t) == int(answerEnd) or int(t) == 0:
+            break
+        new.append(int(t))
+    return new
+
+
+def rollout_concat_len(row):
+    """CH2: lenH of a history row [W]"""
+    nz = np.flatnonzero(np.asarray(row).reshape(-1))
+    return int(np.asarray(row).size - nz[0]) if nz.size else 0
+
+
+def rollout_concat_row(prev_row, ques_row, answer_row, endToken, answerEnd, cut=None):
+    """CH2 - CH4: the concatenated history row [W] that follows `prev_row` [W] after a round with question row `ques_row` and answer token
+    row `answer_row`.  `cut` (a list): gains True if CH4 cut a new token, else False."""
+    prev = np.asarray(prev_row).reshape(-1)
+    W, lenH = prev.size, rollout_concat_len(prev_row)
+    new = rollout_concat_new(ques_row, answer_row, endToken, answerEnd)
+    keep = new[:W - lenH]
+    if cut is not None:
+        cut.append(len(keep) < len(new))
+    row = [int(t) for t in prev[W - lenH:]] + keep
+    out = np.zeros(W, np.int64)
+    out[W - len(row):] = row
+    return out
+
+
 # Ranking on a rollout (csrc/beam.hip E1-E5; evaluate.py -rollout 1): the candidates of round r of a discriminative model are ranked on a
 # history that holds the model's own picks for the rounds before it.  O = numOptions, To = the width of an `options` row.
 #   E1. round 0's history row is the batch's (R1).
@@ -199,15 +246,19 @@ def rollout_pick(ranks_row):
     return int(first[0])
 
 
-def rollout_picked_history(batch, picks):
+def rollout_picked_history(batch, picks, concat=False, endToken=None, cut=None):
     """E1 / E4: the history [B x R x Th] of `batch` (ques_fwd [B x R x Tq], hist [B x R x Th], options [B * R x O x To]) when round r of
-    every dialog was answered with candidate picks[dialog * R + r]: row 0 is the batch's, rows >= 1 are rebuilt"""
+    every dialog was answered with candidate picks[dialog * R + r]: row 0 is the batch's, rows >= 1 are rebuilt.  concat: by CH1 - CH4 with
+    <END> = endToken instead of E4 (`cut` as `rollout_concat_row`)"""
     B, R, Th = batch['hist'].shape
     hist = np.array(batch['hist'])
     for i in range(B):
         for r in range(R - 1):
-            cand = batch['options'][i * R + r, int(picks[i * R + r])]
-            hist[i, r + 1] = rollout_history_row(batch['ques_fwd'][i, r], rollout_candidate_row(cand), Th, 0)
+            cand = rollout_candidate_row(batch['options'][i * R + r, int(picks[i * R + r])])
+            if concat:
+                hist[i, r + 1] = rollout_concat_row(hist[i, r], batch['ques_fwd'][i, r], cand, endToken, 0, cut)
+            else:
+                hist[i, r + 1] = rollout_history_row(batch['ques_fwd'][i, r], cand, Th, 0)
     return hist
 
 
@@ -302,6 +353,7 @@ class SplitEval(object):
     lhoodTreeStats = dict(nodes=0, live=0, executed=0, total=0)
 
     rolloutRows = (0, 0)         # params rollout: (history rows that differ from the ground truth's, history rows) of the last retrieve / predict
+    rolloutCut = 0               # params rolloutHistory = 'concat': the generated history rows CH4 cut, of the last retrieve / predict
 
     def _rollout(self):
         """params rollout (0 / 1) of retrieve / predict, refusing what cannot be ranked on a rollout"""
@@ -311,11 +363,27 @@ class SplitEval(object):
         if rollout and int(self.params.get('optionCache', 0) or 0):
             raise ValueError('rollout = 1 with optionCache: a cached batch carries only the candidates the cache did not hold, and the '
                              'rollout reads a picked candidate\'s tokens from the batch; combining the two is left for a follow-up')
-        if rollout and self.params.get('concatHistory') and self.params.get('useHistory'):
+        concat = self.params.get('rolloutHistory') == 'concat'
+        if rollout and self.params.get('concatHistory') and self.params.get('useHistory') and not concat:
             raise ValueError("rollout = 1 with encoder '%s' (concatHistory): its history row is the running concatenation of the rounds, "
-                             "and E4 describes the per-round row only; a concatenation rule is left for a follow-up"
-                             % self.params.get('encoder'))
+                             "and E4 describes the per-round row only; params rolloutHistory = 'concat' (with rolloutConcatEnd = the <END> "
+                             "id) rolls out by the concatenation rule CH1-CH6" % self.params.get('encoder'))
+        if rollout and concat and self.params.get('useHistory'):
+            if not self.params.get('concatHistory'):
+                raise ValueError("rollout = 1 with rolloutHistory = 'concat' and encoder '%s': its history is one row per round (E4), not the "
+                                 "running concatenation" % self.params.get('encoder'))
+            self._concat_end()
         return rollout
+
+    def _concat_end(self):
+        """the <END> id of CH3 if this host rolls out on a concatenated history (params rolloutHistory = 'concat'), else 0"""
+        if self.params.get('rolloutHistory') != 'concat' or not (self.params.get('useHistory') and self.params.get('concatHistory')):
+            return 0
+        end = int(self.params.get('rolloutConcatEnd') or 0)
+        if end < 1 or end > int(self.params.get('vocabSize', end)):
+            raise ValueError("rolloutHistory = 'concat' needs params rolloutConcatEnd = the <END> token id in [1, vocabSize], got %r"
+                             % (self.params.get('rolloutConcatEnd'),))
+        return end
 
     def _all_ranks(self, batch):
         """the host's own retrieval of every candidate's rank, [N x O], whatever params useGt says"""
@@ -329,8 +397,8 @@ class SplitEval(object):
 
     def retrieve_rollout_batch(self, batch):
         """E1-E5 on the host, the obviously-right path (like beamBatch = 0): R retrievals of the whole batch; before call r + 1 history row
-        r + 1 of every dialog is rewritten IN `batch` from the rank-1 candidate of round r in call r (E2 - E4); round r's ranks are those
-        of call r.  `batch` carries `options` (decoder disc) and the history at its untrimmed width.  Returns all ranks [N x O]; a batch
+        r + 1 of every dialog is rewritten IN `batch` from the rank-1 candidate of round r in call r (E2 - E4; params rolloutHistory =
+        'concat': CH1 - CH4 with <END> = params rolloutConcatEnd); round r's ranks are those of call r.  `batch` carries `options` (decoder disc) and the history at its untrimmed width.  Returns all ranks [N x O]; a batch
         without a history is ranked once, as ever."""
         if 'hist' not in batch:
             return self._all_ranks(batch)
@@ -338,6 +406,7 @@ class SplitEval(object):
             raise ValueError("rollout = 1 on this host ranks the candidates of decoder 'disc'; for decoder 'gen' the rollout is the beam "
                              "search's and runs in the model-level runtime: use -host native (visdial_amd.native.NativeModel)")
         B, R, Th = batch['hist'].shape
+        end = self._concat_end()                                           # CH1 - CH4 instead of E4
         out = None
         for r in range(R):
             ranks = self._all_ranks(batch)
@@ -345,8 +414,11 @@ class SplitEval(object):
             out[r::R] = ranks[r::R]
             if r + 1 < R:
                 for i in range(B):
-                    cand = batch['options'][i * R + r, rollout_pick(ranks[i * R + r])]
-                    batch['hist'][i, r + 1] = rollout_history_row(batch['ques_fwd'][i, r], rollout_candidate_row(cand), Th, 0)
+                    cand = rollout_candidate_row(batch['options'][i * R + r, rollout_pick(ranks[i * R + r])])
+                    if end:
+                        batch['hist'][i, r + 1] = rollout_concat_row(batch['hist'][i, r], batch['ques_fwd'][i, r], cand, end, 0)
+                    else:
+                        batch['hist'][i, r + 1] = rollout_history_row(batch['ques_fwd'][i, r], cand, Th, 0)
         return out
 
     def _test_batch(self, dataloader, start, dtype, rollout):
@@ -367,10 +439,12 @@ class SplitEval(object):
             truth = batch.pop('hist_gt', None)
             ranks = np.asarray(self.retrieve_rollout_batch(batch))
             if truth is not None:
+                self._cut = []
                 hist = self.rollout_history(batch, ranks)
-                tally += [0] * (8 - len(tally))
+                tally += [0] * (9 - len(tally))
                 tally[6] += int((hist != truth).any(2).sum())
                 tally[7] += hist.shape[0] * hist.shape[1]
+                tally[8] += int(sum(self._cut))                    # (`rollout_history` leaves CH4's cuts there)
         else:
             ranks = np.asarray(self.retrieveBatch(batch))
         if int(self.params.get('fusedLhood', 0) or 0) == 2:
@@ -390,7 +464,9 @@ class SplitEval(object):
 
     def rollout_history(self, batch, ranks):
         """the history [B x R x Th] a rollout of `batch` generated, given the all ranks [N x O] it returned: rebuilt from the picks (E4)"""
-        return rollout_picked_history(batch, [rollout_pick(row) for row in ranks])
+        end = self._concat_end()
+        self._cut = []
+        return rollout_picked_history(batch, [rollout_pick(row) for row in ranks], bool(end), end, self._cut)
 
     def evaluate(self, dataloader, dtype):
         """model.lua:109-139: validation loss / perplexity over a split: the sum over batches of `forwardBackward(batch, true)` (gen:
@@ -450,6 +526,7 @@ class SplitEval(object):
         self.optionCacheRows = tuple(tally[:2])
         self.lhoodTreeStats = dict(zip(('nodes', 'live', 'executed', 'total'), (tally + [0] * 4)[2:6]))
         self.rolloutRows = tuple((tally + [0] * 6)[6:8])
+        self.rolloutCut = (tally + [0] * 9)[8]
         print('\n%s - Retrieval:' % dtype)
         metrics = utils.processRanks(ranks)
         self._set_training(True)
@@ -471,6 +548,7 @@ class SplitEval(object):
         self.optionCacheRows = tuple(tally[:2])
         self.lhoodTreeStats = dict(zip(('nodes', 'live', 'executed', 'total'), (tally + [0] * 4)[2:6]))
         self.rolloutRows = tuple((tally + [0] * 6)[6:8])
+        self.rolloutCut = (tally + [0] * 9)[8]
         self._set_training(True)
         return self._rank_records(dataloader, dtype, ranks, dtype == 'test')
 
@@ -504,14 +582,16 @@ class SplitEval(object):
             batch['hist'] = np.ascontiguousarray(dataloader.data[dtype]['hist'][np.asarray(convIds, np.int64) - 1]).astype(np.int32)
         return batch
 
-    def rollout_dialog(self, batch, search, endToken):
-        """R1-R6 for the ONE dialog of `batch` on the host: `search(r)` is the beam search of round r from the state `_gen_begin` left,
+    def rollout_dialog(self, batch, search, endToken, concat=False):
+        """R1-R6 (concat: CH1-CH6, the row by `rollout_concat_row`) for the ONE dialog of `batch` on the host: `search(r)` is the beam search of round r from the state `_gen_begin` left,
         returning its groups' (tokens, score) (`beam_search_round`).  Round r >= 1 first gets its history row from round r - 1's answer
         (batch['hist'] is rewritten in place) and a new `_gen_encode`.  Returns search(r) per round."""
         R, Th = batch['ques_fwd'].shape[1], batch['hist'].shape[2]
         found = []
         for r in range(R):
-            if r > 0:
+            if r > 0 and concat:
+                batch['hist'][0, r] = rollout_concat_row(batch['hist'][0, r - 1], batch['ques_fwd'][0, r - 1], found[-1][0][0], endToken, endToken)
+            elif r > 0:
                 batch['hist'][0, r] = rollout_history_row(batch['ques_fwd'][0, r - 1], found[-1][0][0], Th, endToken)
             self._gen_encode(batch)
             found.append(search(r))
