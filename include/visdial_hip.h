@@ -437,7 +437,14 @@ int vd_model_set_training(vd_model* m, int on);           /* wrapper:training() 
 int vd_model_set_dropout_mask(vd_model* m, const char* site, const uint8_t* host_keep, int64_t n); /* NULL host = clear */
 /* batch re-layout + upload (model.lua:255-294, dataloader.lua:410-475), asynchronous, double-buffered */
 int vd_model_upload_batch(vd_model* m, const vd_batch* host_batch);
-/* Model:forwardBackward on the uploaded batch (model.lua:249-342); zeroes the gradients first unless only_forward */
+/* Model:forwardBackward on the uploaded batch (model.lua:249-342); zeroes the gradients first unless only_forward.
+ * Environment VD_LABEL_SMOOTHING = eps, a real in [0, 1) (0 / unset = off; any other text is refused by name), read by vd_model_create
+ * for both decoders: a TRAINING step (only_forward = 0) takes soft targets t = (1 - eps) onehot + eps / K in the place of the one-hot
+ * ones -- disc: K = the O options of a round, loss_n = lse - sum_o t_o s_o, ds_o = (softmax_o - t_o) gscale; gen: K = the V vocabulary
+ * words, on every row that contributes without it (non-pad input and target > 0), loss_r = lse - sum_c t_c logit_c, gradient
+ * softmax - t (rules LS1-LS4 at the top of csrc/loss.hip).  vd_model_loss then reports the smoothed loss.  only_forward = 1,
+ * vd_model_retrieve*, perplexity and every score or rank are what they are without the variable, and eps = 0 launches the kernels
+ * of a library that does not know it, with the same arguments. */
 int vd_model_forward_backward(vd_model* m, int only_forward);
 int vd_model_loss(vd_model* m, float* loss);              /* curLoss of the last forward (waits for it): disc = mean
                                                              cross-entropy, gen = summed NLL (model.lua:309-311,330) */
@@ -488,7 +495,15 @@ int vd_model_retrieve(vd_model* m);
  * kernel's row tile for N), total = To * rounds * options.  vd_model_retrieve is unaffected.  vd_model_create refuses the variable
  * for decoder disc and for lstmBf16 = 1. */
 int vd_model_retrieve_lhood(vd_model* m);
-/* wrapperdW*gscale -> clamp(-5,5) -> adam -> lr decay (model.lua:96-105; optim_updates.lua:62-91) */
+/* wrapperdW*gscale -> clamp(-5,5) -> adam -> lr decay (model.lua:96-105; optim_updates.lua:62-91).
+ * Environment VD_GRAD_CLIP_NORM = c and VD_WEIGHT_DECAY = lambda, finite reals >= 0 (0 / unset = off; any other text is refused by
+ * name), read by vd_model_create for both decoders (rules GC1-GC3 and WD1 in csrc/elementwise.hip).  c > 0: the norm
+ * || gscale wrapperdW ||_2 of the whole flat gradient -- after the caller's all-reduce -- is computed on the main stream by a
+ * partial-sum kernel and a one-workgroup kernel (no atomic, no host read, no synchronisation; a fixed order, so two runs give the same
+ * bits); where it is finite and > c every element is scaled by c / norm in front of the clamp, otherwise by 1, so a non-finite norm
+ * never turns finite gradients into NaN.  wrapperdW keeps the clamped value, as without the variable.  lambda > 0: decoupled decay,
+ * w <- w - step m / (sqrt(v) + eps) - lr lambda w_old on every element, lr the learning rate before this call's decay.  With both off
+ * the call launches vd_clamp_adam as a library that does not know the variables does. */
 int vd_model_update(vd_model* m, float gscale);
 int vd_model_learning_rate(vd_model* m, double* lr, int set);
 /* Model:generateAnswers, device side (model.lua:432-613; generative decoder).  The host keeps the candidate

@@ -1,7 +1,10 @@
 // HBM-bound helper kernels: embedding gather / gradient scatter, dropout masks, small
 // pointwise glue, token counting-sort + segmented row sum (option-table gradient), and the
-// fused clamp + Adam update.  All are plain coalesced float4 / wave-per-row kernels.
+// fused clamp + Adam update (with its opt-in global-norm clip and weight decay: rules GC1-GC3, WD1 there).  All are plain coalesced
+// float4 / wave-per-row kernels.
 #include <stdlib.h>
+
+#include <algorithm>
 
 #include "common.h"
 
@@ -327,9 +330,23 @@ segment_rowsum_kernel(const float* __restrict__ X, long ldx, const int* __restri
 // model.lua:96-99 + model_utils/optim_updates.lua:62-91: g <- clamp(gscale*g, +-clip);
 // m <- b1 m + (1-b1) g ; v <- b2 v + (1-b2) g^2 ; w <- w - step * m / (sqrt(v) + eps)
 // (eps is added to the UNcorrected sqrt(v); step = lr*sqrt(1-b2^t)/(1-b1^t) from the host.)
-__global__ void clamp_adam_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m,
-                                  float* __restrict__ v, long n, float gscale, float clip, float b1, float b2,
-                                  float eps, float step) {
+//
+// Global-norm clip c >= 0 (VD_GRAD_CLIP_NORM) and decoupled weight decay lambda >= 0 (VD_WEIGHT_DECAY); neither is in the reference:
+//   GC1 the norm is || gscale G ||_2 over the whole flat gradient, after any all-reduce; the scale is c / norm if c > 0 and the norm is
+//       finite and > c, otherwise 1: a non-finite norm never turns finite gradients into NaN.
+//   GC2 each element then goes through clamp(gscale scale g, +-clip) and Adam as above; dW keeps the clamped value.
+//   GC3 the norm is computed on the caller's stream with no atomic and no host read, in a fixed order, so two runs give the same bits:
+//       grad_sqnorm_partial_kernel leaves one partial sum per workgroup (at most VD_NORM_BLOCKS), clip_scale_kernel -- ONE workgroup --
+//       adds them and writes the scale, which the update kernel reads from device memory.
+//   WD1 w <- w - step m / (sqrt(v) + eps) - lr lambda w_old, lr before this step's decay, on every element of the flat vector.
+//       lambda = 0 and c = 0 together are clamp_adam_kernel with its arguments.
+template <bool KNOBS>
+__device__ __forceinline__ void clamp_adam_body(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                long n, float gscale, float clip, float b1, float b2, float eps, float step,
+                                                const float* __restrict__ scale_dev, float decay) {
+  if constexpr (KNOBS) {
+    if (scale_dev) gscale *= scale_dev[0];
+  }
   const long i4 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i4 + 3 < n) {
     float4 W = *reinterpret_cast<float4*>(w + i4), G = *reinterpret_cast<float4*>(g + i4);
@@ -345,7 +362,12 @@ __global__ void clamp_adam_kernel(float* __restrict__ w, float* __restrict__ g, 
       Gp[k] = gg;
       Mp[k] = b1 * Mp[k] + (1.f - b1) * gg;
       Vp[k] = b2 * Vp[k] + (1.f - b2) * gg * gg;
-      Wp[k] -= step * Mp[k] / (sqrtf(Vp[k]) + eps);
+      if constexpr (KNOBS) {
+        const float w0 = Wp[k];
+        Wp[k] = w0 - step * Mp[k] / (sqrtf(Vp[k]) + eps) - decay * w0;
+      } else {
+        Wp[k] -= step * Mp[k] / (sqrtf(Vp[k]) + eps);
+      }
     }
     *reinterpret_cast<float4*>(w + i4) = W;
     *reinterpret_cast<float4*>(g + i4) = G;
@@ -358,8 +380,70 @@ __global__ void clamp_adam_kernel(float* __restrict__ w, float* __restrict__ g, 
       g[i] = gg;
       m[i] = b1 * m[i] + (1.f - b1) * gg;
       v[i] = b2 * v[i] + (1.f - b2) * gg * gg;
-      w[i] -= step * m[i] / (sqrtf(v[i]) + eps);
+      if constexpr (KNOBS) {
+        const float w0 = w[i];
+        w[i] = w0 - step * m[i] / (sqrtf(v[i]) + eps) - decay * w0;
+      } else {
+        w[i] -= step * m[i] / (sqrtf(v[i]) + eps);
+      }
     }
+  }
+}
+__global__ void clamp_adam_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m,
+                                  float* __restrict__ v, long n, float gscale, float clip, float b1, float b2,
+                                  float eps, float step) {
+  clamp_adam_body<false>(w, g, m, v, n, gscale, clip, b1, b2, eps, step, nullptr, 0.f);
+}
+// scale_dev: the scale of GC1 (clip_scale_kernel's out[0]) or null for 1; decay = lr * lambda
+__global__ void clip_decay_adam_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m,
+                                       float* __restrict__ v, long n, float gscale, float clip, float b1, float b2,
+                                       float eps, float step, const float* __restrict__ scale_dev, float decay) {
+  clamp_adam_body<true>(w, g, m, v, n, gscale, clip, b1, b2, eps, step, scale_dev, decay);
+}
+
+// partial[b] = the sum of (gscale g[i])^2 over workgroup b's share of g [n] (16-byte aligned).  Thread t of the grid takes the float4s
+// t, t + T, t + 2T, ... (T = threads of the grid) into four running sums, one per component -- about 14 additions each at the full
+// model's 14 M elements on VD_NORM_BLOCKS workgroups -- which are added pairwise, reduced over the wave by the xor butterfly of
+// wave_sum and over the four waves in a fixed order; the n % 4 tail elements go to the first threads of workgroup 0.
+#define VD_NORM_BLOCKS 1024
+__global__ void __launch_bounds__(256)
+grad_sqnorm_partial_kernel(const float* __restrict__ g, long n, float gscale, float* __restrict__ partial) {
+  __shared__ float red[4];
+  const int tid = threadIdx.x;
+  const long n4 = n >> 2;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (long i = (long)blockIdx.x * 256 + tid; i < n4; i += (long)gridDim.x * 256) {
+    const float4 G = *reinterpret_cast<const float4*>(g + i * 4);
+    const float x = G.x * gscale, y = G.y * gscale, z = G.z * gscale, u = G.w * gscale;
+    acc.x += x * x;
+    acc.y += y * y;
+    acc.z += z * z;
+    acc.w += u * u;
+  }
+  float a = (acc.x + acc.y) + (acc.z + acc.w);
+  if (blockIdx.x == 0 && tid < (int)(n & 3)) {
+    const float x = g[n4 * 4 + tid] * gscale;
+    a += x * x;
+  }
+  a = wave_sum(a);
+  if ((tid & 63) == 0) red[tid >> 6] = a;
+  __syncthreads();
+  if (tid == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+// one workgroup: out[0] = the scale of GC1, out[1] = the norm, from P <= VD_NORM_BLOCKS partial sums (thread t adds partials t, t + 256, ...)
+__global__ void __launch_bounds__(256)
+clip_scale_kernel(const float* __restrict__ partial, int P, float c, float* __restrict__ out) {
+  __shared__ float red[4];
+  const int tid = threadIdx.x;
+  float a = 0.f;
+  for (int i = tid; i < P; i += 256) a += partial[i];
+  a = wave_sum(a);
+  if ((tid & 63) == 0) red[tid >> 6] = a;
+  __syncthreads();
+  if (tid == 0) {
+    const float norm = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
+    out[0] = (c > 0.f && norm > c && norm <= 3.402823466e+38f) ? c / norm : 1.f;   // NaN fails both comparisons, inf the second
+    out[1] = norm;
   }
 }
 
@@ -517,6 +601,31 @@ int vd_clamp_adam(float* w, float* g, float* m, float* v, int64_t n, float gscal
 }
 
 }  // extern "C"
+
+// internal (rt_core.h): the scale of a global-norm clip at c (GC1, GC3) into work[0] and the norm into work[1]; work holds
+// vd_clip_work_floats() floats (the partial sums behind the two results).  g is 16-byte aligned.
+int64_t vd_clip_work_floats() { return 4 + VD_NORM_BLOCKS; }
+int vd_grad_clip_scale_p(const float* g, int64_t n, float gscale, float c, float* work, hipStream_t stream) {
+  VD_CHECK_ARG(g && work && n >= 0 && c >= 0.f && ((uintptr_t)g & 15) == 0 && ((uintptr_t)work & 3) == 0, "vd_grad_clip_scale_p: bad args");
+  const int P = (int)std::max<long>(1, std::min<long>(((n >> 2) + 255) / 256, VD_NORM_BLOCKS));
+  hipLaunchKernelGGL(grad_sqnorm_partial_kernel, dim3(P), dim3(256), 0, stream, g, (long)n, gscale, work + 4);
+  VD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(clip_scale_kernel, dim3(1), dim3(256), 0, stream, work + 4, P, c, work);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+// internal (rt_core.h): vd_clamp_adam with the gradient scaled by gscale * scale_dev[0] (scale_dev = work of vd_grad_clip_scale_p, or null
+// for 1) and the decoupled decay w -= decay * w_old (WD1; decay = lr * lambda)
+int vd_clip_decay_adam_p(float* w, float* g, float* m, float* v, int64_t n, float gscale, float clip, float beta1, float beta2, float eps,
+                         float step, const float* scale_dev, float decay, hipStream_t stream) {
+  VD_CHECK_ARG(w && g && m && v && n >= 0 && decay >= 0.f, "vd_clip_decay_adam_p: bad args");
+  VD_CHECK_ARG((((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "vd_clip_decay_adam_p: buffers must be 16-byte aligned");
+  if (n == 0) return VD_OK;
+  hipLaunchKernelGGL(clip_decay_adam_kernel, grid1d((n + 3) / 4, 256), dim3(256), 0, stream, w, g, m, v, (long)n, gscale, clip, beta1, beta2,
+                     eps, step, scale_dev, decay);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
 
 // internal (common.h): the same segmented row sum over bf16 rows (the compact da of a bf16 pass)
 int vd_segment_rowsum_acc_bf16(const vd_bf16_bits* X16, int64_t ldx, const int32_t* tok, const int32_t* perm, int64_t n, int ncol,

@@ -113,6 +113,22 @@ int vd_disc_rollout_pick_p(const float* scores, int O, const int32_t* opt_tok, i
 // history row r of every dialog (the new tokens CH4 kept), right-aligned with zeros in front.  1 <= r < R, 1 <= Wn <= W.
 int vd_rollout_concat_window_p(const int32_t* hist_tok, int dialogs, int R, int r, int W, int Wn, int32_t* win, hipStream_t stream);
 
+// loss.hip: the two training heads on targets smoothed by `smooth` in [0, 1) (VD_LABEL_SMOOTHING; LS1 - LS4 there): vd_score_ce /
+// vd_logsoftmax_nll with t = (1 - smooth) onehot + smooth / K in the place of onehot (K = O options / V valid columns).  smooth = 0 IS the
+// C-ABI entry point: the same kernel with the same arguments.  The smoothed vd_score_ce_p needs gt and loss_rows.
+int vd_score_ce_p(const float* optH, const float* enc, const int32_t* gt, float* scores, float* loss_rows, float* dOptH, float* dEnc, int N,
+                  int O, int H, float gscale, float smooth, hipStream_t stream);
+int vd_logsoftmax_nll_p(float* logits, int64_t ld, int64_t rows, int V, const int32_t* tok_in, const int32_t* target, float* loss_rows,
+                        int write_grad, float smooth, hipStream_t stream);
+// elementwise.hip: the update with a global-norm clip and decoupled weight decay (VD_GRAD_CLIP_NORM / VD_WEIGHT_DECAY; GC1 - GC3, WD1
+// there).  vd_grad_clip_scale_p: work[0] = c / || gscale g ||_2 where that norm is finite and > c > 0, else 1; work[1] = the norm; two
+// launches on `stream`, no atomic, no host read, the same bits on every run; work holds vd_clip_work_floats() floats.
+// vd_clip_decay_adam_p: vd_clamp_adam on gscale * scale_dev[0] * g (scale_dev null: 1), then w -= decay * w_old.
+int64_t vd_clip_work_floats();
+int vd_grad_clip_scale_p(const float* g, int64_t n, float gscale, float c, float* work, hipStream_t stream);
+int vd_clip_decay_adam_p(float* w, float* g, float* m, float* v, int64_t n, float gscale, float clip, float beta1, float beta2, float eps,
+                         float step, const float* scale_dev, float decay, hipStream_t stream);
+
 #define VD_TRY(expr)                  \
   do {                                \
     const int rc__ = (expr);          \

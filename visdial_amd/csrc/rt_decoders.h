@@ -177,7 +177,9 @@ struct Disc : Decoder {
       VD_TRY(ws_get(m, "crit.d_enc", (size_t)N * H, &d_enc));
       if (dedup) VD_TRY(ws_get(m, "crit.d_optH_full", (size_t)NOfull * H, &d_optH_full));
     }
-    VD_TRY(vd_score_ce(optH, enc_out, b.gt, scores, loss_rows, dedup ? d_optH_full : d_optH, d_enc, N, O, (int)H, 1.0f / N, s));
+    // a training step's targets are smoothed by VD_LABEL_SMOOTHING (loss.hip LS1, LS3); 0 is vd_score_ce itself
+    VD_TRY(vd_score_ce_p(optH, enc_out, b.gt, scores, loss_rows, dedup ? d_optH_full : d_optH, d_enc, N, O, (int)H, 1.0f / N,
+                         only_forward ? 0.f : (float)m->sw.label_smoothing, s));
     if (dedup && !only_forward) {   // the gradients of the copies of a distinct row add up
       VD_TRY(vd_memset(d_optH, 0, (long)NO * H * 4, s));
       VD_TRY(vd_embed_scatter_acc(d_optH, b.opt_uid, nullptr, d_optH_full, NOfull, (int)H, 1.f, s));
@@ -473,7 +475,9 @@ struct Gen : Decoder {
     m->prof_hist = false;
     VD_HIP(hipEventRecord(m->ev_prof[4], s));          // family 3 of a gen pair: vocabulary projection + criterion + their gradients
     VD_TRY(vd_gemm_nt(h, H, Wp(m, "vocab.W"), H, Wp(m, "vocab.b"), logits, Vp, (int)rows, (int)V, (int)H, VD_ACT_NONE, 0, s));
-    VD_TRY(vd_logsoftmax_nll(logits, Vp, rows, (int)V, b.ain.tok, b.aout.tok, loss_rows, only_forward ? 0 : 1, s));   // model.lua:309-311
+    // model.lua:309-311; a training step's targets are smoothed by VD_LABEL_SMOOTHING (loss.hip LS2, LS3); 0 is vd_logsoftmax_nll itself
+    VD_TRY(vd_logsoftmax_nll_p(logits, Vp, rows, (int)V, b.ain.tok, b.aout.tok, loss_rows, only_forward ? 0 : 1,
+                               only_forward ? 0.f : (float)m->sw.label_smoothing, s));
     VD_TRY(stage_loss(m, loss_rows, rows, true, s));
     if (only_forward) return VD_OK;
     float* dh;                                                                      // logits now hold d loss / d logits

@@ -10,6 +10,8 @@
 //    VD_BEAM_DIVERSITY in [0, FLT_MAX] (lambda is applied in fp32), VD_BEAM_LENGTH_PENALTY in [0, DBL_MAX].  errno is not looked at.
 //  - the sampling and beam variables and VD_BEAM_ROLLOUT are not read for decoder disc, VD_RETRIEVE_ROLLOUT not for decoder gen: garbage in
 //    them is ignored there.  VD_ROLLOUT_ENCODER and VD_ROLLOUT_CONCAT_END are validated for every model.
+//  - the training knobs are read for both decoders: VD_LABEL_SMOOTHING in [0, 1), VD_GRAD_CLIP_NORM and VD_WEIGHT_DECAY in [0, FLT_MAX]
+//    (both are applied in fp32); 0 or unset = off.
 #pragma once
 #include <errno.h>
 #include <float.h>
@@ -41,6 +43,12 @@ struct Switches {                     // (decoder the variable is read for) what
   // VD_ROLLOUT_CONCAT_END (both): the <END> id; a rollout then writes CONCATENATED history rows (beam.hip CH1-CH6: row r + 1 = row r, <END>, the
   // question, the answer) instead of per-round rows; 0 = off.  vd_model_create refuses a value above vocabSize (it knows V; this header does not)
   int rollout_concat_end = 0;
+  // the training knobs (both): vd_model_forward_backward(m, 0) trains on targets smoothed by label_smoothing (loss.hip LS1-LS4);
+  // vd_model_update clips the flat gradient to the global norm grad_clip_norm and decays the weights by weight_decay (elementwise.hip
+  // GC1-GC3, WD1); 0 = off
+  double label_smoothing = 0.0;       // VD_LABEL_SMOOTHING
+  double grad_clip_norm = 0.0;        // VD_GRAD_CLIP_NORM
+  double weight_decay = 0.0;          // VD_WEIGHT_DECAY
 };
 
 // The typed readers.  An unset variable leaves *out alone; a refusal is "vd_model_create: NAME = 'text' <must>".
@@ -127,6 +135,12 @@ inline int parse_switches(const char* encoder, const char* decoder, int lstmBf16
     return vd_set_error("vd_model_create: VD_ROLLOUT_CONCAT_END = %d with encoder '%s': its history is one row per round (beam.hip R2 / E4), not "
                         "the running concatenation of the dialog; the concatenation rule (CH1-CH6) is for lf-ques-hist, lf-ques-im-hist and "
                         "lf-att-ques-im-hist", sw.rollout_concat_end, encoder), -1;
+  // all three are applied in fp32: the largest float below 1 closes [0, 1)
+  const char* real0 = "must be a finite real >= 0 (0 = off)";
+  if (!(read_real("VD_LABEL_SMOOTHING", 0.0, false, 1.0 - (double)FLT_EPSILON / 2, "must be a real in [0, 1) (0 = off)", &sw.label_smoothing) &&
+        read_real("VD_GRAD_CLIP_NORM", 0.0, false, (double)FLT_MAX, real0, &sw.grad_clip_norm) &&
+        read_real("VD_WEIGHT_DECAY", 0.0, false, (double)FLT_MAX, real0, &sw.weight_decay)))
+    return -1;
   *out = sw;
   return 0;
 }

@@ -783,7 +783,18 @@ int vd_model_update(vd_model* m, float gscale) {
   m->ocache.flush();
   const double t = m->adam_t;
   const float step = (float)(m->lr * sqrt(1.0 - pow(0.999, t)) / (1.0 - pow(0.9, t)));
-  VD_TRY(vd_clamp_adam(m->W, m->G, m->M, m->V, m->numel, gscale, 5.0f, 0.9f, 0.999f, 1e-8f, step, m->s_main));
+  const float clip_norm = (float)m->sw.grad_clip_norm, decay = (float)(m->lr * m->sw.weight_decay);   // lr before this step's decay (WD1)
+  if (clip_norm > 0.f || decay > 0.f) {   // decided on the fp32 values the kernels see: a lambda whose lr * lambda rounds to 0 is off
+    // VD_GRAD_CLIP_NORM / VD_WEIGHT_DECAY (elementwise.hip GC1-GC3, WD1): the norm of gscale * G and its scale stay on the device
+    float* work = nullptr;
+    if (clip_norm > 0.f) {
+      VD_TRY(ws_get(m, "upd.clip_work", (size_t)vd_clip_work_floats(), &work));
+      VD_TRY(vd_grad_clip_scale_p(m->G, m->numel, gscale, clip_norm, work, m->s_main));
+    }
+    VD_TRY(vd_clip_decay_adam_p(m->W, m->G, m->M, m->V, m->numel, gscale, 5.0f, 0.9f, 0.999f, 1e-8f, step, work, decay, m->s_main));
+  } else {
+    VD_TRY(vd_clamp_adam(m->W, m->G, m->M, m->V, m->numel, gscale, 5.0f, 0.9f, 0.999f, 1e-8f, step, m->s_main));
+  }
   VD_HIP(hipEventRecord(m->ev_updated, m->s_main));
   m->updated_recorded = true;
   if (m->lr > m->p.minLRate) m->lr *= m->p.lrDecayRate;

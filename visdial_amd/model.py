@@ -42,6 +42,21 @@ class Wrapper(object):
         return self._m.encoder if i == 1 else self._m.decoder
 
 
+def refuse_training_knobs(params):
+    """a training call of the operator-level host with a non-zero knob of the model-level runtime is refused by name: the smoothed heads,
+    the norm and the decayed update are internal to the library (its C symbol set is frozen).  Ranking or generating with a checkpoint
+    whose params carry the knobs is untouched: they change no forward value."""
+    for key in ('labelSmoothing', 'gradClipNorm', 'weightDecay'):
+        v = params.get(key)
+        try:
+            off = v is None or float(v) == 0.0
+        except (TypeError, ValueError):
+            off = False
+        if not off:
+            raise ValueError("%s = %r: label smoothing, the global-norm clip and weight decay run in the model-level runtime only: use "
+                             "-host native (visdial_amd.native.NativeModel); the operator-level host trains with %s = 0" % (key, v, key))
+
+
 class Model(SplitEval):
     def __init__(self, params, dist_group=None):
         self.params = params
@@ -243,6 +258,7 @@ class Model(SplitEval):
 
     def update(self):
         """[all-reduce] -> clamp(-5, 5) -> adam -> lr decay (model.lua:96-105)."""
+        refuse_training_knobs(self.params)
         gscale = 1.0
         if self._dp_active():
             from .parallel import reduce_gradients
@@ -274,6 +290,7 @@ class Model(SplitEval):
         device and returns it (everything is enqueued when forwardBackward returns)."""
         inputs, dec_in = prepared if prepared is not None else self.prepare_inputs(batch)
         if not onlyForward and not encOutOnly:
+            refuse_training_knobs(self.params)
             self._flush_option_cache()         # gradients are about to move the weights
         if 'option_rows' in dec_in and 'options' not in dec_in and (not onlyForward or not self._option_cache_active()):
             # prepared for cached evaluation, stepped otherwise: the uncached path needs every distinct row on the device

@@ -46,6 +46,13 @@ generateAnswers checks what it is asked for against it.  rolloutConcatEnd (VD_RO
 concatenated history (split_eval.py CH1-CH6): evaluate.py -rolloutHistory concat fills it from the loader, and `retrieve_rollout_batch`
 refuses a device rollout whose params rolloutHistory does not agree with what the model was created with."""
 
+TRAIN_SWITCHES = (
+    # rows of the same type, chained behind SWITCHES: the knobs of a training step (loss.hip LS1-LS4; elementwise.hip GC1-GC3, WD1)
+    ('labelSmoothing', 'VD_LABEL_SMOOTHING', _text, float, 0.0, None),                    # vd_model_forward_backward(m, 0): soft targets
+    ('gradClipNorm', 'VD_GRAD_CLIP_NORM', _text, float, 0.0, None),                       # vd_model_update: global-norm clip
+    ('weightDecay', 'VD_WEIGHT_DECAY', _text, float, 0.0, None),                          # vd_model_update: decoupled weight decay
+)
+
 
 class _DevArray(object):
     """a raw device pointer as something torch.as_tensor understands (plumbing for torch.distributed only)"""
@@ -102,7 +109,7 @@ class NativeModel(SplitEval):
         self.params = p
         h = C.c_void_p()
         import os
-        switches = {var: text(p.get(key)) for key, var, text, _, _, _ in SWITCHES}
+        switches = {var: text(p.get(key)) for key, var, text, _, _, _ in SWITCHES + TRAIN_SWITCHES}
 
         def put(values):
             for k, v in values.items():
@@ -117,7 +124,7 @@ class NativeModel(SplitEval):
         finally:
             put(prev)
         self._knobs = {key: default if p.get(key) is None or decoder not in (None, p['decoder']) else conv(p[key])
-                       for key, _, _, conv, default, decoder in SWITCHES}
+                       for key, _, _, conv, default, decoder in SWITCHES + TRAIN_SWITCHES}
         self.h = h
         lib = _lib.load()
         self.tensors = []

@@ -1,6 +1,7 @@
 """Command-line options: same flag names and defaults as the reference's opts.lua:5-40, plus the
 derived capability flags it infers from the encoder NAME (opts.lua:54-67)."""
 import argparse
+import ctypes
 import time
 
 # (flag, default, help) -- opts.lua:5-40
@@ -78,7 +79,22 @@ def parse(argv=None):
                          "'declaration', or a JSON file: {\"order\": [names]} or the output of lua/dump_param_order.lua under Torch7")
     ap.add_argument('-synthetic', '--synthetic', type=int, default=0,
                     help='1 = allow resuming (-loadPath) on synthetic batches when no dataset files exist')
+    # training knobs the reference does not have (-host native; csrc/loss.hip LS1-LS4, csrc/elementwise.hip GC1-GC3, WD1); 0 = off
+    ap.add_argument('-labelSmoothing', '--labelSmoothing', type=float, default=0.0,
+                    help='(training only, -host native) label smoothing eps in [0, 1): a training target is (1 - eps) onehot + eps / K over the K options (disc) or '
+                         'vocabulary words (gen)')
+    ap.add_argument('-gradClipNorm', '--gradClipNorm', type=float, default=0.0,
+                    help='(training only, -host native) clip the whole gradient to this L2 norm in front of the element clamp at +-5 (a finite real >= 0)')
+    ap.add_argument('-weightDecay', '--weightDecay', type=float, default=0.0,
+                    help='(training only, -host native) decoupled weight decay lambda: w -= lr * lambda * w beside the Adam step (a finite real >= 0)')
     opt = vars(ap.parse_args(argv))
+    # refused by name before any model exists (the library refuses the same values: csrc/rt_switches.h)
+    # (eps is applied in fp32, as in the library: a value that rounds to 1.0f is not below 1)
+    if not 0.0 <= ctypes.c_float(opt['labelSmoothing']).value < 1.0:
+        ap.error('-labelSmoothing %r must be a real in [0, 1) (0 = off)' % (opt['labelSmoothing'],))
+    for k in ('gradClipNorm', 'weightDecay'):
+        if not 0.0 <= opt[k] < float('inf'):
+            ap.error('-%s %r must be a finite real >= 0 (0 = off)' % (k, opt[k]))
     opt.update(maxQuesCount=10, maxQuesLen=20, maxAnsLen=20, numOptions=100)
     if opt['savePath'] == 'checkpoints/':
         t = time.localtime()
