@@ -82,6 +82,19 @@ struct VdZeroSet {
 };
 int vd_zero_inactive_multi(const VdZeroSet& z, const int32_t* nact_dev, int T, int N, hipStream_t stream);
 
+// C_p [M x N] += A_p^T * B_p over the live rows of length-sorted steps, up to VD_LIVE_MAXP products in ONE launch (gemm_ops.hip;
+// wgrad_plan.h has the segment tables and the work list, all device arrays here; M, N multiples of 128, 16-byte rows)
+constexpr int VD_LIVE_MAXP = 8;   // (two stacks of two layers: 2 x (two dWh + the layer-2 dWx) = 6)
+struct VdLiveProduct {
+  const float *A, *B;      // B from the row that pairs with row 0 of A
+  float* C;
+  const int32_t* segs;     // [segments + sentinel][4]
+  long lda, ldb, ldc;
+  int M, N;
+};
+int vd_gemm_tn_live_grouped(const VdLiveProduct* prod, int nprod, const int32_t* items, const int32_t* chunk_start, int chunks,
+                            hipStream_t stream);
+
 typedef unsigned short vd_bf16_bits;
 // ---- compact bf16 state of the option recurrence (model-level runtime, lstmBf16 = 1: BASELINE configs[4]) --------------------
 // The saved gates / da live ONLY as bf16 [T x N x 4H], the projection table as bf16 rows, h as bf16 (+ the last step's fp32 h):

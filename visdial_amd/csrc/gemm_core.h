@@ -876,6 +876,181 @@ static int launch_gemm_glds(int M, int N, int K, int splits, const float* A, lon
 }
 
 // ---------------------------------------------------------------------------
+// Live-prefix contractions, grouped: the k-major LDS-DMA pipeline above (same tiles, same fragment reads, same MFMA order, same
+// barrier and vmcnt scheme) over the K rows a SEGMENT TABLE names instead of a dense range -- the live rows of the steps of a
+// length-sorted sequence set (wgrad_plan.h: segments, k-steps, work list).  Up to MAXP products C_p += A_p^T * B_p in one launch; a
+// workgroup takes its chunk of the work list and runs its items one after the other, each ending in float atomics into its product's C.
+//   * the walker advances through the table with wave-uniform arithmetic, one entry load per segment (no per-row index); a ring holds
+//     the k-steps of tiles kt .. kt + 3 because a tile is requested two (B) or three (A) iterations before it is read
+//   * a SHORT k-step (cnt < 16 rows left in its step): the DMA lanes of rows >= cnt re-read row cnt - 1, so nothing outside the step
+//     is touched, and the A fragments of those k are zeroed on their way to the MFMA
+// ---------------------------------------------------------------------------
+struct LiveProduct {
+  const float* A;      // [rows x lda]
+  const float* B;      // [rows x ldb], walked with A's row index
+  float* C;            // [M x ldc]
+  const int4* segs;    // {first row, k-steps, rows of the last k-step, k-steps before}, closed by the sentinel
+  int lda, ldb, ldc, tiles_n;
+};
+template <int MAXP>
+struct LiveGroupArgs {
+  LiveProduct p[MAXP];
+  const int4* items;         // {product << 24 | tile, segment, k-step inside it, k-steps}
+  const int* chunk_start;    // [grid + 1]
+};
+
+// a table the launch only reads, written before it: wave-uniform reads become scalar loads
+typedef int vd_i32x4 __attribute__((ext_vector_type(4)));
+typedef const vd_i32x4 __attribute__((address_space(4))) vd_const_i32x4;
+__device__ __forceinline__ const vd_const_i32x4* vd_as_const(const void* p) { return (const vd_const_i32x4*)(uintptr_t)p; }
+
+template <class Cfg, class Epi>
+__device__ __forceinline__ void gemm_block_glds_live(int row_base, int col_base, const float* A, long lda, const float* B, long ldb,
+                                                     const int4* __restrict__ segs, int seg, int j, int nk, const Epi& epi, float* smem) {
+  constexpr int WM = Cfg::WM, NT = Cfg::NT, BM = Cfg::BM, BN = Cfg::BN;
+  constexpr int NIA = (BM / 16) / WM, NIB = (BN / 16) / WM;
+  constexpr int ABUF = BM * 16, BBUF = BN * 16;
+  static_assert(Cfg::WK == 1 && Cfg::KW == 16 && BM == 128 && BN == 128 && Cfg::BF16 == 0, "k-major fp32 tiles of 16 x 128");
+  static_assert((3 * ABUF + 2 * BBUF) * 4 <= Cfg::LDS_BYTES && (3 * ABUF + 3 * BBUF) * 4 > Cfg::LDS_BYTES,
+                "three A buffers and two B buffers: the ring below is written for that request distance");
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int wm = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hi = lane >> 5, l31 = lane & 31;
+
+  f32x16 acc[NT];
+#pragma unroll
+  for (int jj = 0; jj < NT; ++jj)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[jj][r] = 0.f;
+
+  // the k-steps from (seg, j) on, as row * 32 + cnt.  The table is read through the constant address space: scalar loads the compiler
+  // counts itself (lgkmcnt), outside the vmcnt bookkeeping of the DMA requests below
+  const vd_const_i32x4* const ctab = vd_as_const(segs);
+  vd_i32x4 sg = ctab[seg];
+  auto next = [&]() {
+    const int d = ((sg.x + j * 16) << 5) | (j + 1 == sg.y ? sg.z : 16);
+    if (++j == sg.y) {
+      sg = ctab[++seg];
+      j = 0;
+    }
+    return d;
+  };
+
+  unsigned voffa[NIA], voffb[NIB];
+#pragma unroll
+  for (int i = 0; i < NIA; ++i) voffa[i] = (unsigned)((((long)(i * WM + wm) * 2 + hi) * lda + row_base + l31 * 4) * 4);
+#pragma unroll
+  for (int i = 0; i < NIB; ++i) voffb[i] = (unsigned)((((long)(i * WM + wm) * 2 + hi) * ldb + col_base + l31 * 4) * 4);
+  float* const sA = smem;
+  float* const sB = smem + 3 * ABUF;
+  const unsigned ldsA = (unsigned)(uintptr_t)sA, ldsB = (unsigned)(uintptr_t)sB;
+  // rows >= cnt of a short k-step re-read row cnt - 1
+  auto back = [&](int i, int cnt, long ld) { return (unsigned)(max((i * WM + wm) * 2 + hi - (cnt - 1), 0) * ld * 4); };
+  auto issue_a = [&](int d, int buf) {
+    const float* ak = A + (long)(d >> 5) * lda;
+    const int cnt = d & 31;
+    if (cnt == 16) {
+#pragma unroll
+      for (int i = 0; i < NIA; ++i) glds16(voffa[i], ak, ldsA + buf * (ABUF * 4) + (i * WM + wm) * 1024);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NIA; ++i) glds16(voffa[i] - back(i, cnt, lda), ak, ldsA + buf * (ABUF * 4) + (i * WM + wm) * 1024);
+    }
+  };
+  auto issue_b = [&](int d, int buf) {
+    const float* bk = B + (long)(d >> 5) * ldb;
+    const int cnt = d & 31;
+    if (cnt == 16) {
+#pragma unroll
+      for (int i = 0; i < NIB; ++i) glds16(voffb[i], bk, ldsB + buf * (BBUF * 4) + (i * WM + wm) * 1024);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NIB; ++i) glds16(voffb[i] - back(i, cnt, ldb), bk, ldsB + buf * (BBUF * 4) + (i * WM + wm) * 1024);
+    }
+  };
+  struct Frag {
+    float a[4];
+    float b[NT][4];
+  };
+  auto read_frags = [&](int bufa, int bufb, int half, int d, Frag& f) {
+    const float* sa = sA + bufa * ABUF + (half * 8 + hi) * BM + wm * 32 + l31;
+    const float* sb = sB + bufb * BBUF + (half * 8 + hi) * BN + l31;
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+      f.a[s4] = sa[s4 * 2 * BM];
+#pragma unroll
+      for (int jj = 0; jj < NT; ++jj) f.b[jj][s4] = sb[s4 * 2 * BN + jj * 32];
+    }
+    const int cnt = d & 31;
+    if (cnt < 16) {
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4)
+        if (half * 8 + hi + s4 * 2 >= cnt) f.a[s4] = 0.f;
+    }
+  };
+  auto mfma16 = [&](const Frag& f) {
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+      for (int jj = 0; jj < NT; ++jj) acc[jj] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[s4], f.b[jj][s4], acc[jj], 0, 0, 0);
+  };
+  auto wait_vm = [&](int n) {
+    switch (n) {
+      case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+      case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+      case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+      case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+      case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+      case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+      case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+      default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    }
+  };
+
+  if (nk > 0) {
+    Frag f0, f1;
+    int d0 = next(), d1 = next(), d2 = next();   // tiles kt, kt + 1, kt + 2 (beyond nk: never requested)
+    // request order B, then A, as in gemm_block_glds: the operand with fewer buffers is always the older request
+    issue_b(d0, 0);
+    issue_a(d0, 0);
+    if (1 < nk) {
+      issue_b(d1, 1);
+      issue_a(d1, 1);
+    }
+    if (2 < nk) issue_a(d2, 2);
+    wait_vm(NIA * (min(nk, 3) - 1) + NIB * (min(nk, 2) - 1));
+    asm volatile("s_barrier" ::: "memory");
+    read_frags(0, 0, 0, d0, f0);
+    int ca = 0, cb = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+      const int na = (ca + 1 == 3) ? 0 : ca + 1, nb = cb ^ 1;
+      read_frags(ca, cb, 1, d0, f1);
+      mfma16(f0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (kt + 3 <= nk) {
+        static_assert(NIA == 2, "steady-state vmcnt immediate");
+        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");   // NIA * (3 - 2) + NIB * (2 - 2)
+      } else {
+        wait_vm(NIA * max(0, min(kt + 2, nk - 1) - (kt + 1)) + NIB * max(0, min(kt + 1, nk - 1) - (kt + 1)));
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      const int d3 = next();
+      if (kt + 2 < nk) issue_b(d2, cb);
+      if (kt + 3 < nk) issue_a(d3, ca);
+      if (kt + 1 < nk) read_frags(na, nb, 0, d1, f0);
+      mfma16(f1);
+      ca = na;
+      cb = nb;
+      d0 = d1;
+      d1 = d2;
+      d2 = d3;
+    }
+  }
+  epi(acc, row_base + wm * 32, col_base, lane, 1 << 30, 1 << 30, smem + wm * 1024);
+}
+
+// ---------------------------------------------------------------------------
 // Grouped launch: up to MAXP independent problems (same tile config and functor types, different
 // pointers / dims) in ONE launch -- used to advance several recurrences by one tick per launch.
 // ---------------------------------------------------------------------------
@@ -982,6 +1157,37 @@ struct EpiAtomic {
     }
   }
 };
+
+// the live-prefix contractions of one work list (gemm_block_glds_live): workgroup w runs the items of chunk w, C_p += with float atomics
+template <class Cfg, int MAXP>
+__global__ void __launch_bounds__(Cfg::THREADS, Cfg::MINW)
+gemm_f32_live_grouped_kernel(LiveGroupArgs<MAXP> g) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
+  const int i0 = g.chunk_start[wg], i1 = g.chunk_start[wg + 1];
+  for (int it = i0; it < i1; ++it) {
+    const vd_i32x4 item = vd_as_const(g.items)[it];
+    const LiveProduct& P = g.p[item.x >> 24];
+    const int tile = item.x & 0xffffff;
+    const EpiAtomic<Cfg::NT> e{P.C, (long)P.ldc};
+    gemm_block_glds_live<Cfg>((tile / P.tiles_n) * Cfg::BM, (tile % P.tiles_n) * Cfg::BN, P.A, P.lda, P.B, P.ldb, P.segs, item.y, item.z,
+                              item.w, e, smem);
+  }
+}
+
+template <class Cfg, int MAXP>
+static int launch_live_grouped(const LiveGroupArgs<MAXP>& g, int chunks, hipStream_t stream) {
+  if (chunks <= 0) return VD_OK;
+  auto kern = gemm_f32_live_grouped_kernel<Cfg, MAXP>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    VD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(kern, dim3(chunks), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, g);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
 
 // host-side launcher
 template <class Cfg, class ASrc, class BSrc, class Epi>

@@ -570,6 +570,29 @@ int vd_colsum_acc(const float* X, int64_t ld, int M, int N, float* out, void* st
 
 }  // extern "C"
 
+// internal (common.h): the encoder LSTMs' weight gradients of one backward over their live rows, one launch (gemm_core.h
+// gemm_block_glds_live).  The tile configuration is vd_gemm_tn_acc's k-major one: 41 984 bytes of LDS let a workgroup share a CU with
+// two option-backward workgroups.
+int vd_gemm_tn_live_grouped(const VdLiveProduct* prod, int nprod, const int32_t* items, const int32_t* chunk_start, int chunks,
+                            hipStream_t stream) {
+  using Cfg = GemmCfg<4, 1, 4, 16, 0, 4, 41984>;
+  VD_CHECK_ARG(prod && nprod >= 1 && nprod <= VD_LIVE_MAXP && items && chunk_start && chunks >= 0, "vd_gemm_tn_live_grouped: bad args");
+  LiveGroupArgs<VD_LIVE_MAXP> g{};
+  for (int i = 0; i < nprod; ++i) {
+    const VdLiveProduct& p = prod[i];
+    VD_CHECK_ARG(p.A && p.B && p.C && p.segs && p.M > 0 && p.N > 0 && p.M % Cfg::BM == 0 && p.N % Cfg::BN == 0 && p.lda >= p.M && p.ldb >= p.N &&
+                     16 * p.lda * 4 < (1L << 31) && 16 * p.ldb * 4 < (1L << 31) && p.ldc < (1L << 31) &&
+                     (long)(p.M / Cfg::BM) * (p.N / Cfg::BN) < (1 << 24),
+                 "vd_gemm_tn_live_grouped: product %d: M=%d N=%d", i, p.M, p.N);
+    if (int rc = check_align(p.A, p.lda, "vd_gemm_tn_live_grouped A")) return rc;
+    if (int rc = check_align(p.B, p.ldb, "vd_gemm_tn_live_grouped B")) return rc;
+    g.p[i] = LiveProduct{p.A, p.B, p.C, reinterpret_cast<const int4*>(p.segs), (int)p.lda, (int)p.ldb, (int)p.ldc, p.N / Cfg::BN};
+  }
+  g.items = reinterpret_cast<const int4*>(items);
+  g.chunk_start = chunk_start;
+  return launch_live_grouped<Cfg, VD_LIVE_MAXP>(g, chunks, stream);
+}
+
 // internal (common.h): C[M x N] += A16[K x M]^T * B16[K x N], both operands bf16 rows (the compact h / da of a bf16 pass)
 __global__ void __launch_bounds__(256) bf16_tn_tail_kernel(const vd_bf16_bits* __restrict__ A, const vd_bf16_bits* __restrict__ B, float* __restrict__ C,
                                                            long ldc, int M, int N, int K) {

@@ -45,6 +45,14 @@ static inline bool vd_tn_kmajor_fits(long M, long N, long K) { return M % 128 ==
 constexpr int VD_SPLIT_TN_BM = 256, VD_SPLIT_TN_BN = 128;
 static inline bool vd_tn_split_tiles(long M, long N) { return M % VD_SPLIT_TN_BM == 0 && N % VD_SPLIT_TN_BN == 0; }
 
+// live-row group of an encoder backward (vd_gemm_tn_live_grouped, gemm_ops.hip; rt_core.h wgrad_flush): a product C [M x N] += A^T * B of an
+// encoder LSTM waits for the backward's one grouped launch when its rows are a length-sorted sequence set (the live rows of a step are a
+// prefix of it), M and N are multiples of the 128 x 128 tile and the pass is not bf16.  Everything else keeps vd_gemm_tn_acc /
+// vd_gemm_tn_rows_acc: layer-1 input weights at E = 300, the bf16 pass, the unsorted stacks
+static inline bool vd_wgrad_group_fits(bool sorted_rows, long M, long N, int flags) {
+  return sorted_rows && M % 128 == 0 && N % 128 == 0 && !(flags & VD_FLAG_BF16);
+}
+
 // ---- image attention (attention.hip vd_img_*_p; rt_encoders.h) -----------------------------------------------------------------
 // the dense products of a split9 pass on the exact split, from the materialised dropped image tensor xdrop [rows x H] (rows = N * S2);
 // the runtime materialises xdrop exactly when this holds

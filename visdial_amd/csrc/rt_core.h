@@ -22,6 +22,7 @@
 #include "common.h"
 #include "paths.h"
 #include "rt_switches.h"
+#include "wgrad_plan.h"
 
 static_assert(VD_OK == 0 && VD_ERR_ARG == -1, "rt_switches.h returns the two as literals: it includes no common.h");
 
@@ -160,6 +161,10 @@ struct SeqTok {
   // the pairs with t >= 1 and their previous-step rows (weight gradients contract these only)
   int32_t *act = nullptr, *act1 = nullptr, *prev1 = nullptr;
   int n_act = 0, n_act1 = 0;
+  // the same pairs as segments of whole k-steps (wgrad_plan.h), [0]: the pairs of one step, [1]: (t - 1, t) pairs; host copy + device table
+  std::vector<vdplan::Seg> seg_host[2];
+  int32_t* seg_dev[2] = {nullptr, nullptr};
+  int seg_ksteps[2] = {0, 0};
 };
 
 // Prefix tree of a chunk of candidates (generative retrieval with VD_LHOOD_TREE; built on the host at upload time, runtime.hip): the
@@ -197,6 +202,11 @@ struct BatchSlot {
   bool cached = false;
   uint64_t cache_stamp = 0;
   std::vector<int32_t> miss_keys, opt_host;
+  // work list of the encoder backward's live-row weight-gradient launch (wgrad_flush): built on the first backward over this upload's
+  // sequence sets, kept while the products stay the same (wgrad_sig; an upload of tokens clears it)
+  std::vector<long> wgrad_sig;
+  int32_t *wgrad_items = nullptr, *wgrad_chunk_start = nullptr;
+  int wgrad_chunks = 0;
   hipEvent_t ready = nullptr;  // recorded on the side lane when the upload has landed
   hipEvent_t done = nullptr;   // recorded on the main stream behind the last reader of this slot
   bool used = false;      // a step has read this slot (done is recorded)
@@ -268,6 +278,13 @@ struct OptionCache {
 };
 static constexpr long VD_OPTION_CACHE_FIRST_ROWS = 16384;      // first allocation; doubles from there
 
+// one dense weight-gradient product of a length-sorted encoder LSTM, held back for the backward's grouped launch (wgrad_flush)
+struct WgradProduct {
+  VdLiveProduct p;      // (segs: filled in by the flush)
+  const SeqTok* rows;
+  int t_first;          // 0: x and da of one step; 1: h of step t - 1 with da of step t
+};
+
 struct Encoder;
 struct Decoder;
 
@@ -291,6 +308,11 @@ struct vd_model {
   // lane (runtime.hip).  wg_active: the current backward uses it; wg_used: it holds un-joined work
   hipStream_t s_wg = nullptr;
   bool wg_active = false, wg_used = false;
+  // wgrad_open: SeqLSTM::param_grads appends its eligible products (paths.h vd_wgrad_group_fits) here instead of launching them, and the
+  // encoder backward that opened the group flushes it as one launch (wgrad_flush) -- or, with wgrad_hold set by its caller, leaves the
+  // products here for the caller's flush
+  std::vector<vdrt::WgradProduct> wgrad;
+  bool wgrad_open = false, wgrad_hold = false;
   std::vector<hipEvent_t> ev_pool;
   size_t ev_next = 0;
   hipEvent_t ev_enc_grads = nullptr;  // recorded behind the encoder backward: its gradient tensors are final
@@ -398,6 +420,66 @@ inline int wg_fork(vd_model* m, hipStream_t cur, hipStream_t* out) {
   m->wg_used = true;
   *out = m->s_wg;
   return VD_OK;
+}
+
+// The live-row weight-gradient group of one encoder backward.  Between wgrad_begin and wgrad_flush the length-sorted LSTMs' param_grads
+// hold their eligible products back; the flush contracts them in ONE launch on `s` over the live rows only (the pad pairs hold da = 0:
+// exact zeros leave the sums).  About one round of workgroups (3 per CU), a chunk no shorter than 32 k-steps: every item ends in 64 KB
+// of float atomics.  The work list depends on the batch's lengths and the products' tiles alone: built once per upload into the slot.
+// (384 and 1536 chunks measured the same step time as 768, profiles/enc_wgrad_group.txt.)
+// The group ends with the encoder backward (wgrad_end): flushed there, or, under wgrad_hold, left to the caller's own wgrad_flush -- the
+// discriminative step puts it behind its option recurrence (rt_decoders.h).
+constexpr int VD_WGRAD_CHUNKS = 768, VD_WGRAD_MIN_KSTEPS = 32;
+inline void wgrad_begin(vd_model* m) {
+  m->wgrad.clear();
+  m->wgrad_open = true;
+}
+inline int wgrad_flush(vd_model* m, BatchSlot& b, hipStream_t s) {
+  m->wgrad_open = false;
+  const int n = (int)m->wgrad.size();
+  if (n == 0) return VD_OK;
+  VD_CHECK_ARG(n <= VD_LIVE_MAXP, "%d weight-gradient products in one encoder backward, the grouped launch takes %d", n, VD_LIVE_MAXP);
+  VdLiveProduct lp[VD_LIVE_MAXP];
+  vdplan::Product prod[VD_LIVE_MAXP];
+  std::vector<long> sig;
+  long total = 0;
+  for (int i = 0; i < n; ++i) {
+    const WgradProduct& w = m->wgrad[i];
+    const int f = w.t_first;
+    lp[i] = w.p;
+    lp[i].segs = w.rows->seg_dev[f];
+    prod[i] = vdplan::Product{w.rows->seg_host[f].data(), (int)w.rows->seg_host[f].size() - 1, w.rows->seg_ksteps[f], (w.p.M / 128) * (w.p.N / 128)};
+    total += (long)prod[i].ksteps * prod[i].tiles;
+    for (const long v : {(long)(intptr_t)w.rows, (long)f, (long)w.p.M, (long)w.p.N}) sig.push_back(v);
+  }
+  m->wgrad.clear();
+  if (total == 0) return VD_OK;   // no live pair at all
+  if (sig != b.wgrad_sig) {
+    std::vector<vdplan::Item> items;
+    std::vector<int32_t> start;
+    const int chunks = (int)std::min<long>(VD_WGRAD_CHUNKS, (total + VD_WGRAD_MIN_KSTEPS - 1) / VD_WGRAD_MIN_KSTEPS);
+    vdplan::work_list(prod, n, chunks, &items, &start);
+    const size_t ints = 4 * items.size() + start.size();
+    int32_t *stage, *dev;
+    VD_TRY(pin_get(b.pinned, "wgrad.plan", ints * sizeof(int32_t), (void**)&stage));
+    VD_TRY(dev_get(b.bufs, "wgrad.plan", ints * sizeof(int32_t), (void**)&dev));
+    for (size_t i = 0; i < items.size(); ++i) {
+      const vdplan::Item& it = items[i];
+      const int32_t packed[4] = {(it.product << 24) | it.tile, it.seg, it.j, it.nk};
+      memcpy(stage + 4 * i, packed, sizeof(packed));
+    }
+    memcpy(stage + 4 * items.size(), start.data(), start.size() * sizeof(int32_t));
+    VD_HIP(hipMemcpyAsync(dev, stage, ints * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    b.wgrad_items = dev;
+    b.wgrad_chunk_start = dev + 4 * items.size();
+    b.wgrad_chunks = chunks;
+    b.wgrad_sig = sig;
+  }
+  return vd_gemm_tn_live_grouped(lp, n, b.wgrad_items, b.wgrad_chunk_start, b.wgrad_chunks, s);
+}
+inline int wgrad_end(vd_model* m, BatchSlot& b, hipStream_t s) {
+  m->wgrad_open = false;
+  return m->wgrad_hold ? VD_OK : wgrad_flush(m, b, s);
 }
 
 // nn.Dropout keep-mask for a call site (null in evaluate mode or p == 0); external masks pin the noise for parity runs
@@ -658,12 +740,21 @@ struct SeqLSTM {
     // contraction of the non-pad pairs: the pad pairs hold da = 0 (rt_encoders.h zero-fills them), the kernel streams at
     // the option dWh kernel's rate, and its workgroups live ~0.1 ms instead of ~0.8 ms -- the index-list kernel is a chain
     // of dependent (row index -> row) loads per K tile whose long-lived workgroups take the third slot of a third of the
-    // CUs away from the option-LSTM backward kernels for most of their run.
+    // CUs away from the option-LSTM backward kernels for most of their run.  (Inside an encoder backward those products do not
+    // launch here at all: `grouped` below hands them to the backward's one live-row launch, which skips the pad pairs without an
+    // index list -- the live rows of a step are a contiguous prefix.  The dense path remains for a recurrence outside such a group.)
     auto dense_fits = [&](long Mrows, long K) { return vd_tn_kmajor_fits(Mrows, 4 * H, K); };
     // bf16 pass (lstmPrecision = 'bf16', configs[4]): the dense contractions whose shape the bf16 kernel takes (256-row tiles) round both
     // fp32 operands to bf16 in registers and multiply on the bf16 MFMA (gemm_ops.hip: 77 vs 167 us at K = 8 000)
     auto wg_flags = [&](long Mrows) { return (m->flags & VD_FLAG_BF16) && vd_tn_split_tiles(Mrows, 4 * H) ? VD_FLAG_BF16 : 0; };
-    if (by_rows && !(T > 1 && dense_fits(H, (long)(T - 1) * N))) {
+    // inside an encoder backward's group (wgrad_begin): the products the grouped live-row launch takes wait for its flush
+    auto grouped = [&](const float* A, long Mrows, const float* B, float* C, int t_first) {
+      if (!m->wgrad_open || !vd_wgrad_group_fits(by_rows, Mrows, 4 * H, m->flags)) return false;
+      m->wgrad.push_back(WgradProduct{VdLiveProduct{A, B, C, nullptr, Mrows, 4 * H, 4 * H, (int)Mrows, (int)(4 * H)}, rows, t_first});
+      return true;
+    };
+    if (T > 1 && grouped(h, H, gates + (long)N * 4 * H, dWh, 1)) {
+    } else if (by_rows && !(T > 1 && dense_fits(H, (long)(T - 1) * N))) {
       if (rows->n_act1 > 0)
         VD_TRY(vd_gemm_tn_rows_acc(h, H, rows->prev1, gates, 4 * H, rows->act1, dWh, 4 * H, (int)H, (int)(4 * H), rows->n_act1, s));
     } else if (T > 1) {
@@ -674,7 +765,8 @@ struct SeqLSTM {
     if (dxs) dxs->assign(parts.size(), nullptr);
     long roff = 0;
     for (size_t i = 0; i < parts.size(); ++i) {
-      if (by_rows && !dense_fits(parts[i], TN)) {
+      if (grouped(xs[i], parts[i], gates, dW + roff * 4 * H, 0)) {
+      } else if (by_rows && !dense_fits(parts[i], TN)) {
         if (rows->n_act > 0)
           VD_TRY(vd_gemm_tn_rows_acc(xs[i], parts[i], rows->act, gates, 4 * H, rows->act, dW + roff * 4 * H, 4 * H, (int)parts[i],
                                      (int)(4 * H), rows->n_act, s));

@@ -205,7 +205,10 @@ struct Disc : Decoder {
     m->wg_used = false;
     auto enc_bwd = [&]() -> int {
       VdRange r("encoder backward");
-      VD_TRY(m->enc->backward(m, sd, b, d_enc));
+      m->wgrad_hold = true;      // the grouped weight-gradient launch is flushed below, behind the option recurrence's fork
+      const int rc = m->enc->backward(m, sd, b, d_enc);
+      m->wgrad_hold = false;
+      VD_TRY(rc);
       VD_PROBE_REC(1, sd);
       if (m->wg_used) VD_PROBE_REC(2, m->s_wg);
       if (m->wg_used) {   // encoder tensors final = the chain on `sd` AND the gradient work on s_wg
@@ -229,6 +232,14 @@ struct Disc : Decoder {
     // takes 2.9 ms instead of 0.7 and dWh 6.9 instead of 6.1 (profiles/r03_experiments.txt section 9)
     VdRange rwg("disc: table gradient + dWh");
     VD_TRY(fork_stream(m, s, sd));
+    // the encoder LSTMs' held-back weight gradients (wgrad_hold above), one launch: behind this fork it runs beside the dWh contraction
+    // instead of beside the last option-backward launches, which all have every workgroup resident and stretch with whatever shares their
+    // CUs (profiles/enc_wgrad_group.txt section 2: parent 22.30 ms, flushed at the end of the encoder backward 22.26, here 21.96).  A group exists only outside a
+    // bf16 pass, so the encoder's tensors are final on `sd` alone
+    if (!m->wgrad.empty()) {
+      VD_TRY(wgrad_flush(m, b, sd));
+      VD_HIP(hipEventRecord(m->ev_enc_grads, sd));
+    }
     if (c16) VD_TRY(vd_segment_rowsum_acc_bf16(gates16, 4 * H, b.opt.tok, perm, (long)To * NO, (int)(4 * H), dtab, 4 * H, sd));
     else VD_TRY(vd_segment_rowsum_acc(gates, 4 * H, b.opt.tok, perm, (long)To * NO, (int)(4 * H), dtab, 4 * H, sd));
     VD_TRY(vd_colsum_acc(dtab, 4 * H, (int)V + 1, (int)(4 * H), Gp(m, "opt.b"), sd));

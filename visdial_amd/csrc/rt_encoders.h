@@ -201,8 +201,9 @@ struct TextBranches {
     VD_TRY(wave_backward(m, s, st, ss, 2, dlast));
     hipStream_t sw;
     VD_TRY(wg_fork(m, s, &sw));                 // the recurrences are done: only parameter gradients are left
+    wgrad_begin(m);                             // both stacks' dense weight gradients: one live-row launch behind the tails
     for (int k = 0; k < 2; ++k) VD_TRY(st[k]->param_tail(m, sw, *ss[k]));
-    return VD_OK;
+    return wgrad_end(m, b, sw);
   }
 };
 
@@ -357,7 +358,9 @@ struct HistoryBranch {
       WaveStack* st = &wave;
       const SeqTok* ss = &b.h;
       VD_TRY(wave_backward(m, s, &st, &ss, 1, &dlast));
-      return wave.param_tail(m, s, b.h);
+      wgrad_begin(m);
+      VD_TRY(wave.param_tail(m, s, b.h));
+      return wgrad_end(m, b, s);
     }
     std::vector<float*> dx;
     VD_TRY(lstm_stack_backward(m, s, hist, dlast, nullptr, &dx));

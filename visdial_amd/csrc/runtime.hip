@@ -38,8 +38,11 @@ int upload_tokens(BatchSlot& sl, SeqTok& ss, const std::string& tag, const int32
   ss.N = N;
   ss.present = true;
   ss.sorted = sorted;
+  sl.wgrad_sig.clear();   // new lengths: the weight-gradient work list is rebuilt (rt_core.h wgrad_flush)
   const size_t TN = (size_t)T * N;
-  const size_t total = sorted ? 7 * TN + 2 * (size_t)N + T : TN;   // (+ up to 3 x T*N row-list entries)
+  // (+ up to 3 x T*N row-list entries; behind them, 16-byte aligned, the two segment tables of the live-row weight-gradient contractions)
+  const size_t seg_at = (7 * TN + 2 * (size_t)N + T + 3) / 4 * 4, seg_ints = 4 * ((size_t)T + 1);
+  const size_t total = sorted ? seg_at + 2 * seg_ints : TN;
   int32_t* stage = nullptr;
   VD_TRY(pin_get(sl.pinned, tag + ".stage", total * sizeof(int32_t), (void**)&stage));
   int32_t* tok = stage;
@@ -93,6 +96,10 @@ int upload_tokens(BatchSlot& sl, SeqTok& ss, const std::string& tag, const int32
     for (int k = n0; k < na; ++k) prev1[k - n0] = act[k] - N;
     ss.n_act = na;
     ss.n_act1 = na - n0;
+    for (int f = 0; f < 2; ++f) {   // wgrad_plan.h: t_first = 0 (dWx pairs), 1 (dWh pairs); a table holds at most T segments + the sentinel
+      ss.seg_ksteps[f] = vdplan::live_segments(ss.nact.data(), T, N, f, &ss.seg_host[f]);
+      memcpy(stage + seg_at + f * seg_ints, ss.seg_host[f].data(), ss.seg_host[f].size() * sizeof(vdplan::Seg));
+    }
   }
   int32_t* dev = nullptr;
   VD_TRY(dev_get(sl.bufs, tag + ".dev", total * sizeof(int32_t), (void**)&dev));
@@ -108,6 +115,7 @@ int upload_tokens(BatchSlot& sl, SeqTok& ss, const std::string& tag, const int32
     ss.act = ss.nact_dev + T;
     ss.act1 = ss.act + (T > 0 ? ss.nact[0] : 0);
     ss.prev1 = ss.act + TN;
+    for (int f = 0; f < 2; ++f) ss.seg_dev[f] = dev + seg_at + f * seg_ints;
   }
   return VD_OK;
 }
