@@ -5,7 +5,8 @@ on the chosen split of the REAL data files (evaluate.lua:80-81) and ranks the 10
 -useGt 1 -> retrieve (R@1/5/10, median/mean rank, MRR), else predict.  Optionally dumps the {image_id, round_id,
 ranks} records as JSON (evaluate.lua:104-107; the EvalAI submission format).  -rollout 1 ranks every round on a history of
 the model's own answers to the rounds before it (visdial_amd/split_eval.py E1-E5; -rolloutHistory concat: CH1-CH6, for the encoders whose
-history is the running concatenation of the dialog): the same ranks, metrics and records.  Without data files on disk it falls
+history is the running concatenation of the dialog): the same ranks, metrics and records.  -denseAnnotations <json> adds the NDCG of the annotated rounds
+(visdial_amd/dense.py; -host native: ndcg_kernel).  Without data files on disk it falls
 back to synthetic VisDial-shaped batches (plumbing check only; says so)."""
 import argparse
 import os
@@ -56,6 +57,9 @@ def parse_args(argv=None):
                     help='-rollout 1: row = every history row holds one round (E4); concat = the encoders that read the running concatenation '
                          'of the dialog (lf-ques-hist, lf-ques-im-hist, lf-att-ques-im-hist) roll out by the concatenation rule '
                          '(visdial_amd/split_eval.py CH1-CH6): row r + 1 = row r, <END>, the question, the answer, cut at the end where it does not fit')
+    ap.add_argument('-denseAnnotations', '--denseAnnotations', default='',
+                    help='a file of dense relevance annotations (VisDial v1.0: a JSON list of {image_id, round_id, gt_relevance}): also print the '
+                         'NDCG of the annotated rounds of the split (csrc/loss.hip DT2; -host native: on the device) and add it to their records')
     a = ap.parse_args(argv)
     if a.rolloutHistory == 'concat' and not a.rollout:
         raise SystemExit('-rolloutHistory concat is the history rule of a rollout: it needs -rollout 1')
@@ -135,6 +139,12 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit(str(e))
     restore_weights(model, saved, a.paramOrder or None)          # evaluate.lua:91
+    if a.denseAnnotations:                                       # NDCG reads the final scores: every decoder, head, cache and rollout
+        from visdial_amd.dense import load_dense_annotations
+        try:
+            model.denseAnnotations = load_dense_annotations(a.denseAnnotations)
+        except (OSError, ValueError) as e:
+            raise SystemExit('-denseAnnotations: %s' % e)
     print('Evaluating..')
     if a.perplexity:
         model.evaluate(dl, a.split)

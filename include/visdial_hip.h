@@ -431,7 +431,20 @@ int vd_comm_stats(int64_t* bucket1_floats, int64_t* bucket2_floats, int* overlap
 int vd_comm_overlap_ms(float* lead_ms);
 int vd_model_allreduce_grads(vd_model* m);                /* enqueue only; every rank, once per step */
 int vd_model_init_params(vd_model* m, uint64_t seed);     /* library-default init */
+/* Names that start with '@' are batch attachments, not parameters (no parameter's name starts with it).
+ * "@dense_relevance", n = N * O floats: the dense relevance matrix (VisDial v1.0 annotations) of the batch uploaded last, row n = round
+ * n.  A row is annotated (every entry finite and >= 0) or not annotated (every entry -1); a mixed row, a NaN, an infinity or another
+ * negative value, a wrong n, and a call before any upload are argument errors that name the attachment.  The matrix is checked on the
+ * host, staged in pinned memory and copied on the upload lane; the call waits for no step and does not empty the answer-encoding cache.
+ * The next upload into the batch's slot drops it.  What it changes: vd_model_forward_backward(m, 0) of a disc model trains on it
+ * (below), and vd_model_get_tensor "@ndcg" ranks with it.  Everything else ignores it. */
 int vd_model_set_tensor(vd_model* m, const char* name, const float* host, int64_t n);   /* wrapperW:copy(...) */
+/* "@ndcg", which = 0, n = 2 N: runs the NDCG kernel on the scores of the last forward or retrieval of the current batch (either decoder)
+ * and its "@dense_relevance"; `host` receives N DOUBLES, bit for bit, in the 2 N floats of the signature (read the buffer as double[N]).
+ * k = the number of candidates with relevance > 0; candidates ranked by score as vd_model_ranks ranks them; DCG = the sum over ranks
+ * r <= k of relevance / log2(1 + r); IDCG = the same with the candidates ranked by relevance (ties: the lower index first); the value is
+ * DCG / IDCG, -1 for an annotated round with k = 0 (leave it out of a mean) and -2 for a round that is not annotated.  Without an
+ * attachment on the current batch: a state error that names it. */
 int vd_model_get_tensor(vd_model* m, const char* name, int which /*0 W, 1 dW, 2 m, 3 v*/, float* host, int64_t n);
 int vd_model_set_training(vd_model* m, int on);           /* wrapper:training() / :evaluate() (model.lua:57,111) */
 int vd_model_set_dropout_mask(vd_model* m, const char* site, const uint8_t* host_keep, int64_t n); /* NULL host = clear */
@@ -444,7 +457,15 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* host_batch);
  * words, on every row that contributes without it (non-pad input and target > 0), loss_r = lse - sum_c t_c logit_c, gradient
  * softmax - t (rules LS1-LS4 at the top of csrc/loss.hip).  vd_model_loss then reports the smoothed loss.  only_forward = 1,
  * vd_model_retrieve*, perplexity and every score or rank are what they are without the variable, and eps = 0 launches the kernels
- * of a library that does not know it, with the same arguments. */
+ * of a library that does not know it, with the same arguments.
+ * Dense fine-tuning (decoder disc): when the batch carries "@dense_relevance" (vd_model_set_tensor), a TRAINING step takes the target
+ * t = rel / sum(rel) with weight w = 1 for an annotated round with a relevant candidate, w = 0 for an annotated round without one, and
+ * t = onehot(answer_ind) with w = mu for a round that is not annotated; loss = sum_n w_n (lse_n - sum_o t_o s_o) / W with W = sum_n w_n
+ * over the batch, ds = w_n (softmax - t) / W (rules DT1-DT5 at the top of csrc/loss.hip); vd_model_loss reports that weighted mean.
+ * mu is the environment's VD_DENSE_MIX, a finite real in [0, 1] (0 / unset: rounds without an annotation do not train), read by
+ * vd_model_create, which refuses any other text by name.  A batch with W = 0, a model created with VD_LABEL_SMOOTHING > 0 and a
+ * model of decoder gen refuse the dense step by name; only_forward = 1, retrieval, scores and ranks ignore the attachment, and a batch
+ * without one launches the kernels it launched before. */
 int vd_model_forward_backward(vd_model* m, int only_forward);
 int vd_model_loss(vd_model* m, float* loss);              /* curLoss of the last forward (waits for it): disc = mean
                                                              cross-entropy, gen = summed NLL (model.lua:309-311,330) */

@@ -15,7 +15,7 @@ import torch
 
 from visdial_amd import opts
 from visdial_amd.dataloader import Dataloader, SyntheticDataloader
-from visdial_amd.model import Model, refuse_training_knobs
+from visdial_amd.model import Model, refuse_dense_training, refuse_training_knobs
 from visdial_amd.checkpoint import load_checkpoint, restore_weights, save_t7
 
 
@@ -46,13 +46,18 @@ def main():
         mp['gpuid'], mp['batchSize'] = opt['gpuid'], opt['batchSize']
         # run control and runtime (non-architectural) choices stay with the command line
         for k in ('numEpochs', 'maxIters', 'savePath', 'saveIter', 'host', 'lstmPrecision', 'saveFormat',
-                  'synthetic', 'labelSmoothing', 'gradClipNorm', 'weightDecay'):
+                  'synthetic', 'labelSmoothing', 'gradClipNorm', 'weightDecay', 'denseAnnotations', 'denseMix'):
             mp[k] = opt.get(k)
     if mp.get('host', 'python') != 'native':                     # -labelSmoothing / -gradClipNorm / -weightDecay need -host native
         try:
             refuse_training_knobs(mp)
+            refuse_dense_training(mp)
         except ValueError as e:
             raise SystemExit(str(e))
+    try:
+        opts.check_dense(mp)                                     # -denseAnnotations with decoder gen / -labelSmoothing: before any model exists
+    except ValueError as e:
+        raise SystemExit(str(e))
     # the dataloader is built from the CURRENT command line (train.lua:47-48), never from paths stored in a checkpoint
     have = lambda p: os.path.exists(p) or os.path.exists(p[:-3] + '.npz')
     if os.path.exists(opt['inputJson']) and have(opt['inputQues']):

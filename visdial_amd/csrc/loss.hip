@@ -16,6 +16,23 @@
 //       its own (block_row_sum_stage below).
 // Both heads evaluate t as onehot - eps (onehot - 1/K), i.e. loss = (lse - s_gt) + eps (s_gt - sum s / K): a head with one class
 // (O = 1) then gives the plain head's bits, because onehot - 1/1 and s_gt - sum s / 1 are exactly 0.
+//
+// Dense relevance (the VisDial v1.0 annotations: one annotated round per dialog, a relevance in [0, 1] for each candidate; not in the
+// reference).  visdial_amd/dense.py restates the rules in fp64 numpy:
+//   DT1 a batch of N rounds may carry a relevance matrix rel [N x O] of floats (vd_model_set_tensor "@dense_relevance").  A row is annotated
+//       -- every entry finite and >= 0 -- or not annotated -- every entry -1; anything else (a mixed row, a NaN, another negative value) is
+//       refused by name on the host, before it reaches the device.
+//   DT2 NDCG of an annotated row: k = #{o : rel_o > 0}; candidates ranked by score with the rule of ranks_kernel (higher score first, lower
+//       index first among equal scores); DCG = sum over the candidates of rank r <= k of rel / log2(1 + r); IDCG = the same sum with the
+//       candidates ranked by relevance, descending, lower index first among equal values; NDCG = DCG / IDCG (the official v1.0 evaluation).
+//       A row with k = 0 has none: -1, left out of the mean.  A row that is not annotated: -2.
+//   DT3 the target of an annotated row with sum_o rel > 0 is t = rel / sum rel with weight w = 1; an annotated row whose relevances are all 0
+//       has w = 0.  A row that is not annotated keeps t = onehot(gt) with w = mu (VD_DENSE_MIX in [0, 1]; 0 or unset: such rounds do not train).
+//   DT4 loss_n = lse - sum_o t_o s_o; the step's loss is sum_n w_n loss_n / W with W = sum_n w_n over this batch; ds_o = w_n (softmax_o - t_o)
+//       / W.  A batch with W = 0 is refused by name.  loss_rows[n] holds w_n loss_n; the host divides the sum by W (vd_model_loss).
+//   DT5 the dense target applies to vd_model_forward_backward(m, 0) of a disc model only, as LS3: only_forward = 1, retrieval, scores and
+//       ranks ignore it; a batch without the matrix launches score_ce_kernel / score_ce_smooth_kernel with their arguments; a dense batch on
+//       a model created with VD_LABEL_SMOOTHING > 0 and a dense training step of a gen model are refused by name (gen accepts it for NDCG).
 #include "common.h"
 
 #define MAX_OPT 128
@@ -23,11 +40,14 @@
 // One workgroup per QA round n.
 //   score[o] = <optH[n,o,:], enc[n,:]> ; loss_n = logsumexp(score) - score[gt]
 //   if train: ds = (softmax - onehot) * gscale ; dOptH[n,o,:] = ds[o]*enc[n,:] ; dEnc[n,:] = sum_o ds[o]*optH[n,o,:]
-//   SMOOTH: onehot is LS1's target
-template <bool SMOOTH>
+//   TARGET_SMOOTH: onehot is LS1's target.  TARGET_DENSE: the target and the weight of DT3 from the round's row of `rel` (staged in LDS next
+//   to sc / ds); `smooth` is mu and gscale is 1 / W; a round of weight 0 writes its scores, loss 0 and zero gradients and reads optH once.
+enum ScoreTarget { TARGET_ONEHOT, TARGET_SMOOTH, TARGET_DENSE };
+template <ScoreTarget TARGET>
 __device__ __forceinline__ void score_ce_body(const float* __restrict__ optH, const float* __restrict__ enc, const int* __restrict__ gt,
                                               float* __restrict__ scores, float* __restrict__ loss_rows, float* __restrict__ dOptH,
-                                              float* __restrict__ dEnc, int O, int H, float gscale, float smooth) {
+                                              float* __restrict__ dEnc, int O, int H, float gscale, float smooth,
+                                              const float* __restrict__ rel = nullptr, float* rl = nullptr, float* row_w = nullptr) {
   __shared__ float sc[MAX_OPT];
   __shared__ float ds[MAX_OPT];
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -46,6 +66,8 @@ __device__ __forceinline__ void score_ce_body(const float* __restrict__ optH, co
       scores[(long)n * O + o] = a;
     }
   }
+  if constexpr (TARGET == TARGET_DENSE)
+    for (int o = tid; o < O; o += 256) rl[o] = rel[(long)n * O + o];
   __syncthreads();
   if (gt == nullptr) return;
   if (wave == 0) {
@@ -57,7 +79,25 @@ __device__ __forceinline__ void score_ce_body(const float* __restrict__ optH, co
     sum = wave_sum(sum);
     const float lse = mx + logf(sum);
     const int g = gt[n];
-    if constexpr (SMOOTH) {
+    if constexpr (TARGET == TARGET_DENSE) {
+      float tot = 0.f;
+      for (int o = lane; o < O; o += 64) tot += rl[o];
+      tot = wave_sum(tot);
+      const bool annotated = rl[0] >= 0.f;               // DT1: a row is all -1 or all >= 0
+      const float w = annotated ? (tot > 0.f ? 1.f : 0.f) : smooth;
+      const float inv = annotated && tot > 0.f ? 1.f / tot : 0.f;
+      float dot = 0.f;
+      for (int o = lane; o < O; o += 64) {
+        const float t = annotated ? rl[o] * inv : (o == g ? 1.f : 0.f);
+        dot += t * sc[o];
+        ds[o] = (expf(sc[o] - lse) - t) * (w * gscale);
+      }
+      dot = wave_sum(dot);
+      if (lane == 0) {
+        loss_rows[n] = w > 0.f ? w * (lse - dot) : 0.f;
+        *row_w = w;
+      }
+    } else if constexpr (TARGET == TARGET_SMOOTH) {
       const float invO = 1.f / (float)O;
       float tot = 0.f;
       for (int o = lane; o < O; o += 64) tot += sc[o];
@@ -72,6 +112,16 @@ __device__ __forceinline__ void score_ce_body(const float* __restrict__ optH, co
   }
   if (dOptH == nullptr) return;
   __syncthreads();
+  if constexpr (TARGET == TARGET_DENSE) {
+    if (*row_w == 0.f) {   // DT3: the round does not train
+      const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int k = tid * 4; k < H; k += 1024) {
+        for (int o = 0; o < O; ++o) *reinterpret_cast<float4*>(dOptH + ((long)n * O + o) * H + k) = z;
+        *reinterpret_cast<float4*>(dEnc + (long)n * H + k) = z;
+      }
+      return;
+    }
+  }
   for (int k = tid * 4; k < H; k += 1024) {
     const float4 ev = *reinterpret_cast<const float4*>(e + k);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -92,13 +142,21 @@ __global__ void __launch_bounds__(256)
 score_ce_kernel(const float* __restrict__ optH, const float* __restrict__ enc, const int* __restrict__ gt,
                 float* __restrict__ scores, float* __restrict__ loss_rows, float* __restrict__ dOptH,
                 float* __restrict__ dEnc, int O, int H, float gscale) {
-  score_ce_body<false>(optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, 0.f);
+  score_ce_body<TARGET_ONEHOT>(optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, 0.f);
 }
 __global__ void __launch_bounds__(256)
 score_ce_smooth_kernel(const float* __restrict__ optH, const float* __restrict__ enc, const int* __restrict__ gt,
                        float* __restrict__ scores, float* __restrict__ loss_rows, float* __restrict__ dOptH,
                        float* __restrict__ dEnc, int O, int H, float gscale, float smooth) {
-  score_ce_body<true>(optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, smooth);
+  score_ce_body<TARGET_SMOOTH>(optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, smooth);
+}
+__global__ void __launch_bounds__(256)
+score_ce_dense_kernel(const float* __restrict__ optH, const float* __restrict__ enc, const int* __restrict__ gt,
+                      float* __restrict__ scores, float* __restrict__ loss_rows, float* __restrict__ dOptH,
+                      float* __restrict__ dEnc, int O, int H, float gscale, float mix, const float* __restrict__ rel) {
+  __shared__ float rl[MAX_OPT];   // the round's relevance row, next to the body's sc[] / ds[]
+  __shared__ float row_w;
+  score_ce_body<TARGET_DENSE>(optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, mix, rel, rl, &row_w);
 }
 
 // rank[n,o] = 1 + #{j : s[j] > s[o]  or (s[j] == s[o] and j < o)}   (descending sort position)
@@ -113,6 +171,64 @@ ranks_kernel(const float* __restrict__ scores, int* __restrict__ ranks, int O) {
   int r = 1;
   for (int j = 0; j < O; ++j) r += (sc[j] > s) || (sc[j] == s && j < o);
   ranks[(long)n * O + o] = r;
+}
+
+// DT2: NDCG of round n from its scores and its row of rel, one double per round (-1: k = 0, -2: not annotated).  Thread o ranks candidate o
+// by score (the comparison of ranks_kernel) and by relevance and computes its two terms in double with log2 in double; thread 0 adds the
+// <= 128 terms in index order (a candidate outside the first k adds an exact 0), so the value is the fp64 restatement's to rounding.  No
+// atomics, no host read.
+__global__ void __launch_bounds__(128)
+ndcg_kernel(const float* __restrict__ scores, const float* __restrict__ rel, double* __restrict__ out, int O) {
+  __shared__ float sc[MAX_OPT];
+  __shared__ float rl[MAX_OPT];
+  __shared__ int srank[MAX_OPT];
+  __shared__ int rrank[MAX_OPT];
+  __shared__ double dterm[MAX_OPT];
+  __shared__ double iterm[MAX_OPT];
+  __shared__ int kk;
+  const int n = blockIdx.x, o = threadIdx.x;
+  if (o < O) {
+    sc[o] = scores[(long)n * O + o];
+    rl[o] = rel[(long)n * O + o];
+  }
+  __syncthreads();
+  if (o < O) {
+    const float s = sc[o], v = rl[o];
+    int r = 1, q = 1;
+    for (int j = 0; j < O; ++j) {
+      r += (sc[j] > s) || (sc[j] == s && j < o);
+      q += (rl[j] > v) || (rl[j] == v && j < o);
+    }
+    srank[o] = r;
+    rrank[o] = q;
+  }
+  if (o == 0) {
+    int k = 0;
+    for (int j = 0; j < O; ++j) k += rl[j] > 0.f;
+    kk = k;
+  }
+  __syncthreads();
+  const int k = kk;
+  if (o < O) {
+    dterm[o] = srank[o] <= k ? (double)rl[o] / log2(1.0 + (double)srank[o]) : 0.0;
+    iterm[o] = rrank[o] <= k ? (double)rl[o] / log2(1.0 + (double)rrank[o]) : 0.0;
+  }
+  __syncthreads();
+  if (o != 0) return;
+  if (rl[0] < 0.f) {
+    out[n] = -2.0;
+    return;
+  }
+  if (k == 0) {
+    out[n] = -1.0;
+    return;
+  }
+  double dcg = 0.0, idcg = 0.0;
+  for (int j = 0; j < O; ++j) {
+    dcg += dterm[j];
+    idcg += iterm[j];
+  }
+  out[n] = dcg / idcg;
 }
 
 // sum of one row of V logits for a 256-thread block (LS4): 256 strided threads, wave_sum, the four wave partials added in a fixed order.
@@ -255,6 +371,29 @@ int vd_score_ce_p(const float* optH, const float* enc, const int32_t* gt, float*
   if (N == 0) return VD_OK;
   hipLaunchKernelGGL(score_ce_smooth_kernel, dim3(N), dim3(256), 0, stream, optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale,
                      smooth);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+// internal (rt_core.h): the discriminative training head on the targets of DT3 / DT4 (rel [N x O], validated by the host: DT1); gscale = 1 / W
+int vd_score_ce_dense_p(const float* optH, const float* enc, const int32_t* gt, const float* rel, float* scores, float* loss_rows,
+                        float* dOptH, float* dEnc, int N, int O, int H, float gscale, float mix, hipStream_t stream) {
+  VD_CHECK_ARG(optH && enc && scores && gt && rel && loss_rows && N >= 0 && O >= 1 && O <= MAX_OPT && H % 4 == 0,
+               "vd_score_ce_dense_p: bad args (O=%d must be <= %d; the dense head needs gt, rel and loss_rows)", O, MAX_OPT);
+  VD_CHECK_ARG((dOptH == nullptr) == (dEnc == nullptr), "vd_score_ce_dense_p: dOptH and dEnc go together");
+  VD_CHECK_ARG(mix >= 0.f && mix <= 1.f, "vd_score_ce_dense_p: the mix %g is not in [0, 1]", (double)mix);
+  if (N == 0) return VD_OK;
+  hipLaunchKernelGGL(score_ce_dense_kernel, dim3(N), dim3(256), 0, stream, optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, mix,
+                     rel);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+// internal (rt_core.h): DT2, ndcg [N] doubles from scores and rel [N x O]
+int vd_ndcg_p(const float* scores, const float* rel, double* ndcg, int N, int O, hipStream_t stream) {
+  VD_CHECK_ARG(scores && rel && ndcg && N >= 0 && O >= 1 && O <= MAX_OPT, "vd_ndcg_p: bad args");
+  if (N == 0) return VD_OK;
+  hipLaunchKernelGGL(ndcg_kernel, dim3(N), dim3(128), 0, stream, scores, rel, ndcg, O);
   VD_LAUNCH_CHECK();
   return VD_OK;
 }

@@ -121,6 +121,11 @@ int vd_score_ce_p(const float* optH, const float* enc, const int32_t* gt, float*
                   int O, int H, float gscale, float smooth, hipStream_t stream);
 int vd_logsoftmax_nll_p(float* logits, int64_t ld, int64_t rows, int V, const int32_t* tok_in, const int32_t* target, float* loss_rows,
                         int write_grad, float smooth, hipStream_t stream);
+// loss.hip: the discriminative training head on dense relevance targets (DT3 / DT4 there): rel [N x O] holds DT1's rows, mix is mu, gscale is
+// 1 / W; loss_rows[n] = w_n loss_n.  vd_ndcg_p: DT2, one double per round (-1: no relevant candidate, -2: not annotated).
+int vd_score_ce_dense_p(const float* optH, const float* enc, const int32_t* gt, const float* rel, float* scores, float* loss_rows,
+                        float* dOptH, float* dEnc, int N, int O, int H, float gscale, float mix, hipStream_t stream);
+int vd_ndcg_p(const float* scores, const float* rel, double* ndcg, int N, int O, hipStream_t stream);
 // elementwise.hip: the update with a global-norm clip and decoupled weight decay (VD_GRAD_CLIP_NORM / VD_WEIGHT_DECAY; GC1 - GC3, WD1
 // there).  vd_grad_clip_scale_p: work[0] = c / || gscale g ||_2 where that norm is finite and > c > 0, else 1; work[1] = the norm; two
 // launches on `stream`, no atomic, no host read, the same bits on every run; work holds vd_clip_work_floats() floats.
@@ -190,6 +195,10 @@ struct BatchSlot {
   int32_t* gt = nullptr;  // [N] 0-based
   std::vector<int32_t> gt_host;
   bool has_gt = false;
+  // batch attachment "@dense_relevance" (vd_model_set_tensor; loss.hip DT1): the relevance matrix [N x O] of this upload, or null; the next
+  // upload into the slot clears it.  rel_W = the sum of DT3's weights over the batch with the model's mu
+  float* rel = nullptr;
+  double rel_W = 0.0;
   // option de-duplication (decoder disc): the option LSTM encodes every DISTINCT candidate once (decoders/disc.lua:4-15 --
   // the encoding depends on the tokens only); opt_uid[n * O + o] = its row among the opt.N unique rows, or null
   int32_t* opt_uid = nullptr;
@@ -330,6 +339,7 @@ struct vd_model {
   float* loss_host = nullptr;  // pinned
   long loss_cap = 0, loss_n = 0;
   bool loss_is_sum = false;
+  double loss_div = 0.0;   // a dense step (loss.hip DT4): vd_model_loss divides the sum of the rows by W; 0 = by loss_n
   std::unique_ptr<vdrt::Encoder> enc;
   std::unique_ptr<vdrt::Decoder> dec;
   float* scores = nullptr;  // [N x O] of the last forward / retrieval

@@ -41,6 +41,7 @@ inline int stage_loss(vd_model* m, const float* loss_rows, long n, bool is_sum, 
   }
   m->loss_n = n;
   m->loss_is_sum = is_sum;
+  m->loss_div = 0.0;
   VD_HIP(hipMemcpyAsync(m->loss_host, loss_rows, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
   VD_HIP(hipEventRecord(m->ev_loss, s));
   return VD_OK;
@@ -143,6 +144,13 @@ struct Disc : Decoder {
     VD_CHECK_ARG(b.opt.present, "decoder 'disc' needs batch.options");
     VD_CHECK_ARG(only_forward || b.has_gt, "training decoder 'disc' needs batch.answer_ind");
     if (b.cached) return forward_cached(m, b, only_forward);
+    const bool dense = !only_forward && b.rel != nullptr;   // loss.hip DT5
+    VD_CHECK_ARG(!dense || m->sw.label_smoothing == 0.0,
+                 "vd_model_forward_backward: the batch carries '@dense_relevance' and this model was created with VD_LABEL_SMOOTHING = %g: a "
+                 "dense target is not smoothed; create the model without it", m->sw.label_smoothing);
+    VD_CHECK_ARG(!dense || b.rel_W > 0.0,
+                 "vd_model_forward_backward: the batch's '@dense_relevance' gives every round the weight 0 (W = 0, VD_DENSE_MIX = %g): no "
+                 "annotated round has a relevant candidate and rounds without an annotation weigh VD_DENSE_MIX", m->sw.dense_mix);
     // NO = rows the option LSTM executes: N * O, or the number of DISTINCT candidates when the upload de-duplicated them
     const int N = b.q.N, O = m->p.numOptions, NOfull = N * O, NO = b.opt.N, To = b.opt.T;
     const bool dedup = b.opt_uid != nullptr;
@@ -177,14 +185,20 @@ struct Disc : Decoder {
       VD_TRY(ws_get(m, "crit.d_enc", (size_t)N * H, &d_enc));
       if (dedup) VD_TRY(ws_get(m, "crit.d_optH_full", (size_t)NOfull * H, &d_optH_full));
     }
-    // a training step's targets are smoothed by VD_LABEL_SMOOTHING (loss.hip LS1, LS3); 0 is vd_score_ce itself
-    VD_TRY(vd_score_ce_p(optH, enc_out, b.gt, scores, loss_rows, dedup ? d_optH_full : d_optH, d_enc, N, O, (int)H, 1.0f / N,
-                         only_forward ? 0.f : (float)m->sw.label_smoothing, s));
+    // a training step's targets are smoothed by VD_LABEL_SMOOTHING (loss.hip LS1, LS3); 0 is vd_score_ce itself.  A batch that carries
+    // "@dense_relevance" trains on DT3's targets instead (DT4: gscale = 1 / W)
+    if (dense)
+      VD_TRY(vd_score_ce_dense_p(optH, enc_out, b.gt, b.rel, scores, loss_rows, dedup ? d_optH_full : d_optH, d_enc, N, O, (int)H,
+                                 (float)(1.0 / b.rel_W), (float)m->sw.dense_mix, s));
+    else
+      VD_TRY(vd_score_ce_p(optH, enc_out, b.gt, scores, loss_rows, dedup ? d_optH_full : d_optH, d_enc, N, O, (int)H, 1.0f / N,
+                           only_forward ? 0.f : (float)m->sw.label_smoothing, s));
     if (dedup && !only_forward) {   // the gradients of the copies of a distinct row add up
       VD_TRY(vd_memset(d_optH, 0, (long)NO * H * 4, s));
       VD_TRY(vd_embed_scatter_acc(d_optH, b.opt_uid, nullptr, d_optH_full, NOfull, (int)H, 1.f, s));
     }
     VD_TRY(stage_loss(m, loss_rows, N, false, s));
+    if (dense) m->loss_div = b.rel_W;
     m->scores = scores;
     m->prof_valid = !only_forward;
     if (only_forward) return VD_OK;
@@ -466,6 +480,9 @@ struct Gen : Decoder {
   }
   int forward_backward(vd_model* m, BatchSlot& b, bool only_forward) override {
     VD_CHECK_ARG(b.ain.present && b.aout.present, "decoder 'gen' needs batch.answer_in / answer_out");
+    VD_CHECK_ARG(only_forward || !b.rel,
+                 "vd_model_forward_backward: the batch carries '@dense_relevance', which trains the option scores of decoder 'disc' (loss.hip "
+                 "DT5); this model's decoder is 'gen', which reads the attachment for '@ndcg' only");
     hipStream_t s = m->s_main;
     const int N = b.q.N, Ta = b.ain.T;
     const long rows = (long)Ta * N;

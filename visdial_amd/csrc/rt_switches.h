@@ -11,7 +11,7 @@
 //  - the sampling and beam variables and VD_BEAM_ROLLOUT are not read for decoder disc, VD_RETRIEVE_ROLLOUT not for decoder gen: garbage in
 //    them is ignored there.  VD_ROLLOUT_ENCODER and VD_ROLLOUT_CONCAT_END are validated for every model.
 //  - the training knobs are read for both decoders: VD_LABEL_SMOOTHING in [0, 1), VD_GRAD_CLIP_NORM and VD_WEIGHT_DECAY in [0, FLT_MAX]
-//    (both are applied in fp32); 0 or unset = off.
+//    (both are applied in fp32); 0 or unset = off.  VD_DENSE_MIX in [0, 1], for both decoders too.
 #pragma once
 #include <errno.h>
 #include <float.h>
@@ -49,6 +49,9 @@ struct Switches {                     // (decoder the variable is read for) what
   double label_smoothing = 0.0;       // VD_LABEL_SMOOTHING
   double grad_clip_norm = 0.0;        // VD_GRAD_CLIP_NORM
   double weight_decay = 0.0;          // VD_WEIGHT_DECAY
+  // VD_DENSE_MIX (both): the weight mu of a round that is not annotated in a training step on a batch that carries "@dense_relevance"
+  // (loss.hip DT3); 0 = such rounds do not train
+  double dense_mix = 0.0;
 };
 
 // The typed readers.  An unset variable leaves *out alone; a refusal is "vd_model_create: NAME = 'text' <must>".
@@ -140,6 +143,9 @@ inline int parse_switches(const char* encoder, const char* decoder, int lstmBf16
   if (!(read_real("VD_LABEL_SMOOTHING", 0.0, false, 1.0 - (double)FLT_EPSILON / 2, "must be a real in [0, 1) (0 = off)", &sw.label_smoothing) &&
         read_real("VD_GRAD_CLIP_NORM", 0.0, false, (double)FLT_MAX, real0, &sw.grad_clip_norm) &&
         read_real("VD_WEIGHT_DECAY", 0.0, false, (double)FLT_MAX, real0, &sw.weight_decay)))
+    return -1;
+  if (!read_real("VD_DENSE_MIX", 0.0, false, 1.0, "must be a finite real in [0, 1] (0 = rounds without an annotation do not train)",
+                 &sw.dense_mix))
     return -1;
   *out = sw;
   return 0;

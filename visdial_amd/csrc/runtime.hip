@@ -502,7 +502,71 @@ int vd_model_init_params(vd_model* m, uint64_t seed) {
   return VD_OK;
 }
 
+// Batch attachments: names that start with '@' (no parameter's does).  "@dense_relevance" (loss.hip DT1): the relevance matrix [N x O] of the
+// batch uploaded last, validated here, staged in pinned memory and copied on the upload lane behind the batch's own fields.  It waits for
+// neither the main stream nor a running step, and leaves the answer-encoding cache alone: it touches no weight.
+static int attach_dense_relevance(vd_model* m, const float* host, int64_t n) {
+  const char* who = "vd_model_set_tensor: '@dense_relevance'";
+  VD_CHECK_ARG(m->uploaded >= 0, "%s attaches to the batch uploaded last, and no batch has been uploaded", who);
+  BatchSlot& sl = m->slot[m->uploaded];
+  const int N = sl.q.N, O = m->p.numOptions;
+  VD_CHECK_ARG(n == (int64_t)N * O, "%s holds N x O = %d x %d = %ld values for this batch, got %ld", who, N, O, (long)N * O, (long)n);
+  double W = 0.0;
+  for (int r = 0; r < N; ++r) {
+    const float* row = host + (size_t)r * O;
+    int minus = 0;
+    double sum = 0.0;
+    for (int o = 0; o < O; ++o) {
+      const float v = row[o];
+      VD_CHECK_ARG(v == -1.f || (v >= 0.f && v <= FLT_MAX),
+                   "%s row %d, candidate %d = %g: a relevance is finite and >= 0, and a round without an annotation is a full row of -1", who, r,
+                   o, (double)v);
+      minus += v == -1.f;
+      sum += v;
+    }
+    VD_CHECK_ARG(minus == 0 || minus == O, "%s row %d mixes -1 (%d entries) with relevances: a round without an annotation is a full row of -1",
+                 who, r, minus);
+    W += minus ? m->sw.dense_mix : sum > 0.0 ? 1.0 : 0.0;
+  }
+  hipStream_t s = m->s_side;
+  if (sl.used) VD_HIP(hipStreamWaitEvent(s, sl.done, 0));   // a step that reads an earlier attachment of this upload may still run
+  if (sl.rel) VD_HIP(hipEventSynchronize(sl.ready));        // ... and its copy may still read the staging buffer
+  float* stage = nullptr;
+  VD_TRY(pin_get(sl.pinned, "rel.stage", (size_t)n * sizeof(float), (void**)&stage));
+  memcpy(stage, host, (size_t)n * sizeof(float));
+  VD_TRY(dev_get(sl.bufs, "rel", (size_t)n * sizeof(float), (void**)&sl.rel));
+  VD_HIP(hipMemcpyAsync(sl.rel, stage, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+  VD_HIP(hipEventRecord(sl.ready, s));   // the slot is ready when the attachment has landed too
+  sl.rel_W = W;
+  return VD_OK;
+}
+
+// "@ndcg" (loss.hip DT2): NDCG of every round of the current batch from the scores of its last forward / retrieval and its attached
+// relevance matrix.  n = 2 N: the N doubles the kernel wrote, bit for bit, in the float buffer of the signature.
+static int read_ndcg(vd_model* m, int which, float* host, int64_t n) {
+  const char* who = "vd_model_get_tensor: '@ndcg'";
+  if (!(m->cur >= 0 && m->scores)) return vd_set_error("%s ranks the scores of the last forward or retrieval, and there are none", who), VD_ERR_STATE;
+  BatchSlot& b = m->slot[m->cur];
+  if (!b.rel)
+    return vd_set_error("%s needs the relevance matrix of the current batch: attach it with vd_model_set_tensor '@dense_relevance' after "
+                        "the upload", who), VD_ERR_STATE;
+  VD_CHECK_ARG(which == 0 && n == 2 * (int64_t)m->N, "%s returns N = %d doubles in 2 N = %d floats with selector 0, got n = %ld, selector %d", who,
+               m->N, 2 * m->N, (long)n, which);
+  double* out;
+  VD_TRY(ws_get(m, "ndcg.rows", (size_t)m->N, &out));
+  VD_HIP(hipStreamWaitEvent(m->s_main, b.ready, 0));   // an attachment made after the step began
+  VD_TRY(vd_ndcg_p(m->scores, b.rel, out, m->N, m->O, m->s_main));
+  VD_HIP(hipMemcpyAsync(host, out, (size_t)m->N * sizeof(double), hipMemcpyDeviceToHost, m->s_main));
+  VD_HIP(hipEventRecord(b.done, m->s_main));
+  VD_HIP(hipStreamSynchronize(m->s_main));
+  return VD_OK;
+}
+
 int vd_model_set_tensor(vd_model* m, const char* name, const float* host, int64_t n) {
+  if (m && name && host && name[0] == '@') {
+    if (!strcmp(name, "@dense_relevance")) return attach_dense_relevance(m, host, n);
+    VD_CHECK_ARG(false, "vd_model_set_tensor: unknown batch attachment '%s' (the library knows '@dense_relevance')", name);
+  }
   VD_CHECK_ARG(m && name && host && m->index.count(name), "vd_model_set_tensor: unknown tensor '%s'", name ? name : "(null)");
   const Tensor& t = m->spec[m->index.at(name)];
   VD_CHECK_ARG(n == t.numel(), "vd_model_set_tensor: '%s' holds %ld values, got %ld", name, t.numel(), (long)n);
@@ -513,6 +577,10 @@ int vd_model_set_tensor(vd_model* m, const char* name, const float* host, int64_
 }
 
 int vd_model_get_tensor(vd_model* m, const char* name, int which, float* host, int64_t n) {
+  if (m && name && host && name[0] == '@') {
+    if (!strcmp(name, "@ndcg")) return read_ndcg(m, which, host, n);
+    VD_CHECK_ARG(false, "vd_model_get_tensor: unknown batch attachment '%s' (the library knows '@ndcg')", name);
+  }
   VD_CHECK_ARG(m && name && host && m->index.count(name), "vd_model_get_tensor: unknown tensor '%s'", name ? name : "(null)");
   const Tensor& t = m->spec[m->index.at(name)];
   VD_CHECK_ARG(n == t.numel() && which >= 0 && which <= 3, "vd_model_get_tensor: bad size / selector");
@@ -572,6 +640,8 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
   // would otherwise overwrite them under the copy.  In the pipelined training loop this returns at once.
   if (sl.uploaded) VD_HIP(hipEventSynchronize(sl.ready));
   sl.uploaded = true;
+  sl.rel = nullptr;   // an attachment belongs to one upload
+  sl.rel_W = 0.0;
   sl.B = hb->B;
   const int R = m->p.maxQuesCount, N = hb->B * R, O = m->p.numOptions;
   const long NO = (long)N * O;
@@ -779,7 +849,7 @@ int vd_model_loss(vd_model* m, float* loss) {
   VD_HIP(hipEventSynchronize(m->ev_loss));
   double s = 0;
   for (long i = 0; i < m->loss_n; ++i) s += m->loss_host[i];
-  *loss = (float)(m->loss_is_sum ? s : s / (double)m->loss_n);
+  *loss = (float)(m->loss_is_sum ? s : s / (m->loss_div > 0.0 ? m->loss_div : (double)m->loss_n));
   return VD_OK;
 }
 

@@ -149,6 +149,19 @@ class SyntheticDataloader(object):
             self.add_gen_options(batch, nb)
         return batch, start_id + nb
 
+    def getDenseTrainBatch(self, params, annotations, batch_size=None):
+        """a training batch whose dialogs carry the ids of annotated train images (drawn with replacement from the loader's rng), with
+        `image_id` [B] and `dense_relevance` [B * R x O] (dense.relevance_matrix)"""
+        from .dense import relevance_matrix
+        pool = np.asarray([i for i in self.unique_img_train if any((int(i), r + 1) in annotations for r in range(self.maxQuesCount))], np.int64)
+        if pool.size == 0:
+            raise ValueError("getDenseTrainBatch: no dialog of the train split is annotated")
+        B = int(batch_size or params['batchSize'])
+        batch = self.getTrainBatch(params, batch_size=B)
+        batch['image_id'] = pool[self.rng.randint(0, pool.size, size=B)]
+        batch['dense_relevance'] = relevance_matrix(batch['image_id'], annotations, self.maxQuesCount, self.numOptions)
+        return batch
+
     def add_gen_options(self, batch, B):
         R, O, To = self.maxQuesCount, self.numOptions, self.maxAnsLen
         N = B * R
@@ -402,6 +415,29 @@ class Dataloader(object):
             o = self.getIndexOption(inds, params, 'train')
             out['options'] = o.reshape(o.shape[0] * o.shape[1], o.shape[2], -1)
             out['answer_ind'] = out['answer_ind'].reshape(-1)
+        return out
+
+    def getDenseTrainBatch(self, params, annotations, batchSize=None):
+        """`size` ANNOTATED train dialogs sampled with replacement from the loader's own rng (annotations: dense.load_dense_annotations);
+        the batch of getTrainBatch for them plus `dense_relevance` [size * R x O] (dense.relevance_matrix: DT1 of csrc/loss.hip).
+        getTrainBatch itself is untouched: a loader that never calls this draws what it drew before."""
+        from .dense import relevance_matrix
+        size = int(batchSize or params['batchSize'])
+        ids = np.asarray(self.unique_img_train)
+        R = self.maxQuesCount
+        pool = np.asarray([i + 1 for i, iid in enumerate(ids[:self.numThreads['train']])
+                           if any((int(iid), r + 1) in annotations for r in range(R))], np.int64)
+        if pool.size == 0:
+            raise ValueError("getDenseTrainBatch: no dialog of the train split is annotated (%d annotations, %d train dialogs)"
+                             % (len(annotations), self.numThreads['train']))
+        inds = pool[self.rng.randint(0, pool.size, size=size)]
+        out = self.getIndexData(inds, params, 'train')
+        if params['decoder'] == 'disc':
+            o = self.getIndexOption(inds, params, 'train')
+            out['options'] = o.reshape(o.shape[0] * o.shape[1], o.shape[2], -1)
+            out['answer_ind'] = out['answer_ind'].reshape(-1)
+        out['image_id'] = ids[inds - 1]
+        out['dense_relevance'] = relevance_matrix(out['image_id'], annotations, R, self.numOptions)
         return out
 
     def getTestBatch(self, startId, params, dtype):

@@ -57,6 +57,14 @@ def refuse_training_knobs(params):
                              "-host native (visdial_amd.native.NativeModel); the operator-level host trains with %s = 0" % (key, v, key))
 
 
+def refuse_dense_training(params):
+    """a training run of the operator-level host on dense annotations is refused by name: the dense head (score_ce_dense_kernel) and the
+    batch attachment are internal to the model-level runtime.  Evaluating with -denseAnnotations is untouched: NDCG needs the scores only."""
+    if params.get('denseAnnotations'):
+        raise ValueError("denseAnnotations = %r: dense-annotation fine-tuning runs in the model-level runtime only: use -host native "
+                         "(visdial_amd.native.NativeModel); the operator-level host trains on one-hot targets" % (params['denseAnnotations'],))
+
+
 class Model(SplitEval):
     def __init__(self, params, dist_group=None):
         self.params = params
@@ -291,6 +299,7 @@ class Model(SplitEval):
         inputs, dec_in = prepared if prepared is not None else self.prepare_inputs(batch)
         if not onlyForward and not encOutOnly:
             refuse_training_knobs(self.params)
+            refuse_dense_training(self.params)
             self._flush_option_cache()         # gradients are about to move the weights
         if 'option_rows' in dec_in and 'options' not in dec_in and (not onlyForward or not self._option_cache_active()):
             # prepared for cached evaluation, stepped otherwise: the uncached path needs every distinct row on the device

@@ -53,6 +53,15 @@ TRAIN_SWITCHES = (
     ('weightDecay', 'VD_WEIGHT_DECAY', _text, float, 0.0, None),                          # vd_model_update: decoupled weight decay
 )
 
+DENSE_SWITCHES = (
+    # rows of the same type, chained behind TRAIN_SWITCHES: dense-annotation fine-tuning (loss.hip DT1-DT5)
+    ('denseMix', 'VD_DENSE_MIX', _text, float, 0.0, None),                                # weight of a round without an annotation in a dense step
+)
+"""What a dense step adds to the environment.  The relevance matrix itself is no switch: it is a batch attachment, `attach_dense_relevance`
+(vd_model_set_tensor '@dense_relevance') behind an upload, and `ndcg_rows` (vd_model_get_tensor '@ndcg') reads the NDCG of the scores."""
+
+ALL_SWITCHES = SWITCHES + TRAIN_SWITCHES + DENSE_SWITCHES
+
 
 class _DevArray(object):
     """a raw device pointer as something torch.as_tensor understands (plumbing for torch.distributed only)"""
@@ -109,7 +118,7 @@ class NativeModel(SplitEval):
         self.params = p
         h = C.c_void_p()
         import os
-        switches = {var: text(p.get(key)) for key, var, text, _, _, _ in SWITCHES + TRAIN_SWITCHES}
+        switches = {var: text(p.get(key)) for key, var, text, _, _, _ in ALL_SWITCHES}
 
         def put(values):
             for k, v in values.items():
@@ -124,7 +133,7 @@ class NativeModel(SplitEval):
         finally:
             put(prev)
         self._knobs = {key: default if p.get(key) is None or decoder not in (None, p['decoder']) else conv(p[key])
-                       for key, _, _, conv, default, decoder in SWITCHES + TRAIN_SWITCHES}
+                       for key, _, _, conv, default, decoder in ALL_SWITCHES}
         self.h = h
         lib = _lib.load()
         self.tensors = []
@@ -242,11 +251,40 @@ class NativeModel(SplitEval):
             hb.To, hb.option_in, hb.option_out = a.shape[-1], ptr(a), ptr(i32(batch['option_out']))
         call("vd_model_upload_batch", self.h, C.byref(hb))      # host buffers are consumed before it returns
         self._N = batch['ques_fwd'].shape[0] * batch['ques_fwd'].shape[1]
+        if batch.get('dense_relevance') is not None:            # a dense batch (dataloader.getDenseTrainBatch) trains on its matrix
+            self.attach_dense_relevance(batch['dense_relevance'])
         # non-pad target tokens of THIS batch: the gen loss EMA divides by it (model.lua:76-85)
         self._numTokens = float((np.asarray(batch['answer_out']) > 0).sum()) if 'answer_out' in batch else 0.0
         # whatever was prefetched for trainIteration has just been replaced (evaluate / retrieve / predict / generate
         # between two training steps): the next trainIteration must fetch its own batch
         self._keep = None
+
+    def attach_dense_relevance(self, rel):
+        """attach the relevance matrix [N x O] (dense.relevance_matrix: DT1) to the batch uploaded last: a training step of a disc model
+        then takes the dense target (DT3-DT4), and `ndcg_rows` ranks with it.  The library validates it and refuses by name."""
+        a = np.ascontiguousarray(rel, dtype=np.float32)
+        call("vd_model_set_tensor", self.h, b"@dense_relevance", a.ctypes.data, a.size)
+
+    def ndcg_rows(self):
+        """NDCG [N] (float64) of the scores of the last forward / retrieval of the current batch under its attached relevance matrix
+        (ndcg_kernel; DT2): -1 = no relevant candidate, -2 = not annotated.  The call returns the kernel's doubles bit for bit in 2 N floats."""
+        out = np.empty(int(self._N), np.float64)
+        call("vd_model_get_tensor", self.h, b"@ndcg", 0, out.ctypes.data, 2 * out.size)
+        return out
+
+    def _ndcg_of_batch(self, batch, rel):
+        self.attach_dense_relevance(rel)
+        return self.ndcg_rows()
+
+    def _train_batch(self, dataloader):
+        """the next training batch: params denseAnnotations (a file of dense annotations) draws annotated dialogs with their matrix"""
+        path = self.params.get('denseAnnotations')
+        if not path:
+            return dataloader.getTrainBatch(self.params)
+        if getattr(self, '_dense', None) is None or self._dense[0] != path:
+            from .dense import load_dense_annotations
+            self._dense = (path, load_dense_annotations(path))
+        return dataloader.getDenseTrainBatch(self.params, self._dense[1])
 
     def forwardBackward(self, batch=None, onlyForward=False, deferLoss=False):
         if batch is not None:
@@ -317,11 +355,11 @@ class NativeModel(SplitEval):
             if self._next_batch is not None and self._next_src is dataloader:
                 self.upload(self._next_batch)
             else:
-                self.upload(dataloader.getTrainBatch(self.params))
+                self.upload(self._train_batch(dataloader))
         numTokens = self._numTokens                             # of the batch this step trains on
         call("vd_model_forward_backward", self.h, 0)
         self.update()
-        self._next_batch, self._next_src = dataloader.getTrainBatch(self.params), dataloader
+        self._next_batch, self._next_src = self._train_batch(dataloader), dataloader
         self.upload(self._next_batch)                           # prefetch: the second slot, on the copy stream
         self._keep = dataloader                                 # (upload() clears it: set AFTER the prefetch)
         curLoss = self.loss()

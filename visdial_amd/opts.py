@@ -58,6 +58,20 @@ def derive(opt):
     return opt
 
 
+def check_dense(opt):
+    """what -denseAnnotations cannot be combined with, refused by name before any model exists (the library refuses the same: loss.hip DT5)"""
+    if not opt.get('denseAnnotations'):
+        return
+    if opt.get('decoder') != 'disc':
+        raise ValueError("-denseAnnotations with -decoder %s: the dense target trains the option scores of decoder 'disc'" % opt.get('decoder'))
+    if float(opt.get('labelSmoothing') or 0.0) > 0.0:
+        raise ValueError("-denseAnnotations with -labelSmoothing %r: a dense target is not smoothed; train with -labelSmoothing 0"
+                         % (opt.get('labelSmoothing'),))
+    mix = float(opt.get('denseMix') or 0.0)
+    if not 0.0 <= mix <= 1.0:
+        raise ValueError("-denseMix %r must be a finite real in [0, 1] (0 = rounds without an annotation do not train)" % (opt.get('denseMix'),))
+
+
 def default_params(**overrides):
     opt = {k: v for k, v, _ in OPTIONS}
     # sizes the reference copies from the dataloader (train.lua:55-59)
@@ -87,6 +101,13 @@ def parse(argv=None):
                     help='(training only, -host native) clip the whole gradient to this L2 norm in front of the element clamp at +-5 (a finite real >= 0)')
     ap.add_argument('-weightDecay', '--weightDecay', type=float, default=0.0,
                     help='(training only, -host native) decoupled weight decay lambda: w -= lr * lambda * w beside the Adam step (a finite real >= 0)')
+    # dense-annotation fine-tuning (-host native, decoder disc; csrc/loss.hip DT1-DT5)
+    ap.add_argument('-denseAnnotations', '--denseAnnotations', default='',
+                    help='(training only, -host native, decoder disc) a file of dense relevance annotations of train dialogs: train on batches of '
+                         'annotated dialogs with the normalised relevance as the target of the annotated round')
+    ap.add_argument('-denseMix', '--denseMix', type=float, default=0.0,
+                    help='(with -denseAnnotations) weight mu in [0, 1] of the rounds without an annotation, which keep their one-hot target '
+                         '(0 = they do not train)')
     opt = vars(ap.parse_args(argv))
     # refused by name before any model exists (the library refuses the same values: csrc/rt_switches.h)
     # (eps is applied in fp32, as in the library: a value that rounds to 1.0f is not below 1)
@@ -95,6 +116,12 @@ def parse(argv=None):
     for k in ('gradClipNorm', 'weightDecay'):
         if not 0.0 <= opt[k] < float('inf'):
             ap.error('-%s %r must be a finite real >= 0 (0 = off)' % (k, opt[k]))
+    if not 0.0 <= opt['denseMix'] <= 1.0:
+        ap.error('-denseMix %r must be a finite real in [0, 1] (0 = rounds without an annotation do not train)' % (opt['denseMix'],))
+    try:
+        check_dense(dict(opt, decoder='disc') if opt['loadPath'] else opt)   # (-loadPath: the decoder is the checkpoint's; train.py checks again)
+    except ValueError as e:
+        ap.error(str(e))
     opt.update(maxQuesCount=10, maxQuesLen=20, maxAnsLen=20, numOptions=100)
     if opt['savePath'] == 'checkpoints/':
         t = time.localtime()

@@ -355,6 +355,38 @@ class SplitEval(object):
     rolloutRows = (0, 0)         # params rollout: (history rows that differ from the ground truth's, history rows) of the last retrieve / predict
     rolloutCut = 0               # params rolloutHistory = 'concat': the generated history rows CH4 cut, of the last retrieve / predict
 
+    # dense annotations ({(image_id, round_id): relevance}, dense.load_dense_annotations) a host was given: retrieve / predict then also
+    # compute the NDCG of every annotated round from the final scores of its batch (csrc/loss.hip DT2) and leave it in `ndcgRows`
+    # [dialogs x R] (-1: no relevant candidate, -2: not annotated); None = no NDCG, every printed number and record as ever
+    denseAnnotations = None
+    ndcgRows = None
+
+    def _ndcg_of_batch(self, batch, rel):
+        """NDCG [N] of the scores the last retrieval of `batch` left, on the host (dense.ndcg_rows); the native host overrides it with
+        the device kernel"""
+        from . import dense
+        s = self.scores
+        s = s.detach().cpu().numpy() if hasattr(s, 'detach') else np.asarray(s)
+        return dense.ndcg_rows(s.reshape(rel.shape), rel)
+
+    def _ndcg_report(self, dataloader, dtype, n, R):
+        """after the metrics: NDCG over the annotated rounds that have one, and the counts (none of it without denseAnnotations)"""
+        self.ndcgRows = None
+        if self.denseAnnotations is None:
+            return
+        from . import dense
+        rows = np.concatenate(self._ndcg).reshape(n, R) if self._ndcg else np.full((n, R), dense.NOT_ANNOTATED)
+        rounds = getattr(dataloader, dtype + '_num_rounds', None)
+        if rounds is not None:                                     # rounds that do not exist carry no annotation
+            rows[np.arange(R)[None, :] >= np.asarray(rounds).reshape(-1, 1)[:n]] = dense.NOT_ANNOTATED
+        self.ndcgRows = rows
+        mean, annotated, left_out = dense.ndcg_mean(rows)
+        ids = set(int(i) for i in (getattr(dataloader, 'unique_img_' + dtype, None) or []))
+        outside = sum(1 for (iid, _) in self.denseAnnotations if iid not in ids)
+        print('NDCG: %.6f\t(%d annotated rounds in %s, %d of them without a relevant candidate left out; %d annotations of images outside '
+              'the split)' % (mean, annotated, dtype, left_out, outside))
+        self.ndcg = dict(ndcg=mean, annotated=annotated, left_out=left_out, outside=outside)
+
     def _rollout(self):
         """params rollout (0 / 1) of retrieve / predict, refusing what cannot be ranked on a rollout"""
         rollout = int(self.params.get('rollout', 0) or 0)
@@ -458,6 +490,11 @@ class SplitEval(object):
             ex, tot = self.option_rows()
             tally[0] += ex
             tally[1] += tot
+        if self.denseAnnotations is not None:                  # NDCG reads the final scores only: any decoder, head, cache or rollout
+            from . import dense
+            rel = dense.relevance_matrix(self._image_ids, self.denseAnnotations, batch['ques_fwd'].shape[1],
+                                         int(self.params.get('numOptions', 100)))
+            self._ndcg.append(np.asarray(self._ndcg_of_batch(batch, rel), np.float64))
         if rollout and self.params.get('useGt'):
             ranks = ranks[np.arange(ranks.shape[0]), np.asarray(batch['answer_ind']).reshape(-1) - 1]
         return ranks
@@ -507,6 +544,11 @@ class SplitEval(object):
                 for j in range(nr):
                     r = ranks[i, j]
                     out.append({'image_id': iid, 'round_id': j + 1, 'ranks': r.tolist() if np.ndim(r) else float(r)})
+            if self.ndcgRows is not None:                            # the records of annotated rounds gain their NDCG (-1: none, DT2)
+                for rec in out[-(1 if last_round_only else nr):] if nr else []:
+                    v = float(self.ndcgRows[i, rec['round_id'] - 1])
+                    if v != -2.0:
+                        rec['ndcg'] = v
         return out
 
     def retrieve(self, dataloader, dtype):
@@ -519,8 +561,10 @@ class SplitEval(object):
         O = int(self.params.get('numOptions', 100))
         ranks = np.full((n, R), O + 1.0)                               # model.lua:153-154
         start, tally, rollout = 1, [0, 0], self._rollout()
+        self._ndcg = []
         while start <= n:
             batch, nxt = self._test_batch(dataloader, start, dtype, rollout)
+            self._image_ids = (getattr(dataloader, 'unique_img_' + dtype, None) or list(range(1, n + 1)))[start - 1:nxt - 1]
             ranks[start - 1:nxt - 1] = self._ranked(batch, tally, rollout).reshape(-1, R)
             start = nxt
         self.optionCacheRows = tuple(tally[:2])
@@ -529,6 +573,7 @@ class SplitEval(object):
         self.rolloutCut = (tally + [0] * 9)[8]
         print('\n%s - Retrieval:' % dtype)
         metrics = utils.processRanks(ranks)
+        self._ndcg_report(dataloader, dtype, n, R)
         self._set_training(True)
         return metrics, self._rank_records(dataloader, dtype, ranks, False)
 
@@ -541,14 +586,17 @@ class SplitEval(object):
         O = int(self.params.get('numOptions', 100))
         ranks = np.full((n, R, O), O + 1.0)
         start, tally, rollout = 1, [0, 0], self._rollout()
+        self._ndcg = []
         while start <= n:
             batch, nxt = self._test_batch(dataloader, start, dtype, rollout)
+            self._image_ids = (getattr(dataloader, 'unique_img_' + dtype, None) or list(range(1, n + 1)))[start - 1:nxt - 1]
             ranks[start - 1:nxt - 1] = self._ranked(batch, tally, rollout).reshape(-1, R, O)
             start = nxt
         self.optionCacheRows = tuple(tally[:2])
         self.lhoodTreeStats = dict(zip(('nodes', 'live', 'executed', 'total'), (tally + [0] * 4)[2:6]))
         self.rolloutRows = tuple((tally + [0] * 6)[6:8])
         self.rolloutCut = (tally + [0] * 9)[8]
+        self._ndcg_report(dataloader, dtype, n, R)
         self._set_training(True)
         return self._rank_records(dataloader, dtype, ranks, dtype == 'test')
 
