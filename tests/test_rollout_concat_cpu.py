@@ -181,7 +181,8 @@ def test_the_host_loop_concatenates_its_own_picks(loader):
                 cand = rollout_candidate_row(batch['options'][n, rollout_pick(mine)])
                 want[i, r + 1] = rollout_concat_row(want[i, r], batch['ques_fwd'][i, r], cand, END, 0)
     assert np.array_equal(batch['hist'], want) and (want != truth).any(2).sum() >= 1
-    assert np.array_equal(host.rollout_history(dict(batch, hist=truth), ranks), want) and host._cut == [False] * 18
+    cut = []
+    assert np.array_equal(host.rollout_history(dict(batch, hist=truth), ranks, cut), want) and cut == [False] * 18
     # retrieve(): the tally of differing and cut rows; at W = 40 rows are cut
     host = StubHost(dict(p, decoder='disc', batchSize=3, rollout=1, rolloutHistory='concat', rolloutConcatEnd=END))
     host.retrieve(dl, 'val')
@@ -204,8 +205,9 @@ def test_the_cut_is_counted(loader):
     batch.pop('hist_gt')
     batch['hist'] = np.ascontiguousarray(batch['hist'][:, :, -40:])
     ranks = host.retrieve_rollout_batch(batch)
-    hist = host.rollout_history(batch, ranks)
-    assert np.array_equal(hist, batch['hist']) and sum(host._cut) >= 20 and ((hist[:, -1] != 0).sum(1) == 40).all()
+    cut = []
+    hist = host.rollout_history(batch, ranks, cut)
+    assert np.array_equal(hist, batch['hist']) and sum(cut) >= 20 and ((hist[:, -1] != 0).sum(1) == 40).all()
     assert any(np.array_equal(hist[i, 9], hist[i, 8]) for i in range(4))                                   # a full row repeats itself
 
 

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .split_eval import SplitEval
+from .split_eval import SplitEval, rollout_answered_history
 
 call = _lib.call
 
@@ -378,6 +378,10 @@ class NativeModel(SplitEval):
         if useGt is None:
             useGt = bool(self.params.get('useGt', True))
         self.upload(batch)
+        return self._retrieved_ranks(useGt)
+
+    def _retrieved_ranks(self, useGt):
+        """retrieve the batch in the slot through the configured head; the ground-truth ranks [N] (useGt) or all ranks [N x O]"""
         # params fusedLhood: the generative decoder's candidates through the live-row log-likelihood head (a disc model: argument error);
         # a model created with fusedLhood = 2 scores them over the prefix tree behind the same call
         call("vd_model_retrieve_lhood" if int(self.params.get('fusedLhood', 0) or 0) else "vd_model_retrieve", self.h)
@@ -401,7 +405,6 @@ class NativeModel(SplitEval):
                              "rollout takes its history rule when the model is created (params rolloutConcatEnd of NativeModel)"
                              % (self.params.get('rolloutHistory', 'row'), self._concat_end(), self._knobs['rolloutConcatEnd']))
         self.upload(batch)
-        N, O = self._N, int(self.params.get('numOptions', 100))
         if gen:
             beam = self.params.get('rolloutBeam')
             if not beam:
@@ -409,26 +412,13 @@ class NativeModel(SplitEval):
             call("vd_model_encode", self.h)
             self._rollout_answers = (self._gen_beam(beam['beamSize'], beam['beamLen'], beam['startToken'], beam['endToken'])[0],
                                      int(beam['endToken']))
-        call("vd_model_retrieve_lhood" if int(self.params.get('fusedLhood', 0) or 0) else "vd_model_retrieve", self.h)
-        out = np.empty((N, O), np.int32)
-        call("vd_model_ranks", self.h, 0, out.ctypes.data)
-        return out
+        return self._retrieved_ranks(False)
 
-    def rollout_history(self, batch, ranks):
+    def rollout_history(self, batch, ranks, cut=None):
         if getattr(self, '_rollout_answers', None) is None:
-            return SplitEval.rollout_history(self, batch, ranks)
-        from .split_eval import rollout_concat_row, rollout_history_row
-        tokens, end = self._rollout_answers                       # decoder gen: the beam search's answers (R2 / R3)
-        B, R, Th = batch['hist'].shape
-        hist = np.array(batch['hist'])
-        concat, self._cut = self._concat_end(), []
-        for i in range(B):
-            for r in range(R - 1):
-                if concat:                                        # CH1 - CH4
-                    hist[i, r + 1] = rollout_concat_row(hist[i, r], batch['ques_fwd'][i, r], tokens[i * R + r], concat, end, self._cut)
-                else:
-                    hist[i, r + 1] = rollout_history_row(batch['ques_fwd'][i, r], tokens[i * R + r], Th, end)
-        return hist
+            return SplitEval.rollout_history(self, batch, ranks, cut)
+        tokens, end = self._rollout_answers                       # decoder gen: the beam search's answers (R2 / R3; CH1 - CH4)
+        return rollout_answered_history(batch, tokens, end, self._concat_end(), cut)
 
     # Model:evaluate / retrieve / predict (model.lua:109-246): visdial_amd/split_eval.py, shared with the Python host
     def _set_training(self, on):

@@ -15,7 +15,9 @@ beamLengthPenalty): `_beam_constraints(minLen, noRepeat, lengthPenalty)` raises 
 Rollout (params rollout = 1): `_beam_rollout(rollout)` raises unless that `_gen_beam` feeds every round's answer into the next round's
 history on the device, R1-R6 below.  Ranking on a rollout (params rollout = 1 of retrieve / predict; evaluate.py -rollout 1): E1-E5 below
 and `retrieve_rollout_batch`, over the host's own `retrieveBatch`; a host with a device rollout overrides it."""
+import collections
 import math
+import types
 
 import numpy as np
 
@@ -74,6 +76,14 @@ def check_beam_constraints(beamSize, beamLen, minLen, noRepeat, lengthPenalty, v
     if (minLen > 0 or noRepeat > 0) and vocabSize is not None and vocabSize < beamSize + beamLen - 1:
         raise ValueError('beamMinLen = %d / beamNoRepeat = %d need vocabSize = %d >= beamSize + beamLen - 1 = %d, so that a row never '
                          'runs out of unbanned words' % (minLen, noRepeat, vocabSize, beamSize + beamLen - 1))
+
+
+def check_rollout(value):
+    """params rollout as 0 / 1 (None = 0), for generateAnswers and for retrieve / predict"""
+    rollout = int(value or 0)
+    if rollout not in (0, 1):
+        raise ValueError('rollout = %r must be 0 or 1' % (value,))
+    return rollout
 
 
 def beam_banned(column, step, minLen, noRepeat, endToken):
@@ -250,15 +260,27 @@ def rollout_picked_history(batch, picks, concat=False, endToken=None, cut=None):
     """E1 / E4: the history [B x R x Th] of `batch` (ques_fwd [B x R x Tq], hist [B x R x Th], options [B * R x O x To]) when round r of
     every dialog was answered with candidate picks[dialog * R + r]: row 0 is the batch's, rows >= 1 are rebuilt.  concat: by CH1 - CH4 with
     <END> = endToken instead of E4 (`cut` as `rollout_concat_row`)"""
+    answers = [rollout_candidate_row(batch['options'][n, int(pick)]) for n, pick in enumerate(picks)]
+    return rollout_answered_history(batch, answers, 0, endToken if concat else 0, cut)
+
+
+def rollout_next_row(prev_row, ques_row, answer_row, Th, answerEnd, concatEnd=0, cut=None):
+    """the one step of every rollout: the history row [Th] that follows `prev_row` after a round with question row `ques_row` and answer
+    token row `answer_row`, whose words end at the first `answerEnd` or 0 (<END> for a beam answer, 0 for a `rollout_candidate_row`).
+    concatEnd = 0: R2 / E4, one row per round (`prev_row` is not read); concatEnd = the <END> id: CH2 - CH4, `cut` as `rollout_concat_row`"""
+    if concatEnd:
+        return rollout_concat_row(prev_row, ques_row, answer_row, concatEnd, answerEnd, cut)
+    return rollout_history_row(ques_row, answer_row, Th, answerEnd)
+
+
+def rollout_answered_history(batch, answers, answerEnd, concatEnd=0, cut=None):
+    """the history [B x R x Th] of `batch` (ques_fwd [B x R x Tq], hist [B x R x Th]) when round r of every dialog was answered with the
+    token row answers[dialog * R + r]: row 0 is the batch's, rows >= 1 are rebuilt by `rollout_next_row`"""
     B, R, Th = batch['hist'].shape
     hist = np.array(batch['hist'])
     for i in range(B):
         for r in range(R - 1):
-            cand = rollout_candidate_row(batch['options'][i * R + r, int(picks[i * R + r])])
-            if concat:
-                hist[i, r + 1] = rollout_concat_row(hist[i, r], batch['ques_fwd'][i, r], cand, endToken, 0, cut)
-            else:
-                hist[i, r + 1] = rollout_history_row(batch['ques_fwd'][i, r], cand, Th, 0)
+            hist[i, r + 1] = rollout_next_row(hist[i, r], batch['ques_fwd'][i, r], answers[i * R + r], Th, answerEnd, concatEnd, cut)
     return hist
 
 
@@ -369,13 +391,15 @@ class SplitEval(object):
         s = s.detach().cpu().numpy() if hasattr(s, 'detach') else np.asarray(s)
         return dense.ndcg_rows(s.reshape(rel.shape), rel)
 
-    def _ndcg_report(self, dataloader, dtype, n, R):
-        """after the metrics: NDCG over the annotated rounds that have one, and the counts (none of it without denseAnnotations)"""
+    def _ndcg_report(self, dataloader, dtype, ranks, ndcg):
+        """after the metrics: NDCG over the annotated rounds that have one, and the counts (none of it without denseAnnotations); `ndcg`:
+        the NDCG rows of the batches of `_rank_split`, `ranks` what it returned"""
         self.ndcgRows = None
         if self.denseAnnotations is None:
             return
         from . import dense
-        rows = np.concatenate(self._ndcg).reshape(n, R) if self._ndcg else np.full((n, R), dense.NOT_ANNOTATED)
+        n, R = ranks.shape[:2]
+        rows = np.concatenate(ndcg).reshape(n, R) if ndcg else np.full((n, R), dense.NOT_ANNOTATED)
         rounds = getattr(dataloader, dtype + '_num_rounds', None)
         if rounds is not None:                                     # rounds that do not exist carry no annotation
             rows[np.arange(R)[None, :] >= np.asarray(rounds).reshape(-1, 1)[:n]] = dense.NOT_ANNOTATED
@@ -389,9 +413,7 @@ class SplitEval(object):
 
     def _rollout(self):
         """params rollout (0 / 1) of retrieve / predict, refusing what cannot be ranked on a rollout"""
-        rollout = int(self.params.get('rollout', 0) or 0)
-        if rollout not in (0, 1):
-            raise ValueError('rollout = %r must be 0 or 1' % (self.params.get('rollout'),))
+        rollout = check_rollout(self.params.get('rollout'))
         if rollout and int(self.params.get('optionCache', 0) or 0):
             raise ValueError('rollout = 1 with optionCache: a cached batch carries only the candidates the cache did not hold, and the '
                              'rollout reads a picked candidate\'s tokens from the batch; combining the two is left for a follow-up')
@@ -447,10 +469,7 @@ class SplitEval(object):
             if r + 1 < R:
                 for i in range(B):
                     cand = rollout_candidate_row(batch['options'][i * R + r, rollout_pick(ranks[i * R + r])])
-                    if end:
-                        batch['hist'][i, r + 1] = rollout_concat_row(batch['hist'][i, r], batch['ques_fwd'][i, r], cand, end, 0)
-                    else:
-                        batch['hist'][i, r + 1] = rollout_history_row(batch['ques_fwd'][i, r], cand, Th, 0)
+                    batch['hist'][i, r + 1] = rollout_next_row(batch['hist'][i, r], batch['ques_fwd'][i, r], cand, Th, 0, end)
         return out
 
     def _test_batch(self, dataloader, start, dtype, rollout):
@@ -464,46 +483,42 @@ class SplitEval(object):
             batch['hist_gt'] = np.array(batch['hist'])
         return batch, nxt
 
-    def _ranked(self, batch, tally, rollout=0):
-        """retrieveBatch + the tally of the answer-encoding cache (params optionCache; decoder disc).  rollout: `retrieve_rollout_batch`,
-        the ground-truth ranks taken from all ranks if params useGt, + the tally of the history rows that differ from the ground truth's"""
+    def _ranked(self, batch, tally, rollout, image_ids):
+        """retrieveBatch + the tally (a Counter: `update` ADDS) of the answer-encoding cache (params optionCache; decoder disc) and of the
+        prefix trees.  rollout: `retrieve_rollout_batch`, the ground-truth ranks taken from all ranks if params useGt, + the tally of the
+        history rows that differ from the ground truth's.  Returns (ranks, the NDCG [N] of the batch's rounds or None); `image_ids`: the
+        batch's dialogs"""
         if rollout:
             truth = batch.pop('hist_gt', None)
             ranks = np.asarray(self.retrieve_rollout_batch(batch))
             if truth is not None:
-                self._cut = []
-                hist = self.rollout_history(batch, ranks)
-                tally += [0] * (9 - len(tally))
-                tally[6] += int((hist != truth).any(2).sum())
-                tally[7] += hist.shape[0] * hist.shape[1]
-                tally[8] += int(sum(self._cut))                    # (`rollout_history` leaves CH4's cuts there)
+                cut = []
+                hist = self.rollout_history(batch, ranks, cut)
+                tally.update(differ=int((hist != truth).any(2).sum()), rows=hist.shape[0] * hist.shape[1], cut=int(sum(cut)))
         else:
             ranks = np.asarray(self.retrieveBatch(batch))
         if int(self.params.get('fusedLhood', 0) or 0) == 2:
             from . import prefix_tree
             st = prefix_tree.stats(batch['option_in'])
             ex, tot = self.option_rows()
-            tally += [0] * (6 - len(tally))
-            for i, v in enumerate((st['nodes'], st['live'], ex, tot)):
-                tally[2 + i] += v
+            tally.update(nodes=st['nodes'], live=st['live'], executed=ex, total=tot)
         if int(self.params.get('optionCache', 0) or 0):
             ex, tot = self.option_rows()
-            tally[0] += ex
-            tally[1] += tot
+            tally.update(cacheRan=ex, cacheRows=tot)
+        ndcg = None
         if self.denseAnnotations is not None:                  # NDCG reads the final scores only: any decoder, head, cache or rollout
             from . import dense
-            rel = dense.relevance_matrix(self._image_ids, self.denseAnnotations, batch['ques_fwd'].shape[1],
-                                         int(self.params.get('numOptions', 100)))
-            self._ndcg.append(np.asarray(self._ndcg_of_batch(batch, rel), np.float64))
+            rel = dense.relevance_matrix(image_ids, self.denseAnnotations, batch['ques_fwd'].shape[1], int(self.params.get('numOptions', 100)))
+            ndcg = np.asarray(self._ndcg_of_batch(batch, rel), np.float64)
         if rollout and self.params.get('useGt'):
             ranks = ranks[np.arange(ranks.shape[0]), np.asarray(batch['answer_ind']).reshape(-1) - 1]
-        return ranks
+        return ranks, ndcg
 
-    def rollout_history(self, batch, ranks):
-        """the history [B x R x Th] a rollout of `batch` generated, given the all ranks [N x O] it returned: rebuilt from the picks (E4)"""
+    def rollout_history(self, batch, ranks, cut=None):
+        """the history [B x R x Th] a rollout of `batch` generated, given the all ranks [N x O] it returned: rebuilt from the picks (E4);
+        `cut` (a list) gains one entry per rebuilt row of a concatenated history, as `rollout_concat_row`"""
         end = self._concat_end()
-        self._cut = []
-        return rollout_picked_history(batch, [rollout_pick(row) for row in ranks], bool(end), end, self._cut)
+        return rollout_picked_history(batch, [rollout_pick(row) for row in ranks], bool(end), end, cut)
 
     def evaluate(self, dataloader, dtype):
         """model.lua:109-139: validation loss / perplexity over a split: the sum over batches of `forwardBackward(batch, true)` (gen:
@@ -551,29 +566,37 @@ class SplitEval(object):
                         rec['ndcg'] = v
         return out
 
+    def _rank_split(self, dataloader, dtype):
+        """the batch walk of retrieve (params useGt: the ground truth's rank, [n x R]) and predict (every candidate's, [n x R x O]); leaves
+        the tallies of the walk in optionCacheRows / lhoodTreeStats / rolloutRows / rolloutCut.  Returns (ranks, the NDCG rows of the
+        batches for `_ndcg_report`)."""
+        n = dataloader.numThreads[dtype]
+        R = int(self.params['maxQuesCount'])
+        O = int(self.params.get('numOptions', 100))
+        ranks = np.full((n, R) if self.params['useGt'] else (n, R, O), O + 1.0)       # model.lua:153-154
+        start, tally, ndcg, rollout = 1, collections.Counter(), [], self._rollout()
+        image_ids = getattr(dataloader, 'unique_img_' + dtype, None) or list(range(1, n + 1))
+        while start <= n:
+            batch, nxt = self._test_batch(dataloader, start, dtype, rollout)
+            got, rows = self._ranked(batch, tally, rollout, image_ids[start - 1:nxt - 1])
+            ranks[start - 1:nxt - 1] = got.reshape((-1,) + ranks.shape[1:])
+            ndcg += [] if rows is None else [rows]
+            start = nxt
+        self.optionCacheRows = (tally['cacheRan'], tally['cacheRows'])
+        self.lhoodTreeStats = {key: tally[key] for key in ('nodes', 'live', 'executed', 'total')}
+        self.rolloutRows = (tally['differ'], tally['rows'])
+        self.rolloutCut = tally['cut']
+        return ranks, ndcg
+
     def retrieve(self, dataloader, dtype):
         """model.lua:142-189: ground-truth ranks + metrics.  params rollout = 1: the same on a history of the model's own answers
         (`retrieve_rollout_batch`, E1-E5 above); `rolloutRows` then counts the history rows that differ.  Returns (metrics, records)."""
         self._set_training(False)
         self.params['useGt'] = True
-        n = dataloader.numThreads[dtype]
-        R = int(self.params['maxQuesCount'])
-        O = int(self.params.get('numOptions', 100))
-        ranks = np.full((n, R), O + 1.0)                               # model.lua:153-154
-        start, tally, rollout = 1, [0, 0], self._rollout()
-        self._ndcg = []
-        while start <= n:
-            batch, nxt = self._test_batch(dataloader, start, dtype, rollout)
-            self._image_ids = (getattr(dataloader, 'unique_img_' + dtype, None) or list(range(1, n + 1)))[start - 1:nxt - 1]
-            ranks[start - 1:nxt - 1] = self._ranked(batch, tally, rollout).reshape(-1, R)
-            start = nxt
-        self.optionCacheRows = tuple(tally[:2])
-        self.lhoodTreeStats = dict(zip(('nodes', 'live', 'executed', 'total'), (tally + [0] * 4)[2:6]))
-        self.rolloutRows = tuple((tally + [0] * 6)[6:8])
-        self.rolloutCut = (tally + [0] * 9)[8]
+        ranks, ndcg = self._rank_split(dataloader, dtype)
         print('\n%s - Retrieval:' % dtype)
         metrics = utils.processRanks(ranks)
-        self._ndcg_report(dataloader, dtype, n, R)
+        self._ndcg_report(dataloader, dtype, ranks, ndcg)
         self._set_training(True)
         return metrics, self._rank_records(dataloader, dtype, ranks, False)
 
@@ -581,22 +604,8 @@ class SplitEval(object):
         """model.lua:192-246: all 100 ranks per round (val: every existing round; test: the last round only); params rollout as retrieve"""
         self._set_training(False)
         self.params['useGt'] = False
-        n = dataloader.numThreads[dtype]
-        R = int(self.params['maxQuesCount'])
-        O = int(self.params.get('numOptions', 100))
-        ranks = np.full((n, R, O), O + 1.0)
-        start, tally, rollout = 1, [0, 0], self._rollout()
-        self._ndcg = []
-        while start <= n:
-            batch, nxt = self._test_batch(dataloader, start, dtype, rollout)
-            self._image_ids = (getattr(dataloader, 'unique_img_' + dtype, None) or list(range(1, n + 1)))[start - 1:nxt - 1]
-            ranks[start - 1:nxt - 1] = self._ranked(batch, tally, rollout).reshape(-1, R, O)
-            start = nxt
-        self.optionCacheRows = tuple(tally[:2])
-        self.lhoodTreeStats = dict(zip(('nodes', 'live', 'executed', 'total'), (tally + [0] * 4)[2:6]))
-        self.rolloutRows = tuple((tally + [0] * 6)[6:8])
-        self.rolloutCut = (tally + [0] * 9)[8]
-        self._ndcg_report(dataloader, dtype, n, R)
+        ranks, ndcg = self._rank_split(dataloader, dtype)
+        self._ndcg_report(dataloader, dtype, ranks, ndcg)
         self._set_training(True)
         return self._rank_records(dataloader, dtype, ranks, dtype == 'test')
 
@@ -637,10 +646,9 @@ class SplitEval(object):
         R, Th = batch['ques_fwd'].shape[1], batch['hist'].shape[2]
         found = []
         for r in range(R):
-            if r > 0 and concat:
-                batch['hist'][0, r] = rollout_concat_row(batch['hist'][0, r - 1], batch['ques_fwd'][0, r - 1], found[-1][0][0], endToken, endToken)
-            elif r > 0:
-                batch['hist'][0, r] = rollout_history_row(batch['ques_fwd'][0, r - 1], found[-1][0][0], Th, endToken)
+            if r > 0:
+                batch['hist'][0, r] = rollout_next_row(batch['hist'][0, r - 1], batch['ques_fwd'][0, r - 1], found[-1][0][0], Th, endToken,
+                                                       endToken if concat else 0)
             self._gen_encode(batch)
             found.append(search(r))
         return found
@@ -665,9 +673,30 @@ class SplitEval(object):
         round and dialog with beamBatch = 0; with beamBatch > 0 it needs a host whose device search rolls out (`_beam_rollout`).  An encoder
         without a history generates as with rollout = 0.
         Returns [{image_id, dialog: [{question, answer}...]}]."""
+        s = self._generation_settings(params or {})
+        s.startToken, s.endToken = dataloader.word2ind['<START>'], dataloader.word2ind['<END>']
+        s.numThreads = int(s.maxThreads or dataloader.numThreads[dtype])
+        ind2word = dataloader.ind2word
+        self._set_training(False)
+        img_ids = getattr(dataloader, 'unique_img_' + dtype, None)
+
+        def record(convId, questions, answers, groups=None):
+            """{image_id, dialog: [{question, answer}...]}: one question row and one answer row per round; with `groups` (per round,
+            the G groups' token rows) every entry also gets `answers`"""
+            rec = {'image_id': img_ids[convId - 1] if img_ids else int(convId),
+                   'dialog': [{'question': utils.idToWords(q, ind2word), 'answer': utils.idToWords(a, ind2word)}
+                              for q, a in zip(questions, answers)]}
+            for entry, rows in zip(rec['dialog'], [] if groups is None else groups):
+                entry['answers'] = [utils.idToWords(a, ind2word) for a in rows]
+            return rec
+        answerTable = (self._generate_chunks if s.chunk > 0 else self._generate_dialogs)(dataloader, dtype, s, record)
+        self._set_training(True)
+        return answerTable
+
+    def _generation_settings(self, params):
+        """the settings of generateAnswers from its params, refusing what cannot be generated before any device work"""
         if self.params['decoder'] == 'disc':
             raise SystemExit('Sampling/beam search only for generative model')
-        params = params or {}
         sampleWords = bool(params.get('sampleWords', 0) == 1)
         beamBatch = int(params.get('beamBatch', 0) or 0)
         if beamBatch > 0 and sampleWords:
@@ -698,9 +727,7 @@ class SplitEval(object):
             if sampleWords:
                 raise ValueError('beamMinLen / beamNoRepeat / beamLengthPenalty constrain beam search: sampling (sampleWords = 1) has none')
         minLen, noRepeat, lengthPenalty = int(minLen), int(noRepeat), float(lengthPenalty)
-        rollout = int(params.get('rollout', 0) or 0)
-        if rollout not in (0, 1):
-            raise ValueError('rollout = %r must be 0 or 1' % (params.get('rollout'),))
+        rollout = check_rollout(params.get('rollout'))
         if rollout and sampleWords:
             raise ValueError('rollout = 1 feeds the beam search\'s answers back: with sampling (sampleWords = 1) one divergent draw would '
                              'cascade over the rounds')
@@ -711,87 +738,74 @@ class SplitEval(object):
             self._beam_grouping(beamGroups, beamDiversity)
             self._beam_constraints(minLen, noRepeat, lengthPenalty)
             self._beam_rollout(rollout)
-        startToken, endToken = dataloader.word2ind['<START>'], dataloader.word2ind['<END>']
-        numThreads = int(params.get('maxThreads') or dataloader.numThreads[dtype])
-        rng = np.random.RandomState(int(params.get('seed', 1234)))
-        ind2word = dataloader.ind2word
+        return types.SimpleNamespace(
+            sampleWords=sampleWords, chunk=sampleBatch if sampleWords else beamBatch, temperature=temperature, topK=topK, topP=topP,
+            truncate=truncate, beamSize=beamSize, beamLen=beamLen, beamGroups=beamGroups, beamDiversity=beamDiversity, minLen=minLen,
+            noRepeat=noRepeat, lengthPenalty=lengthPenalty, rollout=rollout, maxThreads=params.get('maxThreads'),
+            seed=int(params.get('seed', 1234)))
+
+    def _generate_chunks(self, dataloader, dtype, s, record):
+        """generateAnswers, s.chunk dialogs at a time on the device: one `_gen_encode` + one `_gen_sample` / `_gen_beam` per chunk"""
+        rng = np.random.RandomState(s.seed)
         answerTable = []
-        self._set_training(False)
-        img_ids = getattr(dataloader, 'unique_img_' + dtype, None)
-
-        def record(convId, questions, answers, groups=None):
-            """{image_id, dialog: [{question, answer}...]}: one question row and one answer row per round; with `groups` (per round,
-            the G groups' token rows) every entry also gets `answers`"""
-            rec = {'image_id': img_ids[convId - 1] if img_ids else int(convId),
-                   'dialog': [{'question': utils.idToWords(q, ind2word), 'answer': utils.idToWords(a, ind2word)}
-                              for q, a in zip(questions, answers)]}
-            for entry, rows in zip(rec['dialog'], [] if groups is None else groups):
-                entry['answers'] = [utils.idToWords(a, ind2word) for a in rows]
-            return rec
-        chunk = sampleBatch if sampleWords else beamBatch
-        if chunk > 0:
-            for first in range(1, numThreads + 1, chunk):
-                convIds = np.arange(first, min(first + chunk, numThreads + 1))
-                batch = self.rollout_batch(dataloader, convIds, dtype) if rollout else dataloader.getIndexData(convIds, self.params, dtype)
-                B, R = len(convIds), batch['ques_fwd'].shape[1]
-                self._gen_encode(batch)
-                if sampleWords:
-                    u = rng.random_sample((B, beamLen, R))      # the per-dialog loop's draws: dialog, then step, then round
-                    tokens, _ = self._gen_sample(beamLen, startToken, endToken, temperature,
-                                                 u.transpose(1, 0, 2).reshape(beamLen, B * R))   # [step x row]
-                elif beamGroups > 1:                            # tokens [N x G x beamLen], scores [N x G]
-                    grouped, sc = self._gen_beam(beamSize, beamLen, startToken, endToken)
-                    tokens = [pick_answer(list(zip(t, s_)), endToken, lengthPenalty)[0] for t, s_ in zip(grouped, sc)]
-                    answerTable += [record(convId, batch['ques_fwd'][i], tokens[i * R:(i + 1) * R], grouped[i * R:(i + 1) * R])
-                                    for i, convId in enumerate(convIds)]
-                    continue
-                else:
-                    tokens, _ = self._gen_beam(beamSize, beamLen, startToken, endToken)
-                answerTable += [record(convId, batch['ques_fwd'][i], tokens[i * R:(i + 1) * R])    # row = dialog * R + round
-                                for i, convId in enumerate(convIds)]
-            self._set_training(True)
-            return answerTable
-        for convId in range(1, numThreads + 1):
-            if rollout:
-                batch = self.rollout_batch(dataloader, np.array([convId]), dtype)
+        for first in range(1, s.numThreads + 1, s.chunk):
+            convIds = np.arange(first, min(first + s.chunk, s.numThreads + 1))
+            batch = self.rollout_batch(dataloader, convIds, dtype) if s.rollout else dataloader.getIndexData(convIds, self.params, dtype)
+            B, R = len(convIds), batch['ques_fwd'].shape[1]
+            self._gen_encode(batch)
+            grouped = None
+            if s.sampleWords:
+                u = rng.random_sample((B, s.beamLen, R))        # the per-dialog loop's draws: dialog, then step, then round
+                tokens, _ = self._gen_sample(s.beamLen, s.startToken, s.endToken, s.temperature,
+                                             u.transpose(1, 0, 2).reshape(s.beamLen, B * R))     # [step x row]
             else:
-                batch = dataloader.getIndexData(np.array([convId]), self.params, dtype)
+                tokens, scores = self._gen_beam(s.beamSize, s.beamLen, s.startToken, s.endToken)
+                if s.beamGroups > 1:                            # tokens [N x G x beamLen], scores [N x G]
+                    grouped = tokens
+                    tokens = [pick_answer(list(zip(t, sc)), s.endToken, s.lengthPenalty)[0] for t, sc in zip(grouped, scores)]
+            answerTable += [record(convId, batch['ques_fwd'][i], tokens[i * R:(i + 1) * R],        # row = dialog * R + round
+                                   None if grouped is None else grouped[i * R:(i + 1) * R]) for i, convId in enumerate(convIds)]
+        return answerTable
+
+    def _generate_dialogs(self, dataloader, dtype, s, record):
+        """generateAnswers one dialog at a time, as the reference drives it from the host"""
+        rng = np.random.RandomState(s.seed)
+
+        def search(it):
+            """the beam search of round `it` of the dialog encoded last: its groups' (tokens, score)"""
+            self._gen_begin(np.full(s.beamSize, it, np.int32))                    # hiddenBeams, model.lua:478-503
+            return beam_search_round(self._gen_step, self._gen_select, s.beamSize, s.beamLen, s.startToken, s.endToken, s.beamGroups,
+                                     s.beamDiversity, s.minLen, s.noRepeat, s.lengthPenalty)
+        answerTable = []
+        for convId in range(1, s.numThreads + 1):
+            convIds = np.array([convId])
+            batch = self.rollout_batch(dataloader, convIds, dtype) if s.rollout else dataloader.getIndexData(convIds, self.params, dtype)
             R = batch['ques_fwd'].shape[1]
-            answers, grouped = [], []
-            if rollout and 'hist' in batch:
-
-                def search(it):
-                    self._gen_begin(np.full(beamSize, it, np.int32))
-                    return beam_search_round(self._gen_step, self._gen_select, beamSize, beamLen, startToken, endToken, 1, beamDiversity,
-                                             minLen, noRepeat, lengthPenalty)
-                answers = [found[0][0] for found in self.rollout_dialog(batch, search, endToken)]
-                answerTable.append(record(convId, batch['ques_fwd'][0], answers))
-                continue
-            self._gen_encode(batch)                                               # forwardBackward(batch, true, true)
-            if not sampleWords:
-                for it in range(R):
-                    self._gen_begin(np.full(beamSize, it, np.int32))              # hiddenBeams, model.lua:478-503
-                    found = beam_search_round(self._gen_step, self._gen_select, beamSize, beamLen, startToken, endToken, beamGroups,
-                                              beamDiversity, minLen, noRepeat, lengthPenalty)
-                    answers.append(pick_answer(found, endToken, lengthPenalty)[0] if beamGroups > 1 else found[0][0])
-                    grouped.append([tokens for tokens, _ in found])
-            else:
-                numQues = R
+            grouped = None
+            if s.sampleWords:
+                self._gen_encode(batch)                                           # forwardBackward(batch, true, true)
                 self._gen_begin(np.arange(R, dtype=np.int32))
-                answerIn = np.full(numQues, startToken, np.int64)
+                answerIn = np.full(R, s.startToken, np.int64)
                 answer = [answerIn[:, None].copy()]
-                for timeStep in range(beamLen):
+                for timeStep in range(s.beamLen):
                     logp = self._gen_step(answerIn)
-                    self._gen_select(np.arange(numQues, dtype=np.int32), numQues)
-                    if truncate:
-                        pr = np.stack([truncated_weights(logp[i], temperature, topK, topP) for i in range(numQues)])
+                    self._gen_select(np.arange(R, dtype=np.int32), R)
+                    if s.truncate:
+                        pr = np.stack([truncated_weights(logp[i], s.temperature, s.topK, s.topP) for i in range(R)])
                     else:
-                        pr = np.exp(logp.astype(np.float64) / temperature)
+                        pr = np.exp(logp.astype(np.float64) / s.temperature)
                     pr /= pr.sum(1, keepdims=True)
-                    nxt = np.array([rng.choice(pr.shape[1], p=pr[i]) + 1 for i in range(numQues)], np.int64)
-                    answer.append(nxt[:, None])
-                    answerIn = nxt
+                    answerIn = np.array([rng.choice(pr.shape[1], p=pr[i]) + 1 for i in range(R)], np.int64)
+                    answer.append(answerIn[:, None])
                 answers = np.concatenate(answer, 1)
-            answerTable.append(record(convId, batch['ques_fwd'][0], answers, grouped if beamGroups > 1 else None))
-        self._set_training(True)
+            else:
+                if s.rollout and 'hist' in batch:                                 # (beamGroups = 1: a rollout refuses groups)
+                    found = self.rollout_dialog(batch, search, s.endToken)
+                else:
+                    self._gen_encode(batch)
+                    found = [search(it) for it in range(R)]
+                answers = [pick_answer(f, s.endToken, s.lengthPenalty)[0] if s.beamGroups > 1 else f[0][0] for f in found]
+                if s.beamGroups > 1:
+                    grouped = [[tokens for tokens, _ in f] for f in found]
+            answerTable.append(record(convId, batch['ques_fwd'][0], answers, grouped))
         return answerTable
