@@ -34,7 +34,11 @@ def f32(rng, *shape):
 
 
 # asymmetric operands everywhere (guide: symmetric inputs hide transposes)
-# (M >= 1024 with K % 16 == 0 runs on the LDS-DMA pipeline: 4 / 5 / 128 K tiles, partial row and column tiles)
+# Families (csrc/gemm_ops.hip vd_gemm_nt asks use_small -- fewer than 48 tiles of 128 x 128 -- first; restated in tests/gemm_cases.py):
+#   CfgSmall: (200, 512, 512) 8 tiles, (260, 300, 300) 9, (33, 40, 4) 1, (1, 512, 2048) 4, (1500, 300, 64) 36, (1025, 44, 80) 9
+#   LDS-DMA pipeline (M >= 1024, K >= 64, K % 16 == 0): (3920, 512, 512) 32 K tiles, partial row tile; (11323, 300, 2048) 128 K tiles,
+#     partial row and column tiles.  Its short loops of 4 / 5 / 6 K tiles are tests/test_gemm_ops_gpu.py's
+#   register-staged CfgBig: (5000, 2048, 300), K % 16 != 0
 @pytest.mark.parametrize("M,N,K", [(200, 512, 512), (3920, 512, 512), (260, 300, 300), (33, 40, 4), (1, 512, 2048),
                                    (1500, 300, 64), (1025, 44, 80), (11323, 300, 2048),
                                    (5000, 2048, 300)])
