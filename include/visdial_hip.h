@@ -437,7 +437,15 @@ int vd_model_init_params(vd_model* m, uint64_t seed);     /* library-default ini
  * negative value, a wrong n, and a call before any upload are argument errors that name the attachment.  The matrix is checked on the
  * host, staged in pinned memory and copied on the upload lane; the call waits for no step and does not empty the answer-encoding cache.
  * The next upload into the batch's slot drops it.  What it changes: vd_model_forward_backward(m, 0) of a disc model trains on it
- * (below), and vd_model_get_tensor "@ndcg" ranks with it.  Everything else ignores it. */
+ * (below), and vd_model_get_tensor "@ndcg" ranks with it.  Everything else ignores it.
+ * "@dense_relevance_live": the same matrix through the same checks, named by their own name; an attachment replaces the one before it on
+ * the same upload.  It asks in addition that the next TRAINING step run the option recurrence, its backward, the table-gradient row sum
+ * and the dWh contraction over the candidate rows of the LIVE rounds only -- the rounds whose weight (below) is > 0, in ascending order,
+ * one row per (live round, candidate); the encoder runs over all N rounds.  Loss and gradients are those of "@dense_relevance" up to fp32
+ * summation order (a round of weight 0 adds exact zeros).  After such a step vd_model_scores holds the live rounds' scores and 0.0 in
+ * every other round's row, and vd_model_option_rows reports (n_live * O, N * O).  With every round live it IS "@dense_relevance".
+ * only_forward = 1, retrieval and "@ndcg" see all rounds either way.  Refused by name: a model with lstmBf16 = 1 (rules DL1-DL5 at the
+ * top of csrc/loss.hip). */
 int vd_model_set_tensor(vd_model* m, const char* name, const float* host, int64_t n);   /* wrapperW:copy(...) */
 /* "@ndcg", which = 0, n = 2 N: runs the NDCG kernel on the scores of the last forward or retrieval of the current batch (either decoder)
  * and its "@dense_relevance"; `host` receives N DOUBLES, bit for bit, in the 2 N floats of the signature (read the buffer as double[N]).

@@ -46,7 +46,7 @@ def main():
         mp['gpuid'], mp['batchSize'] = opt['gpuid'], opt['batchSize']
         # run control and runtime (non-architectural) choices stay with the command line
         for k in ('numEpochs', 'maxIters', 'savePath', 'saveIter', 'host', 'lstmPrecision', 'saveFormat',
-                  'synthetic', 'labelSmoothing', 'gradClipNorm', 'weightDecay', 'denseAnnotations', 'denseMix'):
+                  'synthetic', 'labelSmoothing', 'gradClipNorm', 'weightDecay', 'denseAnnotations', 'denseMix', 'denseRows'):
             mp[k] = opt.get(k)
     if mp.get('host', 'python') != 'native':                     # -labelSmoothing / -gradClipNorm / -weightDecay need -host native
         try:
@@ -56,6 +56,7 @@ def main():
             raise SystemExit(str(e))
     try:
         opts.check_dense(mp)                                     # -denseAnnotations with decoder gen / -labelSmoothing: before any model exists
+        opts.check_dense_rows(mp)                                # -denseRows live without the annotations / with -lstmPrecision bf16
     except ValueError as e:
         raise SystemExit(str(e))
     # the dataloader is built from the CURRENT command line (train.lua:47-48), never from paths stored in a checkpoint
@@ -107,6 +108,9 @@ def main():
                 time.ctime(), it / float(opt['numIterPerEpoch']), it, model.runningLoss,
                 model.optims['learningRate'], rounds / (time.time() - t0)))
             t0 = time.time()
+    if (opt.get('denseRows') or 'all') == 'live' and total > 0:
+        executed, rows = model.option_rows()                         # of the last step: the live rounds' candidates
+        print('-denseRows live: the last step ran %d of %d candidate rows through the option recurrence' % (executed, rows))
     if opt.get('saveFormat', 't7') == 't7':                          # train.lua:120-121
         save_t7(os.path.join(opt['savePath'], 'model_final.t7'), model, _plain(opt))
     else:

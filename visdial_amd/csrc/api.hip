@@ -143,12 +143,15 @@ int vd_bf16_shadow_get(int /*slot*/, const float* base, size_t floats, vd_bf16_b
   return VD_OK;
 }
 
-const vd_bf16_bits* vd_bf16_shadow_find(const float* p, size_t floats) {
+// anchor (common.h): VD_SHADOW_AT_BASE = the range starts at the registered base, VD_SHADOW_AT_END = it ends at the registered end
+const vd_bf16_bits* vd_bf16_shadow_find(const float* p, size_t floats, int anchor) {
   std::lock_guard<std::mutex> lk(g_shadow_mu);
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return nullptr;
   for (const Bf16Shadow& s : g_shadow)
-    if (s.base && s.dev == dev && p >= s.base && p + floats <= s.base + s.floats) return s.buf + (p - s.base);
+    if (s.base && s.dev == dev && p >= s.base && p + floats <= s.base + s.floats &&
+        (anchor != VD_SHADOW_AT_BASE || p == s.base) && (anchor != VD_SHADOW_AT_END || p + floats == s.base + s.floats))
+      return s.buf + (p - s.base);
   return nullptr;
 }
 

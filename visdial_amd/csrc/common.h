@@ -117,9 +117,15 @@ int vd_segment_rowsum_acc_bf16(const vd_bf16_bits* X16, int64_t ldx, const int32
 // until an fp32 producer overwrites its range (vd_bf16_shadow_invalidate: the fp32 recurrences, a forward pass over the gates buffer,
 // vd_memset).  The registry is process-global and keyed by address only: VD_FLAG_BF16 on vd_gemm_tn_acc is meant for the contraction that
 // directly follows the bf16 recurrences of the same pass -- a host that writes those ranges by other means (its own kernels, a tensor
-// library) must not pass the flag afterwards.
+// library) must not pass the flag afterwards.  What the registry can do against an entry that outlived its tensor (a host that freed h / gates
+// to an allocator which hands the addresses out again) it does: vd_gemm_tn_acc takes the shadows only for the contraction the producers
+// leave behind -- A = h from its registered base, B = da from step 1 up to its registered end (`anchor` of vd_bf16_shadow_find) -- so an
+// unrelated pair of operands that merely lies inside two stale ranges is contracted from its fp32 rows.
+#define VD_SHADOW_ANYWHERE 0
+#define VD_SHADOW_AT_BASE 1
+#define VD_SHADOW_AT_END 2
 int vd_bf16_shadow_get(int slot, const float* base, size_t floats, vd_bf16_bits** out);
-const vd_bf16_bits* vd_bf16_shadow_find(const float* p, size_t floats);
+const vd_bf16_bits* vd_bf16_shadow_find(const float* p, size_t floats, int anchor = VD_SHADOW_ANYWHERE);
 void vd_bf16_shadow_invalidate(const float* p, size_t floats);
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

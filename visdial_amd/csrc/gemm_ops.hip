@@ -493,8 +493,9 @@ int vd_gemm_tn_acc(const float* A, int64_t lda, const float* B, int64_t ldb, flo
   if (flags & VD_FLAG_BF16) {   // opt-in reduced precision: bf16 operands, fp32 accumulation
     // both operands already exist as bf16 (shadows written by the LSTM step kernels of this pass): multiply them directly
     if (M % 128 == 0 && N % 128 == 0 && K >= 32 && lda == M && ldb == N && (long)32 * N * 2 + 256 < (1L << 31)) {
-      const vd_bf16_bits* a16 = vd_bf16_shadow_find(A, (size_t)K * M);
-      const vd_bf16_bits* b16 = vd_bf16_shadow_find(B, (size_t)K * N);
+      // (anchored: h from its registered base, da up to its registered end -- the dWh contraction of the pass that wrote them; common.h)
+      const vd_bf16_bits* a16 = vd_bf16_shadow_find(A, (size_t)K * M, VD_SHADOW_AT_BASE);
+      const vd_bf16_bits* b16 = vd_bf16_shadow_find(B, (size_t)K * N, VD_SHADOW_AT_END);
       if (a16 && b16) {
         const int K1 = K & ~31;     // whole 32-row K tiles; the last < 32 rows go through the staging kernel below
         if (int rc = launch_gemm_bf16_tn_tr(a16, b16, C, ldc, M, N, K1, (hipStream_t)stream)) return rc;

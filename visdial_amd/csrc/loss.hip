@@ -33,6 +33,22 @@
 //   DT5 the dense target applies to vd_model_forward_backward(m, 0) of a disc model only, as LS3: only_forward = 1, retrieval, scores and
 //       ranks ignore it; a batch without the matrix launches score_ce_kernel / score_ce_smooth_kernel with their arguments; a dense batch on
 //       a model created with VD_LABEL_SMOOTHING > 0 and a dense training step of a gen model are refused by name (gen accepts it for NDCG).
+//
+// Live rounds (vd_model_set_tensor "@dense_relevance_live": the same matrix, the same validation, and the candidate rows of the rounds that
+// train only).  visdial_amd/dense.py restates DL1 and the compaction (live_rounds, live_option_tokens):
+//   DL1 a round is live iff its DT3 weight w_n is > 0 under the model's mu: annotated with sum rel > 0, or not annotated with mu > 0.  The live
+//       rounds are taken in ascending round order (live_idx [n_live]; live_slot [N] = the place of round n in it, or -1), candidate order kept.
+//   DL2 if every round is live the attachment IS "@dense_relevance": the same kernels with the same arguments, nothing extra.  W = 0 is refused
+//       at the step as before.
+//   DL3 otherwise vd_model_forward_backward(m, 0) runs the option recurrence, its backward, the table-gradient row sum and the dWh contraction
+//       over the n_live * O candidate rows of the live rounds (dense_live_tokens_kernel compacts their tokens at attach time, resolving a
+//       de-duplicated upload's opt_uid: one row per (live round, candidate)); the encoder runs over all N rounds.  Loss, loss_div and every
+//       gradient are those of the all-rows dense step up to fp32 summation order: a round of weight 0 adds exact zeros to each of them.
+//       score_ce_dense_live_kernel writes the live rounds' scores; every other round's score row, loss_rows entry and d_enc row is 0.
+//   DL4 only_forward = 1, retrieval and "@ndcg" ignore the live set (DT5): they see all rounds.  After a live training step "@ndcg" is still
+//       right for every row that has an NDCG: k > 0 <=> w = 1 <=> live.
+//   DL5 refused by name, before anything is enqueued: a model with lstmBf16 = 1 (the compact-state path is not covered), a gen model's
+//       training step and VD_LABEL_SMOOTHING > 0 (both with DT5's words).  Candidates that repeat among the live rows are not de-duplicated.
 #include "common.h"
 
 #define MAX_OPT 128
@@ -42,17 +58,20 @@
 //   if train: ds = (softmax - onehot) * gscale ; dOptH[n,o,:] = ds[o]*enc[n,:] ; dEnc[n,:] = sum_o ds[o]*optH[n,o,:]
 //   TARGET_SMOOTH: onehot is LS1's target.  TARGET_DENSE: the target and the weight of DT3 from the round's row of `rel` (staged in LDS next
 //   to sc / ds); `smooth` is mu and gscale is 1 / W; a round of weight 0 writes its scores, loss 0 and zero gradients and reads optH once.
+//   Two row indices: enc, dEnc, scores, loss_rows, gt and rel are read and written at round n, optH / dOptH at the O rows of round-sized block
+//   `hn` (the three all-rows kernels pass n twice; the live head passes the round's slot among the live rounds: DL3).
 enum ScoreTarget { TARGET_ONEHOT, TARGET_SMOOTH, TARGET_DENSE };
 template <ScoreTarget TARGET>
 __device__ __forceinline__ void score_ce_body(const float* __restrict__ optH, const float* __restrict__ enc, const int* __restrict__ gt,
                                               float* __restrict__ scores, float* __restrict__ loss_rows, float* __restrict__ dOptH,
                                               float* __restrict__ dEnc, int O, int H, float gscale, float smooth,
-                                              const float* __restrict__ rel = nullptr, float* rl = nullptr, float* row_w = nullptr) {
+                                              const int n, const int hn, const float* __restrict__ rel = nullptr, float* rl = nullptr,
+                                              float* row_w = nullptr) {
   __shared__ float sc[MAX_OPT];
   __shared__ float ds[MAX_OPT];
-  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* e = enc + (long)n * H;
-  const float* oh = optH + (long)n * O * H;
+  const float* oh = optH + (long)hn * O * H;
   for (int o = wave; o < O; o += 4) {
     float a = 0.f;
     for (int k = lane * 4; k < H; k += 256) {
@@ -116,7 +135,7 @@ __device__ __forceinline__ void score_ce_body(const float* __restrict__ optH, co
     if (*row_w == 0.f) {   // DT3: the round does not train
       const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
       for (int k = tid * 4; k < H; k += 1024) {
-        for (int o = 0; o < O; ++o) *reinterpret_cast<float4*>(dOptH + ((long)n * O + o) * H + k) = z;
+        for (int o = 0; o < O; ++o) *reinterpret_cast<float4*>(dOptH + ((long)hn * O + o) * H + k) = z;
         *reinterpret_cast<float4*>(dEnc + (long)n * H + k) = z;
       }
       return;
@@ -132,7 +151,7 @@ __device__ __forceinline__ void score_ce_body(const float* __restrict__ optH, co
       acc.y += d * x.y;
       acc.z += d * x.z;
       acc.w += d * x.w;
-      *reinterpret_cast<float4*>(dOptH + ((long)n * O + o) * H + k) =
+      *reinterpret_cast<float4*>(dOptH + ((long)hn * O + o) * H + k) =
           make_float4(d * ev.x, d * ev.y, d * ev.z, d * ev.w);
     }
     *reinterpret_cast<float4*>(dEnc + (long)n * H + k) = acc;
@@ -142,13 +161,13 @@ __global__ void __launch_bounds__(256)
 score_ce_kernel(const float* __restrict__ optH, const float* __restrict__ enc, const int* __restrict__ gt,
                 float* __restrict__ scores, float* __restrict__ loss_rows, float* __restrict__ dOptH,
                 float* __restrict__ dEnc, int O, int H, float gscale) {
-  score_ce_body<TARGET_ONEHOT>(optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, 0.f);
+  score_ce_body<TARGET_ONEHOT>(optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, 0.f, blockIdx.x, blockIdx.x);
 }
 __global__ void __launch_bounds__(256)
 score_ce_smooth_kernel(const float* __restrict__ optH, const float* __restrict__ enc, const int* __restrict__ gt,
                        float* __restrict__ scores, float* __restrict__ loss_rows, float* __restrict__ dOptH,
                        float* __restrict__ dEnc, int O, int H, float gscale, float smooth) {
-  score_ce_body<TARGET_SMOOTH>(optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, smooth);
+  score_ce_body<TARGET_SMOOTH>(optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, smooth, blockIdx.x, blockIdx.x);
 }
 __global__ void __launch_bounds__(256)
 score_ce_dense_kernel(const float* __restrict__ optH, const float* __restrict__ enc, const int* __restrict__ gt,
@@ -156,7 +175,41 @@ score_ce_dense_kernel(const float* __restrict__ optH, const float* __restrict__ 
                       float* __restrict__ dEnc, int O, int H, float gscale, float mix, const float* __restrict__ rel) {
   __shared__ float rl[MAX_OPT];   // the round's relevance row, next to the body's sc[] / ds[]
   __shared__ float row_w;
-  score_ce_body<TARGET_DENSE>(optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, mix, rel, rl, &row_w);
+  score_ce_body<TARGET_DENSE>(optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, mix, blockIdx.x, blockIdx.x, rel, rl, &row_w);
+}
+// DL3: the dense head over all N rounds with optH / dOptH holding the live rounds' rows only, [n_live * O x H].  A round that is not live
+// (live_slot[n] < 0) writes its zero score row, loss 0 and its zero dEnc row and reads no optH.
+__global__ void __launch_bounds__(256)
+score_ce_dense_live_kernel(const float* __restrict__ optH, const float* __restrict__ enc, const int* __restrict__ gt,
+                           float* __restrict__ scores, float* __restrict__ loss_rows, float* __restrict__ dOptH,
+                           float* __restrict__ dEnc, int O, int H, float gscale, float mix, const float* __restrict__ rel,
+                           const int* __restrict__ live_slot) {
+  __shared__ float rl[MAX_OPT];
+  __shared__ float row_w;
+  const int n = blockIdx.x, tid = threadIdx.x, slot = live_slot[n];
+  if (slot < 0) {
+    if (tid < O) scores[(long)n * O + tid] = 0.f;
+    if (tid == 0) loss_rows[n] = 0.f;
+    if (dEnc != nullptr)
+      for (int k = tid * 4; k < H; k += 1024) *reinterpret_cast<float4*>(dEnc + (long)n * H + k) = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  score_ce_body<TARGET_DENSE>(optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, mix, n, slot, rel, rl, &row_w);
+}
+
+// DL3: the option tokens of the live rounds, step-major [To x n_live * O], from the uploaded step-major tok [To x rows]: output row
+// (slot, o) = the row of candidate (live_idx[slot], o), through uid [N * O] where the upload de-duplicated the candidates.  One thread per
+// output element; consecutive lanes write consecutive candidate rows of one step.
+__global__ void __launch_bounds__(256)
+dense_live_tokens_kernel(const int* __restrict__ tok, long rows, const int* __restrict__ uid, const int* __restrict__ live_idx, int O,
+                         long live_rows, long total, int* __restrict__ out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const long t = i / live_rows, r = i - t * live_rows;
+  const long slot = r / O, o = r - slot * O;
+  const long cand = (long)live_idx[slot] * O + o;
+  const long src = uid != nullptr ? (long)uid[cand] : cand;
+  out[i] = tok[t * rows + src];
 }
 
 // rank[n,o] = 1 + #{j : s[j] > s[o]  or (s[j] == s[o] and j < o)}   (descending sort position)
@@ -385,6 +438,34 @@ int vd_score_ce_dense_p(const float* optH, const float* enc, const int32_t* gt, 
   if (N == 0) return VD_OK;
   hipLaunchKernelGGL(score_ce_dense_kernel, dim3(N), dim3(256), 0, stream, optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, mix,
                      rel);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+// internal (rt_core.h): the dense head of a live step (DL3): optH / dOptH [n_live * O x H] hold the rows of the live rounds in live order,
+// live_slot [N] (device) = a round's place among them or -1; everything else as vd_score_ce_dense_p, which live_slot[n] = n reproduces
+int vd_score_ce_dense_live_p(const float* optH, const float* enc, const int32_t* gt, const float* rel, const int32_t* live_slot, float* scores,
+                             float* loss_rows, float* dOptH, float* dEnc, int N, int O, int H, float gscale, float mix, hipStream_t stream) {
+  VD_CHECK_ARG(optH && enc && scores && gt && rel && live_slot && loss_rows && N >= 0 && O >= 1 && O <= MAX_OPT && H % 4 == 0,
+               "vd_score_ce_dense_live_p: bad args (O=%d must be <= %d; the live dense head needs gt, rel, live_slot and loss_rows)", O, MAX_OPT);
+  VD_CHECK_ARG((dOptH == nullptr) == (dEnc == nullptr), "vd_score_ce_dense_live_p: dOptH and dEnc go together");
+  VD_CHECK_ARG(mix >= 0.f && mix <= 1.f, "vd_score_ce_dense_live_p: the mix %g is not in [0, 1]", (double)mix);
+  if (N == 0) return VD_OK;
+  hipLaunchKernelGGL(score_ce_dense_live_kernel, dim3(N), dim3(256), 0, stream, optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale,
+                     mix, rel, live_slot);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+// internal (rt_core.h): DL3's token compaction: out [To x n_live * O] from tok [To x rows], uid [N * O] or null, live_idx [n_live] (device)
+int vd_dense_live_tokens_p(const int32_t* tok, int64_t rows, int To, const int32_t* uid, const int32_t* live_idx, int n_live, int O,
+                           int32_t* out, hipStream_t stream) {
+  VD_CHECK_ARG(tok && live_idx && out && rows >= 1 && To >= 1 && n_live >= 0 && O >= 1, "vd_dense_live_tokens_p: bad args");
+  const long live_rows = (long)n_live * O, total = (long)To * live_rows;
+  VD_CHECK_ARG((total + 255) / 256 <= 0x7fffffffL, "vd_dense_live_tokens_p: %ld elements are more than one launch covers", total);
+  if (total == 0) return VD_OK;
+  hipLaunchKernelGGL(dense_live_tokens_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, tok, (long)rows, uid, live_idx, O,
+                     live_rows, total, out);
   VD_LAUNCH_CHECK();
   return VD_OK;
 }

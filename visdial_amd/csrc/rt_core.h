@@ -126,6 +126,14 @@ int vd_logsoftmax_nll_p(float* logits, int64_t ld, int64_t rows, int V, const in
 int vd_score_ce_dense_p(const float* optH, const float* enc, const int32_t* gt, const float* rel, float* scores, float* loss_rows,
                         float* dOptH, float* dEnc, int N, int O, int H, float gscale, float mix, hipStream_t stream);
 int vd_ndcg_p(const float* scores, const float* rel, double* ndcg, int N, int O, hipStream_t stream);
+// loss.hip: a live dense step (DL1 - DL5 there).  vd_dense_live_tokens_p: the option tokens of the live rounds, out [To x n_live * O] from
+// the uploaded tok [To x rows], through uid [N * O] where the upload de-duplicated (or null); live_idx [n_live] ascending, on the device.
+// vd_score_ce_dense_live_p: vd_score_ce_dense_p over all N rounds with optH / dOptH [n_live * O x H] holding the live rounds' rows;
+// live_slot [N] (device) = a round's place among the live rounds or -1, whose scores, loss and dEnc row come back 0.
+int vd_dense_live_tokens_p(const int32_t* tok, int64_t rows, int To, const int32_t* uid, const int32_t* live_idx, int n_live, int O,
+                           int32_t* out, hipStream_t stream);
+int vd_score_ce_dense_live_p(const float* optH, const float* enc, const int32_t* gt, const float* rel, const int32_t* live_slot, float* scores,
+                             float* loss_rows, float* dOptH, float* dEnc, int N, int O, int H, float gscale, float mix, hipStream_t stream);
 // elementwise.hip: the update with a global-norm clip and decoupled weight decay (VD_GRAD_CLIP_NORM / VD_WEIGHT_DECAY; GC1 - GC3, WD1
 // there).  vd_grad_clip_scale_p: work[0] = c / || gscale g ||_2 where that norm is finite and > c > 0, else 1; work[1] = the norm; two
 // launches on `stream`, no atomic, no host read, the same bits on every run; work holds vd_clip_work_floats() floats.
@@ -199,6 +207,11 @@ struct BatchSlot {
   // upload into the slot clears it.  rel_W = the sum of DT3's weights over the batch with the model's mu
   float* rel = nullptr;
   double rel_W = 0.0;
+  // "@dense_relevance_live" (loss.hip DL1 - DL3) where some but not all rounds are live: the live rounds' option tokens, compacted and
+  // sorted behind the attachment on the side lane.  opt_live.N = n_live * O rows; live_slot [N] on the device; n_live = 0: all rows
+  SeqTok opt_live;
+  int n_live = 0;
+  int32_t *live_slot = nullptr, *live_sort_off = nullptr, *live_sort_perm = nullptr;
   // option de-duplication (decoder disc): the option LSTM encodes every DISTINCT candidate once (decoders/disc.lua:4-15 --
   // the encoding depends on the tokens only); opt_uid[n * O + o] = its row among the opt.N unique rows, or null
   int32_t* opt_uid = nullptr;
@@ -349,6 +362,7 @@ struct vd_model {
   // vd_model_option_rows after vd_model_retrieve_lhood: (step, candidate) rows in a row group the candidate recurrence ran, of To * N * O;
   // -1 = the last step call was another one
   long lhood_exec = -1, lhood_total = 0;
+  bool step_live = false;   // the last step call ran the live rounds' candidate rows only (DL3): vd_model_option_rows reports them
   // capability flags from the encoder NAME (opts.lua:54-67)
   bool use_im = false, use_hist = false, is_att = false, is_graph = false;
   vdrt::OptionCache ocache;

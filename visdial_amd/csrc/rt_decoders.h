@@ -87,15 +87,16 @@ inline hipEvent_t* probe_events() {
 struct Disc : Decoder {
   void declare(vd_model* m) override { add_lstm(m, "opt", m->p.embedSize, m->p.rnnHiddenSize); }
   // The candidates' final states, on the main stream: the projection table, then ONE recurrence over the NO rows the upload kept (N * O, or
-  // the distinct candidates).  They depend on the option tokens and the weights only (decoders/disc.lua:4-15).
+  // the distinct candidates).  They depend on the option tokens and the weights only (decoders/disc.lua:4-15).  `opt` is the token set it
+  // runs: b.opt, or b.opt_live in a live dense step (loss.hip DL3).
   struct OptStates {
     bool c16;                 // bf16 pass at a throughput shape: COMPACT state (common.h)
     float *table, *gates, *h, *c, *h_last;
     vd_bf16_bits *gates16, *h16;
     const float* optH;        // [NO x H]
   };
-  int option_states(vd_model* m, BatchSlot& b, OptStates* o) {
-    const int NO = b.opt.N, To = b.opt.T;
+  int option_states(vd_model* m, const SeqTok& opt, OptStates* o) {
+    const int NO = opt.N, To = opt.T;
     const long H = m->p.rnnHiddenSize, E = m->p.embedSize, V = m->p.vocabSize;
     hipStream_t s = m->s_main;
     VD_TRY(ws_get(m, "opt.table", (size_t)(V + 1) * 4 * H, &o->table));
@@ -122,8 +123,8 @@ struct Disc : Decoder {
     VD_HIP(hipEventRecord(m->ev_prof[0], s));
     {
       VdRange r("disc: option LSTM forward");
-      if (o->c16) VD_TRY(vd_lstm_forward_c16(table16, 4 * H, b.opt.tok, Wopt + E * 4 * H, o->gates16, o->h16, o->h_last, o->c, To, NO, (int)H, s));
-      else VD_TRY(vd_lstm_forward(o->table, 0, 4 * H, b.opt.tok, nullptr, Wopt + E * 4 * H, nullptr, nullptr, o->gates, o->h, o->c, To, NO, (int)H, flags, s));
+      if (o->c16) VD_TRY(vd_lstm_forward_c16(table16, 4 * H, opt.tok, Wopt + E * 4 * H, o->gates16, o->h16, o->h_last, o->c, To, NO, (int)H, s));
+      else VD_TRY(vd_lstm_forward(o->table, 0, 4 * H, opt.tok, nullptr, Wopt + E * 4 * H, nullptr, nullptr, o->gates, o->h, o->c, To, NO, (int)H, flags, s));
     }
     VD_HIP(hipEventRecord(m->ev_prof[1], s));
     o->optH = o->c16 ? o->h_last : o->h + (long)(To - 1) * NO * H;
@@ -151,10 +152,14 @@ struct Disc : Decoder {
     VD_CHECK_ARG(!dense || b.rel_W > 0.0,
                  "vd_model_forward_backward: the batch's '@dense_relevance' gives every round the weight 0 (W = 0, VD_DENSE_MIX = %g): no "
                  "annotated round has a relevant candidate and rounds without an annotation weigh VD_DENSE_MIX", m->sw.dense_mix);
-    // NO = rows the option LSTM executes: N * O, or the number of DISTINCT candidates when the upload de-duplicated them
-    const int N = b.q.N, O = m->p.numOptions, NOfull = N * O, NO = b.opt.N, To = b.opt.T;
-    const bool dedup = b.opt_uid != nullptr;
-    VD_CHECK_ARG(dedup ? NO <= NOfull : NO == NOfull, "decoder 'disc': %d option rows for %d x %d candidates", NO, N, O);
+    // DL3: the batch carries '@dense_relevance_live' and some rounds do not train: the candidate rows of the live rounds only, which the
+    // attachment compacted (opt_uid resolved there: no gather, no scatter-add)
+    const bool live = dense && b.n_live > 0;
+    const SeqTok& opt = live ? b.opt_live : b.opt;
+    // NO = rows the option LSTM executes: N * O, the number of DISTINCT candidates when the upload de-duplicated them, or n_live * O
+    const int N = b.q.N, O = m->p.numOptions, NOfull = N * O, NO = opt.N, To = opt.T;
+    const bool dedup = !live && b.opt_uid != nullptr;
+    VD_CHECK_ARG(live ? NO == b.n_live * O : dedup ? NO <= NOfull : NO == NOfull, "decoder 'disc': %d option rows for %d x %d candidates", NO, N, O);
     const long H = m->p.rnnHiddenSize, E = m->p.embedSize, V = m->p.vocabSize;
     hipStream_t s = m->s_main;
     hipStream_t sd = side_stream(m, s);   // encoder, then the table-gradient chain, in this function's enqueue order
@@ -166,7 +171,7 @@ struct Disc : Decoder {
     VD_TRY(fork_stream(m, s, sd));
     float* enc_out = nullptr;
     OptStates os;
-    VD_TRY(option_states(m, b, &os));
+    VD_TRY(option_states(m, opt, &os));
     const bool c16 = os.c16;
     float *gates = os.gates, *h = os.h, *c = os.c;
     vd_bf16_bits *gates16 = os.gates16, *h16 = os.h16;
@@ -177,8 +182,8 @@ struct Disc : Decoder {
     }
     VD_TRY(join_stream(m, sd, s));
     // criterion (+ nn.MM backward) in one kernel (model.lua:330-335)
-    const float* optH;
-    VD_TRY(option_states_full(m, b, os, &optH));
+    const float* optH = os.optH;
+    if (!live) VD_TRY(option_states_full(m, b, os, &optH));
     float *d_optH = nullptr, *d_enc = nullptr, *d_optH_full = nullptr;
     if (!only_forward) {
       VD_TRY(ws_get(m, "crit.d_optH", (size_t)NO * H, &d_optH));
@@ -187,7 +192,10 @@ struct Disc : Decoder {
     }
     // a training step's targets are smoothed by VD_LABEL_SMOOTHING (loss.hip LS1, LS3); 0 is vd_score_ce itself.  A batch that carries
     // "@dense_relevance" trains on DT3's targets instead (DT4: gscale = 1 / W)
-    if (dense)
+    if (live)
+      VD_TRY(vd_score_ce_dense_live_p(optH, enc_out, b.gt, b.rel, b.live_slot, scores, loss_rows, d_optH, d_enc, N, O, (int)H,
+                                      (float)(1.0 / b.rel_W), (float)m->sw.dense_mix, s));
+    else if (dense)
       VD_TRY(vd_score_ce_dense_p(optH, enc_out, b.gt, b.rel, scores, loss_rows, dedup ? d_optH_full : d_optH, d_enc, N, O, (int)H,
                                  (float)(1.0 / b.rel_W), (float)m->sw.dense_mix, s));
     else
@@ -199,13 +207,14 @@ struct Disc : Decoder {
     }
     VD_TRY(stage_loss(m, loss_rows, N, false, s));
     if (dense) m->loss_div = b.rel_W;
+    m->step_live = live;
     m->scores = scores;
     m->prof_valid = !only_forward;
     if (only_forward) return VD_OK;
     // decoder backward on the main stream, encoder backward beside it (model.lua:335-337)
     VD_TRY(fork_stream(m, s, sd));
     float *dc, *dtab;
-    int32_t* perm = b.opt_sort_perm;               // sorted at upload time (runtime.hip)
+    int32_t* perm = live ? b.live_sort_perm : b.opt_sort_perm;   // sorted at upload / attach time (runtime.hip)
     VD_TRY(ws_get(m, "opt.dc", (size_t)NO * H, &dc));
     VD_TRY(ws_get(m, "opt.dtable", (size_t)(V + 1) * 4 * H, &dtab));
     VD_CHECK_ARG(perm, "decoder 'disc': the batch slot carries no option-token sort");
@@ -254,8 +263,8 @@ struct Disc : Decoder {
       VD_TRY(wgrad_flush(m, b, sd));
       VD_HIP(hipEventRecord(m->ev_enc_grads, sd));
     }
-    if (c16) VD_TRY(vd_segment_rowsum_acc_bf16(gates16, 4 * H, b.opt.tok, perm, (long)To * NO, (int)(4 * H), dtab, 4 * H, sd));
-    else VD_TRY(vd_segment_rowsum_acc(gates, 4 * H, b.opt.tok, perm, (long)To * NO, (int)(4 * H), dtab, 4 * H, sd));
+    if (c16) VD_TRY(vd_segment_rowsum_acc_bf16(gates16, 4 * H, opt.tok, perm, (long)To * NO, (int)(4 * H), dtab, 4 * H, sd));
+    else VD_TRY(vd_segment_rowsum_acc(gates, 4 * H, opt.tok, perm, (long)To * NO, (int)(4 * H), dtab, 4 * H, sd));
     VD_TRY(vd_colsum_acc(dtab, 4 * H, (int)V + 1, (int)(4 * H), Gp(m, "opt.b"), sd));
     VD_TRY(vd_gemm_tn_acc(Wp(m, "embed"), E, dtab, 4 * H, Gp(m, "opt.W"), 4 * H, (int)E, (int)(4 * H), (int)V + 1, 0, sd));
     VD_HIP(hipEventRecord(m->ev_prof[4], s));
@@ -306,7 +315,7 @@ struct Disc : Decoder {
     VD_TRY(ws_get(m, "crit.loss_rows", (size_t)N, &loss_rows));
     VD_TRY(fork_stream(m, s, sd));
     OptStates os;
-    VD_TRY(option_states(m, b, &os));
+    VD_TRY(option_states(m, b.opt, &os));
     float* enc_out = nullptr;
     {
       VdRange r("encoder forward");

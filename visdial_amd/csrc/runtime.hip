@@ -505,13 +505,20 @@ int vd_model_init_params(vd_model* m, uint64_t seed) {
 // Batch attachments: names that start with '@' (no parameter's does).  "@dense_relevance" (loss.hip DT1): the relevance matrix [N x O] of the
 // batch uploaded last, validated here, staged in pinned memory and copied on the upload lane behind the batch's own fields.  It waits for
 // neither the main stream nor a running step, and leaves the answer-encoding cache alone: it touches no weight.
-static int attach_dense_relevance(vd_model* m, const float* host, int64_t n) {
-  const char* who = "vd_model_set_tensor: '@dense_relevance'";
+// "@dense_relevance_live" (`live`; loss.hip DL1 - DL5): the same matrix, validated with the same words under its own name; where some but not
+// all rounds are live, the live rounds' option tokens are compacted and sorted behind the copy, so that the next training step runs the
+// option recurrence and its gradients over those rows only.  An attachment replaces whatever was attached to the upload before.
+static int attach_dense_relevance(vd_model* m, const float* host, int64_t n, bool live) {
+  const char* who = live ? "vd_model_set_tensor: '@dense_relevance_live'" : "vd_model_set_tensor: '@dense_relevance'";
+  VD_CHECK_ARG(!live || !(m->flags & VD_FLAG_BF16),
+               "%s runs the live rounds' candidate rows through the fp32 / split option recurrence; this model was created with lstmBf16 = 1, "
+               "whose compact-state recurrence is not covered: attach '@dense_relevance'", who);
   VD_CHECK_ARG(m->uploaded >= 0, "%s attaches to the batch uploaded last, and no batch has been uploaded", who);
   BatchSlot& sl = m->slot[m->uploaded];
   const int N = sl.q.N, O = m->p.numOptions;
   VD_CHECK_ARG(n == (int64_t)N * O, "%s holds N x O = %d x %d = %ld values for this batch, got %ld", who, N, O, (long)N * O, (long)n);
   double W = 0.0;
+  std::vector<int32_t> live_idx, live_slot((size_t)N, -1);   // DL1
   for (int r = 0; r < N; ++r) {
     const float* row = host + (size_t)r * O;
     int minus = 0;
@@ -526,7 +533,12 @@ static int attach_dense_relevance(vd_model* m, const float* host, int64_t n) {
     }
     VD_CHECK_ARG(minus == 0 || minus == O, "%s row %d mixes -1 (%d entries) with relevances: a round without an annotation is a full row of -1",
                  who, r, minus);
-    W += minus ? m->sw.dense_mix : sum > 0.0 ? 1.0 : 0.0;
+    const double w = minus ? m->sw.dense_mix : sum > 0.0 ? 1.0 : 0.0;
+    W += w;
+    if (w > 0.0) {
+      live_slot[r] = (int32_t)live_idx.size();
+      live_idx.push_back(r);
+    }
   }
   hipStream_t s = m->s_side;
   if (sl.used) VD_HIP(hipStreamWaitEvent(s, sl.done, 0));   // a step that reads an earlier attachment of this upload may still run
@@ -536,8 +548,37 @@ static int attach_dense_relevance(vd_model* m, const float* host, int64_t n) {
   memcpy(stage, host, (size_t)n * sizeof(float));
   VD_TRY(dev_get(sl.bufs, "rel", (size_t)n * sizeof(float), (void**)&sl.rel));
   VD_HIP(hipMemcpyAsync(sl.rel, stage, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
-  VD_HIP(hipEventRecord(sl.ready, s));   // the slot is ready when the attachment has landed too
   sl.rel_W = W;
+  sl.n_live = 0;
+  const int n_live = (int)live_idx.size();
+  // DL2: every round live (or none: W = 0 is refused at the step) is the all-rows attachment.  A slot resolved against the answer-encoding
+  // cache holds the missing rows only and refuses a training step; a gen model holds no candidates to compact and refuses it too (DT5)
+  if (live && n_live > 0 && n_live < N && sl.opt.present && !sl.cached && m->dec_name == "disc") {
+    const int To = sl.opt.T;
+    const long NL = (long)n_live * O, V1 = (long)m->p.vocabSize + 1;
+    VD_CHECK_ARG((long)To * N * O <= 0x7fffffffL, "%s: %d x %d x %d option tokens do not fit the token sort's 32-bit row indices", who, To, N, O);
+    int32_t *istage = nullptr, *idev = nullptr, *tok = nullptr, *work = nullptr;
+    // (buffers sized by all N rounds: another live set on the same upload reallocates nothing)
+    VD_TRY(pin_get(sl.pinned, "live.stage", (size_t)2 * N * sizeof(int32_t), (void**)&istage));
+    memcpy(istage, live_slot.data(), (size_t)N * sizeof(int32_t));
+    memcpy(istage + N, live_idx.data(), (size_t)n_live * sizeof(int32_t));
+    VD_TRY(dev_get(sl.bufs, "live.idx", (size_t)2 * N * sizeof(int32_t), (void**)&idev));
+    VD_HIP(hipMemcpyAsync(idev, istage, (size_t)(N + n_live) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    VD_TRY(dev_get(sl.bufs, "opt_live.dev", (size_t)To * N * O * sizeof(int32_t), (void**)&tok));
+    VD_TRY(vd_dense_live_tokens_p(sl.opt.tok, sl.opt.N, To, sl.opt_uid, idev + N, n_live, O, tok, s));
+    VD_TRY(dev_get(sl.bufs, "live.sort_off", (size_t)(V1 + 1) * sizeof(int32_t), (void**)&sl.live_sort_off));
+    VD_TRY(dev_get(sl.bufs, "opt.sort_work", (size_t)2 * V1 * sizeof(int32_t), (void**)&work));   // the upload's sort is ahead on this lane
+    VD_TRY(dev_get(sl.bufs, "live.sort_perm", (size_t)To * N * O * sizeof(int32_t), (void**)&sl.live_sort_perm));
+    VD_TRY(vd_token_sort(tok, (long)To * NL, (int)V1, sl.live_sort_off, work, sl.live_sort_perm, s));
+    sl.opt_live.T = To;
+    sl.opt_live.N = (int)NL;
+    sl.opt_live.present = true;
+    sl.opt_live.sorted = false;
+    sl.opt_live.tok = tok;
+    sl.live_slot = idev;
+    sl.n_live = n_live;
+  }
+  VD_HIP(hipEventRecord(sl.ready, s));   // the slot is ready when the attachment has landed too
   return VD_OK;
 }
 
@@ -564,8 +605,10 @@ static int read_ndcg(vd_model* m, int which, float* host, int64_t n) {
 
 int vd_model_set_tensor(vd_model* m, const char* name, const float* host, int64_t n) {
   if (m && name && host && name[0] == '@') {
-    if (!strcmp(name, "@dense_relevance")) return attach_dense_relevance(m, host, n);
-    VD_CHECK_ARG(false, "vd_model_set_tensor: unknown batch attachment '%s' (the library knows '@dense_relevance')", name);
+    if (!strcmp(name, "@dense_relevance")) return attach_dense_relevance(m, host, n, false);
+    if (!strcmp(name, "@dense_relevance_live")) return attach_dense_relevance(m, host, n, true);
+    VD_CHECK_ARG(false, "vd_model_set_tensor: unknown batch attachment '%s' (the library knows '@dense_relevance' and '@dense_relevance_live')",
+                 name);
   }
   VD_CHECK_ARG(m && name && host && m->index.count(name), "vd_model_set_tensor: unknown tensor '%s'", name ? name : "(null)");
   const Tensor& t = m->spec[m->index.at(name)];
@@ -642,6 +685,7 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
   sl.uploaded = true;
   sl.rel = nullptr;   // an attachment belongs to one upload
   sl.rel_W = 0.0;
+  sl.n_live = 0;
   sl.B = hb->B;
   const int R = m->p.maxQuesCount, N = hb->B * R, O = m->p.numOptions;
   const long NO = (long)N * O;
@@ -758,6 +802,7 @@ static int begin_step(vd_model* m, bool zero_grads, BatchSlot** out) {
   m->cur = m->uploaded;
   m->enc_grads_recorded = false;
   m->lhood_exec = -1;   // vd_model_option_rows describes the last step call (Gen::retrieve_begin sets it again)
+  m->step_live = false;
   BatchSlot& b = m->slot[m->cur];
   m->N = b.q.N;
   m->O = m->p.numOptions;
@@ -939,6 +984,7 @@ int vd_model_family_ms(vd_model* m, float* ms3) {
 
 // rows the option LSTM executed for the batch of the LAST STEP (vd_model_forward_backward / vd_model_retrieve) vs the N * O candidates
 // they stand for (decoder disc); before any step: of the uploaded batch.  In a pipelined loop that is NOT the prefetched batch.
+// After a training step on "@dense_relevance_live" with some but not all rounds live: (n_live * O, N * O).
 // After vd_model_retrieve_lhood (decoder gen): the (step, candidate) rows that lay in a row group the candidate recurrence ran, summed
 // over the chunks, vs To * N * O; any other step call or upload afterwards brings the answer above back.
 int vd_model_option_rows(vd_model* m, int64_t* executed, int64_t* total) {
@@ -949,7 +995,7 @@ int vd_model_option_rows(vd_model* m, int64_t* executed, int64_t* total) {
     return VD_OK;
   }
   const BatchSlot& b = m->slot[m->cur >= 0 ? m->cur : m->uploaded];
-  *executed = b.opt.present ? b.opt.N : 0;
+  *executed = b.opt.present ? (m->step_live ? b.opt_live.N : b.opt.N) : 0;   // (a live dense step: the live rounds' rows, loss.hip DL3)
   *total = b.opt.present ? (b.opt_total ? b.opt_total : b.opt.N) : 0;
   return VD_OK;
 }

@@ -120,6 +120,23 @@ def dense_targets(rel, gt, mix):
     return t, w
 
 
+def live_rounds(rel, mix):
+    """DL1: the rounds whose DT3 weight is > 0 under `mix`, ascending (int64 [n_live]): annotated with a relevant candidate, or not annotated
+    with mix > 0.  These are the rounds whose candidate rows a step on '@dense_relevance_live' executes."""
+    rel = np.asarray(rel, np.float64)
+    _, w = dense_targets(rel, np.zeros(rel.shape[0], np.int64), mix)
+    return np.nonzero(w > 0)[0]
+
+
+def live_option_tokens(tok_step_major, uid, live, O):
+    """DL3's compaction: int32 [To x len(live) * O] from the uploaded step-major tokens [To x rows]; output row (slot, o) is the row of candidate
+    (live[slot], o) -- uid[live[slot] * O + o] where the upload de-duplicated the candidates (uid [N * O]), else the candidate's own row"""
+    tok = np.asarray(tok_step_major)
+    cand = (np.asarray(live, np.int64)[:, None] * int(O) + np.arange(int(O))[None, :]).reshape(-1)
+    src = cand if uid is None else np.asarray(uid, np.int64).reshape(-1)[cand]
+    return np.ascontiguousarray(tok[:, src], dtype=np.int32).reshape(tok.shape[0], cand.size)
+
+
 def dense_ce(scores, rel, gt, mix):
     """DT4: (loss, ds [N x O]) in fp64 -- loss = sum_n w_n (lse_n - sum_o t_o s_o) / W, ds = w_n (softmax - t) / W, W = sum_n w_n;
     a batch with W = 0 is refused by name"""

@@ -60,6 +60,9 @@ def refuse_training_knobs(params):
 def refuse_dense_training(params):
     """a training run of the operator-level host on dense annotations is refused by name: the dense head (score_ce_dense_kernel) and the
     batch attachment are internal to the model-level runtime.  Evaluating with -denseAnnotations is untouched: NDCG needs the scores only."""
+    if (params.get('denseRows') or 'all') != 'all':
+        raise ValueError("denseRows = %r: a dense step over the live rounds' candidate rows runs in the model-level runtime only: use -host native "
+                         "(visdial_amd.native.NativeModel); the operator-level host takes denseRows = 'all'" % (params['denseRows'],))
     if params.get('denseAnnotations'):
         raise ValueError("denseAnnotations = %r: dense-annotation fine-tuning runs in the model-level runtime only: use -host native "
                          "(visdial_amd.native.NativeModel); the operator-level host trains on one-hot targets" % (params['denseAnnotations'],))

@@ -58,7 +58,9 @@ DENSE_SWITCHES = (
     ('denseMix', 'VD_DENSE_MIX', _text, float, 0.0, None),                                # weight of a round without an annotation in a dense step
 )
 """What a dense step adds to the environment.  The relevance matrix itself is no switch: it is a batch attachment, `attach_dense_relevance`
-(vd_model_set_tensor '@dense_relevance') behind an upload, and `ndcg_rows` (vd_model_get_tensor '@ndcg') reads the NDCG of the scores."""
+(vd_model_set_tensor '@dense_relevance') behind an upload, and `ndcg_rows` (vd_model_get_tensor '@ndcg') reads the NDCG of the scores.
+Neither is the choice of the rows a dense step executes: `attach_dense_relevance(rel, live=True)` attaches the matrix under the name
+'@dense_relevance_live' (params denseRows = 'live' makes `upload` do so for a dense batch)."""
 
 ALL_SWITCHES = SWITCHES + TRAIN_SWITCHES + DENSE_SWITCHES
 
@@ -252,18 +254,21 @@ class NativeModel(SplitEval):
         call("vd_model_upload_batch", self.h, C.byref(hb))      # host buffers are consumed before it returns
         self._N = batch['ques_fwd'].shape[0] * batch['ques_fwd'].shape[1]
         if batch.get('dense_relevance') is not None:            # a dense batch (dataloader.getDenseTrainBatch) trains on its matrix
-            self.attach_dense_relevance(batch['dense_relevance'])
+            self.attach_dense_relevance(batch['dense_relevance'], live=self.params.get('denseRows', 'all') == 'live')
         # non-pad target tokens of THIS batch: the gen loss EMA divides by it (model.lua:76-85)
         self._numTokens = float((np.asarray(batch['answer_out']) > 0).sum()) if 'answer_out' in batch else 0.0
         # whatever was prefetched for trainIteration has just been replaced (evaluate / retrieve / predict / generate
         # between two training steps): the next trainIteration must fetch its own batch
         self._keep = None
 
-    def attach_dense_relevance(self, rel):
+    def attach_dense_relevance(self, rel, live=False):
         """attach the relevance matrix [N x O] (dense.relevance_matrix: DT1) to the batch uploaded last: a training step of a disc model
-        then takes the dense target (DT3-DT4), and `ndcg_rows` ranks with it.  The library validates it and refuses by name."""
+        then takes the dense target (DT3-DT4), and `ndcg_rows` ranks with it.  The library validates it and refuses by name.
+        live=True attaches it as '@dense_relevance_live' (DL1-DL5): the same matrix and the same step, with the option recurrence and its
+        gradients run over the candidate rows of the rounds of weight > 0 only (`option_rows` reports them).  An attachment replaces the
+        one before it on the same upload."""
         a = np.ascontiguousarray(rel, dtype=np.float32)
-        call("vd_model_set_tensor", self.h, b"@dense_relevance", a.ctypes.data, a.size)
+        call("vd_model_set_tensor", self.h, b"@dense_relevance_live" if live else b"@dense_relevance", a.ctypes.data, a.size)
 
     def ndcg_rows(self):
         """NDCG [N] (float64) of the scores of the last forward / retrieval of the current batch under its attached relevance matrix
@@ -495,7 +500,8 @@ class NativeModel(SplitEval):
 
     def option_rows(self):
         """(rows the option LSTM executes, N * O candidates) of the current batch: the upload de-duplicates candidates; with
-        params optionCache in evaluation mode the rows the cache did not hold (possibly 0)"""
+        params optionCache in evaluation mode the rows the cache did not hold (possibly 0); after a training step on a live attachment
+        the candidate rows of the live rounds"""
         a, b = C.c_int64(), C.c_int64()
         call("vd_model_option_rows", self.h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)

@@ -72,6 +72,21 @@ def check_dense(opt):
         raise ValueError("-denseMix %r must be a finite real in [0, 1] (0 = rounds without an annotation do not train)" % (opt.get('denseMix'),))
 
 
+def check_dense_rows(opt):
+    """what -denseRows live cannot be combined with, refused by name before any model exists (the library refuses the bf16 model: loss.hip DL5)"""
+    rows = opt.get('denseRows') or 'all'
+    if rows not in ('all', 'live'):
+        raise ValueError("-denseRows %r must be 'all' or 'live'" % (rows,))
+    if rows != 'live':
+        return
+    if not opt.get('denseAnnotations'):
+        raise ValueError("-denseRows live without -denseAnnotations: the live rounds are those of a dense batch; give the annotation file or "
+                         "train with -denseRows all")
+    if opt.get('lstmPrecision') == 'bf16':
+        raise ValueError("-denseRows live with -lstmPrecision bf16: the compact-state bf16 option recurrence does not run the live rounds' "
+                         "rows alone; train with -denseRows all or another -lstmPrecision")
+
+
 def default_params(**overrides):
     opt = {k: v for k, v, _ in OPTIONS}
     # sizes the reference copies from the dataloader (train.lua:55-59)
@@ -108,6 +123,11 @@ def parse(argv=None):
     ap.add_argument('-denseMix', '--denseMix', type=float, default=0.0,
                     help='(with -denseAnnotations) weight mu in [0, 1] of the rounds without an annotation, which keep their one-hot target '
                          '(0 = they do not train)')
+    # not a reference flag (kept out of OPTIONS): which candidate rows a dense step executes (csrc/loss.hip DL1-DL5)
+    ap.add_argument('-denseRows', '--denseRows', choices=('all', 'live'), default='all',
+                    help="(with -denseAnnotations, -host native) 'all' (default): every round's candidates go through the option recurrence and "
+                         "its gradients | 'live': only the candidates of the rounds that carry a gradient (weight > 0); the same loss and "
+                         "gradients up to fp32 summation order")
     opt = vars(ap.parse_args(argv))
     # refused by name before any model exists (the library refuses the same values: csrc/rt_switches.h)
     # (eps is applied in fp32, as in the library: a value that rounds to 1.0f is not below 1)
@@ -120,6 +140,7 @@ def parse(argv=None):
         ap.error('-denseMix %r must be a finite real in [0, 1] (0 = rounds without an annotation do not train)' % (opt['denseMix'],))
     try:
         check_dense(dict(opt, decoder='disc') if opt['loadPath'] else opt)   # (-loadPath: the decoder is the checkpoint's; train.py checks again)
+        check_dense_rows(opt)
     except ValueError as e:
         ap.error(str(e))
     opt.update(maxQuesCount=10, maxQuesLen=20, maxAnsLen=20, numOptions=100)
