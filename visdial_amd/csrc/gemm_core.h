@@ -148,6 +148,32 @@ __device__ __forceinline__ void tile_to_rows(const f32x16& a, float* scr, int la
   asm volatile("" ::: "memory");
 }
 
+// The accumulators of v_mfma_f32_16x16x32_bf16 (split_core.h): lane l holds column l & 15, rows 4 (l >> 4) + i, i = 0..3, of a 16 x 16
+// result.  The 2 x 2 quad q00 q01 / q10 q11 that covers one 32 x 32 tile is handed back in the layout of the 32x32 MFMAs (mfma_row, column
+// lane & 31), which is what every epilogue functor takes.  Through the wave's private scratch (32 rows of QUAD_LD floats: with a row stride
+// of 36 the four row groups of a store land on banks 16 apart, conflict-free); single wave, no barrier, as tile_to_rows.
+typedef float vd_f32x4 __attribute__((ext_vector_type(4)));
+constexpr int QUAD_LD = 36;
+__device__ __forceinline__ int quad_row(int i, int lane) { return 4 * (lane >> 4) + i; }
+__device__ __forceinline__ f32x16 quad_to_tile(const vd_f32x4& q00, const vd_f32x4& q01, const vd_f32x4& q10, const vd_f32x4& q11, float* scr,
+                                               int lane) {
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float* w = scr + quad_row(i, lane) * QUAD_LD + (lane & 15);
+    w[0] = q00[i];
+    w[16] = q01[i];
+    w[16 * QUAD_LD] = q10[i];
+    w[16 * QUAD_LD + 16] = q11[i];
+  }
+  asm volatile("" ::: "memory");
+  f32x16 t;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) t[r] = scr[mfma_row(r, lane) * QUAD_LD + (lane & 31)];
+  asm volatile("" ::: "memory");
+  return t;
+}
+
 // Epilogue functors may declare `struct Pre` + `preload(Pre&, row0, lane, M)`: state fetched before the K loop of the
 // LDS-DMA pipeline and handed to operator() as a trailing `const Pre*` (nullptr from the other pipelines).
 struct EpiNoPre {};

@@ -9,23 +9,32 @@
 //
 // Operands: A [M x K] fp32 rows exactly as the fp32 kernels read them -- the activations stay fp32 in memory, a wave splits its
 // fragments into three bf16 planes IN REGISTERS -- and B as three precomputed bf16 planes Bt_p [N x K] (k contiguous; the recurrent
-// weights, converted once per pass).  Tiles go global -> LDS by DMA; one macro step = 16 k = one fp32 A tile [128 x 16] (64-byte rows,
-// chunk swizzle of gemm_block_glds) + three bf16 B tiles [128 x 16] (32-byte rows, chunk swizzle (row >> 4) & 1: conflict-free for
-// ds_read_b128's lane groups {0-3,12-15,20-27} / {4-11,16-19,28-31}, SQ_LDS_BANK_CONFLICT = 0; round 4's (row >> 2) & 1 was two-way
-// conflicted on every B read): 20 KB per stage, two stages = 40 KB, four workgroups per CU -- the epilogue of one (gates, c, h, the
-// projection-table gather) runs under the MFMAs of the others.  Per K step a B plane's four fragments are read once and multiplied
-// with the three A planes, column tile innermost: consecutive MFMAs never share an accumulator.
+// weights, converted once per pass).
 //
-// What bounds it (profiles/r05_experiments.txt section 1): POWER.  v_mfma_f32_32x32x16_bf16 on non-zero operands sustains 1.85 PFLOP/s
-// on this chip, not 2.5 (scripts/probes/mfma_bf16_peak.hip: the clock falls to ~1.75 GHz); 9 x 41.9 GFLOP take 204 us at that rate with
-// the pipe 100 % busy.  The K loop alone runs 299 us on random operands and 206 us on zeros (same code, same cycles, higher clock);
-// bigger wave tiles (64 x 128 per wave: half the LDS-DMA bytes and fragment reads per MFMA) do not change it.
+// Step kernels (gemm_split_kernel): v_mfma_f32_16x16x32_bf16.  The two bf16 shapes have the same peak (1024 FLOP per cycle and SIMD), but
+// this chip holds a higher clock on the 16x16x32 one under load: +10 % by wall in a register-only loop on random operands, equal on
+// zeros (scripts/probes/mfma_bf16_peak.hip, profiles/mfma_shape.txt).  A wave still owns 32 rows x 128 columns: 2 x 8 accumulators of
+// 16 x 16, 64 registers, all in VGPRs (in AGPRs the short instruction loses 1 to 2.5 cycles: the probe's first build).  One macro step =
+// 32 k = one MFMA's depth; K = 16 (mod 32) ends on a half step whose upper k half multiplies zeros.
+//   A: each wave reads only its own 32 rows, so they go global -> registers, one macro step ahead: lane l holds k = 8 (l >> 4) .. + 7 of rows
+//      l & 15 and 16 + (l & 15), 2 x 32 contiguous bytes; the four lanes of a row fetch one 128-byte line.
+//   B: three planes [128 x 32] bf16 by LDS-DMA, 64-byte rows, 24 KB per stage, two stages = 48 KB; chunk swizzle split_swz (below):
+//      ds_read_b128 conflict-free.  Per plane the eight fragments are read once and multiplied with the three A planes of both row halves,
+//      column tile innermost: consecutive MFMAs never share an accumulator.
+//   Workgroup: four waves (128 x 128), three per CU -- 3 x 48 KB = 144 KB of LDS.  The suggested six-wave workgroup (192 rows, two per CU,
+//      96 KB) keeps the same 12 waves per CU but measured SLOWER than the 32x32x16 kernel (434 / 498 us per forward / backward launch in
+//      the step against 374 / 437): with two workgroups per CU the epilogue of one (gates, c, h, the projection-table gather) has only one
+//      other workgroup's MFMAs to hide under.  With three, 341 / 423 us, and the step's side streams still run beside it (profiles/mfma_shape.txt).
+//   Epilogues take 32 x 32 tiles in the 32x32 layout: each 2 x 2 quad of 16 x 16 results passes the wave's scratch once (gemm_core.h quad_to_tile).
+//
+// What bounds it (profiles/r05_experiments.txt section 1): POWER.  On non-zero operands the clock falls to ~1.75-1.9 GHz on 32x32x16 and to
+// ~2.05-2.15 GHz on 16x16x32; the same K loop ran 299 us on random operands and 206 us on zeros on the old shape (same code, same cycles).
+// The weight-gradient contraction below (gemm_split_tn_kernel) stays on v_mfma_f32_32x32x16_bf16.
 #pragma once
 #include "gemm_core.h"
 #include "paths.h"
 
 typedef __bf16 vd_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float vd_f32x4 __attribute__((ext_vector_type(4)));
 
 // v (8 consecutive k of one row) -> hi / mid / lo planes
 __device__ __forceinline__ void vd_split3(const float4& u, const float4& w, vd_bf16x8& hi, vd_bf16x8& mid, vd_bf16x8& lo) {
@@ -63,16 +72,13 @@ static int weights_to_bf16x3(const float* src, vd_bf16_bits* dst, long n, hipStr
 }
 
 struct SplitCfg {
-  static constexpr int NT = 4, WM = 4, THREADS = 256;
-  static constexpr int BM = 128, BN = 128;
-  static constexpr int ATILE = BM * 64;                           // [BM rows][16 fp32]      = 64-byte rows
-  static constexpr int BTILE = BN * 32;                           // [BN rows][16 bf16]      = 32-byte rows, one per plane
-  static constexpr int STAGE = ATILE + 3 * BTILE;                 // one macro step = 16 k
-#ifndef VD_SPLIT_LDS
-#define VD_SPLIT_LDS 41984                                        // as the fp32 step kernels: three workgroups per CU + room for one latency-shape
-#endif                                                            // workgroup of the encoder streams (`make variant DEFS=-DVD_SPLIT_LDS=40960`: four)
-  static constexpr int LDS_BYTES = VD_SPLIT_LDS;
-  static_assert(LDS_BYTES >= 2 * STAGE, "two stages of 20 KB");
+    static constexpr int NT = 4, WM = 4, THREADS = 64 * WM;
+  static constexpr int BM = 32 * WM, BN = 128, KS = 32;           // four waves of 32 rows x 128 columns; one macro step = 32 k
+  static constexpr int BTILE = BN * 64;                           // [BN rows][32 bf16]      = 64-byte rows, one per plane
+  static constexpr int STAGE = 3 * BTILE;                         // 24 KB: the B planes only (A goes global -> registers)
+  static constexpr int LDS_BYTES = 2 * STAGE;                     // 48 KB, three workgroups per CU (the registers allow no more)
+  static constexpr int SCR = LDS_BYTES / WM / 4;                     // floats of epilogue scratch per wave (3072 >= 32 x QUAD_LD)
+  static_assert(SCR >= 32 * QUAD_LD, "quad_to_tile's 32 rows of QUAD_LD floats");
 };
 
 // workgroup id -> tile.  Block b runs on XCD b % 8 (round-robin dispatch), so the map decides which operand bytes each XCD's private L2
@@ -99,6 +105,10 @@ __device__ __forceinline__ bool split_tile_of(int bid, int nwg, int tiles_m, int
   tile_m = wg / tiles_n;
   return true;
 }
+// chunk swizzle of the 64-byte B rows: row group q = (row >> 2) & 3 stores k chunk c at c ^ {0, 2, 3, 1}[q].  A B fragment read (lane l: row
+// l & 15, chunk l >> 4) then puts the 16 lanes of each ds_read_b128 group -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 -- on
+// 16 different 16-byte bank groups: rows q = 0, 3 of one chunk with rows q = 1, 2 of its neighbour, {s0, s3, 1 ^ s1, 1 ^ s2} all different.
+__device__ __forceinline__ int split_swz(int q) { return (0x78 >> (2 * (q & 3))) & 3; }
 static int split_grid(int tiles_m, int tiles_n) {
   constexpr int CG = VD_SPLIT_CG, RG = 8 / CG;
   if ((tiles_n % CG) == 0 && tiles_n >= 8) return 8 * ((tiles_m + RG - 1) / RG) * (tiles_n / CG);
@@ -106,7 +116,7 @@ static int split_grid(int tiles_m, int tiles_n) {
 }
 
 template <int NPROD, class Epi>
-__global__ void __launch_bounds__(256, 3)
+__global__ void __launch_bounds__(SplitCfg::THREADS, 3)
 gemm_split_kernel(int M, int N, int K, int tiles_n, const float* A, long lda, const vd_bf16_bits* B, long ldb, long bplane, Epi epi) {
   using Cfg = SplitCfg;
   constexpr int NT = Cfg::NT;
@@ -114,77 +124,85 @@ gemm_split_kernel(int M, int N, int K, int tiles_n, const float* A, long lda, co
   int tile_m, tile_n;
   if (!split_tile_of((int)blockIdx.x, (int)gridDim.x, (M + Cfg::BM - 1) / Cfg::BM, tiles_n, tile_m, tile_n)) return;
   const int row_base = tile_m * Cfg::BM, col_base = tile_n * Cfg::BN;
-  constexpr int NIA = 2;                                         // this wave's own 32 rows = 2 pieces of 16 rows x 64 bytes
-  constexpr int NIB = 3;                                         // row group `wave` (32 rows x 32 bytes) of every plane
+  constexpr int NIB = 24 / Cfg::WM;                                       // 24 pieces of 16 rows x 64 bytes per stage, six per wave
   const int tid = (int)threadIdx.x, lane = tid & 63;
   const int wm = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nm = K / 16;                                         // macro steps
+  const int nfull = K / 32, nm = nfull + ((K >> 4) & 1);         // macro steps; the last one is a half step when K = 16 (mod 32)
   const int wrow = row_base + wm * 32;                           // first row of this wave
+  const int g = lane >> 4, l15 = lane & 15;                      // MFMA operand lane: row / column l15, k = 8 g .. 8 g + 7
 
-  f32x16 acc[NT];
+  vd_f32x4 acc[2][2 * NT];                                       // [16-row half][16-column tile]
 #pragma unroll
-  for (int j = 0; j < NT; ++j)
+  for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    for (int j = 0; j < 2 * NT; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[rt][j][r] = 0.f;
 
   typename EpiPreOf<Epi>::type pre;
   if constexpr (EpiPreOf<Epi>::value) epi.preload(pre, wrow, lane, M);
 
-  // per-thread source byte offsets of this wave's DMA instructions (macro step 0); chunk index swizzled on the source side
-  unsigned voffa[NIA], voffb[NIB];
+  // A: the lane's own 8 k of rows l15 and 16 + l15 of this wave, 32 bytes each, straight into registers one macro step ahead (the four
+  // lanes of a row fetch one whole 128-byte line).  In a half step the lanes of the upper k half load nothing and multiply zeros.
+  unsigned aoff[2];
 #pragma unroll
-  for (int i = 0; i < NIA; ++i) {
-    const int r = wm * 32 + i * 16 + (lane >> 2);
-    const int c = (lane & 3) ^ ((r >> 2) & 3);
-    voffa[i] = (unsigned)(((long)min(row_base + r, M - 1) * lda + c * 4) * 4);
-  }
-  {
-    const int r = wm * 32 + (lane >> 1);
-    const int c = (lane & 1) ^ ((r >> 4) & 1);
-    const unsigned v = (unsigned)(((long)min(col_base + r, N - 1) * ldb + c * 8) * 2);
+  for (int rt = 0; rt < 2; ++rt) aoff[rt] = (unsigned)(((long)min(wrow + rt * 16 + l15, M - 1) * lda + g * 8) * 4);
+  float4 an[2][2];
+  auto load_a = [&](int m) {
+    const char* ak = reinterpret_cast<const char*>(A + (long)m * 32);
+    const bool live = m < nfull || g < 2;
 #pragma unroll
-    for (int i = 0; i < NIB; ++i) voffb[i] = v;
+    for (int rt = 0; rt < 2; ++rt) {
+      an[rt][0] = an[rt][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (live) {
+        an[rt][0] = *reinterpret_cast<const float4*>(ak + aoff[rt]);
+        an[rt][1] = *reinterpret_cast<const float4*>(ak + aoff[rt] + 16);
+      }
+    }
+  };
+  // B: per-thread source byte offsets of this wave's DMA instructions; the DMA writes lane-linear (row lane >> 2, chunk lane & 3 of the
+  // piece), the chunk index is swizzled on the source side by split_swz(row >> 2).  In a half step the chunks of the upper k half fetch
+  // the lower half again (finite values that meet the zeros of A): nothing is read past k = K.
+  const int csrc = (lane & 3) ^ split_swz(lane >> 4);            // (row >> 2) & 3 = lane >> 4: a piece starts on a multiple of 16 rows
+  unsigned voffb[NIB];
+#pragma unroll
+  for (int i = 0; i < NIB; ++i) {
+    const int r = ((wm * NIB + i) & 7) * 16 + (lane >> 2);
+    voffb[i] = (unsigned)(((long)min(col_base + r, N - 1) * ldb + csrc * 8) * 2);
   }
   const unsigned lds0 = (unsigned)(uintptr_t)smem;
-  auto issue = [&](int m, int st) {
-    const unsigned base = lds0 + st * Cfg::STAGE;
+  auto issue_b = [&](int m, int st) {
+    const unsigned back = m < nfull ? 0u : (unsigned)(csrc >> 1) * 32u;
 #pragma unroll
-    for (int i = 0; i < NIB; ++i)
-      glds16(voffb[i], reinterpret_cast<const float*>(B + (long)i * bplane + (long)m * 16), base + Cfg::ATILE + i * Cfg::BTILE + wm * 1024);
-    const float* ak = A + (long)m * 16;
-#pragma unroll
-    for (int i = 0; i < NIA; ++i) glds16(voffa[i], ak, base + (wm * NIA + i) * 1024);
+    for (int i = 0; i < NIB; ++i) {
+      const int q = wm * NIB + i;                                // piece q: plane q >> 3, rows (q & 7) * 16 .. + 15
+      glds16(voffb[i] - back, reinterpret_cast<const float*>(B + (long)(q >> 3) * bplane + (long)m * 32), lds0 + st * Cfg::STAGE + q * 1024);
+    }
   };
-  const int hi = lane >> 5, l31 = lane & 31;
-  const int sw = (l31 >> 2) & 3;
-  const int cb = (hi ^ ((l31 >> 4) & 1)) * 16;                   // this lane's 8 bf16 k inside a 32-byte B row
+  const int bfrag = l15 * 64 + ((g ^ split_swz(l15 >> 2)) * 16);  // this lane's 8 bf16 k of column l15 of a 16-column tile
 
   if (nm > 0) {
-    issue(0, 0);
+    issue_b(0, 0);
+    load_a(0);
     int st = 0;
     for (int m = 0; m < nm; ++m) {
-      if (m + 1 < nm) {
-        issue(m + 1, st ^ 1);
-        asm volatile("s_waitcnt vmcnt(5)" ::: "memory");          // NIA + NIB requests of step m + 1 may stay in flight
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
+      vd_bf16x8 ap[2][3];
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) vd_split3(an[rt][0], an[rt][1], ap[rt][0], ap[rt][1], ap[rt][2]);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       asm volatile("s_barrier" ::: "memory");                    // every wave's share of macro step m has landed
-      const char* sbase = reinterpret_cast<const char*>(smem) + st * Cfg::STAGE;
-      const float* sa = reinterpret_cast<const float*>(sbase) + (wm * 32 + l31) * 16;
-      const float4 u = *reinterpret_cast<const float4*>(sa + (((hi * 2) ^ sw) * 4));
-      const float4 w = *reinterpret_cast<const float4*>(sa + (((hi * 2 + 1) ^ sw) * 4));
-      vd_bf16x8 ap[3];
-      vd_split3(u, w, ap[0], ap[1], ap[2]);
-      // plane p of B against planes i of A, smallest terms first; j innermost.  (Measured and dropped: producing the A planes one at a time,
-      // hi first, with the next plane's VALU instructions interleaved into the MFMAs by sched_group_barrier -- the technique that pays in
-      // the dWh kernel below: 337 / 330 vs 342 / 322 us alone, 23.6 vs 23.4 ms in the step, 158 instead of 124 VGPRs.)
+      if (m + 1 < nm) {                                          // step m + 1 flies under the 144 MFMAs of step m
+        issue_b(m + 1, st ^ 1);
+        load_a(m + 1);
+      }
+      const char* sbase = reinterpret_cast<const char*>(smem) + st * Cfg::STAGE + bfrag;
+      // plane p of B against planes i of A, smallest terms first; column tile innermost: consecutive MFMAs never share an accumulator
 #pragma unroll
       for (int p = 2; p >= 0; --p) {
-        vd_bf16x8 bp[NT];
+        vd_bf16x8 bp[2 * NT];
 #pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          const vd_f32x4 t = *reinterpret_cast<const vd_f32x4*>(sbase + Cfg::ATILE + p * Cfg::BTILE + (j * 32 + l31) * 32 + cb);
+        for (int j = 0; j < 2 * NT; ++j) {
+          const vd_f32x4 t = *reinterpret_cast<const vd_f32x4*>(sbase + p * Cfg::BTILE + j * 1024);
           bp[j] = __builtin_bit_cast(vd_bf16x8, t);
         }
 #pragma unroll
@@ -192,15 +210,22 @@ gemm_split_kernel(int M, int N, int K, int tiles_n, const float* A, long lda, co
           constexpr int LIM = NPROD >= 9 ? 4 : NPROD >= 6 ? 2 : NPROD >= 3 ? 1 : 0;     // products with i + p <= LIM are issued
           if (i + p > LIM) continue;
 #pragma unroll
-          for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[i], bp[j], acc[j], 0, 0, 0);
+          for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int j = 0; j < 2 * NT; ++j) acc[rt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[rt][i], bp[j], acc[rt][j], 0, 0, 0);
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // stage `st` may be refilled
       st ^= 1;
     }
   }
-  if constexpr (EpiPreOf<Epi>::value) epi(acc, wrow, col_base, lane, M, N, smem + wm * 1024, &pre);
-  else epi(acc, wrow, col_base, lane, M, N, smem + wm * 1024);
+  // the epilogues take 32 x 32 tiles in the layout of the 32x32 MFMAs: each 2 x 2 quad of 16 x 16 results goes through the wave's scratch once
+  float* scr = smem + wm * Cfg::SCR;
+  f32x16 tile[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) tile[j] = quad_to_tile(acc[0][2 * j], acc[0][2 * j + 1], acc[1][2 * j], acc[1][2 * j + 1], scr, lane);
+  if constexpr (EpiPreOf<Epi>::value) epi(tile, wrow, col_base, lane, M, N, scr, &pre);
+  else epi(tile, wrow, col_base, lane, M, N, scr);
 }
 
 // C[M x N] = epi(A[M x K] (fp32 rows) * Bt[N x K]^T), Bt given as three bf16 planes; K % 16 == 0
@@ -218,7 +243,7 @@ static int launch_gemm_split(int M, int N, int K, const float* A, long lda, cons
     VD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set = true;
   }
-  hipLaunchKernelGGL(kern, dim3(split_grid(tiles_m, tiles_n)), dim3(256), Cfg::LDS_BYTES, stream, M, N, K, tiles_n, A, lda, B, ldb, bplane, e);
+  hipLaunchKernelGGL(kern, dim3(split_grid(tiles_m, tiles_n)), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, M, N, K, tiles_n, A, lda, B, ldb, bplane, e);
   VD_LAUNCH_CHECK();
   return VD_OK;
 }
