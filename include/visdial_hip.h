@@ -196,12 +196,14 @@ int vd_lstm2_backward(const vd_lstm2_bwd_t* stacks, int nstacks, int H, void* st
 int vd_lstm2_forward_flags(const vd_lstm2_fwd_t* stacks, int nstacks, int H, int flags, void* stream);
 int vd_lstm2_backward_flags(const vd_lstm2_bwd_t* stacks, int nstacks, int H, int flags, void* stream);
 
-/* zero rows [nact[t], N) of every time slice of a [T x N x ld] buffer (nact_dev: DEVICE int32[T]) */
+/* zero rows [nact[t], N) of every time slice of a [T x N x ld] buffer (nact_dev: DEVICE int32[T]).
+ * float4 stores: buf 16-byte aligned; ncols, ld and tstride multiples of 4 (refused otherwise) */
 int vd_zero_inactive_rows(float* buf, int64_t tstride, int64_t ld, int ncols, const int32_t* nact_dev, int T,
                           int N, void* stream);
 
 /* ---- nn.LookupTableMaskZero / nn.Dropout / small glue ------------------------------------- */
-/* out[r,:] = emb[tok[r],:] * (mask ? mask*scale : 1)        mn-att:21,24-25; disc.lua:12 */
+/* out[r,:] = emb[tok[r],:] * (mask ? mask*scale : 1)        mn-att:21,24-25; disc.lua:12
+ * E % 4 == 0, emb and out 16-byte aligned, mask 4-byte aligned (refused otherwise) */
 int vd_embed_gather(const float* emb, const int32_t* tok, const uint8_t* mask, float* out, int64_t rows,
                     int E, float scale, void* stream);
 /* demb[tok[r],:] += dx[r,:] * mask*scale                    LookupTable:accGradParameters */
@@ -216,7 +218,7 @@ int vd_mask_time_backward(const float* dout, const int32_t* tok, float* dfeat, i
  * work int32[2V], perm int32[n] */
 int vd_token_sort(const int32_t* tok, int64_t n, int V, int32_t* offset, int32_t* work, int32_t* perm,
                   void* stream);
-/* out[tok[r], 0:ncol] += X[r, 0:ncol] for all n rows */
+/* out[tok[r], 0:ncol] += X[r, 0:ncol] for all n rows; X 16-byte aligned, ncol, ldx and ldo multiples of 4 */
 int vd_segment_rowsum_acc(const float* X, int64_t ldx, const int32_t* tok, const int32_t* perm, int64_t n,
                           int ncol, float* out, int64_t ldo, void* stream);
 /* Bernoulli(1-p) keep-mask bytes from a counter-based generator (nn.Dropout noise) */

@@ -509,6 +509,8 @@ int vd_mask_time_backward(const float* dout, const int32_t* tok, float* dfeat, i
 int vd_zero_inactive_rows(float* buf, int64_t tstride, int64_t ld, int ncols, const int32_t* nact_dev, int T,
                           int N, void* stream) {
   VD_CHECK_ARG(buf && nact_dev && T >= 0 && N >= 0 && ncols % 4 == 0 && ld % 4 == 0, "vd_zero_inactive_rows: bad args");
+  VD_CHECK_ARG(((uintptr_t)buf & 15) == 0 && tstride % 4 == 0,
+               "vd_zero_inactive_rows: pointer must be 16-byte aligned and leading dimension a multiple of 4 (tstride=%ld)", (long)tstride);
   if (T == 0 || N == 0) return VD_OK;
   hipLaunchKernelGGL(zero_inactive_rows_kernel, dim3(64, T), dim3(256), 0, (hipStream_t)stream, buf, (long)tstride,
                      (long)ld, ncols, nact_dev, N);
@@ -537,6 +539,8 @@ extern "C" {
 int vd_embed_gather(const float* emb, const int32_t* tok, const uint8_t* mask, float* out, int64_t rows, int E,
                     float scale, void* stream) {
   VD_CHECK_ARG(emb && tok && out && rows >= 0 && E > 0 && E % 4 == 0, "vd_embed_gather: bad args (E=%d)", E);
+  VD_CHECK_ARG((((uintptr_t)emb | (uintptr_t)out) & 15) == 0, "vd_embed_gather: pointer must be 16-byte aligned and leading dimension a multiple of 4 (emb, out; E=%d)", E);
+  VD_CHECK_ARG(((uintptr_t)mask & 3) == 0, "vd_embed_gather: the mask is read four bytes at a time: pointer must be 4-byte aligned");
   if (rows == 0) return VD_OK;
   hipLaunchKernelGGL(embed_gather_kernel, grid1d(rows * (E / 4), 256), dim3(256), 0, (hipStream_t)stream, emb,
                      tok, mask, out, (long)rows, E, scale);
@@ -581,6 +585,7 @@ int vd_segment_rowsum_acc(const float* X, int64_t ldx, const int32_t* tok, const
                           int ncol, float* out, int64_t ldo, void* stream) {
   VD_CHECK_ARG(X && tok && perm && out && n >= 0 && ncol > 0 && ncol % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0,
                "vd_segment_rowsum_acc: bad args");
+  VD_CHECK_ARG(((uintptr_t)X & 15) == 0, "vd_segment_rowsum_acc: pointer must be 16-byte aligned and leading dimension a multiple of 4 (ldx=%ld)", (long)ldx);
   if (n == 0) return VD_OK;
   hipLaunchKernelGGL(segment_rowsum_kernel<256>, grid1d(n, 256), dim3(256), 0, (hipStream_t)stream, X, (long)ldx, tok, perm, (long)n, ncol,
                      out, (long)ldo);
@@ -630,7 +635,8 @@ int vd_clip_decay_adam_p(float* w, float* g, float* m, float* v, int64_t n, floa
 // internal (common.h): the same segmented row sum over bf16 rows (the compact da of a bf16 pass)
 int vd_segment_rowsum_acc_bf16(const vd_bf16_bits* X16, int64_t ldx, const int32_t* tok, const int32_t* perm, int64_t n, int ncol,
                                float* out, int64_t ldo, hipStream_t stream) {
-  VD_CHECK_ARG(X16 && tok && perm && out && n >= 0 && ncol % 4 == 0 && ldx % 4 == 0, "vd_segment_rowsum_acc_bf16: bad args");
+  VD_CHECK_ARG(X16 && tok && perm && out && n >= 0 && ncol > 0 && ncol % 4 == 0 && ldx % 4 == 0, "vd_segment_rowsum_acc_bf16: bad args");
+  VD_CHECK_ARG(((uintptr_t)X16 & 7) == 0, "vd_segment_rowsum_acc_bf16: the rows are read four bf16 at a time: pointer must be 8-byte aligned");
   if (n == 0) return VD_OK;
   hipLaunchKernelGGL((segment_rowsum_kernel<256, true>), grid1d(n, 256), dim3(256), 0, stream, reinterpret_cast<const float*>(X16), (long)ldx,
                      tok, perm, (long)n, ncol, out, (long)ldo);

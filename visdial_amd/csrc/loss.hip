@@ -53,6 +53,11 @@
 
 #define MAX_OPT 128
 
+// the heads read optH / enc and write dOptH / dEnc as float4 at multiples of H floats (H % 4 == 0): null, or 16-byte aligned
+static inline bool score_ce_aligned(const float* optH, const float* enc, const float* dOptH, const float* dEnc) {
+  return (((uintptr_t)optH | (uintptr_t)enc | (uintptr_t)dOptH | (uintptr_t)dEnc) & 15) == 0;
+}
+
 // One workgroup per QA round n.
 //   score[o] = <optH[n,o,:], enc[n,:]> ; loss_n = logsumexp(score) - score[gt]
 //   if train: ds = (softmax - onehot) * gscale ; dOptH[n,o,:] = ds[o]*enc[n,:] ; dEnc[n,:] = sum_o ds[o]*optH[n,o,:]
@@ -308,7 +313,8 @@ __device__ __forceinline__ void logsoftmax_nll_body(float* __restrict__ logits, 
   const long r = blockIdx.x;
   const int tid = threadIdx.x;
   float* row = logits + r * ld;
-  if (write_grad && tid < ld - V) row[V + tid] = 0.f;  // keep the alignment pad columns finite (K-padding rule)
+  if (write_grad)
+    for (long c = V + tid; c < ld; c += 256) row[c] = 0.f;  // keep the alignment pad columns finite (K-padding rule), however many
   // masked rows: a pad decoder input (MaskZero, gen.lua:23-24) or a pad TARGET -- utils.computeLhood masks on
   // words == 0 (utils.lua:86-102): an empty candidate has option_in = <START>,0.. and option_out = 0.. (processOptions
   // writes no <END> for length 0), so its first row has a non-pad input and target 0; it must contribute 0, not
@@ -394,6 +400,7 @@ int vd_score_ce(const float* optH, const float* enc, const int32_t* gt, float* s
                "vd_score_ce: bad args (O=%d must be <= %d)", O, MAX_OPT);
   VD_CHECK_ARG(gt == nullptr || loss_rows != nullptr, "vd_score_ce: loss_rows required with gt");
   VD_CHECK_ARG((dOptH == nullptr) == (dEnc == nullptr), "vd_score_ce: dOptH and dEnc go together");
+  VD_CHECK_ARG(score_ce_aligned(optH, enc, dOptH, dEnc), "vd_score_ce: pointer must be 16-byte aligned and leading dimension a multiple of 4 (optH, enc, dOptH, dEnc; H=%d)", H);
   VD_CHECK_ARG(dOptH == nullptr || gt != nullptr, "vd_score_ce: gradients need gt");
   if (N == 0) return VD_OK;
   hipLaunchKernelGGL(score_ce_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, optH, enc, gt, scores,
@@ -421,6 +428,7 @@ int vd_score_ce_p(const float* optH, const float* enc, const int32_t* gt, float*
   VD_CHECK_ARG(optH && enc && scores && gt && loss_rows && N >= 0 && O >= 1 && O <= MAX_OPT && H % 4 == 0,
                "vd_score_ce_p: bad args (O=%d must be <= %d; the smoothed head needs gt and loss_rows)", O, MAX_OPT);
   VD_CHECK_ARG((dOptH == nullptr) == (dEnc == nullptr), "vd_score_ce_p: dOptH and dEnc go together");
+  VD_CHECK_ARG(score_ce_aligned(optH, enc, dOptH, dEnc), "vd_score_ce_p: pointer must be 16-byte aligned and leading dimension a multiple of 4 (optH, enc, dOptH, dEnc; H=%d)", H);
   if (N == 0) return VD_OK;
   hipLaunchKernelGGL(score_ce_smooth_kernel, dim3(N), dim3(256), 0, stream, optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale,
                      smooth);
@@ -434,6 +442,7 @@ int vd_score_ce_dense_p(const float* optH, const float* enc, const int32_t* gt, 
   VD_CHECK_ARG(optH && enc && scores && gt && rel && loss_rows && N >= 0 && O >= 1 && O <= MAX_OPT && H % 4 == 0,
                "vd_score_ce_dense_p: bad args (O=%d must be <= %d; the dense head needs gt, rel and loss_rows)", O, MAX_OPT);
   VD_CHECK_ARG((dOptH == nullptr) == (dEnc == nullptr), "vd_score_ce_dense_p: dOptH and dEnc go together");
+  VD_CHECK_ARG(score_ce_aligned(optH, enc, dOptH, dEnc), "vd_score_ce_dense_p: pointer must be 16-byte aligned and leading dimension a multiple of 4 (optH, enc, dOptH, dEnc; H=%d)", H);
   VD_CHECK_ARG(mix >= 0.f && mix <= 1.f, "vd_score_ce_dense_p: the mix %g is not in [0, 1]", (double)mix);
   if (N == 0) return VD_OK;
   hipLaunchKernelGGL(score_ce_dense_kernel, dim3(N), dim3(256), 0, stream, optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale, mix,
@@ -449,6 +458,7 @@ int vd_score_ce_dense_live_p(const float* optH, const float* enc, const int32_t*
   VD_CHECK_ARG(optH && enc && scores && gt && rel && live_slot && loss_rows && N >= 0 && O >= 1 && O <= MAX_OPT && H % 4 == 0,
                "vd_score_ce_dense_live_p: bad args (O=%d must be <= %d; the live dense head needs gt, rel, live_slot and loss_rows)", O, MAX_OPT);
   VD_CHECK_ARG((dOptH == nullptr) == (dEnc == nullptr), "vd_score_ce_dense_live_p: dOptH and dEnc go together");
+  VD_CHECK_ARG(score_ce_aligned(optH, enc, dOptH, dEnc), "vd_score_ce_dense_live_p: pointer must be 16-byte aligned and leading dimension a multiple of 4 (optH, enc, dOptH, dEnc; H=%d)", H);
   VD_CHECK_ARG(mix >= 0.f && mix <= 1.f, "vd_score_ce_dense_live_p: the mix %g is not in [0, 1]", (double)mix);
   if (N == 0) return VD_OK;
   hipLaunchKernelGGL(score_ce_dense_live_kernel, dim3(N), dim3(256), 0, stream, optH, enc, gt, scores, loss_rows, dOptH, dEnc, O, H, gscale,
