@@ -19,8 +19,8 @@
 //   A: each wave reads only its own 32 rows, so they go global -> registers, one macro step ahead: lane l holds k = 8 (l >> 4) .. + 7 of rows
 //      l & 15 and 16 + (l & 15), 2 x 32 contiguous bytes; the four lanes of a row fetch one 128-byte line.
 //   B: three planes [128 x 32] bf16 by LDS-DMA, 64-byte rows, 24 KB per stage, two stages = 48 KB; chunk swizzle split_swz (below):
-//      ds_read_b128 conflict-free.  Per plane the eight fragments are read once and multiplied with the three A planes of both row halves,
-//      column tile innermost: consecutive MFMAs never share an accumulator.
+//      ds_read_b128 conflict-free.  Per plane the eight fragments are read once, four at a time (16 registers), and multiplied with the
+//      three A planes of both row halves, column tile innermost: consecutive MFMAs never share an accumulator.
 //   Workgroup: four waves (128 x 128), three per CU -- 3 x 48 KB = 144 KB of LDS.  The suggested six-wave workgroup (192 rows, two per CU,
 //      96 KB) keeps the same 12 waves per CU but measured SLOWER than the 32x32x16 kernel (434 / 498 us per forward / backward launch in
 //      the step against 374 / 437): with two workgroups per CU the epilogue of one (gates, c, h, the projection-table gather) has only one
@@ -36,17 +36,49 @@
 
 typedef __bf16 vd_bf16x8 __attribute__((ext_vector_type(8)));
 
+// The split's four operations as ONE vector instruction each.  Written out in C++ the compiler SLP-packs neighbouring subtractions into
+// v_pk_add_f32 (which costs more beside MFMAs than the two v_sub_f32 it replaces), converts some values singly and re-packs them, and
+// copies registers in between; here a pair of values costs 3 conversions, 4 unpacks and 4 subtractions, 5.5 instructions per value
+// (scripts/loop_isa.py, profiles/split_loop_isa.txt).  The conversion is the instruction the compiler chooses too: RNE, bf16(a) low.
+__device__ __forceinline__ unsigned vd_cvt_pk_bf16(float a, float b) {
+  unsigned r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ float vd_bf16_lo_f32(unsigned p) {    // the low bf16 of a pair as fp32
+  float r;
+  asm("v_lshlrev_b32 %0, 16, %1" : "=v"(r) : "v"(p));
+  return r;
+}
+__device__ __forceinline__ float vd_bf16_hi_f32(unsigned p) {    // the high one
+  float r;
+  asm("v_and_b32 %0, 0xffff0000, %1" : "=v"(r) : "v"(p));
+  return r;
+}
+__device__ __forceinline__ float vd_sub_f32(float a, float b) {
+  float r;
+  asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// two values -> their packed hi / mid / lo: hi = RNE(v), mid = RNE(v - hi), lo = RNE(v - hi - mid); both subtractions are exact
+__device__ __forceinline__ void vd_split3_pair(float a, float b, unsigned& hi, unsigned& mid, unsigned& lo) {
+  hi = vd_cvt_pk_bf16(a, b);
+  const float ra = vd_sub_f32(a, vd_bf16_lo_f32(hi)), rb = vd_sub_f32(b, vd_bf16_hi_f32(hi));
+  mid = vd_cvt_pk_bf16(ra, rb);
+  lo = vd_cvt_pk_bf16(vd_sub_f32(ra, vd_bf16_lo_f32(mid)), vd_sub_f32(rb, vd_bf16_hi_f32(mid)));
+}
+
+typedef unsigned vd_u32x4 __attribute__((ext_vector_type(4)));
 // v (8 consecutive k of one row) -> hi / mid / lo planes
 __device__ __forceinline__ void vd_split3(const float4& u, const float4& w, vd_bf16x8& hi, vd_bf16x8& mid, vd_bf16x8& lo) {
-  const float v[8] = {u.x, u.y, u.z, u.w, w.x, w.y, w.z, w.w};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 h = (__bf16)v[i];
-    const float r1 = v[i] - (float)h;          // exact: the leading 8 bits cancel
-    const __bf16 m = (__bf16)r1;
-    const float r2 = r1 - (float)m;            // exact
-    hi[i] = h; mid[i] = m; lo[i] = (__bf16)r2;
-  }
+  unsigned h[4], m[4], l[4];
+  vd_split3_pair(u.x, u.y, h[0], m[0], l[0]);
+  vd_split3_pair(u.z, u.w, h[1], m[1], l[1]);
+  vd_split3_pair(w.x, w.y, h[2], m[2], l[2]);
+  vd_split3_pair(w.z, w.w, h[3], m[3], l[3]);
+  hi = __builtin_bit_cast(vd_bf16x8, (vd_u32x4){h[0], h[1], h[2], h[3]});
+  mid = __builtin_bit_cast(vd_bf16x8, (vd_u32x4){m[0], m[1], m[2], m[3]});
+  lo = __builtin_bit_cast(vd_bf16x8, (vd_u32x4){l[0], l[1], l[2], l[3]});
 }
 
 // fp32 matrix -> three bf16 planes (dst + p * plane), same element order
@@ -181,28 +213,51 @@ gemm_split_kernel(int M, int N, int K, int tiles_n, const float* A, long lda, co
   };
   const int bfrag = l15 * 64 + ((g ^ split_swz(l15 >> 2)) * 16);  // this lane's 8 bf16 k of column l15 of a 16-column tile
 
-  if (nm > 0) {
-    issue_b(0, 0);
-    load_a(0);
-    int st = 0;
-    for (int m = 0; m < nm; ++m) {
-      vd_bf16x8 ap[2][3];
+  // the same when macro step m is known to be a full one: no predicate, no zero fill, no source offset
+  auto load_a_full = [&](int m) {
+    const char* ak = reinterpret_cast<const char*>(A + (long)m * 32);
 #pragma unroll
-      for (int rt = 0; rt < 2; ++rt) vd_split3(an[rt][0], an[rt][1], ap[rt][0], ap[rt][1], ap[rt][2]);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_barrier" ::: "memory");                    // every wave's share of macro step m has landed
-      if (m + 1 < nm) {                                          // step m + 1 flies under the 144 MFMAs of step m
-        issue_b(m + 1, st ^ 1);
-        load_a(m + 1);
-      }
-      const char* sbase = reinterpret_cast<const char*>(smem) + st * Cfg::STAGE + bfrag;
-      // plane p of B against planes i of A, smallest terms first; column tile innermost: consecutive MFMAs never share an accumulator
+    for (int rt = 0; rt < 2; ++rt) {
+      an[rt][0] = *reinterpret_cast<const float4*>(ak + aoff[rt]);
+      an[rt][1] = *reinterpret_cast<const float4*>(ak + aoff[rt] + 16);
+    }
+  };
+  auto issue_b_full = [&](int m, int st) {
 #pragma unroll
-      for (int p = 2; p >= 0; --p) {
-        vd_bf16x8 bp[2 * NT];
+    for (int i = 0; i < NIB; ++i) {
+      const int q = wm * NIB + i;
+      glds16(voffb[i], reinterpret_cast<const float*>(B + (long)(q >> 3) * bplane + (long)m * 32), lds0 + st * Cfg::STAGE + q * 1024);
+    }
+  };
+
+  // one macro step on stage st; full_next: step m + 1 exists and is a full one
+  auto step = [&](int m, int st, auto full_next) {
+    vd_bf16x8 ap[2][3];
 #pragma unroll
-        for (int j = 0; j < 2 * NT; ++j) {
-          const vd_f32x4 t = *reinterpret_cast<const vd_f32x4*>(sbase + p * Cfg::BTILE + j * 1024);
+    for (int rt = 0; rt < 2; ++rt) vd_split3(an[rt][0], an[rt][1], ap[rt][0], ap[rt][1], ap[rt][2]);
+    __builtin_amdgcn_sched_barrier(0);                         // the split in front of the barrier, not behind it
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_barrier" ::: "memory");                    // every wave's share of macro step m has landed
+    if constexpr (decltype(full_next)::value) {                // step m + 1 flies under the 144 MFMAs of step m
+      issue_b_full(m + 1, st ^ 1);
+      load_a_full(m + 1);
+    } else if (m + 1 < nm) {
+      issue_b(m + 1, st ^ 1);
+      load_a(m + 1);
+    }
+    // the loads stay HERE, in front of the MFMAs they fly under (the split above has freed their registers; left free, the scheduler
+    // sinks them to the end of the step to save registers and the next step's split waits for them with nothing in between)
+    __builtin_amdgcn_sched_barrier(0);
+    const char* sbase = reinterpret_cast<const char*>(smem) + st * Cfg::STAGE + bfrag;
+    // plane p of B against planes i of A, smallest terms first; column tile innermost: consecutive MFMAs never share an accumulator
+#pragma unroll
+    for (int p = 2; p >= 0; --p)
+#pragma unroll
+      for (int jh = 0; jh < 2; ++jh) {                         // four column tiles at a time: 16 fragment registers, not 32
+        vd_bf16x8 bp[NT];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          const vd_f32x4 t = *reinterpret_cast<const vd_f32x4*>(sbase + p * Cfg::BTILE + (jh * NT + j) * 1024);
           bp[j] = __builtin_bit_cast(vd_bf16x8, t);
         }
 #pragma unroll
@@ -212,11 +267,22 @@ gemm_split_kernel(int M, int N, int K, int tiles_n, const float* A, long lda, co
 #pragma unroll
           for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-            for (int j = 0; j < 2 * NT; ++j) acc[rt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[rt][i], bp[j], acc[rt][j], 0, 0, 0);
+            for (int j = 0; j < NT; ++j)
+              acc[rt][jh * NT + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[rt][i], bp[j], acc[rt][jh * NT + j], 0, 0, 0);
         }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // stage `st` may be refilled
-      st ^= 1;
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // stage `st` may be refilled
+  };
+  if (nm > 0) {
+    issue_b(0, 0);
+    load_a(0);
+    // The main loop runs the full steps that a full step follows: unconditional loads, nothing but the split between the MFMAs.  Peeled
+    // behind it: the last full step (which may prefetch the half step) and the half step itself, K = 16 (mod 32), with the predicated loads.
+    int m = 0;
+    for (; m + 1 < nfull; ++m) step(m, m & 1, std::true_type{});
+    if (m < nm) {
+      step(m, m & 1, std::false_type{});
+      if (++m < nm) step(m, m & 1, std::false_type{});
     }
   }
   // the epilogues take 32 x 32 tiles in the layout of the 32x32 MFMAs: each 2 x 2 quad of 16 x 16 results goes through the wave's scratch once
@@ -324,65 +390,79 @@ gemm_split_tn_kernel(int M, int N, int kchunk, int K, int tiles, int tiles_n, in
   };
   const int hi = lane >> 5, l31 = lane & 31;
 
-  if (nm > 0) {
-    issue(0, 0);
-    int st = 0;
-    for (int m = 0; m < nm; ++m) {
-      if (m + 1 < nm) {
-        issue(m + 1, st ^ 1);
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      asm volatile("s_barrier" ::: "memory");
-      const float* sA = reinterpret_cast<const float*>(reinterpret_cast<const char*>(smem) + st * Cfg::STAGE) + (hi * 8) * Cfg::BM + wm * 64 + l31;
-      const float* sB = reinterpret_cast<const float*>(reinterpret_cast<const char*>(smem) + st * Cfg::STAGE + Cfg::ATILE) + (hi * 8) * Cfg::BN + l31;
-      // Software pipeline inside the step: the A planes and the B planes of column tile 0 are converted up front; then the 18 MFMAs of column
-      // tile j are issued INTERLEAVED with the fragment reads and the split of column tile j + 1 (sched_group_barrier: one MFMA, four VALU
-      // instructions, ...), so most of the ~240 VALU instructions a step spends on splitting sit in the shadow of the matrix pipe instead of
-      // in front of it (left to itself the compiler hoists every conversion above the first MFMA: 5.91 -> 5.51 ms on the headline dWh).
-      // (Measured and dropped: three LDS stages with one barrier per step and the NEXT step's first conversions under the last column
-      //  tile's MFMAs -- 5.82 ms; largest products first so that a step's first MFMAs need only the hi planes -- 5.68 vs 5.61 ms.)
-      vd_bf16x8 ap[2][3], bp[2][3];
-      auto load_b = [&](int j, vd_bf16x8 (&dst)[3]) {
-        const float* p = sB + j * 32;
-        const float4 u = make_float4(p[0], p[Cfg::BN], p[2 * Cfg::BN], p[3 * Cfg::BN]);
-        const float4 w = make_float4(p[4 * Cfg::BN], p[5 * Cfg::BN], p[6 * Cfg::BN], p[7 * Cfg::BN]);
-        vd_split3(u, w, dst[0], dst[1], dst[2]);
-      };
+  // one 16-k step on stage ST, a compile-time constant: every LDS address of the step is then one of two lane registers plus an immediate
+  // (the second 32-row block of A gets a base of its own, opaque to the compiler, which then pairs the k rows of one block into
+  //  ds_read2st64_b32 with immediate offsets; given one base it pairs the two blocks of a k row and spends a register or an add per k row)
+  int mb1 = 32;
+  asm("" : "+v"(mb1));
+  const float* sA0 = smem + (hi * 8) * Cfg::BM + wm * 64 + l31;
+  const float* sA1 = sA0 + mb1;
+  const float* sB0 = smem + Cfg::ATILE / 4 + (hi * 8) * Cfg::BN + l31;
+  auto step = [&](int m, auto stage) {
+    constexpr int st = decltype(stage)::value;
+    if (m + 1 < nm) {
+      issue(m + 1, st ^ 1);
+      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    asm volatile("s_barrier" ::: "memory");
+    const float* sB = sB0 + st * (Cfg::STAGE / 4);
+    // Software pipeline inside the step: the A planes and the B planes of column tile 0 are converted up front; then the 18 MFMAs of column
+    // tile j are issued INTERLEAVED with the fragment reads and the split of column tile j + 1 (sched_group_barrier: one MFMA, four VALU
+    // instructions, ...), so most of the ~240 VALU instructions a step spends on splitting sit in the shadow of the matrix pipe instead of
+    // in front of it (left to itself the compiler hoists every conversion above the first MFMA: 5.91 -> 5.51 ms on the headline dWh).
+    // The split's instructions are inline asm (vd_split3), which the group barriers do not count as VALU: they order the MFMAs and the
+    // fragment reads, and the split falls between them by its dependences -- coarser than four per MFMA (profiles/split_loop_issue.txt).
+    // (Measured and dropped: three LDS stages with one barrier per step and the NEXT step's first conversions under the last column
+    //  tile's MFMAs -- 5.82 ms; largest products first so that a step's first MFMAs need only the hi planes -- 5.68 vs 5.61 ms.)
+    vd_bf16x8 ap[2][3], bp[2][3];
+    auto load_b = [&](int j, vd_bf16x8 (&dst)[3]) {
+      const float* p = sB + j * 32;
+      const float4 u = make_float4(p[0], p[Cfg::BN], p[2 * Cfg::BN], p[3 * Cfg::BN]);
+      const float4 w = make_float4(p[4 * Cfg::BN], p[5 * Cfg::BN], p[6 * Cfg::BN], p[7 * Cfg::BN]);
+      vd_split3(u, w, dst[0], dst[1], dst[2]);
+    };
 #pragma unroll
-      for (int mb = 0; mb < 2; ++mb) {
-        const float* p = sA + mb * 32;
-        const float4 u = make_float4(p[0], p[Cfg::BM], p[2 * Cfg::BM], p[3 * Cfg::BM]);
-        const float4 w = make_float4(p[4 * Cfg::BM], p[5 * Cfg::BM], p[6 * Cfg::BM], p[7 * Cfg::BM]);
-        vd_split3(u, w, ap[mb][0], ap[mb][1], ap[mb][2]);
-      }
-      load_b(0, bp[0]);
+    for (int mb = 0; mb < 2; ++mb) {
+      const float* p = (mb ? sA1 : sA0) + st * (Cfg::STAGE / 4);
+      const float4 u = make_float4(p[0], p[Cfg::BM], p[2 * Cfg::BM], p[3 * Cfg::BM]);
+      const float4 w = make_float4(p[4 * Cfg::BM], p[5 * Cfg::BM], p[6 * Cfg::BM], p[7 * Cfg::BM]);
+      vd_split3(u, w, ap[mb][0], ap[mb][1], ap[mb][2]);
+    }
+    load_b(0, bp[0]);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        __builtin_amdgcn_sched_barrier(0);
-        if (j + 1 < 4) load_b(j + 1, bp[(j + 1) & 1]);
+    for (int j = 0; j < 4; ++j) {
+      __builtin_amdgcn_sched_barrier(0);
+      if (j + 1 < 4) load_b(j + 1, bp[(j + 1) & 1]);
 #pragma unroll
-        for (int pb = 2; pb >= 0; --pb)
+      for (int pb = 2; pb >= 0; --pb)
 #pragma unroll
-          for (int pa = 2; pa >= 0; --pa) {
-            constexpr int LIM = NPROD >= 9 ? 4 : NPROD >= 6 ? 2 : NPROD >= 3 ? 1 : 0;
-            if (pa + pb > LIM) continue;
+        for (int pa = 2; pa >= 0; --pa) {
+          constexpr int LIM = NPROD >= 9 ? 4 : NPROD >= 6 ? 2 : NPROD >= 3 ? 1 : 0;
+          if (pa + pb > LIM) continue;
 #pragma unroll
-            for (int mb = 0; mb < 2; ++mb) acc[mb][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[mb][pa], bp[j & 1][pb], acc[mb][j], 0, 0, 0);
-          }
-        if (j + 1 < 4) {
-          __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);        // the next tile's fragment reads first (their latency hides under the MFMAs)
+          for (int mb = 0; mb < 2; ++mb) acc[mb][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[mb][pa], bp[j & 1][pb], acc[mb][j], 0, 0, 0);
+        }
+      if (j + 1 < 4) {
+        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);        // the next tile's fragment reads first (their latency hides under the MFMAs)
 #pragma unroll
-          for (int i = 0; i < 18; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA ...
-            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);      // ... four VALU instructions of the next tile's split
-          }
+        for (int i = 0; i < 18; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA ...
+          __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);      // ... four VALU instructions of the next tile's split
         }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      st ^= 1;
     }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  };
+  if (nm > 0) {
+    issue(0, 0);
+    int m = 0;
+    for (; m + 1 < nm; m += 2) {
+      step(m, std::integral_constant<int, 0>{});
+      step(m + 1, std::integral_constant<int, 1>{});
+    }
+    if (m < nm) step(m, std::integral_constant<int, 0>{});
   }
   if (nm == 0) return;                            // (a K range past the end: the range count is rounded up to a multiple of 8)
   const EpiAtomic<4> e{C, ldc};
