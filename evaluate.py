@@ -60,7 +60,13 @@ def parse_args(argv=None):
     ap.add_argument('-denseAnnotations', '--denseAnnotations', default='',
                     help='a file of dense relevance annotations (VisDial v1.0: a JSON list of {image_id, round_id, gt_relevance}): also print the '
                          'NDCG of the annotated rounds of the split (csrc/loss.hip DT2; -host native: on the device) and add it to their records')
+    ap.add_argument('-imgRegions', '--imgRegions', type=int, default=0,
+                    help='M > 0 (-host native, the two att encoders): -inputImg holds regions_<split> [n x M x C] and num_regions_<split> [n]; '
+                         'every image attends its own regions only (csrc/attention.hip IR1 - IR6).  A property of the data: it comes '
+                         'from this command line, not from the checkpoint.  0 = off')
     a = ap.parse_args(argv)
+    if a.imgRegions < 0:
+        raise SystemExit('-imgRegions %d must be an integer >= 0 (0 = off: one S x S grid per image)' % a.imgRegions)
     if a.rolloutHistory == 'concat' and not a.rollout:
         raise SystemExit('-rolloutHistory concat is the history rule of a rollout: it needs -rollout 1')
     if a.rolloutEncoder == 'round':
@@ -97,6 +103,11 @@ def main(argv=None):
     saved = load_checkpoint(a.loadPath)
     p = opts.derive(saved['modelParams'])                    # sets useHistory / useIm / concatHistory (evaluate.lua:69-75)
     p['gpuid'], p['batchSize'], p['useGt'] = a.gpuid, a.batchSize, bool(a.useGt)
+    p['imgRegions'], p['host'] = a.imgRegions, a.host
+    try:
+        opts.apply_img_regions(p)                            # -imgRegions M: refusals by name, imgSpatialSize = ceil(sqrt(M))
+    except ValueError as e:
+        raise SystemExit(str(e))
     if a.fusedLhood and p['decoder'] != 'gen':
         raise SystemExit('-fusedLhood %d: the live-row log-likelihood head is only for a generative model' % a.fusedLhood)
     if a.fusedLhood == 2 and a.host != 'native':
@@ -113,7 +124,10 @@ def main(argv=None):
     p.update(inputImg=a.inputImg, inputQues=a.inputQues, inputJson=a.inputJson)
     have = lambda f: os.path.exists(f) or os.path.exists(f[:-3] + '.npz')
     if os.path.exists(a.inputJson) and have(a.inputQues):
-        dl = Dataloader(seed=1234).initialize(p, [a.split])                      # evaluate.lua:80-81
+        try:
+            dl = Dataloader(seed=1234).initialize(p, [a.split])                  # evaluate.lua:80-81
+        except ValueError as e:                                                  # (-imgRegions: a dataset that does not hold M regions)
+            raise SystemExit(str(e))
         for k in ('vocabSize', 'maxQuesCount', 'maxQuesLen', 'maxAnsLen', 'numOptions'):
             p[k] = getattr(dl, k)
     else:

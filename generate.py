@@ -61,7 +61,12 @@ def parse_args(argv=None):
     ap.add_argument('-gpuid', '--gpuid', type=int, default=0)
     ap.add_argument('-host', '--host', default='python', choices=['python', 'native'],
                     help="'native' drives the model-level C ABI (what lua/model.lua calls)")
+    ap.add_argument('-imgRegions', '--imgRegions', type=int, default=0,
+                    help='M > 0 (-host native, the two att encoders): -inputImg holds regions_<split> [n x M x C] and num_regions_<split> [n]; '
+                         'every image attends its own regions only (csrc/attention.hip IR1 - IR6); from this command line, not the checkpoint')
     a = vars(ap.parse_args(argv))
+    if a['imgRegions'] < 0:
+        raise ValueError('-imgRegions %d must be an integer >= 0 (0 = off: one S x S grid per image)' % a['imgRegions'])
     if a['topK'] < 0 or not (0.0 < a['topP'] <= 1.0):
         raise ValueError('-topK %d must be >= 0 (0 = off) and -topP %g in (0, 1] (1 = off)' % (a['topK'], a['topP']))
     if (a['topK'] != 0 or a['topP'] != 1.0) and a['sampleWords'] != 1:
@@ -93,6 +98,8 @@ def main():
     saved = load_checkpoint(a['loadPath'])
     p = opts.derive(saved['modelParams'])                      # generate.lua:57-70
     p['gpuid'] = a['gpuid']
+    p['imgRegions'], p['host'] = a['imgRegions'], a['host']
+    opts.apply_img_regions(p)                                  # -imgRegions M: refusals by name, imgSpatialSize = ceil(sqrt(M))
     p.update(inputImg=a['inputImg'], inputQues=a['inputQues'], inputJson=a['inputJson'])
     # generate.lua:57-70 derives useHistory / useIm for the dataloader but NOT concatHistory (train.lua and evaluate.lua do): the history
     # of a generation run is the previous round's question + answer even for the lf-* encoders, with the default maxHistoryLen.

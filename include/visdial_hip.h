@@ -447,7 +447,18 @@ int vd_model_init_params(vd_model* m, uint64_t seed);     /* library-default ini
  * summation order (a round of weight 0 adds exact zeros).  After such a step vd_model_scores holds the live rounds' scores and 0.0 in
  * every other round's row, and vd_model_option_rows reports (n_live * O, N * O).  With every round live it IS "@dense_relevance".
  * only_forward = 1, retrieval and "@ndcg" see all rounds either way.  Refused by name: a model with lstmBf16 = 1 (rules DL1-DL5 at the
- * top of csrc/loss.hip). */
+ * top of csrc/loss.hip).
+ * "@img_regions", n = B floats: the number of live regions of every image of the batch uploaded last, for the two encoders with the image
+ * attention (mn-att-ques-im-hist, lf-att-ques-im-hist) -- detector regions, a different number per image, padded to imgSpatialSize^2 rows
+ * in img_feat.  Every value is an integer in 1 .. imgSpatialSize^2; they come as floats because that is the signature.  The image
+ * attention of every pass over that upload (training step, only_forward, retrieval, encode, beam search, sampling, both rollouts and the
+ * round pass) then looks at the first counts[b] regions of image b and at nothing else: softmax over the live regions, probability +0.0
+ * and zero gradient for the others (rules IR1-IR6 at the top of csrc/attention.hip).  The hidden rows of img_feat must be finite (write
+ * zeros): the dense products still read them.  Same transport as "@dense_relevance": checked on the host, staged in pinned memory, copied
+ * on the upload lane, no wait for a step, dropped by the next upload into the slot, replaced by a second attachment on the same upload.
+ * With every count = imgSpatialSize^2 the outputs are the unattached pass's (bit for bit where no atomic is involved).  Argument errors
+ * that name the attachment: a call before any upload, an encoder without the image attention, n != B, a value that is not an integer in
+ * range.  Without the attachment every call launches what it launched before. */
 int vd_model_set_tensor(vd_model* m, const char* name, const float* host, int64_t n);   /* wrapperW:copy(...) */
 /* "@ndcg", which = 0, n = 2 N: runs the NDCG kernel on the scores of the last forward or retrieval of the current batch (either decoder)
  * and its "@dense_relevance"; `host` receives N DOUBLES, bit for bit, in the 2 N floats of the signature (read the buffer as double[N]).

@@ -46,7 +46,8 @@ def main():
         mp['gpuid'], mp['batchSize'] = opt['gpuid'], opt['batchSize']
         # run control and runtime (non-architectural) choices stay with the command line
         for k in ('numEpochs', 'maxIters', 'savePath', 'saveIter', 'host', 'lstmPrecision', 'saveFormat',
-                  'synthetic', 'labelSmoothing', 'gradClipNorm', 'weightDecay', 'denseAnnotations', 'denseMix', 'denseRows'):
+                  'synthetic', 'labelSmoothing', 'gradClipNorm', 'weightDecay', 'denseAnnotations', 'denseMix', 'denseRows',
+                  'imgRegions'):                                   # (a property of the data, not of the weights)
             mp[k] = opt.get(k)
     if mp.get('host', 'python') != 'native':                     # -labelSmoothing / -gradClipNorm / -weightDecay need -host native
         try:
@@ -57,12 +58,18 @@ def main():
     try:
         opts.check_dense(mp)                                     # -denseAnnotations with decoder gen / -labelSmoothing: before any model exists
         opts.check_dense_rows(mp)                                # -denseRows live without the annotations / with -lstmPrecision bf16
+        if saved is not None:
+            opts.apply_img_regions(mp)                           # -imgRegions M on a checkpoint: the grid of the command line's data
+            opt['imgSpatialSize'] = mp['imgSpatialSize']
     except ValueError as e:
         raise SystemExit(str(e))
     # the dataloader is built from the CURRENT command line (train.lua:47-48), never from paths stored in a checkpoint
     have = lambda p: os.path.exists(p) or os.path.exists(p[:-3] + '.npz')
     if os.path.exists(opt['inputJson']) and have(opt['inputQues']):
-        dataloader = Dataloader(seed=1234).initialize(opt, ['train'])            # real VisDial files
+        try:
+            dataloader = Dataloader(seed=1234).initialize(opt, ['train'])        # real VisDial files
+        except ValueError as e:                                                  # (-imgRegions: a dataset that does not hold M regions)
+            raise SystemExit(str(e))
     elif opt['loadPath'] and not opt.get('synthetic'):
         raise SystemExit('-loadPath given but no dataset at %s / %s: refusing to resume on synthetic data '
                          '(pass -synthetic 1 to force)' % (opt['inputJson'], opt['inputQues']))

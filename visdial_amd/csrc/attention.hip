@@ -10,6 +10,21 @@
 //    L2/MALL-resident and the GEMM operand loader applies the per-round dropout mask
 //    (SURVEY.md H4).  img_common + ques_common + tanh + dropout run in the MFMA epilogue;
 //    score/softmax(196)/weighted-sum is one wave-reduction kernel per QA round (K7).
+//
+// Image regions (batch attachment "@img_regions", runtime.hip): an image may carry fewer than S2 regions -- detector boxes, a different number
+// per image, padded to S2 rows.  cnt [B] int32 holds the number of regions of every image; the four streaming kernels of the attention head
+// then have a second instantiation of the same body that walks the live regions only.  The rules, restated in fp64 by tests/region_ref.py:
+//  IR1: region s of image b is live iff s < cnt[b], with 1 <= cnt[b] <= S2.  Round n reads cnt[n / R]; with R = 1 the index is the row, which
+//       is the form forward_round uses.  The count is uniform over a workgroup: a scalar load and a uniform trip count, no divergence.
+//  IR2: the maximum, the sum and the softmax of the scores run over the live regions only; p[n, s] is written as exact +0.0 for s >= cnt.
+//       Hidden regions are left out of the reductions, not pushed to -9999999, and a hidden row of iqc is never read.
+//  IR3: the weighted sum and dp run over s < cnt: hidden rows of pre and of mask1 are never read by these two kernels.
+//  IR4: the backward writes exact zeros for every hidden region: dscore[n, s] = 0 for s >= cnt, hidden rows of dz are written as 0 without
+//       being read first, and dqc, dwa and dba add live regions only.  The three dense products, the bias column sum and img_proj's backward
+//       then need no change: a hidden row contributes 0 * finite.
+//  IR5: the hidden rows of the uploaded features must be finite, because the dense products still read them; the loaders write zeros there.
+//  IR6: with cnt[b] = S2 for every image each output that involves no atomic (p, u1, dscore, dz, dqc) is the unmasked kernel's bit for bit:
+//       the loop bounds are the only thing that changes.
 #include "gemm_core.h"
 #include "split_core.h"
 
@@ -355,15 +370,23 @@ __device__ __forceinline__ float block_reduce(float v, float* red, int wave, int
   return r;
 }
 
-__global__ void __launch_bounds__(IMG_ATT_WAVES * 64)
-img_att_score_kernel(const float* __restrict__ iqc, const float* __restrict__ wa, const float* __restrict__ ba,
-                     float* __restrict__ p_out, int S2, int Kc) {
+// The live region count of round n (IR1).  The unmasked instantiations (cnt is not read) keep S2, so their loops are what they were.
+template <bool MASKED>
+__device__ __forceinline__ int img_live_regions(const int32_t* __restrict__ cnt, int n, int R, int S2) {
+  if (!MASKED) return S2;
+  return max(0, min(cnt[n / R], S2));   // n = blockIdx.x: a scalar load, uniform over the workgroup; clamped: no count can index outside a round
+}
+
+// One body per kernel: L = S2 is the kernel as it was, L = cnt[n / R] its "_regions" twin (IR2 - IR4).
+template <bool MASKED>
+__device__ __forceinline__ void img_att_score_body(const float* __restrict__ iqc, const float* __restrict__ wa, const float* __restrict__ ba,
+                                                   float* __restrict__ p_out, int L, int S2, int Kc) {
   extern __shared__ float sc[];  // [S2]
   __shared__ float red[IMG_ATT_WAVES];
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* iq = iqc + (long)n * S2 * Kc;
   const float b0 = ba[0];
-  for (int s = wave; s < S2; s += IMG_ATT_WAVES) {
+  for (int s = wave; s < L; s += IMG_ATT_WAVES) {
     float a = 0.f;
     for (int k = lane * 4; k < Kc; k += 256) {
       const float4 v = *reinterpret_cast<const float4*>(iq + (long)s * Kc + k);
@@ -375,37 +398,47 @@ img_att_score_kernel(const float* __restrict__ iqc, const float* __restrict__ wa
   }
   __syncthreads();
   float mx = -INFINITY;
-  for (int s = tid; s < S2; s += IMG_ATT_WAVES * 64) mx = fmaxf(mx, sc[s]);
+  for (int s = tid; s < L; s += IMG_ATT_WAVES * 64) mx = fmaxf(mx, sc[s]);
   mx = block_reduce(mx, red, wave, lane, true);
   float sum = 0.f;
-  for (int s = tid; s < S2; s += IMG_ATT_WAVES * 64) {
+  for (int s = tid; s < L; s += IMG_ATT_WAVES * 64) {
     const float e = expf(sc[s] - mx);
     sc[s] = e;
     sum += e;
   }
   sum = block_reduce(sum, red, wave, lane, false);
   const float inv = 1.f / sum;
-  for (int s = tid; s < S2; s += IMG_ATT_WAVES * 64) p_out[(long)n * S2 + s] = sc[s] * inv;
+  for (int s = tid; s < S2; s += IMG_ATT_WAVES * 64) p_out[(long)n * S2 + s] = (!MASKED || s < L) ? sc[s] * inv : 0.f;
+}
+__global__ void __launch_bounds__(IMG_ATT_WAVES * 64)
+img_att_score_kernel(const float* __restrict__ iqc, const float* __restrict__ wa, const float* __restrict__ ba,
+                     float* __restrict__ p_out, int S2, int Kc) {
+  img_att_score_body<false>(iqc, wa, ba, p_out, S2, S2, Kc);
+}
+__global__ void __launch_bounds__(IMG_ATT_WAVES * 64)
+img_att_score_regions_kernel(const float* __restrict__ iqc, const float* __restrict__ wa, const float* __restrict__ ba,
+                             float* __restrict__ p_out, const int32_t* __restrict__ cnt, int S2, int R, int Kc) {
+  img_att_score_body<true>(iqc, wa, ba, p_out, img_live_regions<true>(cnt, blockIdx.x, R, S2), S2, Kc);
 }
 
 // 256 threads = 8 region groups x 32 lanes; lane l owns 4 consecutive channels of a 128-channel tile.
-__global__ void __launch_bounds__(256)
-img_att_wsum_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ mask1,
-                    const float* __restrict__ p, const float* __restrict__ u0, float* __restrict__ u1, int S2,
-                    int R, int H, float scale) {
+template <bool MASKED>
+__device__ __forceinline__ void img_att_wsum_body(const float* __restrict__ pre, const uint8_t* __restrict__ mask1, const float* __restrict__ p,
+                                                  const float* __restrict__ u0, float* __restrict__ u1, int L, int S2, int R, int H,
+                                                  float scale) {
   extern __shared__ float sh[];  // p [S2] | partial sums [8][128]
   float* ps = sh;
   float* part = sh + ((S2 + 3) & ~3);
   const int n = blockIdx.x, tid = threadIdx.x, g = tid >> 5, l = tid & 31;
   const int h = blockIdx.y * 128 + l * 4;
-  for (int s = tid; s < S2; s += 256) ps[s] = p[(long)n * S2 + s];
+  for (int s = tid; s < L; s += 256) ps[s] = p[(long)n * S2 + s];
   __syncthreads();
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   if (h < H) {
     const float* pr = pre + (long)(n / R) * S2 * H + h;
     const uint8_t* m1 = mask1 ? mask1 + (long)n * S2 * H + h : nullptr;
 #pragma unroll 4
-    for (int s = g; s < S2; s += 8) {
+    for (int s = g; s < L; s += 8) {
       float4 v = *reinterpret_cast<const float4*>(pr + (long)s * H);
       if (m1) {
         const uint32_t m = *reinterpret_cast<const uint32_t*>(m1 + (long)s * H);
@@ -430,6 +463,18 @@ img_att_wsum_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ m
     *reinterpret_cast<float4*>(u1 + (long)n * H + h) = t;
   }
 }
+__global__ void __launch_bounds__(256)
+img_att_wsum_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ mask1,
+                    const float* __restrict__ p, const float* __restrict__ u0, float* __restrict__ u1, int S2,
+                    int R, int H, float scale) {
+  img_att_wsum_body<false>(pre, mask1, p, u0, u1, S2, S2, R, H, scale);
+}
+__global__ void __launch_bounds__(256)
+img_att_wsum_regions_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ mask1, const float* __restrict__ p,
+                            const float* __restrict__ u0, float* __restrict__ u1, const int32_t* __restrict__ cnt, int S2, int R, int H,
+                            float scale) {
+  img_att_wsum_body<true>(pre, mask1, p, u0, u1, img_live_regions<true>(cnt, blockIdx.x, R, S2), S2, R, H, scale);
+}
 
 // ---------------------------------------------------------------------------
 // Backward of the attention head + of the tanh/dropout epilogue of img_common.  Per QA round n:
@@ -438,17 +483,17 @@ img_att_wsum_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ m
 //   dz[n,s,k] = dscore[s]*wa[k]*scale2*mask2*(1 - tanh^2)   (written over iqc in place)
 //   dqc[n,k] = sum_s dz[n,s,k]                                               (img_att_dz_kernel)
 // ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(IMG_ATT_WAVES * 64)
-img_att_dscore_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ mask1,
-                      const float* __restrict__ p, const float* __restrict__ datt, float* __restrict__ dscore,
-                      float* __restrict__ dba, int S2, int R, int H, float scale) {
+template <bool MASKED>
+__device__ __forceinline__ void img_att_dscore_body(const float* __restrict__ pre, const uint8_t* __restrict__ mask1, const float* __restrict__ p,
+                                                    const float* __restrict__ datt, float* __restrict__ dscore, float* __restrict__ dba, int L,
+                                                    int S2, int R, int H, float scale) {
   extern __shared__ float sc[];  // dp [S2]
   __shared__ float red[IMG_ATT_WAVES];
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* pr = pre + (long)(n / R) * S2 * H;
   const uint8_t* m1 = mask1 ? mask1 + (long)n * S2 * H : nullptr;
   const float* da = datt + (long)n * H;
-  for (int s = wave; s < S2; s += IMG_ATT_WAVES) {
+  for (int s = wave; s < L; s += IMG_ATT_WAVES) {
     float a = 0.f;
     for (int h = lane * 4; h < H; h += 256) {
       float4 v = *reinterpret_cast<const float4*>(pr + (long)s * H + h);
@@ -467,28 +512,42 @@ img_att_dscore_kernel(const float* __restrict__ pre, const uint8_t* __restrict__
   }
   __syncthreads();
   float dot = 0.f;
-  for (int s = tid; s < S2; s += IMG_ATT_WAVES * 64) dot += p[(long)n * S2 + s] * sc[s];
+  for (int s = tid; s < L; s += IMG_ATT_WAVES * 64) dot += p[(long)n * S2 + s] * sc[s];
   dot = block_reduce(dot, red, wave, lane, false);
   float dsum = 0.f;
-  for (int s = tid; s < S2; s += IMG_ATT_WAVES * 64) {
+  for (int s = tid; s < L; s += IMG_ATT_WAVES * 64) {
     const float ds = p[(long)n * S2 + s] * (sc[s] - dot);
     dscore[(long)n * S2 + s] = ds;
     dsum += ds;
   }
+  if (MASKED)
+    for (int s = L + tid; s < S2; s += IMG_ATT_WAVES * 64) dscore[(long)n * S2 + s] = 0.f;
   dsum = block_reduce(dsum, red, wave, lane, false);
   if (tid == 0) unsafeAtomicAdd(dba, dsum);
 }
+__global__ void __launch_bounds__(IMG_ATT_WAVES * 64)
+img_att_dscore_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ mask1,
+                      const float* __restrict__ p, const float* __restrict__ datt, float* __restrict__ dscore,
+                      float* __restrict__ dba, int S2, int R, int H, float scale) {
+  img_att_dscore_body<false>(pre, mask1, p, datt, dscore, dba, S2, S2, R, H, scale);
+}
+__global__ void __launch_bounds__(IMG_ATT_WAVES * 64)
+img_att_dscore_regions_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ mask1, const float* __restrict__ p,
+                              const float* __restrict__ datt, float* __restrict__ dscore, float* __restrict__ dba,
+                              const int32_t* __restrict__ cnt, int S2, int R, int H, float scale) {
+  img_att_dscore_body<true>(pre, mask1, p, datt, dscore, dba, img_live_regions<true>(cnt, blockIdx.x, R, S2), S2, R, H, scale);
+}
 
-__global__ void __launch_bounds__(256)
-img_att_dz_kernel(float* __restrict__ iqc, const float* __restrict__ wa, const uint8_t* __restrict__ mask2,
-                  const float* __restrict__ dscore, float* __restrict__ dwa, float* __restrict__ dqc, int S2,
-                  int Kc, float scale) {
+template <bool MASKED>
+__device__ __forceinline__ void img_att_dz_body(float* __restrict__ iqc, const float* __restrict__ wa, const uint8_t* __restrict__ mask2,
+                                                const float* __restrict__ dscore, float* __restrict__ dwa, float* __restrict__ dqc, int L, int S2,
+                                                int Kc, float scale) {
   extern __shared__ float sh[];  // dscore [S2] | partial sums [2][8][128]
   float* dsv = sh;
   float* part = sh + ((S2 + 3) & ~3);
   const int n = blockIdx.x, tid = threadIdx.x, g = tid >> 5, l = tid & 31;
   const int k = blockIdx.y * 128 + l * 4;
-  for (int s = tid; s < S2; s += 256) dsv[s] = dscore[(long)n * S2 + s];
+  for (int s = tid; s < L; s += 256) dsv[s] = dscore[(long)n * S2 + s];
   __syncthreads();
   float4 aw = make_float4(0.f, 0.f, 0.f, 0.f), aq = aw;
   if (k < Kc) {
@@ -499,7 +558,7 @@ img_att_dz_kernel(float* __restrict__ iqc, const float* __restrict__ wa, const u
     float4 w = *reinterpret_cast<const float4*>(wa + k);
     w.x *= sc2; w.y *= sc2; w.z *= sc2; w.w *= sc2;
 #pragma unroll 4
-    for (int s = g; s < S2; s += 8) {
+    for (int s = g; s < L; s += 8) {
       const float4 y = *reinterpret_cast<const float4*>(iq + (long)s * Kc);
       const uint32_t m = m2 ? *reinterpret_cast<const uint32_t*>(m2 + (long)s * Kc) : 0xffffffffu;
       const float ds = dsv[s];
@@ -512,6 +571,8 @@ img_att_dz_kernel(float* __restrict__ iqc, const float* __restrict__ wa, const u
       *reinterpret_cast<float4*>(iq + (long)s * Kc) = dz;
       aq.x += dz.x; aq.y += dz.y; aq.z += dz.z; aq.w += dz.w;
     }
+    if (MASKED)   // the hidden rows of dz: written, never read (IR4)
+      for (int s = L + g; s < S2; s += 8) *reinterpret_cast<float4*>(iq + (long)s * Kc) = make_float4(0.f, 0.f, 0.f, 0.f);
   }
   *reinterpret_cast<float4*>(part + g * 128 + l * 4) = aw;
   *reinterpret_cast<float4*>(part + 1024 + g * 128 + l * 4) = aq;
@@ -531,6 +592,18 @@ img_att_dz_kernel(float* __restrict__ iqc, const float* __restrict__ wa, const u
     unsafeAtomicAdd(dwa + k + 2, tw.z);
     unsafeAtomicAdd(dwa + k + 3, tw.w);
   }
+}
+__global__ void __launch_bounds__(256)
+img_att_dz_kernel(float* __restrict__ iqc, const float* __restrict__ wa, const uint8_t* __restrict__ mask2,
+                  const float* __restrict__ dscore, float* __restrict__ dwa, float* __restrict__ dqc, int S2,
+                  int Kc, float scale) {
+  img_att_dz_body<false>(iqc, wa, mask2, dscore, dwa, dqc, S2, S2, Kc, scale);
+}
+__global__ void __launch_bounds__(256)
+img_att_dz_regions_kernel(float* __restrict__ iqc, const float* __restrict__ wa, const uint8_t* __restrict__ mask2,
+                          const float* __restrict__ dscore, float* __restrict__ dwa, float* __restrict__ dqc, const int32_t* __restrict__ cnt,
+                          int S2, int R, int Kc, float scale) {
+  img_att_dz_body<true>(iqc, wa, mask2, dscore, dwa, dqc, img_live_regions<true>(cnt, blockIdx.x, R, S2), S2, Kc, scale);
 }
 
 using CfgBigDB = GemmCfg<4, 1, 4, 32>;
@@ -683,6 +756,38 @@ int vd_img_common_wgrad(const float* dz, const float* pre, const uint8_t* mask1,
 }
 
 }  // extern "C"
+
+// The attention head over the live regions of every image (IR1 - IR6): cnt [ceil(N / R)] int32 on the device, or null = the C-ABI entry point,
+// argument for argument.  The caller holds every count to 1 .. S2 (runtime.hip validates an attachment on the host).
+int vd_img_att_forward_p(const float* iqc, const float* wa, const float* ba, const float* pre, const uint8_t* mask1, const float* u0, float* p,
+                         float* u1, int N, int R, int S2, int H, int Kc, float scale, const int32_t* cnt, hipStream_t stream) {
+  if (!cnt) return vd_img_att_forward(iqc, wa, ba, pre, mask1, u0, p, u1, N, R, S2, H, Kc, scale, stream);
+  VD_CHECK_ARG(iqc && wa && ba && pre && u0 && p && u1 && N >= 0 && R >= 1 && S2 >= 1 && Kc % 4 == 0 && H % 4 == 0, "vd_img_att_forward_p: bad args");
+  if (N == 0) return VD_OK;
+  hipLaunchKernelGGL(img_att_score_regions_kernel, dim3(N), dim3(IMG_ATT_WAVES * 64), S2 * sizeof(float), stream, iqc, wa, ba, p, cnt, S2, R, Kc);
+  VD_LAUNCH_CHECK();
+  const size_t lds = (((S2 + 3) & ~3) + 8 * 128) * sizeof(float);
+  hipLaunchKernelGGL(img_att_wsum_regions_kernel, dim3(N, vd_cdiv(H, 128)), dim3(256), lds, stream, pre, mask1, p, u0, u1, cnt, S2, R, H, scale);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+int vd_img_att_backward_p(float* iqc_dz, const float* wa, const float* pre, const uint8_t* mask1, const uint8_t* mask2, const float* p,
+                          const float* datt, float* dwa, float* dba, float* dqc, float* work, int N, int R, int S2, int H, int Kc, float scale,
+                          const int32_t* cnt, hipStream_t stream) {
+  if (!cnt) return vd_img_att_backward(iqc_dz, wa, pre, mask1, mask2, p, datt, dwa, dba, dqc, work, N, R, S2, H, Kc, scale, stream);
+  VD_CHECK_ARG(iqc_dz && wa && pre && p && datt && dwa && dba && dqc && work && N >= 0 && R >= 1 && S2 >= 1 && Kc % 4 == 0 && H % 4 == 0,
+               "vd_img_att_backward_p: bad args");
+  if (N == 0) return VD_OK;
+  hipLaunchKernelGGL(img_att_dscore_regions_kernel, dim3(N), dim3(IMG_ATT_WAVES * 64), S2 * sizeof(float), stream, pre, mask1, p, datt, work, dba,
+                     cnt, S2, R, H, scale);
+  VD_LAUNCH_CHECK();
+  const size_t lds = (((S2 + 3) & ~3) + 2 * 8 * 128) * sizeof(float);
+  hipLaunchKernelGGL(img_att_dz_regions_kernel, dim3(N, vd_cdiv(Kc, 128)), dim3(256), lds, stream, iqc_dz, wa, mask2, work, dwa, dqc, cnt, S2, R, Kc,
+                     scale);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // The three dense [N*S2 x 512 x 512] products of the image attention on the EXACT SPLIT (split_core.h), for a split9 pass of the model-level

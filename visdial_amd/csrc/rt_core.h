@@ -41,6 +41,15 @@ int vd_img_tr_backward_p(const float* dz, const float* Wc, const float* p, const
 int vd_img_common_wgrad_p(const float* dz, const float* pre, const uint8_t* mask1, const float* xdrop, float* dWc, int N, int R, int S2, int H,
                           int Kc, float scale, int flags, hipStream_t stream);
 
+// attention.hip: the attention head over the live regions of every image (IR1 - IR6).  cnt [ceil(N / R)] int32 on the device: round n attends
+// the first cnt[n / R] regions of its image and writes exact zeros for the rest; cnt = null is vd_img_att_forward / vd_img_att_backward,
+// argument for argument
+int vd_img_att_forward_p(const float* iqc, const float* wa, const float* ba, const float* pre, const uint8_t* mask1, const float* u0, float* p,
+                         float* u1, int N, int R, int S2, int H, int Kc, float scale, const int32_t* cnt, hipStream_t stream);
+int vd_img_att_backward_p(float* iqc_dz, const float* wa, const float* pre, const uint8_t* mask1, const uint8_t* mask2, const float* p,
+                          const float* datt, float* dwa, float* dba, float* dqc, float* work, int N, int R, int S2, int H, int Kc, float scale,
+                          const int32_t* cnt, hipStream_t stream);
+
 // attention.hip: one round of a rollout (VD_ROLLOUT_ENCODER = round; rt_encoders.h forward_round).  Row (d, r) of vd_mn_attention_forward /
 // vd_hrea_attention_forward under the causal mask, bit for bit, from facts (d, 0 .. r) alone: hAtt / att [B x H] and P [B x R] (or null) are
 // compact.  The memory query of dialog d is row d of Q [B x q_ld] (q_ld = R * H reads round r of a per-round tensor in place); Qout [B x H]
@@ -209,6 +218,9 @@ struct BatchSlot {
   double rel_W = 0.0;
   // "@dense_relevance_live" (loss.hip DL1 - DL3) where some but not all rounds are live: the live rounds' option tokens, compacted and
   // sorted behind the attachment on the side lane.  opt_live.N = n_live * O rows; live_slot [N] on the device; n_live = 0: all rows
+  // batch attachment "@img_regions" (attention.hip IR1): the number of live regions of every image of this upload [B] on the device, or
+  // null = every image holds all S2; the next upload into the slot clears it
+  int32_t* regions = nullptr;
   SeqTok opt_live;
   int n_live = 0;
   int32_t *live_slot = nullptr, *live_sort_off = nullptr, *live_sort_perm = nullptr;

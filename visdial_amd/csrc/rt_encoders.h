@@ -460,6 +460,7 @@ struct SANBlock {
   std::vector<float*> iqc, patt;
   float sc = 1.f;
   float* xdrop = nullptr;   // split9 pass: dropout1(gather(pre)) [N*S2 x H], materialised once per step
+  const int32_t* cnt = nullptr;   // the slot's "@img_regions" [B] or null (attention.hip IR1): the head walks the live regions only
   int iflags = 0;
   static void declare(vd_model* m) {
     const long H = m->p.rnnHiddenSize, C = m->p.imgFeatureSize, K = m->p.commonEmbeddingSize;
@@ -481,6 +482,7 @@ struct SANBlock {
   // per-image projection + this step's dropout masks: independent of the text branches -> own stream
   int prefetch(vd_model* m, hipStream_t s, BatchSlot& b, int N_) {
     N = N_;
+    cnt = b.regions;
     hipStream_t si = side_stream(m, s);
     VD_TRY(fork_stream(m, s, si));
     VD_TRY(img_proj.forward(m, si, b.img, (long)b.B * S2, true, &pre));           // mn-att:74-78 (pre-dropout)
@@ -510,8 +512,8 @@ struct SANBlock {
       VD_TRY(ws_get(m, "att.u1" + sf, (size_t)N * H, &u1));
       VD_TRY(vd_img_common_forward_p(pre, m1, xdrop, Wp(m, "img_common" + sf + ".W"), Wp(m, "img_common" + sf + ".b"), qc, m2[i], iqc[i], N, R,
                                      S2, (int)H, (int)K, sc, iflags, s));         // mn-att:83-92
-      VD_TRY(vd_img_att_forward(iqc[i], Wp(m, "att" + sf + ".W"), Wp(m, "att" + sf + ".b"), pre, m1, u, patt[i], u1, N, R, S2, (int)H,
-                                (int)K, sc, s));                                  // mn-att:93-102
+      VD_TRY(vd_img_att_forward_p(iqc[i], Wp(m, "att" + sf + ".W"), Wp(m, "att" + sf + ".b"), pre, m1, u, patt[i], u1, N, R, S2, (int)H,
+                                  (int)K, sc, cnt, s));                           // mn-att:93-102
       u_in[i] = u;
       u = u1;
     }
@@ -535,7 +537,8 @@ struct SANBlock {
       // without dropout the per-round image tensor of a B-row pass IS `pre`
       VD_TRY(vd_img_common_forward_p(pre, nullptr, fl ? pre : nullptr, Wp(m, "img_common" + sf + ".W"), Wp(m, "img_common" + sf + ".b"), qc, nullptr,
                                      iq, B_, 1, S2, (int)H, (int)K, 1.f, fl, s));
-      VD_TRY(vd_img_att_forward(iq, Wp(m, "att" + sf + ".W"), Wp(m, "att" + sf + ".b"), pre, nullptr, u, pa, u1, B_, 1, S2, (int)H, (int)K, 1.f, s));
+      VD_TRY(vd_img_att_forward_p(iq, Wp(m, "att" + sf + ".W"), Wp(m, "att" + sf + ".b"), pre, nullptr, u, pa, u1, B_, 1, S2, (int)H, (int)K, 1.f,
+                                  cnt, s));
       u = u1;
     }
     return round_linear(m, s, "out", u, H, H, H, B_, true, y, ldy);
@@ -554,8 +557,8 @@ struct SANBlock {
       float *dqc, *duq, *dun;
       VD_TRY(ws_get(m, "att.dqc" + sf, (size_t)N * K, &dqc));
       VD_TRY(ws_get(m, "att.du0" + sf, (size_t)N * H, &dun));
-      VD_TRY(vd_img_att_backward(iqc[i], Wp(m, "att" + sf + ".W"), pre, m1, m2[i], patt[i], dcur, Gp(m, "att" + sf + ".W"),
-                                 Gp(m, "att" + sf + ".b"), dqc, dscore, N, R, S2, (int)H, (int)K, sc, s));   // iqc now holds dz
+      VD_TRY(vd_img_att_backward_p(iqc[i], Wp(m, "att" + sf + ".W"), pre, m1, m2[i], patt[i], dcur, Gp(m, "att" + sf + ".W"),
+                                   Gp(m, "att" + sf + ".b"), dqc, dscore, N, R, S2, (int)H, (int)K, sc, cnt, s));   // iqc now holds dz
       // dz is final: what follows on `sw` feeds parameter gradients only (the chain to the text branches continues with dqc)
       hipStream_t sw;
       VD_TRY(wg_fork(m, s, &sw));

@@ -582,6 +582,36 @@ static int attach_dense_relevance(vd_model* m, const float* host, int64_t n, boo
   return VD_OK;
 }
 
+// "@img_regions" (attention.hip IR1 - IR6): the number of live regions of every image of the batch uploaded last, B counts that come as floats
+// because that is the signature.  Validated here, staged in pinned memory as int32 and copied on the upload lane behind the batch's own
+// fields, with attach_dense_relevance's waits: the image attention of every pass over this upload then walks the first cnt[b] regions of image
+// b alone.  The hidden rows of the uploaded features stay the caller's: finite (IR5).  It touches no weight and no candidate, so the
+// answer-encoding cache stays as it is.
+static int attach_img_regions(vd_model* m, const float* host, int64_t n) {
+  const char* who = "vd_model_set_tensor: '@img_regions'";
+  VD_CHECK_ARG(m->uploaded >= 0, "%s attaches to the batch uploaded last, and no batch has been uploaded", who);
+  VD_CHECK_ARG(m->is_att, "%s gives the image attention a region count per image, and encoder '%s' has no image attention (the encoders with it "
+               "are mn-att-ques-im-hist and lf-att-ques-im-hist)", who, m->enc_name.c_str());
+  BatchSlot& sl = m->slot[m->uploaded];
+  const int S2 = m->p.imgSpatialSize * m->p.imgSpatialSize;
+  VD_CHECK_ARG(n == (int64_t)sl.B, "%s holds one count per image, B = %d values for this batch, got %ld", who, sl.B, (long)n);
+  for (int b = 0; b < sl.B; ++b) {
+    const float v = host[b];
+    VD_CHECK_ARG(v >= 1.f && v <= (float)S2 && v == (float)(int32_t)v,
+                 "%s image %d = %g: a region count is an integer in 1 .. S2 = %d (imgSpatialSize^2)", who, b, (double)v, S2);
+  }
+  hipStream_t s = m->s_side;
+  if (sl.used) VD_HIP(hipStreamWaitEvent(s, sl.done, 0));       // a step that reads an earlier attachment of this upload may still run
+  if (sl.regions) VD_HIP(hipEventSynchronize(sl.ready));        // ... and its copy may still read the staging buffer
+  int32_t* stage = nullptr;
+  VD_TRY(pin_get(sl.pinned, "regions.stage", (size_t)n * sizeof(int32_t), (void**)&stage));
+  for (int b = 0; b < sl.B; ++b) stage[b] = (int32_t)host[b];
+  VD_TRY(dev_get(sl.bufs, "regions", (size_t)n * sizeof(int32_t), (void**)&sl.regions));
+  VD_HIP(hipMemcpyAsync(sl.regions, stage, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  VD_HIP(hipEventRecord(sl.ready, s));   // the slot is ready when the attachment has landed too
+  return VD_OK;
+}
+
 // "@ndcg" (loss.hip DT2): NDCG of every round of the current batch from the scores of its last forward / retrieval and its attached
 // relevance matrix.  n = 2 N: the N doubles the kernel wrote, bit for bit, in the float buffer of the signature.
 static int read_ndcg(vd_model* m, int which, float* host, int64_t n) {
@@ -607,8 +637,9 @@ int vd_model_set_tensor(vd_model* m, const char* name, const float* host, int64_
   if (m && name && host && name[0] == '@') {
     if (!strcmp(name, "@dense_relevance")) return attach_dense_relevance(m, host, n, false);
     if (!strcmp(name, "@dense_relevance_live")) return attach_dense_relevance(m, host, n, true);
-    VD_CHECK_ARG(false, "vd_model_set_tensor: unknown batch attachment '%s' (the library knows '@dense_relevance' and '@dense_relevance_live')",
-                 name);
+    if (!strcmp(name, "@img_regions")) return attach_img_regions(m, host, n);
+    VD_CHECK_ARG(false, "vd_model_set_tensor: unknown batch attachment '%s' (the library knows '@dense_relevance' and '@dense_relevance_live') "
+                 "and, for the image attention, '@img_regions'", name);
   }
   VD_CHECK_ARG(m && name && host && m->index.count(name), "vd_model_set_tensor: unknown tensor '%s'", name ? name : "(null)");
   const Tensor& t = m->spec[m->index.at(name)];
@@ -684,6 +715,7 @@ int vd_model_upload_batch(vd_model* m, const vd_batch* hb) {
   if (sl.uploaded) VD_HIP(hipEventSynchronize(sl.ready));
   sl.uploaded = true;
   sl.rel = nullptr;   // an attachment belongs to one upload
+  sl.regions = nullptr;
   sl.rel_W = 0.0;
   sl.n_live = 0;
   sl.B = hb->B;

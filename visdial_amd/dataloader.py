@@ -7,6 +7,8 @@ HDF5/JSON (no dataset offline):
   ques_fwd   int32 [B, R, Tq]   right-aligned, left-padded with 0, trimmed to the batch max
   hist       int32 [B, R, Th]   right-aligned (round 1 = caption, round r = QA of r-1)
   img_feat   fp32  [B, S, S, C] (att encoders, pool5, non-negative) or [B, F] (fc7, L2-normalised)
+  img_regions int32 [B]         (params imgRegions = M > 0 only) live regions of every image, 1 .. M: img_feat then holds M detector regions
+                                padded to S*S = ceil(sqrt(M))^2 rows, every row >= the count zero (csrc/attention.hip IR1, IR5)
   options    int32 [B*R, O, To] left-aligned, trailing zeros, no <START>/<END> (disc)
   answer_ind int32 [B*R]        1-based index of the ground-truth option (prepro.py:169)
   answer_in / answer_out int32 [B, R, Ta]  <START>+tokens / tokens+<END>, left-aligned (gen)
@@ -28,6 +30,17 @@ def _left_align(rows, T):
     out = np.zeros((len(rows), T), np.int32)
     for i, r in enumerate(rows):
         out[i, :len(r)] = r
+    return out
+
+
+def pad_regions(feat, counts, S2):
+    """[n x M x C] region features -> [n x S2 x C] float32 with every row >= counts[i] zero (csrc/attention.hip IR5: the dense products
+    still read the hidden rows, so they are finite)"""
+    feat = np.asarray(feat, np.float32)
+    n, M, C = feat.shape
+    out = np.zeros((n, S2, C), np.float32)
+    out[:, :M] = feat
+    out *= (np.arange(S2)[None, :] < np.asarray(counts)[:, None])[:, :, None]
     return out
 
 
@@ -61,6 +74,9 @@ class SyntheticDataloader(object):
         self.maxHistLen = int(opt.get('maxHistoryLenPerRound', 40))
         self.numOptions = int(opt.get('numOptions', 100))
         self.rng = np.random.RandomState(seed)
+        # detector regions (imgRegions = M > 0): the counts come from a generator of their own, so M = 0 leaves the batch stream untouched
+        self.imgRegions = int(opt.get('imgRegions') or 0)
+        self.region_rng = np.random.RandomState(seed + 7907) if self.imgRegions > 0 else None
         n = int(num_threads or opt.get('numTrainThreads', 1000))
         self.numThreads = {'train': n, 'val': n, 'test': n}
         self.numTrainThreads = n
@@ -115,6 +131,13 @@ class SyntheticDataloader(object):
                     batch['img_feat'] = self._img_pool[self.gen.integers(0, len(self._img_pool), size=B)]
                 else:
                     batch['img_feat'] = np.abs(rng.randn(B, S, S, C)).astype(np.float32)
+                if self.imgRegions > 0:
+                    M = self.imgRegions
+                    if not 1 <= M <= S * S:
+                        raise ValueError("imgRegions = %d does not fit imgSpatialSize = %d (%d region rows)" % (M, S, S * S))
+                    cnt = self.region_rng.randint(1, M + 1, size=B).astype(np.int32)
+                    batch['img_feat'] = pad_regions(batch['img_feat'].reshape(B, S * S, C), cnt, S * S).reshape(B, S, S, C)
+                    batch['img_regions'] = cnt
             else:
                 f = rng.randn(B, int(params['imgFeatureSize'])).astype(np.float32)
                 if int(params.get('imgNorm', 1)) == 1:
@@ -296,7 +319,26 @@ class Dataloader(object):
             d['ans'], d['ans_len'] = A('ans_' + dtype).astype(np.int64), A('ans_length_' + dtype).astype(np.int64)
             if dtype != 'test':
                 d['ans_ind'] = A('ans_index_' + dtype).astype(np.int64)
-            if self.useIm:
+            M = int(opt.get('imgRegions') or 0)
+            if self.useIm and M > 0:                                # detector regions [n x M x C] + their count per image
+                S = int(opt['imgSpatialSize'])
+                for name in ('regions_' + dtype, 'num_regions_' + dtype):
+                    if name not in img:
+                        raise ValueError("-imgRegions %d: %s holds no dataset '%s' (it takes regions_<split> [n x M x C] float32 and "
+                                         "num_regions_<split> [n])" % (M, opt.get('inputImg'), name))
+                f, cnt = np.asarray(img['regions_' + dtype], dtype=np.float32), np.asarray(img['num_regions_' + dtype])
+                if f.ndim != 3 or f.shape[1] != M:
+                    raise ValueError("-imgRegions %d: 'regions_%s' of %s has the shape %s, its second dimension must be M = %d"
+                                     % (M, dtype, opt.get('inputImg'), tuple(f.shape), M))
+                if cnt.shape != (f.shape[0],) or (cnt != np.round(cnt)).any() or cnt.min() < 1 or cnt.max() > M:
+                    bad = cnt.reshape(-1)[((cnt.reshape(-1) < 1) | (cnt.reshape(-1) > M) | (cnt.reshape(-1) != np.round(cnt.reshape(-1))))]
+                    raise ValueError("-imgRegions %d: 'num_regions_%s' of %s must hold one integer count in 1 .. %d per image%s"
+                                     % (M, dtype, opt.get('inputImg'), M, ', found %r' % (bad[0].item(),) if bad.size else
+                                        ', found the shape %s for %d images' % (tuple(cnt.shape), f.shape[0])))
+                d['img_fv'] = pad_regions(f, cnt, S * S).reshape(f.shape[0], S, S, f.shape[2])
+                d['img_regions'] = cnt.astype(np.int32)
+                d['img_pos'] = A('img_pos_' + dtype).astype(np.int64) + 1
+            elif self.useIm:
                 f = np.asarray(img['images_' + dtype], dtype=np.float32)
                 if int(opt.get('imgNorm', 1)) == 1:                 # :64-68 (L2 norm over dim 2)
                     f = f / np.sqrt((f * f).sum(1, keepdims=True))
@@ -467,6 +509,8 @@ class Dataloader(object):
             out['hist'] = np.ascontiguousarray(d['hist'][ix][:, :, d['hist'].shape[2] - mh:]).astype(np.int32)
         if self.useIm:
             out['img_feat'] = d['img_fv'][d['img_pos'][ix] - 1]
+            if 'img_regions' in d:
+                out['img_regions'] = d['img_regions'][d['img_pos'][ix] - 1]
         ma = int(d['ans_len'][ix].max())
         out['answer_in'] = np.ascontiguousarray(d['ans_in'][ix][:, :, :ma]).astype(np.int32)
         out['answer_out'] = np.ascontiguousarray(d['ans_out'][ix][:, :, :ma]).astype(np.int32)

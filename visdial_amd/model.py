@@ -68,9 +68,18 @@ def refuse_dense_training(params):
                          "(visdial_amd.native.NativeModel); the operator-level host trains on one-hot targets" % (params['denseAnnotations'],))
 
 
+def refuse_img_regions(params):
+    """a model of the operator-level host over detector regions is refused by name: the masked attention kernels and the batch attachment
+    are internal to the model-level runtime (its C symbol set is frozen)"""
+    if int(params.get('imgRegions') or 0) != 0:
+        raise ValueError("imgRegions = %r: the image attention over a region count per image runs in the model-level runtime only: use "
+                         "-host native (visdial_amd.native.NativeModel); the operator-level host takes imgRegions = 0" % (params['imgRegions'],))
+
+
 class Model(SplitEval):
     def __init__(self, params, dist_group=None):
         self.params = params
+        refuse_img_regions(params)
         if int(params.get('fusedLhood', 0) or 0) == 2:
             # the prefix-tree head is internal to the library (its C symbol set is frozen): only the model-level runtime reaches it
             raise ValueError("fusedLhood = 2 (generative retrieval over a prefix tree of the candidates) runs in the model-level runtime only: "

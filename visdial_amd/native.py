@@ -255,6 +255,8 @@ class NativeModel(SplitEval):
         self._N = batch['ques_fwd'].shape[0] * batch['ques_fwd'].shape[1]
         if batch.get('dense_relevance') is not None:            # a dense batch (dataloader.getDenseTrainBatch) trains on its matrix
             self.attach_dense_relevance(batch['dense_relevance'], live=self.params.get('denseRows', 'all') == 'live')
+        if batch.get('img_regions') is not None:                # detector regions: every image attends its own first count rows
+            self.attach_img_regions(batch['img_regions'])
         # non-pad target tokens of THIS batch: the gen loss EMA divides by it (model.lua:76-85)
         self._numTokens = float((np.asarray(batch['answer_out']) > 0).sum()) if 'answer_out' in batch else 0.0
         # whatever was prefetched for trainIteration has just been replaced (evaluate / retrieve / predict / generate
@@ -269,6 +271,15 @@ class NativeModel(SplitEval):
         one before it on the same upload."""
         a = np.ascontiguousarray(rel, dtype=np.float32)
         call("vd_model_set_tensor", self.h, b"@dense_relevance_live" if live else b"@dense_relevance", a.ctypes.data, a.size)
+
+    def attach_img_regions(self, counts):
+        """attach the number of live regions of every image [B] (integers in 1 .. imgSpatialSize^2) to the batch uploaded last
+        (vd_model_set_tensor '@img_regions'; csrc/attention.hip IR1 - IR6): the image attention of every pass over that upload -- training
+        step, retrieval, generation, rollouts -- looks at the first counts[b] regions of image b and at nothing else.  The hidden rows of
+        the uploaded img_feat must be finite (the loaders write zeros).  The library validates the counts and refuses by name; the next
+        upload clears them."""
+        a = np.ascontiguousarray(np.asarray(counts).reshape(-1), dtype=np.float32)
+        call("vd_model_set_tensor", self.h, b"@img_regions", a.ctypes.data, a.size)
 
     def ndcg_rows(self):
         """NDCG [N] (float64) of the scores of the last forward / retrieval of the current batch under its attached relevance matrix
@@ -431,7 +442,7 @@ class NativeModel(SplitEval):
 
     # Model:generateAnswers (host loop in split_eval.py); the four device steps through the model-level ABI
     def _gen_encode(self, batch):
-        self.upload({k: v for k, v in batch.items() if k in ('ques_fwd', 'hist', 'img_feat')})
+        self.upload({k: v for k, v in batch.items() if k in ('ques_fwd', 'hist', 'img_feat', 'img_regions')})
         call("vd_model_encode", self.h)
 
     def _gen_begin(self, rounds):

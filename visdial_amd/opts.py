@@ -2,6 +2,7 @@
 derived capability flags it infers from the encoder NAME (opts.lua:54-67)."""
 import argparse
 import ctypes
+import math
 import time
 
 # (flag, default, help) -- opts.lua:5-40
@@ -87,6 +88,41 @@ def check_dense_rows(opt):
                          "rows alone; train with -denseRows all or another -lstmPrecision")
 
 
+ATT_ENCODERS = ('mn-att-ques-im-hist', 'lf-att-ques-im-hist')    # the encoders with the image attention
+
+
+def check_img_regions(opt):
+    """what -imgRegions M cannot be combined with, refused by name before any model exists (the library refuses the attachment on an encoder
+    without the image attention: csrc/attention.hip IR1 - IR6).  -> M"""
+    M = opt.get('imgRegions') or 0
+    if int(M) != M or M < 0:
+        raise ValueError("-imgRegions %r must be an integer >= 0 (0 = off: one S x S grid per image)" % (M,))
+    M = int(M)
+    if M == 0:
+        return 0
+    if opt.get('encoder') not in ATT_ENCODERS:
+        raise ValueError("-imgRegions %d with -encoder %s: a region count per image masks the image attention, which only %s have"
+                         % (M, opt.get('encoder'), ' and '.join(ATT_ENCODERS)))
+    if (opt.get('host') or 'python') != 'native':
+        raise ValueError("-imgRegions %d: the masked image attention runs in the model-level runtime only: use -host native "
+                         "(visdial_amd.native.NativeModel); the operator-level host takes -imgRegions 0" % M)
+    return M
+
+
+def apply_img_regions(opt):
+    """-imgRegions M > 0: the padded grid holds S2 = ceil(sqrt(M))^2 >= M rows per image (imgNorm stays 0, as derive sets it for these encoders)"""
+    M = check_img_regions(opt)
+    if M > 0:
+        S = int(math.ceil(math.sqrt(M)))
+        while S * S < M:      # (sqrt of a perfect square rounds either way)
+            S += 1
+        while (S - 1) * (S - 1) >= M:
+            S -= 1
+        opt['imgSpatialSize'] = S
+        print('-imgRegions %d: imgSpatialSize = %d (%d region rows per image, the rows behind an image\'s count are hidden)' % (M, S, S * S))
+    return opt
+
+
 def default_params(**overrides):
     opt = {k: v for k, v, _ in OPTIONS}
     # sizes the reference copies from the dataloader (train.lua:55-59)
@@ -128,6 +164,10 @@ def parse(argv=None):
                     help="(with -denseAnnotations, -host native) 'all' (default): every round's candidates go through the option recurrence and "
                          "its gradients | 'live': only the candidates of the rounds that carry a gradient (weight > 0); the same loss and "
                          "gradients up to fp32 summation order")
+    # not a reference flag (kept out of OPTIONS): detector regions, a different number per image (csrc/attention.hip IR1 - IR6)
+    ap.add_argument('-imgRegions', '--imgRegions', type=int, default=0,
+                    help="(-host native, the two att encoders) M > 0: -inputImg holds regions_<split> [n x M x C] and num_regions_<split> [n]; "
+                         "every image attends its own first num_regions rows only.  imgSpatialSize becomes ceil(sqrt(M)).  0 (default) = off")
     opt = vars(ap.parse_args(argv))
     # refused by name before any model exists (the library refuses the same values: csrc/rt_switches.h)
     # (eps is applied in fp32, as in the library: a value that rounds to 1.0f is not below 1)
@@ -141,6 +181,8 @@ def parse(argv=None):
     try:
         check_dense(dict(opt, decoder='disc') if opt['loadPath'] else opt)   # (-loadPath: the decoder is the checkpoint's; train.py checks again)
         check_dense_rows(opt)
+        if opt['imgRegions'] < 0 or not opt['loadPath']:                     # (-loadPath: the encoder is the checkpoint's; the scripts check again)
+            check_img_regions(opt)
     except ValueError as e:
         ap.error(str(e))
     opt.update(maxQuesCount=10, maxQuesLen=20, maxAnsLen=20, numOptions=100)
@@ -148,4 +190,5 @@ def parse(argv=None):
         t = time.localtime()
         opt['savePath'] = 'checkpoints/model-%d-%d-%d-%d:%d:%d-%s-%s/' % (
             t.tm_mon, t.tm_mday, t.tm_year, t.tm_hour, t.tm_min, t.tm_sec, opt['encoder'], opt['decoder'])
-    return derive(opt)
+    opt = derive(opt)
+    return opt if opt['loadPath'] else apply_img_regions(opt)
