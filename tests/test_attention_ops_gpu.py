@@ -5,7 +5,7 @@ tests/test_attention_ref_cpu.py):
      img_att_dz_kernel, the second trip of the 256-strided loops of img_att_score_kernel / img_att_dscore_kernel, S2 = 196, the smallest
      legal widths and eight column tiles;
   2. the dense products of a split9 pass operator by operator -- vd_img_drop_gather, vd_img_common_forward_p, vd_img_tr_backward_p,
-     vd_img_common_wgrad_p (internal: reached by the mangled names the library exports, declarations in csrc/rt_core.h) -- on ragged
+     vd_img_common_wgrad_p (internal: bound by visdial_amd._lib.internal, declarations in csrc/rt_core.h) -- on ragged
      row / column tiles, the XCD grid map, the 128-row threshold, ragged transposes, the evaluation form, the tail contraction and
      every fall-back of the weight gradient; each against fp64 AND against the fp32 entry point on the same inputs;
   3. vd_hrea_attention_*, vd_rowdot_*, vd_mn_attention_* and the LDS guards of the latter.
@@ -16,7 +16,6 @@ rows of round N - 1, rows of image B - 1 for dpre); gathers and integer results 
 (dba = sum of dscore; dsq[i] = sum_j dA[i, j]) is held to 1e-5 x the sum of the magnitudes it adds up, which is what its fp32 rounding
 error scales with; no other output is.  Every written or accumulated output lies in front of 128
 guard rows that must stay untouched.  The split-versus-fp32 error ratio is printed, not asserted."""
-import ctypes as C
 import functools
 import types
 
@@ -65,26 +64,11 @@ def stream():
 
 @pytest.fixture(scope="module")
 def internal(ops):
-    """the four internal entry points of a split9 pass (csrc/rt_core.h), by the names the built library exports"""
+    """the four internal entry points of a split9 pass (csrc/rt_core.h), bound by visdial_amd._lib.internal"""
     from visdial_amd import _lib
-    lib = _lib.load()
-    p, i, f = C.c_void_p, C.c_int, C.c_float
-
-    def fn(name, argtypes):
-        raw = getattr(lib, name)
-        raw.argtypes = argtypes
-        raw.restype = C.c_int
-
-        def call(*args):
-            rc = raw(*args)
-            if rc != 0:
-                raise _lib.VisdialHipError("%s failed (%d): %s" % (name, rc, lib.vd_last_error().decode()))
-        return call
     return types.SimpleNamespace(
-        drop_gather=fn('_Z18vd_img_drop_gatherPKfPKhPfiiiifP12ihipStream_t', [p, p, p, i, i, i, i, f, p]),
-        common_forward=fn('_Z23vd_img_common_forward_pPKfPKhS0_S0_S0_S0_S2_PfiiiiifiP12ihipStream_t', [p] * 8 + [i] * 5 + [f, i, p]),
-        tr_backward=fn('_Z20vd_img_tr_backward_pPKfS0_S0_S0_PKhPfiiiiifiP12ihipStream_t', [p] * 6 + [i] * 5 + [f, i, p]),
-        common_wgrad=fn('_Z21vd_img_common_wgrad_pPKfS0_PKhS0_PfiiiiifiP12ihipStream_t', [p] * 5 + [i] * 5 + [f, i, p]))
+        drop_gather=_lib.internal('vd_img_drop_gather'), common_forward=_lib.internal('vd_img_common_forward_p'),
+        tr_backward=_lib.internal('vd_img_tr_backward_p'), common_wgrad=_lib.internal('vd_img_common_wgrad_p'))
 
 
 def split_ok(rows, H, Kc):

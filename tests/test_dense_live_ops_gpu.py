@@ -1,5 +1,5 @@
 """The two kernels of a live dense step (csrc/loss.hip DL3) as operators, entered through the internal vd_dense_live_tokens_p and
-vd_score_ce_dense_live_p by the mangled names read from the built library (declarations in csrc/rt_core.h):
+vd_score_ce_dense_live_p, bound by visdial_amd._lib.internal (declarations in csrc/rt_core.h):
 
   dense_live_tokens_kernel     bit for bit against dense.live_option_tokens: To in {1, 5}, O in {5, 64, 65, 128} (a partial wave, the wave
                                boundary on either side, MAX_OPT), N = 6 rounds, the live sets {0}, {5}, {0, 2, 3, 5}, {1, 4}, with and
@@ -11,8 +11,6 @@ vd_score_ce_dense_live_p by the mangled names read from the built library (decla
                                dOptH's guard rows untouched.  Bounds, those of tests/test_dense_gpu.py check 1 and conftest.grad_mismatches:
                                1e-4 absolute on the loss rows, rel-L2 1e-4 per tensor on scores, dOptH and dEnc.
                                With every round live and the same operands it reproduces vd_score_ce_dense_p bit for bit."""
-import ctypes as C
-import re
 import types
 
 import numpy as np
@@ -36,26 +34,9 @@ def lib():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     from visdial_amd import _lib
-    so = _lib.load()
-    image = open(_lib.LIB_PATH, 'rb').read()
-    p, i, l, f = C.c_void_p, C.c_int, C.c_int64, C.c_float
-
-    def fn(name, argtypes):
-        found = set(re.findall(('_Z%d%s' % (len(name), name)).encode() + b'[A-Za-z0-9_]+', image))
-        assert len(found) == 1, (name, found)
-        raw = getattr(so, found.pop().decode())
-        raw.argtypes, raw.restype = argtypes, C.c_int
-
-        def call(*args):
-            rc = raw(*args)
-            if rc != 0:
-                raise _lib.VisdialHipError("%s failed (%d): %s" % (name, rc, so.vd_last_error().decode()))
-        return call
     return types.SimpleNamespace(
-        tokens=fn('vd_dense_live_tokens_p', [p, l, i, p, p, i, i, p, p]),
-        head=fn('vd_score_ce_dense_live_p', [p, p, p, p, p, p, p, p, p, i, i, i, f, f, p]),
-        dense=fn('vd_score_ce_dense_p', [p, p, p, p, p, p, p, p, i, i, i, f, f, p]),
-        Error=_lib.VisdialHipError)
+        tokens=_lib.internal('vd_dense_live_tokens_p'), head=_lib.internal('vd_score_ce_dense_live_p'),
+        dense=_lib.internal('vd_score_ce_dense_p'), Error=_lib.VisdialHipError)
 
 
 def dev(a):

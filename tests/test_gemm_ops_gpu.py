@@ -1,5 +1,5 @@
 """The GEMM entry points of csrc/gemm_ops.hip -- vd_gemm_nt, vd_gemm_nn, vd_gemm_tn_acc, vd_gemm_tn_rows_acc through visdial_amd.ops, the
-internal vd_gemm_nn_live_p by its mangled name -- over the case table of tests/gemm_cases.py: every kernel family of the dispatch, at the
+internal vd_gemm_nn_live_p through visdial_amd._lib.internal -- over the case table of tests/gemm_cases.py: every kernel family of the dispatch, at the
 strides the runtime passes (views at a column offset, leading dimension > width), ragged widths on padded rows, every epilogue mode, short
 K loops of the LDS-DMA pipelines, against fp64.
 
@@ -7,7 +7,6 @@ Every operand holds NaN wherever the contract says it is never used and a large 
 the output lies in front of marked columns, rows and a trailing guard that must come back bit for bit.  Bounds (gemm_cases.py): rel-L2 <
 1e-5 (1e-2 under FLAG_BF16) and, on the exact-fp32 paths without tanh, |got - ref| <= (K + 4) 2^-24 (|A|.|B| + |bias| + |C0|) per element.
 The worst figures per family are printed when the whole module has run (profiles/gemm_ops_parity.txt: VD_GEMM_PARITY_OUT=<file> writes them)."""
-import ctypes as C
 import os
 import re
 
@@ -34,16 +33,7 @@ def ops():
 @pytest.fixture(scope="module")
 def live_p(ops):
     from visdial_amd import _lib
-    lib = _lib.load()
-    p, i, l = C.c_void_p, C.c_int, C.c_int64
-    raw = getattr(lib, '_Z17vd_gemm_nn_live_pPKflS0_lS0_PfliiiPKiiP12ihipStream_t')
-    raw.argtypes, raw.restype = [p, l, p, l, p, p, l, i, i, i, p, i, p], C.c_int
-
-    def call(*args):
-        rc = raw(*args)
-        if rc != 0:
-            raise _lib.VisdialHipError("vd_gemm_nn_live_p failed (%d): %s" % (rc, lib.vd_last_error().decode()))
-    return call
+    return _lib.internal('vd_gemm_nn_live_p')
 
 
 @pytest.fixture(scope="module", autouse=True)

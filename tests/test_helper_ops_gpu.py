@@ -1,6 +1,6 @@
 """The entry points of csrc/elementwise.hip and csrc/loss.hip as operators over the case tables of tests/helper_cases.py: the C ABI through
-visdial_amd._lib, vd_zero_inactive_multi / vd_segment_rowsum_acc_bf16 / vd_score_ce_p / vd_logsoftmax_nll_p (internal: declarations in
-csrc/common.h and csrc/rt_core.h) by the mangled names read from the built library.
+visdial_amd._lib.call, vd_zero_inactive_multi / vd_segment_rowsum_acc_bf16 / vd_score_ce_p / vd_logsoftmax_nll_p (internal: declarations in
+csrc/common.h and csrc/rt_core.h) through visdial_amd._lib.internal, which binds them from the symbols the built library exports.
 
 Every input lies inside a larger buffer with NaN or a large token id behind it and in its pad columns; every output starts as marks in
 front of 128 marked guard elements, and everything the operation does not own must come back bit for bit.  Bounds: helper_cases.py.  Each
@@ -11,6 +11,7 @@ tests/golden/helper_nll_parent.json holds, for every gen-head case with ld - V <
 that the build BEFORE the pad-column loop of logsoftmax_nll_body left behind (written by this module run against that build with
 VD_HELPER_PARENT_OUT=<file>); test_logsoftmax_nll_cases asserts the same bits."""
 import ctypes as C
+import functools
 import hashlib
 import json
 import os
@@ -45,35 +46,12 @@ def lib():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     from visdial_amd import _lib
-    so = _lib.load()
-    image = open(_lib.LIB_PATH, 'rb').read()
-    p, i, l, f = C.c_void_p, C.c_int, C.c_int64, C.c_float
-
-    def mangled(name):
-        found = set(re.findall(('_Z%d%s' % (len(name), name)).encode() + b'[A-Za-z0-9_]+', image))
-        assert len(found) == 1, (name, found)
-        return found.pop().decode()
-
-    def fn(name, argtypes=None):
-        raw = getattr(so, mangled(name) if argtypes else name)
-        if argtypes:
-            raw.argtypes, raw.restype = argtypes, C.c_int
-
-        def call(*args):
-            rc = raw(*args)
-            if rc != 0:
-                raise _lib.VisdialHipError("%s failed (%d): %s" % (name, rc, so.vd_last_error().decode()))
-            return rc
-        return call
     public = ('dropout_mask', 'dropout_apply', 'tanh_backward', 'axpby', 'embed_gather', 'embed_scatter_acc', 'mask_time_forward',
               'mask_time_backward', 'zero_inactive_rows', 'token_sort', 'segment_rowsum_acc', 'log_softmax_rows', 'logsoftmax_nll', 'score_ce',
               'ranks')
-    return types.SimpleNamespace(
-        zero_inactive_multi=fn('vd_zero_inactive_multi', [C.POINTER(VdZeroSet), p, i, i, p]),
-        segment_rowsum_acc_bf16=fn('vd_segment_rowsum_acc_bf16', [p, l, p, p, l, i, p, l, p]),
-        score_ce_p=fn('vd_score_ce_p', [p, p, p, p, p, p, p, i, i, i, f, f, p]),
-        logsoftmax_nll_p=fn('vd_logsoftmax_nll_p', [p, l, l, i, p, p, p, i, f, p]),
-        Error=_lib.VisdialHipError, **dict((n, fn('vd_' + n)) for n in public))
+    internal = ('zero_inactive_multi', 'segment_rowsum_acc_bf16', 'score_ce_p', 'logsoftmax_nll_p')
+    return types.SimpleNamespace(Error=_lib.VisdialHipError, **dict((n, _lib.internal('vd_' + n)) for n in internal),
+                                 **dict((n, functools.partial(_lib.call, 'vd_' + n)) for n in public))
 
 
 @pytest.fixture(scope="module", autouse=True)

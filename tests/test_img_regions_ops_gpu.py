@@ -1,7 +1,7 @@
 """Operator parity for the image attention over a region count per image (csrc/attention.hip IR1 - IR6) against the fp64 restatement of
 tests/region_ref.py (pinned to torch.autograd on the CPU by tests/test_region_ref_cpu.py).  The two internal entry points
-vd_img_att_forward_p / vd_img_att_backward_p (declarations in csrc/rt_core.h) are reached by the mangled names the library exports, as
-tests/test_attention_ops_gpu.py reaches the split products.
+vd_img_att_forward_p / vd_img_att_backward_p (declarations in csrc/rt_core.h) are bound by visdial_amd._lib.internal, as
+tests/test_attention_ops_gpu.py binds the split products.
 
   1. the chain vd_img_common_forward -> vd_img_att_forward_p -> vd_img_att_backward_p -> vd_img_tr_backward -> vd_img_common_wgrad, each
      step fed the device's own earlier outputs, with finite garbage in the hidden rows of the features (the dense products read them);
@@ -12,7 +12,6 @@ Shapes (B, R, S2, H, Kc): (7, 2, 49, 192, 144) with counts on either side of the
 score / dscore, one region and a full image; (3, 1, 5, 4, 4): R = 1, the form of a round pass; (2, 2, 196, 320, 272): the real S2.
 Bounds (tests/test_attention_ops_gpu.py's own): rel-L2 < 1e-5 per output and per named slice; dba, a sum that cancels in exact arithmetic,
 to 1e-5 x the magnitudes it sums; 128 guard rows behind every output untouched."""
-import ctypes as C
 import functools
 import types
 
@@ -45,22 +44,7 @@ def ops():
 @pytest.fixture(scope="module")
 def head(ops):
     from visdial_amd import _lib
-    lib = _lib.load()
-    p, i, f = C.c_void_p, C.c_int, C.c_float
-
-    def fn(name, argtypes):
-        raw = getattr(lib, name)
-        raw.argtypes = argtypes
-        raw.restype = C.c_int
-
-        def call(*args):
-            rc = raw(*args)
-            if rc != 0:
-                raise _lib.VisdialHipError("%s failed (%d): %s" % (name, rc, lib.vd_last_error().decode()))
-        return call
-    return types.SimpleNamespace(
-        forward=fn('_Z20vd_img_att_forward_pPKfS0_S0_S0_PKhS0_PfS3_iiiiifPKiP12ihipStream_t', [p] * 8 + [i] * 5 + [f, p, p]),
-        backward=fn('_Z21vd_img_att_backward_pPfPKfS1_PKhS3_S1_S1_S_S_S_S_iiiiifPKiP12ihipStream_t', [p] * 11 + [i] * 5 + [f, p, p]))
+    return types.SimpleNamespace(forward=_lib.internal('vd_img_att_forward_p'), backward=_lib.internal('vd_img_att_backward_p'))
 
 
 def dev(a):

@@ -1,6 +1,6 @@
 """The entry points of csrc/lhood.hip as operators over the case tables of tests/lhood_cases.py: vd_lhood_nll and vd_lhood_live_rows through
 the C ABI, vd_lhood_lse_p / vd_lhood_edge_sum_p / vd_lhood_order_p / vd_lhood_order_work_ints / vd_lhood_sum_p (internal: declarations in
-csrc/rt_core.h) by the mangled names read from the built library.  Both kernel families of the head (the fused MFMA kernel and the
+csrc/rt_core.h) through visdial_amd._lib.internal, which binds them from the symbols the built library exports.  Both kernel families of the head (the fused MFMA kernel and the
 one-workgroup-per-row kernel) at their smallest shapes, ragged tiles, strided and offset operands, NULL bias, every target slot, logits
 spread over +-80; the edge sum around its 256-float stride; the length order up to T = 255 on every length profile; the live-row list past
 256 counting blocks; the sum scattered through a permutation; the refusals and no-ops.
@@ -11,6 +11,7 @@ slice; the edge sum within (K + T + 4) 2^-24 x the magnitudes it adds; integers 
 entry point.  Each test prints its worst error over its bound; the worst figures per family are printed when the module has run
 (profiles/lhood_ops_parity.txt: VD_LHOOD_PARITY_OUT=<file> writes them)."""
 import ctypes as C
+import functools
 import os
 import re
 import types
@@ -32,39 +33,14 @@ HEAD_ENTRY = {'nll': 'vd_lhood_nll', 'lse': 'vd_lhood_lse_p'}
 
 @pytest.fixture(scope="module")
 def lib():
-    """the C ABI entry points and the five internal ones, the latter by the names the built library exports"""
+    """the C ABI entry points through _lib.call and the five internal ones through _lib.internal"""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     from visdial_amd import _lib
-    so = _lib.load()
-    image = open(_lib.LIB_PATH, 'rb').read()
-    p, i, l = C.c_void_p, C.c_int, C.c_int64
-
-    def mangled(name):
-        found = set(re.findall(('_Z%d%s' % (len(name), name)).encode() + b'[A-Za-z0-9_]+', image))
-        assert len(found) == 1, (name, found)
-        return found.pop().decode()
-
-    def fn(name, argtypes, restype=C.c_int, internal=True):
-        raw = getattr(so, mangled(name) if internal else name)
-        raw.argtypes, raw.restype = argtypes, restype
-        if restype is not C.c_int:
-            return raw
-
-        def call(*args):
-            rc = raw(*args)
-            if rc != 0:
-                raise _lib.VisdialHipError("%s failed (%d): %s" % (name, rc, so.vd_last_error().decode()))
-            return rc
-        return call
     return types.SimpleNamespace(
-        nll=fn('vd_lhood_nll', [p, l, l, p, l, p, p, l, p, i, i, p, p], internal=False),
-        live_rows=fn('vd_lhood_live_rows', [p, p, l, p, p, p, p], internal=False),
-        lse=fn('vd_lhood_lse_p', [p, l, l, p, l, p, l, p, i, i, p, p]),
-        edge_sum=fn('vd_lhood_edge_sum_p', [p, l, p, p, p, p, i, l, i, p, l, p, i, p, l, p]),
-        order=fn('vd_lhood_order_p', [p, p, i, l, i, p, p, p, p, p, p, p]),
-        order_work_ints=fn('vd_lhood_order_work_ints', [i, l], restype=C.c_int64),
-        sum=fn('vd_lhood_sum_p', [p, p, l, i, l, i, p, p, l, p]),
+        nll=functools.partial(_lib.call, 'vd_lhood_nll'), live_rows=functools.partial(_lib.call, 'vd_lhood_live_rows'),
+        lse=_lib.internal('vd_lhood_lse_p'), edge_sum=_lib.internal('vd_lhood_edge_sum_p'), order=_lib.internal('vd_lhood_order_p'),
+        order_work_ints=_lib.internal('vd_lhood_order_work_ints', C.c_int64), sum=_lib.internal('vd_lhood_sum_p'),
         Error=_lib.VisdialHipError)
 
 

@@ -530,14 +530,8 @@ def test_bf16_compact_state_saturated_gates(ops):
     saturates to exactly 1.0f (pre-activation above ~16.6) must not be stored as +0 -- the backward pass would read s = 0 and cut the
     cell gradient through a saturated forget gate.  Forget-gate pre-activations of +20 / +40 on most rows: dc0 and da
     against the fp64 recurrence on the same bf16-rounded table and weights."""
-    import ctypes as C
     from visdial_amd import _lib
-    lib = _lib.load()
-    fwd = getattr(lib, '_Z19vd_lstm_forward_c16PKtlPKiPKfPtS5_PfS6_iiiP12ihipStream_t')
-    bwd = getattr(lib, '_Z20vd_lstm_backward_c16PKfPtS0_S0_PfiiiP12ihipStream_t')
-    p = C.c_void_p
-    fwd.argtypes = [p, C.c_long, p, p, p, p, p, p, C.c_int, C.c_int, C.c_int, p]
-    bwd.argtypes = [p, p, p, p, p, C.c_int, C.c_int, C.c_int, p]
+    fwd, bwd = _lib.internal('vd_lstm_forward_c16'), _lib.internal('vd_lstm_backward_c16')
     T, N, H, V = 4, 2048, 128, 50
     rng = np.random.RandomState(11)
     Wh = (f32(rng, H, 4 * H) / np.sqrt(H) * 0.5).astype(np.float32)
@@ -580,18 +574,14 @@ def test_bf16_weight_gradient_contraction(ops, M, N, K):
     LDS-DMA tiles + transpose reads, 128 x 128 tiles (any M, N % 128 == 0) or 256 x 256 tiles with eight waves (M, N % 256 == 0 and
     K >= 8192), split-K partial sums by atomics, the last < 32 rows by a tail kernel.  bf16 products are exact in fp32, so the only
     difference to an fp32 matmul of the same bf16 values is the summation order: 1e-5 relative.  ACCUMULATES into C."""
-    import ctypes as C
     from visdial_amd import _lib
-    lib = _lib.load()
-    tn = getattr(lib, '_Z19vd_gemm_tn_acc_bf16PKtS0_PfliiiP12ihipStream_t')
-    p = C.c_void_p
-    tn.argtypes = [p, p, p, C.c_long, C.c_int, C.c_int, C.c_int, p]
-    g = torch.Generator(device='cuda').manual_seed(5)
+    tn = _lib.internal('vd_gemm_tn_acc_bf16')
+    g =torch.Generator(device='cuda').manual_seed(5)
     a16 = (torch.randn(K, M, device='cuda', generator=g) * 0.3).to(torch.bfloat16)
     b16 = (torch.randn(K, N, device='cuda', generator=g) * 0.05).to(torch.bfloat16)
     c0 = torch.randn(M, N, device='cuda', generator=g)
     c = c0.clone()
-    assert tn(a16.data_ptr(), b16.data_ptr(), c.data_ptr(), N, M, N, K, torch.cuda.current_stream().cuda_stream) == 0, lib.vd_last_error()
+    assert tn(a16.data_ptr(), b16.data_ptr(), c.data_ptr(), N, M, N, K, torch.cuda.current_stream().cuda_stream) == 0
     torch.cuda.synchronize()
     ref = c0.double() + a16.double().t() @ b16.double()
     err = ((c.double() - ref).norm() / ref.norm()).item()
@@ -602,12 +592,8 @@ def test_bf16_segment_rowsum(ops):
     """configs[4] projection-table gradient: out[token] += sum of the bf16 rows of that token, rows visited in token order (csrc/elementwise.hip
     `vd_segment_rowsum_acc_bf16`: 16-byte loads, fp32 sums, a run of one token that spans two chunks flushed by float atomics).  Against
     index_add of the same bf16 values in fp64; ragged chunk at the end, a long run (the most frequent token) and absent tokens."""
-    import ctypes as C
     from visdial_amd import _lib
-    lib = _lib.load()
-    fn = getattr(lib, '_Z26vd_segment_rowsum_acc_bf16PKtlPKiS2_liPflP12ihipStream_t')
-    p = C.c_void_p
-    fn.argtypes = [p, C.c_long, p, p, C.c_long, C.c_int, p, C.c_long, p]
+    fn = _lib.internal('vd_segment_rowsum_acc_bf16')
     rng = np.random.RandomState(3)
     n, ncol, V1 = 5000 + 37, 512, 300
     tok = rng.randint(1, V1, size=n).astype(np.int32)

@@ -15,7 +15,6 @@ The round pass and the full pass run the same products on B rows instead of N = 
 row count (gemm_ops.hip use_small), the dialog LSTM of the hierarchical encoders runs one step of B rows instead of R steps, and the
 image attention's dense product leaves the exact split below 128 rows (paths.h vd_img_split_ok), so the scores are held to the tolerance and
 each disc case prints whether they came out bit-identical to the full device rollout's."""
-import ctypes as C
 import json
 import os
 import sys
@@ -179,23 +178,13 @@ def test_gen_round_rollout_at_the_edges(gpu, edge):
 
 
 # ------------------------------------------------------------------------------------------------------------ 4. the two kernels alone
-def _fn(name, argtypes):
-    from visdial_amd import _lib
-    f = getattr(_lib.load(), name)
-    f.argtypes = argtypes
-    f.restype = C.c_int
-    return f
-
-
 @pytest.mark.parametrize("B", [1, 3])
 @pytest.mark.parametrize("H", [32, 512])
 def test_the_round_kernels_return_the_full_kernels_rows_bit_for_bit(gpu, B, H):
     """R = 10, r in {1, 5, 9}: row (d, r) of vd_mn_attention_forward / vd_hrea_attention_forward under the causal mask, from the same
     inputs; the memory query is read in place out of the per-round tensor (leading dimension R * H), as the runtime reads q.last"""
     from visdial_amd import _lib
-    p = C.c_void_p
-    mn = _fn('_Z23vd_mn_attention_round_pPKflS0_PfS1_S1_iiiiP12ihipStream_t', [p, C.c_long, p, p, p, p, C.c_int, C.c_int, C.c_int, C.c_int, p])
-    hrea = _fn('_Z25vd_hrea_attention_round_pPKfS0_S0_PfS1_iiiiP12ihipStream_t', [p, p, p, p, p, C.c_int, C.c_int, C.c_int, C.c_int, p])
+    mn, hrea = _lib.internal('vd_mn_attention_round_p'), _lib.internal('vd_hrea_attention_round_p')
     R, N = 10, B * 10
     g = torch.Generator(device='cuda').manual_seed(100 * B + H)
     Q = torch.randn(N, H, device='cuda', generator=g) * 0.3
@@ -225,7 +214,8 @@ def test_the_round_kernels_return_the_full_kernels_rows_bit_for_bit(gpu, B, H):
         assert hrea(sq.data_ptr(), sh.data_ptr(), Hm.data_ptr(), None, Ah2.data_ptr(), B, R, r, H, stream) == 0
         torch.cuda.synchronize()
         assert torch.equal(A2, A) and torch.equal(Ah2, Ah)
-    assert mn(Q.data_ptr(), R * H, Hm.data_ptr(), None, A.data_ptr(), None, B, R, R, H, stream) != 0      # r < R
+    with pytest.raises(_lib.VisdialHipError, match='vd_mn_attention_round_p failed'):                    # r < R
+        mn(Q.data_ptr(), R * H, Hm.data_ptr(), None, A.data_ptr(), None, B, R, R, H, stream)
 
 
 # ------------------------------------------------------------------------------------------------------------ 5. off is off

@@ -1,4 +1,4 @@
-"""Operator parity for the training knobs (internal entry points, csrc/rt_core.h, reached by the mangled names the library exports) against
+"""Operator parity for the training knobs (internal entry points, csrc/rt_core.h, bound by visdial_amd._lib.internal) against
 the fp64 restatement tests/train_knobs_ref.py (pinned to torch on the CPU by tests/test_train_knobs_cpu.py):
 
   1. the smoothed discriminative head (csrc/loss.hip LS1) at one option, two options, the ops suite's shape and the most options a round
@@ -42,27 +42,10 @@ def ops():
 @pytest.fixture(scope="module")
 def internal(ops):
     from visdial_amd import _lib
-    lib = _lib.load()
-    p, i, f, l = C.c_void_p, C.c_int, C.c_float, C.c_int64
-
-    def fn(name, argtypes):
-        raw = getattr(lib, name)
-        raw.argtypes = argtypes
-        raw.restype = C.c_int
-
-        def call(*args):
-            rc = raw(*args)
-            if rc != 0:
-                raise _lib.VisdialHipError("%s failed (%d): %s" % (name, rc, lib.vd_last_error().decode()))
-        return call
-    work = getattr(lib, '_Z19vd_clip_work_floatsv')
-    work.argtypes, work.restype = [], C.c_int64
     return types.SimpleNamespace(
-        score_ce=fn('_Z13vd_score_ce_pPKfS0_PKiPfS3_S3_S3_iiiffP12ihipStream_t', [p] * 7 + [i, i, i, f, f, p]),
-        logsoftmax_nll=fn('_Z19vd_logsoftmax_nll_pPflliPKiS1_S_ifP12ihipStream_t', [p, l, l, i, p, p, p, i, f, p]),
-        clip_scale=fn('_Z20vd_grad_clip_scale_pPKflffPfP12ihipStream_t', [p, l, f, f, p, p]),
-        clip_decay_adam=fn('_Z20vd_clip_decay_adam_pPfS_S_S_lffffffPKffP12ihipStream_t', [p] * 4 + [l] + [f] * 6 + [p, f, p]),
-        work_floats=int(work()))
+        score_ce=_lib.internal('vd_score_ce_p'), logsoftmax_nll=_lib.internal('vd_logsoftmax_nll_p'),
+        clip_scale=_lib.internal('vd_grad_clip_scale_p'), clip_decay_adam=_lib.internal('vd_clip_decay_adam_p'),
+        work_floats=int(_lib.internal('vd_clip_work_floats', C.c_int64)()))
 
 
 def stream():

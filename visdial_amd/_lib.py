@@ -5,6 +5,7 @@ call fails this module raises -- it never routes to the oracle or to torch ops.
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VD_LIB_PATH") or os.path.join(_HERE, "libvisdial_hip.so")   # override: A/B builds
@@ -190,3 +191,76 @@ def call(name, *args):
     if rc != 0:
         raise VisdialHipError("%s failed (%d): %s" % (name, rc, lib.vd_last_error().decode()))
     return rc
+
+
+# ---- internal C++ entry points (csrc/rt_core.h, csrc/common.h): not part of the C ABI, bound from the symbols the library exports.
+# An Itanium-mangled name spells every parameter type, so name AND argtypes follow the built library: no hand-written copy can go stale.
+_BUILTIN = {'i': C.c_int, 'j': C.c_uint, 'l': C.c_int64, 'm': C.c_uint64, 'x': C.c_longlong, 'y': C.c_ulonglong, 'f': C.c_float,
+            'd': C.c_double, 'b': C.c_bool, 'a': C.c_byte, 'h': C.c_ubyte, 'c': C.c_char, 's': C.c_short, 't': C.c_ushort,
+            'v': None}                                         # None: legal only behind a pointer or reference (void, a class)
+
+
+def decode_argtypes(symbol, name):
+    """argtypes of the function `name` from its mangled `symbol`.  Builtins by width and kind, every pointer or reference c_void_p, K
+    transparent, S_ / S<n>_ from the substitution candidates in Itanium order; anything else raises -- it never guesses."""
+    head = '_Z%d%s' % (len(name), name)
+    if not symbol.startswith(head) or symbol == head:
+        raise VisdialHipError("%s is not the mangled name of a function %s" % (symbol, name))
+    s, subs = symbol[len(head):], []
+
+    def one(i):                                                # -> (ctypes type or None, index behind the type)
+        c, m = s[i:i + 1], re.match(r'S([0-9A-Z]*)_|\d+', s[i:])
+        if c in ('P', 'R', 'K'):
+            t, j = one(i + 1)
+            subs.append(t if c == 'K' else _p)
+            return subs[-1], j
+        if m and c == 'S':
+            k = int(m.group(1), 36) + 1 if m.group(1) else 0
+            if k < len(subs):
+                return subs[k], i + m.end()
+        elif m:                                                # <len>ident: a class or a typedef'd struct
+            subs.append(None)
+            return None, i + m.end() + int(m.group())
+        elif c in _BUILTIN:
+            return _BUILTIN[c], i + 1
+        raise VisdialHipError("%s: cannot bind the parameter at '%s'" % (symbol, s[i:]))   # variadic, template, nested name, function, ...
+
+    out, i = [], 0
+    while i < len(s) and s != 'v':
+        t, j = one(i)
+        if t is None or j > len(s):
+            raise VisdialHipError("%s: void or a class by value, or a truncated name, at '%s'" % (symbol, s[i:]))
+        out.append(t)
+        i = j
+    return out
+
+
+_exports = None            # every _Z<len>vd_... string in the library image (read once)
+_internal = {}
+
+
+def internal(name, restype=C.c_int):
+    """The internal entry point `name`, bound from the one symbol the library exports for it.  restype c_int: raises VisdialHipError with
+    vd_last_error() on a non-zero return, like call(); any other restype returns the raw value.  .symbol / .argtypes say what was bound."""
+    global _exports
+    if (name, restype) in _internal:
+        return _internal[name, restype]
+    lib = load()
+    if _exports is None:
+        with open(LIB_PATH, 'rb') as f:
+            _exports = set(m.decode() for m in re.findall(rb'_Z\d+vd_[A-Za-z0-9_]*', f.read()))
+    head = '_Z%d%s' % (len(name), name)
+    found = sorted(m for m in _exports if m.startswith(head) and hasattr(lib, m))
+    if len(found) != 1:
+        raise VisdialHipError("%s: %s in %s" % (name, "overloaded: " + ", ".join(found) if found else "no exported symbol", LIB_PATH))
+    raw = lib[found[0]]
+    raw.argtypes, raw.restype = decode_argtypes(found[0], name), restype
+
+    def fn(*args):
+        rc = raw(*args)
+        if restype is C.c_int and rc != 0:
+            raise VisdialHipError("%s failed (%d): %s" % (name, rc, lib.vd_last_error().decode()))
+        return rc
+    fn.symbol, fn.argtypes = found[0], raw.argtypes
+    _internal[name, restype] = fn
+    return fn
