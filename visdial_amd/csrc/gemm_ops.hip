@@ -445,6 +445,18 @@ int vd_gemm_nn_live_p(const float* A, int64_t lda, const float* B, int64_t ldb, 
   return launch_gemm<CfgBig>(M, N, K, 1, a, b, e, s);
 }
 
+// split_core.h's contraction alone, below the K thresholds of vd_gemm_tn_acc: nprod = 9 (the split9 pass) or 1 (the bf16 pass's encoder
+// weight gradients); M % 256 == 0, N % 128 == 0, K % 16 == 0.  Internal (declared in split_core.h): tests/test_dwh_coop_split_gpu.py.
+int vd_gemm_split_tn_p(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N, int K, int nprod,
+                       hipStream_t stream) {
+  VD_CHECK_ARG(A && B && C && M > 0 && N > 0 && K >= 0 && (nprod == 9 || nprod == 1), "vd_gemm_split_tn_p: bad args M=%d N=%d K=%d nprod=%d",
+               M, N, K, nprod);
+  if (int rc = check_align(A, lda, "vd_gemm_split_tn_p A")) return rc;
+  if (int rc = check_align(B, ldb, "vd_gemm_split_tn_p B")) return rc;
+  if (nprod == 9) return launch_gemm_split_tn<9>(M, N, K, A, lda, B, ldb, C, ldc, stream);
+  return launch_gemm_split_tn<1>(M, N, K, A, lda, B, ldb, C, ldc, stream);
+}
+
 extern "C" {
 
 // C[M x N] += A[K x M]^T * B[K x N]   (weight gradients; split-K with float atomics)

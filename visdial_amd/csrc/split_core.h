@@ -103,6 +103,18 @@ static int weights_to_bf16x3(const float* src, vd_bf16_bits* dst, long n, hipStr
   return VD_OK;
 }
 
+// The dynamic-LDS limit of a kernel is an attribute of the kernel ON ONE DEVICE: it is raised once per device ordinal, not once per process
+// (past the table, on every launch).
+constexpr int SPLIT_ATTR_DEVS = 64;
+static int split_lds_attr(const void* kern, bool (&done)[SPLIT_ATTR_DEVS]) {
+  int dev = 0;
+  VD_HIP(hipGetDevice(&dev));
+  if (dev >= 0 && dev < SPLIT_ATTR_DEVS && done[dev]) return VD_OK;
+  VD_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  if (dev >= 0 && dev < SPLIT_ATTR_DEVS) done[dev] = true;
+  return VD_OK;
+}
+
 struct SplitCfg {
     static constexpr int NT = 4, WM = 4, THREADS = 64 * WM;
   static constexpr int BM = 32 * WM, BN = 128, KS = 32;           // four waves of 32 rows x 128 columns; one macro step = 32 k
@@ -304,11 +316,8 @@ static int launch_gemm_split(int M, int N, int K, const float* A, long lda, cons
                "launch_gemm_split: unsupported shape M=%d N=%d K=%d", M, N, K);
   const int tiles_m = vd_cdiv(M, Cfg::BM), tiles_n = vd_cdiv(N, Cfg::BN);
   auto kern = gemm_split_kernel<NPROD, Epi>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    VD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  static bool attr_set[SPLIT_ATTR_DEVS] = {};
+  if (const int rc = split_lds_attr(reinterpret_cast<const void*>(kern), attr_set)) return rc;
   hipLaunchKernelGGL(kern, dim3(split_grid(tiles_m, tiles_n)), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, M, N, K, tiles_n, A, lda, B, ldb, bplane, e);
   VD_LAUNCH_CHECK();
   return VD_OK;
@@ -326,27 +335,39 @@ static int launch_gemm_split(int nprod, int M, int N, int K, const float* A, lon
 // ---------------------------------------------------------------------------------------------------------------------------
 // The same exact split for the weight-gradient contraction  C[M x N] += A[K x M]^T * B[K x N]  (dWh = h^T * da over all
 // (timestep, row) pairs: K = 380 000 at the headline shape).  Both operands are fp32 rows contracted over their ROW index, so
-// NEITHER can be converted ahead of time without another pass over 4 GB: tiles go global -> LDS by DMA as [16 k][256 m] and
-// [16 k][128 n] fp32 (k-major, dense: a row of the tile is a row segment of the operand), a wave reads its MFMA fragments with
-// ds_read_b32 (lane = one m or n, 8 consecutive k: conflict-free, lanes 0-31 walk one k row) and splits BOTH in registers.
-// A wave owns 64 m x 128 n (8 accumulator tiles): 48 split values (16 of A, 32 of B) per 72 MFMAs.  Split-K over the rows with
+// NEITHER can be converted ahead of time without another pass over 4 GB: tiles go global -> LDS by DMA as fp32, A as [16 k][256 m]
+// (k-major, dense: a row of the tile is a row segment of the operand), B as four column tiles [16 k][32 n].  A wave owns 64 m x 128 n
+// (8 accumulator tiles).  Its A rows are its own: it reads the fragments with ds_read_b32 (lane = one m, 8 consecutive k: conflict-free,
+// lanes 0-31 walk one k row) and splits them in registers.  The B tile is shared by the four waves and is split ONCE per workgroup: wave
+// w splits column tile w and leaves the three planes in LDS as MFMA fragments, every wave reads them with ds_read_b128 -- 16 + 8 split
+// values per wave and 72 MFMAs where a split per wave took 16 + 32 (profiles/dwh_coop_split.txt).  Split-K over the rows with
 // float atomics at the end; the splits of one K range run on ONE XCD (block b runs on XCD b % 8), so the 16 column tiles that
 // read the same h rows and the 2 row tiles that read the same da rows share them through that XCD's L2.
 // ---------------------------------------------------------------------------------------------------------------------------
 struct SplitTnCfg {
   static constexpr int BM = 256, BN = 128, THREADS = 256;
   static constexpr int ATILE = 16 * BM * 4;                       // [16 k][256 m] fp32
-  static constexpr int BTILE = 16 * BN * 4;                       // [16 k][128 n] fp32
-  static constexpr int STAGE = ATILE + BTILE;                     // 24 KB
-  static constexpr int LDS_BYTES = 2 * STAGE;                     // 48 KB: two workgroups per CU (the registers allow no more)
+  static constexpr int BQUART = 16 * 32 * 4;                      // [16 k][32 n] fp32: one column tile of B, what one wave splits
+  // the same column tile as MFMA fragments, [plane][lane] 16 bytes, is written over the fp32 quarter: a block holds the larger of the two
+  static constexpr int nplanes(int nprod) { return nprod >= 6 ? 3 : nprod >= 3 ? 2 : 1; }   // planes of B that an issued product reads
+  static constexpr int bblock(int nprod) { return nplanes(nprod) * 1024 > BQUART ? nplanes(nprod) * 1024 : BQUART; }
+  static constexpr int stage(int nprod) { return ATILE + 4 * bblock(nprod); }               // 28 KB (24 KB below six products)
+  static constexpr int lds_bytes(int nprod) { return 2 * stage(nprod); }
+  static constexpr int LDS_BYTES = 2 * (ATILE + 4 * 3 * 1024);    // 56 KB = lds_bytes(9): two workgroups per CU (the registers allow no more)
+  static constexpr int SIDE_LDS = 41 * 1024;                      // the table-gradient chain / grouped weight gradients beside it
 };
 static_assert(SplitTnCfg::BM == VD_SPLIT_TN_BM && SplitTnCfg::BN == VD_SPLIT_TN_BN, "paths.h vd_tn_split_tiles");
+// two of these and one 41 KB side-lane workgroup share a CU's 160 KB: 2 x 56 + 41 = 153.  At 60 KB (a plane buffer beside the fp32 tile)
+// the side lane is locked out and the step loses what the contraction gains (profiles/r06_experiments.txt section 5c).
+static_assert(SplitTnCfg::LDS_BYTES == SplitTnCfg::lds_bytes(9) && SplitTnCfg::lds_bytes(1) == 48 * 1024, "nine products: 56 KB; one: 48 KB");
+static_assert(2 * SplitTnCfg::LDS_BYTES + SplitTnCfg::SIDE_LDS <= 160 * 1024, "the side lane's workgroups must fit beside two of these");
 
 template <int NPROD>
 __global__ void __launch_bounds__(256, 2)
 gemm_split_tn_kernel(int M, int N, int kchunk, int K, int tiles, int tiles_n, int splits, const float* A, long lda, const float* B, long ldb,
                      float* C, long ldc) {
   using Cfg = SplitTnCfg;
+  constexpr int NPL = Cfg::nplanes(NPROD), BBLK = Cfg::bblock(NPROD), STAGE = Cfg::stage(NPROD);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   // tile / K-range of this workgroup: XCD x takes the K ranges [x * spx, (x + 1) * spx) (spx = splits / 8) and all tiles of each
   int tile, split;
@@ -372,103 +393,178 @@ gemm_split_tn_kernel(int M, int N, int kchunk, int K, int tiles, int tiles_n, in
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[mb][j][r] = 0.f;
 
-  // DMA: A rows are 1 KB (one instruction per k row: 4 per wave), B rows 512 bytes (two k rows per instruction: 2 per wave)
+  // DMA: A rows are 1 KB (one instruction per k row: 4 per wave).  B lands as four column tiles [j][16 k][32 n], each at the head of its
+  // 3 KB block; wave w fetches column tile w, the one it splits: 8 k rows of 128 bytes per instruction (lane: k row lane >> 3, 16-byte
+  // chunk lane & 7; the eight lanes of a k row fetch one 128-byte line), 2 per wave
   unsigned voffa[4], voffb[2];
 #pragma unroll
   for (int i = 0; i < 4; ++i) voffa[i] = (unsigned)(((long)(wm * 4 + i) * lda + m_base + lane * 4) * 4);
 #pragma unroll
-  for (int i = 0; i < 2; ++i) voffb[i] = (unsigned)(((long)((wm * 2 + i) * 2 + (lane >> 5)) * ldb + n_base + (lane & 31) * 4) * 4);
+  for (int i = 0; i < 2; ++i) voffb[i] = (unsigned)(((long)(i * 8 + (lane >> 3)) * ldb + n_base + wm * 32 + (lane & 7) * 4) * 4);
   const unsigned lds0 = (unsigned)(uintptr_t)smem;
   auto issue = [&](int m, int st) {
-    const unsigned base = lds0 + st * Cfg::STAGE;
+    const unsigned base = lds0 + st * STAGE;
     const float* ak = A + (long)(ks + m * 16) * lda;
     const float* bk = B + (long)(ks + m * 16) * ldb;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) glds16(voffb[i], bk, base + Cfg::ATILE + (wm * 2 + i) * 1024);
+    for (int i = 0; i < 2; ++i) glds16(voffb[i], bk, base + Cfg::ATILE + wm * BBLK + i * 1024);
 #pragma unroll
     for (int i = 0; i < 4; ++i) glds16(voffa[i], ak, base + (wm * 4 + i) * 1024);
   };
   const int hi = lane >> 5, l31 = lane & 31;
 
-  // one 16-k step on stage ST, a compile-time constant: every LDS address of the step is then one of two lane registers plus an immediate
-  // (the second 32-row block of A gets a base of its own, opaque to the compiler, which then pairs the k rows of one block into
-  //  ds_read2st64_b32 with immediate offsets; given one base it pairs the two blocks of a k row and spends a register or an add per k row)
+  // the second 32-row block of A gets a base of its own, opaque to the compiler, which then pairs the k rows of one block into
+  // ds_read2st64_b32 with immediate offsets; given one base it pairs the two blocks of a k row and spends a register or an add per k row
   int mb1 = 32;
   asm("" : "+v"(mb1));
   const float* sA0 = smem + (hi * 8) * Cfg::BM + wm * 64 + l31;
   const float* sA1 = sA0 + mb1;
-  const float* sB0 = smem + Cfg::ATILE / 4 + (hi * 8) * Cfg::BN + l31;
-  auto step = [&](int m, auto stage) {
-    constexpr int st = decltype(stage)::value;
-    if (m + 1 < nm) {
-      issue(m + 1, st ^ 1);
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    asm volatile("s_barrier" ::: "memory");
-    const float* sB = sB0 + st * (Cfg::STAGE / 4);
-    // Software pipeline inside the step: the A planes and the B planes of column tile 0 are converted up front; then the 18 MFMAs of column
-    // tile j are issued INTERLEAVED with the fragment reads and the split of column tile j + 1 (sched_group_barrier: one MFMA, four VALU
-    // instructions, ...), so most of the ~240 VALU instructions a step spends on splitting sit in the shadow of the matrix pipe instead of
-    // in front of it (left to itself the compiler hoists every conversion above the first MFMA: 5.91 -> 5.51 ms on the headline dWh).
-    // The split's instructions are inline asm (vd_split3), which the group barriers do not count as VALU: they order the MFMAs and the
-    // fragment reads, and the split falls between them by its dependences -- coarser than four per MFMA (profiles/split_loop_issue.txt).
-    // (Measured and dropped: three LDS stages with one barrier per step and the NEXT step's first conversions under the last column
-    //  tile's MFMAs -- 5.82 ms; largest products first so that a step's first MFMAs need only the hi planes -- 5.68 vs 5.61 ms.)
+  const float* sBq = smem + (Cfg::ATILE + wm * BBLK) / 4 + (hi * 8) * 32 + l31;            // this wave's column tile, fp32
+  const char* sBp = reinterpret_cast<const char*>(smem) + Cfg::ATILE + lane * 16;          // the planes: + j * BBLK + plane * 1024
+  constexpr int LIM = NPROD >= 9 ? 4 : NPROD >= 6 ? 2 : NPROD >= 3 ? 1 : 0;                // products with pa + pb <= LIM are issued
+  // The B tile is shared by the four waves, so it is split ONCE per workgroup: wave w fetches column tile w itself, reads it (lane = one n,
+  // 8 consecutive k) behind its own vmcnt, splits it and stores the planes as MFMA fragments, [plane][lane] 16 bytes, over the block whose
+  // first 2 KB it has just read -- no other wave reads that fp32 quarter or writes that block, so the wave's own program order guards it.
+  auto read_own = [&](int st, float4& u, float4& w) {
+    const float* p = sBq + st * (STAGE / 4);
+    u = make_float4(p[0], p[32], p[2 * 32], p[3 * 32]);
+    w = make_float4(p[4 * 32], p[5 * 32], p[6 * 32], p[7 * 32]);
+  };
+  auto write_own = [&](int st, const float4& u, const float4& w) {
+    vd_bf16x8 own[3];
+    vd_split3(u, w, own[0], own[1], own[2]);
+    char* d = const_cast<char*>(sBp) + st * STAGE + wm * BBLK;
+#pragma unroll
+    for (int pl = 0; pl < NPL; ++pl) *reinterpret_cast<vd_bf16x8*>(d + pl * 1024) = own[pl];
+  };
+  // One 16-k step on stage st -- in the main loop a compile-time constant: every LDS address of the step is then a lane register plus an
+  // immediate; the last step of a K range takes it at run time.  A step is entered behind ONE barrier, in front of which every wave has
+  // waited for its DMA share of this step (vmcnt), for its reads of the other stage and for its plane stores of this step (lgkmcnt): the
+  // other stage may be refilled at once, A and the planes of this stage may be read.  Every wave reads the planes of all four column
+  // tiles, 3 ds_read_b128 per tile in place of 8 ds_read_b32 and a split: those of tile j + 1 under the 18 MFMAs of tile j.  Under the
+  // MFMAs of the LAST tile the wave splits its column tile of the NEXT step, whose two DMA instructions it issued first at the top of
+  // this step (vmcnt(4): the four of A may still fly), and stores the planes into the other stage: the split of B has left the front of
+  // the step, and the step's one barrier publishes it.  In front of the MFMAs stands the split of the wave's first A block only, while
+  // the first planes are on their way; the second block is split between the first tile's MFMAs.
+  // Planes, products and their order per accumulator are those of a per-wave split, so a workgroup's sum is bit for bit the same.
+  // Measured (profiles/dwh_coop_split.txt): the split behind the step's first barrier with a barrier of its own to publish it, as the
+  // per-wave kernel's pipeline suggests, 5.44 -> 5.31 ms alone; this schedule 5.82 -> 5.31 ms on a slower box.
+  // (Measured and dropped on the per-wave split: three LDS stages with the NEXT step's first conversions under the last column tile's
+  //  MFMAs -- 5.82 ms; largest products first so that a step's first MFMAs need only the hi planes -- 5.68 vs 5.61 ms.)
+  auto step = [&](int m, auto stage, auto has_next) {
+    const int st = stage, other = st ^ 1;
+    constexpr bool next = decltype(has_next)::value;
+    if constexpr (next) issue(m + 1, st ^ 1);
     vd_bf16x8 ap[2][3], bp[2][3];
-    auto load_b = [&](int j, vd_bf16x8 (&dst)[3]) {
-      const float* p = sB + j * 32;
-      const float4 u = make_float4(p[0], p[Cfg::BN], p[2 * Cfg::BN], p[3 * Cfg::BN]);
-      const float4 w = make_float4(p[4 * Cfg::BN], p[5 * Cfg::BN], p[6 * Cfg::BN], p[7 * Cfg::BN]);
-      vd_split3(u, w, dst[0], dst[1], dst[2]);
-    };
+    float4 au[2], aw[2], u, w;
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb) {
-      const float* p = (mb ? sA1 : sA0) + st * (Cfg::STAGE / 4);
-      const float4 u = make_float4(p[0], p[Cfg::BM], p[2 * Cfg::BM], p[3 * Cfg::BM]);
-      const float4 w = make_float4(p[4 * Cfg::BM], p[5 * Cfg::BM], p[6 * Cfg::BM], p[7 * Cfg::BM]);
-      vd_split3(u, w, ap[mb][0], ap[mb][1], ap[mb][2]);
+      const float* q = (mb ? sA1 : sA0) + st * (STAGE / 4);
+      au[mb] = make_float4(q[0], q[Cfg::BM], q[2 * Cfg::BM], q[3 * Cfg::BM]);
+      aw[mb] = make_float4(q[4 * Cfg::BM], q[5 * Cfg::BM], q[6 * Cfg::BM], q[7 * Cfg::BM]);
     }
-    load_b(0, bp[0]);
+    const char* sP = sBp + st * STAGE;
+    auto load_b = [&](int j, vd_bf16x8 (&dst)[3]) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      __builtin_amdgcn_sched_barrier(0);
-      if (j + 1 < 4) load_b(j + 1, bp[(j + 1) & 1]);
+      for (int pl = 0; pl < NPL; ++pl) dst[pl] = *reinterpret_cast<const vd_bf16x8*>(sP + j * BBLK + pl * 1024);
+    };
+    load_b(0, bp[0]);
+    __builtin_amdgcn_sched_barrier(0);                            // all the reads are in flight before the first conversion waits
+    vd_split3(au[0], aw[0], ap[0][0], ap[0][1], ap[0][2]);
+    // column tile 0: the products of the first A block first, the second block's split between them, pair by pair (an accumulator still
+    // receives its products in the same order; a chain on one accumulator costs this MFMA nothing)
+    __builtin_amdgcn_sched_barrier(0);
+    {
+      unsigned h[4], md[4], lo[4];
+      auto pair = [&](int i) {
+        vd_split3_pair(i == 0 ? au[1].x : i == 1 ? au[1].z : i == 2 ? aw[1].x : aw[1].z, i == 0 ? au[1].y : i == 1 ? au[1].w : i == 2 ? aw[1].y : aw[1].w,
+                       h[i], md[i], lo[i]);
+      };
+      int idx = 0;
 #pragma unroll
       for (int pb = 2; pb >= 0; --pb)
 #pragma unroll
         for (int pa = 2; pa >= 0; --pa) {
-          constexpr int LIM = NPROD >= 9 ? 4 : NPROD >= 6 ? 2 : NPROD >= 3 ? 1 : 0;
+          if (pa + pb > LIM) continue;
+          acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[0][pa], bp[0][pb], acc[0][0], 0, 0, 0);
+          if (idx < 4) {
+            __builtin_amdgcn_sched_barrier(0);
+            pair(idx);
+            if (idx == 3) load_b(1, bp[1]);                       // (behind the last pair: its registers are free by now)
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          ++idx;
+        }
+#pragma unroll
+      for (int i = idx; i < 4; ++i) pair(i);
+      if (idx < 4) load_b(1, bp[1]);
+      ap[1][0] = __builtin_bit_cast(vd_bf16x8, (vd_u32x4){h[0], h[1], h[2], h[3]});
+      ap[1][1] = __builtin_bit_cast(vd_bf16x8, (vd_u32x4){md[0], md[1], md[2], md[3]});
+      ap[1][2] = __builtin_bit_cast(vd_bf16x8, (vd_u32x4){lo[0], lo[1], lo[2], lo[3]});
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int pb = 2; pb >= 0; --pb)
+#pragma unroll
+        for (int pa = 2; pa >= 0; --pa) {
+          if (pa + pb > LIM) continue;
+          acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[1][pa], bp[0][pb], acc[1][0], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {
+      __builtin_amdgcn_sched_barrier(0);
+      if (j + 1 < 4) {
+        load_b(j + 1, bp[(j + 1) & 1]);
+      } else if constexpr (next) {
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");          // this wave's column tile of step m + 1 has landed
+        read_own(other, u, w);
+      }
+#pragma unroll
+      for (int pb = 2; pb >= 0; --pb)
+#pragma unroll
+        for (int pa = 2; pa >= 0; --pa) {
           if (pa + pb > LIM) continue;
 #pragma unroll
           for (int mb = 0; mb < 2; ++mb) acc[mb][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[mb][pa], bp[j & 1][pb], acc[mb][j], 0, 0, 0);
         }
       if (j + 1 < 4) {
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);        // the next tile's fragment reads first (their latency hides under the MFMAs)
-#pragma unroll
-        for (int i = 0; i < 18; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA ...
-          __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);      // ... four VALU instructions of the next tile's split
-        }
+        __builtin_amdgcn_sched_group_barrier(0x100, NPL, 0);      // the next tile's plane reads first: they fly under these MFMAs
+      } else if constexpr (next) {
+        write_own(other, u, w);
+        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);        // the reads, then the split between the MFMAs by its dependences
+        __builtin_amdgcn_sched_group_barrier(0x008, LIM >= 4 ? 14 : 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x200, NPL, 0);      // the stores leave under the last MFMAs
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   };
   if (nm > 0) {
+    const std::integral_constant<int, 0> s0{};
+    const std::integral_constant<int, 1> s1{};
     issue(0, 0);
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    float4 u, w;
+    read_own(0, u, w);
+    write_own(0, u, w);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    // the main loop runs the steps that a step follows, two at a time (one per stage); the last step, on either stage, is peeled behind it
     int m = 0;
-    for (; m + 1 < nm; m += 2) {
-      step(m, std::integral_constant<int, 0>{});
-      step(m + 1, std::integral_constant<int, 1>{});
+    for (; m + 2 < nm; m += 2) {
+      step(m, s0, std::true_type{});
+      step(m + 1, s1, std::true_type{});
     }
-    if (m < nm) step(m, std::integral_constant<int, 0>{});
+    if (m + 2 == nm) step(m++, s0, std::true_type{});
+    step(m, m & 1, std::false_type{});
   }
   if (nm == 0) return;                            // (a K range past the end: the range count is rounded up to a multiple of 8)
   const EpiAtomic<4> e{C, ldc};
 #pragma unroll
   for (int mb = 0; mb < 2; ++mb) e(acc[mb], m_base + wm * 64 + mb * 32, n_base, lane, M, N);
 }
+
+// gemm_ops.hip: launch_gemm_split_tn<nprod> and nothing else, for the tests (bound by visdial_amd._lib.internal)
+int vd_gemm_split_tn_p(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N, int K, int nprod,
+                       hipStream_t stream);
 
 // C[M x N] += A[K x M]^T * B[K x N] on the exact split; M % 256 == 0, N % 128 == 0, K % 16 == 0 (the caller contracts a ragged tail elsewhere)
 template <int NPROD>
@@ -486,12 +582,9 @@ static int launch_gemm_split_tn(int M, int N, int K, const float* A, long lda, c
   splits = vd_cdiv(K, kchunk);
   if (splits >= 8) splits = (splits + 7) & ~7;        // (trailing K ranges past the end are empty workgroups)
   auto kern = gemm_split_tn_kernel<NPROD>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    VD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(tiles * splits), dim3(256), Cfg::LDS_BYTES, stream, M, N, kchunk, K, tiles, tiles_n, splits, A, lda, B, ldb, C, ldc);
+  static bool attr_set[SPLIT_ATTR_DEVS] = {};                  // per instantiation
+  if (const int rc = split_lds_attr(reinterpret_cast<const void*>(kern), attr_set)) return rc;
+  hipLaunchKernelGGL(kern, dim3(tiles * splits), dim3(256), Cfg::lds_bytes(NPROD), stream, M, N, kchunk, K, tiles, tiles_n, splits, A, lda, B, ldb, C, ldc);
   VD_LAUNCH_CHECK();
   return VD_OK;
 }
