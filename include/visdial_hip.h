@@ -167,7 +167,17 @@ int vd_lstm_backward(const float* Wh, float* gates, const float* c, const float*
  * Forward: gates1 must hold x*Wx1+b1 on entry (vd_gemm_nn); outputs as vd_lstm_forward for both layers.
  * Backward: gates1/gates2 are overwritten by da1/da2; dh_last2 [N x H] is the gradient at the top
  * layer's last step; dh1_seq [T x N x H], dc1, dc2 [N x H] are scratch.  Weight gradients are then
- * formed by the caller with vd_gemm_tn_acc / vd_colsum_acc exactly as for vd_lstm_backward. */
+ * formed by the caller with vd_gemm_tn_acc / vd_colsum_acc exactly as for vd_lstm_backward.
+ * Live-row counts (nact != NULL).  The rows are sorted by decreasing length and a row is pad BEFORE its first token, so the
+ * counts are NON-DECREASING in t, each in [0, N]; both entries refuse a count outside [0, N] and the backward entry refuses
+ * counts that decrease (VD_ERR_ARG, nothing is written).  Inside its span a row is still masked per token by tok_mask.
+ * Only rows [0, nact[t]) of step t are read or written; the CALLER zero-fills what the skipped (t, row) pairs must read as:
+ *   forward:  rows >= nact[t] of gates1 (vd_zero_inactive_rows), and h1, c1, gates2, h2, c2 (whole buffers or those rows);
+ *   backward: nothing more -- gates1 / gates2 / c1 / c2 come from that forward; rows >= nact[t] of da1, da2 and dh1_seq
+ *             stay as they were (zero in gates1 / gates2, so the weight-gradient contractions may run over every row).
+ * dc1 / dc2 on return: without counts dL/dc0 of each layer, all N rows.  With counts, rows < nact[T-1] only (the others are
+ * not written): a row that is live from step t0 on holds the cell gradient flowing INTO step t0, which is dL/dc0 of its own
+ * sequence (its state before t0 is zero); for t0 = 0 that is dL/dc0. */
 typedef struct {
   int T, N;
   const int32_t* tok_mask;               /* [T x N] or NULL (maskZero) */
@@ -175,7 +185,8 @@ typedef struct {
   float *gates1, *h1, *c1, *gates2, *h2, *c2;
   const int32_t* nact;                   /* HOST int32[T] or NULL.  Rows sorted by sequence length: only rows
                                             [0, nact[t]) are non-pad at step t and are computed; the caller
-                                            zero-fills the rest (vd_zero_inactive_rows / memset) */
+                                            zero-fills the rest (vd_zero_inactive_rows / memset).  Non-decreasing
+                                            in t, 0 <= nact[t] <= N (see above) */
 } vd_lstm2_fwd_t;
 typedef struct {
   int T, N;
@@ -187,7 +198,8 @@ typedef struct {
   const float* dh_last2;
   float* dh1_seq;
   float *dc1, *dc2;
-  const int32_t* nact;                   /* HOST int32[T] or NULL, as in vd_lstm2_fwd_t */
+  const int32_t* nact;                   /* HOST int32[T] or NULL, as in vd_lstm2_fwd_t: non-decreasing in t (checked),
+                                            0 <= nact[t] <= N; dc1 / dc2 are written for rows < nact[T-1] only */
 } vd_lstm2_bwd_t;
 int vd_lstm2_forward(const vd_lstm2_fwd_t* stacks, int nstacks, int H, void* stream);
 int vd_lstm2_backward(const vd_lstm2_bwd_t* stacks, int nstacks, int H, void* stream);

@@ -1180,6 +1180,9 @@ int vd_lstm2_forward_p(const vd_lstm2_fwd_t* st, int nstacks, int H, int flags, 
                      st[s].h1 && st[s].c1 && st[s].gates2 && st[s].h2 && st[s].c2,
                  "vd_lstm2_forward: stack %d has null/empty fields", s);
     Tmax = st[s].T > Tmax ? st[s].T : Tmax;
+    for (int t = 0; st[s].nact && t < st[s].T; ++t)   // a count becomes a problem's M as it stands
+      VD_CHECK_ARG(st[s].nact[t] >= 0 && st[s].nact[t] <= st[s].N, "vd_lstm2_forward: stack %d: nact[%d] = %d outside [0, N = %d]", s, t,
+                   st[s].nact[t], st[s].N);
   }
   if ((flags & VD_FLAG_BF16) && H % 64 == 0) return lstm2_forward_ticks<CfgTickFwdBf16>(st, nstacks, H, Tmax, stream);
   return lstm2_forward_ticks<CfgFwdSmallC>(st, nstacks, H, Tmax, stream);
@@ -1194,6 +1197,14 @@ int vd_lstm2_backward_p(const vd_lstm2_bwd_t* st, int nstacks, int H, int flags,
                      st[s].gates2 && st[s].c2 && st[s].dh_last2 && st[s].dh1_seq && st[s].dc1 && st[s].dc2,
                  "vd_lstm2_backward: stack %d has null/empty fields", s);
     Tmax = st[s].T > Tmax ? st[s].T : Tmax;
+    for (int t = 0; st[s].nact && t < st[s].T; ++t) {
+      VD_CHECK_ARG(st[s].nact[t] >= 0 && st[s].nact[t] <= st[s].N, "vd_lstm2_backward: stack %d: nact[%d] = %d outside [0, N = %d]", s, t,
+                   st[s].nact[t], st[s].N);
+      // dc is initialised at the last step only, for its rows: a row that is live earlier but not there would read dc as it was left
+      VD_CHECK_ARG(t == 0 || st[s].nact[t] >= st[s].nact[t - 1],
+                   "vd_lstm2_backward: stack %d: nact must be non-decreasing in t (rows pad BEFORE their first token): nact[%d] = %d > nact[%d] = %d",
+                   s, t - 1, st[s].nact[t - 1], t, st[s].nact[t]);
+    }
   }
   if (flags & VD_FLAG_BF16) return lstm2_backward_ticks<CfgTickBwdBf16>(st, nstacks, H, Tmax, stream);   // (BK = 128 divides 4H)
   return lstm2_backward_ticks<CfgBwdSmallD>(st, nstacks, H, Tmax, stream);   // two register stages
