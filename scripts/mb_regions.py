@@ -3,14 +3,15 @@ v1.0 detector features through the native host: mn-att-ques-im-hist + disc, 20 d
 regions per image at most (S = 10, S2 = 100), C = 2048, H = K = 512, split9, random weights, one synthetic batch uploaded once per path.
 
   --mode step (default): the training step (vd_model_forward_backward(m, 0) + vd_model_loss; no update) on
-      plain      no attachment: the four unmasked kernels
-      full       '@img_regions' with every count = 100: the masked kernels over every region
-      mixed      counts uniform in 10 .. 100 (fixed seed; the hidden rows of the features zero): the masked kernels over 55 % of the rows
+      plain      no attachment: the four head kernels with a null cnt
+      full       '@img_regions' with every count = 100: the same kernels with counts, over every region
+      mixed      counts uniform in 10 .. 100 (fixed seed; the hidden rows of the features zero): the same kernels over 55 % of the rows
     alternated in one process after warm-up; per path the median step time over --repeats windows of --inner steps with min / max.
     --paths plain runs the first alone (a library that does not know the attachment -- the parent commit's, through VD_LIB_PATH);
     --tag NAME marks the process's lines for an A/B of two libraries, processes alternated by the caller.
   --mode trace: --inner steps of every path after a warm-up, nothing timed: run it under `rocprofv3 --kernel-trace --stats` for the times of
-      img_att_{score,wsum,dscore,dz}_kernel against their _regions twins, and for the share of the three dense image products
+      img_att_{score,wsum,dscore,dz}_kernel with and without counts (one kernel each: the paths are told apart by their order in the
+      trace; a library from before the fold shows the counted launches under _regions names), and for the share of the three dense image products
       (EpiImgCommon, EpiImgTrBwd, the TN weight gradient) in the step.
 
     python scripts/mb_regions.py [--mode step|trace] [--repeats 15] [--inner 5] [--paths all|plain,full,mixed] [--tag NAME]"""

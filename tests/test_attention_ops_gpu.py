@@ -167,14 +167,22 @@ def test_image_attention_fp32_chain(ops, B, R, S2, H, Kc, use_drop):
 
 
 # ------------------------------------------------------------------------------------------------------------ 2. the split products
-@pytest.mark.parametrize("use_mask", [False, True])
-@pytest.mark.parametrize("H", [4, 192])
-def test_img_drop_gather_is_the_gather_bit_for_bit(ops, internal, H, use_mask):
-    B, R, S2 = 2, 3, 49
-    N = B * R
+GATHER_SHAPE, GATHER_H = (2, 3, 49), [4, 192]
+
+
+def gather_inputs(H, use_mask):
+    B, R, S2 = GATHER_SHAPE
     rng = np.random.RandomState(H + int(use_mask))
     pre = f32(rng, B * S2, H)
-    m1 = (rng.rand(N * S2, H) > 0.5).astype(np.uint8) if use_mask else None
+    return pre, (rng.rand(B * R * S2, H) > 0.5).astype(np.uint8) if use_mask else None
+
+
+@pytest.mark.parametrize("use_mask", [False, True])
+@pytest.mark.parametrize("H", GATHER_H)
+def test_img_drop_gather_is_the_gather_bit_for_bit(ops, internal, H, use_mask):
+    B, R, S2 = GATHER_SHAPE
+    N = B * R
+    pre, m1 = gather_inputs(H, use_mask)
     rows = ((np.arange(N) // R)[:, None] * S2 + np.arange(S2)[None, :]).reshape(-1)
     want = pre[rows]
     if use_mask:
@@ -305,14 +313,23 @@ def test_split9_weight_gradient(ops, internal, what, shape, H, Kc, with_xdrop, s
 
 
 # ------------------------------------------------------------------------------------------------------------ 3. hrea, rowdot, mn
-@pytest.mark.parametrize("B,R,H", [(1, 1, 4), (3, 10, 36), (2, 16, 512), (5, 10, 512)])
-def test_hrea_attention(ops, B, R, H):
+HREA_CASES = [(1, 1, 4), (3, 10, 36), (2, 16, 512), (5, 10, 512)]
+MN_CASES = [(1, 1, 4), (3, 10, 36), (7, 10, 512)]
+
+
+def hrea_inputs(B, R, H):
     rng = np.random.RandomState(B * 100 + R * 10 + H)
-    N = B * R
     sq, sh, h, datt = f32(rng, B, R), f32(rng, B, R), f32(rng, B, R, H) * np.float32(0.5), f32(rng, B, R, H)
     if R > 1:
         sh[0, 1] = -sq[0, R - 1]                 # dialog 0, round R - 1, fact 1 (visible): an exact zero -> ReplaceZero(-inf)
         assert sq[0, R - 1] + sh[0, 1] == 0.0
+    return sq, sh, h, datt
+
+
+@pytest.mark.parametrize("B,R,H", HREA_CASES)
+def test_hrea_attention(ops, B, R, H):
+    N = B * R
+    sq, sh, h, datt = hrea_inputs(B, R, H)
     P_ref, att_ref = ar.hrea_forward(sq, sh, h)
     dsq_ref, dsh_ref, dh_ref, dA = ar.hrea_backward(P_ref, h, datt)
     rep = ar.Report('hrea (%d, %d, %d):' % (B, R, H))
@@ -371,10 +388,18 @@ def random_mask(rng, B, R):
     return mask
 
 
-def run_mn(ops, B, R, H, mask, what, backward=True):
+def mn_inputs(B, R, H):
     rng = np.random.RandomState(B * 100 + R * 10 + H)
+    return f32(rng, B, R, H) * np.float32(0.2), f32(rng, B, R, H) * np.float32(0.2), f32(rng, B, R, H)
+
+
+def mn_mask(B, R, H, mask_kind):
+    return vo.causal_mask(B, R) if mask_kind == 'causal' else random_mask(np.random.RandomState(R + H), B, R)
+
+
+def run_mn(ops, B, R, H, mask, what, backward=True):
     N = B * R
-    q, h, dhatt = f32(rng, B, R, H) * np.float32(0.2), f32(rng, B, R, H) * np.float32(0.2), f32(rng, B, R, H)
+    q, h, dhatt = mn_inputs(B, R, H)
     p_ref, hatt_ref = vo.mn_attention_forward(q.astype(D), h.astype(D), mask)
     rep = ar.Report('mn (%d, %d, %d) %s:' % (B, R, H, what))
     last = [ar.row_block('dialog B - 1', B - 1, R)]
@@ -398,10 +423,9 @@ def run_mn(ops, B, R, H, mask, what, backward=True):
 
 
 @pytest.mark.parametrize("mask_kind", ['causal', 'random'])
-@pytest.mark.parametrize("B,R,H", [(1, 1, 4), (3, 10, 36), (7, 10, 512)])
+@pytest.mark.parametrize("B,R,H", MN_CASES)
 def test_mn_attention(ops, B, R, H, mask_kind):
-    mask = vo.causal_mask(B, R) if mask_kind == 'causal' else random_mask(np.random.RandomState(R + H), B, R)
-    run_mn(ops, B, R, H, mask, mask_kind)
+    run_mn(ops, B, R, H, mn_mask(B, R, H, mask_kind), mask_kind)
 
 
 def test_mn_attention_lds_guards(ops):

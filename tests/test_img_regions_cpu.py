@@ -250,7 +250,10 @@ def test_the_frozen_surfaces_stay_frozen():
         assert name not in header
     att = read('attention.hip')
     ext = att[att.index('extern "C" {'):att.index('}  // extern "C"')]
-    assert '_p(' not in ext and 'cnt' not in ext                                            # the C-ABI entry points are as they were
+    # the C-ABI entry points keep their signatures (the header above) and take no count: each is one call of its _p with a null cnt
+    assert 'cnt' not in ext and ext.count('_p(') == 2 and 'hipLaunchKernelGGL(img_att_' not in ext
+    for name in ('vd_img_att_forward', 'vd_img_att_backward'):
+        assert re.search(r'return %s_p\([^;]*\bnullptr, \(hipStream_t\)stream\);' % name, ext)
 
 
 def test_the_rules_stand_once_at_the_top_of_attention_hip_and_the_documents_name_the_attachment():
@@ -260,11 +263,12 @@ def test_the_rules_stand_once_at_the_top_of_attention_hip_and_the_documents_name
     for i in range(1, 7):
         assert att.count('IR%d:' % i) == 1 and 'IR%d:' % i in top
     assert [top.index('IR%d:' % i) for i in range(1, 7)] == sorted(top.index('IR%d:' % i) for i in range(1, 7))
-    # one shared body per kernel, two instantiations; the unmasked ones keep their names
+    # one kernel per stage under the name it always had, a nullable cnt its argument, launched from one place
+    assert '_regions_kernel' not in att and 'template <bool MASKED>' not in att
     for k in ('score', 'wsum', 'dscore', 'dz'):
-        assert att.count('void img_att_%s_body(' % k) == 1
-        assert att.count('img_att_%s_body<false>(' % k) == 1 and att.count('img_att_%s_body<true>(' % k) == 1
-        assert re.search(r'\nimg_att_%s_kernel\(' % k, att) and re.search(r'\nimg_att_%s_regions_kernel\(' % k, att)
+        decl = re.search(r'\nimg_att_%s_kernel\(([^)]*)\)' % k, att)
+        assert decl and 'const int32_t* __restrict__ cnt' in decl.group(1) and 'int R' in decl.group(1)
+        assert att.count('hipLaunchKernelGGL(img_att_%s_kernel,' % k) == 1
     ref = read('tests', 'region_ref.py')
     for i in range(1, 7):
         assert 'IR%d' % i in ref

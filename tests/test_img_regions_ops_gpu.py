@@ -256,3 +256,9 @@ def test_the_entry_points_refuse_bad_arguments(head):
     with pytest.raises(_lib.VisdialHipError, match='vd_img_att_backward_p: bad args'):
         head.backward(ptr(x), ptr(x), ptr(x), None, None, ptr(x), ptr(x), ptr(x), ptr(x), ptr(x), ptr(x), 1, 1, 4, 4, 6, 1.0, ptr(cnt),
                       stream())                                                                                                   # Kc % 4
+    # the C ABI is the same body with a null cnt: R = 0 is refused under the name that was called, before any kernel divides by it
+    with pytest.raises(_lib.VisdialHipError, match='vd_img_att_forward: bad args'):
+        _lib.call('vd_img_att_forward', ptr(x), ptr(x), ptr(x), ptr(x), None, ptr(x), ptr(x), ptr(x), 1, 0, 4, 4, 4, 1.0, stream())
+    with pytest.raises(_lib.VisdialHipError, match='vd_img_att_backward: bad args'):
+        _lib.call('vd_img_att_backward', ptr(x), ptr(x), ptr(x), None, None, ptr(x), ptr(x), ptr(x), ptr(x), ptr(x), ptr(x), 1, 0, 4, 4, 4, 1.0,
+                  stream())

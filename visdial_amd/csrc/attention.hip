@@ -13,7 +13,7 @@
 //
 // Image regions (batch attachment "@img_regions", runtime.hip): an image may carry fewer than S2 regions -- detector boxes, a different number
 // per image, padded to S2 rows.  cnt [B] int32 holds the number of regions of every image; the four streaming kernels of the attention head
-// then have a second instantiation of the same body that walks the live regions only.  The rules, restated in fp64 by tests/region_ref.py:
+// take it as a nullable argument and walk the live regions only (null = every region is live).  The rules, restated in fp64 by tests/region_ref.py:
 //  IR1: region s of image b is live iff s < cnt[b], with 1 <= cnt[b] <= S2.  Round n reads cnt[n / R]; with R = 1 the index is the row, which
 //       is the form forward_round uses.  The count is uniform over a workgroup: a scalar load and a uniform trip count, no divergence.
 //  IR2: the maximum, the sum and the softmax of the scores run over the live regions only; p[n, s] is written as exact +0.0 for s >= cnt.
@@ -23,8 +23,8 @@
 //       being read first, and dqc, dwa and dba add live regions only.  The three dense products, the bias column sum and img_proj's backward
 //       then need no change: a hidden row contributes 0 * finite.
 //  IR5: the hidden rows of the uploaded features must be finite, because the dense products still read them; the loaders write zeros there.
-//  IR6: with cnt[b] = S2 for every image each output that involves no atomic (p, u1, dscore, dz, dqc) is the unmasked kernel's bit for bit:
-//       the loop bounds are the only thing that changes.
+//  IR6: with cnt[b] = S2 for every image each output that involves no atomic (p, u1, dscore, dz, dqc) is the null-cnt launch's bit for bit:
+//       the count sets loop bounds and nothing else, and the zero-fill tails are empty loops at S2.
 #include "gemm_core.h"
 #include "split_core.h"
 
@@ -33,6 +33,27 @@
 // =====================================================================================
 #define MN_MAX_R 16
 typedef float MnScoreTile[MN_MAX_R * MN_MAX_R];   // one R x R score / probability tile in static LDS
+
+// Softmax of one row of n scores by one thread, left in s[0 .. n): s[j] = score(j), the max over j ascending, expf(s - max) in place, the
+// sum over j ascending, the scale by 1 / sum.  The one row arithmetic of the four history-attention kernels: row r of a round kernel
+// equals the full kernel's bit for bit because both run this (what the full kernel adds for a masked j > r are exact zeros).
+template <class Score>
+__device__ __forceinline__ void row_softmax(float* s, int n, Score score) {
+  float mx = -INFINITY;
+  for (int j = 0; j < n; ++j) {
+    const float v = score(j);
+    s[j] = v;
+    mx = fmaxf(mx, v);
+  }
+  float sum = 0.f;
+  for (int j = 0; j < n; ++j) {
+    const float e = expf(s[j] - mx);
+    s[j] = e;
+    sum += e;
+  }
+  const float inv = 1.f / sum;
+  for (int j = 0; j < n; ++j) s[j] *= inv;
+}
 
 // One 16-wave workgroup per dialog.  The R question states and R facts of the dialog (2 x 20 KB) are
 // staged in LDS with one coalesced pass, so the R*R dot products and the R*H weighted sums never touch
@@ -62,24 +83,9 @@ mn_att_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ Hm, con
   if (tid < R) {
     const int i = tid;
     const uint8_t* mrow = mask + ((long)b * R + i) * R;
-    float mx = -INFINITY;
-    for (int j = 0; j < R; ++j) {
-      float v = mrow[j] ? -9999999.f : S[i * MN_MAX_R + j];
-      S[i * MN_MAX_R + j] = v;
-      mx = fmaxf(mx, v);
-    }
-    float sum = 0.f;
-    for (int j = 0; j < R; ++j) {
-      const float e = expf(S[i * MN_MAX_R + j] - mx);
-      S[i * MN_MAX_R + j] = e;
-      sum += e;
-    }
-    const float inv = 1.f / sum;
-    for (int j = 0; j < R; ++j) {
-      const float pv = S[i * MN_MAX_R + j] * inv;
-      S[i * MN_MAX_R + j] = pv;
-      P[((long)b * R + i) * R + j] = pv;
-    }
+    float* row = S + i * MN_MAX_R;
+    row_softmax(row, R, [&](int j) { return mrow[j] ? -9999999.f : row[j]; });
+    for (int j = 0; j < R; ++j) P[((long)b * R + i) * R + j] = row[j];
   }
   __syncthreads();
   for (int idx = tid; idx < R * H; idx += MN_THREADS) {
@@ -151,25 +157,12 @@ hrea_att_fwd_kernel(const float* __restrict__ sq, const float* __restrict__ sh, 
   const float* h = Hm + (long)b * R * H;
   if (tid < R) {
     const int i = tid;
-    float mx = -INFINITY;
-    for (int j = 0; j < R; ++j) {
-      float v = (j > i) ? 0.f : sq[b * R + i] + sh[b * R + j];
-      v = (v == 0.f) ? -INFINITY : v;
-      S[i * MN_MAX_R + j] = v;
-      mx = fmaxf(mx, v);
-    }
-    float sum = 0.f;
-    for (int j = 0; j < R; ++j) {
-      const float e = expf(S[i * MN_MAX_R + j] - mx);
-      S[i * MN_MAX_R + j] = e;
-      sum += e;
-    }
-    const float inv = 1.f / sum;
-    for (int j = 0; j < R; ++j) {
-      const float pv = S[i * MN_MAX_R + j] * inv;
-      S[i * MN_MAX_R + j] = pv;
-      P[((long)b * R + i) * R + j] = pv;
-    }
+    float* row = S + i * MN_MAX_R;
+    row_softmax(row, R, [&](int j) {
+      const float v = (j > i) ? 0.f : sq[b * R + i] + sh[b * R + j];
+      return (v == 0.f) ? -INFINITY : v;
+    });
+    for (int j = 0; j < R; ++j) P[((long)b * R + i) * R + j] = row[j];
   }
   __syncthreads();
   for (int idx = tid; idx < R * H; idx += 256) {
@@ -270,13 +263,7 @@ struct SrcImgDropRow {
   __device__ __forceinline__ float4 ld4(int row, int k) const {
     const int n = row / S2, s = row - n * S2;
     float4 v = *reinterpret_cast<const float4*>(pre + ((long)(n / R) * S2 + s) * H + k);
-    if (mask) {
-      const uint32_t m = *reinterpret_cast<const uint32_t*>(mask + (long)row * H + k);
-      v.x = (m & 0xff) ? v.x * scale : 0.f;
-      v.y = (m & 0xff00) ? v.y * scale : 0.f;
-      v.z = (m & 0xff0000) ? v.z * scale : 0.f;
-      v.w = (m & 0xff000000u) ? v.w * scale : 0.f;
-    }
+    if (mask) v = vd_mask4(v, *reinterpret_cast<const uint32_t*>(mask + (long)row * H + k), scale);
     return v;
   }
 };
@@ -370,20 +357,19 @@ __device__ __forceinline__ float block_reduce(float v, float* red, int wave, int
   return r;
 }
 
-// The live region count of round n (IR1).  The unmasked instantiations (cnt is not read) keep S2, so their loops are what they were.
-template <bool MASKED>
+// The live region count L of round n (IR1): S2 without counts.  Every loop of the four kernels below that reads a region stops at L, and
+// the zero fills of IR2 / IR4 run from L to S2: empty loops when every region is live.
 __device__ __forceinline__ int img_live_regions(const int32_t* __restrict__ cnt, int n, int R, int S2) {
-  if (!MASKED) return S2;
-  return max(0, min(cnt[n / R], S2));   // n = blockIdx.x: a scalar load, uniform over the workgroup; clamped: no count can index outside a round
+  return cnt ? max(0, min(cnt[n / R], S2)) : S2;   // n = blockIdx.x: a scalar load, uniform over the workgroup; clamped: no count can index outside a round
 }
 
-// One body per kernel: L = S2 is the kernel as it was, L = cnt[n / R] its "_regions" twin (IR2 - IR4).
-template <bool MASKED>
-__device__ __forceinline__ void img_att_score_body(const float* __restrict__ iqc, const float* __restrict__ wa, const float* __restrict__ ba,
-                                                   float* __restrict__ p_out, int L, int S2, int Kc) {
+__global__ void __launch_bounds__(IMG_ATT_WAVES * 64)
+img_att_score_kernel(const float* __restrict__ iqc, const float* __restrict__ wa, const float* __restrict__ ba,
+                     float* __restrict__ p_out, const int32_t* __restrict__ cnt, int S2, int R, int Kc) {
   extern __shared__ float sc[];  // [S2]
   __shared__ float red[IMG_ATT_WAVES];
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int L = img_live_regions(cnt, n, R, S2);
   const float* iq = iqc + (long)n * S2 * Kc;
   const float b0 = ba[0];
   for (int s = wave; s < L; s += IMG_ATT_WAVES) {
@@ -408,29 +394,20 @@ __device__ __forceinline__ void img_att_score_body(const float* __restrict__ iqc
   }
   sum = block_reduce(sum, red, wave, lane, false);
   const float inv = 1.f / sum;
-  for (int s = tid; s < S2; s += IMG_ATT_WAVES * 64) p_out[(long)n * S2 + s] = (!MASKED || s < L) ? sc[s] * inv : 0.f;
-}
-__global__ void __launch_bounds__(IMG_ATT_WAVES * 64)
-img_att_score_kernel(const float* __restrict__ iqc, const float* __restrict__ wa, const float* __restrict__ ba,
-                     float* __restrict__ p_out, int S2, int Kc) {
-  img_att_score_body<false>(iqc, wa, ba, p_out, S2, S2, Kc);
-}
-__global__ void __launch_bounds__(IMG_ATT_WAVES * 64)
-img_att_score_regions_kernel(const float* __restrict__ iqc, const float* __restrict__ wa, const float* __restrict__ ba,
-                             float* __restrict__ p_out, const int32_t* __restrict__ cnt, int S2, int R, int Kc) {
-  img_att_score_body<true>(iqc, wa, ba, p_out, img_live_regions<true>(cnt, blockIdx.x, R, S2), S2, Kc);
+  for (int s = tid; s < S2; s += IMG_ATT_WAVES * 64) p_out[(long)n * S2 + s] = s < L ? sc[s] * inv : 0.f;
 }
 
 // 256 threads = 8 region groups x 32 lanes; lane l owns 4 consecutive channels of a 128-channel tile.
-template <bool MASKED>
-__device__ __forceinline__ void img_att_wsum_body(const float* __restrict__ pre, const uint8_t* __restrict__ mask1, const float* __restrict__ p,
-                                                  const float* __restrict__ u0, float* __restrict__ u1, int L, int S2, int R, int H,
-                                                  float scale) {
+__global__ void __launch_bounds__(256)
+img_att_wsum_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ mask1, const float* __restrict__ p,
+                    const float* __restrict__ u0, float* __restrict__ u1, const int32_t* __restrict__ cnt, int S2, int R, int H,
+                    float scale) {
   extern __shared__ float sh[];  // p [S2] | partial sums [8][128]
   float* ps = sh;
   float* part = sh + ((S2 + 3) & ~3);
   const int n = blockIdx.x, tid = threadIdx.x, g = tid >> 5, l = tid & 31;
   const int h = blockIdx.y * 128 + l * 4;
+  const int L = img_live_regions(cnt, n, R, S2);
   for (int s = tid; s < L; s += 256) ps[s] = p[(long)n * S2 + s];
   __syncthreads();
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -440,13 +417,7 @@ __device__ __forceinline__ void img_att_wsum_body(const float* __restrict__ pre,
 #pragma unroll 4
     for (int s = g; s < L; s += 8) {
       float4 v = *reinterpret_cast<const float4*>(pr + (long)s * H);
-      if (m1) {
-        const uint32_t m = *reinterpret_cast<const uint32_t*>(m1 + (long)s * H);
-        v.x = (m & 0xffu) ? v.x * scale : 0.f;
-        v.y = (m & 0xff00u) ? v.y * scale : 0.f;
-        v.z = (m & 0xff0000u) ? v.z * scale : 0.f;
-        v.w = (m & 0xff000000u) ? v.w * scale : 0.f;
-      }
+      if (m1) v = vd_mask4(v, *reinterpret_cast<const uint32_t*>(m1 + (long)s * H), scale);
       const float w = ps[s];
       acc.x += w * v.x; acc.y += w * v.y; acc.z += w * v.z; acc.w += w * v.w;
     }
@@ -463,18 +434,6 @@ __device__ __forceinline__ void img_att_wsum_body(const float* __restrict__ pre,
     *reinterpret_cast<float4*>(u1 + (long)n * H + h) = t;
   }
 }
-__global__ void __launch_bounds__(256)
-img_att_wsum_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ mask1,
-                    const float* __restrict__ p, const float* __restrict__ u0, float* __restrict__ u1, int S2,
-                    int R, int H, float scale) {
-  img_att_wsum_body<false>(pre, mask1, p, u0, u1, S2, S2, R, H, scale);
-}
-__global__ void __launch_bounds__(256)
-img_att_wsum_regions_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ mask1, const float* __restrict__ p,
-                            const float* __restrict__ u0, float* __restrict__ u1, const int32_t* __restrict__ cnt, int S2, int R, int H,
-                            float scale) {
-  img_att_wsum_body<true>(pre, mask1, p, u0, u1, img_live_regions<true>(cnt, blockIdx.x, R, S2), S2, R, H, scale);
-}
 
 // ---------------------------------------------------------------------------
 // Backward of the attention head + of the tanh/dropout epilogue of img_common.  Per QA round n:
@@ -483,13 +442,14 @@ img_att_wsum_regions_kernel(const float* __restrict__ pre, const uint8_t* __rest
 //   dz[n,s,k] = dscore[s]*wa[k]*scale2*mask2*(1 - tanh^2)   (written over iqc in place)
 //   dqc[n,k] = sum_s dz[n,s,k]                                               (img_att_dz_kernel)
 // ---------------------------------------------------------------------------
-template <bool MASKED>
-__device__ __forceinline__ void img_att_dscore_body(const float* __restrict__ pre, const uint8_t* __restrict__ mask1, const float* __restrict__ p,
-                                                    const float* __restrict__ datt, float* __restrict__ dscore, float* __restrict__ dba, int L,
-                                                    int S2, int R, int H, float scale) {
+__global__ void __launch_bounds__(IMG_ATT_WAVES * 64)
+img_att_dscore_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ mask1, const float* __restrict__ p,
+                      const float* __restrict__ datt, float* __restrict__ dscore, float* __restrict__ dba,
+                      const int32_t* __restrict__ cnt, int S2, int R, int H, float scale) {
   extern __shared__ float sc[];  // dp [S2]
   __shared__ float red[IMG_ATT_WAVES];
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int L = img_live_regions(cnt, n, R, S2);
   const float* pr = pre + (long)(n / R) * S2 * H;
   const uint8_t* m1 = mask1 ? mask1 + (long)n * S2 * H : nullptr;
   const float* da = datt + (long)n * H;
@@ -497,13 +457,7 @@ __device__ __forceinline__ void img_att_dscore_body(const float* __restrict__ pr
     float a = 0.f;
     for (int h = lane * 4; h < H; h += 256) {
       float4 v = *reinterpret_cast<const float4*>(pr + (long)s * H + h);
-      if (m1) {
-        const uint32_t m = *reinterpret_cast<const uint32_t*>(m1 + (long)s * H + h);
-        v.x = (m & 0xffu) ? v.x * scale : 0.f;
-        v.y = (m & 0xff00u) ? v.y * scale : 0.f;
-        v.z = (m & 0xff0000u) ? v.z * scale : 0.f;
-        v.w = (m & 0xff000000u) ? v.w * scale : 0.f;
-      }
+      if (m1) v = vd_mask4(v, *reinterpret_cast<const uint32_t*>(m1 + (long)s * H + h), scale);
       const float4 d = *reinterpret_cast<const float4*>(da + h);
       a += d.x * v.x + d.y * v.y + d.z * v.z + d.w * v.w;
     }
@@ -520,33 +474,21 @@ __device__ __forceinline__ void img_att_dscore_body(const float* __restrict__ pr
     dscore[(long)n * S2 + s] = ds;
     dsum += ds;
   }
-  if (MASKED)
-    for (int s = L + tid; s < S2; s += IMG_ATT_WAVES * 64) dscore[(long)n * S2 + s] = 0.f;
+  for (int s = L + tid; s < S2; s += IMG_ATT_WAVES * 64) dscore[(long)n * S2 + s] = 0.f;
   dsum = block_reduce(dsum, red, wave, lane, false);
   if (tid == 0) unsafeAtomicAdd(dba, dsum);
 }
-__global__ void __launch_bounds__(IMG_ATT_WAVES * 64)
-img_att_dscore_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ mask1,
-                      const float* __restrict__ p, const float* __restrict__ datt, float* __restrict__ dscore,
-                      float* __restrict__ dba, int S2, int R, int H, float scale) {
-  img_att_dscore_body<false>(pre, mask1, p, datt, dscore, dba, S2, S2, R, H, scale);
-}
-__global__ void __launch_bounds__(IMG_ATT_WAVES * 64)
-img_att_dscore_regions_kernel(const float* __restrict__ pre, const uint8_t* __restrict__ mask1, const float* __restrict__ p,
-                              const float* __restrict__ datt, float* __restrict__ dscore, float* __restrict__ dba,
-                              const int32_t* __restrict__ cnt, int S2, int R, int H, float scale) {
-  img_att_dscore_body<true>(pre, mask1, p, datt, dscore, dba, img_live_regions<true>(cnt, blockIdx.x, R, S2), S2, R, H, scale);
-}
 
-template <bool MASKED>
-__device__ __forceinline__ void img_att_dz_body(float* __restrict__ iqc, const float* __restrict__ wa, const uint8_t* __restrict__ mask2,
-                                                const float* __restrict__ dscore, float* __restrict__ dwa, float* __restrict__ dqc, int L, int S2,
-                                                int Kc, float scale) {
+__global__ void __launch_bounds__(256)
+img_att_dz_kernel(float* __restrict__ iqc, const float* __restrict__ wa, const uint8_t* __restrict__ mask2,
+                  const float* __restrict__ dscore, float* __restrict__ dwa, float* __restrict__ dqc, const int32_t* __restrict__ cnt,
+                  int S2, int R, int Kc, float scale) {
   extern __shared__ float sh[];  // dscore [S2] | partial sums [2][8][128]
   float* dsv = sh;
   float* part = sh + ((S2 + 3) & ~3);
   const int n = blockIdx.x, tid = threadIdx.x, g = tid >> 5, l = tid & 31;
   const int k = blockIdx.y * 128 + l * 4;
+  const int L = img_live_regions(cnt, n, R, S2);
   for (int s = tid; s < L; s += 256) dsv[s] = dscore[(long)n * S2 + s];
   __syncthreads();
   float4 aw = make_float4(0.f, 0.f, 0.f, 0.f), aq = aw;
@@ -563,16 +505,15 @@ __device__ __forceinline__ void img_att_dz_body(float* __restrict__ iqc, const f
       const uint32_t m = m2 ? *reinterpret_cast<const uint32_t*>(m2 + (long)s * Kc) : 0xffffffffu;
       const float ds = dsv[s];
       aw.x += ds * y.x; aw.y += ds * y.y; aw.z += ds * y.z; aw.w += ds * y.w;
-      float4 dz;
-      { const float t = y.x * inv_scale; dz.x = (m & 0xffu) ? ds * w.x * (1.f - t * t) : 0.f; }
-      { const float t = y.y * inv_scale; dz.y = (m & 0xff00u) ? ds * w.y * (1.f - t * t) : 0.f; }
-      { const float t = y.z * inv_scale; dz.z = (m & 0xff0000u) ? ds * w.z * (1.f - t * t) : 0.f; }
-      { const float t = y.w * inv_scale; dz.w = (m & 0xff000000u) ? ds * w.w * (1.f - t * t) : 0.f; }
+      const float4 t = make_float4(y.x * inv_scale, y.y * inv_scale, y.z * inv_scale, y.w * inv_scale);
+      // the mask gates the gradient (its scale is in w already): a dropped element gets 0
+      const float4 dz = vd_mask4(make_float4(ds * w.x * (1.f - t.x * t.x), ds * w.y * (1.f - t.y * t.y), ds * w.z * (1.f - t.z * t.z),
+                                             ds * w.w * (1.f - t.w * t.w)), m, 1.f);
       *reinterpret_cast<float4*>(iq + (long)s * Kc) = dz;
       aq.x += dz.x; aq.y += dz.y; aq.z += dz.z; aq.w += dz.w;
     }
-    if (MASKED)   // the hidden rows of dz: written, never read (IR4)
-      for (int s = L + g; s < S2; s += 8) *reinterpret_cast<float4*>(iq + (long)s * Kc) = make_float4(0.f, 0.f, 0.f, 0.f);
+    // the hidden rows of dz: written, never read (IR4)
+    for (int s = L + g; s < S2; s += 8) *reinterpret_cast<float4*>(iq + (long)s * Kc) = make_float4(0.f, 0.f, 0.f, 0.f);
   }
   *reinterpret_cast<float4*>(part + g * 128 + l * 4) = aw;
   *reinterpret_cast<float4*>(part + 1024 + g * 128 + l * 4) = aq;
@@ -593,21 +534,42 @@ __device__ __forceinline__ void img_att_dz_body(float* __restrict__ iqc, const f
     unsafeAtomicAdd(dwa + k + 3, tw.w);
   }
 }
-__global__ void __launch_bounds__(256)
-img_att_dz_kernel(float* __restrict__ iqc, const float* __restrict__ wa, const uint8_t* __restrict__ mask2,
-                  const float* __restrict__ dscore, float* __restrict__ dwa, float* __restrict__ dqc, int S2,
-                  int Kc, float scale) {
-  img_att_dz_body<false>(iqc, wa, mask2, dscore, dwa, dqc, S2, S2, Kc, scale);
-}
-__global__ void __launch_bounds__(256)
-img_att_dz_regions_kernel(float* __restrict__ iqc, const float* __restrict__ wa, const uint8_t* __restrict__ mask2,
-                          const float* __restrict__ dscore, float* __restrict__ dwa, float* __restrict__ dqc, const int32_t* __restrict__ cnt,
-                          int S2, int R, int Kc, float scale) {
-  img_att_dz_body<true>(iqc, wa, mask2, dscore, dwa, dqc, img_live_regions<true>(cnt, blockIdx.x, R, S2), S2, Kc, scale);
-}
 
 using CfgBigDB = GemmCfg<4, 1, 4, 32>;
 using CfgBig = GemmCfg<4, 1, 4, 16, 0, 3>;
+
+// The attention head over the live regions of every image (IR1 - IR6): cnt [ceil(N / R)] int32 on the device, or null = every region is live,
+// which is the C-ABI entry point vd_img_att_forward / vd_img_att_backward (it calls these, and a refusal names it).  The caller holds every
+// count to 1 .. S2 (runtime.hip validates an attachment on the host).
+int vd_img_att_forward_p(const float* iqc, const float* wa, const float* ba, const float* pre, const uint8_t* mask1, const float* u0, float* p,
+                         float* u1, int N, int R, int S2, int H, int Kc, float scale, const int32_t* cnt, hipStream_t stream) {
+  VD_CHECK_ARG(iqc && wa && ba && pre && u0 && p && u1 && N >= 0 && R >= 1 && S2 >= 1 && Kc % 4 == 0 && H % 4 == 0,
+               "vd_img_att_forward%s: bad args", cnt ? "_p" : "");
+  if (N == 0) return VD_OK;
+  hipLaunchKernelGGL(img_att_score_kernel, dim3(N), dim3(IMG_ATT_WAVES * 64), S2 * sizeof(float), stream, iqc, wa, ba, p, cnt, S2, R, Kc);
+  VD_LAUNCH_CHECK();
+  const size_t lds = (((S2 + 3) & ~3) + 8 * 128) * sizeof(float);
+  hipLaunchKernelGGL(img_att_wsum_kernel, dim3(N, vd_cdiv(H, 128)), dim3(256), lds, stream, pre, mask1, p, u0, u1, cnt, S2, R, H, scale);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
+
+// iqc is overwritten by dz.  dwa/dba are accumulated, dqc is written.  work: [N x S2] floats (dscore).
+int vd_img_att_backward_p(float* iqc_dz, const float* wa, const float* pre, const uint8_t* mask1, const uint8_t* mask2, const float* p,
+                          const float* datt, float* dwa, float* dba, float* dqc, float* work, int N, int R, int S2, int H, int Kc, float scale,
+                          const int32_t* cnt, hipStream_t stream) {
+  VD_CHECK_ARG(iqc_dz && wa && pre && p && datt && dwa && dba && dqc && work && N >= 0 && R >= 1 && S2 >= 1 && Kc % 4 == 0 && H % 4 == 0,
+               "vd_img_att_backward%s: bad args", cnt ? "_p" : "");
+  if (N == 0) return VD_OK;
+  hipLaunchKernelGGL(img_att_dscore_kernel, dim3(N), dim3(IMG_ATT_WAVES * 64), S2 * sizeof(float), stream, pre, mask1, p, datt, work, dba,
+                     cnt, S2, R, H, scale);
+  VD_LAUNCH_CHECK();
+  const size_t lds = (((S2 + 3) & ~3) + 2 * 8 * 128) * sizeof(float);
+  hipLaunchKernelGGL(img_att_dz_kernel, dim3(N, vd_cdiv(Kc, 128)), dim3(256), lds, stream, iqc_dz, wa, mask2, work, dwa, dqc, cnt, S2, R, Kc,
+                     scale);
+  VD_LAUNCH_CHECK();
+  return VD_OK;
+}
 
 extern "C" {
 
@@ -694,37 +656,13 @@ int vd_img_common_forward(const float* pre, const uint8_t* mask1, const float* W
 int vd_img_att_forward(const float* iqc, const float* wa, const float* ba, const float* pre,
                        const uint8_t* mask1, const float* u0, float* p, float* u1, int N, int R, int S2, int H,
                        int Kc, float scale, void* stream) {
-  VD_CHECK_ARG(iqc && wa && ba && pre && u0 && p && u1 && N >= 0 && Kc % 4 == 0 && H % 4 == 0,
-               "vd_img_att_forward: bad args");
-  if (N == 0) return VD_OK;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(img_att_score_kernel, dim3(N), dim3(IMG_ATT_WAVES * 64), S2 * sizeof(float), s, iqc, wa, ba,
-                     p, S2, Kc);
-  VD_LAUNCH_CHECK();
-  const size_t lds = (((S2 + 3) & ~3) + 8 * 128) * sizeof(float);
-  hipLaunchKernelGGL(img_att_wsum_kernel, dim3(N, vd_cdiv(H, 128)), dim3(256), lds, s, pre, mask1, p, u0, u1, S2,
-                     R, H, scale);
-  VD_LAUNCH_CHECK();
-  return VD_OK;
+  return vd_img_att_forward_p(iqc, wa, ba, pre, mask1, u0, p, u1, N, R, S2, H, Kc, scale, nullptr, (hipStream_t)stream);
 }
 
-// iqc is overwritten by dz.  dwa/dba are accumulated, dqc is written.  work: [N x S2] floats (dscore).
 int vd_img_att_backward(float* iqc_dz, const float* wa, const float* pre, const uint8_t* mask1,
                         const uint8_t* mask2, const float* p, const float* datt, float* dwa, float* dba,
                         float* dqc, float* work, int N, int R, int S2, int H, int Kc, float scale, void* stream) {
-  VD_CHECK_ARG(iqc_dz && wa && pre && p && datt && dwa && dba && dqc && work && N >= 0 && Kc % 4 == 0 &&
-                   H % 4 == 0,
-               "vd_img_att_backward: bad args");
-  if (N == 0) return VD_OK;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(img_att_dscore_kernel, dim3(N), dim3(IMG_ATT_WAVES * 64), S2 * sizeof(float), s, pre, mask1,
-                     p, datt, work, dba, S2, R, H, scale);
-  VD_LAUNCH_CHECK();
-  const size_t lds = (((S2 + 3) & ~3) + 2 * 8 * 128) * sizeof(float);
-  hipLaunchKernelGGL(img_att_dz_kernel, dim3(N, vd_cdiv(Kc, 128)), dim3(256), lds, s, iqc_dz, wa, mask2, work,
-                     dwa, dqc, S2, Kc, scale);
-  VD_LAUNCH_CHECK();
-  return VD_OK;
+  return vd_img_att_backward_p(iqc_dz, wa, pre, mask1, mask2, p, datt, dwa, dba, dqc, work, N, R, S2, H, Kc, scale, nullptr, (hipStream_t)stream);
 }
 
 // dpre[(b,s), :] += sum_{rounds} (dz[(n,s), :] * Wc + p[n,s]*datt[n, :]) * mask1*scale
@@ -757,38 +695,6 @@ int vd_img_common_wgrad(const float* dz, const float* pre, const uint8_t* mask1,
 
 }  // extern "C"
 
-// The attention head over the live regions of every image (IR1 - IR6): cnt [ceil(N / R)] int32 on the device, or null = the C-ABI entry point,
-// argument for argument.  The caller holds every count to 1 .. S2 (runtime.hip validates an attachment on the host).
-int vd_img_att_forward_p(const float* iqc, const float* wa, const float* ba, const float* pre, const uint8_t* mask1, const float* u0, float* p,
-                         float* u1, int N, int R, int S2, int H, int Kc, float scale, const int32_t* cnt, hipStream_t stream) {
-  if (!cnt) return vd_img_att_forward(iqc, wa, ba, pre, mask1, u0, p, u1, N, R, S2, H, Kc, scale, stream);
-  VD_CHECK_ARG(iqc && wa && ba && pre && u0 && p && u1 && N >= 0 && R >= 1 && S2 >= 1 && Kc % 4 == 0 && H % 4 == 0, "vd_img_att_forward_p: bad args");
-  if (N == 0) return VD_OK;
-  hipLaunchKernelGGL(img_att_score_regions_kernel, dim3(N), dim3(IMG_ATT_WAVES * 64), S2 * sizeof(float), stream, iqc, wa, ba, p, cnt, S2, R, Kc);
-  VD_LAUNCH_CHECK();
-  const size_t lds = (((S2 + 3) & ~3) + 8 * 128) * sizeof(float);
-  hipLaunchKernelGGL(img_att_wsum_regions_kernel, dim3(N, vd_cdiv(H, 128)), dim3(256), lds, stream, pre, mask1, p, u0, u1, cnt, S2, R, H, scale);
-  VD_LAUNCH_CHECK();
-  return VD_OK;
-}
-
-int vd_img_att_backward_p(float* iqc_dz, const float* wa, const float* pre, const uint8_t* mask1, const uint8_t* mask2, const float* p,
-                          const float* datt, float* dwa, float* dba, float* dqc, float* work, int N, int R, int S2, int H, int Kc, float scale,
-                          const int32_t* cnt, hipStream_t stream) {
-  if (!cnt) return vd_img_att_backward(iqc_dz, wa, pre, mask1, mask2, p, datt, dwa, dba, dqc, work, N, R, S2, H, Kc, scale, stream);
-  VD_CHECK_ARG(iqc_dz && wa && pre && p && datt && dwa && dba && dqc && work && N >= 0 && R >= 1 && S2 >= 1 && Kc % 4 == 0 && H % 4 == 0,
-               "vd_img_att_backward_p: bad args");
-  if (N == 0) return VD_OK;
-  hipLaunchKernelGGL(img_att_dscore_regions_kernel, dim3(N), dim3(IMG_ATT_WAVES * 64), S2 * sizeof(float), stream, pre, mask1, p, datt, work, dba,
-                     cnt, S2, R, H, scale);
-  VD_LAUNCH_CHECK();
-  const size_t lds = (((S2 + 3) & ~3) + 2 * 8 * 128) * sizeof(float);
-  hipLaunchKernelGGL(img_att_dz_regions_kernel, dim3(N, vd_cdiv(Kc, 128)), dim3(256), lds, stream, iqc_dz, wa, mask2, work, dwa, dqc, cnt, S2, R, Kc,
-                     scale);
-  VD_LAUNCH_CHECK();
-  return VD_OK;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // The three dense [N*S2 x 512 x 512] products of the image attention on the EXACT SPLIT (split_core.h), for a split9 pass of the model-level
 // runtime (every fp32 GEMM with K >= 512 that shares the chip with the option recurrence costs 9/16 of the matrix-pipe
@@ -806,13 +712,7 @@ __global__ void __launch_bounds__(256) img_drop_gather_kernel(const float* __res
   const int k4 = (int)(i - row * H4);
   const long n = row / S2, sidx = row - n * S2;
   float4 v = reinterpret_cast<const float4*>(pre)[((n / R) * S2 + sidx) * H4 + k4];
-  if (mask) {
-    const uint32_t mk = reinterpret_cast<const uint32_t*>(mask)[i];
-    v.x = (mk & 0xff) ? v.x * scale : 0.f;
-    v.y = (mk & 0xff00) ? v.y * scale : 0.f;
-    v.z = (mk & 0xff0000) ? v.z * scale : 0.f;
-    v.w = (mk & 0xff000000u) ? v.w * scale : 0.f;
-  }
+  if (mask) v = vd_mask4(v, reinterpret_cast<const uint32_t*>(mask)[i], scale);
   reinterpret_cast<float4*>(out)[i] = v;
 }
 __global__ void __launch_bounds__(256) transpose32_kernel(const float* __restrict__ src, float* __restrict__ dst, int rows, int cols) {
@@ -884,8 +784,8 @@ int vd_img_common_wgrad_p(const float* dz, const float* pre, const uint8_t* mask
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // One round of a rollout (VD_ROLLOUT_ENCODER = round; rt_encoders.h forward_round).  After pass r - 1 only history row r of every dialog
 // has changed, so the encoder output of round r needs row (d, r) of each attention alone.  The two kernels below compute that row with
-// the arithmetic of the full kernels above -- the same per-lane product order and wave reduction of a score, the same max / exp / sum /
-// scale of the softmax over j in ascending order, the same j-ascending weighted sum -- so for identical inputs row (d, r) equals the
+// the arithmetic of the full kernels above -- the same per-lane product order and wave reduction of a score, the softmax over j of the
+// same row_softmax, the same j-ascending weighted sum -- so for identical inputs row (d, r) equals the
 // full kernel's bit for bit: what the full kernel adds for the masked j > r are exact zeros (exp(-9999999 - max) and exp(-inf)
 // underflow to +0).  One workgroup per dialog, B workgroups: the pass is launch-bound, not throughput-bound.
 // ---------------------------------------------------------------------------------------------------------------------------------------
@@ -917,20 +817,9 @@ mn_att_round_kernel(const float* __restrict__ Q, long q_ld, const float* __restr
   }
   __syncthreads();
   if (tid == 0) {
-    float mx = -INFINITY;
-    for (int j = 0; j < nf; ++j) mx = fmaxf(mx, S[j]);
-    float sum = 0.f;
-    for (int j = 0; j < nf; ++j) {
-      const float e = expf(S[j] - mx);
-      S[j] = e;
-      sum += e;
-    }
-    const float inv = 1.f / sum;
-    for (int j = 0; j < R; ++j) {
-      const float pv = j < nf ? S[j] * inv : 0.f;
-      if (j < nf) S[j] = pv;
-      if (P) P[(long)d * R + j] = pv;
-    }
+    row_softmax(S, nf, [&](int j) { return S[j]; });
+    if (P)
+      for (int j = 0; j < R; ++j) P[(long)d * R + j] = j < nf ? S[j] : 0.f;
   }
   __syncthreads();
   for (int k = tid; k < H; k += MN_ROUND_THREADS) {
@@ -949,25 +838,12 @@ hrea_att_round_kernel(const float* __restrict__ sq, const float* __restrict__ sh
   const float* h = Hm + (long)d * R * H;
   const int nf = r + 1;
   if (tid == 0) {
-    float mx = -INFINITY;
-    for (int j = 0; j < nf; ++j) {
-      float v = sq[d * R + r] + sh[d * R + j];
-      v = (v == 0.f) ? -INFINITY : v;
-      S[j] = v;
-      mx = fmaxf(mx, v);
-    }
-    float sum = 0.f;
-    for (int j = 0; j < nf; ++j) {
-      const float e = expf(S[j] - mx);
-      S[j] = e;
-      sum += e;
-    }
-    const float inv = 1.f / sum;
-    for (int j = 0; j < R; ++j) {
-      const float pv = j < nf ? S[j] * inv : 0.f;
-      if (j < nf) S[j] = pv;
-      if (P) P[(long)d * R + j] = pv;
-    }
+    row_softmax(S, nf, [&](int j) {
+      const float v = sq[d * R + r] + sh[d * R + j];
+      return (v == 0.f) ? -INFINITY : v;
+    });
+    if (P)
+      for (int j = 0; j < R; ++j) P[(long)d * R + j] = j < nf ? S[j] : 0.f;
   }
   __syncthreads();
   for (int k = tid; k < H; k += 256) {

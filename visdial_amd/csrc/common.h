@@ -197,6 +197,16 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Dropout on four consecutive elements: m holds their four mask bytes (byte 0 = v.x), a non-zero byte keeps the element times scale, a zero
+// byte gives +0 whatever the element holds (a select, not a product: NaN or Inf in a dropped element does not come through).
+__device__ __forceinline__ float4 vd_mask4(float4 v, uint32_t m, float scale) {
+  v.x = (m & 0xffu) ? v.x * scale : 0.f;
+  v.y = (m & 0xff00u) ? v.y * scale : 0.f;
+  v.z = (m & 0xff0000u) ? v.z * scale : 0.f;
+  v.w = (m & 0xff000000u) ? v.w * scale : 0.f;
+  return v;
+}
+
 // Log-sum-exp of one row of V logits for a 256-thread block: 256 strided threads take the max, then the sum of exp(x - max),
 // each reduced by wave_max / wave_sum with the four wave partials combined in a fixed order; `red` is the block's 8-float
 // shared buffer.  The one row arithmetic of vd_logsoftmax_nll, vd_log_softmax_rows, vd_beam_topk and vd_sample_draw: the

@@ -72,13 +72,7 @@ __global__ void embed_gather_kernel(const float* __restrict__ emb, const int* __
   const long r = idx / e4;
   const int q = (int)(idx - r * e4);
   float4 v = *reinterpret_cast<const float4*>(emb + (long)tok[r] * E + q * 4);
-  if (mask) {
-    const uint32_t m = *reinterpret_cast<const uint32_t*>(mask + r * E + q * 4);
-    v.x = (m & 0xff) ? v.x * scale : 0.f;
-    v.y = (m & 0xff00) ? v.y * scale : 0.f;
-    v.z = (m & 0xff0000) ? v.z * scale : 0.f;
-    v.w = (m & 0xff000000u) ? v.w * scale : 0.f;
-  }
+  if (mask) v = vd_mask4(v, *reinterpret_cast<const uint32_t*>(mask + r * E + q * 4), scale);
   *reinterpret_cast<float4*>(out + r * E + q * 4) = v;
 }
 
